@@ -16,6 +16,12 @@ exactly like Utilities::MPI::create_evenly_distributed_partitioning (LOD.cc:116-
 block per rank, no data-path collective inside the timed basis build.  After the timed
 region every rank's (phi,psi) slab is all-gathered over RCCL (north_star's exchange step);
 that time is reported separately as `allgather_ms` (SURVEY 8d excludes it from the metric).
+
+A plain run sets up, warms up, times --steps steps and prints the headline line.  --full adds
+everything outside the headline: roofline and per-kernel times, the two-stream pipelined pass,
+the consumers of (phi, psi), the CPU baseline and, for N > 1, the all-gather and C-ABI exchange
+legs.  --dump-outputs DIR writes the (phi, psi) slabs of the last timed step as DIR/basis.npy
+and DIR/premult.npy (float64, one row of plan stride per patch of rank 0).
 """
 import argparse
 import json
@@ -42,6 +48,23 @@ CONFIGS = {
 }
 PEAK_FP64_TFLOPS = 78.6   # MI355X dense fp64 (vector = matrix): half the 157.3 TF fp32 vector peak
 PEAK_HBM_GBPS = 8000.0    # /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_BYTES = 60 * 1000 * 1000   # --dump-outputs: all arrays together stay below 64 MB
+
+
+def dump_outputs(out_dir, basis, premult, n_patches, stride):
+    """(phi, psi) of the rank's patches as [patch, stride] float64 arrays.  A larger output keeps a
+    fixed, seeded sample of patch rows (the same rows in every run of the same arguments)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows = None
+    per_row = 2 * 8 * stride
+    if n_patches * per_row > DUMP_BYTES:
+        k = max(1, DUMP_BYTES // per_row)
+        rows = np.sort(np.random.default_rng(SEED).choice(n_patches, size=k, replace=False))
+    for name, slab in (("basis", basis), ("premult", premult)):
+        a = slab[:n_patches * stride].view(n_patches, stride)
+        if rows is not None:
+            a = a[rows.tolist()]
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy().astype(np.float64, copy=False))
 
 
 def canonical_counts(slod, gids):
@@ -164,13 +187,21 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pipeline", action="store_true", help="skip the two-stream measurement")
-    ap.add_argument("--no-lod-system", action="store_true", help="skip the timing of the consumers of (phi, psi)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies outside the headline: roofline / per-kernel times, two-stream "
+                         "pipeline, consumers of (phi, psi), CPU baseline, N > 1 exchange legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write (phi, psi) of the last timed step to DIR/basis.npy and DIR/premult.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-pipeline", action="store_true", help="with --full: skip the two-stream measurement")
+    ap.add_argument("--no-lod-system", action="store_true",
+                    help="with --full: skip the timing of the consumers of (phi, psi)")
     ap.add_argument("--dist", default="D1e4", choices=["D100", "D1e4"])
     ap.add_argument("--config", default="C2", choices=sorted(CONFIGS),
                     help="BASELINE.json configuration (C2 = the headline metric's; C3, C4: extra lines)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     CFG, scaling, cfg_label = CONFIGS[args.config]
 
     import torch
@@ -229,7 +260,8 @@ def main():
     torch.cuda.synchronize()
     plan.status()
 
-    plan.profile(args.steps)          # HIP events around every launch of the timed region
+    if args.full:
+        plan.profile(args.steps)      # one HIP event slot per launch of the timed region
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -237,14 +269,21 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     plan.status()
-    # mean per-kernel device time over the timed region (events on the launch stream)
-    ks = np.array(plan.kernel_ms())
+    if world > 1:                     # the slowest rank sets the step time
+        tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        elapsed = float(tmax[0])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, basis, premult, n_local, plan.stride)
+    if args.full:
+        # mean per-kernel device time over the timed region (events on the launch stream)
+        ks = np.array(plan.kernel_ms())
 
     # outside the metric: the same K steps double-buffered over two plans / two HIP streams.  The
     # passes are independent, so the next pass fills the CUs that the last slow patches (SVD
     # fallback) of the previous one leave idle; reported next to the serial headline number.
     pipelined = None
-    if world == 1 and not args.no_pipeline:
+    if args.full and world == 1 and not args.no_pipeline:
         ref_b, ref_q = basis.clone(), premult.clone()
         try:
             plan.set_overlap(2)           # library-level: second workspace + two internal streams
@@ -270,12 +309,12 @@ def main():
     # outside the metric: the consumers of (phi, psi) at this configuration's scale:
     # A_LOD = C^T (A C), C^T f, coarse solve, reconstruction, fine FEM reference solve
     lod_system = None
-    if world == 1 and not args.no_lod_system and n_prob == 1:
+    if args.full and world == 1 and not args.no_lod_system and n_prob == 1:
         lod_system = lod_system_leg(slod, torch, dev, basis, premult, plan.stride)
 
     # the exchange step (outside the metric): RCCL all-gather of the (phi,psi) slabs
     allgather_ms = None
-    if world > 1:
+    if args.full and world > 1:
         for _ in range(2):
             gb = sd.all_gather_slabs(basis, world)
             gp = sd.all_gather_slabs(premult, world)
@@ -288,9 +327,9 @@ def main():
         # every rank's block must land where a single-GPU run would put it
         mine = gb[rank * basis.numel():(rank + 1) * basis.numel()]
         assert torch.equal(mine, basis)
-        tmax = torch.tensor([elapsed, allgather_ms], dtype=torch.float64, device=dev)
+        tmax = torch.tensor([allgather_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        elapsed, allgather_ms = float(tmax[0]), float(tmax[1])
+        allgather_ms = float(tmax[0])
 
     # The same exchange through the C-ABI (what a C++ host calls: slod_comm_* over RCCL,
     # slod_plan_execute_allgather computes the rank's block in pieces and broadcasts every finished
@@ -300,7 +339,7 @@ def main():
     # driver's scaling run).
     abi_exchange = None
     headline = {}
-    if world > 1:
+    if args.full and world > 1:
         import threading
 
         def bail():
@@ -338,17 +377,7 @@ def main():
         return res
 
     if rank == 0:
-        flops, nbytes = canonical_counts(slod, gids)
         ms_step = elapsed / args.steps * 1e3
-        solve_s = ks[1] * 1e-3
-        achieved_tf = flops / solve_s / 1e12
-        traffic = None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tpath) and args.config == "C2":
-            try:
-                traffic = json.load(open(tpath)).get("k_solve_hbm_bytes_per_launch")
-            except Exception:
-                traffic = None
         out = {
             "metric": "SLOD patches/sec (basis built), 2D Poisson H=1/32 n_sub=8 oversampling 2" if args.config == "C2"
                       else "SLOD patches/sec (basis built), " + cfg_label,
@@ -363,6 +392,19 @@ def main():
                                                       "ensemble of %d realisations" % world if scaling == "weak"
                                                       else "%d patches sharded over %d ranks" % (total, world)),
                        "patches_per_gpu": n_local, "parallelism": "patch-sharded x%d" % world},
+        }
+    if rank == 0 and args.full:
+        flops, nbytes = canonical_counts(slod, gids)
+        solve_s = ks[1] * 1e-3
+        achieved_tf = flops / solve_s / 1e12
+        traffic = None
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tpath) and args.config == "C2":
+            try:
+                traffic = json.load(open(tpath)).get("k_solve_hbm_bytes_per_launch")
+            except Exception:
+                traffic = None
+        out.update({
             # the kernel's roof is the fp64 rate (on MI355X the vector and the matrix pipe have the
             # same 78.6 TFLOP/s): "mfma" names that peak; what actually limits the kernel today is
             # the instruction issue / dependent-chain latency of its Gauss-Jordan waves
@@ -379,11 +421,11 @@ def main():
             "allgather_ms": allgather_ms,
             "pipelined": pipelined,
             "lod_system": lod_system,
-        }
+        })
         if not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(CFG, fields[probs[0]], NP, every={"C2": 1, "C3": 256, "C4": 8}[args.config])
         headline.update(out)
-    if world > 1:
+    if args.full and world > 1:
         dist.barrier()            # rank 0 comes out of its CPU-baseline leg here
         watchdog.start()
         try:
@@ -392,12 +434,12 @@ def main():
             abi_exchange = {"error": "%s: %s" % (type(e).__name__, e)}
         watchdog.cancel()
     if rank == 0:
-        out["abi_exchange"] = abi_exchange
+        if args.full:
+            out["abi_exchange"] = abi_exchange
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-
 
 if __name__ == "__main__":
     main()

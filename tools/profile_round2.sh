@@ -7,10 +7,10 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 B="python3 $R/bench.py"
-timeout -k 10 300 $B --steps 200 --warmup 20 > $O/${tag}_bench_C2.log 2>&1 || exit 1
-timeout -k 10 300 $B --config C4 --steps 20 --warmup 3 > $O/${tag}_bench_C4.log 2>&1 || exit 1
-timeout -k 10 600 $B --config C3 --steps 3 --warmup 1 > $O/${tag}_bench_C3.log 2>&1 || exit 1
-SLOD_SOLVE=mf timeout -k 10 300 $B --steps 100 --warmup 10 --no-cpu-baseline > $O/${tag}_bench_C2_mf.log 2>&1 || exit 1
+timeout -k 10 300 $B --full --steps 200 --warmup 20 > $O/${tag}_bench_C2.log 2>&1 || exit 1
+timeout -k 10 300 $B --full --config C4 --steps 20 --warmup 3 > $O/${tag}_bench_C4.log 2>&1 || exit 1
+timeout -k 10 600 $B --full --config C3 --steps 3 --warmup 1 > $O/${tag}_bench_C3.log 2>&1 || exit 1
+SLOD_SOLVE=mf timeout -k 10 300 $B --full --steps 100 --warmup 10 --no-cpu-baseline > $O/${tag}_bench_C2_mf.log 2>&1 || exit 1
 echo "bench lines done"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}_prof_C2 -- $B --steps 50 --warmup 5 --no-cpu-baseline --no-pipeline > $O/${tag}_prof_C2.log 2>&1 || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}_prof_C4 -- $B --config C4 --steps 10 --warmup 2 --no-cpu-baseline --no-pipeline > $O/${tag}_prof_C4.log 2>&1 || exit 1

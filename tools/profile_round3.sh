@@ -6,10 +6,10 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 B="python3 $R/bench.py"
-timeout -k 10 300 $B --steps 200 --warmup 20 > $O/${tag}_bench_C2.log 2>&1 || exit 1
-timeout -k 10 300 $B > $O/${tag}_bench_C2_default.log 2>&1 || exit 1
-timeout -k 10 300 $B --config C4 --steps 20 --warmup 3 --no-lod-system > $O/${tag}_bench_C4.log 2>&1 || exit 1
-timeout -k 10 600 $B --config C3 --steps 3 --warmup 1 --no-lod-system > $O/${tag}_bench_C3.log 2>&1 || exit 1
+timeout -k 10 300 $B --full --steps 200 --warmup 20 > $O/${tag}_bench_C2.log 2>&1 || exit 1
+timeout -k 10 300 $B --full > $O/${tag}_bench_C2_default.log 2>&1 || exit 1
+timeout -k 10 300 $B --full --config C4 --steps 20 --warmup 3 --no-lod-system > $O/${tag}_bench_C4.log 2>&1 || exit 1
+timeout -k 10 600 $B --full --config C3 --steps 3 --warmup 1 --no-lod-system > $O/${tag}_bench_C3.log 2>&1 || exit 1
 echo "bench lines done"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/${tag}_prof_C2 -- $B --steps 50 --warmup 5 --no-cpu-baseline --no-pipeline --no-lod-system > $O/${tag}_prof_C2.log 2>&1 || exit 1
 cp $(find /tmp/${tag}_prof_C2 -name "*kernel_stats.csv" | head -1) $O/${tag}_kernel_stats_C2.csv
