@@ -38,7 +38,8 @@ struct slod_plan
   int                        nb_buf = 0; // rows of k_select's boundary-trace buffer
   size_t                     stride = 0, out_size = 0;
   size_t                     chunk = 0;
-  double                    *ws_st = nullptr, *ws_v = nullptr, *ws_x = nullptr, *ws_m = nullptr;
+  double                    *ws_st = nullptr, *ws_v = nullptr, *ws_x = nullptr;
+  double                    *ws_m = nullptr; // [chunk][nc_max^2] diag stamps / k_solve_ws's M, then [chunk][nc_max^2 + 1] k_solve_tw's M + flag
   double                    *ws_z = nullptr; // k_solve_tw: Z of the forward sweep (active column prefix per line)
   double                    *ws_x_alloc = nullptr; // ws_x sits `guard` doubles inside this allocation
   size_t                     guard = 0;
@@ -214,7 +215,9 @@ namespace
     a.x_stride  = p->x_stride;
     a.nc_max    = p->nc_max;
     a.ms        = p->ws_m;
+    a.mt        = p->ws_m + p->chunk * (size_t)p->nc_max * p->nc_max; // behind the stamps: [chunk][nc_max^2 + 1]
     a.m_fused   = 0; // set by slod_launch_solve when the wave-specialised kernel runs
+    a.m_tw      = 0;
     a.nb_buf    = p->nb_buf;
     a.nf_max    = p->nf_max;
     a.fuse_select = 0; // set by slod_launch_solve
@@ -230,6 +233,7 @@ namespace
         a.xs     = p->alt.ws_x;
         a.zs     = p->alt.ws_z ? p->alt.ws_z : p->alt.ws_x;
         a.ms     = p->alt.ws_m;
+        a.mt     = p->alt.ws_m + p->chunk * (size_t)p->nc_max * p->nc_max;
         a.status = p->alt.d_status;
       }
     return a;
@@ -569,7 +573,8 @@ int slod_plan_create(slod_handle *h, const uint32_t *gids, size_t n, const uint6
   p->v_stride  = p->choice.v_patch_elems ? p->choice.v_patch_elems : (size_t)p->L_max * p->choice.v_line_elems;
   p->x_stride  = (size_t)p->L_max * p->m_max * p->nc_max;
   const bool   own_z = p->choice.kind == SLOD_K_TW;
-  const size_t per_patch = (p->st_stride + p->v_stride + (own_z ? 2 : 1) * p->x_stride) * sizeof(double);
+  const size_t per_patch =
+    (p->st_stride + p->v_stride + (own_z ? 2 : 1) * p->x_stride + 2 * (size_t)p->nc_max * p->nc_max + 1) * sizeof(double);
   // Workspace budget: 24 GB, or 60 % of what is free on the device if that is more (an MI355X has
   // 288 GB: big plans then run in few, long launches -- C3 in 3 chunks instead of 14, less idle
   // tail per chunk), never more than 80 % of what is free right now (the caller's outputs and
@@ -612,7 +617,7 @@ int slod_plan_create(slod_handle *h, const uint32_t *gids, size_t n, const uint6
       w      = w && hipMalloc((void **)&p->ws_x_alloc, (p->chunk * p->x_stride + 2 * p->guard) * sizeof(double)) == hipSuccess;
       if (own_z)
         w = w && hipMalloc((void **)&p->ws_z, (p->chunk * p->x_stride + p->guard) * sizeof(double)) == hipSuccess;
-      w = w && hipMalloc((void **)&p->ws_m, p->chunk * (size_t)p->nc_max * p->nc_max * sizeof(double)) == hipSuccess;
+      w = w && hipMalloc((void **)&p->ws_m, p->chunk * (2 * (size_t)p->nc_max * p->nc_max + 1) * sizeof(double)) == hipSuccess;
       if (w || !ok || p->chunk == 1)
         {
           ok = w;
@@ -769,7 +774,7 @@ int slod_plan_set_overlap(slod_plan *p, int depth)
       ok = ok && hipMalloc((void **)&p->alt.ws_x_alloc, (p->chunk * p->x_stride + 2 * p->guard) * sizeof(double)) == hipSuccess;
       if (own_z)
         ok = ok && hipMalloc((void **)&p->alt.ws_z, (p->chunk * p->x_stride + p->guard) * sizeof(double)) == hipSuccess;
-      ok = ok && hipMalloc((void **)&p->alt.ws_m, p->chunk * (size_t)p->nc_max * p->nc_max * sizeof(double)) == hipSuccess;
+      ok = ok && hipMalloc((void **)&p->alt.ws_m, p->chunk * (2 * (size_t)p->nc_max * p->nc_max + 1) * sizeof(double)) == hipSuccess;
       ok = ok && hipMalloc((void **)&p->alt.d_status, sizeof(int32_t)) == hipSuccess;
       ok = ok && hipMemset(p->alt.ws_st, 0, (p->chunk * p->st_stride + st_slack) * sizeof(double)) == hipSuccess;
       ok = ok && hipMemset(p->alt.ws_x_alloc, 0, (p->chunk * p->x_stride + 2 * p->guard) * sizeof(double)) == hipSuccess;

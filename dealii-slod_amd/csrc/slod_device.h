@@ -24,6 +24,8 @@ struct SlodPatchDesc
   uint64_t out_off;  // offset (doubles) of this patch in basis / premult
 };
 
+__host__ __device__ inline size_t slod_mt_stride(int nc_max) { return (size_t)nc_max * nc_max + 1; }
+
 enum : int32_t
 {
   SLOD_F_LOD        = 1 << 4,
@@ -78,6 +80,9 @@ struct SlodKernelArgs
   int32_t nc_max;
   double *ms;       // per patch M = P^T A^-1 P / H^2 accumulated by k_solve_ws (nc_max^2 doubles)
   int32_t m_fused;  // 1: k_select reads M from ms instead of recomputing it from X
+  double *mt;       // per patch M built inside the sweeps of k_solve_tw: nc_max^2 doubles, then a flag (1.0: M
+                    // is there, 0.0: the patch fell back); stride slod_mt_stride, not the stamps of ms
+  int32_t m_tw;     // 1: k_solve_tw builds M in its sweeps where the patch allows it
   int32_t nb_buf;   // rows of the selection stage's boundary-trace buffer
   int32_t nf_max;   // largest n_fine of the plan
   int32_t fuse_select; // set by slod_launch_solve: the solve kernel also ran the selection stage
@@ -102,7 +107,7 @@ enum SlodSolverKind : int32_t
 struct SlodTuning
 {
   int solver = 0;        // 0 = automatic, else a SlodSolverKind
-  int fuse_select = 1, fuse_assemble = 1, fuse_m = 0;
+  int fuse_select = 1, fuse_assemble = 1, fuse_m = -1; // fuse_m: -1 = the kernel's default
   int twisted = -1;      // coop kernel only: -1 = automatic
   int balance = 1;       // launch order balanced over the CUs (SLOD_BALANCE=0: the caller's order)
   int debug = 0;
@@ -111,7 +116,7 @@ struct SlodSolveChoice
 {
   int    kind = 0;
   size_t lds  = 0;
-  int    fuse_select = 0, fuse_assemble = 0, m_fused = 0, twisted = 0, debug = 0;
+  int    fuse_select = 0, fuse_assemble = 0, m_fused = 0, m_tw = 0, twisted = 0, debug = 0;
   int    v_line_pad = 0; // rows = columns of a V line as the kernel sees it
   size_t v_line_elems = 0; // doubles per stored V line (k_solve_tw: the 36 upper lane tiles only)
   int    nv = 0;            // k_solve_nd: cell size
@@ -136,7 +141,7 @@ hipError_t slod_launch_select(int S, const SlodKernelArgs &a, int n_patches, int
                               int nf_max, hipStream_t st);
 size_t     slod_solve_lds_bytes(int S, int m_max, int nc_max, int twisted);
 size_t     slod_solve_ws_lds_bytes(int S, int m_max, int nc_max);
-size_t     slod_solve_tw_lds_bytes(int S, int m_max, int nc_max);
+size_t     slod_solve_tw_lds_bytes(int S, int m_max, int nc_max, bool with_m = false);
 size_t     slod_solve_mf_lds_bytes(int S, int m_max, int nc_max);
 int        slod_solve_ws_tile(int m_max);
 int        slod_solve_mf_tiles(int S, int m_max); // 16 x 16 tiles per line side, 0 = does not fit

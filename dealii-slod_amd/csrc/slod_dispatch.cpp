@@ -3,6 +3,7 @@
 // when nothing fits), slod_plan_execute launches exactly that choice.
 #include "slod_device.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -10,7 +11,9 @@
 // per plan (slod_plan_create), never in the launch path.
 //   SLOD_SOLVE=mf|tw|ws|coop  force a kernel family       SLOD_FUSE_SELECT=0  selection as its own launch
 //   SLOD_FUSE_ASSEMBLE=0      stencil assembly as its own launch
-//   SLOD_FUSE_M=1 (ws only)   SLOD_TWISTED=0|1 (coop only) SLOD_DEBUG=1 print the choice
+//   SLOD_FUSE_M=0|1           M = P^T A^-1 P / H^2 built inside the sweeps instead of re-read from X:
+//                             tw default on (SLOD_FUSE_M=0 turns it off, for A/B timing), ws opt-in
+//   SLOD_TWISTED=0|1 (coop only) SLOD_DEBUG=1 print the choice
 //   SLOD_BALANCE=0            launch the patches in the caller's order (default: balanced over the CUs)
 SlodTuning slod_read_tuning()
 {
@@ -87,6 +90,20 @@ bool slod_choose_solver(int S, int n_sub, int m_max, int L_max, int nc_max, int 
       // the selection stage runs in the same launch (scalar problems) while four workgroups
       // still fit a CU
       c.fuse_select = (S == 1 && t.fuse_select && lds_sel <= 64 * 1024) ? 1 : 0;
+      // M from the sweeps (chain tiles of the forward sweep + the meeting line, k_solve_tw; the selection
+      // stage, fused or k_select, reads it where the patch allowed it) needs a
+      // scalar problem, at most two 16-column tiles and three row tiles per line; its two 16 x 16 LDS
+      // tiles must not cost a workgroup per CU (the registers allow at most four)
+      if (S == 1 && t.fuse_m != 0 && nc_max <= 32 && 8 * wt <= 48)
+        {
+          const size_t sel    = c.fuse_select ? lds_sel : 0;
+          const size_t with_m = std::max(slod_solve_tw_lds_bytes(S, m_max, nc_max, true), sel);
+          if (std::min<size_t>(4, lds_max / with_m) == std::min<size_t>(4, lds_max / std::max(c.lds, sel)))
+            {
+              c.m_tw = 1;
+              c.lds  = slod_solve_tw_lds_bytes(S, m_max, nc_max, true);
+            }
+        }
       if (c.fuse_select && lds_sel > c.lds)
         c.lds = lds_sel;
     }
@@ -99,7 +116,7 @@ bool slod_choose_solver(int S, int n_sub, int m_max, int L_max, int nc_max, int 
       c.v_line_elems = (size_t)c.v_line_pad * c.v_line_pad;
       // fusing M = sum_l R_l^T Z_l into the helper waves saves the selection stage's re-read of X
       // but costs a fourth barrier per line; measured neutral on C2, so opt-in (SLOD_FUSE_M=1)
-      c.m_fused = (t.fuse_m && nc_max * nc_max <= 192 * 4) ? 1 : 0;
+      c.m_fused = (t.fuse_m > 0 && nc_max * nc_max <= 192 * 4) ? 1 : 0;
     }
   else if (t.solver == 0 || t.solver == SLOD_K_COOP || !ws_fits)
     {
@@ -127,6 +144,7 @@ bool slod_choose_solver(int S, int n_sub, int m_max, int L_max, int nc_max, int 
 hipError_t slod_launch_solve(int S, const SlodSolveChoice &c, SlodKernelArgs &a, int n_patches, hipStream_t st)
 {
   a.m_fused       = c.m_fused;
+  a.m_tw          = c.m_tw;
   a.fuse_select   = c.fuse_select;
   a.fuse_assemble = c.fuse_assemble;
   a.debug         = c.debug;

@@ -7,7 +7,10 @@ namespace
   __global__ __launch_bounds__(256, S == 1 ? 1 : 2) void k_select(const SlodKernelArgs A, int nb_max, int nf_max)
   {
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    select_patch<S, true>(A, nb_max, nf_max, blockIdx.x, smem);
+    // M built by k_solve_tw's sweeps where the patch allowed it (flag behind the matrix)
+    const double *mt = A.m_tw ? A.mt + (size_t)blockIdx.x * slod_mt_stride(A.nc_max) : nullptr;
+    select_patch<S, true>(A, nb_max, nf_max, blockIdx.x, smem,
+                          (mt && mt[(size_t)A.nc_max * A.nc_max] != 0.0) ? mt : nullptr);
   }
 } // namespace
 

@@ -20,10 +20,11 @@ namespace
   // One 256-thread workgroup, patch `patch` of the launch; `smem` = the workgroup's dynamic LDS
   // (slod_select_lds_bytes).  Called by k_select and, fused, at the end of k_solve_tw.
   // OWN: the stage is a kernel of its own (k_select) and may spend registers on batched LDS loads;
-  // fused into a solve kernel it shares that kernel's tighter register budget
+  // fused into a solve kernel it shares that kernel's tighter register budget.
+  // mpre: M of this patch already built by the solve kernel ([nc][nc], scaled), nullptr: computed here
   template <int S, bool OWN = false>
   __device__ __forceinline__ void select_patch(const SlodKernelArgs &A, const int nb_max, const int nf_max,
-                                               const int patch, double *smem)
+                                               const int patch, double *smem, const double *mpre = nullptr)
   {
     const SlodPatchDesc d   = A.desc[patch];
     const int           tid = threadIdx.x;
@@ -114,15 +115,16 @@ namespace
     // ---- M = P^T X / H^dim (LOD.cc:548-551).  X rows come from the global workspace: the
     //      inner loop has no control dependence (clamped address, zero weight on the patch
     //      boundary where X = 0) so its n+1 loads are in flight together.
-    if (A.m_fused)
+    const bool m_given = mpre != nullptr || A.m_fused;
+    if (m_given)
       {
-        const double *mg = A.ms + (size_t)patch * A.nc_max * A.nc_max;
+        const double *mg = mpre ? mpre : A.ms + (size_t)patch * A.nc_max * A.nc_max;
         for (int idx = tid; idx < nc * nc; idx += 256)
           Ms[(idx / nc) * ldm + (idx % nc)] = mg[idx];
       }
     // M = P^T A^-1 P is symmetric and the sweep below treats it as such (column k is taken from
     // row k), so only the entries a <= b are computed (half the load batches) and mirrored
-    for (int idx = tid; idx < ((SLOD_DG(A, 64)) || A.m_fused ? 0 : nc * (nc + 1) / 2); idx += 256)
+    for (int idx = tid; idx < ((SLOD_DG(A, 64)) || m_given ? 0 : nc * (nc + 1) / 2); idx += 256)
       {
         // row a of the upper triangle holds nc - a entries: a = largest a with a (2 nc - a + 1) / 2 <= idx
         int a = (int)((2.0f * nc + 1.0f - sqrtf((2.0f * nc + 1.0f) * (2.0f * nc + 1.0f) - 8.0f * idx)) * 0.5f);

@@ -54,6 +54,26 @@ namespace
     int *perm = colk + 2 * A.nc_max + chain * 3 * A.nc_max, *inv = perm + A.nc_max, *act = inv + A.nc_max;
     int *operm = colk + 2 * A.nc_max + (1 - chain) * 3 * A.nc_max, *oinv = operm + A.nc_max, *oact = oinv + A.nc_max;
     (void)operm;
+    // M = P^T A^-1 P / H^2 from the sweeps (A.m_tw; the selection stage then skips its re-read of X).
+    // The elimination is a block LDL^T in the order 0..mid-1, L-1..mid+1, mid, so with F = P^T scaled,
+    // R_l the eliminated right-hand side of line l and Z_l = V_l R_l:
+    //   F^T A^-1 F = sum_{l != mid} R_l^T Z_l + R_mid^T X_mid.
+    // The chain terms are nonzero only on the chain's active columns (at most 16 here): one 16 x 16 tile
+    // per chain (mtile, chain order), accumulated by the helper wave right after its GEMM.  The meeting
+    // term is summed by the four waves in turn into mfull (P^T order) in chain 1's block, which is free
+    // from M1 to the backward sweep, and the last wave writes M to A.mt.
+    double *mtile = smem + 2 * chsz + 4 * A.nc_max; // [2][16][16] (behind colk/perm/inv/act: 8 nc_max ints)
+    double *mfull = smem + chsz;                    // [nc][nc], meeting line only
+    bool    mfuse = false;                          // (decided per patch after the band prologue)
+    // active columns of chain ch after its last step
+    auto nafin = [&](int ch) {
+      const int *ac = colk + 2 * A.nc_max + ch * 3 * A.nc_max + 2 * A.nc_max;
+      const int  nl = ch == 0 ? L / 2 : L - 1 - L / 2;
+      int        na = 0;
+      for (int k = 0; k < nc; ++k)
+        na += ac[k] <= nl - 1 ? 1 : 0;
+      return na;
+    };
 
     const double *st    = A.st + (size_t)blockIdx.x * A.st_stride;
     double       *vg    = A.vinv + (size_t)blockIdx.x * A.v_stride;
@@ -85,7 +105,11 @@ namespace
     // Row tile ti of X_mid = V_mid R_mid (R_mid in chain 0's LDS block), all columns: after the meeting
     // line is inverted every wave of the workgroup takes one row tile (one operand round trip instead
     // of one per tile in series on a single wave)
-    auto mid_tile = [&](int ti) __attribute__((always_inline)) {
+    // With mfuse (nc <= 32: one pass of tj) the tile's accumulators are also the B operands of its share
+    // of R_mid^T X_mid: D rows 16 ti + kq + 4 r of X = K index kq of MFMA step r.  pm: tiles (0,0), (0,1),
+    // (1,1) of the symmetric product (A operand R_mid^T from the LDS block, zero beyond m and nc).
+    double4_t pm[3] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+    auto mid_tile = [&](int ti, bool with_m) __attribute__((always_inline)) {
       const double *vl = vg + (size_t)mid * vline;
       double       *xl = xg + (size_t)mid * xline;
       const int     tiles_j = (nc + 15) >> 4;
@@ -112,7 +136,76 @@ namespace
               if (two && row < m && col + 16 < nc)
                 xl[row * ncg + col + 16] = acc1[r];
             }
+          if (with_m)
+            {
+              double ra[2][4];
+#pragma unroll
+              for (int it = 0; it < 2; ++it)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                  {
+                    const int  k = 16 * ti + (lane >> 4) + 4 * r, i = 16 * it + (lane & 15);
+                    const bool ok = k < m && i < nc;
+                    const double v = smem[ok ? k * ncs + i : 0];
+                    ra[it][r] = ok ? v : 0.0;
+                  }
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                {
+                  pm[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(ra[0][r], acc0[r], pm[0], 0, 0, 0);
+                  if (two)
+                    {
+                      pm[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(ra[0][r], acc1[r], pm[1], 0, 0, 0);
+                      pm[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(ra[1][r], acc1[r], pm[2], 0, 0, 0);
+                    }
+                }
+            }
         }
+    };
+    // The meeting line's row tiles (all four waves), with mfuse the turn-by-turn sum of R_mid^T X_mid
+    // into mfull (entries i <= j, mirrored: M stays exactly symmetric) and, by the last wave, M to A.mt;
+    // ends with barrier M3.  Every wave passes the same barriers.
+    auto mid_phase = [&]() __attribute__((always_inline)) {
+      if (!(SLOD_DG(A, 8)))
+        for (int ti = wave; 16 * ti < m; ti += 4)
+          mid_tile(ti, mfuse);
+      if (mfuse)
+        {
+          const int nw   = min((m + 15) >> 4, 4); // waves that own a row tile (one each: m <= 48)
+          double   *mtg  = A.mt + (size_t)blockIdx.x * slod_mt_stride(A.nc_max);
+          auto      turn = [&](bool last) __attribute__((always_inline)) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                {
+                  const int i = 16 * (q == 2 ? 1 : 0) + (lane >> 4) + 4 * r, j = 16 * (q == 0 ? 0 : 1) + (lane & 15);
+                  if (i <= j && j < nc)
+                    {
+                      const double v = mfull[i * nc + j] + pm[q][r];
+                      if (last)
+                        {
+                          mtg[i * nc + j] = v * A.invH2;
+                          mtg[j * nc + i] = v * A.invH2;
+                        }
+                      else
+                        {
+                          mfull[i * nc + j] = v;
+                          mfull[j * nc + i] = v;
+                        }
+                    }
+                }
+          };
+          for (int w = 0; w + 1 < nw; ++w)
+            {
+              if (wave == w)
+                turn(false);
+              __syncthreads();
+            }
+          if (wave == nw - 1)
+            turn(true);
+        }
+      __syncthreads(); // M3: X_mid is in the workspace (and M in A.mt)
     };
     const int n0 = mid, n1 = L - 1 - mid, nstp = n0 > n1 ? n0 : n1;
     const int nmy = chain == 0 ? n0 : n1; // lines of this chain
@@ -146,6 +239,9 @@ namespace
       }
     for (int idx = tid; idx < 2 * chsz; idx += 256)
       smem[idx] = 0.0;
+    if (A.m_tw)
+      for (int idx = tid; idx < 2 * 256; idx += 256)
+        mtile[idx] = 0.0;
     for (int c = tid; c < nc; c += 256)
       {
         int kx, ky;
@@ -208,6 +304,20 @@ namespace
     }
     __syncthreads();
     tstamp(1);
+    // M in the sweeps for this patch: every forward step of both chains takes gemm_Z_keep with at most
+    // 16 active columns, X_mid has at most two column tiles, mfull fits chain 1's free block.  Otherwise
+    // the selection stage computes M from X as before.
+    mfuse = S == 1 && A.m_tw && (MP + 15) / 16 <= 3 && nc <= 32 &&
+                 nc * nc <= MP * ncs + MP + 3 * bsz && !(SLOD_DG(A, 8));
+    int na_end[2] = {0, 0};
+    if (mfuse)
+      {
+        na_end[0] = __builtin_amdgcn_readfirstlane(nafin(0));
+        na_end[1] = __builtin_amdgcn_readfirstlane(nafin(1));
+        mfuse     = na_end[0] <= 16 && na_end[1] <= 16;
+      }
+    if (A.m_tw && tid == 0) // tells the selection stage (fused or k_select) where M comes from
+      A.mt[(size_t)blockIdx.x * slod_mt_stride(A.nc_max) + (size_t)A.nc_max * A.nc_max] = mfuse ? 1.0 : 0.0;
 
     // ------------------------------ forward elimination ---------------------------
     if (is_gj)
@@ -514,10 +624,7 @@ namespace
           atomicOr(A.status, 1);
         __builtin_amdgcn_s_setprio(0);
         __syncthreads(); // M2: V_mid is in the workspace
-        if (!(SLOD_DG(A, 8)))
-          for (int ti = wave; 16 * ti < m; ti += 4)
-            mid_tile(ti);
-        __syncthreads(); // M3: X_mid is in the workspace
+        mid_phase();
       }
     else
       {
@@ -727,6 +834,26 @@ namespace
             }
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
           __builtin_amdgcn_wave_barrier();
+          if (mfuse)
+            {
+              // chain tile += R^T Z (ncols <= 16): A operand R^T = the B operands still in bq[0], B operand Z
+              // from the block in the same K order.  Rows / columns beyond ncols are zero in R and Z (or,
+              // beyond ncs, other rows' values: they land in tile entries that are never read).
+              __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+              double   *mtc = mtile + chain * 256 + (lane >> 4) * 16 + (lane & 15);
+              double4_t macc;
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                macc[r] = mtc[64 * r];
+#pragma unroll
+              for (int kk = 0; kk < MP / 4; ++kk)
+                macc = __builtin_amdgcn_mfma_f64_16x16x4f64(bq[0][kk], bp[brow(kk) * ncs], macc, 0, 0, 0);
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                mtc[64 * r] = macc[r];
+              __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+              __builtin_amdgcn_wave_barrier();
+            }
         };
         // put_step in two halves for this wave: the stencil values of step stp are requested before the
         // RHS block / GEMM work of the step (branch-free, so that the loads really are in flight) and
@@ -856,11 +983,28 @@ namespace
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
           }
-        __syncthreads(); // M2: V_mid is in the workspace
-        if (!(SLOD_DG(A, 8)))
-          for (int ti = wave; 16 * ti < m; ti += 4)
-            mid_tile(ti);
-        __syncthreads(); // M3
+        else if (mfuse)
+          {
+            // chain 1's helper (idle until M2): mfull = both chain tiles in the order of P^T, entry (a, b)
+            // from the tile entry of (min, max), so that mfull is exactly symmetric
+            const int na0 = na_end[0], na1 = na_end[1];
+            for (int idx = lane; idx < nc * nc; idx += 64)
+              {
+                const int a = idx / nc, b = idx - a * nc, lo = min(a, b), hi = max(a, b);
+                double    v = 0.0;
+#pragma unroll
+                for (int ch = 0; ch < 2; ++ch)
+                  {
+                    const int *ci = colk + 2 * A.nc_max + ch * 3 * A.nc_max + A.nc_max;
+                    const int  i0 = ci[lo], j0 = ci[hi];
+                    if (i0 < (ch ? na1 : na0) && j0 < (ch ? na1 : na0))
+                      v += mtile[ch * 256 + i0 * 16 + j0];
+                  }
+                mfull[idx] = v;
+              }
+          }
+        __syncthreads(); // M2: V_mid is in the workspace (and mfull holds the chain terms)
+        mid_phase();
       }
 
     tstamp(3);
@@ -1148,7 +1292,8 @@ namespace
     if (S == 1 && A.fuse_select)
       {
         __syncthreads(); // X of all lines is written; LDS is free
-        select_patch<S>(A, A.nb_buf, A.nf_max, blockIdx.x, smem);
+        select_patch<S>(A, A.nb_buf, A.nf_max, blockIdx.x, smem,
+                        mfuse ? A.mt + (size_t)blockIdx.x * slod_mt_stride(A.nc_max) : nullptr);
         if (stamp)
           A.ms[(size_t)blockIdx.x * A.nc_max * A.nc_max + 2] = (double)wall_clock64();
       }
@@ -1156,14 +1301,15 @@ namespace
 
 } // namespace
 
-size_t slod_solve_tw_lds_bytes(int S, int m_max, int nc_max)
+size_t slod_solve_tw_lds_bytes(int S, int m_max, int nc_max, bool with_m)
 {
   // must mirror the carve-up at the top of k_solve_tw
   const int    T = slod_solve_ws_tile(m_max), W = 2 * S - 1, BW = 2 * W + 1, MP = 8 * T;
   const int    ncs = (nc_max + 1) & ~1, bsz = ((MP + 2 * W) * (BW + 1) + 1) & ~1;
   (void)m_max;
-  const size_t chsz = (size_t)MP * ncs + MP + 6 * (size_t)bsz;
-  return ((2 * chsz * sizeof(double) + 8 * (size_t)nc_max * sizeof(int)) + 15) & ~(size_t)15; // colk + perm/inv/act
+  const size_t chsz  = (size_t)MP * ncs + MP + 6 * (size_t)bsz;
+  const size_t mtile = with_m ? 2 * 256 * sizeof(double) : 0; // the chains' 16 x 16 tiles of M (A.m_tw)
+  return ((2 * chsz * sizeof(double) + 8 * (size_t)nc_max * sizeof(int) + mtile) + 15) & ~(size_t)15; // colk + perm/inv/act
 }
 
 template <int T, int S>
@@ -1177,8 +1323,8 @@ static hipError_t launch_tw_TS(const SlodKernelArgs &a, int n_patches, size_t ld
     {
       int nb = 0;
       (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, lds);
-      fprintf(stderr, "[slod] k_solve_tw<%d,%d>: %d patches, lds %zu B, occupancy %d blocks/CU\n", T, S, n_patches,
-              lds, nb);
+      fprintf(stderr, "[slod] k_solve_tw<%d,%d>: %d patches, lds %zu B, occupancy %d blocks/CU, M in the sweeps %d\n", T,
+              S, n_patches, lds, nb, a.m_tw);
     }
   hipLaunchKernelGGL((k_solve_tw<T, S>), dim3(n_patches), dim3(256), lds, st, a);
   return hipGetLastError();
