@@ -1,11 +1,15 @@
-// Counterpart of reference app/main_Diffusion.cc for the basis-construction path only:
-//   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]]
+// Counterpart of reference app/main_Diffusion.cc for the basis-construction path:
+//   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare]
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
 // file name it dumps, per patch, phi and psi in patch-lexicographic order (parity tests).
+// --compare (anywhere on the command line): after run(), the rest of the reference run() -- global
+// matrix, fine FEM solve (f = 1), LOD solve, compare_lod_with_fem -- and the "SLOD vs reference FEM(h)"
+// errors (LOD.cc:1462-1463) in L2, H1, Linfty and the energy norm.
 #include "../host/Diffusion.h"
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 using namespace slod;
 
@@ -34,8 +38,18 @@ public:
   }
 };
 
-int main(int argc, char **argv)
+int main(int argc_all, char **argv_all)
 {
+  // --compare is taken out wherever it stands; the positional arguments keep their meaning
+  bool               compare = false;
+  std::vector<char *> args;
+  for (int i = 0; i < argc_all; ++i)
+    if (i > 0 && !std::strcmp(argv_all[i], "--compare"))
+      compare = true;
+    else
+      args.push_back(argv_all[i]);
+  const int argc = (int)args.size();
+  char    **argv = args.data();
   try
     {
       LODParameters<2, 1> par;
@@ -58,6 +72,21 @@ int main(int argc, char **argv)
       std::printf("basis build time: %.3f ms\n", problem.basis_build_seconds() * 1e3);
       if (argc > 5)
         problem.dump(argv[5]);
+      if (compare)
+        {
+          problem.assemble_global_matrix();
+          problem.assemble_and_solve_fem_problem();
+          problem.solve();
+          problem.compare_lod_with_fem();
+          const slod_error_norms &e = problem.error_LOD_FEMh(), &u = problem.norms_FEMh();
+          const double h1 = std::sqrt(e.l2[0] * e.l2[0] + e.h1_semi[0] * e.h1_semi[0]),
+                       uh1 = std::sqrt(u.l2[0] * u.l2[0] + u.h1_semi[0] * u.h1_semi[0]);
+          std::printf("SLOD vs reference FEM(h)\n");
+          std::printf("  L2     error = %.12e  (relative %.6e)\n", e.l2[0], e.l2[0] / u.l2[0]);
+          std::printf("  H1     error = %.12e  (relative %.6e)\n", h1, h1 / uh1);
+          std::printf("  Linfty error = %.12e  (relative %.6e)\n", e.linf[0], e.linf[0] / u.linf[0]);
+          std::printf("  energy error = %.12e  (relative %.6e)\n", e.energy, e.energy / u.energy);
+        }
     }
   catch (std::exception &exc)
     {

@@ -318,6 +318,8 @@ void slod_destroy(slod_handle *h)
   for (int f = 0; f < 2; ++f)
     if (h->d_coef[f])
       (void)hipFree(h->d_coef[f]);
+  if (h->d_err_ws)
+    (void)hipFree(h->d_err_ws);
   if (h->stream)
     (void)hipStreamDestroy(h->stream);
   delete h;

@@ -21,6 +21,7 @@ struct slod_handle
   std::vector<char>   coef_set;  // [problem*2 + field]
   hipStream_t         stream = nullptr;
   bool                device_ready = false; // stream and coefficient storage exist
+  double             *d_err_ws = nullptr;   // slod_compute_error_norms partials (slod_error.hip), on first use
   mutable std::string error;
 };
 

@@ -1,10 +1,16 @@
 #include "LOD.h"
 
+#include <hip/hip_runtime_api.h>
+
 #include <chrono>
 #include <cstdlib>
 
 namespace slod
 {
+  // solver settings of the global steps (the reference: fine_solver_control / coarse CG, LOD.cc:990-998,1070-1075)
+  constexpr double fem_rel_tol = 1e-12, lod_rel_tol = 1e-13;
+  constexpr int    fem_max_iterations = 50000, lod_max_iterations = 5000;
+
   template <int dim, int spacedim>
   LOD<dim, spacedim>::LOD(const LODParameters<dim, spacedim> &par)
     : par(par)
@@ -18,6 +24,8 @@ namespace slod
   template <int dim, int spacedim>
   LOD<dim, spacedim>::~LOD()
   {
+    for (void *p : device_arrays)
+      (void)hipFree(p);
     slod_destroy(handle);
   }
 
@@ -26,6 +34,17 @@ namespace slod
   {
     if (status < 0)
       throw std::runtime_error(std::string(what) + ": " + slod_last_error(handle));
+  }
+
+  template <int dim, int spacedim>
+  template <typename T>
+  T *LOD<dim, spacedim>::device_alloc(const std::size_t n)
+  {
+    void *p = nullptr;
+    if (hipMalloc(&p, std::max<std::size_t>(n, 1) * sizeof(T)) != hipSuccess)
+      throw std::runtime_error("hipMalloc of a global vector failed");
+    device_arrays.push_back(p);
+    return static_cast<T *>(p);
   }
 
   // GridGenerator::hyper_cube + refine_global + evenly distributed partitioning (LOD.cc:110-119)
@@ -197,6 +216,91 @@ namespace slod
     initialize_patches();
     create_random_problem_coefficients();
     compute_basis_function_candidates();
+  }
+
+  // LOD.cc:860-973.  Patch::basis_function(_premultiplied) back to the patch-lexicographic order of the
+  // C-ABI, every patch at p * basis_stride of one device slab, then the block rows of A_LOD.
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::assemble_global_matrix()
+  {
+    const unsigned int n_patches = (unsigned int)patches.size();
+    if (locally_owned_patches.first != 0 || locally_owned_patches.second != n_patches)
+      throw std::runtime_error("assemble_global_matrix: the global steps need every patch in this process");
+    basis_stride = 0;
+    for (const auto &patch : patches)
+      basis_stride = std::max(basis_stride, (std::size_t)spacedim * patch.dealii_to_lexicographic.size());
+    std::vector<double> basis(n_patches * basis_stride, 0.0), premult(basis.size(), 0.0);
+    for (unsigned int p = 0; p < n_patches; ++p)
+      {
+        const Patch<dim> &patch  = patches[p];
+        const std::size_t n_fine = patch.dealii_to_lexicographic.size();
+        for (int d = 0; d < spacedim; ++d)
+          for (std::size_t i = 0; i < n_fine; ++i)
+            {
+              const std::size_t at = p * basis_stride + d * n_fine + patch.dealii_to_lexicographic[i];
+              basis[at]            = patch.basis_function[d][i];
+              premult[at]          = patch.basis_function_premultiplied[d][i];
+            }
+      }
+    d_basis   = device_alloc<double>(basis.size());
+    d_premult = device_alloc<double>(premult.size());
+    if (hipMemcpy(d_basis, basis.data(), basis.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_premult, premult.data(), premult.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+      throw std::runtime_error("assemble_global_matrix: basis upload failed");
+    const int cap = slod_lod_row_capacity(handle);
+    check(cap, "slod_lod_row_capacity");
+    d_lod_values = device_alloc<double>((std::size_t)n_patches * cap * spacedim * spacedim);
+    d_lod_cols   = device_alloc<uint32_t>((std::size_t)n_patches * cap);
+    std::vector<uint32_t> rows(n_patches);
+    for (unsigned int p = 0; p < n_patches; ++p)
+      rows[p] = p;
+    check(slod_lod_matrix(handle, rows.data(), n_patches, d_basis, d_premult, basis_stride, d_lod_values, d_lod_cols,
+                          nullptr),
+          "slod_lod_matrix");
+  }
+
+  // LOD.cc:1004-1094 with the example's f = 1
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::assemble_and_solve_fem_problem()
+  {
+    const std::size_t NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+    d_fem_rhs            = device_alloc<double>((NE + 1) * (NE + 1) * spacedim);
+    d_fem_solution       = device_alloc<double>((NE + 1) * (NE + 1) * spacedim);
+    check(slod_fem_rhs(handle, nullptr, d_fem_rhs, nullptr), "slod_fem_rhs");
+    check(slod_fem_solve(handle, 0, d_fem_rhs, d_fem_solution, fem_rel_tol, fem_max_iterations, nullptr),
+          "slod_fem_solve");
+  }
+
+  // LOD.cc:976-1002
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve()
+  {
+    if (!d_lod_values || !d_fem_rhs)
+      throw std::runtime_error("solve: assemble_global_matrix and assemble_and_solve_fem_problem come first");
+    const unsigned int    n_patches = (unsigned int)patches.size();
+    std::vector<uint32_t> rows(n_patches);
+    for (unsigned int p = 0; p < n_patches; ++p)
+      rows[p] = p;
+    double *d_rhs = device_alloc<double>((std::size_t)n_patches * spacedim);
+    d_lod_u       = device_alloc<double>((std::size_t)n_patches * spacedim);
+    check(slod_lod_rhs(handle, rows.data(), n_patches, d_basis, basis_stride, d_fem_rhs, d_rhs, nullptr), "slod_lod_rhs");
+    check(slod_lod_solve(handle, d_lod_values, d_lod_cols, d_rhs, d_lod_u, lod_rel_tol, lod_max_iterations, nullptr),
+          "slod_lod_solve");
+  }
+
+  // LOD.cc:1240-1260: u_LOD = C u_H, then error_LOD_FEMh.difference(u_h, u_LOD) in L2, H1, Linfty and energy
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::compare_lod_with_fem()
+  {
+    if (!d_lod_u || !d_fem_solution)
+      throw std::runtime_error("compare_lod_with_fem: solve and assemble_and_solve_fem_problem come first");
+    const std::size_t NE         = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+    double           *d_lod_fine = device_alloc<double>((NE + 1) * (NE + 1) * spacedim);
+    check(slod_lod_reconstruct(handle, d_basis, basis_stride, d_lod_u, d_lod_fine, nullptr), "slod_lod_reconstruct");
+    check(slod_compute_error_norms(handle, 0, d_fem_solution, d_lod_fine, nullptr, nullptr, &lod_fem_error, nullptr),
+          "slod_compute_error_norms");
+    check(slod_compute_error_norms(handle, 0, d_fem_solution, nullptr, nullptr, nullptr, &fem_norms, nullptr),
+          "slod_compute_error_norms");
   }
 
   template class LOD<2, 1>;

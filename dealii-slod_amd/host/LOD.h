@@ -2,9 +2,10 @@
 // (reference include/LOD.h:68-262, source/LOD.cc), without deal.II: same class and member
 // names, same argument meaning, same error behaviour (exceptions, as AssertThrow does in
 // LODtools.h:416-438).  compute_basis_function_candidates() is the drop-in body: it calls
-// the HIP library through the C-ABI of include/slod.h.  Everything the reference does
-// after the basis build (assemble_global_matrix, solve, FEM comparison, VTU output:
-// LOD.cc:860-1378) is out of scope and not mirrored.
+// the HIP library through the C-ABI of include/slod.h.  The steps of the reference run() after the
+// basis build (assemble_global_matrix, assemble_and_solve_fem_problem, solve, compare_lod_with_fem:
+// LOD.cc:860-1260) are public methods that chain the device entry points; run() stops after the
+// basis build as before.  VTU output and the coarse FEM(H) comparison are not mirrored.
 #ifndef slod_host_lod_h
 #define slod_host_lod_h
 
@@ -100,6 +101,19 @@ namespace slod
     // wall time of the last compute_basis_function_candidates() [s]
     double basis_build_seconds() const { return last_build_seconds; }
 
+    // The rest of the reference run() (LOD.cc:1430-1433), after run(); one process owning every patch.
+    // A_LOD = C^T (A C) from the basis, uploaded once as a uniform-stride slab (LOD.cc:860-973)
+    void assemble_global_matrix();
+    // fine FEM solution u_h with f = 1 (LOD.cc:1004-1094)
+    void assemble_and_solve_fem_problem();
+    // A_LOD u_H = C^T f_h (LOD.cc:976-1002)
+    void solve();
+    // u_LOD = C u_H and the norms of u_h - u_LOD (error_LOD_FEMh.difference, LOD.cc:1240-1260)
+    void compare_lod_with_fem();
+    const slod_error_norms &error_LOD_FEMh() const { return lod_fem_error; }
+    // the same norms of u_h alone (the denominators of relative errors)
+    const slod_error_norms &norms_FEMh() const { return fem_norms; }
+
   protected:
     void make_fe();
     void make_grid();
@@ -126,7 +140,17 @@ namespace slod
     slod_handle *                         handle = nullptr;
     double                                last_build_seconds = 0.0;
 
+    // device arrays of the global steps (freed by the destructor)
+    std::vector<void *> device_arrays;
+    std::size_t         basis_stride = 0;
+    double             *d_basis = nullptr, *d_premult = nullptr, *d_lod_values = nullptr;
+    uint32_t           *d_lod_cols = nullptr;
+    double             *d_fem_rhs = nullptr, *d_fem_solution = nullptr, *d_lod_u = nullptr;
+    slod_error_norms    lod_fem_error{}, fem_norms{};
+
     void check(const int status, const char *what) const;
+    template <typename T>
+    T *device_alloc(std::size_t n);
   };
 } // namespace slod
 

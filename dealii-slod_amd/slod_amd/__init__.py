@@ -40,6 +40,12 @@ class PatchDiag(C.Structure):
                 ("dinf", C.c_double), ("sigma_max", C.c_double), ("sigma_min", C.c_double)]
 
 
+class ErrorNorms(C.Structure):
+    """slod_error_norms: per-component L2, H1-seminorm and max-norm of e = u - v - w, and a(e,e)^{1/2}."""
+    _fields_ = [("l2", C.c_double * 2), ("h1_semi", C.c_double * 2), ("linf", C.c_double * 2),
+                ("energy", C.c_double), ("reserved", C.c_double * 3)]
+
+
 _lib = None
 
 
@@ -109,6 +115,7 @@ def load():
     lib.slod_lod_reconstruct.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
     lib.slod_fem_rhs.argtypes = [vp, vp, vp, vp]
     lib.slod_fem_solve.argtypes = [vp, C.c_uint32, vp, vp, C.c_double, C.c_int, dp]
+    lib.slod_compute_error_norms.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, C.POINTER(ErrorNorms), vp]
     lib.slod_device_patch_layout.argtypes = [vp, u32p, C.c_size_t, C.POINTER(PatchInfo)]
     lib.slod_sample_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, C.c_int]
     lib.slod_assemble_stiffness_for_patch.argtypes = [vp, C.c_uint32, dp]
@@ -351,6 +358,24 @@ class Slod:
         if it < 0:
             self._check(it)
         return it, res.value
+
+    def error_norms(self, d_u, d_v=None, d_exact=None, d_exact_grad=None, problem=0, stream=None):
+        """Norms of e = u - v - w on the fine grid (slod_compute_error_norms; raw device pointers, None = 0).
+        Per-component lists and, as ParsedConvergenceTable groups components of one name, totals over the
+        components: l2 and h1_semi in squares, h1 = (l2^2 + h1_semi^2)^{1/2} (deal.II's H1_norm), linf the
+        maximum; energy = a(e,e)^{1/2} with the coefficient of `problem`.  Synchronises `stream`."""
+        n = ErrorNorms()
+        self._check(self.lib.slod_compute_error_norms(self.h, problem, d_u, d_v, d_exact, d_exact_grad, C.byref(n),
+                                                      stream))
+        s = self.spacedim
+        l2 = [n.l2[c] for c in range(s)]
+        h1s = [n.h1_semi[c] for c in range(s)]
+        linf = [n.linf[c] for c in range(s)]
+        l2t = float(np.sqrt(sum(x * x for x in l2)))
+        h1st = float(np.sqrt(sum(x * x for x in h1s)))
+        return {"l2_components": l2, "h1_semi_components": h1s, "linf_components": linf,
+                "l2": l2t, "h1_semi": h1st, "h1": float(np.hypot(l2t, h1st)), "linf": max(linf),
+                "energy": n.energy}
 
     def device_patch_layout(self, ids):
         ids = np.ascontiguousarray(ids, dtype=np.uint32)

@@ -233,6 +233,41 @@ int slod_fem_rhs(slod_handle *h, const double *d_f_qp, double *d_fine_rhs, void 
 int slod_fem_solve(slod_handle *h, uint32_t problem, const double *d_fine_rhs, double *d_fine_u, double rel_tol,
                    int max_iterations, double *rel_residual);
 
+/* ---- error norms on the global fine grid (compare_lod_with_fem, LOD.cc:1240-1260:
+ * error_LOD_FEMh.difference and error_LOD_exact.error_from_exact; error_FEMh_exact, LOD.cc:1080-1088;
+ * the tables printed at the end of run(), LOD.cc:1425-1466) ----
+ * e = u - v - w, with u, v DEVICE nodal Q1 fields [(NE+1)^2][s] (the layout of slod_fem_solve and
+ * slod_lod_reconstruct; NULL = 0) and w an optional exact function given at the quadrature points:
+ * d_exact_qp [s][NE][NE][4] values, d_exact_grad_qp [s][2][NE][NE][4] gradients (d = 0: x, 1: y), both
+ * DEVICE, 16-byte aligned, and given together or both NULL.  The points are those of slod_set_coefficient
+ * layout 1 and of slod_fem_rhs's d_f_qp: q = q0 + 2 q1 at ((ex + g[q0]) h, (ey + g[q1]) h),
+ * g = 1/2 -+ 1/(2 sqrt 3), h = 1/NE: the 2 x 2 Gauss rule of the fine stiffness (QIterated(QGauss(2), n),
+ * LOD.cc:91-92) on every fine element, which is what every integral below uses.
+ *   l2[c]      = (int e_c^2)^{1/2}           h1_semi[c] = (int |grad e_c|^2)^{1/2}
+ *   linf[c]    = max over the quadrature points of |e_c|       (entries c >= spacedim are 0)
+ *   energy     = a(e,e)^{1/2} with the coefficient of `problem`: int alpha |grad e|^2 (spacedim 1),
+ *                int 2 mu eps(e):eps(e) + lambda (div e)^2 (spacedim 2, Elasticity.h:245-254).
+ * For FE fields (w NULL) energy^2 equals e^T A_h e of the unconstrained fine stiffness up to rounding.
+ * deal.II's H1_norm is the full norm (l2^2 + h1_semi^2)^{1/2}; ParsedConvergenceTable sums components
+ * of the same name in squares.  deal.II's error_from_exact integrates with a quadrature of its own, so
+ * errors against an exact solution are comparable to the reference's but not bit-equal.
+ * The reduction has a fixed order (no atomics): the same inputs give bitwise the same result.
+ * SLOD_ERR_ARGUMENT: NULL h or out, problem out of range, only one of the exact arrays, misaligned
+ * exact arrays; SLOD_ERR_DEVICE: no usable GPU; SLOD_ERR_STATE: coefficient of `problem` not set.
+ * The handle owns the reduction workspace (allocated on first use).  hip_stream NULL = the handle's
+ * stream; the call SYNCHRONISES hip_stream. */
+typedef struct
+{
+  double l2[2];      /* ||e_c||_L2, c < spacedim (unused entries 0)            */
+  double h1_semi[2]; /* |e_c|_H1                                              */
+  double linf[2];    /* max over quadrature points |e_c|                      */
+  double energy;     /* a(e,e)^{1/2} with the coefficient of `problem`         */
+  double reserved[3];
+} slod_error_norms;
+int slod_compute_error_norms(slod_handle *h, uint32_t problem, const double *d_u, const double *d_v,
+                             const double *d_exact_qp, const double *d_exact_grad_qp, slod_error_norms *out,
+                             void *hip_stream);
+
 /* ---- inputs of the path produced on the device --------------------------------------
  * create_patches + create_mesh_for_patch + fill_dofs_indices_vector (LOD.cc:122-244,
  * 770-858; LODtools.h:334-375) evaluated by a kernel, one thread per patch; out is a HOST
