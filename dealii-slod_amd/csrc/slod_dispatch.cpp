@@ -13,6 +13,8 @@
 //   SLOD_FUSE_ASSEMBLE=0      stencil assembly as its own launch
 //   SLOD_FUSE_M=0|1           M = P^T A^-1 P / H^2 built inside the sweeps instead of re-read from X:
 //                             tw default on (SLOD_FUSE_M=0 turns it off, for A/B timing), ws opt-in
+//   SLOD_BWD_KSPLIT=0|1       tw backward sweep (lines of at most three row tiles, nc_max <= 32): K of X = Z - V Y
+//                             split between the chain's two waves (default) or, 0, the column-tile split
 //   SLOD_TWISTED=0|1 (coop only) SLOD_DEBUG=1 print the choice
 //   SLOD_BALANCE=0            launch the patches in the caller's order (default: balanced over the CUs)
 SlodTuning slod_read_tuning()
@@ -27,6 +29,8 @@ SlodTuning slod_read_tuning()
     t.fuse_assemble = atoi(e) ? 1 : 0;
   if (const char *e = getenv("SLOD_FUSE_M"))
     t.fuse_m = atoi(e) ? 1 : 0;
+  if (const char *e = getenv("SLOD_BWD_KSPLIT"))
+    t.bwd_ksplit = atoi(e) ? 1 : 0;
   if (const char *e = getenv("SLOD_TWISTED"))
     t.twisted = atoi(e) ? 1 : 0;
   if (const char *e = getenv("SLOD_BALANCE"))
@@ -106,6 +110,9 @@ bool slod_choose_solver(int S, int n_sub, int m_max, int L_max, int nc_max, int 
         }
       if (c.fuse_select && lds_sel > c.lds)
         c.lds = lds_sel;
+      // backward sweep with K split over the chain's two waves: the LDS-resident variant of the loop only
+      // (at most three row tiles per line, at most two column tiles)
+      c.bwd_ksplit = (t.bwd_ksplit && 8 * wt <= 48 && nc_max <= 32) ? 1 : 0;
     }
   else if ((want(SLOD_K_WS) || t.solver == SLOD_K_TW) && ws_fits &&
            slod_solve_ws_lds_bytes(S, m_max, nc_max) <= lds_max)
@@ -145,6 +152,7 @@ hipError_t slod_launch_solve(int S, const SlodSolveChoice &c, SlodKernelArgs &a,
 {
   a.m_fused       = c.m_fused;
   a.m_tw          = c.m_tw;
+  a.bwd_ksplit    = c.bwd_ksplit;
   a.fuse_select   = c.fuse_select;
   a.fuse_assemble = c.fuse_assemble;
   a.debug         = c.debug;

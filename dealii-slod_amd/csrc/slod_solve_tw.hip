@@ -1057,10 +1057,17 @@ namespace
             const int i = idx / nc, c = idx - i * nc;
             Rb[i * ncs + c] = xg[(size_t)mid * xline + i * ncg + c];
           }
-      // (two instances of the loop, one per variant: sharing one loop made the register allocator spill
-      // the prefetched operands of the LDS-resident variant)
-      auto backward = [&](auto KEEP) __attribute__((always_inline)) {
-      constexpr bool keep_x = decltype(KEEP)::value;
+      // Workgroup barrier of the K-split variant: LDS traffic only.  __syncthreads() also waits for every
+      // global access (vmcnt(0)), which would drain the V and Z loads in flight across it.
+      auto bar_lds = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+      // (one instance of the loop per variant: sharing one loop made the register allocator spill
+      // the prefetched operands of the LDS-resident variants)
+      //   MODE 0: X(prev) and Y through the workspace / the block, any size
+      //   MODE 1: X(prev) resident in the block, GEMM split by column tile between the chain's two waves
+      //   MODE 2: X(prev) resident in the block, GEMM split by K half (A.bwd_ksplit)
+      auto backward = [&](auto MODE_) __attribute__((always_inline)) {
+      constexpr int  MODE   = decltype(MODE_)::value;
+      constexpr bool keep_x = MODE == 1;
       for (int t = tstart; t >= 0; --t)
         {
           while (nab > 0 && act[nab - 1] > t)
@@ -1069,9 +1076,160 @@ namespace
           const int     line = line_of(chain, t), prev = line_of(chain, t + 1); // prev: solved before (mid first)
           const double *Bn = (t & 1) ? Bc1 : Bc0;
           asm volatile("" : "+v"(lane));
-          __syncthreads(); // bands of this line are in LDS, X(prev) is in the workspace / the LDS block
+          // bands of this line are in LDS, X(prev) is in the workspace / the LDS block
+          if constexpr (MODE == 2)
+            bar_lds(); // (X(prev) is read from the block only: the X stores to the workspace stay in flight)
+          else
+            __syncthreads();
           if (active && t > 0)
             fetch_B(line_of(chain, t - 1));
+          if constexpr (MODE == 2)
+            {
+              // X_l = Z_l - V_l Y with K split between the chain's two waves: wave w2 takes the K half
+              // g = w2 of load_A (rows T (kq + 4 w2) + kr of Y) for every row tile and both column tiles,
+              // finishes column tile w2 and hands its partial of the other tile to its partner through the
+              // partner's columns of the block.  Each wave loads half of V_l, all of it requested up front
+              // (one workspace round trip per line), and forms its B operands in registers.
+              // Workgroup barriers of a line (every wave passes them, idle steps of the shorter chain too):
+              //   top: X(prev) and the bands are in LDS;  K1: every window of X(prev) is read by both waves,
+              //   the block may be overwritten;  K2: the partner's partial is in the block.
+              const double *vl = vg + (size_t)line * vline;
+              double       *xl = xg + (size_t)line * xline;
+              const int     kq = lane >> 4, nl = lane & 15;
+              const int     colw = 16 * w2 + nl;       // column this lane finishes
+              const int     colo = 16 * (1 - w2) + nl; // column of the partial it hands over
+              const bool    mine = active && 16 * w2 < nc, oth = active && 16 * (1 - w2) < nc;
+              // am: accumulators of the tile this wave finishes, started at -Z_l (so Z needs no registers of
+              // its own while the V operands, Y and the accumulators are all live): am = V Y - Z, X = -(am + partner)
+              double    av[TIB][T];
+              double4_t am[TIB];
+              // (the loads only, addresses clamped: sign and the mask of columns not yet active in the forward
+              // sweep -- never written, zero -- are applied after K1, so that nothing here waits for a load)
+              const int  zc  = colw < nc ? inv[colw] : nc;
+              const bool zok = zc < nab; // the chain order is sorted by the first active step
+              if (mine)
+                {
+                  const double *zrow = zg + (size_t)line * xline;
+#pragma unroll
+                  for (int ti = 0; ti < TIB; ++ti)
+                    if (ti < tiles_i)
+                      {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                          {
+                            const int row = 16 * ti + kq + 4 * r;
+                            am[ti][r]     = zrow[(row < m && zok) ? row * nab + zc : 0];
+                          }
+                      }
+                }
+              if (active)
+                {
+#pragma unroll
+                  for (int ti = 0; ti < TIB; ++ti)
+                    if (ti < tiles_i)
+                      {
+                        const int     row = min(16 * ti + nl, MP - 1);
+                        const int     rt = row / T, rr = row - rt * T;
+                        const double *base = vl + (rt * 8 + kq + 4 * w2) * (T * T) + rr * T;
+#pragma unroll
+                        for (int kr = 0; kr < T; ++kr)
+                          av[ti][kr] = base[kr];
+                      }
+                }
+              // B operands: Y[T (kq + 4 w2) + kr][c] = (B(line -> prev) X(prev))[..][c] for c = colw (y[0])
+              // and c = colo (y[1]), X(prev) from the block; zero beyond m and nc
+              double    y[2][T];
+              const int r0 = T * (kq + 4 * w2);
+              if (active)
+                {
+#pragma unroll
+                  for (int k = 0; k < 2; ++k)
+                    {
+                      const int c = k == 0 ? colw : colo;
+                      double    win[T + 2 * W];
+#pragma unroll
+                      for (int e = 0; e < T + 2 * W; ++e)
+                        {
+                          const int    pr  = r0 + e - W;
+                          const bool   inb = c < nc && pr >= 0 && pr < m;
+                          const double x   = Rb[(inb ? pr : 0) * ncs + (inb ? c : 0)];
+                          win[e]           = inb ? x : 0.0;
+                        }
+#pragma unroll
+                      for (int ta = 0; ta < T; ++ta)
+                        {
+                          double v = 0.0;
+#pragma unroll
+                          for (int o = 0; o < BW; ++o)
+                            v = fma(Bn[(r0 + ta + W) * BWP + o], win[ta + o], v);
+                          y[k][ta] = r0 + ta < m ? v : 0.0;
+                        }
+                    }
+                }
+              bar_lds(); // K1
+              if (oth) // the partner's tile first: it waits for this
+                {
+#pragma unroll
+                  for (int ti = 0; ti < TIB; ++ti)
+                    if (ti < tiles_i)
+                      {
+                        double4_t a1 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                        for (int kr = 0; kr < T; ++kr)
+                          a1 = __builtin_amdgcn_mfma_f64_16x16x4f64(av[ti][kr], y[1][kr], a1, 0, 0, 0);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                          {
+                            const int row = 16 * ti + kq + 4 * r;
+                            if (row < m && colo < nc)
+                              Rb[row * ncs + colo] = a1[r];
+                          }
+                      }
+                }
+              if (mine)
+                {
+#pragma unroll
+                  for (int ti = 0; ti < TIB; ++ti)
+                    if (ti < tiles_i)
+                      {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                          am[ti][r] = zok ? -am[ti][r] : 0.0; // (rows beyond m are never stored)
+#pragma unroll
+                        for (int kr = 0; kr < T; ++kr)
+                          am[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[ti][kr], y[0][kr], am[ti], 0, 0, 0);
+                      }
+                }
+              bar_lds(); // K2
+              // the bands of the next line go to the other band buffer before the X stores are issued: once
+              // those are in flight, a wait for the band loads would wait for them as well
+#pragma unroll
+              for (int q = 0; q < NBV; ++q)
+                asm volatile("" : "+v"(bv[q]));
+              if (active && t > 0)
+                store_B(((t - 1) & 1) ? Bc1 : Bc0);
+              if (mine)
+                {
+                  // (own half + partner's half: the same sum whichever wave finishes the tile)
+#pragma unroll
+                  for (int ti = 0; ti < TIB; ++ti)
+                    if (ti < tiles_i)
+                      {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                          {
+                            const int row = 16 * ti + kq + 4 * r;
+                            if (row < m && colw < nc)
+                              {
+                                const double x       = -(am[ti][r] + Rb[row * ncs + colw]);
+                                xl[row * ncg + colw] = x;
+                                Rb[row * ncs + colw] = x;
+                              }
+                          }
+                      }
+                }
+              continue;
+            }
           if constexpr (keep_x)
             {
               const double *vl = vg + (size_t)line * vline;
@@ -1277,10 +1435,12 @@ namespace
           // the next iteration's first barrier orders the X and band writes before their readers
         }
       };
-      if (keepb)
-        backward(std::true_type{});
+      if (keepb && A.bwd_ksplit)
+        backward(std::integral_constant<int, 2>{});
+      else if (keepb)
+        backward(std::integral_constant<int, 1>{});
       else
-        backward(std::false_type{});
+        backward(std::integral_constant<int, 0>{});
     }
     // Fused selection stage: the same workgroup goes on with M, D, the boundary trace, the
     // least squares, phi and psi of its patch (X is fresh in this CU's L2 slice).  Patches of
@@ -1323,8 +1483,8 @@ static hipError_t launch_tw_TS(const SlodKernelArgs &a, int n_patches, size_t ld
     {
       int nb = 0;
       (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, lds);
-      fprintf(stderr, "[slod] k_solve_tw<%d,%d>: %d patches, lds %zu B, occupancy %d blocks/CU, M in the sweeps %d\n", T,
-              S, n_patches, lds, nb, a.m_tw);
+      fprintf(stderr, "[slod] k_solve_tw<%d,%d>: %d patches, lds %zu B, occupancy %d blocks/CU, backward K split %d, M in the sweeps %d\n",
+              T, S, n_patches, lds, nb, a.bwd_ksplit, a.m_tw);
     }
   hipLaunchKernelGGL((k_solve_tw<T, S>), dim3(n_patches), dim3(256), lds, st, a);
   return hipGetLastError();
