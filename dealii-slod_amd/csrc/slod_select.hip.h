@@ -1,6 +1,7 @@
 // K3 as a device function: coarse Schur block, (S)LOD selection, normalisation, premultiplication.
 #ifndef SLOD_SELECT_HIP_H
 #define SLOD_SELECT_HIP_H
+#include <type_traits>
 #include "slod_common.hip.h"
 
 namespace
@@ -839,17 +840,39 @@ namespace
                         int          *pn  = pcol + (1 - pb) * ncm;
                         const double *cnc = (k & 1) ? utg : sig; // trailing column norms^2 (rows >= k)
                         double       *cnn = (k & 1) ? sig : utg;
-                        int           p    = k;
-                        double        best = cnc[pc[k]];
-                        for (int j = k + 1; j < nn1; ++j)
-                          {
-                            const double v = cnc[pc[j]];
-                            if (v > best)
-                              {
-                                best = v;
-                                p    = j;
-                              }
-                          }
+                        // Pivot search, lane parallel (nn1 <= 31; every wave on its own, so no barrier): lane j
+                        // takes the norm of position j, an arg-max over each 16-lane row by DPP rotations
+                        // follows and rows 0 and 1 are combined through readlane.  Ties go to the lowest
+                        // position, which is what a serial scan with a strict comparison picks, so the pivot
+                        // order is that of the scan (one LDS round trip instead of one per position).
+                        int    p;
+                        double best;
+                        {
+                          const bool pin = lane >= k && lane < nn1;
+                          double     v   = cnc[pc[pin ? lane : k]];
+                          int        q   = pin ? lane : 64;
+                          v              = pin ? v : -1.0; // (norms^2 are >= 0)
+                          auto step = [&](auto CTRL_) __attribute__((always_inline)) {
+                            constexpr int CTRL = decltype(CTRL_)::value;
+                            const double  ov   = dpp_rot<CTRL>(v);
+                            const int     oq   = __builtin_amdgcn_mov_dpp(q, CTRL, 0xf, 0xf, false);
+                            const bool    take = (ov > v) | ((ov == v) & (oq < q)); // (no short circuit: no branch)
+                            v                  = take ? ov : v;
+                            q                  = take ? oq : q;
+                          };
+                          step(std::integral_constant<int, 0x128>{}); // row_ror:8
+                          step(std::integral_constant<int, 0x124>{}); // row_ror:4
+                          step(std::integral_constant<int, 0x122>{}); // row_ror:2
+                          step(std::integral_constant<int, 0x121>{}); // row_ror:1
+                          const int    q0 = __builtin_amdgcn_readlane(q, 0), q1 = __builtin_amdgcn_readlane(q, 16);
+                          const double v0 = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 0),
+                                                             __builtin_amdgcn_readlane(__double2loint(v), 0));
+                          const double v1 = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 16),
+                                                             __builtin_amdgcn_readlane(__double2loint(v), 16));
+                          const bool   hi = v1 > v0; // (row 1 holds the higher positions: it wins only if larger)
+                          best            = hi ? v1 : v0;
+                          p               = hi ? q1 : q0;
+                        }
                         if (!(best > 0.0))
                           break; // the trailing block is zero (uniform decision)
                         const int cp = pc[p];
@@ -922,6 +945,8 @@ namespace
                       }
                   }
                 __syncthreads();
+                if (stamping && A.nc_max * A.nc_max >= 16)
+                  msd[14] = (double)wall_clock64(); // end of the pivoted second-stage QR
                 const int *pc = pcol + pb * ncm; // position -> column of BD'
                 if (tposed)
                   {
@@ -1101,6 +1126,8 @@ namespace
                       if (!any)
                         break;
                     }
+                if (stamping && A.nc_max * A.nc_max >= 16)
+                  msd[15] = (double)wall_clock64(); // end of the Jacobi sweeps
                 // sig_j = sigma_j(G); utg_j = coefficient of the j-th term's vector
                 for (int j = tid; j < nn1; j += 256)
                   {

@@ -33,13 +33,16 @@ buf = np.zeros(len(ids) * ncm * ncm)
 lib = g.lib
 lib.slod_debug_read_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_size_t]
 assert lib.slod_debug_read_ms(plan.p, buf.ctypes.data_as(C.POINTER(C.c_double)), buf.size) == 0
-r = buf.reshape(len(ids), ncm * ncm)[:, :12] / 100.0
+r = buf.reshape(len(ids), ncm * ncm)[:, :16] / 100.0
 print("kernel_ms", plan.kernel_ms())
 full = [k for k, pid in enumerate(ids) if (lambda i: i.mx == 5 and i.my == 5)(g.patch_layout(int(pid)))]
 rr = r[full]
 ph = dict(D=rr[:, 4] - rr[:, 3], fill=rr[:, 5], mult=rr[:, 6], qr=rr[:, 7], rinv=rr[:, 8] - rr[:, 4] - rr[:, 5] - rr[:, 6] - rr[:, 7],
           svd=rr[:, 9] - rr[:, 8], phi=rr[:, 10] - rr[:, 9], psi=rr[:, 11] - rr[:, 10], total_after_M=rr[:, 11] - rr[:, 3])
 slow = ph["svd"] > np.median(ph["svd"]) * 3 + 20
+if slow.any() and rr[slow][:, 14].min() > rr[slow][:, 8].min():  # stamps inside the fallback (one component: S = 1)
+    ph.update(svd_pivoted_qr=rr[:, 14] - rr[:, 8], svd_jacobi=rr[:, 15] - rr[:, 14], svd_sort_loop=rr[:, 9] - rr[:, 15])
 for name, m in (("fast path", ~slow), ("SVD fallback", slow)):
     if m.sum():
-        print("%-13s n=%3d " % (name, m.sum()) + "  ".join("%s %.1f" % (k, v[m].mean()) for k, v in ph.items()))
+        print("%-13s n=%3d " % (name, m.sum()) + "  ".join("%s %.1f" % (k, v[m].mean()) for k, v in ph.items()
+                                                             if name != "fast path" or not k.startswith("svd_")))
