@@ -1,10 +1,12 @@
 // Counterpart of reference app/main_Diffusion.cc for the basis-construction path:
-//   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare]
+//   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare] [--coarse]
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
 // file name it dumps, per patch, phi and psi in patch-lexicographic order (parity tests).
 // --compare (anywhere on the command line): after run(), the rest of the reference run() -- global
 // matrix, fine FEM solve (f = 1), LOD solve, compare_lod_with_fem -- and the "SLOD vs reference FEM(h)"
 // errors (LOD.cc:1462-1463) in L2, H1, Linfty and the energy norm.
+// --coarse implies --compare and adds the coarse FEM(H) problem (LOD.cc:1103-1237): its table "FEM(H) vs
+// reference FEM(h)" comes before the SLOD table, the reference's order (LOD.cc:1458-1465).
 #include "../host/Diffusion.h"
 
 #include <cstdio>
@@ -40,12 +42,14 @@ public:
 
 int main(int argc_all, char **argv_all)
 {
-  // --compare is taken out wherever it stands; the positional arguments keep their meaning
-  bool               compare = false;
+  // --compare and --coarse are taken out wherever they stand; the positional arguments keep their meaning
+  bool               compare = false, coarse = false;
   std::vector<char *> args;
   for (int i = 0; i < argc_all; ++i)
     if (i > 0 && !std::strcmp(argv_all[i], "--compare"))
       compare = true;
+    else if (i > 0 && !std::strcmp(argv_all[i], "--coarse"))
+      compare = coarse = true;
     else
       args.push_back(argv_all[i]);
   const int argc = (int)args.size();
@@ -76,11 +80,23 @@ int main(int argc_all, char **argv_all)
         {
           problem.assemble_global_matrix();
           problem.assemble_and_solve_fem_problem();
+          if (coarse)
+            problem.assemble_and_solve_coarse_fem_problem();
           problem.solve();
           problem.compare_lod_with_fem();
           const slod_error_norms &e = problem.error_LOD_FEMh(), &u = problem.norms_FEMh();
           const double h1 = std::sqrt(e.l2[0] * e.l2[0] + e.h1_semi[0] * e.h1_semi[0]),
                        uh1 = std::sqrt(u.l2[0] * u.l2[0] + u.h1_semi[0] * u.h1_semi[0]);
+          if (coarse)
+            {
+              const slod_error_norms &c = problem.error_FEMH_FEMh();
+              const double ch1 = std::sqrt(c.l2[0] * c.l2[0] + c.h1_semi[0] * c.h1_semi[0]);
+              std::printf("FEM(H) vs reference FEM(h)\n");
+              std::printf("  L2     error = %.12e  (relative %.6e)\n", c.l2[0], c.l2[0] / u.l2[0]);
+              std::printf("  H1     error = %.12e  (relative %.6e)\n", ch1, ch1 / uh1);
+              std::printf("  Linfty error = %.12e  (relative %.6e)\n", c.linf[0], c.linf[0] / u.linf[0]);
+              std::printf("  energy error = %.12e  (relative %.6e)\n", c.energy, c.energy / u.energy);
+            }
           std::printf("SLOD vs reference FEM(h)\n");
           std::printf("  L2     error = %.12e  (relative %.6e)\n", e.l2[0], e.l2[0] / u.l2[0]);
           std::printf("  H1     error = %.12e  (relative %.6e)\n", h1, h1 / uh1);

@@ -729,7 +729,82 @@ namespace
     const int idx = (int)floor(x / eta) + NC * (int)floor(y / eta);
     coef[i]       = vals[idx];
   }
+
+  // ---- coarse FEM(H) reference problem (the coarse part of assemble_and_solve_fem_problem,
+  // LOD.cc:1103-1237): Q1 on the coarse mesh, the coefficient at the 2 x 2 Gauss points of every coarse
+  // cell (assemble_stiffness_coarse, Diffusion.h:210-305, Elasticity.h:304ff).  Stiffness, load vector and
+  // solve are the fine-grid kernels with NE := N; new are only the sampling and the interpolation back.
+  //
+  // Where the coarse Gauss abscissa (C + g[k]) H falls in the fine grid, per axis: fine element C n + off[k],
+  // quadrature slot slot[k] of that element (the stored fine field read as piecewise constant on the
+  // quadrants of the fine elements).  Computed once on the host from n (coarse_sample_rule): no per-thread
+  // floating-point floor decides an index.
+  struct CoarseSampleRule
+  {
+    int32_t off[2], slot[2];
+  };
+  // out [N][N][4] (q = q0 + 2 q1, the layout of a fine field with NE -> N) from fine [NE][NE][4]
+  __global__ void k_coarse_sample(int N, int n, const CoarseSampleRule R, const double *fine, double *out)
+  {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)N * N * 4)
+      return;
+    const int    q0 = (int)(i & 1), q1 = (int)((i >> 1) & 1);
+    const size_t cell = i >> 2;
+    const int    Cx = (int)(cell % (size_t)N), Cy = (int)(cell / (size_t)N), NE = N * n;
+    const int    ex = Cx * n + R.off[q0], ey = Cy * n + R.off[q1]; // off <= n - 1: inside the coarse cell
+    out[i]          = fine[((size_t)ey * NE + ex) * 4 + R.slot[q0] + 2 * R.slot[q1]];
+  }
+  // fem_coarse_solution_interpolated (FETools::interpolate, LOD.cc:1201-1204): bilinear interpolant of the
+  // coarse nodal field [(N+1)^2][s] at every fine node, [(NE+1)^2][s].  One thread per fine node, blockIdx.y
+  // walks the node rows (no division by the row length; consecutive threads store consecutive nodes).  The
+  // weights are the integers (n - rx, rx) x (n - ry, ry) over n^2, so a field that is exactly representable
+  // sees one rounding (the division); a fine node on a coarse node copies the value bit for bit.
+  __global__ void k_coarse_prolong(int N, int n, int s, const double *coarse, double *fine)
+  {
+    const int NE = N * n, np = NE + 1, npc = N + 1;
+    const int ix = blockIdx.x * 256 + threadIdx.x;
+    if (ix >= np)
+      return;
+    const int Cx = ix / n < N ? ix / n : N - 1, rx = ix - Cx * n; // the last node line: cell N - 1, rx = n
+    for (int iy = blockIdx.y; iy < np; iy += gridDim.y)
+      {
+        const int    Cy = iy / n < N ? iy / n : N - 1, ry = iy - Cy * n; // rx, ry in [0, n]
+        const size_t node = (size_t)iy * np + ix, c00 = (size_t)Cx + (size_t)Cy * npc;
+        if ((rx == 0 || rx == n) && (ry == 0 || ry == n))
+          {
+            const size_t src = c00 + (rx ? 1 : 0) + (ry ? (size_t)npc : 0);
+            for (int c = 0; c < s; ++c)
+              fine[node * s + c] = coarse[src * s + c];
+            continue;
+          }
+        const double w00 = (double)((n - rx) * (n - ry)), w10 = (double)(rx * (n - ry)), w01 = (double)((n - rx) * ry),
+                     w11 = (double)(rx * ry), nn = (double)n * (double)n;
+        for (int c = 0; c < s; ++c)
+          {
+            // (a weight of 0 still reads its corner: every corner is a node of the coarse grid)
+            const double v = w00 * coarse[c00 * s + c] + w10 * coarse[(c00 + 1) * s + c] + w01 * coarse[(c00 + npc) * s + c] +
+                             w11 * coarse[(c00 + npc + 1) * s + c];
+            fine[node * s + c] = v / nn;
+          }
+      }
+  }
 } // namespace
+
+// position of the two coarse Gauss abscissae of one axis in the fine grid (see CoarseSampleRule); n g is
+// irrational, so the point never sits on an element edge or on a quadrant boundary
+static CoarseSampleRule coarse_sample_rule(int n)
+{
+  const double     g[2] = {0.21132486540518711775, 0.78867513459481288225}; // (1 -+ 1/sqrt 3)/2
+  CoarseSampleRule R;
+  for (int k = 0; k < 2; ++k)
+    {
+      const double t = n * g[k];
+      R.off[k]       = (int32_t)std::floor(t);
+      R.slot[k]      = t - std::floor(t) >= 0.5 ? 1 : 0;
+    }
+  return R;
+}
 
 // slod_plan_create's device pass (declared in slod_host.h): descriptors, maxima, realisations in use,
 // balanced order.  Everything stays on the device except the 40-byte summary and the used-problem map.
@@ -1061,22 +1136,17 @@ int slod_fem_rhs(slod_handle *h, const double *d_f_qp, double *d_fine_rhs, void 
   return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_fem_rhs");
 }
 
-int slod_fem_solve(slod_handle *h, uint32_t problem, const double *d_fine_rhs, double *d_fine_u, double rel_tol,
-                   int max_iterations, double *rel_residual)
+// The Q1 problem on an NE x NE grid of the unit square, on the handle's stream: stencil planes of k_assemble
+// from the coefficient fields c0, c1 ([NE][NE][4] each, c1 for spacedim 2 only), then the CG bursts with
+// device scalars, multigrid-preconditioned where that applies.  slod_fem_solve calls it with the fine grid
+// and the stored field of a problem, slod_coarse_fem_solve with the coarse grid and the sampled field.
+// Returns the iteration count or a negative slod_status (`who` names the caller in the error text).
+static int fem_solve_grid(slod_handle *h, const char *who, int NE, const double *c0, const double *c1, const double *d_fine_rhs,
+                          double *d_fine_u, double rel_tol, int max_iterations, double *rel_residual)
 {
-  if (!h || !d_fine_rhs || !d_fine_u || max_iterations < 0)
-    return SLOD_ERR_ARGUMENT;
-  if (problem >= (uint32_t)h->cfg.n_problems)
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_fem_solve: problem out of range");
-  const int s = h->cfg.spacedim;
-  for (int f = 0; f < s; ++f)
-    if (!h->coef_set[(size_t)problem * 2 + f])
-      return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_fem_solve: coefficient not set");
-  if (const int rc = slod_ensure_device(h))
-    return rc;
-  (void)hipSetDevice(h->cfg.device);
+  const int     s = h->cfg.spacedim;
   hipStream_t   st = h->stream;
-  const int     NE = h->NE, nn = (NE + 1) * (NE + 1), nblk = (nn + 255) / 256;
+  const int     nn = (NE + 1) * (NE + 1), nblk = (nn + 255) / 256;
   const size_t  nrow = (size_t)nn * s;
   double       *planes = nullptr, *work = nullptr;
   SlodPatchDesc *d_desc = nullptr;
@@ -1093,18 +1163,18 @@ int slod_fem_solve(slod_handle *h, uint32_t problem, const double *d_fine_rhs, d
   int it = 0;
   if (e == hipSuccess)
     {
-      // the whole domain as one patch of k_assemble: NE x NE fine elements at the origin
+      // the whole domain as one patch of k_assemble: NE x NE elements at the origin
       SlodPatchDesc d;
       std::memset(&d, 0, sizeof(d));
       d.nx   = NE;
       d.ny   = NE;
-      d.prob = (int32_t)problem;
+      d.prob = 0; // c0, c1 point at the field itself
       e      = hipMemcpyAsync(d_desc, &d, sizeof(d), hipMemcpyHostToDevice, st);
       SlodKernelArgs a;
       std::memset(&a, 0, sizeof(a));
       a.desc        = d_desc;
-      a.coef0       = h->d_coef[0];
-      a.coef1       = h->d_coef[1];
+      a.coef0       = c0;
+      a.coef1       = c1;
       a.coef_stride = (size_t)NE * NE * 4;
       a.NE          = NE;
       a.n_sub       = h->cfg.n_subdivisions;
@@ -1296,8 +1366,120 @@ int slod_fem_solve(slod_handle *h, uint32_t problem, const double *d_fine_rhs, d
   if (sc)
     (void)hipFree(sc);
   if (e != hipSuccess)
-    return slod_hip_fail(h, e, "slod_fem_solve");
+    return slod_hip_fail(h, e, who);
   return it;
+}
+
+int slod_fem_solve(slod_handle *h, uint32_t problem, const double *d_fine_rhs, double *d_fine_u, double rel_tol,
+                   int max_iterations, double *rel_residual)
+{
+  if (!h || !d_fine_rhs || !d_fine_u || max_iterations < 0)
+    return SLOD_ERR_ARGUMENT;
+  if (problem >= (uint32_t)h->cfg.n_problems)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_fem_solve: problem out of range");
+  const int s = h->cfg.spacedim;
+  for (int f = 0; f < s; ++f)
+    if (!h->coef_set[(size_t)problem * 2 + f])
+      return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_fem_solve: coefficient not set");
+  if (const int rc = slod_ensure_device(h))
+    return rc;
+  (void)hipSetDevice(h->cfg.device);
+  const size_t cs = (size_t)problem * h->NE * h->NE * 4;
+  return fem_solve_grid(h, "slod_fem_solve", h->NE, h->d_coef[0] + cs, s == 2 ? h->d_coef[1] + cs : nullptr, d_fine_rhs,
+                        d_fine_u, rel_tol, max_iterations, rel_residual);
+}
+
+// ---- coarse FEM(H) reference problem (LOD.cc:1103-1237) ----
+static void launch_coarse_sample(const slod_handle *h, uint32_t problem, int field, double *d_out, hipStream_t st)
+{
+  const size_t cnt = (size_t)h->N * h->N * 4;
+  hipLaunchKernelGGL(k_coarse_sample, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, h->N, h->cfg.n_subdivisions,
+                     coarse_sample_rule(h->cfg.n_subdivisions), h->d_coef[field] + (size_t)problem * h->NE * h->NE * 4, d_out);
+}
+
+int slod_coarse_coefficient(slod_handle *h, uint32_t problem, int field, double *d_out, void *hip_stream)
+{
+  if (!h || !d_out)
+    return SLOD_ERR_ARGUMENT;
+  if (problem >= (uint32_t)h->cfg.n_problems || field < 0 || field >= h->cfg.spacedim)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_coarse_coefficient: problem/field out of range");
+  if (const int rc = slod_ensure_device(h))
+    return rc;
+  if (!h->coef_set[(size_t)problem * 2 + field])
+    return slod_fail(h, SLOD_ERR_STATE, "slod_coarse_coefficient: coefficient not set");
+  (void)hipSetDevice(h->cfg.device);
+  launch_coarse_sample(h, problem, field, d_out, hip_stream ? (hipStream_t)hip_stream : h->stream);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_coarse_coefficient");
+}
+
+int slod_coarse_fem_rhs(slod_handle *h, const double *d_f_cqp, double *d_coarse_rhs, void *hip_stream)
+{
+  if (!h || !d_coarse_rhs)
+    return SLOD_ERR_ARGUMENT;
+  if (const int rc = slod_ensure_device(h))
+    return rc;
+  (void)hipSetDevice(h->cfg.device);
+  hipStream_t  st = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  const int    nn = (h->N + 1) * (h->N + 1);
+  const double H  = 1.0 / h->N;
+  // k_fem_rhs with NE := N, h := H: FE_Q_iso_Q1(1) with QIterated(QGauss(2), 1) (coarse_fem_subdivisions = 1)
+  hipLaunchKernelGGL(k_fem_rhs, dim3((nn + 255) / 256), dim3(256), 0, st, h->N, h->cfg.spacedim, H * H * 0.25, d_f_cqp,
+                     d_coarse_rhs);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_coarse_fem_rhs");
+}
+
+int slod_coarse_fem_solve(slod_handle *h, uint32_t problem, const double *d_coarse_rhs, double *d_coarse_u, double rel_tol,
+                          int max_iterations, double *rel_residual)
+{
+  if (!h || !d_coarse_rhs || !d_coarse_u || max_iterations < 0)
+    return SLOD_ERR_ARGUMENT;
+  if (problem >= (uint32_t)h->cfg.n_problems)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_coarse_fem_solve: problem out of range");
+  if (const int rc = slod_ensure_device(h))
+    return rc;
+  const int s = h->cfg.spacedim;
+  for (int f = 0; f < s; ++f)
+    if (!h->coef_set[(size_t)problem * 2 + f])
+      return slod_fail(h, SLOD_ERR_STATE, "slod_coarse_fem_solve: coefficient not set");
+  (void)hipSetDevice(h->cfg.device);
+  const size_t cnt = (size_t)h->N * h->N * 4;
+  double      *d_cc = nullptr; // the coefficient at the coarse Gauss points, one field after the other
+  hipError_t   e = hipMalloc((void **)&d_cc, (size_t)s * cnt * sizeof(double));
+  if (e != hipSuccess)
+    return slod_hip_fail(h, e, "slod_coarse_fem_solve: sampled coefficient");
+  for (int f = 0; f < s && e == hipSuccess; ++f)
+    {
+      launch_coarse_sample(h, problem, f, d_cc + (size_t)f * cnt, h->stream);
+      e = hipGetLastError();
+    }
+  // fem_solve_grid synchronises the handle's stream before it returns: d_cc is idle when it is freed
+  const int rc = e == hipSuccess ? fem_solve_grid(h, "slod_coarse_fem_solve", h->N, d_cc, s == 2 ? d_cc + cnt : nullptr,
+                                                  d_coarse_rhs, d_coarse_u, rel_tol, max_iterations, rel_residual)
+                                 : slod_hip_fail(h, e, "slod_coarse_fem_solve: k_coarse_sample");
+  if (rc < 0)
+    (void)hipStreamSynchronize(h->stream);
+  (void)hipFree(d_cc);
+  return rc;
+}
+
+int slod_coarse_interpolate(slod_handle *h, const double *d_coarse, double *d_fine, void *hip_stream)
+{
+  if (!h || !d_coarse || !d_fine)
+    return SLOD_ERR_ARGUMENT;
+  if (const int rc = slod_ensure_device(h))
+    return rc;
+  (void)hipSetDevice(h->cfg.device);
+  hipStream_t  st = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  const int   np = h->NE + 1;
+  // up to 8 node rows per block on large grids (with one store per thread the kernel is bound by workgroup
+  // dispatch), but never fewer than 256 blocks per column of blocks: small grids need every CU
+  const int   rows = std::min({np, std::max((np + 7) / 8, 256), 65535});
+  hipLaunchKernelGGL(k_coarse_prolong, dim3((unsigned)((np + 255) / 256), (unsigned)rows), dim3(256), 0, st, h->N,
+                     h->cfg.n_subdivisions, h->cfg.spacedim, d_coarse, d_fine);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_coarse_interpolate");
 }
 
 } // extern "C"

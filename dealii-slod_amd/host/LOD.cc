@@ -303,6 +303,42 @@ namespace slod
           "slod_compute_error_norms");
   }
 
+  // LOD.cc:1103-1237 with f = 1.  The reference solves with SolverDirect; the CG of the fine problem runs on the
+  // coarse grid to the tolerance of the fine solve.
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::assemble_and_solve_coarse_fem_problem()
+  {
+    if (!d_fem_solution)
+      throw std::runtime_error("assemble_and_solve_coarse_fem_problem: assemble_and_solve_fem_problem comes first");
+    const std::size_t N = (std::size_t)1 << par.n_global_refinements, NE = N * par.n_subdivisions;
+    double           *d_coarse_rhs = device_alloc<double>((N + 1) * (N + 1) * spacedim);
+    d_fem_coarse_solution          = device_alloc<double>((N + 1) * (N + 1) * spacedim);
+    d_fem_coarse_interpolated      = device_alloc<double>((NE + 1) * (NE + 1) * spacedim);
+    check(slod_coarse_fem_rhs(handle, nullptr, d_coarse_rhs, nullptr), "slod_coarse_fem_rhs");
+    check(slod_coarse_fem_solve(handle, 0, d_coarse_rhs, d_fem_coarse_solution, fem_rel_tol, fem_max_iterations, nullptr),
+          "slod_coarse_fem_solve");
+    check(slod_coarse_interpolate(handle, d_fem_coarse_solution, d_fem_coarse_interpolated, nullptr),
+          "slod_coarse_interpolate");
+    check(slod_compute_error_norms(handle, 0, d_fem_solution, d_fem_coarse_interpolated, nullptr, nullptr, &femH_fem_error,
+                                   nullptr),
+          "slod_compute_error_norms");
+    check(slod_compute_error_norms(handle, 0, d_fem_solution, nullptr, nullptr, nullptr, &fem_norms, nullptr),
+          "slod_compute_error_norms");
+  }
+
+  template <int dim, int spacedim>
+  std::vector<double> LOD<dim, spacedim>::fem_coarse_solution_interpolated() const
+  {
+    if (!d_fem_coarse_interpolated)
+      throw std::runtime_error("fem_coarse_solution_interpolated: assemble_and_solve_coarse_fem_problem comes first");
+    const std::size_t   NE = ((std::size_t)1 << par.n_global_refinements) * par.n_subdivisions;
+    std::vector<double> v((NE + 1) * (NE + 1) * spacedim);
+    // (a blocking copy on the null stream: ordered after the handle's stream, which slod_compute_error_norms left idle)
+    if (hipMemcpy(v.data(), d_fem_coarse_interpolated, v.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      throw std::runtime_error("fem_coarse_solution_interpolated: download failed");
+    return v;
+  }
+
   template class LOD<2, 1>;
   template class LOD<2, 2>;
 } // namespace slod

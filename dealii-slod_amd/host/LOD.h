@@ -5,7 +5,8 @@
 // the HIP library through the C-ABI of include/slod.h.  The steps of the reference run() after the
 // basis build (assemble_global_matrix, assemble_and_solve_fem_problem, solve, compare_lod_with_fem:
 // LOD.cc:860-1260) are public methods that chain the device entry points; run() stops after the
-// basis build as before.  VTU output and the coarse FEM(H) comparison are not mirrored.
+// basis build as before.  The coarse FEM(H) comparison (LOD.cc:1103-1237) is the public method
+// assemble_and_solve_coarse_fem_problem().  VTU output is not mirrored.
 #ifndef slod_host_lod_h
 #define slod_host_lod_h
 
@@ -113,6 +114,16 @@ namespace slod
     const slod_error_norms &error_LOD_FEMh() const { return lod_fem_error; }
     // the same norms of u_h alone (the denominators of relative errors)
     const slod_error_norms &norms_FEMh() const { return fem_norms; }
+    // The coarse FEM(H) problem with f = 1 (the coarse block of assemble_and_solve_fem_problem, LOD.cc:1103-1237,
+    // which the reference runs for spacedim == 2 only and marks TODO; here for both problem classes), after
+    // assemble_and_solve_fem_problem(): the coefficient at the Gauss points of the coarse cells
+    // (assemble_stiffness_coarse), load vector, solve, FETools::interpolate onto the fine space and
+    // error_FEMH_FEMh.difference(u_h, interpolated) (LOD.cc:1206-1208).
+    void assemble_and_solve_coarse_fem_problem();
+    const slod_error_norms &error_FEMH_FEMh() const { return femH_fem_error; }
+    // fem_coarse_solution_interpolated (LOD.cc:1199-1204) on the fine grid, [(NE+1)^2][spacedim] lexicographic,
+    // component-minor; copied from the device on every call
+    std::vector<double> fem_coarse_solution_interpolated() const;
 
   protected:
     void make_fe();
@@ -146,7 +157,8 @@ namespace slod
     double             *d_basis = nullptr, *d_premult = nullptr, *d_lod_values = nullptr;
     uint32_t           *d_lod_cols = nullptr;
     double             *d_fem_rhs = nullptr, *d_fem_solution = nullptr, *d_lod_u = nullptr;
-    slod_error_norms    lod_fem_error{}, fem_norms{};
+    double             *d_fem_coarse_solution = nullptr, *d_fem_coarse_interpolated = nullptr;
+    slod_error_norms    lod_fem_error{}, fem_norms{}, femH_fem_error{};
 
     void check(const int status, const char *what) const;
     template <typename T>

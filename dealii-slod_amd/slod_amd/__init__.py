@@ -115,6 +115,10 @@ def load():
     lib.slod_lod_reconstruct.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
     lib.slod_fem_rhs.argtypes = [vp, vp, vp, vp]
     lib.slod_fem_solve.argtypes = [vp, C.c_uint32, vp, vp, C.c_double, C.c_int, dp]
+    lib.slod_coarse_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, vp]
+    lib.slod_coarse_fem_rhs.argtypes = [vp, vp, vp, vp]
+    lib.slod_coarse_fem_solve.argtypes = [vp, C.c_uint32, vp, vp, C.c_double, C.c_int, dp]
+    lib.slod_coarse_interpolate.argtypes = [vp, vp, vp, vp]
     lib.slod_compute_error_norms.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, C.POINTER(ErrorNorms), vp]
     lib.slod_device_patch_layout.argtypes = [vp, u32p, C.c_size_t, C.POINTER(PatchInfo)]
     lib.slod_sample_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, C.c_int]
@@ -358,6 +362,27 @@ class Slod:
         if it < 0:
             self._check(it)
         return it, res.value
+
+    # ---- coarse FEM(H) reference problem: Q1 on the N x N coarse mesh (raw device pointers as ints) ----
+    def coarse_coefficient(self, field, d_out, problem=0, stream=None):
+        """Coefficient `field` at the 2 x 2 Gauss points of every coarse cell, d_out [N][N][4]."""
+        self._check(self.lib.slod_coarse_coefficient(self.h, problem, field, d_out, stream))
+
+    def coarse_fem_rhs(self, d_f_cqp, d_coarse_rhs, stream=None):
+        """Coarse FEM load vector [(N+1)^2][s] (d_f_cqp = None: f = 1)."""
+        self._check(self.lib.slod_coarse_fem_rhs(self.h, d_f_cqp, d_coarse_rhs, stream))
+
+    def coarse_fem_solve(self, d_coarse_rhs, d_coarse_u, rel_tol=1e-13, max_iterations=20000, problem=0):
+        res = C.c_double()
+        it = self.lib.slod_coarse_fem_solve(self.h, problem, d_coarse_rhs, d_coarse_u, rel_tol, max_iterations,
+                                            C.byref(res))
+        if it < 0:
+            self._check(it)
+        return it, res.value
+
+    def coarse_interpolate(self, d_coarse, d_fine, stream=None):
+        """Bilinear interpolation of a coarse nodal field [(N+1)^2][s] onto the fine grid [(NE+1)^2][s]."""
+        self._check(self.lib.slod_coarse_interpolate(self.h, d_coarse, d_fine, stream))
 
     def error_norms(self, d_u, d_v=None, d_exact=None, d_exact_grad=None, problem=0, stream=None):
         """Norms of e = u - v - w on the fine grid (slod_compute_error_norms; raw device pointers, None = 0).

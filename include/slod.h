@@ -233,6 +233,46 @@ int slod_fem_rhs(slod_handle *h, const double *d_f_qp, double *d_fine_rhs, void 
 int slod_fem_solve(slod_handle *h, uint32_t problem, const double *d_fine_rhs, double *d_fine_u, double rel_tol,
                    int max_iterations, double *rel_residual);
 
+/* ---- coarse FEM(H) reference problem (the coarse part of assemble_and_solve_fem_problem,
+ * LOD.cc:1103-1237) ----
+ * Q1 on the COARSE mesh (N x N cells, H = 1/N; FE_Q_iso_Q1(1) with QIterated(QGauss(2), 1), the reference's
+ * coarse_fem_subdivisions = 1), the coefficient sampled at the 2 x 2 Gauss points of every coarse cell
+ * (assemble_stiffness_coarse, Diffusion.h:210-305, Elasticity.h:304ff): the baseline with the number of
+ * unknowns of the LOD system and no correctors.  Coarse nodal vectors are [(N+1)^2][s], lexicographic,
+ * component-minor; coarse quadrature data is [N][N][4], q = q0 + 2 q1 at ((Cx + g[q0]) H, (Cy + g[q1]) H):
+ * the layouts of the fine problem with NE -> N.
+ * Common to the four calls: SLOD_ERR_ARGUMENT for a NULL handle or array, a problem or a field (>= spacedim)
+ * out of range, before any device work; SLOD_ERR_DEVICE without a usable GPU; SLOD_ERR_STATE when the
+ * coefficient the call reads has not been set.
+ *
+ * The coefficient of (problem, field) at the coarse Gauss points, DEVICE out [N][N][4]; exposed for parity
+ * tests and callers that assemble their own coarse operator.  The stored fine field [NE][NE][4] is read as
+ * piecewise constant on the quadrants of the fine elements, which is what problem_parameter::value
+ * (Diffusion.h:40-53) gives whenever 2^r <= 2 NE: the point (Cx + g[q0]) H lies in fine element
+ * ex = Cx n + floor(n g[q0]) at local coordinate xi = n g[q0] - floor(n g[q0]) and reads its slot
+ * q0' = (xi >= 1/2); the same in y.  With n_subdivisions = 1 the output is the fine field.  Asynchronous on
+ * hip_stream. */
+int slod_coarse_coefficient(slod_handle *h, uint32_t problem, int field, double *d_out, void *hip_stream);
+/* Coarse load vector (fem_coarse_rhs of assemble_stiffness_coarse, Diffusion.h:210-305) [(N+1)^2][s], zero on
+ * the Dirichlet nodes; d_f_cqp = f at the coarse Gauss points, DEVICE [s][N][N][4], or NULL for f = (1,..,1).
+ * Asynchronous on hip_stream. */
+int slod_coarse_fem_rhs(slod_handle *h, const double *d_f_cqp, double *d_coarse_rhs, void *hip_stream);
+/* FEM(H) solution [(N+1)^2][s] for the coefficient of `problem`, zero on the boundary (the reference:
+ * SolverDirect, LOD.cc:1191-1197; here the solver of slod_fem_solve on the coarse grid: run it to a tight
+ * tolerance).  Returns the iteration count (>= 0) or a negative slod_status, *rel_residual as slod_fem_solve.
+ * Synchronises. */
+int slod_coarse_fem_solve(slod_handle *h, uint32_t problem, const double *d_coarse_rhs, double *d_coarse_u,
+                          double rel_tol, int max_iterations, double *rel_residual);
+/* fem_coarse_solution_interpolated (FETools::interpolate, LOD.cc:1201-1204): bilinear interpolation of a
+ * coarse nodal field onto the fine grid, DEVICE [(NE+1)^2][s]; fine nodes on coarse nodes copy the value bit
+ * for bit.  Asynchronous on hip_stream.
+ * The error tables of the coarse problem need no norm kernel of their own: every fine element lies inside
+ * one coarse cell, so the fine-grid quadrature of slod_compute_error_norms is exact for the interpolated
+ * field.  "FEM(H) vs reference FEM(h)" (LOD.cc:1206-1217,1458-1459) is slod_compute_error_norms(u = fem_h,
+ * v = interpolated), "FEM(H) vs exact solution" (LOD.cc:1450-1451) the same call with u = interpolated and
+ * the exact arrays. */
+int slod_coarse_interpolate(slod_handle *h, const double *d_coarse, double *d_fine, void *hip_stream);
+
 /* ---- error norms on the global fine grid (compare_lod_with_fem, LOD.cc:1240-1260:
  * error_LOD_FEMh.difference and error_LOD_exact.error_from_exact; error_FEMh_exact, LOD.cc:1080-1088;
  * the tables printed at the end of run(), LOD.cc:1425-1466) ----

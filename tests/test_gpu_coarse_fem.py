@@ -1,0 +1,450 @@
+"""GPU tests of the coarse FEM(H) reference problem (the coarse block of assemble_and_solve_fem_problem,
+LOD.cc:1103-1237): Q1 on the coarse mesh with the coefficient at the 2 x 2 Gauss points of every coarse cell
+(assemble_stiffness_coarse), its solve, FETools::interpolate onto the fine space and the tables
+"FEM(H) vs reference FEM(h)" / "FEM(H) vs exact solution" (LOD.cc:1206-1217,1450-1462).
+
+The reference implementation lives in this file and uses numpy only: Q1 assembly on N x N cells from a
+[N][N][4] field and a dense solve of at most 2 * 81 unknowns.
+
+Tolerances:
+  sampling, coincident nodes of the interpolation: bit equality (the kernels only move values).
+  interpolation of a bilinear function: 1e-15 absolute on values <= 7.  The coarse values are multiples of 1/16,
+      so the weighted sum is exact and the one division rounds correctly; the expected value is the correctly
+      rounded exact rational.
+  load vector: 1e-14 relative per entry (16 positive terms per entry, one rounding each, on either side).
+  solve against the dense solve, and coarse against fine at n_sub = 1: FEM_SOLVE_RTOL, the bound
+      tests/test_gpu_lod_system.py puts on slod_fem_solve against scipy's sparse direct solver.
+  convergence rates: the bounds tests/test_gpu_error_norms.py puts on FEM(h) (L2_RATE, H1_RATE)."""
+import os
+import re
+import subprocess
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+from test_gpu_error_norms import _exact_at_qp
+from test_gpu_lod_system import _lod_matrix
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "dealii-slod_amd", "bin", "main_Diffusion")
+
+FEM_SOLVE_RTOL = 1e-8                       # test_fem_solve_matches_sparse_direct: max |u - uref| <= 1e-8 max |uref|
+L2_RATE, H1_RATE = (3.6, 4.4), (1.8, 2.2)   # test_fem_error_against_exact_solution_converges
+G0 = 0.5 * (1.0 - 1.0 / np.sqrt(3.0))
+GP = (G0, 1.0 - G0)
+
+
+def _torch():
+    import torch
+    return torch, torch.device("cuda", 0)
+
+
+def _slod(**kw):
+    import slod_amd
+    return slod_amd.Slod(**kw)
+
+
+def _dev(a):
+    torch, dev = _torch()
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+
+
+def _zeros(n):
+    torch, dev = _torch()
+    return torch.zeros(n, dtype=torch.float64, device=dev)
+
+
+def _gauss_points(M):
+    """x, y of the 2 x 2 Gauss points of an M x M grid of the unit square, arrays [M][M][4], q = q0 + 2 q1."""
+    cy, cx, q = np.meshgrid(np.arange(M), np.arange(M), np.arange(4), indexing="ij")
+    x = (cx + np.where(q & 1, GP[1], GP[0])) / M
+    y = (cy + np.where(q & 2, GP[1], GP[0])) / M
+    return x, y
+
+
+def _table_at(vals, r, x, y):
+    """problem_parameter::value (Diffusion.h:47-51): vals[floor(x / eta) + 2^r floor(y / eta)], eta = 2^-r."""
+    eta = 1.0 / (1 << r)
+    return vals[np.floor(x / eta).astype(np.int64) + (1 << r) * np.floor(y / eta).astype(np.int64)]
+
+
+def _random_table(seed, r, dist):
+    rng = np.random.default_rng(seed)
+    u = rng.uniform(0.0, 1.0, 4 ** r)
+    return 1.0 + 99.0 * u if dist == "D100" else 1.0e4 ** u       # D100: uniform in [1, 100]; D1e4: log-uniform in [1, 1e4]
+
+
+def _sample_tables(g, tables, r):
+    """Coefficient of every field from its table, on the device (slod_sample_coefficient)."""
+    for f, vals in enumerate(tables):
+        g.sample_coefficient(f, _dev(vals).data_ptr(), r)
+
+
+def _coarse_coefficient(g, field):
+    out = _zeros(g.N * g.N * 4)
+    g.coarse_coefficient(field, out.data_ptr())
+    torch, _ = _torch()
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
+# ---- 1. sampling ------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("spacedim", [1, 2])
+@pytest.mark.parametrize("n_sub", [1, 2, 4, 8])
+def test_coarse_coefficient_is_the_table_at_the_coarse_gauss_points(n_sub, spacedim):
+    g = _slod(nref=2, n_sub=n_sub, oversampling=1, spacedim=spacedim)
+    X, Y = _gauss_points(g.N)
+    xf, yf = _gauss_points(g.NE)
+    r_max = int(np.log2(2 * g.NE))
+    assert 1 << r_max == 2 * g.NE
+    for r in range(r_max + 1):
+        tables = [_random_table(100 * r + f, r, "D100") for f in range(spacedim)]
+        _sample_tables(g, tables, r)
+        for f in range(spacedim):
+            got = _coarse_coefficient(g, f)
+            assert np.array_equal(got, _table_at(tables[f], r, X, Y).ravel()), (n_sub, r, f)
+            if n_sub == 1:     # the coarse mesh is the fine mesh: the stored field itself
+                assert np.array_equal(got, _table_at(tables[f], r, xf, yf).ravel())
+
+
+@pytest.mark.parametrize("spacedim", [1, 2])
+@pytest.mark.parametrize("n_sub", [1, 2, 3, 4, 8])
+def test_coarse_coefficient_quadrant_rule(n_sub, spacedim):
+    """A per-qp field whose 4 NE^2 values are all different: the coarse Gauss point (C + g) H reads the
+    fine quadrature slot of the quadrant it lies in (quadrant j = floor(2 n (C + g)) of 2 NE per axis)."""
+    g = _slod(nref=2, n_sub=n_sub, oversampling=1, spacedim=spacedim)
+    NE, N = g.NE, g.N
+    fields = [(1.0 + f * 4 * NE * NE + np.arange(4 * NE * NE, dtype=np.float64)) for f in range(spacedim)]
+    for f in range(spacedim):
+        g.set_coefficient(f, fields[f])
+    X, Y = _gauss_points(N)
+    jx, jy = np.floor(2 * NE * X).astype(np.int64), np.floor(2 * NE * Y).astype(np.int64)
+    for f in range(spacedim):
+        want = fields[f].reshape(NE, NE, 4)[jy // 2, jx // 2, (jx % 2) + 2 * (jy % 2)]
+        got = _coarse_coefficient(g, f)
+        assert np.array_equal(got, want.ravel()), (n_sub, f)
+        if n_sub == 1:
+            assert np.array_equal(got, fields[f])
+
+
+def test_coarse_calls_need_the_coefficient():
+    """SLOD_ERR_STATE for the calls that read the coefficient; the other two do not need it."""
+    import slod_amd
+    g = _slod(nref=2, n_sub=2, oversampling=1, spacedim=2)
+    rhs, u, out = _zeros(25 * 2), _zeros(25 * 2), _zeros(16 * 4)
+    g.coarse_fem_rhs(None, rhs.data_ptr())
+    g.set_coefficient(0, np.ones(8 * 8 * 4))          # lambda alone: mu is still missing
+    g.coarse_coefficient(0, out.data_ptr())
+    with pytest.raises(slod_amd.SlodError) as e:
+        g.coarse_coefficient(1, out.data_ptr())
+    assert e.value.code == -4 and "coefficient not set" in str(e.value)
+    with pytest.raises(slod_amd.SlodError) as e:
+        g.coarse_fem_solve(rhs.data_ptr(), u.data_ptr())
+    assert e.value.code == -4 and "coefficient not set" in str(e.value)
+
+
+# ---- 2. interpolation -------------------------------------------------------------------------------------
+
+BILINEAR = [(1, 1, 2, 3), (2, -1, Fraction(1, 2), 2)]     # a + b x + c y + d x y, one function per component
+
+
+@pytest.mark.parametrize("spacedim", [1, 2])
+@pytest.mark.parametrize("n_sub", [1, 3, 4])
+def test_coarse_interpolate_reproduces_bilinear_functions(n_sub, spacedim):
+    torch, _ = _torch()
+    g = _slod(nref=2, n_sub=n_sub, oversampling=1, spacedim=spacedim)
+    N, NE, s = g.N, g.NE, spacedim
+
+    def nodal(M):      # correctly rounded values at the nodes of an M x M grid, [(M+1)^2][s]
+        v = np.zeros((M + 1, M + 1, s))
+        for iy in range(M + 1):
+            for ix in range(M + 1):
+                x, y = Fraction(ix, M), Fraction(iy, M)
+                for c in range(s):
+                    a, b, cc, d = BILINEAR[c]
+                    v[iy, ix, c] = float(a + b * x + cc * y + d * x * y)
+        return v
+
+    coarse, want = nodal(N), nodal(NE)
+    assert np.abs(want).max() <= 7.0
+    fine = _zeros((NE + 1) ** 2 * s)
+    fine.fill_(-77.0)                                   # every node must be written
+    g.coarse_interpolate(_dev(coarse).data_ptr(), fine.data_ptr())
+    torch.cuda.synchronize()
+    got = fine.cpu().numpy().reshape(NE + 1, NE + 1, s)
+    err = np.abs(got - want).max()
+    print("n_sub %d, s %d: max |interpolant - function| = %.3e" % (n_sub, s, err))
+    assert err <= 1e-15
+    assert np.array_equal(got[::n_sub, ::n_sub], coarse)
+
+
+def test_coarse_interpolate_copies_coarse_nodes_bit_for_bit():
+    """Random values (not exactly representable weights, signed zeros): the fine nodes on coarse nodes carry the
+    input bits; every other node lies between its neighbours on the coarse edge or cell."""
+    torch, _ = _torch()
+    for n_sub, s in ((3, 1), (3, 2), (5, 2)):
+        g = _slod(nref=2, n_sub=n_sub, oversampling=1, spacedim=s)
+        N, NE = g.N, g.NE
+        rng = np.random.default_rng(5 + n_sub + s)
+        coarse = rng.uniform(-1.0, 1.0, (N + 1, N + 1, s)) / 3.0
+        coarse[1, 1, 0] = -0.0
+        fine = _zeros((NE + 1) ** 2 * s)
+        g.coarse_interpolate(_dev(coarse).data_ptr(), fine.data_ptr())
+        torch.cuda.synchronize()
+        got = fine.cpu().numpy().reshape(NE + 1, NE + 1, s)
+        assert got[::n_sub, ::n_sub].tobytes() == coarse.tobytes()
+        # against the same formula in numpy: a few roundings
+        t = np.arange(NE + 1) / n_sub
+        c0 = np.minimum(np.floor(t).astype(int), N - 1)
+        w = t - c0
+        wx, wy = w[None, :, None], w[:, None, None]
+        cy, cx = c0[:, None], c0[None, :]
+        want = ((1 - wx) * (1 - wy) * coarse[cy, cx] + wx * (1 - wy) * coarse[cy, cx + 1] +
+                (1 - wx) * wy * coarse[cy + 1, cx] + wx * wy * coarse[cy + 1, cx + 1])
+        assert np.abs(got - want).max() <= 8 * np.finfo(float).eps
+
+
+# ---- 3. solve against dense numpy -------------------------------------------------------------------------
+
+def _element_matrix(s, co):
+    """Q1 stiffness of one square cell (scale-free in 2-D) from the coefficient at its 4 Gauss points:
+    int alpha grad u . grad v (s = 1), int 2 mu eps(u):eps(v) + lambda div u div v (s = 2; co = (lambda, mu))."""
+    K = np.zeros((4 * s, 4 * s))
+    for q in range(4):
+        xi, eta = GP[q & 1], GP[q >> 1]
+        gx = np.array([-(1 - eta), 1 - eta, -eta, eta])
+        gy = np.array([-(1 - xi), -xi, 1 - xi, xi])
+        grad = np.stack([gx, gy])                            # [direction][corner]
+        if s == 1:
+            K += 0.25 * co[0][q] * (np.outer(gx, gx) + np.outer(gy, gy))
+            continue
+        lam, mu = co[0][q], co[1][q]
+        B = np.zeros((3, 8))                                 # (eps_xx, eps_yy, 2 eps_xy) of dof (corner, component)
+        for a in range(4):
+            B[0, 2 * a], B[1, 2 * a + 1] = grad[0, a], grad[1, a]
+            B[2, 2 * a], B[2, 2 * a + 1] = grad[1, a], grad[0, a]
+        D = np.array([[lam + 2 * mu, lam, 0.0], [lam, lam + 2 * mu, 0.0], [0.0, 0.0, mu]])
+        K += 0.25 * B.T @ D @ B
+    return K
+
+
+def _coarse_reference(N, s, cfields, fq=None):
+    """Dense coarse stiffness and load vector on N x N cells; returns (A_II, f_I, interior dof indices)."""
+    Np, H = N + 1, 1.0 / N
+    A = np.zeros((Np * Np * s, Np * Np * s))
+    f = np.zeros(Np * Np * s)
+    for cy in range(N):
+        for cx in range(N):
+            ge = (cy * N + cx) * 4
+            K = _element_matrix(s, [fld[ge:ge + 4] for fld in cfields])
+            nodes = [cx + cy * Np, cx + 1 + cy * Np, cx + (cy + 1) * Np, cx + 1 + (cy + 1) * Np]
+            dofs = [nd * s + c for nd in nodes for c in range(s)]
+            A[np.ix_(dofs, dofs)] += K
+            for a, nd in enumerate(nodes):
+                for q in range(4):
+                    xi, eta = GP[q & 1], GP[q >> 1]
+                    Na = (xi if a & 1 else 1 - xi) * (eta if a & 2 else 1 - eta)
+                    for c in range(s):
+                        f[nd * s + c] += Na * (1.0 if fq is None else fq[c * N * N * 4 + ge + q]) * H * H * 0.25
+    ix, iy = np.meshgrid(np.arange(Np), np.arange(Np))
+    interior = ((ix > 0) & (ix < N) & (iy > 0) & (iy < N)).ravel()
+    idx = np.nonzero(np.repeat(interior, s))[0]
+    return A[np.ix_(idx, idx)], f[idx], idx
+
+
+@pytest.mark.parametrize("nref,spacedim,dist", [(2, 1, "D100"), (3, 1, "D100"), (2, 1, "D1e4"), (3, 1, "D1e4"),
+                                                (2, 2, "D100"), (3, 2, "D100")])
+def test_coarse_fem_matches_dense_numpy(nref, spacedim, dist):
+    torch, _ = _torch()
+    s, r = spacedim, 5
+    g = _slod(nref=nref, n_sub=4, oversampling=1, spacedim=s)
+    N, nn = g.N, (g.N + 1) ** 2
+    tables = [_random_table(20250614 + f, r, dist) for f in range(s)]
+    _sample_tables(g, tables, r)
+    X, Y = _gauss_points(N)
+    cfields = [_table_at(t, r, X, Y).ravel() for t in tables]      # independent of k_coarse_sample
+    bnd = np.ones(nn * s, bool)
+    # load vector: f = 1, and a given positive f at the coarse Gauss points
+    rhs = _zeros(nn * s)
+    fq = np.random.default_rng(3).uniform(0.5, 2.0, s * N * N * 4)
+    for given in (fq, None):
+        rhs.fill_(-77.0)
+        g.coarse_fem_rhs(None if given is None else _dev(given).data_ptr(), rhs.data_ptr())
+        torch.cuda.synchronize()
+        A, fref, idx = _coarse_reference(N, s, cfields, given)
+        hr = rhs.cpu().numpy()
+        bnd[:] = True
+        bnd[idx] = False
+        np.testing.assert_allclose(hr[idx], fref, rtol=1e-14, atol=0)
+        assert np.all(hr[bnd] == 0.0)
+    # the solve with f = 1 (rhs, A, fref, idx are those of the last pass)
+    u = _zeros(nn * s)
+    u.fill_(-77.0)
+    it, res = g.coarse_fem_solve(rhs.data_ptr(), u.data_ptr(), 1e-13, 20000)
+    assert 0 < it < 20000 and res <= 1e-12, (it, res)
+    uref = np.linalg.solve(A, fref)
+    hu = u.cpu().numpy()
+    err = np.abs(hu[idx] - uref).max() / np.abs(uref).max()
+    print("N %d, s %d, %s: %d iterations, relative residual %.2e, max-norm deviation from the dense solve %.2e"
+          % (N, s, dist, it, res, err))
+    assert err <= FEM_SOLVE_RTOL
+    assert np.all(hu[bnd] == 0.0)
+
+
+# ---- 4. consistency with the fine solve -------------------------------------------------------------------
+
+def test_coarse_problem_is_the_fine_problem_for_one_subdivision():
+    torch, _ = _torch()
+    g = _slod(nref=3, n_sub=1, oversampling=1, spacedim=1)
+    r = 4                                                  # 2^r = 2 NE: a value per quadrant
+    _sample_tables(g, [_random_table(7, r, "D1e4")], r)
+    nn = (g.N + 1) ** 2
+    rhs_c, rhs_f, u_c, u_f = _zeros(nn), _zeros(nn), _zeros(nn), _zeros(nn)
+    g.coarse_fem_rhs(None, rhs_c.data_ptr())
+    g.fem_rhs(None, rhs_f.data_ptr())
+    torch.cuda.synchronize()
+    assert torch.equal(rhs_c, rhs_f)
+    it_c, res_c = g.coarse_fem_solve(rhs_c.data_ptr(), u_c.data_ptr(), 1e-13, 20000)
+    it_f, res_f = g.fem_solve(rhs_f.data_ptr(), u_f.data_ptr(), 1e-13, 20000)
+    assert res_c <= 1e-12 and res_f <= 1e-12
+    assert float((u_c - u_f).abs().max()) <= FEM_SOLVE_RTOL * float(u_f.abs().max())
+    back = _zeros(nn)
+    g.coarse_interpolate(u_c.data_ptr(), back.data_ptr())
+    torch.cuda.synchronize()
+    assert back.cpu().numpy().tobytes() == u_c.cpu().numpy().tobytes()
+
+
+# ---- 5. convergence ---------------------------------------------------------------------------------------
+
+def test_coarse_fem_error_against_exact_solution_converges():
+    """error_FEMH_exact (LOD.cc:1214-1216): alpha = 1, u = sin(pi x) sin(pi y), f = 2 pi^2 u at the coarse Gauss
+    points.  FEM(H) at N = 4, 8, 16 (n_sub = 2), measured on the fine grid: L2 falls as H^2, the H1 seminorm as H."""
+    torch, _ = _torch()
+    errs = []
+    for nref in (2, 3, 4):
+        g = _slod(nref=nref, n_sub=2, oversampling=1, spacedim=1)
+        g.set_coefficient(0, np.ones(g.NE * g.NE * 4))
+        _, _, f_c = _exact_at_qp(g.N)
+        w, wg, _ = _exact_at_qp(g.NE)
+        nc, nf = (g.N + 1) ** 2, (g.NE + 1) ** 2
+        rhs, uH, uHh = _zeros(nc), _zeros(nc), _zeros(nf)
+        g.coarse_fem_rhs(_dev(f_c).data_ptr(), rhs.data_ptr())
+        it, res = g.coarse_fem_solve(rhs.data_ptr(), uH.data_ptr(), 1e-13, 20000)
+        assert res <= 1e-12
+        g.coarse_interpolate(uH.data_ptr(), uHh.data_ptr())
+        dw, dwg = _dev(w), _dev(wg)
+        errs.append(g.error_norms(uHh.data_ptr(), None, dw.data_ptr(), dwg.data_ptr()))
+    print("u_H - u: L2 %s, H1-semi %s" % (["%.3e" % e["l2"] for e in errs], ["%.3e" % e["h1_semi"] for e in errs]))
+    for a, b in zip(errs[:-1], errs[1:]):
+        assert L2_RATE[0] <= a["l2"] / b["l2"] <= L2_RATE[1], [e["l2"] for e in errs]
+        assert H1_RATE[0] <= a["h1_semi"] / b["h1_semi"] <= H1_RATE[1], [e["h1_semi"] for e in errs]
+
+
+# ---- 6. the comparison the feature exists for -------------------------------------------------------------
+
+def _fem_h_and_fem_H(g):
+    """f = 1: (fine FEM solution, interpolated coarse FEM solution, fine load vector), device tensors."""
+    s = g.spacedim
+    nc, nf = (g.N + 1) ** 2 * s, (g.NE + 1) ** 2 * s
+    f, ufem = _zeros(nf), _zeros(nf)
+    g.fem_rhs(None, f.data_ptr())
+    g.fem_solve(f.data_ptr(), ufem.data_ptr(), 1e-12, 50000)
+    rhs, uH, uHh = _zeros(nc), _zeros(nc), _zeros(nf)
+    g.coarse_fem_rhs(None, rhs.data_ptr())
+    g.coarse_fem_solve(rhs.data_ptr(), uH.data_ptr(), 1e-12, 50000)
+    g.coarse_interpolate(uH.data_ptr(), uHh.data_ptr())
+    return ufem, uHh, f
+
+
+def _slod_solution(g, f):
+    """u_LOD = C u_H of the reference run() after the basis build, on the fine grid."""
+    torch, dev = _torch()
+    s = g.spacedim
+    ids = np.arange(g.num_patches, dtype=np.uint32)
+    plan = g.plan(ids)
+    stride = plan.stride
+    b = _zeros(len(ids) * stride)
+    q = torch.zeros_like(b)
+    plan.execute(b.data_ptr(), q.data_ptr())
+    plan.status()
+    values, cols = _lod_matrix(g, b, q, stride, s)
+    rhs = _zeros(g.num_patches * s)
+    g.lod_rhs(ids, b.data_ptr(), stride, f.data_ptr(), rhs.data_ptr())
+    uH = torch.zeros_like(rhs)
+    g.lod_solve(values.data_ptr(), cols.data_ptr(), rhs.data_ptr(), uH.data_ptr(), 1e-13, 5000)
+    ulod = torch.zeros_like(f)
+    g.lod_reconstruct(b.data_ptr(), stride, uH.data_ptr(), ulod.data_ptr())
+    return ulod
+
+
+def test_coarse_fem_is_worse_than_slod_on_a_rough_coefficient():
+    """N = 8, n_sub = 4, l = 2, SLOD, contrast 1e4 on the fine scale (r = 5: eta = h), f = 1: with the same number
+    of unknowns the error of FEM(H) against FEM(h) is strictly larger than that of the SLOD solution, in the
+    energy norm and in L2."""
+    g = _slod(nref=3, n_sub=4, oversampling=2, spacedim=1, stabilize=1)
+    _sample_tables(g, [_random_table(20250614, 5, "D1e4")], 5)
+    ufem, uHh, f = _fem_h_and_fem_H(g)
+    ulod = _slod_solution(g, f)
+    ref = g.error_norms(ufem.data_ptr())
+    eH = g.error_norms(ufem.data_ptr(), uHh.data_ptr())
+    eL = g.error_norms(ufem.data_ptr(), ulod.data_ptr())
+    print("against FEM(h), relative (L2, energy): FEM(H) (%.6e, %.6e), SLOD (%.6e, %.6e)"
+          % (eH["l2"] / ref["l2"], eH["energy"] / ref["energy"], eL["l2"] / ref["l2"], eL["energy"] / ref["energy"]))
+    assert eH["energy"] > eL["energy"]
+    assert eH["l2"] > eL["l2"]
+
+
+# ---- 7. driver --------------------------------------------------------------------------------------------
+
+def _tables_of(stdout):
+    """{title: {L2, H1, Linfty, energy}} of the error tables in the order they are printed."""
+    out, title = [], None
+    for ln in stdout.splitlines():
+        m = re.match(r"^\s*(L2|H1|Linfty|energy)\s+error = (\S+)", ln)
+        if m and title is not None:
+            out[-1][1][m.group(1)] = float(m.group(2))
+        elif ln.endswith("vs reference FEM(h)"):
+            title = ln.strip()
+            out.append((title, {}))
+    return out
+
+
+def test_host_mirror_coarse_table_matches_python_path(so):
+    """bin/main_Diffusion 3 4 --coarse 2 1: the FEM(H) table comes first and carries the numbers of the Python
+    path on the same Alpha(1, 100, 3), srand(1); the SLOD table still comes last; --compare and the plain run
+    print what they printed before."""
+    if not os.path.exists(BIN):
+        subprocess.check_call(["make", "-C", os.path.join(ROOT, "dealii-slod_amd"), "bin/main_Diffusion"])
+    run = lambda *a: subprocess.run([BIN, *a], capture_output=True, text=True, timeout=300)
+    coarse, compare, plain = run("3", "4", "--coarse", "2", "1"), run("3", "4", "--compare", "2", "1"), run("3", "4", "2", "1")
+    for r in (coarse, compare, plain):
+        assert r.returncode == 0, r.stderr
+    tc, tp = _tables_of(coarse.stdout), _tables_of(compare.stdout)
+    assert [t for t, _ in tc] == ["FEM(H) vs reference FEM(h)", "SLOD vs reference FEM(h)"], coarse.stdout
+    assert [t for t, _ in tp] == ["SLOD vs reference FEM(h)"], compare.stdout
+    assert "vs reference" not in plain.stdout and "FEM(H)" not in compare.stdout
+    for t in tc + tp:
+        assert set(t[1]) == {"L2", "H1", "Linfty", "energy"}, t
+    # what test_gpu_error_norms.py reads (the last lines of each name) is still the SLOD table
+    last = {k: float(v) for k, v in re.findall(r"^\s*(L2|H1|Linfty|energy)\s+error = (\S+)", coarse.stdout, re.M)}
+    assert last == tc[1][1]
+    for k, v in tp[0][1].items():
+        assert tc[1][1][k] == pytest.approx(v, rel=1e-9), k
+    # the lines before the tables are unchanged (the build time apart)
+    head = lambda r: [ln for ln in r.stdout.splitlines() if not ln.startswith("basis build time")][:3]
+    assert head(coarse) == head(compare) == head(plain)
+    assert head(plain)[2].startswith("basis digest")
+    n_plain = len(plain.stdout.splitlines())
+    assert len(compare.stdout.splitlines()) == n_plain + 5 and len(coarse.stdout.splitlines()) == n_plain + 10
+    # the Python path
+    g = _slod(nref=3, n_sub=4, oversampling=2, spacedim=1, stabilize=1)
+    g.set_coefficient(0, so.fill_coefficient_rand(1.0, 100.0, 3, g.NE, seed=1))
+    ufem, uHh, _ = _fem_h_and_fem_H(g)
+    e = g.error_norms(ufem.data_ptr(), uHh.data_ptr())
+    printed = tc[0][1]
+    for k, key in (("L2", "l2"), ("H1", "h1"), ("Linfty", "linf"), ("energy", "energy")):
+        assert printed[k] == pytest.approx(e[key], rel=1e-9), k
