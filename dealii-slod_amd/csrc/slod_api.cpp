@@ -27,6 +27,23 @@ std::string &slod_create_error()
   return e;
 }
 
+struct slod_plan;
+
+// Device state of one execute in flight: the workspace of a chunk of patches and the status word.
+// slod_plan_set_overlap(2) gives a plan a second one.
+struct PlanWorkspace
+{
+  double  *st = nullptr, *v = nullptr, *x = nullptr;
+  double  *x_alloc = nullptr; // x sits `guard` doubles inside this allocation
+  double  *z = nullptr;       // k_solve_tw: Z of the forward sweep (active column prefix per line)
+  double  *m = nullptr;       // [chunk][nc_max^2]: nothing but the clock stamps of the diag build, then
+                              // [chunk][nc_max^2 + 1]: k_solve_tw's M + flag
+  int32_t *status = nullptr;
+  // all of it for p.chunk patches, zero-filled where the kernels need it, or nothing (and the HIP error)
+  hipError_t allocate(const slod_plan &p, bool own_z);
+  void       release();
+};
+
 struct slod_plan
 {
   slod_handle               *h = nullptr;
@@ -38,13 +55,9 @@ struct slod_plan
   int                        nb_buf = 0; // rows of k_select's boundary-trace buffer
   size_t                     stride = 0, out_size = 0;
   size_t                     chunk = 0;
-  double                    *ws_st = nullptr, *ws_v = nullptr, *ws_x = nullptr;
-  double                    *ws_m = nullptr; // [chunk][nc_max^2] diag stamps / k_solve_ws's M, then [chunk][nc_max^2 + 1] k_solve_tw's M + flag
-  double                    *ws_z = nullptr; // k_solve_tw: Z of the forward sweep (active column prefix per line)
-  double                    *ws_x_alloc = nullptr; // ws_x sits `guard` doubles inside this allocation
+  PlanWorkspace              ws[2]; // [1]: slod_plan_set_overlap(2)
   size_t                     guard = 0;
   size_t                     st_stride = 0, v_stride = 0, x_stride = 0;
-  int32_t                   *d_status = nullptr;
   SlodPatchDiag             *d_pdiag  = nullptr; // [n][spacedim] decisions of the selection stage
   SlodSolveChoice            choice;             // kernel chosen at plan creation (slod_dispatch.cpp)
   std::vector<hipEvent_t>    ev; // [depth][n_chunks][4]
@@ -52,12 +65,7 @@ struct slod_plan
   int                        depth = 1; // event slots (slod_plan_profile)
   size_t                     n_exec = 0;
   bool                       ran = false;
-  // slod_plan_set_overlap(2): a second workspace and two internal streams, consecutive executes alternate
-  struct AltWs
-  {
-    double  *ws_st = nullptr, *ws_v = nullptr, *ws_x_alloc = nullptr, *ws_x = nullptr, *ws_z = nullptr, *ws_m = nullptr;
-    int32_t *d_status = nullptr;
-  } alt;
+  // slod_plan_set_overlap(2): the second workspace and two internal streams, consecutive executes alternate
   int         overlap = 1;
   hipStream_t istream[2] = {nullptr, nullptr};
   hipEvent_t  fork_ev = nullptr, done_ev[2] = {nullptr, nullptr};
@@ -66,8 +74,71 @@ struct slod_plan
   std::vector<char>          prob_used;             // [n_problems] coefficient realisations the plan reads
 };
 
+hipError_t PlanWorkspace::allocate(const slod_plan &p, bool own_z)
+{
+  // Guards: the kernels read the banded neighbours of a row / node without range tests (the
+  // matching band coefficient is zero, or the result is dropped), so up to a few rows before the
+  // first and after the last slot are touched.  X is zero-filled once: a skipped product must meet
+  // a finite number.
+  const size_t st_bytes = (p.chunk * p.st_stride + (size_t)4 * p.nn_max) * sizeof(double);
+  const size_t v_bytes  = std::max<size_t>(1, p.chunk * p.v_stride) * sizeof(double);
+  const size_t x_bytes  = (p.chunk * p.x_stride + 2 * p.guard) * sizeof(double);
+  const size_t z_bytes  = (p.chunk * p.x_stride + p.guard) * sizeof(double);
+  const size_t m_bytes  = p.chunk * (2 * (size_t)p.nc_max * p.nc_max + 1) * sizeof(double);
+  hipError_t   e        = hipMalloc((void **)&st, st_bytes);
+  if (e == hipSuccess)
+    e = hipMalloc((void **)&v, v_bytes);
+  if (e == hipSuccess)
+    e = hipMalloc((void **)&x_alloc, x_bytes);
+  if (e == hipSuccess && own_z)
+    e = hipMalloc((void **)&z, z_bytes);
+  if (e == hipSuccess)
+    e = hipMalloc((void **)&m, m_bytes);
+  if (e == hipSuccess)
+    e = hipMalloc((void **)&status, sizeof(int32_t));
+  if (e == hipSuccess)
+    e = hipMemset(st, 0, st_bytes);
+  if (e == hipSuccess)
+    e = hipMemset(x_alloc, 0, x_bytes);
+  if (e == hipSuccess && own_z)
+    e = hipMemset(z, 0, z_bytes);
+  if (e == hipSuccess)
+    e = hipMemset(status, 0, sizeof(int32_t));
+  if (e == hipSuccess)
+    x = x_alloc + p.guard;
+  else
+    release();
+  return e;
+}
+
+void PlanWorkspace::release()
+{
+  for (void *q : {(void *)st, (void *)v, (void *)x_alloc, (void *)z, (void *)m, (void *)status})
+    if (q)
+      (void)hipFree(q);
+  *this = PlanWorkspace();
+}
+
 namespace
 {
+  // what slod_plan_set_overlap(2) adds to a plan: all of it exists, or none
+  void release_overlap(slod_plan *p)
+  {
+    p->ws[1].release();
+    for (int k = 0; k < 2; ++k)
+      {
+        if (p->istream[k])
+          (void)hipStreamDestroy(p->istream[k]);
+        if (p->done_ev[k])
+          (void)hipEventDestroy(p->done_ev[k]);
+        p->istream[k] = nullptr;
+        p->done_ev[k] = nullptr;
+      }
+    if (p->fork_ev)
+      (void)hipEventDestroy(p->fork_ev);
+    p->fork_ev = nullptr;
+  }
+
   int fail(const slod_handle *h, int code, const std::string &msg) { return slod_fail(h, code, msg); }
   int hip_fail(const slod_handle *h, hipError_t e, const char *what) { return slod_hip_fail(h, e, what); }
 
@@ -151,43 +222,42 @@ namespace
 
 int slod_ensure_device(slod_handle *h)
 {
-  {
-    if (h->device_ready)
-      return SLOD_OK;
-    hipError_t e = hipSetDevice(h->cfg.device);
-    if (e != hipSuccess)
-      return hip_fail(h, e, "hipSetDevice (no usable HIP device; this library has no CPU fallback)");
-    hipStream_t  stream = nullptr;
-    double      *coef[2] = {nullptr, nullptr};
-    e = hipStreamCreate(&stream);
-    if (e != hipSuccess)
-      return hip_fail(h, e, "hipStreamCreate");
-    const size_t bytes = (size_t)h->cfg.n_problems * h->NE * h->NE * 4 * sizeof(double);
-    for (int f = 0; f < h->cfg.spacedim && e == hipSuccess; ++f)
-      e = hipMalloc((void **)&coef[f], bytes);
-    if (e != hipSuccess)
-      {
-        // nothing half-initialised is kept: the next call starts from scratch
-        for (int f = 0; f < 2; ++f)
-          if (coef[f])
-            (void)hipFree(coef[f]);
-        (void)hipStreamDestroy(stream);
-        return hip_fail(h, e, "hipMalloc(coefficient field)");
-      }
-    h->stream       = stream;
-    h->d_coef[0]    = coef[0];
-    h->d_coef[1]    = coef[1];
-    h->device_ready = true;
+  if (h->device_ready)
     return SLOD_OK;
-  }
+  hipError_t e = hipSetDevice(h->cfg.device);
+  if (e != hipSuccess)
+    return hip_fail(h, e, "hipSetDevice (no usable HIP device; this library has no CPU fallback)");
+  hipStream_t  stream = nullptr;
+  double      *coef[2] = {nullptr, nullptr};
+  e = hipStreamCreate(&stream);
+  if (e != hipSuccess)
+    return hip_fail(h, e, "hipStreamCreate");
+  const size_t bytes = (size_t)h->cfg.n_problems * h->NE * h->NE * 4 * sizeof(double);
+  for (int f = 0; f < h->cfg.spacedim && e == hipSuccess; ++f)
+    e = hipMalloc((void **)&coef[f], bytes);
+  if (e != hipSuccess)
+    {
+      // nothing half-initialised is kept: the next call starts from scratch
+      for (int f = 0; f < 2; ++f)
+        if (coef[f])
+          (void)hipFree(coef[f]);
+      (void)hipStreamDestroy(stream);
+      return hip_fail(h, e, "hipMalloc(coefficient field)");
+    }
+  h->stream       = stream;
+  h->d_coef[0]    = coef[0];
+  h->d_coef[1]    = coef[1];
+  h->device_ready = true;
+  return SLOD_OK;
 }
 
 namespace
 {
   SlodKernelArgs make_args(const slod_plan *p, size_t first, double *d_basis, double *d_premult, bool balanced, int slot = 0)
   {
-    const slod_handle *h = p->h;
-    SlodKernelArgs     a;
+    const slod_handle   *h = p->h;
+    const PlanWorkspace &w = p->ws[slot];
+    SlodKernelArgs       a;
     std::memset(&a, 0, sizeof(a));
     a.desc        = (balanced && p->d_desc_bal ? p->d_desc_bal : p->d_desc) + first;
     a.coef0       = h->d_coef[0];
@@ -203,20 +273,19 @@ namespace
     const double H = 1.0 / (double)h->N, hh = H / (double)h->cfg.n_subdivisions;
     a.scale     = hh * hh / 4.0; // LOD.cc:341
     a.invH2     = 1.0 / (H * H); // LOD.cc:551
-    a.st        = p->ws_st;
+    a.st        = w.st;
     a.st_stride = p->st_stride;
     a.nn_max    = p->nn_max;
-    a.vinv      = p->ws_v;
+    a.vinv      = w.v;
     a.v_stride  = p->v_stride;
     a.m_max     = p->m_max;
     a.L_max     = p->L_max;
-    a.xs        = p->ws_x;
-    a.zs        = p->ws_z ? p->ws_z : p->ws_x;
+    a.xs        = w.x;
+    a.zs        = w.z ? w.z : w.x;
     a.x_stride  = p->x_stride;
     a.nc_max    = p->nc_max;
-    a.ms        = p->ws_m;
-    a.mt        = p->ws_m + p->chunk * (size_t)p->nc_max * p->nc_max; // behind the stamps: [chunk][nc_max^2 + 1]
-    a.m_fused   = 0; // set by slod_launch_solve when the wave-specialised kernel runs
+    a.ms        = w.m;
+    a.mt        = w.m + p->chunk * (size_t)p->nc_max * p->nc_max; // behind the stamps: [chunk][nc_max^2 + 1]
     a.m_tw      = 0;
     a.nb_buf    = p->nb_buf;
     a.nf_max    = p->nf_max;
@@ -224,18 +293,8 @@ namespace
     a.fuse_assemble = 0;
     a.basis     = d_basis;
     a.premult   = d_premult;
-    a.status    = p->d_status;
+    a.status    = w.status;
     a.pdiag     = p->d_pdiag;
-    if (slot == 1)
-      {
-        a.st     = p->alt.ws_st;
-        a.vinv   = p->alt.ws_v;
-        a.xs     = p->alt.ws_x;
-        a.zs     = p->alt.ws_z ? p->alt.ws_z : p->alt.ws_x;
-        a.ms     = p->alt.ws_m;
-        a.mt     = p->alt.ws_m + p->chunk * (size_t)p->nc_max * p->nc_max;
-        a.status = p->alt.d_status;
-      }
     return a;
   }
 } // namespace
@@ -255,7 +314,7 @@ namespace
     if (e == hipSuccess && ev)
       e = hipEventRecord(ev[1], st);
     if (e == hipSuccess)
-      e = slod_launch_solve(s, p->choice, a, cnt, st); // sets a.m_fused, a.fuse_select, a.fuse_assemble
+      e = slod_launch_solve(s, p->choice, a, cnt, st); // sets a.fuse_select, a.fuse_assemble
     if (e == hipSuccess && ev)
       e = hipEventRecord(ev[2], st);
     if (e == hipSuccess && !a.fuse_select)
@@ -481,10 +540,10 @@ int slod_plan_create(slod_handle *h, const uint32_t *gids, size_t n, const uint6
   if (const int rc = ensure_device(h))
     return rc;
   (void)hipSetDevice(h->cfg.device);
-  const uint64_t total = (uint64_t)h->NP * (uint64_t)h->cfg.n_problems;
-  slod_plan     *p     = new slod_plan;
-  p->h                 = h;
-  p->n                 = n;
+  const SlodTuning tuning = slod_read_tuning();
+  slod_plan       *p      = new slod_plan;
+  p->h                    = h;
+  p->n                    = n;
   const int s = h->cfg.spacedim, n_sub = h->cfg.n_subdivisions, full = 2 * h->cfg.oversampling + 1;
   // uniform stride = the full patch's s vectors of n_fine (what an all-gather slab uses)
   p->stride         = (size_t)s * s * (size_t)(n_sub * full + 1) * (size_t)(n_sub * full + 1);
@@ -499,11 +558,10 @@ int slod_plan_create(slod_handle *h, const uint32_t *gids, size_t n, const uint6
   // check, the realisations in use and the balanced launch order (k_balance_order): no per-patch work
   // on the host.  The host copy p->desc is one bulk read-back for the entry points that hand out
   // per-patch data (slod_compute_basis, slod_plan_patch_layout).
-  (void)total;
   int n_cu = 256;
   (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
   n_cu               = std::max(n_cu, 1);
-  const bool balance = slod_read_tuning().balance && n > 1 && n <= 65536;
+  const bool balance = tuning.balance && n > 1 && n <= 65536;
   bool       ok      = hipMalloc((void **)&p->d_desc, n * sizeof(SlodPatchDesc)) == hipSuccess;
   if (ok && balance)
     ok = hipMalloc((void **)&p->d_desc_bal, n * sizeof(SlodPatchDesc)) == hipSuccess;
@@ -565,7 +623,7 @@ int slod_plan_create(slod_handle *h, const uint32_t *gids, size_t n, const uint6
       slod_plan_destroy(p);
       return fail(h, SLOD_ERR_UNSUPPORTED, "slod_plan_create: boundary-trace buffer beyond the selection kernel's 160 rows");
     }
-  if (!slod_choose_solver(s, n_sub, p->m_max, p->L_max, p->nc_max, p->nb_buf, p->nf_max, n, slod_read_tuning(), &p->choice))
+  if (!slod_choose_solver(s, n_sub, p->m_max, p->L_max, p->nc_max, p->nb_buf, p->nf_max, n, tuning, &p->choice))
     {
       slod_plan_destroy(p);
       return fail(h, SLOD_ERR_UNSUPPORTED, "slod_plan_create: patch does not fit the 160 KB LDS of any solver kernel");
@@ -595,54 +653,25 @@ int slod_plan_create(slod_handle *h, const uint32_t *gids, size_t n, const uint6
   if (const char *env = std::getenv("SLOD_WORKSPACE_MB"))
     budget_mb = (size_t)std::max(1L, std::atol(env));
   p->chunk = std::max<size_t>(1, std::min<size_t>(n, budget_mb * 1024 * 1024 / per_patch));
-  ok = true;
-  // Guards: the kernels read the banded neighbours of a row / node without range tests (the
-  // matching band coefficient is zero, or the result is dropped), so up to a few rows before the
-  // first and after the last slot are touched.  X is zero-filled once: a skipped product must meet
-  // a finite number.
-  p->guard = (size_t)24 * p->nc_max + 64;
-  const size_t st_slack = (size_t)4 * p->nn_max;
-  auto free_ws = [&]() {
-    for (double **q : {&p->ws_st, &p->ws_v, &p->ws_x_alloc, &p->ws_z, &p->ws_m})
-      if (*q)
-        {
-          (void)hipFree(*q);
-          *q = nullptr;
-        }
-    p->ws_x = nullptr;
-  };
-  for (;;)
+  p->guard = (size_t)24 * p->nc_max + 64; // see PlanWorkspace::allocate
+  hipError_t we;
+  while ((we = p->ws[0].allocate(*p, own_z)) != hipSuccess && p->chunk > 1)
     {
-      bool w = ok;
-      w      = w && hipMalloc((void **)&p->ws_st, (p->chunk * p->st_stride + st_slack) * sizeof(double)) == hipSuccess;
-      w      = w && hipMalloc((void **)&p->ws_v, std::max<size_t>(1, p->chunk * p->v_stride) * sizeof(double)) == hipSuccess;
-      w      = w && hipMalloc((void **)&p->ws_x_alloc, (p->chunk * p->x_stride + 2 * p->guard) * sizeof(double)) == hipSuccess;
-      if (own_z)
-        w = w && hipMalloc((void **)&p->ws_z, (p->chunk * p->x_stride + p->guard) * sizeof(double)) == hipSuccess;
-      w = w && hipMalloc((void **)&p->ws_m, p->chunk * (2 * (size_t)p->nc_max * p->nc_max + 1) * sizeof(double)) == hipSuccess;
-      if (w || !ok || p->chunk == 1)
-        {
-          ok = w;
-          break;
-        }
       (void)hipGetLastError(); // out of memory: clear it, halve the chunk, try again
-      free_ws();
       p->chunk = (p->chunk + 1) / 2;
     }
-  ok      = ok && hipMemset(p->ws_st, 0, (p->chunk * p->st_stride + st_slack) * sizeof(double)) == hipSuccess;
-  ok      = ok && hipMemset(p->ws_x_alloc, 0, (p->chunk * p->x_stride + 2 * p->guard) * sizeof(double)) == hipSuccess;
-  p->ws_x = p->ws_x_alloc ? p->ws_x_alloc + p->guard : nullptr;
-  if (own_z)
-    ok = ok && hipMemset(p->ws_z, 0, (p->chunk * p->x_stride + p->guard) * sizeof(double)) == hipSuccess;
-  ok       = ok && hipMalloc((void **)&p->d_status, sizeof(int32_t)) == hipSuccess;
-  ok       = ok && hipMalloc((void **)&p->d_pdiag, n * (size_t)s * sizeof(SlodPatchDiag)) == hipSuccess;
-  ok       = ok && hipMemset(p->d_pdiag, 0, n * (size_t)s * sizeof(SlodPatchDiag)) == hipSuccess;
+  if (we != hipSuccess)
+    {
+      slod_plan_destroy(p);
+      return hip_fail(h, we, "slod_plan_create: device allocation");
+    }
+  ok = hipMalloc((void **)&p->d_pdiag, n * (size_t)s * sizeof(SlodPatchDiag)) == hipSuccess;
+  ok = ok && hipMemset(p->d_pdiag, 0, n * (size_t)s * sizeof(SlodPatchDiag)) == hipSuccess;
   // Launch order (d_desc_bal, built by k_balance_order above).  All workgroups of a launch are resident
   // at once (a few per CU) and the step ends with the slowest CU; measured on MI355X
   // (tools/patch_timeline.py) the blocks b, b + n_cu, b + 2 n_cu, ... share a CU.  Patches ranked by
   // estimated cost (canonical solve flops, rim patches are cheaper) and dealt in a snake over rows of
   // n_cu give every CU the same mix.
-  ok = ok && hipMemset(p->d_status, 0, sizeof(int32_t)) == hipSuccess;
   p->n_chunks = (n + p->chunk - 1) / p->chunk;
   p->ev.assign(4 * p->n_chunks, nullptr);
   for (auto &ev : p->ev)
@@ -668,31 +697,8 @@ void slod_plan_destroy(slod_plan *p)
     (void)hipFree(p->d_desc);
   if (p->d_desc_bal)
     (void)hipFree(p->d_desc_bal);
-  if (p->ws_st)
-    (void)hipFree(p->ws_st);
-  if (p->ws_v)
-    (void)hipFree(p->ws_v);
-  if (p->ws_x_alloc)
-    (void)hipFree(p->ws_x_alloc);
-  if (p->ws_z)
-    (void)hipFree(p->ws_z);
-  if (p->ws_m)
-    (void)hipFree(p->ws_m);
-  if (p->d_status)
-    (void)hipFree(p->d_status);
-  for (void *q : {(void *)p->alt.ws_st, (void *)p->alt.ws_v, (void *)p->alt.ws_x_alloc, (void *)p->alt.ws_z, (void *)p->alt.ws_m,
-                  (void *)p->alt.d_status})
-    if (q)
-      (void)hipFree(q);
-  for (int k = 0; k < 2; ++k)
-    {
-      if (p->istream[k])
-        (void)hipStreamDestroy(p->istream[k]);
-      if (p->done_ev[k])
-        (void)hipEventDestroy(p->done_ev[k]);
-    }
-  if (p->fork_ev)
-    (void)hipEventDestroy(p->fork_ev);
+  p->ws[0].release();
+  release_overlap(p);
   if (p->d_pdiag)
     (void)hipFree(p->d_pdiag);
   delete p;
@@ -716,7 +722,6 @@ int slod_plan_execute(slod_plan *p, double *d_basis, double *d_premult, void *hi
         return fail(h, SLOD_ERR_STATE, "slod_plan_execute: coefficient field not set");
   (void)hipSetDevice(h->cfg.device);
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
-  const int   s  = h->cfg.spacedim;
   hipError_t  e  = hipSuccess;
   int         slot = 0;
   if (p->overlap == 2)
@@ -732,9 +737,8 @@ int slod_plan_execute(slod_plan *p, double *d_basis, double *d_premult, void *hi
       st = own;
     }
   if (e == hipSuccess)
-    e = hipMemsetAsync(slot ? p->alt.d_status : p->d_status, 0, sizeof(int32_t), st);
+    e = hipMemsetAsync(p->ws[slot].status, 0, sizeof(int32_t), st);
   size_t ci = 0;
-  (void)s;
   for (size_t first = 0; first < p->n && e == hipSuccess; first += p->chunk, ++ci)
     e = launch_range(p, first, (int)std::min(p->chunk, p->n - first), d_basis, d_premult, st,
                      &p->ev[4 * ((p->n_exec % (size_t)p->depth) * p->n_chunks + ci)], true, slot);
@@ -766,33 +770,23 @@ int slod_plan_set_overlap(slod_plan *p, int depth)
     }
   if (p->n_chunks != 1)
     return fail(h, SLOD_ERR_STATE, "slod_plan_set_overlap: the plan runs in several workspace chunks (they de-phase by themselves)");
-  const bool own_z = p->ws_z != nullptr;
-  const size_t st_slack = (size_t)4 * p->nn_max;
-  bool ok = true;
-  if (!p->alt.ws_st)
+  if (!p->fork_ev) // the piece created last: the second workspace, the streams and the events all exist, or none does
     {
-      ok = ok && hipMalloc((void **)&p->alt.ws_st, (p->chunk * p->st_stride + st_slack) * sizeof(double)) == hipSuccess;
-      ok = ok && hipMalloc((void **)&p->alt.ws_v, std::max<size_t>(1, p->chunk * p->v_stride) * sizeof(double)) == hipSuccess;
-      ok = ok && hipMalloc((void **)&p->alt.ws_x_alloc, (p->chunk * p->x_stride + 2 * p->guard) * sizeof(double)) == hipSuccess;
-      if (own_z)
-        ok = ok && hipMalloc((void **)&p->alt.ws_z, (p->chunk * p->x_stride + p->guard) * sizeof(double)) == hipSuccess;
-      ok = ok && hipMalloc((void **)&p->alt.ws_m, p->chunk * (2 * (size_t)p->nc_max * p->nc_max + 1) * sizeof(double)) == hipSuccess;
-      ok = ok && hipMalloc((void **)&p->alt.d_status, sizeof(int32_t)) == hipSuccess;
-      ok = ok && hipMemset(p->alt.ws_st, 0, (p->chunk * p->st_stride + st_slack) * sizeof(double)) == hipSuccess;
-      ok = ok && hipMemset(p->alt.ws_x_alloc, 0, (p->chunk * p->x_stride + 2 * p->guard) * sizeof(double)) == hipSuccess;
-      if (own_z)
-        ok = ok && hipMemset(p->alt.ws_z, 0, (p->chunk * p->x_stride + p->guard) * sizeof(double)) == hipSuccess;
-      ok = ok && hipMemset(p->alt.d_status, 0, sizeof(int32_t)) == hipSuccess;
-      p->alt.ws_x = p->alt.ws_x_alloc ? p->alt.ws_x_alloc + p->guard : nullptr;
-      for (int k = 0; k < 2 && ok; ++k)
+      hipError_t e = p->ws[1].allocate(*p, p->ws[0].z != nullptr);
+      for (int k = 0; k < 2 && e == hipSuccess; ++k)
         {
-          ok = ok && hipStreamCreateWithFlags(&p->istream[k], hipStreamNonBlocking) == hipSuccess;
-          ok = ok && hipEventCreateWithFlags(&p->done_ev[k], hipEventDisableTiming) == hipSuccess;
+          e = hipStreamCreateWithFlags(&p->istream[k], hipStreamNonBlocking);
+          if (e == hipSuccess)
+            e = hipEventCreateWithFlags(&p->done_ev[k], hipEventDisableTiming);
         }
-      ok = ok && hipEventCreateWithFlags(&p->fork_ev, hipEventDisableTiming) == hipSuccess;
+      if (e == hipSuccess)
+        e = hipEventCreateWithFlags(&p->fork_ev, hipEventDisableTiming);
+      if (e != hipSuccess)
+        {
+          release_overlap(p); // the plan is as it was before the call; the next call starts from scratch
+          return hip_fail(h, e, "slod_plan_set_overlap: device allocation");
+        }
     }
-  if (!ok)
-    return hip_fail(h, hipGetLastError(), "slod_plan_set_overlap: device allocation");
   p->overlap = 2;
   p->n_exec  = 0; // the profile slots start over
   return SLOD_OK;
@@ -860,7 +854,7 @@ int slod_debug_read_ms(slod_plan *p, double *out, size_t count)
   const size_t have = p->chunk * (size_t)p->nc_max * p->nc_max;
   (void)hipSetDevice(p->h->cfg.device);
   (void)hipDeviceSynchronize();
-  return hipMemcpy(out, p->ws_m, std::min(count, have) * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess
+  return hipMemcpy(out, p->ws[0].m, std::min(count, have) * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess
              ? SLOD_OK
              : SLOD_ERR_DEVICE;
 }
@@ -923,13 +917,15 @@ int slod_plan_status(slod_plan *p)
     return SLOD_ERR_ARGUMENT;
   if (!p->ran || p->n == 0)
     return SLOD_OK;
-  int32_t    st = 0, st2 = 0;
+  int32_t    st = 0;
   hipError_t e  = hipDeviceSynchronize();
-  if (e == hipSuccess)
-    e = hipMemcpy(&st, p->d_status, sizeof(st), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && p->alt.d_status)
-    e = hipMemcpy(&st2, p->alt.d_status, sizeof(st2), hipMemcpyDeviceToHost);
-  st |= st2;
+  for (const PlanWorkspace &w : p->ws)
+    {
+      int32_t sk = 0;
+      if (e == hipSuccess && w.status)
+        e = hipMemcpy(&sk, w.status, sizeof(sk), hipMemcpyDeviceToHost);
+      st |= sk;
+    }
   p->inflight[0] = p->inflight[1] = false;
   if (e != hipSuccess)
     return hip_fail(p->h, e, "slod_plan_status");
@@ -1029,7 +1025,7 @@ int slod_assemble_stiffness_for_patch(slod_handle *h, uint32_t gid, double *sten
       const SlodPatchDesc &d  = p->desc[0];
       const int            s  = h->cfg.spacedim, nn = (d.nx + 1) * (d.ny + 1);
       std::vector<double>  tmp(p->st_stride);
-      hipError_t e = hipMemcpy(tmp.data(), p->ws_st, p->st_stride * sizeof(double), hipMemcpyDeviceToHost);
+      hipError_t e = hipMemcpy(tmp.data(), p->ws[0].st, p->st_stride * sizeof(double), hipMemcpyDeviceToHost);
       if (e != hipSuccess)
         rc = hip_fail(h, e, "slod_assemble_stiffness_for_patch");
       else
@@ -1061,7 +1057,7 @@ int slod_patch_solution(slod_handle *h, uint32_t gid, double *X)
       const int            s = h->cfg.spacedim, npx = d.nx + 1, nf = s * npx * (d.ny + 1);
       const bool           tr = (d.flags & SLOD_F_TRANSPOSED) != 0;
       std::vector<double>  tmp(p->x_stride);
-      hipError_t e = hipMemcpy(tmp.data(), p->ws_x, p->x_stride * sizeof(double), hipMemcpyDeviceToHost);
+      hipError_t e = hipMemcpy(tmp.data(), p->ws[0].x, p->x_stride * sizeof(double), hipMemcpyDeviceToHost);
       if (e != hipSuccess)
         rc = hip_fail(h, e, "slod_patch_solution");
       else
@@ -1255,7 +1251,7 @@ int slod_plan_execute_allgather(slod_plan *p, slod_comm *c, double *d_basis_all,
   hipStream_t  cs = (hipStream_t)compute_stream, ns = (hipStream_t)comm_stream;
   const size_t slab = patches_per_rank * p->stride;
   double      *mb = d_basis_all + (size_t)c->rank * slab, *mp = d_premult_all + (size_t)c->rank * slab;
-  hipError_t   e  = p->n ? hipMemsetAsync(p->d_status, 0, sizeof(int32_t), cs) : hipSuccess;
+  hipError_t   e  = p->n ? hipMemsetAsync(p->ws[0].status, 0, sizeof(int32_t), cs) : hipSuccess;
   Rccl        &r  = rccl();
   for (int piece = 0; piece < n_pieces && e == hipSuccess; ++piece)
     {

@@ -106,25 +106,13 @@ namespace
     return y * fma(-h * y, y, 1.5);
   }
 
+  // waves per SIMD asked of a kernel whose Gauss-Jordan wave holds a line block as an 8 x 8 lane
+  // grid of T x T register tiles (slod_lane_tile, slod_dispatch.cpp): 2 T^2 VGPRs for the block alone
+  __host__ __device__ constexpr int lane_tile_min_waves(int T) { return T <= 5 ? 4 : (T <= 7 ? 2 : 1); }
 
-  __host__ __device__ constexpr int ws_min_waves(int T) { return T <= 5 ? 4 : (T <= 7 ? 2 : 1); }
-
-  // Z tile (16 x 16) = Vs[16 ti .., :] * Rb[:, 16 tj ..] on the fp64 matrix pipe
-  // (v_mfma_f64_16x16x4_f64: lane l feeds A[l&15][l>>4], B[l>>4][l&15]; D[(l>>4)+4r][l&15], r<4).
-  // Two 8-byte LDS reads per 1024 FMAs instead of 80 bytes per 12 FMAs of the VALU tile, and
-  // no VALU issue slots: the helper waves stop competing with the Gauss-Jordan waves.
+  // accumulator of v_mfma_f64_16x16x4_f64: lane l feeds A[l&15][l>>4], B[l>>4][l&15] and holds
+  // D[(l>>4)+4r][l&15], r<4
   typedef double double4_t __attribute__((ext_vector_type(4)));
-  __device__ __forceinline__ double4_t gemm_mfma_tile(const double *__restrict__ Vs, int ldv,
-                                                      const double *__restrict__ Rb, int ncs, int k4,
-                                                      int ti, int tj, int lane)
-  {
-    double4_t     acc = {0.0, 0.0, 0.0, 0.0};
-    const double *ap  = Vs + (16 * ti + (lane & 15)) * ldv + (lane >> 4);
-    const double *bp  = Rb + (lane >> 4) * ncs + 16 * tj + (lane & 15);
-    for (int k = 0; k < k4; k += 4)
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[k], bp[k * ncs], acc, 0, 0, 0);
-    return acc;
-  }
 
   // all-reduce inside a 16-lane row with DPP rotations (row_ror:8,4,2,1): ~4 VALU steps
   // instead of four LDS-routed shuffles on the dependent chain of every Jacobi rotation

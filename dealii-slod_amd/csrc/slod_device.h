@@ -78,8 +78,7 @@ struct SlodKernelArgs
   double *zs;       // k_solve_tw: Z of the forward sweep (same strides as xs); other kernels keep Z in xs
   size_t  x_stride;
   int32_t nc_max;
-  double *ms;       // per patch M = P^T A^-1 P / H^2 accumulated by k_solve_ws (nc_max^2 doubles)
-  int32_t m_fused;  // 1: k_select reads M from ms instead of recomputing it from X
+  double *ms;       // per patch nc_max^2 doubles of clock stamps (SLOD_ENABLE_DIAG builds, SLOD_DIAG bit 20); nothing else
   double *mt;       // per patch M built inside the sweeps of k_solve_tw: nc_max^2 doubles, then a flag (1.0: M
                     // is there, 0.0: the patch fell back); stride slod_mt_stride, not the stamps of ms
   int32_t m_tw;     // 1: k_solve_tw builds M in its sweeps where the patch allows it
@@ -99,7 +98,6 @@ enum SlodSolverKind : int32_t
 {
   SLOD_K_MF   = 1, // slod_solve_mf.hip
   SLOD_K_TW   = 2, // slod_solve_tw.hip
-  SLOD_K_WS   = 3, // slod_solve_ws.hip
   SLOD_K_COOP = 4, // slod_solve_coop.hip
   SLOD_K_ND   = 5  // slod_solve_nd.hip
 };
@@ -118,9 +116,9 @@ struct SlodSolveChoice
 {
   int    kind = 0;
   size_t lds  = 0;
-  int    fuse_select = 0, fuse_assemble = 0, m_fused = 0, m_tw = 0, bwd_ksplit = 0, twisted = 0, debug = 0;
+  int    fuse_select = 0, fuse_assemble = 0, m_tw = 0, bwd_ksplit = 0, twisted = 0, debug = 0;
   int    v_line_pad = 0; // rows = columns of a V line as the kernel sees it
-  size_t v_line_elems = 0; // doubles per stored V line (k_solve_tw: the 36 upper lane tiles only)
+  size_t v_line_elems = 0; // doubles per stored V line (k_solve_tw: the 8 x 8 lane tiles, both triangles)
   int    nv = 0;            // k_solve_nd: cell size
   size_t v_patch_elems = 0; // k_solve_nd: doubles of scratch per patch (replaces L_max * v_line_elems)
 };
@@ -128,12 +126,11 @@ SlodTuning slod_read_tuning();
 bool       slod_choose_solver(int S, int n_sub, int m_max, int L_max, int nc_max, int nb_buf, int nf_max, size_t n_patches,
                               const SlodTuning &t, SlodSolveChoice *out);
 
-// launchers (slod_assemble.hip, slod_solve_{mf,tw,ws,coop}.hip, slod_select.hip)
+// launchers (slod_assemble.hip, slod_solve_{mf,tw,coop,nd}.hip, slod_select.hip)
 hipError_t slod_launch_assemble(int S, const SlodKernelArgs &a, int n_patches, hipStream_t st);
 hipError_t slod_launch_solve(int S, const SlodSolveChoice &c, SlodKernelArgs &a, int n_patches, hipStream_t st);
 hipError_t slod_launch_solve_mf(int S, const SlodKernelArgs &a, int n_patches, size_t lds, hipStream_t st);
 hipError_t slod_launch_solve_tw(int S, const SlodKernelArgs &a, int n_patches, size_t lds, hipStream_t st);
-hipError_t slod_launch_solve_ws(int S, const SlodKernelArgs &a, int n_patches, size_t lds, hipStream_t st);
 hipError_t slod_launch_solve_coop(int S, int twisted, const SlodKernelArgs &a, int n_patches, hipStream_t st);
 hipError_t slod_launch_solve_nd(const SlodKernelArgs &a, int n_patches, size_t lds, hipStream_t st);
 int        slod_solve_nd_cell(int S, int n_sub, int m_max, int L_max); // cell size, 0 = not applicable
@@ -142,10 +139,9 @@ size_t     slod_solve_nd_lds_bytes(int nv, int m_max, int nc_max);
 hipError_t slod_launch_select(int S, const SlodKernelArgs &a, int n_patches, int nb_max,
                               int nf_max, hipStream_t st);
 size_t     slod_solve_lds_bytes(int S, int m_max, int nc_max, int twisted);
-size_t     slod_solve_ws_lds_bytes(int S, int m_max, int nc_max);
 size_t     slod_solve_tw_lds_bytes(int S, int m_max, int nc_max, bool with_m = false);
 size_t     slod_solve_mf_lds_bytes(int S, int m_max, int nc_max);
-int        slod_solve_ws_tile(int m_max);
+int        slod_lane_tile(int m_max); // T: one wave holds a line block as an 8 x 8 lane grid of T x T tiles (m_max <= 8 T), 0 = too wide
 int        slod_solve_mf_tiles(int S, int m_max); // 16 x 16 tiles per line side, 0 = does not fit
 size_t     slod_select_lds_bytes(int S, int nb_max, int nc_max, int nf_max);
 

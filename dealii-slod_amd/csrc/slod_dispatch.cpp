@@ -9,10 +9,11 @@
 
 // Tuning knobs of the experiments in tools/ and of the kernel-variant parity tests; read once
 // per plan (slod_plan_create), never in the launch path.
-//   SLOD_SOLVE=mf|tw|ws|coop  force a kernel family       SLOD_FUSE_SELECT=0  selection as its own launch
+//   SLOD_SOLVE=mf|tw|coop|nd  force a kernel family (any other value: the automatic choice)
+//   SLOD_FUSE_SELECT=0        selection as its own launch
 //   SLOD_FUSE_ASSEMBLE=0      stencil assembly as its own launch
-//   SLOD_FUSE_M=0|1           M = P^T A^-1 P / H^2 built inside the sweeps instead of re-read from X:
-//                             tw default on (SLOD_FUSE_M=0 turns it off, for A/B timing), ws opt-in
+//   SLOD_FUSE_M=0             tw builds M = P^T A^-1 P / H^2 inside its sweeps by default; 0 turns that off and the
+//                             selection stage computes M from X again (for A/B timing)
 //   SLOD_BWD_KSPLIT=0|1       tw backward sweep (lines of at most three row tiles, nc_max <= 32): K of X = Z - V Y
 //                             split between the chain's two waves (default) or, 0, the column-tile split
 //   SLOD_TWISTED=0|1 (coop only) SLOD_DEBUG=1 print the choice
@@ -21,7 +22,7 @@ SlodTuning slod_read_tuning()
 {
   SlodTuning t;
   if (const char *sel = getenv("SLOD_SOLVE"))
-    t.solver = !strcmp(sel, "mf") ? SLOD_K_MF : !strcmp(sel, "tw") ? SLOD_K_TW : !strcmp(sel, "ws") ? SLOD_K_WS :
+    t.solver = !strcmp(sel, "mf") ? SLOD_K_MF : !strcmp(sel, "tw") ? SLOD_K_TW :
                !strcmp(sel, "coop") ? SLOD_K_COOP : !strcmp(sel, "nd") ? SLOD_K_ND : 0;
   if (const char *e = getenv("SLOD_FUSE_SELECT"))
     t.fuse_select = atoi(e) ? 1 : 0;
@@ -40,6 +41,18 @@ SlodTuning slod_read_tuning()
   return t;
 }
 
+// tile size T of the kernels whose Gauss-Jordan wave keeps a line block in registers as an 8 x 8
+// lane grid of T x T tiles (k_solve_tw, k_solve_nd): the smallest instantiated T with 8 T >= m_max,
+// 0 when the line is too wide
+int slod_lane_tile(int m_max)
+{
+  static const int tiles[] = {2, 3, 4, 5, 6, 8, 10, 12, 14};
+  for (int t : tiles)
+    if (8 * t >= m_max)
+      return t;
+  return 0;
+}
+
 bool slod_choose_solver(int S, int n_sub, int m_max, int L_max, int nc_max, int nb_buf, int nf_max, size_t n_patches,
                         const SlodTuning &t_in, SlodSolveChoice *out)
 {
@@ -55,14 +68,13 @@ bool slod_choose_solver(int S, int n_sub, int m_max, int L_max, int nc_max, int 
   //        tools/solver_compare.py)
   //   mf   MFMA-factorised: blocked Gauss-Jordan on the fp64 matrix pipe, twisted, column-tile
   //        private right-hand-side streams (SLOD_SOLVE=mf; automatic only where tw does not fit)
-  //   ws   wave-specialised, one chain
   //   coop all threads cooperate on every pivot (also for tiles narrower than the band)
-  const int  wt = slod_solve_ws_tile(m_max);
-  const bool ws_fits = wt > 0 && wt >= 2 * S - 1;
+  const int  wt = slod_lane_tile(m_max);
+  const bool lane_tile_fits = wt > 0 && wt >= 2 * S - 1; // the tile is at least as wide as the band
   const auto want = [&](int k) { return t.solver == 0 || t.solver == k; };
   const size_t lds_sel = slod_select_lds_bytes(S, nb_buf, nc_max, nf_max);
   const bool   mf_fits = slod_solve_mf_tiles(S, m_max) > 0 && slod_solve_mf_lds_bytes(S, m_max, nc_max) <= lds_max;
-  const bool   tw_fits = ws_fits && slod_solve_tw_lds_bytes(S, m_max, nc_max) <= lds_max;
+  const bool   tw_fits = lane_tile_fits && slod_solve_tw_lds_bytes(S, m_max, nc_max) <= lds_max;
   if (nd_nv > 0 && t.solver == SLOD_K_ND)
     {
       //   nd   nested dissection: static condensation per cell, edge sets, skeleton lines
@@ -73,7 +85,7 @@ bool slod_choose_solver(int S, int n_sub, int m_max, int L_max, int nc_max, int 
       c.fuse_assemble = t.fuse_assemble ? 1 : 0;
       c.fuse_select   = 0; // 512-thread workgroups: the selection stage is its own launch
     }
-  else if (mf_fits && (t.solver == SLOD_K_MF || (t.solver == 0 && !tw_fits && !ws_fits)))
+  else if (mf_fits && (t.solver == SLOD_K_MF || (t.solver == 0 && !tw_fits && !lane_tile_fits)))
     {
       c.kind          = SLOD_K_MF;
       c.lds           = slod_solve_mf_lds_bytes(S, m_max, nc_max);
@@ -114,18 +126,7 @@ bool slod_choose_solver(int S, int n_sub, int m_max, int L_max, int nc_max, int 
       // (at most three row tiles per line, at most two column tiles)
       c.bwd_ksplit = (t.bwd_ksplit && 8 * wt <= 48 && nc_max <= 32) ? 1 : 0;
     }
-  else if ((want(SLOD_K_WS) || t.solver == SLOD_K_TW) && ws_fits &&
-           slod_solve_ws_lds_bytes(S, m_max, nc_max) <= lds_max)
-    {
-      c.kind       = SLOD_K_WS;
-      c.lds        = slod_solve_ws_lds_bytes(S, m_max, nc_max);
-      c.v_line_pad = 8 * wt;
-      c.v_line_elems = (size_t)c.v_line_pad * c.v_line_pad;
-      // fusing M = sum_l R_l^T Z_l into the helper waves saves the selection stage's re-read of X
-      // but costs a fourth barrier per line; measured neutral on C2, so opt-in (SLOD_FUSE_M=1)
-      c.m_fused = (t.fuse_m > 0 && nc_max * nc_max <= 192 * 4) ? 1 : 0;
-    }
-  else if (t.solver == 0 || t.solver == SLOD_K_COOP || !ws_fits)
+  else if (t.solver == 0 || t.solver == SLOD_K_COOP || !lane_tile_fits)
     {
       // twisted (two chains, 512 threads) when the GPU is not full anyway: it halves the
       // dependent chain per patch; one chain per patch otherwise
@@ -150,7 +151,6 @@ bool slod_choose_solver(int S, int n_sub, int m_max, int L_max, int nc_max, int 
 
 hipError_t slod_launch_solve(int S, const SlodSolveChoice &c, SlodKernelArgs &a, int n_patches, hipStream_t st)
 {
-  a.m_fused       = c.m_fused;
   a.m_tw          = c.m_tw;
   a.bwd_ksplit    = c.bwd_ksplit;
   a.fuse_select   = c.fuse_select;
@@ -162,8 +162,6 @@ hipError_t slod_launch_solve(int S, const SlodSolveChoice &c, SlodKernelArgs &a,
         return slod_launch_solve_mf(S, a, n_patches, c.lds, st);
       case SLOD_K_TW:
         return slod_launch_solve_tw(S, a, n_patches, c.lds, st);
-      case SLOD_K_WS:
-        return slod_launch_solve_ws(S, a, n_patches, c.lds, st);
       case SLOD_K_COOP:
         return slod_launch_solve_coop(S, c.twisted, a, n_patches, st);
       case SLOD_K_ND:

@@ -116,13 +116,10 @@ namespace
     // ---- M = P^T X / H^dim (LOD.cc:548-551).  X rows come from the global workspace: the
     //      inner loop has no control dependence (clamped address, zero weight on the patch
     //      boundary where X = 0) so its n+1 loads are in flight together.
-    const bool m_given = mpre != nullptr || A.m_fused;
+    const bool m_given = mpre != nullptr;
     if (m_given)
-      {
-        const double *mg = mpre ? mpre : A.ms + (size_t)patch * A.nc_max * A.nc_max;
-        for (int idx = tid; idx < nc * nc; idx += 256)
-          Ms[(idx / nc) * ldm + (idx % nc)] = mg[idx];
-      }
+      for (int idx = tid; idx < nc * nc; idx += 256)
+        Ms[(idx / nc) * ldm + (idx % nc)] = mpre[idx];
     // M = P^T A^-1 P is symmetric and the sweep below treats it as such (column k is taken from
     // row k), so only the entries a <= b are computed (half the load batches) and mirrored
     for (int idx = tid; idx < ((SLOD_DG(A, 64)) || m_given ? 0 : nc * (nc + 1) / 2); idx += 256)

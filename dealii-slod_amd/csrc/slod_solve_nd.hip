@@ -10,7 +10,7 @@ int slod_solve_nd_cell(int S, int n_sub, int m_max, int L_max)
   // cell size of the dissection, 0 = this kernel does not take the plan
   if (S != 1 || (n_sub != 4 && n_sub != 8))
     return 0;
-  const int nv = n_sub, T = slod_solve_ws_tile(m_max);
+  const int nv = n_sub, T = slod_lane_tile(m_max);
   if (T <= 0 || T > 5 || ((m_max + 1) / nv - 1) * (nv - 1) > 32)
     return 0;
   (void)L_max;
@@ -19,14 +19,14 @@ int slod_solve_nd_cell(int S, int n_sub, int m_max, int L_max)
 
 size_t slod_solve_nd_scratch(int nv, int m_max, int L_max, int nc_max)
 {
-  return nd_layout(nv, slod_solve_ws_tile(m_max), m_max, L_max, nc_max).total;
+  return nd_layout(nv, slod_lane_tile(m_max), m_max, L_max, nc_max).total;
 }
 
 size_t slod_solve_nd_lds_bytes(int nv, int m_max, int nc_max)
 {
   // the largest of: SIMT phases (per wave: pivot row, ring couplings, parked rows), factor lines,
   // skeleton front (three m x m blocks, edge block, coupling / right-hand-side block, pivot row)
-  const int    T = slod_solve_ws_tile(m_max), MP = 8 * T, NW = ND_WAVES, ncp = (nc_max + 15) & ~15;
+  const int    T = slod_lane_tile(m_max), MP = 8 * T, NW = ND_WAVES, ncp = (nc_max + 15) & ~15;
   const size_t a = (size_t)NW * (MP + 4 * nv * 4 + ((nv - 1) * (nv - 1) > 32 ? 24 * (4 * nv + 2) : 0));
   const size_t b = (size_t)NW * (64 / (nv + 1) + 1) * 2 * (nv + 1);
   const size_t c = (size_t)3 * MP * (MP + 1) + 32 * 33 + (size_t)32 * (2 * MP + ncp) + MP;
@@ -38,7 +38,7 @@ hipError_t slod_launch_nd8b(int T, const SlodKernelArgs &a, int n_patches, size_
 
 hipError_t slod_launch_solve_nd(const SlodKernelArgs &a, int n_patches, size_t lds, hipStream_t st)
 {
-  const int T = slod_solve_ws_tile(a.m_max);
+  const int T = slod_lane_tile(a.m_max);
   if (a.nv == 4)
     switch (T)
       {

@@ -8,8 +8,11 @@ namespace
   // ---------------------------------------------------------------------------------
   // K2 (twisted + wave-specialised).  Two chains per patch: chain 0 eliminates lines
   // 0..mid-1 downwards, chain 1 lines L-1..mid+1 upwards; they meet at line mid.  Wave c
-  // (c = 0,1) is the Gauss-Jordan wave of chain c (k_solve_ws's register scheme), wave 2+c
-  // its helper (RHS block, Z = V R on the fp64 MFMA pipe, band fetches).  V and Z/X live only
+  // (c = 0,1) is the Gauss-Jordan wave of chain c: it holds the whole m x m Schur complement of a
+  // line in registers (8 x 8 lane grid, a contiguous T x T tile per lane, m <= 8 T), publishes pivot
+  // row k to a wave-private LDS line (in-order DS queue of one wave: no barrier) and runs all m
+  // dependent pivot steps alone.  Wave 2+c is its helper (RHS block, Z = V R on the fp64 MFMA pipe,
+  // band fetches), so the matrix pipe leaves the VALU issue slots to the Gauss-Jordan waves.  V and Z/X live only
   // in the global workspace (L2): the helpers feed the MFMA A operand straight from there, so
   // LDS holds just the RHS block, the pivot row and the stencil bands of each chain (26 KB at
   // C2) and four workgroups stay resident per CU while the dependent chain per patch is halved.
@@ -17,7 +20,7 @@ namespace
   // step t+1 are in LDS".
   // ---------------------------------------------------------------------------------
   template <int T, int S>
-  __global__ __launch_bounds__(256, ws_min_waves(T)) void k_solve_tw(const SlodKernelArgs A)
+  __global__ __launch_bounds__(256, lane_tile_min_waves(T)) void k_solve_tw(const SlodKernelArgs A)
   {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const SlodPatchDesc d = A.desc[blockIdx.x];
@@ -1464,7 +1467,7 @@ namespace
 size_t slod_solve_tw_lds_bytes(int S, int m_max, int nc_max, bool with_m)
 {
   // must mirror the carve-up at the top of k_solve_tw
-  const int    T = slod_solve_ws_tile(m_max), W = 2 * S - 1, BW = 2 * W + 1, MP = 8 * T;
+  const int    T = slod_lane_tile(m_max), W = 2 * S - 1, BW = 2 * W + 1, MP = 8 * T;
   const int    ncs = (nc_max + 1) & ~1, bsz = ((MP + 2 * W) * (BW + 1) + 1) & ~1;
   (void)m_max;
   const size_t chsz  = (size_t)MP * ncs + MP + 6 * (size_t)bsz;
@@ -1493,7 +1496,7 @@ static hipError_t launch_tw_TS(const SlodKernelArgs &a, int n_patches, size_t ld
 template <int S>
 static hipError_t launch_tw_S(const SlodKernelArgs &a, int n_patches, size_t lds, hipStream_t st)
 {
-  switch (slod_solve_ws_tile(a.m_max))
+  switch (slod_lane_tile(a.m_max))
     {
       case 2:
         return launch_tw_TS<2, S>(a, n_patches, lds, st);

@@ -163,11 +163,11 @@ def test_size_independent_properties_at_full_size(so):
         assert distinct.size <= (2 * info.mx - 1) * (2 * info.my - 1) + 1
 
 
-@pytest.mark.parametrize("mode", ["mf", "tw", "ws", "coop", "nd"])
+@pytest.mark.parametrize("mode", ["mf", "tw", "coop", "nd"])
 @pytest.mark.parametrize("spacedim", [1, 2])
 def test_all_solver_kernels(so, mode, spacedim, monkeypatch):
     """The patch-solve kernel families (twisted wave-specialised = default, MFMA-factorised,
-    wave-specialised, cooperative, nested dissection -- scalar problems only, vector plans fall back
+    cooperative, nested dissection -- scalar problems only, vector plans fall back
     to the default) must all meet the parity bar; SLOD_SOLVE selects one per plan."""
     monkeypatch.setenv("SLOD_SOLVE", mode)
     kw = dict(nref=3, n_sub=4, oversampling=1, stabilize=1) if spacedim == 1 else \
@@ -179,6 +179,22 @@ def test_all_solver_kernels(so, mode, spacedim, monkeypatch):
     basis, premult, offs = g.compute_basis(ids)
     for k, pid in enumerate(ids):
         _check_patch(so, cfg, fields, int(pid), basis, premult, int(offs[k]), mode)
+
+
+def test_retired_solver_name_gives_the_automatic_choice(so, monkeypatch):
+    """SLOD_SOLVE=ws named the single-chain kernel that no longer exists: like any unknown value it is
+    accepted and the plan gets the automatic choice, bit for bit."""
+    def run():
+        cfg, g = _mk(so, nref=2, n_sub=4, oversampling=1, stabilize=1)
+        _upload(g, make_fields(so, cfg, "D100"))
+        assert g.num_patches == 16
+        return g.compute_basis(np.arange(g.num_patches))
+    monkeypatch.delenv("SLOD_SOLVE", raising=False)
+    basis, premult, offs = run()
+    monkeypatch.setenv("SLOD_SOLVE", "ws")
+    basis_ws, premult_ws, offs_ws = run()
+    assert np.array_equal(offs, offs_ws)
+    assert np.array_equal(basis, basis_ws) and np.array_equal(premult, premult_ws)
 
 
 @pytest.mark.parametrize("kw", [dict(nref=1, n_sub=2, oversampling=1), dict(nref=2, n_sub=3, oversampling=2),
@@ -540,6 +556,17 @@ def test_overlapped_executes_inside_the_library(so):
     plan.execute(b.data_ptr(), q.data_ptr())
     plan.status()
     assert torch.equal(b, ref_b)
+    plan.set_overlap(2)                            # the second workspace, streams and events exist already
+    for b, q in outs[1:]:
+        b.zero_()
+        q.zero_()
+    torch.cuda.synchronize()
+    for b, q in outs[1:]:
+        plan.execute(b.data_ptr(), q.data_ptr())
+    plan.join()
+    plan.status()
+    for b, q in outs[1:]:
+        assert torch.equal(b, ref_b) and torch.equal(q, ref_q)
 
 
 def test_overlap_refused_for_chunked_plans(so, monkeypatch):

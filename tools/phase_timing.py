@@ -1,6 +1,6 @@
 # Timing-only experiment driver: SLOD_DIAG=<mask> makes the kernels skip phases (results are
 # WRONG when mask != 0; the status check is disabled).  Usage: python tools/phase_timing.py 0 16 20
-# k_solve_ws bits: 2 RHS build, 4 sweep (1 pivot only), 8 GEMM, 16 backward pass, 32 band loads,
+# k_solve_tw bits: 2 RHS build, 4 sweep (1 pivot only), 8 GEMM, 16 backward pass, 32 band loads,
 # 16384 next_S, 32768 store_V.  k_select bits: 64 M, 128 D, 256 BD fill, 512 QR+SVD, 1024 phi,
 # 2048 psi, 4096 SVD fallback, 8192 cap sweeps at 3.
 import os, sys, subprocess, json
