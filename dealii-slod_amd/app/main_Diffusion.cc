@@ -1,5 +1,5 @@
 // Counterpart of reference app/main_Diffusion.cc for the basis-construction path:
-//   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare] [--coarse]
+//   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare] [--coarse] [--loads K]
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
 // file name it dumps, per patch, phi and psi in patch-lexicographic order (parity tests).
 // --compare (anywhere on the command line): after run(), the rest of the reference run() -- global
@@ -7,6 +7,9 @@
 // errors (LOD.cc:1462-1463) in L2, H1, Linfty and the energy norm.
 // --coarse implies --compare and adds the coarse FEM(H) problem (LOD.cc:1103-1237): its table "FEM(H) vs
 // reference FEM(h)" comes before the SLOD table, the reference's order (LOD.cc:1458-1465).
+// --loads K: the LOD system for the K loads f_k = sin(k pi x) sin(pi y), k = 1 .. K, in one multi-vector solve
+// (slod_lod_solve_multi); one line per load with its iterations and relative residual, with --compare also the
+// L2 and energy error against the fine FEM solution of that load.
 #include "../host/Diffusion.h"
 
 #include <cstdio>
@@ -40,16 +43,35 @@ public:
   }
 };
 
+// f_k = sin(k pi x) sin(pi y)
+class SineLoad : public Function<2>
+{
+public:
+  explicit SineLoad(int k)
+    : k(k)
+  {}
+  double value(const Point<2> &p, const unsigned int = 0) const override
+  {
+    return std::sin(k * M_PI * p(0)) * std::sin(M_PI * p(1));
+  }
+
+private:
+  int k;
+};
+
 int main(int argc_all, char **argv_all)
 {
   // --compare and --coarse are taken out wherever they stand; the positional arguments keep their meaning
   bool               compare = false, coarse = false;
+  int                n_loads = 0;
   std::vector<char *> args;
   for (int i = 0; i < argc_all; ++i)
     if (i > 0 && !std::strcmp(argv_all[i], "--compare"))
       compare = true;
     else if (i > 0 && !std::strcmp(argv_all[i], "--coarse"))
       compare = coarse = true;
+    else if (i > 0 && !std::strcmp(argv_all[i], "--loads") && i + 1 < argc_all)
+      n_loads = std::atoi(argv_all[++i]);
     else
       args.push_back(argv_all[i]);
   const int argc = (int)args.size();
@@ -102,6 +124,28 @@ int main(int argc_all, char **argv_all)
           std::printf("  H1     error = %.12e  (relative %.6e)\n", h1, h1 / uh1);
           std::printf("  Linfty error = %.12e  (relative %.6e)\n", e.linf[0], e.linf[0] / u.linf[0]);
           std::printf("  energy error = %.12e  (relative %.6e)\n", e.energy, e.energy / u.energy);
+        }
+      if (n_loads > 0)
+        {
+          if (!compare)
+            problem.assemble_global_matrix();
+          std::vector<SineLoad> loads;
+          for (int k = 1; k <= n_loads; ++k)
+            loads.emplace_back(k);
+          std::vector<const Function<2> *> ptrs;
+          for (const auto &l : loads)
+            ptrs.push_back(&l);
+          problem.solve_multi(ptrs);
+          if (compare)
+            problem.compare_multi_with_fem();
+          for (int k = 0; k < n_loads; ++k)
+            {
+              std::printf("load %d: iterations = %d, relative residual = %.6e\n", k + 1, problem.multi_iterations()[k],
+                          problem.multi_rel_residuals()[k]);
+              if (compare)
+                std::printf("load %d: L2 error = %.12e, energy error = %.12e\n", k + 1,
+                            problem.error_multi_LOD_FEMh()[k].l2[0], problem.error_multi_LOD_FEMh()[k].energy);
+            }
         }
     }
   catch (std::exception &exc)

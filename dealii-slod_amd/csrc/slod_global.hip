@@ -196,6 +196,136 @@ namespace
       fine[(size_t)gn * s + c] = acc[c];
   }
 
+  // ---- the same two products for n_rhs load vectors at once (slod_lod_rhs_multi, slod_lod_reconstruct_multi).
+  // Fine multi-vectors are field-major (column c at + c * ld_fine), coarse ones interleaved ([row][column]).
+  // A block takes a tile of MULTI_TILE columns (blockIdx.y): a phi value is loaded once and used for every
+  // column of the tile.
+  constexpr int MULTI_TILE = 16;
+  // C^T F: block = one patch x one column tile, threads = the patch's nodes (reads of F coalesced per column)
+  template <int S>
+  __global__ __launch_bounds__(256) void k_lod_rhs_multi(const SlodGrid G, const uint32_t *rows, const double *basis,
+                                                        size_t stride, const double *frhs, size_t ld_fine, int n_rhs,
+                                                        double *out, size_t ld_out)
+  {
+    __shared__ double red[4][S * MULTI_TILE];
+    const int         n = G.n_sub, NEp = G.N * n + 1;
+    const uint32_t    p = rows[blockIdx.x];
+    const int         c0 = blockIdx.y * MULTI_TILE, nc = min(MULTI_TILE, n_rhs - c0);
+    int               pcx, pcy;
+    grid_centre(G, p, pcx, pcy);
+    const Extent  pe = grid_extent(G, pcx, pcy);
+    const int     pnx = pe.mx * n + 1, pny = pe.my * n + 1, pnf = S * pnx * pny;
+    const double *phi = basis + (size_t)p * stride;
+    double        acc[S][MULTI_TILE];
+#pragma unroll
+    for (int d = 0; d < S; ++d)
+#pragma unroll
+      for (int k = 0; k < MULTI_TILE; ++k)
+        acc[d][k] = 0.0;
+    for (int node = threadIdx.x; node < pnx * pny; node += 256)
+      {
+        const int iy = node / pnx, ix = node - iy * pnx;
+        const int gn = (pe.x0 * n + ix) + (pe.y0 * n + iy) * NEp;
+        double    ph[S][S]; // [d][c]
+#pragma unroll
+        for (int d = 0; d < S; ++d)
+#pragma unroll
+          for (int c = 0; c < S; ++c)
+            ph[d][c] = phi[(size_t)d * pnf + S * node + c];
+#pragma unroll
+        for (int k = 0; k < MULTI_TILE; ++k)
+          if (k < nc)
+            {
+              const double *f = frhs + (size_t)(c0 + k) * ld_fine + (size_t)gn * S;
+#pragma unroll
+              for (int c = 0; c < S; ++c)
+                {
+                  const double fc = f[c];
+#pragma unroll
+                  for (int d = 0; d < S; ++d)
+                    acc[d][k] = fma(ph[d][c], fc, acc[d][k]);
+                }
+            }
+      }
+#pragma unroll
+    for (int d = 0; d < S; ++d)
+#pragma unroll
+      for (int k = 0; k < MULTI_TILE; ++k)
+        {
+          double v = acc[d][k];
+          for (int off = 32; off > 0; off >>= 1)
+            v += __shfl_xor(v, off, 64);
+          if ((threadIdx.x & 63) == 0)
+            red[threadIdx.x >> 6][d * MULTI_TILE + k] = v;
+        }
+    __syncthreads();
+    if ((int)threadIdx.x < S * MULTI_TILE)
+      {
+        const int d = threadIdx.x / MULTI_TILE, k = threadIdx.x - d * MULTI_TILE;
+        if (k < nc)
+          out[((size_t)blockIdx.x * S + d) * ld_out + c0 + k] =
+            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+      }
+  }
+
+  // U_fine = C U_H: one thread per global fine node and column tile; the loop over the covering patches and
+  // the order of the fma chain are those of k_lod_reconstruct, so every field equals the single-vector result
+  template <int S>
+  __global__ __launch_bounds__(256) void k_lod_reconstruct_multi(const SlodGrid G, const double *basis, size_t stride,
+                                                                const double *u, size_t ld_u, int n_rhs, double *fine,
+                                                                size_t ld_fine)
+  {
+    const int n = G.n_sub, NEp = G.N * n + 1, l = G.oversampling;
+    const int gn = blockIdx.x * 256 + threadIdx.x;
+    const int c0 = blockIdx.y * MULTI_TILE, nc = min(MULTI_TILE, n_rhs - c0);
+    if (gn >= NEp * NEp)
+      return;
+    const int X = gn % NEp, Y = gn / NEp;
+    const int cxl = max((X + n - 1) / n - 1 - l, 0), cxh = min(X / n + l, G.N - 1);
+    const int cyl = max((Y + n - 1) / n - 1 - l, 0), cyh = min(Y / n + l, G.N - 1);
+    double    acc[MULTI_TILE][S];
+#pragma unroll
+    for (int k = 0; k < MULTI_TILE; ++k)
+#pragma unroll
+      for (int c = 0; c < S; ++c)
+        acc[k][c] = 0.0;
+    for (int cy = cyl; cy <= cyh; ++cy)
+      for (int cx = cxl; cx <= cxh; ++cx)
+        {
+          const Extent e = grid_extent(G, cx, cy);
+          const int    ix = X - e.x0 * n, iy = Y - e.y0 * n;
+          if (ix < 0 || ix > e.mx * n || iy < 0 || iy > e.my * n)
+            continue;
+          const uint32_t p   = grid_pid(G, cx, cy);
+          const int      pnx = e.mx * n + 1, pnf = S * pnx * (e.my * n + 1);
+          const double  *phi = basis + (size_t)p * stride;
+#pragma unroll
+          for (int d = 0; d < S; ++d)
+            {
+              double ph[S];
+#pragma unroll
+              for (int c = 0; c < S; ++c)
+                ph[c] = phi[(size_t)d * pnf + S * (ix + iy * pnx) + c];
+              const double *ud = u + ((size_t)p * S + d) * ld_u + c0; // contiguous in the column
+#pragma unroll
+              for (int k = 0; k < MULTI_TILE; ++k)
+                if (k < nc)
+                  {
+                    const double uk = ud[k];
+#pragma unroll
+                    for (int c = 0; c < S; ++c)
+                      acc[k][c] = fma(ph[c], uk, acc[k][c]);
+                  }
+            }
+        }
+#pragma unroll
+    for (int k = 0; k < MULTI_TILE; ++k)
+      if (k < nc)
+#pragma unroll
+        for (int c = 0; c < S; ++c)
+          fine[(size_t)(c0 + k) * ld_fine + (size_t)gn * S + c] = acc[k][c];
+  }
+
   // ---- Jacobi-preconditioned CG on the block rows (device scalars: no host round trip per step)
   struct CgScalars
   {
@@ -1061,6 +1191,67 @@ int slod_lod_reconstruct(slod_handle *h, const double *d_basis, size_t stride, c
                      d_basis, stride, d_u, d_fine);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_reconstruct");
+}
+
+int slod_lod_rhs_multi(slod_handle *h, const uint32_t *rows, size_t n_rows, const double *d_basis, size_t stride,
+                       const double *d_fine_rhs, size_t ld_fine, int n_rhs, double *d_out, size_t ld_out, void *hip_stream)
+{
+  if (!h || (n_rows && (!rows || !d_basis || !d_fine_rhs || !d_out)))
+    return SLOD_ERR_ARGUMENT;
+  if (n_rhs < 1 || ld_out < (size_t)n_rhs)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_rhs_multi: n_rhs < 1 or ld_out < n_rhs");
+  if (ld_fine < (size_t)(h->NE + 1) * (h->NE + 1) * h->cfg.spacedim)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_rhs_multi: ld_fine shorter than a fine field");
+  if (n_rows == 0)
+    return SLOD_OK;
+  if (const int rc = slod_ensure_device(h))
+    return rc;
+  (void)hipSetDevice(h->cfg.device);
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  uint32_t   *d_rows = nullptr;
+  if (const int rc = upload_rows(h, rows, n_rows, &d_rows, st))
+    {
+      if (d_rows)
+        (void)hipFree(d_rows);
+      return rc;
+    }
+  const dim3 grid((unsigned)n_rows, (unsigned)((n_rhs + MULTI_TILE - 1) / MULTI_TILE));
+  if (h->cfg.spacedim == 1)
+    hipLaunchKernelGGL(k_lod_rhs_multi<1>, grid, dim3(256), 0, st, slod_grid_of(h), d_rows, d_basis, stride, d_fine_rhs, ld_fine,
+                       n_rhs, d_out, ld_out);
+  else
+    hipLaunchKernelGGL(k_lod_rhs_multi<2>, grid, dim3(256), 0, st, slod_grid_of(h), d_rows, d_basis, stride, d_fine_rhs, ld_fine,
+                       n_rhs, d_out, ld_out);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(st); // d_rows is freed below
+  (void)hipFree(d_rows);
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_rhs_multi");
+}
+
+int slod_lod_reconstruct_multi(slod_handle *h, const double *d_basis, size_t stride, const double *d_u, size_t ld_u, int n_rhs,
+                               double *d_fine, size_t ld_fine, void *hip_stream)
+{
+  if (!h || !d_basis || !d_u || !d_fine)
+    return SLOD_ERR_ARGUMENT;
+  if (n_rhs < 1 || ld_u < (size_t)n_rhs)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_reconstruct_multi: n_rhs < 1 or ld_u < n_rhs");
+  if (ld_fine < (size_t)(h->NE + 1) * (h->NE + 1) * h->cfg.spacedim)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_reconstruct_multi: ld_fine shorter than a fine field");
+  if (const int rc = slod_ensure_device(h))
+    return rc;
+  (void)hipSetDevice(h->cfg.device);
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  const int   NEp = h->NE + 1;
+  const dim3  grid((unsigned)((NEp * NEp + 255) / 256), (unsigned)((n_rhs + MULTI_TILE - 1) / MULTI_TILE));
+  if (h->cfg.spacedim == 1)
+    hipLaunchKernelGGL(k_lod_reconstruct_multi<1>, grid, dim3(256), 0, st, slod_grid_of(h), d_basis, stride, d_u, ld_u, n_rhs,
+                       d_fine, ld_fine);
+  else
+    hipLaunchKernelGGL(k_lod_reconstruct_multi<2>, grid, dim3(256), 0, st, slod_grid_of(h), d_basis, stride, d_u, ld_u, n_rhs,
+                       d_fine, ld_fine);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_reconstruct_multi");
 }
 
 int slod_device_patch_layout(slod_handle *h, const uint32_t *patch_ids, size_t n, slod_patch_info *out)

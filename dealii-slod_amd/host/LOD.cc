@@ -303,6 +303,75 @@ namespace slod
           "slod_compute_error_norms");
   }
 
+  // solve() for K loads: f_k at the points of quadrature_fine, [spacedim][NE][NE][4] per load
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_multi(const std::vector<const Function<dim> *> &loads)
+  {
+    if (!d_lod_values)
+      throw std::runtime_error("solve_multi: assemble_global_matrix comes first");
+    if (loads.empty())
+      throw std::runtime_error("solve_multi: no load");
+    const int          K = (int)loads.size();
+    const unsigned int n_patches = (unsigned int)patches.size();
+    const std::size_t  NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+    const std::size_t  n_qp = NE * NE * 4, fine_size = (NE + 1) * (NE + 1) * spacedim;
+    const double       hf = 1.0 / NE, g0 = 0.5 * (1.0 - 1.0 / std::sqrt(3.0)), g1 = 0.5 * (1.0 + 1.0 / std::sqrt(3.0));
+    std::vector<double> f_qp((std::size_t)K * spacedim * n_qp);
+    for (int k = 0; k < K; ++k)
+      for (int c = 0; c < spacedim; ++c)
+        for (std::size_t ey = 0; ey < NE; ++ey)
+          for (std::size_t ex = 0; ex < NE; ++ex)
+            for (unsigned int q = 0; q < 4; ++q)
+              {
+                Point<dim> p;
+                p(0) = (ex + ((q & 1) ? g1 : g0)) * hf;
+                p(1) = (ey + ((q & 2) ? g1 : g0)) * hf;
+                f_qp[((std::size_t)k * spacedim + c) * n_qp + (ey * NE + ex) * 4 + q] = loads[k]->value(p, (unsigned int)c);
+              }
+    double *d_f_qp = device_alloc<double>(f_qp.size());
+    if (hipMemcpy(d_f_qp, f_qp.data(), f_qp.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+      throw std::runtime_error("solve_multi: load upload failed");
+    d_multi_fem_rhs = device_alloc<double>((std::size_t)K * fine_size);
+    d_multi_fine    = device_alloc<double>((std::size_t)K * fine_size);
+    for (int k = 0; k < K; ++k)
+      check(slod_fem_rhs(handle, d_f_qp + (std::size_t)k * spacedim * n_qp, d_multi_fem_rhs + (std::size_t)k * fine_size, nullptr),
+            "slod_fem_rhs");
+    std::vector<uint32_t> rows(n_patches);
+    for (unsigned int p = 0; p < n_patches; ++p)
+      rows[p] = p;
+    const std::size_t n_coarse = (std::size_t)n_patches * spacedim;
+    double           *d_rhs = device_alloc<double>(n_coarse * K), *d_u = device_alloc<double>(n_coarse * K);
+    check(slod_lod_rhs_multi(handle, rows.data(), n_patches, d_basis, basis_stride, d_multi_fem_rhs, fine_size, K, d_rhs,
+                             (std::size_t)K, nullptr),
+          "slod_lod_rhs_multi");
+    lod_multi_iterations.assign(K, 0);
+    lod_multi_residuals.assign(K, 0.0);
+    check(slod_lod_solve_multi(handle, d_lod_values, d_lod_cols, d_rhs, (std::size_t)K, K, d_u, (std::size_t)K, lod_rel_tol,
+                               lod_max_iterations, lod_multi_iterations.data(), lod_multi_residuals.data()),
+          "slod_lod_solve_multi");
+    check(slod_lod_reconstruct_multi(handle, d_basis, basis_stride, d_u, (std::size_t)K, K, d_multi_fine, fine_size, nullptr),
+          "slod_lod_reconstruct_multi");
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::compare_multi_with_fem()
+  {
+    if (!d_multi_fine)
+      throw std::runtime_error("compare_multi_with_fem: solve_multi comes first");
+    const std::size_t NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+    const std::size_t fine_size = (NE + 1) * (NE + 1) * spacedim;
+    double           *d_fem_u = device_alloc<double>(fine_size);
+    lod_multi_fem_error.assign(lod_multi_iterations.size(), slod_error_norms{});
+    for (std::size_t k = 0; k < lod_multi_fem_error.size(); ++k)
+      {
+        check(slod_fem_solve(handle, 0, d_multi_fem_rhs + k * fine_size, d_fem_u, fem_rel_tol, fem_max_iterations, nullptr),
+              "slod_fem_solve");
+        check(slod_compute_error_norms(handle, 0, d_fem_u, d_multi_fine + k * fine_size, nullptr, nullptr,
+                                       &lod_multi_fem_error[k], nullptr),
+              "slod_compute_error_norms");
+      }
+  }
+
   // LOD.cc:1103-1237 with f = 1.  The reference solves with SolverDirect; the CG of the fine problem runs on the
   // coarse grid to the tolerance of the fine solve.
   template <int dim, int spacedim>

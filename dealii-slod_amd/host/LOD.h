@@ -111,6 +111,15 @@ namespace slod
     void solve();
     // u_LOD = C u_H and the norms of u_h - u_LOD (error_LOD_FEMh.difference, LOD.cc:1240-1260)
     void compare_lod_with_fem();
+    // solve() for K load functions at once, after assemble_global_matrix() (the reference has a single load):
+    // the fine load vectors of loads[k] sampled at the quadrature points, then C^T F, A_LOD U = C^T F and
+    // U_fine = C U through slod_lod_rhs_multi / slod_lod_solve_multi / slod_lod_reconstruct_multi.
+    void solve_multi(const std::vector<const Function<dim> *> &loads);
+    const std::vector<int>    &multi_iterations() const { return lod_multi_iterations; }
+    const std::vector<double> &multi_rel_residuals() const { return lod_multi_residuals; }
+    // per load: the fine FEM solution of that load and the norms of u_h - u_LOD (compare_lod_with_fem per column)
+    void compare_multi_with_fem();
+    const std::vector<slod_error_norms> &error_multi_LOD_FEMh() const { return lod_multi_fem_error; }
     const slod_error_norms &error_LOD_FEMh() const { return lod_fem_error; }
     // the same norms of u_h alone (the denominators of relative errors)
     const slod_error_norms &norms_FEMh() const { return fem_norms; }
@@ -159,6 +168,11 @@ namespace slod
     double             *d_fem_rhs = nullptr, *d_fem_solution = nullptr, *d_lod_u = nullptr;
     double             *d_fem_coarse_solution = nullptr, *d_fem_coarse_interpolated = nullptr;
     slod_error_norms    lod_fem_error{}, fem_norms{}, femH_fem_error{};
+    // solve_multi: fine load vectors and reconstructions, field k at + k * fine_size
+    double                       *d_multi_fem_rhs = nullptr, *d_multi_fine = nullptr;
+    std::vector<int>              lod_multi_iterations;
+    std::vector<double>           lod_multi_residuals;
+    std::vector<slod_error_norms> lod_multi_fem_error;
 
     void check(const int status, const char *what) const;
     template <typename T>

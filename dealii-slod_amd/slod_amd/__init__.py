@@ -113,6 +113,10 @@ def load():
     lib.slod_lod_rhs.argtypes = [vp, u32p, C.c_size_t, vp, C.c_size_t, vp, vp, vp]
     lib.slod_lod_solve.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.c_int, dp]
     lib.slod_lod_reconstruct.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
+    lib.slod_lod_rhs_multi.argtypes = [vp, u32p, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp]
+    lib.slod_lod_solve_multi.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_double, C.c_int,
+                                         C.POINTER(C.c_int), dp]
+    lib.slod_lod_reconstruct_multi.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp]
     lib.slod_fem_rhs.argtypes = [vp, vp, vp, vp]
     lib.slod_fem_solve.argtypes = [vp, C.c_uint32, vp, vp, C.c_double, C.c_int, dp]
     lib.slod_coarse_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, vp]
@@ -351,6 +355,26 @@ class Slod:
 
     def lod_reconstruct(self, d_basis, stride, d_u, d_fine, stream=None):
         self._check(self.lib.slod_lod_reconstruct(self.h, d_basis, stride, d_u, d_fine, stream))
+
+    # ---- the same three steps for n_rhs load vectors at once.  Fine multi-vectors: field c at + c * ld_fine;
+    # coarse multi-vectors interleaved, entry (i, c) at [i * ld + c] (include/slod.h) ----
+    def lod_rhs_multi(self, rows, d_basis, stride, d_fine_rhs, ld_fine, n_rhs, d_out, ld_out, stream=None):
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        self._check(self.lib.slod_lod_rhs_multi(self.h, rows.ctypes.data_as(C.POINTER(C.c_uint32)), len(rows), d_basis,
+                                                stride, d_fine_rhs, ld_fine, n_rhs, d_out, ld_out, stream))
+
+    def lod_solve_multi(self, d_values, d_cols, d_rhs, ld_rhs, n_rhs, d_u, ld_u, rel_tol=1e-12, max_iterations=2000):
+        """Returns (iterations, rel_residual), one entry per column; max(iterations) is the C call's return value."""
+        its = np.zeros(max(n_rhs, 1), dtype=np.intc)
+        res = np.zeros(max(n_rhs, 1))
+        rc = self.lib.slod_lod_solve_multi(self.h, d_values, d_cols, d_rhs, ld_rhs, n_rhs, d_u, ld_u, rel_tol,
+                                           max_iterations, its.ctypes.data_as(C.POINTER(C.c_int)), _dp(res))
+        if rc < 0:
+            self._check(rc)
+        return its[:n_rhs], res[:n_rhs]
+
+    def lod_reconstruct_multi(self, d_basis, stride, d_u, ld_u, n_rhs, d_fine, ld_fine, stream=None):
+        self._check(self.lib.slod_lod_reconstruct_multi(self.h, d_basis, stride, d_u, ld_u, n_rhs, d_fine, ld_fine, stream))
 
     def fem_rhs(self, d_f_qp, d_fine_rhs, stream=None):
         """Fine FEM load vector (d_f_qp = None: f = 1)."""

@@ -217,6 +217,49 @@ int slod_lod_solve(slod_handle *h, const double *d_values, const uint32_t *d_col
 int slod_lod_reconstruct(slod_handle *h, const double *d_basis, size_t stride, const double *d_u,
                          double *d_fine, void *hip_stream);
 
+/* ---- the same three steps for n_rhs load vectors at once -----------------------------
+ * The basis is built once and serves many right-hand sides (load cases, time steps, parameter studies):
+ * one call per step for all of them instead of n_rhs calls (the reference solves a single load,
+ * LOD.cc:976-1002).  slod_lod_rhs, slod_lod_solve and slod_lod_reconstruct are the case n_rhs = 1.
+ * Layouts:
+ *   fine multi-vector    n_rhs fields, each in the layout of the single-vector call ([(NE+1)^2][s],
+ *                        lexicographic, component-minor); field c starts at base + c * ld_fine,
+ *                        ld_fine >= (NE+1)^2 * s.  A field is what slod_fem_rhs writes.
+ *   coarse multi-vector  (d_out, d_rhs, d_u) interleaved: entry (i, c) of the num_patches * s unknowns at
+ *                        base[i * ld + c], ld >= n_rhs: the n_rhs values of one row are contiguous, which is
+ *                        what lets the matrix product read them coalesced.  n_rhs = 1, ld = 1 is the
+ *                        single-vector layout; a column sub-range of a wider array is base + first column.
+ * Entries c >= n_rhs inside a row's ld are never read or written.  SLOD_ERR_ARGUMENT (before any device work):
+ * NULL handle or array, n_rhs < 1, ld < n_rhs, ld_fine shorter than a field, max_iterations < 0. */
+/* d_out[(k * s + d) * ld_out + c] = sum_i phi_{rows[k],d}(i) f_c(i)  (slod_lod_rhs per column, bit for bit).
+ * SYNCHRONISES hip_stream (the row list is uploaded, as in slod_lod_rhs). */
+int slod_lod_rhs_multi(slod_handle *h, const uint32_t *rows, size_t n_rows, const double *d_basis, size_t stride,
+                       const double *d_fine_rhs, size_t ld_fine, int n_rhs,
+                       double *d_out, size_t ld_out, void *hip_stream);
+/* A_LOD u_c = rhs_c for every column c.  Each column runs the Jacobi-preconditioned CG recurrence of
+ * slod_lod_solve with its own alpha, beta, r.z and r.r, from u = 0, and has converged when
+ * r.r <= rel_tol^2 ||rhs_c||^2; that is checked every 8 iterations (the last burst is min(8, max_iterations - it)).
+ * These are n_rhs independent recurrences that share the reads of the matrix and the kernel launches (three per
+ * iteration for all columns), not a block-Krylov method.  A column that passes its check is frozen: its u is not
+ * written again.  A zero column gives u = 0, 0 iterations, residual 0.  The loop ends when every column is frozen
+ * or at max_iterations (not an error, as in slod_lod_solve).
+ * Dot products are summed in a fixed order (no atomics): the bits of column c of d_u, and iterations[c], depend
+ * only on the matrix and on column c of d_rhs -- not on n_rhs, the column's position, ld, the other columns or
+ * the run.  Any n_rhs >= 1; device workspace of 4 * num_patches * s * n_rhs doubles, allocated per call.
+ * Returns the largest per-column iteration count or a negative slod_status; iterations[c] and rel_residual[c]
+ * = ||r_c|| / ||rhs_c|| are HOST arrays of n_rhs entries (either may be NULL).  Runs on the handle's stream;
+ * synchronises. */
+int slod_lod_solve_multi(slod_handle *h, const double *d_values, const uint32_t *d_cols,
+                         const double *d_rhs, size_t ld_rhs, int n_rhs, double *d_u, size_t ld_u,
+                         double rel_tol, int max_iterations,
+                         int *iterations /* HOST [n_rhs], may be NULL */,
+                         double *rel_residual /* HOST [n_rhs], may be NULL */);
+/* field c of d_fine = C u_c (slod_lod_reconstruct on column c, bit for bit: the covering patches are
+ * visited in the same order).  Asynchronous on hip_stream. */
+int slod_lod_reconstruct_multi(slod_handle *h, const double *d_basis, size_t stride,
+                               const double *d_u, size_t ld_u, int n_rhs,
+                               double *d_fine, size_t ld_fine, void *hip_stream);
+
 /* ---- fine FEM reference problem (assemble_and_solve_fem_problem, LOD.cc:1004-1094) ----
  * What the reference compares the LOD solution with (compare_lod_with_fem, LOD.cc:1240-1378).
  * fem_rhs of assemble_stiffness (Diffusion.h:149-193) on the global fine grid, [(NE+1)^2][s],
