@@ -1,5 +1,6 @@
 // Counterpart of reference app/main_Diffusion.cc for the basis-construction path:
 //   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare] [--coarse] [--loads K]
+//                  [--heat STEPS DT]
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
 // file name it dumps, per patch, phi and psi in patch-lexicographic order (parity tests).
 // --compare (anywhere on the command line): after run(), the rest of the reference run() -- global
@@ -10,6 +11,9 @@
 // --loads K: the LOD system for the K loads f_k = sin(k pi x) sin(pi y), k = 1 .. K, in one multi-vector solve
 // (slod_lod_solve_multi); one line per load with its iterations and relative residual, with --compare also the
 // L2 and energy error against the fine FEM solution of that load.
+// --heat STEPS DT: the heat flow  M u' + A u = C^T f  (f = 1, constant in time) from u = 0 by STEPS backward Euler steps
+// of size DT on the LOD space (slod_lod_theta_steps): one line per step with its iterations and relative residual, then
+// the table "SLOD heat flow at T = STEPS DT vs elliptic SLOD solution", which shrinks as STEPS DT grows.
 #include "../host/Diffusion.h"
 
 #include <cstdio>
@@ -63,7 +67,8 @@ int main(int argc_all, char **argv_all)
 {
   // --compare and --coarse are taken out wherever they stand; the positional arguments keep their meaning
   bool               compare = false, coarse = false;
-  int                n_loads = 0;
+  int                n_loads = 0, heat_steps = 0;
+  double             heat_dt = 0.0;
   std::vector<char *> args;
   for (int i = 0; i < argc_all; ++i)
     if (i > 0 && !std::strcmp(argv_all[i], "--compare"))
@@ -72,6 +77,11 @@ int main(int argc_all, char **argv_all)
       compare = coarse = true;
     else if (i > 0 && !std::strcmp(argv_all[i], "--loads") && i + 1 < argc_all)
       n_loads = std::atoi(argv_all[++i]);
+    else if (i > 0 && !std::strcmp(argv_all[i], "--heat") && i + 2 < argc_all)
+      {
+        heat_steps = std::atoi(argv_all[++i]);
+        heat_dt    = std::atof(argv_all[++i]);
+      }
     else
       args.push_back(argv_all[i]);
   const int argc = (int)args.size();
@@ -146,6 +156,30 @@ int main(int argc_all, char **argv_all)
                 std::printf("load %d: L2 error = %.12e, energy error = %.12e\n", k + 1,
                             problem.error_multi_LOD_FEMh()[k].l2[0], problem.error_multi_LOD_FEMh()[k].energy);
             }
+        }
+      if (heat_steps > 0)
+        {
+          if (!compare)
+            {
+              if (n_loads <= 0)
+                problem.assemble_global_matrix();
+              problem.assemble_and_solve_fem_problem();
+              problem.solve();
+            }
+          problem.assemble_mass_matrix();
+          problem.solve_heat((unsigned int)heat_steps, heat_dt, 1.0);
+          problem.compare_heat_with_lod();
+          for (int k = 0; k < heat_steps; ++k)
+            std::printf("heat step %d: iterations = %d, relative residual = %.6e\n", k + 1, problem.heat_iterations()[k],
+                        problem.heat_rel_residuals()[k]);
+          const slod_error_norms &e = problem.error_heat_LOD(), &u = problem.norms_LOD();
+          const double h1 = std::sqrt(e.l2[0] * e.l2[0] + e.h1_semi[0] * e.h1_semi[0]),
+                       uh1 = std::sqrt(u.l2[0] * u.l2[0] + u.h1_semi[0] * u.h1_semi[0]);
+          std::printf("SLOD heat flow at T = %g vs elliptic SLOD solution\n", heat_steps * heat_dt);
+          std::printf("  L2     error = %.12e  (relative %.6e)\n", e.l2[0], e.l2[0] / u.l2[0]);
+          std::printf("  H1     error = %.12e  (relative %.6e)\n", h1, h1 / uh1);
+          std::printf("  Linfty error = %.12e  (relative %.6e)\n", e.linf[0], e.linf[0] / u.linf[0]);
+          std::printf("  energy error = %.12e  (relative %.6e)\n", e.energy, e.energy / u.energy);
         }
     }
   catch (std::exception &exc)

@@ -99,4 +99,9 @@ inline void slod_desc_to_info(const slod_handle *h, const SlodPatchDesc &d, slod
 hipError_t slod_build_descriptors(const slod_handle *h, const uint32_t *gids, size_t n, const uint64_t *offsets, size_t stride,
                                   int n_cu, bool balance, SlodPatchDesc *d_desc, SlodPatchDesc *d_desc_bal, SlodPlanSummary *sum,
                                   std::vector<char> *prob_used);
+// slod_lod_solve_multi on a workspace the caller owns (slod_lod_multi.hip; used by the time loop of slod_lod_time.hip)
+size_t     slod_mcg_work_doubles(const slod_handle *h, int n_rhs);
+hipError_t slod_mcg_solve(slod_handle *h, const double *d_values, const uint32_t *d_cols, const double *d_rhs, size_t ld_rhs,
+                          int n_rhs, double *d_u, size_t ld_u, double rel_tol, int max_iterations, double *work, int *d_active,
+                          int *its, double *rel_residual);
 #endif

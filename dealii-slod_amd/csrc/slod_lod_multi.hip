@@ -19,6 +19,7 @@
 // k_mcg_check sums the r.r partials and freezes the columns that have converged (their u is not written
 // again); the host reads the flags back.
 #include "slod_host.h"
+#include "slod_lod_rows.hip.h"
 
 #include <algorithm>
 #include <cmath>
@@ -123,23 +124,7 @@ namespace
             double    prod = 0.0;
             if (i < nrow && V.active[col])
               {
-                const int    p = i / s, d = i - p * s;
-                const size_t slot0 = (size_t)p * cap;
-                double       acc = 0.0;
-                for (int j = 0; j < cap; ++j)
-                  {
-                    // an unused slot (0xffffffff; anything >= NP) reads the row's own patch and adds nothing:
-                    // no branch, so lanes of different rows stay together
-                    const uint32_t q = cols[slot0 + j];
-                    const bool     used = q < (uint32_t)NP;
-                    const size_t   qs = (size_t)(used ? q : (uint32_t)p) * s;
-                    const double  *a = values + (slot0 + j) * s * s + d * s;
-                    for (int e = 0; e < s; ++e)
-                      {
-                        const double t = fma(a[e], V.p[(qs + e) * n_rhs + col], acc);
-                        acc            = used ? t : acc;
-                      }
-                  }
+                const double acc = slod_lod_row_product(i, s, cap, NP, values, cols, V.p, (size_t)n_rhs, col);
                 const size_t w = (size_t)i * n_rhs + col;
                 V.Ap[w]        = acc;
                 prod           = acc * V.p[w];
@@ -233,6 +218,90 @@ namespace
   }
 } // namespace
 
+// Doubles of device workspace one solve needs: 4 vectors, D^-1, 4 partial arrays, 2 per-column scalars.
+size_t slod_mcg_work_doubles(const slod_handle *h, int n_rhs)
+{
+  const size_t nrow = (size_t)h->NP * h->cfg.spacedim, ngroup = (nrow + MCG_ROWS - 1) / MCG_ROWS;
+  return 4 * nrow * n_rhs + nrow + 4 * ngroup * n_rhs + 2 * (size_t)n_rhs;
+}
+
+// The solve of slod_lod_solve_multi on a workspace the caller owns (work: slod_mcg_work_doubles() doubles, d_active:
+// n_rhs ints), so that a time loop allocates once (slod_lod_theta_steps).  Arguments are checked by the caller; the
+// handle's device is current.  its: HOST [n_rhs]; rel_residual: HOST [n_rhs] or NULL.  Synchronises h->stream.
+hipError_t slod_mcg_solve(slod_handle *h, const double *d_values, const uint32_t *d_cols, const double *d_rhs, size_t ld_rhs,
+                          int n_rhs, double *d_u, size_t ld_u, double rel_tol, int max_iterations, double *work, int *d_active,
+                          int *its, double *rel_residual)
+{
+  hipStream_t  st = h->stream;
+  const int    s = h->cfg.spacedim, cap = slod_lod_row_capacity(h), NP = h->NP, nrow = NP * s;
+  const int    ngroup = (nrow + MCG_ROWS - 1) / MCG_ROWS, nchunk = (n_rhs + MCG_COLS - 1) / MCG_COLS;
+  const size_t nvec = (size_t)nrow * n_rhs, npart = (size_t)ngroup * n_rhs;
+  const dim3   grid((unsigned)std::min(ngroup, MCG_MAX_BLOCKS), (unsigned)nchunk), block(MCG_BLOCK);
+  std::vector<int> active((size_t)n_rhs, 1);
+  std::fill(its, its + n_rhs, 0);
+  int        it = 0;
+  McgVectors V{};
+  V.r       = work;
+  V.z       = V.r + nvec;
+  V.p       = V.z + nvec;
+  V.Ap      = V.p + nvec;
+  V.dinv    = V.Ap + nvec;
+  V.pAp     = V.dinv + nrow;
+  V.rz[0]   = V.pAp + npart;
+  V.rz[1]   = V.rz[0] + npart;
+  V.rr      = V.rz[1] + npart;
+  V.rhs2    = V.rr + npart;
+  V.rr_last = V.rhs2 + n_rhs;
+  V.active  = d_active;
+  const double   tol2 = rel_tol * rel_tol;
+  const unsigned ncheck = (unsigned)((n_rhs + MCG_BLOCK - 1) / MCG_BLOCK);
+  hipLaunchKernelGGL(k_mcg_diag, dim3((unsigned)((nrow + MCG_BLOCK - 1) / MCG_BLOCK)), block, 0, st, nrow, s, cap, d_values, d_cols,
+                     V.dinv);
+  hipLaunchKernelGGL(k_mcg_init, grid, block, 0, st, nrow, n_rhs, ngroup, d_rhs, ld_rhs, d_u, ld_u, V);
+  hipLaunchKernelGGL(k_mcg_check, dim3(ncheck), block, 0, st, n_rhs, ngroup, tol2, 1, V);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(active.data(), d_active, (size_t)n_rhs * sizeof(int), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(st);
+  std::vector<int> was_active = active;
+  bool             any = e == hipSuccess && std::find(active.begin(), active.end(), 1) != active.end();
+  while (e == hipSuccess && any && it < max_iterations)
+    {
+      // a few iterations per convergence check: the scalars stay on the device in between
+      const int burst = std::min(8, max_iterations - it);
+      for (int b = 0; b < burst; ++b)
+        {
+          const int par = (it + b) & 1;
+          hipLaunchKernelGGL(k_mcg_spmv, grid, block, 0, st, nrow, s, cap, NP, n_rhs, ngroup, d_values, d_cols, V);
+          hipLaunchKernelGGL(k_mcg_update_xr, grid, block, 0, st, nrow, n_rhs, ngroup, par, d_u, ld_u, V);
+          hipLaunchKernelGGL(k_mcg_update_p, grid, block, 0, st, nrow, n_rhs, ngroup, par, V);
+        }
+      it += burst;
+      hipLaunchKernelGGL(k_mcg_check, dim3(ncheck), block, 0, st, n_rhs, ngroup, tol2, 0, V);
+      e = hipGetLastError();
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(active.data(), d_active, (size_t)n_rhs * sizeof(int), hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess)
+        e = hipStreamSynchronize(st);
+      // a column that was active during the burst has done `it` iterations, frozen now or not
+      for (int c = 0; c < n_rhs && e == hipSuccess; ++c)
+        if (was_active[c])
+          its[c] = it;
+      was_active = active;
+      any        = e == hipSuccess && std::find(active.begin(), active.end(), 1) != active.end();
+    }
+  std::vector<double> sc(2 * (size_t)n_rhs);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(sc.data(), V.rhs2, sc.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(st);
+  if (e == hipSuccess && rel_residual)
+    for (int c = 0; c < n_rhs; ++c)
+      rel_residual[c] = sc[c] > 0.0 ? std::sqrt(sc[(size_t)n_rhs + c] / sc[c]) : 0.0;
+  return e;
+}
+
 #pragma GCC visibility push(default)
 extern "C" {
 
@@ -249,86 +318,18 @@ int slod_lod_solve_multi(slod_handle *h, const double *d_values, const uint32_t 
   if (const int rc = slod_ensure_device(h))
     return rc;
   (void)hipSetDevice(h->cfg.device);
-  hipStream_t  st = h->stream;
-  const int    s = h->cfg.spacedim, cap = slod_lod_row_capacity(h), NP = h->NP, nrow = NP * s;
-  const int    ngroup = (nrow + MCG_ROWS - 1) / MCG_ROWS, nchunk = (n_rhs + MCG_COLS - 1) / MCG_COLS;
-  const size_t nvec = (size_t)nrow * n_rhs, npart = (size_t)ngroup * n_rhs;
-  const dim3   grid((unsigned)std::min(ngroup, MCG_MAX_BLOCKS), (unsigned)nchunk), block(MCG_BLOCK);
-  // one allocation: 4 vectors, D^-1, 4 partial arrays, 2 per-column scalars, the flags
+  // workspace allocated per call
   double    *work = nullptr;
   int       *d_active = nullptr;
-  hipError_t e = hipMalloc((void **)&work, (4 * nvec + (size_t)nrow + 4 * npart + 2 * (size_t)n_rhs) * sizeof(double));
+  hipError_t e = hipMalloc((void **)&work, slod_mcg_work_doubles(h, n_rhs) * sizeof(double));
   if (e == hipSuccess)
     e = hipMalloc((void **)&d_active, (size_t)n_rhs * sizeof(int));
-  std::vector<int> active((size_t)n_rhs, 1), its((size_t)n_rhs, 0);
-  int              it = 0;
-  McgVectors       V{};
+  std::vector<int> its((size_t)n_rhs, 0);
   if (e == hipSuccess)
-    {
-      V.r       = work;
-      V.z       = V.r + nvec;
-      V.p       = V.z + nvec;
-      V.Ap      = V.p + nvec;
-      V.dinv    = V.Ap + nvec;
-      V.pAp     = V.dinv + nrow;
-      V.rz[0]   = V.pAp + npart;
-      V.rz[1]   = V.rz[0] + npart;
-      V.rr      = V.rz[1] + npart;
-      V.rhs2    = V.rr + npart;
-      V.rr_last = V.rhs2 + n_rhs;
-      V.active  = d_active;
-      const double   tol2 = rel_tol * rel_tol;
-      const unsigned ncheck = (unsigned)((n_rhs + MCG_BLOCK - 1) / MCG_BLOCK);
-      hipLaunchKernelGGL(k_mcg_diag, dim3((unsigned)((nrow + MCG_BLOCK - 1) / MCG_BLOCK)), block, 0, st, nrow, s, cap, d_values,
-                         d_cols, V.dinv);
-      hipLaunchKernelGGL(k_mcg_init, grid, block, 0, st, nrow, n_rhs, ngroup, d_rhs, ld_rhs, d_u, ld_u, V);
-      hipLaunchKernelGGL(k_mcg_check, dim3(ncheck), block, 0, st, n_rhs, ngroup, tol2, 1, V);
-      e = hipGetLastError();
-      if (e == hipSuccess)
-        e = hipMemcpyAsync(active.data(), d_active, (size_t)n_rhs * sizeof(int), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess)
-        e = hipStreamSynchronize(st);
-      std::vector<int> was_active = active;
-      bool             any = e == hipSuccess && std::find(active.begin(), active.end(), 1) != active.end();
-      while (e == hipSuccess && any && it < max_iterations)
-        {
-          // a few iterations per convergence check: the scalars stay on the device in between
-          const int burst = std::min(8, max_iterations - it);
-          for (int b = 0; b < burst; ++b)
-            {
-              const int par = (it + b) & 1;
-              hipLaunchKernelGGL(k_mcg_spmv, grid, block, 0, st, nrow, s, cap, NP, n_rhs, ngroup, d_values, d_cols, V);
-              hipLaunchKernelGGL(k_mcg_update_xr, grid, block, 0, st, nrow, n_rhs, ngroup, par, d_u, ld_u, V);
-              hipLaunchKernelGGL(k_mcg_update_p, grid, block, 0, st, nrow, n_rhs, ngroup, par, V);
-            }
-          it += burst;
-          hipLaunchKernelGGL(k_mcg_check, dim3(ncheck), block, 0, st, n_rhs, ngroup, tol2, 0, V);
-          e = hipGetLastError();
-          if (e == hipSuccess)
-            e = hipMemcpyAsync(active.data(), d_active, (size_t)n_rhs * sizeof(int), hipMemcpyDeviceToHost, st);
-          if (e == hipSuccess)
-            e = hipStreamSynchronize(st);
-          // a column that was active during the burst has done `it` iterations, frozen now or not
-          for (int c = 0; c < n_rhs && e == hipSuccess; ++c)
-            if (was_active[c])
-              its[c] = it;
-          was_active = active;
-          any        = e == hipSuccess && std::find(active.begin(), active.end(), 1) != active.end();
-        }
-      std::vector<double> sc(2 * (size_t)n_rhs);
-      if (e == hipSuccess)
-        e = hipMemcpyAsync(sc.data(), V.rhs2, sc.size() * sizeof(double), hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess)
-        e = hipStreamSynchronize(st);
-      if (e == hipSuccess)
-        for (int c = 0; c < n_rhs; ++c)
-          {
-            if (iterations)
-              iterations[c] = its[c];
-            if (rel_residual)
-              rel_residual[c] = sc[c] > 0.0 ? std::sqrt(sc[(size_t)n_rhs + c] / sc[c]) : 0.0;
-          }
-    }
+    e = slod_mcg_solve(h, d_values, d_cols, d_rhs, ld_rhs, n_rhs, d_u, ld_u, rel_tol, max_iterations, work, d_active, its.data(),
+                       rel_residual);
+  if (e == hipSuccess && iterations)
+    std::copy(its.begin(), its.end(), iterations);
   if (work)
     (void)hipFree(work);
   if (d_active)

@@ -1,0 +1,352 @@
+// The L2 side of the coarse problem and a time loop on it (the reference has no counterpart: it solves one
+// stationary problem, LOD.cc:976-1002):
+//   slod_lod_mass_matrix     block rows of  M_LOD = C^T M_rho C  in the layout and pattern of slod_lod_matrix
+//   slod_lod_apply_multi     Y = A X for any matrix in that layout, columns on lanes
+//   slod_lod_matrix_combine  out = alpha A + beta B on two values arrays of one pattern
+//   slod_lod_theta_steps     n_steps of the theta scheme for  M u' + A u = b(t), the state stays on the device
+// The mass kernel is an L2/HBM-bound gather like k_lod_matrix (slod_global.hip) and shares its index calculus
+// (slod_grid.hip.h); the solve of a step is the recurrence of slod_lod_solve_multi (slod_lod_multi.hip) on a
+// workspace this file owns for the whole loop.
+#include "slod_host.h"
+#include "slod_grid.hip.h"
+#include "slod_lod_rows.hip.h"
+
+#include <algorithm>
+#include <vector>
+
+namespace
+{
+  // ---------------------------------------------------------------------------------
+  // M_LOD block rows.  Block = one row patch p, wave w = the candidate neighbours j = w, w+4, ... as in
+  // k_lod_matrix; lanes = the fine elements of the intersection rectangle of the two closed patches (phi vanishes
+  // on every patch rim, so these elements carry the whole integral).  Lanes run along ix: the corner loads of
+  // neighbouring lanes are neighbouring doubles (spacedim 1) or neighbouring pairs (spacedim 2).
+  //
+  // Element form, Q1 consistent mass rho h^2/36 [[4,2,2,1],[2,4,1,2],[2,1,4,2],[1,2,2,4]] = rho h^2/36 (J+I)x(J+I):
+  //   p^T (J+I)x(J+I) q = (sum p)(sum q) + sum_rows (row sum p)(row sum q) + sum_cols (col sum p)(col sum q) + p.q
+  // Every product pairs a quantity of p with the same quantity of q and nothing is contracted into an fma, so the
+  // form is symmetric in (p, q) bit for bit; with the same lanes, the same component order and the same wave
+  // reduction on both sides, M[(p,d),(q,e)] and M[(q,e),(p,d)] are the same bits.
+  // ---------------------------------------------------------------------------------
+  template <int S>
+  __global__ __launch_bounds__(256) void k_lod_mass(const SlodGrid G, const uint32_t *rows, const double *basis, size_t stride,
+                                                   const double *rho, double scale, double *values, uint32_t *cols)
+  {
+#pragma clang fp contract(off)
+    const int      lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int      n = G.n_sub, NE = G.N * n, span = 4 * G.oversampling + 3, cap = span * span;
+    const uint32_t p = rows[blockIdx.x];
+    int            pcx, pcy;
+    grid_centre(G, p, pcx, pcy);
+    const Extent  pe = grid_extent(G, pcx, pcy);
+    const int     pnx = pe.mx * n + 1, pny = pe.my * n + 1, pnf = S * pnx * pny;
+    const double *phi = basis + (size_t)p * stride;
+    for (int j = wave; j < cap; j += 4)
+      {
+        const int    qcx = pcx + j % span - (span / 2), qcy = pcy + j / span - (span / 2);
+        const size_t out = (size_t)blockIdx.x * cap + j;
+        if (qcx < 0 || qcx >= G.N || qcy < 0 || qcy >= G.N)
+          {
+            if (lane == 0)
+              cols[out] = 0xffffffffu;
+            if (lane < S * S)
+              values[out * S * S + lane] = 0.0;
+            continue;
+          }
+        const uint32_t q  = grid_pid(G, qcx, qcy);
+        const Extent   qe = grid_extent(G, qcx, qcy);
+        const int      qnx = qe.mx * n + 1, qny = qe.my * n + 1, qnf = S * qnx * qny;
+        // overlap in global fine-node coordinates (inclusive): w x hgt nodes, (w - 1) x (hgt - 1) elements
+        const int xa = max(pe.x0, qe.x0) * n, xb = min(pe.x0 + pe.mx, qe.x0 + qe.mx) * n;
+        const int ya = max(pe.y0, qe.y0) * n, yb = min(pe.y0 + pe.my, qe.y0 + qe.my) * n;
+        const int w = xb - xa + 1, hgt = yb - ya + 1;
+        double    acc[S][S];
+#pragma unroll
+        for (int d = 0; d < S; ++d)
+#pragma unroll
+          for (int e = 0; e < S; ++e)
+            acc[d][e] = 0.0;
+        if (w > 1 && hgt > 1)
+          {
+            const double *phq = basis + (size_t)q * stride;
+            const int     we = w - 1;
+            for (int idx = lane; idx < we * (hgt - 1); idx += 64)
+              {
+                const int    iy = idx / we, ix = idx - iy * we;
+                const int    np = (xa + ix - pe.x0 * n) + (ya + iy - pe.y0 * n) * pnx;
+                const int    nq = (xa + ix - qe.x0 * n) + (ya + iy - qe.y0 * n) * qnx;
+                const double r  = rho ? rho[(size_t)(ya + iy) * NE + (xa + ix)] : 1.0;
+#pragma unroll
+                for (int c = 0; c < S; ++c)
+                  {
+                    // corner values and their sums, [d] of the row patch, [e] of the column patch
+                    double a[S][4], b[S][4];
+#pragma unroll
+                    for (int d = 0; d < S; ++d)
+                      {
+                        const double *v = phi + (size_t)d * pnf + c;
+                        a[d][0]         = v[S * np];
+                        a[d][1]         = v[S * (np + 1)];
+                        a[d][2]         = v[S * (np + pnx)];
+                        a[d][3]         = v[S * (np + pnx + 1)];
+                        const double *u = phq + (size_t)d * qnf + c;
+                        b[d][0]         = u[S * nq];
+                        b[d][1]         = u[S * (nq + 1)];
+                        b[d][2]         = u[S * (nq + qnx)];
+                        b[d][3]         = u[S * (nq + qnx + 1)];
+                      }
+#pragma unroll
+                    for (int d = 0; d < S; ++d)
+#pragma unroll
+                      for (int e = 0; e < S; ++e)
+                        {
+                          const double ar0 = a[d][0] + a[d][1], ar1 = a[d][2] + a[d][3];
+                          const double ac0 = a[d][0] + a[d][2], ac1 = a[d][1] + a[d][3];
+                          const double br0 = b[e][0] + b[e][1], br1 = b[e][2] + b[e][3];
+                          const double bc0 = b[e][0] + b[e][2], bc1 = b[e][1] + b[e][3];
+                          const double all = (ar0 + ar1) * (br0 + br1);
+                          const double row = ar0 * br0 + ar1 * br1;
+                          const double col = ac0 * bc0 + ac1 * bc1;
+                          const double dot = (a[d][0] * b[e][0] + a[d][1] * b[e][1]) + (a[d][2] * b[e][2] + a[d][3] * b[e][3]);
+                          acc[d][e]        = acc[d][e] + r * ((all + dot) + (row + col));
+                        }
+                  }
+              }
+          }
+#pragma unroll
+        for (int d = 0; d < S; ++d)
+#pragma unroll
+          for (int e = 0; e < S; ++e)
+            {
+              double v = acc[d][e];
+              for (int off = 32; off > 0; off >>= 1)
+                v += __shfl_xor(v, off, 64);
+              if (lane == 0)
+                values[out * S * S + d * S + e] = v * scale;
+            }
+        // the pattern is that of k_lod_matrix: a pair that shares only a line of nodes keeps its column, value 0
+        if (lane == 0)
+          cols[out] = (w > 0 && hgt > 0) ? q : 0xffffffffu;
+      }
+  }
+
+  // ---------------------------------------------------------------------------------
+  // Y = A X on the block rows, the tiling of k_mcg_spmv: columns in chunks of 64 on lanes (blockIdx.y), a block
+  // takes groups of 16 consecutive rows and spreads the (row, column) items over its threads, row-major.  The row
+  // product is the one the CG uses (slod_lod_rows.hip.h): the bits of a column depend on the matrix and that column.
+  // ---------------------------------------------------------------------------------
+  constexpr int AP_COLS = 64, AP_ROWS = 16, AP_BLOCK = 256, AP_MAX_BLOCKS = 1024;
+
+  __global__ __launch_bounds__(AP_BLOCK) void k_lod_apply(int nrow, int s, int cap, int NP, int n_rhs, int ngroup,
+                                                         const double *__restrict__ values, const uint32_t *__restrict__ cols,
+                                                         const double *__restrict__ x, size_t ld_x, double *__restrict__ y,
+                                                         size_t ld_y)
+  {
+    const int c0 = blockIdx.y * AP_COLS, nb = min(AP_COLS, n_rhs - c0);
+    for (int g = blockIdx.x; g < ngroup; g += gridDim.x)
+      for (int idx = threadIdx.x; idx < AP_ROWS * nb; idx += AP_BLOCK)
+        {
+          const int lr = idx / nb, c = idx - lr * nb, i = g * AP_ROWS + lr, col = c0 + c;
+          if (i >= nrow)
+            continue;
+          const double acc = slod_lod_row_product(i, s, cap, NP, values, cols, x, ld_x, col);
+          y[(size_t)i * ld_y + col] = acc;
+        }
+  }
+
+  // out = alpha a + beta b, two roundings of the products and one of the sum (no fma)
+  __global__ __launch_bounds__(256) void k_lod_combine(size_t n, double alpha, const double *a, double beta, const double *b,
+                                                      double *out)
+  {
+#pragma clang fp contract(off)
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n)
+      {
+        const double ta = alpha * a[i], tb = beta * b[i];
+        out[i]          = ta + tb;
+      }
+  }
+
+  // g = dt (theta b1 + (1 - theta) b0 - g) per (row, column); g holds A u on entry.  b0 / b1 NULL: zero load.
+  __global__ __launch_bounds__(256) void k_theta_rhs(int nrow, int n_rhs, double dt, double theta, const double *b0,
+                                                    const double *b1, size_t ld_b, double *g)
+  {
+#pragma clang fp contract(off)
+    const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= (size_t)nrow * n_rhs)
+      return;
+    const size_t i = w / n_rhs, c = w - i * n_rhs;
+    double       load = 0.0;
+    if (b0)
+      {
+        const double t1 = theta * b1[i * ld_b + c], t0 = (1.0 - theta) * b0[i * ld_b + c];
+        load            = t1 + t0;
+      }
+    g[w] = dt * (load - g[w]);
+  }
+
+  // u += delta
+  __global__ __launch_bounds__(256) void k_theta_advance(int nrow, int n_rhs, const double *delta, double *u, size_t ld_u)
+  {
+    const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= (size_t)nrow * n_rhs)
+      return;
+    const size_t i = w / n_rhs, c = w - i * n_rhs;
+    u[i * ld_u + c] += delta[w];
+  }
+
+  void launch_apply(const slod_handle *h, hipStream_t st, const double *values, const uint32_t *cols, const double *x, size_t ld_x,
+                    int n_rhs, double *y, size_t ld_y)
+  {
+    const int  s = h->cfg.spacedim, cap = slod_lod_row_capacity(h), NP = h->NP, nrow = NP * s;
+    const int  ngroup = (nrow + AP_ROWS - 1) / AP_ROWS, nchunk = (n_rhs + AP_COLS - 1) / AP_COLS;
+    const dim3 grid((unsigned)std::min(ngroup, AP_MAX_BLOCKS), (unsigned)nchunk);
+    hipLaunchKernelGGL(k_lod_apply, grid, dim3(AP_BLOCK), 0, st, nrow, s, cap, NP, n_rhs, ngroup, values, cols, x, ld_x, y, ld_y);
+  }
+} // namespace
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int slod_lod_mass_matrix(slod_handle *h, const uint32_t *rows, size_t n_rows, const double *d_basis, size_t stride,
+                         const double *d_rho, double *d_values, uint32_t *d_cols, void *hip_stream)
+{
+  if (!h || (n_rows && (!rows || !d_basis || !d_values || !d_cols)))
+    return SLOD_ERR_ARGUMENT;
+  for (size_t k = 0; k < n_rows; ++k)
+    if (rows[k] >= (uint32_t)h->NP)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_mass_matrix: row patch id out of range");
+  if (n_rows == 0)
+    return SLOD_OK;
+  if (const int rc = slod_ensure_device(h))
+    return rc;
+  (void)hipSetDevice(h->cfg.device);
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  uint32_t   *d_rows = nullptr;
+  hipError_t  e = hipMalloc((void **)&d_rows, n_rows * sizeof(uint32_t));
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(d_rows, rows, n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(st); // rows is a caller-owned host array
+  if (e == hipSuccess)
+    {
+      const double hf = 1.0 / h->NE, scale = hf * hf / 36.0;
+      if (h->cfg.spacedim == 1)
+        hipLaunchKernelGGL(k_lod_mass<1>, dim3((unsigned)n_rows), dim3(256), 0, st, slod_grid_of(h), d_rows, d_basis, stride,
+                           d_rho, scale, d_values, d_cols);
+      else
+        hipLaunchKernelGGL(k_lod_mass<2>, dim3((unsigned)n_rows), dim3(256), 0, st, slod_grid_of(h), d_rows, d_basis, stride,
+                           d_rho, scale, d_values, d_cols);
+      e = hipGetLastError();
+    }
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(st); // d_rows is freed below
+  if (d_rows)
+    (void)hipFree(d_rows);
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_mass_matrix");
+}
+
+int slod_lod_apply_multi(slod_handle *h, const double *d_values, const uint32_t *d_cols, const double *d_x, size_t ld_x,
+                         int n_rhs, double *d_y, size_t ld_y, void *hip_stream)
+{
+  if (!h || !d_values || !d_cols || !d_x || !d_y)
+    return SLOD_ERR_ARGUMENT;
+  if (n_rhs < 1)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_apply_multi: n_rhs < 1");
+  if (ld_x < (size_t)n_rhs || ld_y < (size_t)n_rhs)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_apply_multi: leading dimension below n_rhs");
+  if (d_x == d_y)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_apply_multi: the product cannot run in place");
+  if (const int rc = slod_ensure_device(h))
+    return rc;
+  (void)hipSetDevice(h->cfg.device);
+  launch_apply(h, hip_stream ? (hipStream_t)hip_stream : h->stream, d_values, d_cols, d_x, ld_x, n_rhs, d_y, ld_y);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_apply_multi");
+}
+
+int slod_lod_matrix_combine(slod_handle *h, double alpha, const double *d_a, double beta, const double *d_b, double *d_out,
+                            void *hip_stream)
+{
+  if (!h || !d_a || !d_b || !d_out)
+    return SLOD_ERR_ARGUMENT;
+  if (const int rc = slod_ensure_device(h))
+    return rc;
+  (void)hipSetDevice(h->cfg.device);
+  const int    s = h->cfg.spacedim;
+  const size_t n = (size_t)h->NP * slod_lod_row_capacity(h) * s * s;
+  hipLaunchKernelGGL(k_lod_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hip_stream ? (hipStream_t)hip_stream : h->stream,
+                     n, alpha, d_a, beta, d_b, d_out);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_matrix_combine");
+}
+
+int slod_lod_theta_steps(slod_handle *h, const double *d_stiffness, const double *d_mass, const uint32_t *d_cols, double dt,
+                         double theta, int n_steps, int n_rhs, double *d_u, size_t ld_u, const double *d_load, size_t ld_load,
+                         size_t load_step_stride, double rel_tol, int max_iterations, int *iterations, double *rel_residual)
+{
+  if (!h || !d_stiffness || !d_mass || !d_cols || !d_u)
+    return SLOD_ERR_ARGUMENT;
+  if (!(dt > 0.0) || !(theta >= 0.0 && theta <= 1.0))
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_theta_steps: dt <= 0 or theta outside [0, 1]");
+  if (n_steps < 1 || n_rhs < 1 || max_iterations < 0)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_theta_steps: n_steps < 1, n_rhs < 1 or max_iterations < 0");
+  if (ld_u < (size_t)n_rhs || (d_load && ld_load < (size_t)n_rhs))
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_theta_steps: leading dimension below n_rhs");
+  if (const int rc = slod_ensure_device(h))
+    return rc;
+  (void)hipSetDevice(h->cfg.device);
+  hipStream_t  st = h->stream;
+  const int    s = h->cfg.spacedim, nrow = h->NP * s;
+  const size_t nmat = (size_t)h->NP * slod_lod_row_capacity(h) * s * s, nvec = (size_t)nrow * n_rhs;
+  // one allocation for the whole loop: S, g, delta and the workspace of the solve
+  double    *work = nullptr;
+  int       *d_active = nullptr;
+  hipError_t e = hipMalloc((void **)&work, (nmat + 2 * nvec + slod_mcg_work_doubles(h, n_rhs)) * sizeof(double));
+  if (e == hipSuccess)
+    e = hipMalloc((void **)&d_active, (size_t)n_rhs * sizeof(int));
+  int worst = 0;
+  if (e == hipSuccess)
+    {
+      double        *S = work, *g = S + nmat, *delta = g + nvec, *cg = delta + nvec;
+      const unsigned nblk = (unsigned)((nvec + 255) / 256);
+      hipLaunchKernelGGL(k_lod_combine, dim3((unsigned)((nmat + 255) / 256)), dim3(256), 0, st, nmat, 1.0, d_mass, theta * dt,
+                         d_stiffness, S);
+      e = hipGetLastError();
+      std::vector<int>    its((size_t)n_rhs);
+      std::vector<double> res((size_t)n_rhs);
+      for (int k = 0; k < n_steps && e == hipSuccess; ++k)
+        {
+          const double *b0 = d_load ? d_load + (size_t)k * load_step_stride : nullptr;
+          const double *b1 = d_load ? d_load + (size_t)(k + 1) * load_step_stride : nullptr;
+          launch_apply(h, st, d_stiffness, d_cols, d_u, ld_u, n_rhs, g, (size_t)n_rhs);
+          hipLaunchKernelGGL(k_theta_rhs, dim3(nblk), dim3(256), 0, st, nrow, n_rhs, dt, theta, b0, b1, ld_load, g);
+          e = hipGetLastError();
+          if (e == hipSuccess)
+            e = slod_mcg_solve(h, S, d_cols, g, (size_t)n_rhs, n_rhs, delta, (size_t)n_rhs, rel_tol, max_iterations, cg, d_active,
+                               its.data(), res.data());
+          if (e != hipSuccess)
+            break;
+          hipLaunchKernelGGL(k_theta_advance, dim3(nblk), dim3(256), 0, st, nrow, n_rhs, delta, d_u, ld_u);
+          e = hipGetLastError();
+          const int step_its = *std::max_element(its.begin(), its.end());
+          worst              = std::max(worst, step_its);
+          if (iterations)
+            iterations[k] = step_its;
+          if (rel_residual)
+            rel_residual[k] = *std::max_element(res.begin(), res.end());
+        }
+      if (e == hipSuccess)
+        e = hipStreamSynchronize(st);
+    }
+  if (work)
+    (void)hipFree(work);
+  if (d_active)
+    (void)hipFree(d_active);
+  if (e != hipSuccess)
+    return slod_hip_fail(h, e, "slod_lod_theta_steps");
+  return worst;
+}
+
+} // extern "C"
+#pragma GCC visibility pop

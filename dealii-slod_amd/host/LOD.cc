@@ -372,6 +372,79 @@ namespace slod
       }
   }
 
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::assemble_mass_matrix()
+  {
+    if (!d_lod_values)
+      throw std::runtime_error("assemble_mass_matrix: assemble_global_matrix comes first");
+    const unsigned int n_patches = (unsigned int)patches.size();
+    const int          cap = slod_lod_row_capacity(handle);
+    check(cap, "slod_lod_row_capacity");
+    const std::size_t n_slots = (std::size_t)n_patches * cap;
+    if (!d_lod_mass)
+      d_lod_mass = device_alloc<double>(n_slots * spacedim * spacedim);
+    // the call writes its columns; they must be those of A_LOD, which the solves use for both matrices
+    uint32_t *d_m_cols = nullptr;
+    if (hipMalloc((void **)&d_m_cols, n_slots * sizeof(uint32_t)) != hipSuccess)
+      throw std::runtime_error("assemble_mass_matrix: hipMalloc of the columns failed");
+    std::vector<uint32_t> rows(n_patches);
+    for (unsigned int p = 0; p < n_patches; ++p)
+      rows[p] = p;
+    const int             rc = slod_lod_mass_matrix(handle, rows.data(), n_patches, d_basis, basis_stride, nullptr, d_lod_mass,
+                                                    d_m_cols, nullptr);
+    std::vector<uint32_t> m_cols(n_slots), a_cols(n_slots);
+    const bool            copied = rc == SLOD_OK &&
+                        hipMemcpy(m_cols.data(), d_m_cols, n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess &&
+                        hipMemcpy(a_cols.data(), d_lod_cols, n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(d_m_cols);
+    check(rc, "slod_lod_mass_matrix");
+    if (!copied || m_cols != a_cols)
+      throw std::runtime_error("assemble_mass_matrix: the pattern of M_LOD differs from that of A_LOD");
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_heat(const unsigned int n_steps, const double dt, const double theta)
+  {
+    if (!d_lod_mass || !d_fem_rhs)
+      throw std::runtime_error("solve_heat: assemble_mass_matrix and assemble_and_solve_fem_problem come first");
+    const unsigned int    n_patches = (unsigned int)patches.size();
+    const std::size_t     n_coarse = (std::size_t)n_patches * spacedim;
+    std::vector<uint32_t> rows(n_patches);
+    for (unsigned int p = 0; p < n_patches; ++p)
+      rows[p] = p;
+    // allocated on the first call, re-used by later ones
+    if (!d_heat_rhs)
+      d_heat_rhs = device_alloc<double>(n_coarse);
+    if (!d_heat_u)
+      d_heat_u = device_alloc<double>(n_coarse);
+    check(slod_lod_rhs(handle, rows.data(), n_patches, d_basis, basis_stride, d_fem_rhs, d_heat_rhs, nullptr), "slod_lod_rhs");
+    if (hipMemset(d_heat_u, 0, n_coarse * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+      throw std::runtime_error("solve_heat: clearing the initial state failed");
+    lod_heat_iterations.assign(n_steps, 0);
+    lod_heat_residuals.assign(n_steps, 0.0);
+    check(slod_lod_theta_steps(handle, d_lod_values, d_lod_mass, d_lod_cols, dt, theta, (int)n_steps, 1, d_heat_u, 1, d_heat_rhs, 1,
+                               0, lod_rel_tol, lod_max_iterations, lod_heat_iterations.data(), lod_heat_residuals.data()),
+          "slod_lod_theta_steps");
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::compare_heat_with_lod()
+  {
+    if (!d_heat_u || !d_lod_u)
+      throw std::runtime_error("compare_heat_with_lod: solve and solve_heat come first");
+    const std::size_t NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+    const std::size_t fine_size = (NE + 1) * (NE + 1) * spacedim;
+    if (!d_heat_fine)
+      d_heat_fine = device_alloc<double>(2 * fine_size); // the elliptic and the heat state, re-used by later calls
+    double *d_lod_fine = d_heat_fine + fine_size;
+    check(slod_lod_reconstruct(handle, d_basis, basis_stride, d_lod_u, d_lod_fine, nullptr), "slod_lod_reconstruct");
+    check(slod_lod_reconstruct(handle, d_basis, basis_stride, d_heat_u, d_heat_fine, nullptr), "slod_lod_reconstruct");
+    check(slod_compute_error_norms(handle, 0, d_lod_fine, d_heat_fine, nullptr, nullptr, &heat_lod_error, nullptr),
+          "slod_compute_error_norms");
+    check(slod_compute_error_norms(handle, 0, d_lod_fine, nullptr, nullptr, nullptr, &lod_norms, nullptr),
+          "slod_compute_error_norms");
+  }
+
   // LOD.cc:1103-1237 with f = 1.  The reference solves with SolverDirect; the CG of the fine problem runs on the
   // coarse grid to the tolerance of the fine solve.
   template <int dim, int spacedim>

@@ -120,6 +120,18 @@ namespace slod
     // per load: the fine FEM solution of that load and the norms of u_h - u_LOD (compare_lod_with_fem per column)
     void compare_multi_with_fem();
     const std::vector<slod_error_norms> &error_multi_LOD_FEMh() const { return lod_multi_fem_error; }
+    // M_LOD = C^T M C (consistent Q1 mass, density 1) in the pattern of A_LOD, after assemble_global_matrix() (the
+    // reference has no counterpart: it has no time-dependent problem)
+    void assemble_mass_matrix();
+    // n_steps of the theta scheme for M u' + A u = C^T f_h from u = 0 with the load of solve(), constant in time,
+    // through slod_lod_theta_steps; after assemble_mass_matrix() and assemble_and_solve_fem_problem()
+    void solve_heat(const unsigned int n_steps, const double dt, const double theta);
+    const std::vector<int>    &heat_iterations() const { return lod_heat_iterations; }
+    const std::vector<double> &heat_rel_residuals() const { return lod_heat_residuals; }
+    // norms of C u_H - C u_heat: the final state against the elliptic SLOD solution of solve(), and of C u_H alone
+    void compare_heat_with_lod();
+    const slod_error_norms &error_heat_LOD() const { return heat_lod_error; }
+    const slod_error_norms &norms_LOD() const { return lod_norms; }
     const slod_error_norms &error_LOD_FEMh() const { return lod_fem_error; }
     // the same norms of u_h alone (the denominators of relative errors)
     const slod_error_norms &norms_FEMh() const { return fem_norms; }
@@ -168,6 +180,11 @@ namespace slod
     double             *d_fem_rhs = nullptr, *d_fem_solution = nullptr, *d_lod_u = nullptr;
     double             *d_fem_coarse_solution = nullptr, *d_fem_coarse_interpolated = nullptr;
     slod_error_norms    lod_fem_error{}, fem_norms{}, femH_fem_error{};
+    // assemble_mass_matrix, solve_heat
+    double             *d_lod_mass = nullptr, *d_heat_rhs = nullptr, *d_heat_u = nullptr, *d_heat_fine = nullptr;
+    std::vector<int>    lod_heat_iterations;
+    std::vector<double> lod_heat_residuals;
+    slod_error_norms    heat_lod_error{}, lod_norms{};
     // solve_multi: fine load vectors and reconstructions, field k at + k * fine_size
     double                       *d_multi_fem_rhs = nullptr, *d_multi_fine = nullptr;
     std::vector<int>              lod_multi_iterations;

@@ -117,6 +117,11 @@ def load():
     lib.slod_lod_solve_multi.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_double, C.c_int,
                                          C.POINTER(C.c_int), dp]
     lib.slod_lod_reconstruct_multi.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp]
+    lib.slod_lod_mass_matrix.argtypes = [vp, u32p, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp]
+    lib.slod_lod_apply_multi.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp]
+    lib.slod_lod_matrix_combine.argtypes = [vp, C.c_double, vp, C.c_double, vp, vp, vp]
+    lib.slod_lod_theta_steps.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.c_size_t, vp,
+                                         C.c_size_t, C.c_size_t, C.c_double, C.c_int, C.POINTER(C.c_int), dp]
     lib.slod_fem_rhs.argtypes = [vp, vp, vp, vp]
     lib.slod_fem_solve.argtypes = [vp, C.c_uint32, vp, vp, C.c_double, C.c_int, dp]
     lib.slod_coarse_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, vp]
@@ -375,6 +380,36 @@ class Slod:
 
     def lod_reconstruct_multi(self, d_basis, stride, d_u, ld_u, n_rhs, d_fine, ld_fine, stream=None):
         self._check(self.lib.slod_lod_reconstruct_multi(self.h, d_basis, stride, d_u, ld_u, n_rhs, d_fine, ld_fine, stream))
+
+    # ---- the L2 side: M_LOD = C^T M_rho C, products and combinations of block-row matrices, theta time steps ----
+    def lod_mass_matrix(self, rows, d_basis, stride, d_values, d_cols, d_rho=None, stream=None):
+        """Block rows of M_LOD in the layout of lod_matrix (d_rho: device [NE][NE] per fine element, None = 1)."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        self._check(self.lib.slod_lod_mass_matrix(self.h, rows.ctypes.data_as(C.POINTER(C.c_uint32)), len(rows), d_basis,
+                                                  stride, d_rho, d_values, d_cols, stream))
+
+    def lod_apply(self, d_values, d_cols, d_x, d_y, n_rhs=1, ld_x=None, ld_y=None, stream=None):
+        """Y = A X on a full set of block rows; coarse multi-vectors, ld defaults to n_rhs.  Asynchronous."""
+        self._check(self.lib.slod_lod_apply_multi(self.h, d_values, d_cols, d_x, n_rhs if ld_x is None else ld_x, n_rhs,
+                                                  d_y, n_rhs if ld_y is None else ld_y, stream))
+
+    def lod_matrix_combine(self, alpha, d_a, beta, d_b, d_out, stream=None):
+        """out = alpha * A + beta * B on two values arrays of one pattern (out may be an input).  Asynchronous."""
+        self._check(self.lib.slod_lod_matrix_combine(self.h, alpha, d_a, beta, d_b, d_out, stream))
+
+    def lod_theta_steps(self, d_stiffness, d_mass, d_cols, dt, theta, n_steps, d_u, n_rhs=1, ld_u=None, d_load=None,
+                        ld_load=None, load_step_stride=0, rel_tol=1e-12, max_iterations=2000):
+        """n_steps of the theta scheme for M u' + A u = b(t) on d_u in place.  Returns (iterations, rel_residual),
+        one entry per step; max(iterations) is the C call's return value."""
+        its = np.zeros(max(n_steps, 1), dtype=np.intc)
+        res = np.zeros(max(n_steps, 1))
+        rc = self.lib.slod_lod_theta_steps(self.h, d_stiffness, d_mass, d_cols, dt, theta, n_steps, n_rhs, d_u,
+                                           n_rhs if ld_u is None else ld_u, d_load, n_rhs if ld_load is None else ld_load,
+                                           load_step_stride, rel_tol, max_iterations,
+                                           its.ctypes.data_as(C.POINTER(C.c_int)), _dp(res))
+        if rc < 0:
+            self._check(rc)
+        return its[:n_steps], res[:n_steps]
 
     def fem_rhs(self, d_f_qp, d_fine_rhs, stream=None):
         """Fine FEM load vector (d_f_qp = None: f = 1)."""

@@ -260,6 +260,67 @@ int slod_lod_reconstruct_multi(slod_handle *h, const double *d_basis, size_t str
                                const double *d_u, size_t ld_u, int n_rhs,
                                double *d_fine, size_t ld_fine, void *hip_stream);
 
+/* ---- the L2 inner product on the LOD space and a time loop on it ----------------------
+ * The reference solves one stationary problem (LOD.cc:976-1002) and has no counterpart of this block.  With
+ * M_LOD = C^T M_rho C the basis serves parabolic problems (M u' + A u = b), the eigenvalue problem
+ * A_LOD u = lambda M_LOD u, and, through slod_lod_apply_multi and slod_lod_matrix_combine, any scheme a host builds
+ * from products and linear combinations of the two matrices.  Every matrix below is a full set of block rows in the
+ * layout of slod_lod_matrix; coarse multi-vectors are those of the _multi calls (entry (i, c) at base[i * ld + c]).
+ * Common: argument checks come before any device work (SLOD_ERR_ARGUMENT); SLOD_ERR_DEVICE without a usable GPU. */
+/* Block rows of M_LOD for the patches rows[0..n_rows), layout and pattern of slod_lod_matrix:
+ *   d_values[(k * cap + j) * s * s + d * s + e] = sum_c int rho phi_{rows[k],d,c} phi_{q,e,c} dx,  q = d_cols[k * cap + j],
+ * cap = slod_lod_row_capacity(), unused slots 0xffffffff with value 0.  For the same rows d_cols equals what
+ * slod_lod_matrix writes, word for word: a pair of patches that shares only a line of nodes keeps its column, here
+ * with the value 0.  Components do not couple in the mass; block (d, e) is the sum over c above.
+ * The integral is the consistent Q1 mass of the global fine grid, element matrix
+ *   rho_e h^2 / 36 [[4,2,2,1],[2,4,1,2],[2,1,4,2],[1,2,2,4]],  h = 1 / NE  (nodes (0,0), (1,0), (0,1), (1,1)),
+ * summed over the fine elements of the intersection rectangle of the two closed patches, which is the global form
+ * because phi vanishes on every patch rim.  d_rho: DEVICE [NE][NE], one value per fine element, ex fastest (layout 0 of
+ * slod_set_coefficient), an argument and not handle state; NULL = 1.  Only the basis slab is read (d_basis, stride as
+ * in slod_lod_matrix).  The sum has a fixed order (no atomics): the same inputs give the same bits, and
+ * M[(p,d),(q,e)] and M[(q,e),(p,d)] are the same bits when both rows are computed.  rows is a HOST array, ids
+ * < num_patches; the call uploads it and SYNCHRONISES hip_stream, like slod_lod_matrix. */
+int slod_lod_mass_matrix(slod_handle *h, const uint32_t *rows, size_t n_rows, const double *d_basis, size_t stride,
+                         const double *d_rho, double *d_values, uint32_t *d_cols, void *hip_stream);
+/* Y = A X for a full set of block rows (rows = 0 .. num_patches-1 of slod_lod_matrix or slod_lod_mass_matrix, or a
+ * combination of them): d_y[i * ld_y + c] = sum_j sum_e values[...] d_x[(q s + e) * ld_x + c].  n_rhs = 1, ld = 1 is
+ * the single-vector product.  One fma chain per entry over the slots of the row in ascending order: the bits of
+ * column c of Y depend only on the matrix and on column c of X, not on n_rhs, ld or the column's position.  Entries
+ * c >= n_rhs of a row are never read or written.  SLOD_ERR_ARGUMENT: NULL handle or array, n_rhs < 1, ld < n_rhs,
+ * d_x == d_y (the product cannot run in place).  Asynchronous on hip_stream. */
+int slod_lod_apply_multi(slod_handle *h, const double *d_values, const uint32_t *d_cols, const double *d_x, size_t ld_x,
+                         int n_rhs, double *d_y, size_t ld_y, void *hip_stream);
+/* d_out = alpha A + beta B on the values arrays of two full sets of block rows that share one d_cols (which the call
+ * does not need): per entry  out = (alpha * a) + (beta * b)  with the two products and the sum rounded separately (no
+ * fma), which is what `alpha * A + beta * B` gives in numpy.  Unused slots stay 0.  d_out may be d_a or d_b.
+ * Asynchronous on hip_stream. */
+int slod_lod_matrix_combine(slod_handle *h, double alpha, const double *d_a, double beta, const double *d_b, double *d_out,
+                            void *hip_stream);
+/* n_steps steps of the theta scheme for  M u' + A u = b(t)  on n_rhs independent columns (initial states and / or loads),
+ * the whole loop on the device.  In increment form, for k = 0 .. n_steps-1:
+ *   S = M + theta dt A                                   (slod_lod_matrix_combine, once per call, workspace of the call)
+ *   g = (theta b^{k+1} + (1 - theta) b^k) - A u^k        (slod_lod_apply_multi; products and sums rounded separately)
+ *   S delta = dt g                                        (the recurrence of slod_lod_solve_multi from delta = 0, per-column
+ *                                                          freeze, rel_tol relative to ||dt g_c||, checked every 8 iterations)
+ *   u^{k+1} = u^k + delta
+ * theta = 1: backward Euler; 1/2: Crank-Nicolson; 0: forward Euler (S = M).  d_stiffness, d_mass: values arrays of
+ * slod_lod_matrix and slod_lod_mass_matrix for rows = 0 .. num_patches-1, d_cols their common columns.  d_u: u^0 on
+ * entry, u^{n_steps} on return (ld_u >= n_rhs).  d_load: the coarse loads b^k = C^T f(t_k), k = 0 .. n_steps, b^k at
+ * d_load + k * load_step_stride (doubles) with ld_load >= n_rhs; load_step_stride = 0: one load, constant in time;
+ * d_load = NULL: zero load (ld_load, load_step_stride ignored).  A zero column of dt g gives delta = 0 and 0 iterations;
+ * reaching max_iterations is not an error.  HOST iterations[n_steps]: the largest per-column iteration count of each
+ * step; HOST rel_residual[n_steps]: the worst column's ||r|| / ||dt g|| of each step; either may be NULL.  Returns the
+ * largest entry of iterations or a negative slod_status.  The bits of column c of the result depend only on the two
+ * matrices, the parameters, and column c of u^0 and of the loads; one call with n_steps = 2 equals two calls with
+ * n_steps = 1.  Device workspace (one matrix, 6 vectors of n_rhs columns) allocated once per call.
+ * SLOD_ERR_ARGUMENT: NULL handle, matrix, d_cols or d_u; dt <= 0; theta outside [0, 1]; n_steps < 1; n_rhs < 1;
+ * ld_u < n_rhs; ld_load < n_rhs with a load; max_iterations < 0.  Runs on the handle's stream; synchronises. */
+int slod_lod_theta_steps(slod_handle *h, const double *d_stiffness, const double *d_mass, const uint32_t *d_cols, double dt,
+                         double theta, int n_steps, int n_rhs, double *d_u, size_t ld_u, const double *d_load, size_t ld_load,
+                         size_t load_step_stride, double rel_tol, int max_iterations,
+                         int *iterations /* HOST [n_steps], may be NULL */,
+                         double *rel_residual /* HOST [n_steps], may be NULL */);
+
 /* ---- fine FEM reference problem (assemble_and_solve_fem_problem, LOD.cc:1004-1094) ----
  * What the reference compares the LOD solution with (compare_lod_with_fem, LOD.cc:1240-1378).
  * fem_rhs of assemble_stiffness (Diffusion.h:149-193) on the global fine grid, [(NE+1)^2][s],
