@@ -1,6 +1,6 @@
 // Counterpart of reference app/main_Diffusion.cc for the basis-construction path:
 //   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare] [--coarse] [--loads K]
-//                  [--heat STEPS DT]
+//                  [--heat STEPS DT] [--eigs K]
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
 // file name it dumps, per patch, phi and psi in patch-lexicographic order (parity tests).
 // --compare (anywhere on the command line): after run(), the rest of the reference run() -- global
@@ -14,6 +14,9 @@
 // --heat STEPS DT: the heat flow  M u' + A u = C^T f  (f = 1, constant in time) from u = 0 by STEPS backward Euler steps
 // of size DT on the LOD space (slod_lod_theta_steps): one line per step with its iterations and relative residual, then
 // the table "SLOD heat flow at T = STEPS DT vs elliptic SLOD solution", which shrinks as STEPS DT grows.
+// --eigs K: the K lowest eigenpairs of  A_LOD u = lambda M_LOD u  (A_LOD symmetrised, slod_lod_eigs with its defaults): one
+// line per pair with its eigenvalue and residual, the outer and inner iteration counts, and the fine-grid L2 norm of
+// every reconstructed eigenfunction.
 #include "../host/Diffusion.h"
 
 #include <cstdio>
@@ -67,7 +70,7 @@ int main(int argc_all, char **argv_all)
 {
   // --compare and --coarse are taken out wherever they stand; the positional arguments keep their meaning
   bool               compare = false, coarse = false;
-  int                n_loads = 0, heat_steps = 0;
+  int                n_loads = 0, heat_steps = 0, n_eigs = 0;
   double             heat_dt = 0.0;
   std::vector<char *> args;
   for (int i = 0; i < argc_all; ++i)
@@ -82,6 +85,8 @@ int main(int argc_all, char **argv_all)
         heat_steps = std::atoi(argv_all[++i]);
         heat_dt    = std::atof(argv_all[++i]);
       }
+    else if (i > 0 && !std::strcmp(argv_all[i], "--eigs") && i + 1 < argc_all)
+      n_eigs = std::atoi(argv_all[++i]);
     else
       args.push_back(argv_all[i]);
   const int argc = (int)args.size();
@@ -180,6 +185,22 @@ int main(int argc_all, char **argv_all)
           std::printf("  H1     error = %.12e  (relative %.6e)\n", h1, h1 / uh1);
           std::printf("  Linfty error = %.12e  (relative %.6e)\n", e.linf[0], e.linf[0] / u.linf[0]);
           std::printf("  energy error = %.12e  (relative %.6e)\n", e.energy, e.energy / u.energy);
+        }
+      if (n_eigs > 0)
+        {
+          if (!compare && n_loads <= 0 && heat_steps <= 0)
+            problem.assemble_global_matrix();
+          if (heat_steps <= 0)
+            problem.assemble_mass_matrix();
+          problem.solve_eigenproblem((unsigned int)n_eigs);
+          for (int k = 0; k < n_eigs; ++k)
+            std::printf("eigenvalue %d = %.12e, residual = %.3e\n", k + 1, problem.eigenvalues()[k], problem.eigen_residuals()[k]);
+          std::printf("eigensolver: outer iterations = %d, inner iterations =", (int)problem.eigen_inner_iterations().size());
+          for (const int it : problem.eigen_inner_iterations())
+            std::printf(" %d", it);
+          std::printf("\n");
+          for (int k = 0; k < n_eigs; ++k)
+            std::printf("eigenfunction %d: L2 norm = %.12e\n", k + 1, problem.eigenfunction_norms()[k].l2[0]);
         }
     }
   catch (std::exception &exc)

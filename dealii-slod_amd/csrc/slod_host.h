@@ -104,4 +104,7 @@ size_t     slod_mcg_work_doubles(const slod_handle *h, int n_rhs);
 hipError_t slod_mcg_solve(slod_handle *h, const double *d_values, const uint32_t *d_cols, const double *d_rhs, size_t ld_rhs,
                           int n_rhs, double *d_u, size_t ld_u, double rel_tol, int max_iterations, double *work, int *d_active,
                           int *its, double *rel_residual);
+// Y = A X on a full set of block rows, the launch of slod_lod_apply_multi (slod_lod_time.hip; used by slod_lod_eig.hip)
+void slod_lod_apply_launch(const slod_handle *h, hipStream_t st, const double *d_values, const uint32_t *d_cols, const double *d_x,
+                           size_t ld_x, int n_rhs, double *d_y, size_t ld_y);
 #endif

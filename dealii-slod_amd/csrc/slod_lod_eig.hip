@@ -1,0 +1,594 @@
+// The eigenvalue problem on the LOD space (the reference has no counterpart: it solves one stationary problem,
+// LOD.cc:976-1002):
+//   slod_lod_matrix_symmetrize  out = (A + A^T) / 2 on the block rows, bit-symmetric
+//   slod_lod_eigs               the lowest eigenpairs of  A u = lambda M u  by block inverse iteration with Rayleigh-Ritz
+// An outer iteration is  Y = M X,  A Z = Y (the multi-column CG of slod_lod_multi.hip),  W = A Z,  V = M Z
+// (k_lod_apply of slod_lod_time.hip) and three kernels of this file on the tall-skinny block [Z | W | V] (nrow x m,
+// m <= 64 columns):
+//   k_eig_gram / k_eig_gram_sum  Ga = sym(Z^T W), Gm = sym(Z^T V): one pass over the rows, slab partials, ordered sum
+//   k_eig_ritz                   Ga Q = Gm Q Theta, Q^T Gm Q = I in one workgroup out of LDS
+//   k_eig_rotate                 X = Z Q; AX = W Q and MX = V Q stay in registers for the residual partials
+// Every reduction has a fixed order (no atomics): the same inputs give the same bits.
+#include "slod_host.h"
+#include "slod_grid.hip.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <utility>
+#include <vector>
+
+namespace
+{
+  constexpr int    EG_COLS = 64; // block columns: the column chunk of k_lod_apply / k_mcg_spmv, and what fits the Ritz LDS
+  constexpr double EG_EPS  = 2.220446049250313e-16;
+
+  // out[p,j][d][e] = (A[p,j][d][e] + A[q,j'][e][d]) / 2, q = cols[p,j], j' the slot of p in row q (0 when there is none).
+  // One rounding of the sum, an exact halving, both commutative: out is symmetric bit for bit.
+  __global__ __launch_bounds__(256) void k_lod_symmetrize(int NP, int s, int cap, const double *__restrict__ values,
+                                                         const uint32_t *__restrict__ cols, double *__restrict__ out)
+  {
+#pragma clang fp contract(off)
+    const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x, ss = (size_t)s * s;
+    if (w >= (size_t)NP * cap * ss)
+      return;
+    const size_t   slot = w / ss;
+    const int      de = (int)(w - slot * ss), d = de / s, e = de - d * s;
+    const uint32_t p = (uint32_t)(slot / cap), q = cols[slot];
+    if (q >= (uint32_t)NP)
+      {
+        out[w] = 0.0;
+        return;
+      }
+    double t = 0.0;
+    for (int j = 0; j < cap; ++j)
+      if (cols[(size_t)q * cap + j] == p)
+        {
+          t = values[((size_t)q * cap + j) * ss + e * s + d];
+          break;
+        }
+    out[w] = 0.5 * (values[w] + t);
+  }
+
+  // ---------------------------------------------------------------------------------
+  // Start block: column j = (mode t = j / s, component d = j % s) is the discrete sine mode (a_t, b_t) on the centre
+  // cells of the patches, in component d.
+  // ---------------------------------------------------------------------------------
+  struct EigModes
+  {
+    unsigned char a[EG_COLS], b[EG_COLS];
+  };
+
+  __global__ __launch_bounds__(256) void k_eig_start(const SlodGrid G, int NP, int s, int m, const EigModes md, double *x, size_t ld_x)
+  {
+    const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= (size_t)NP * s * m)
+      return;
+    const size_t i = w / m;
+    const int    j = (int)(w - i * m), e = (int)(i % s), t = j / s, d = j - t * s;
+    int          cx, cy;
+    grid_centre(G, (uint32_t)(i / s), cx, cy);
+    const double sx = sin(md.a[t] * M_PI * (cx + 0.5) / G.N), sy = sin(md.b[t] * M_PI * (cy + 0.5) / G.N);
+    x[i * ld_x + j] = d == e ? sx * sy : 0.0;
+  }
+
+  // ---------------------------------------------------------------------------------
+  // Gram products.  A block takes slabs of GR_ROWS rows (slab g = blockIdx.x, += gridDim.x, as k_lod_apply walks its
+  // groups), stages the rows of Z, W, V in LDS (48 KiB) and accumulates Z^T W and Z^T V: thread (ti, tj) of the
+  // 16 x 16 grid holds the 4 x 4 tile (4 ti.., 4 tj..) of both products, one fma chain per entry over the rows of
+  // the slab in ascending order.  One partial pair per slab; k_eig_gram_sum adds the slabs in ascending order.
+  // ---------------------------------------------------------------------------------
+  constexpr int GR_ROWS = 32, GR_BLOCK = 256, GR_MAX_BLOCKS = 512;
+
+  __global__ __launch_bounds__(GR_BLOCK) void k_eig_gram(int nrow, int m, int nslab, const double *__restrict__ Z,
+                                                        const double *__restrict__ W, const double *__restrict__ V,
+                                                        double *__restrict__ partial)
+  {
+    __shared__ double sz[GR_ROWS][EG_COLS], sw[GR_ROWS][EG_COLS], sv[GR_ROWS][EG_COLS];
+    const int i0 = 4 * (threadIdx.x >> 4), j0 = 4 * (threadIdx.x & 15), m4 = (m + 3) & ~3;
+    for (int g = blockIdx.x; g < nslab; g += gridDim.x)
+      {
+        const int r0 = g * GR_ROWS, nr = min(GR_ROWS, nrow - r0);
+        for (int idx = threadIdx.x; idx < GR_ROWS * m4; idx += GR_BLOCK)
+          {
+            const int    lr = idx / m4, c = idx - lr * m4;
+            const bool   in = lr < nr && c < m; // the columns m .. m4 pad the last tile with zeros
+            const size_t at = (size_t)(r0 + lr) * m + c;
+            sz[lr][c]       = in ? Z[at] : 0.0;
+            sw[lr][c]       = in ? W[at] : 0.0;
+            sv[lr][c]       = in ? V[at] : 0.0;
+          }
+        __syncthreads();
+        if (i0 < m && j0 < m)
+          {
+            double ga[4][4], gm[4][4];
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+              for (int b = 0; b < 4; ++b)
+                ga[a][b] = gm[a][b] = 0.0;
+            for (int r = 0; r < nr; ++r)
+              {
+                double z[4], w[4], v[4];
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+                  {
+                    z[a] = sz[r][i0 + a];
+                    w[a] = sw[r][j0 + a];
+                    v[a] = sv[r][j0 + a];
+                  }
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                  for (int b = 0; b < 4; ++b)
+                    {
+                      ga[a][b] = fma(z[a], w[b], ga[a][b]);
+                      gm[a][b] = fma(z[a], v[b], gm[a][b]);
+                    }
+              }
+            double *pa = partial + (size_t)g * 2 * m * m, *pm = pa + (size_t)m * m;
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+              for (int b = 0; b < 4; ++b)
+                if (i0 + a < m && j0 + b < m)
+                  {
+                    pa[(i0 + a) * m + j0 + b] = ga[a][b];
+                    pm[(i0 + a) * m + j0 + b] = gm[a][b];
+                  }
+          }
+        __syncthreads();
+      }
+  }
+
+  // G[which][i][j] = (S_ij + S_ji) / 2, S = the sum of the slab partials in ascending slab order
+  __global__ __launch_bounds__(256) void k_eig_gram_sum(int m, int nslab, const double *__restrict__ partial, double *__restrict__ G)
+  {
+#pragma clang fp contract(off)
+    const int idx = blockIdx.x * 256 + threadIdx.x, mm = m * m;
+    if (idx >= 2 * mm)
+      return;
+    const int which = idx / mm, ij = idx - which * mm, i = ij / m, j = ij - i * m;
+    double    a = 0.0, b = 0.0;
+    for (int g = 0; g < nslab; ++g)
+      {
+        const double *P = partial + ((size_t)g * 2 + which) * mm;
+        a += P[i * m + j];
+        b += P[j * m + i];
+      }
+    G[idx] = 0.5 * (a + b);
+  }
+
+  // ---------------------------------------------------------------------------------
+  // The Ritz problem  Ga Q = Gm Q Theta,  Q^T Gm Q = I,  Theta ascending, in one workgroup: three m x m matrices in
+  // LDS (row pitch 65 doubles, 97.5 KiB of the 160 KiB).
+  //   Gm = L L^T             right-looking Cholesky; a pivot that is not above 4 m eps times the diagonal entry it
+  //                          started from is taken as non-positive: *status = column + 1, nothing else is written
+  //   C = L^-1 Ga L^-T       two triangular solves, a thread per column, then per row; symmetrised
+  //   C U = U D              cyclic Jacobi, the pairs of a sweep in round-robin order (m - 1 rounds of m / 2 disjoint
+  //                          pairs: the rotations of a round commute, so the order is fixed and the result does not
+  //                          depend on the thread that applies a rotation), until off(C) <= m eps ||C||_F at the head
+  //                          of a sweep or RZ_SWEEPS sweeps
+  //   sort D ascending, ties by index;  Q = L^-T U (sorted columns)
+  // ---------------------------------------------------------------------------------
+  constexpr int RZ_LD = EG_COLS + 1, RZ_BLOCK = 256, RZ_SWEEPS = 30;
+
+  __global__ __launch_bounds__(RZ_BLOCK) void k_eig_ritz(int m, const double *__restrict__ G, double *__restrict__ Q,
+                                                        double *__restrict__ theta, int *__restrict__ status)
+  {
+    __shared__ double A[EG_COLS * RZ_LD], L[EG_COLS * RZ_LD], U[EG_COLS * RZ_LD];
+    __shared__ double s_c[EG_COLS / 2], s_s[EG_COLS / 2], s_d[EG_COLS], s_off[EG_COLS], s_fro[EG_COLS];
+    __shared__ int    s_p[EG_COLS / 2], s_q[EG_COLS / 2], s_perm[EG_COLS], s_stop;
+    const int tid = threadIdx.x, mm = m * m;
+    for (int idx = tid; idx < mm; idx += RZ_BLOCK)
+      {
+        const int i = idx / m, j = idx - i * m;
+        A[i * RZ_LD + j] = G[idx];
+        L[i * RZ_LD + j] = G[mm + idx];
+        U[i * RZ_LD + j] = i == j ? 1.0 : 0.0;
+      }
+    __syncthreads();
+    // ---- Cholesky, lower triangle of L in place
+    for (int k = 0; k < m; ++k)
+      {
+        if (tid == 0)
+          {
+            const double piv = L[k * RZ_LD + k], orig = G[mm + k * m + k];
+            const bool   ok = piv > 0.0 && piv > (4 * m * EG_EPS) * orig;
+            s_stop          = ok ? 0 : k + 1;
+            if (ok)
+              L[k * RZ_LD + k] = sqrt(piv);
+          }
+        __syncthreads();
+        if (s_stop)
+          {
+            if (tid == 0)
+              *status = s_stop;
+            return;
+          }
+        const double d = L[k * RZ_LD + k];
+        for (int i = k + 1 + tid; i < m; i += RZ_BLOCK)
+          L[i * RZ_LD + k] /= d;
+        __syncthreads();
+        const int n = m - k - 1;
+        for (int idx = tid; idx < n * n; idx += RZ_BLOCK)
+          {
+            const int i = k + 1 + idx / n, j = k + 1 + idx % n;
+            if (j <= i)
+              L[i * RZ_LD + j] = fma(-L[i * RZ_LD + k], L[j * RZ_LD + k], L[i * RZ_LD + j]);
+          }
+        __syncthreads();
+      }
+    // ---- A <- L^-1 A (thread = column), A <- A L^-T (thread = row), symmetrise
+    if (tid < m)
+      for (int i = 0; i < m; ++i)
+        {
+          double acc = A[i * RZ_LD + tid];
+          for (int k = 0; k < i; ++k)
+            acc = fma(-L[i * RZ_LD + k], A[k * RZ_LD + tid], acc);
+          A[i * RZ_LD + tid] = acc / L[i * RZ_LD + i];
+        }
+    __syncthreads();
+    if (tid < m)
+      for (int j = 0; j < m; ++j)
+        {
+          double acc = A[tid * RZ_LD + j];
+          for (int k = 0; k < j; ++k)
+            acc = fma(-A[tid * RZ_LD + k], L[j * RZ_LD + k], acc);
+          A[tid * RZ_LD + j] = acc / L[j * RZ_LD + j];
+        }
+    __syncthreads();
+    for (int idx = tid; idx < mm; idx += RZ_BLOCK)
+      {
+        const int i = idx / m, j = idx - i * m;
+        if (j < i)
+          {
+            const double v   = 0.5 * (A[i * RZ_LD + j] + A[j * RZ_LD + i]);
+            A[i * RZ_LD + j] = v;
+            A[j * RZ_LD + i] = v;
+          }
+      }
+    __syncthreads();
+    // ---- cyclic Jacobi
+    const int n2 = (m + 1) & ~1, nround = n2 - 1, npair = n2 / 2;
+    for (int sweep = 0; sweep < RZ_SWEEPS; ++sweep)
+      {
+        if (tid < m)
+          {
+            double off = 0.0, fro = 0.0;
+            for (int j = 0; j < m; ++j)
+              {
+                const double v = A[tid * RZ_LD + j];
+                fro            = fma(v, v, fro);
+                off            = j == tid ? off : fma(v, v, off);
+              }
+            s_off[tid] = off;
+            s_fro[tid] = fro;
+          }
+        __syncthreads();
+        if (tid == 0)
+          {
+            double off = 0.0, fro = 0.0;
+            for (int i = 0; i < m; ++i)
+              {
+                off += s_off[i];
+                fro += s_fro[i];
+              }
+            const double tol = m * EG_EPS;
+            s_stop           = off <= tol * tol * fro ? 1 : 0;
+          }
+        __syncthreads();
+        if (s_stop)
+          break;
+        for (int r = 0; r < nround; ++r)
+          {
+            if (tid < npair)
+              {
+                // circle method: n2 - 1 stays, the others turn
+                const int a = tid == 0 ? n2 - 1 : (r + tid) % nround, b = tid == 0 ? r : (r - tid + nround) % nround;
+                const int p = min(a, b), q = max(a, b);
+                double    c = 1.0, s = 0.0;
+                if (q < m)
+                  {
+                    const double apq = A[p * RZ_LD + q];
+                    if (apq != 0.0)
+                      {
+                        const double tau = (A[q * RZ_LD + q] - A[p * RZ_LD + p]) / (2.0 * apq);
+                        const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+                        c = 1.0 / sqrt(1.0 + t * t);
+                        s = t * c;
+                      }
+                  }
+                s_p[tid] = q < m && s != 0.0 ? p : -1; // the padding index of an odd m, or nothing to rotate
+                s_q[tid] = q;
+                s_c[tid] = c;
+                s_s[tid] = s;
+              }
+            __syncthreads();
+            // columns p, q of A and of U
+            for (int idx = tid; idx < npair * m; idx += RZ_BLOCK)
+              {
+                const int k = idx / m, i = idx - k * m, p = s_p[k], q = s_q[k];
+                if (p < 0)
+                  continue;
+                const double c = s_c[k], s = s_s[k];
+                double       x = A[i * RZ_LD + p], y = A[i * RZ_LD + q];
+                A[i * RZ_LD + p] = c * x - s * y;
+                A[i * RZ_LD + q] = s * x + c * y;
+                x = U[i * RZ_LD + p], y = U[i * RZ_LD + q];
+                U[i * RZ_LD + p] = c * x - s * y;
+                U[i * RZ_LD + q] = s * x + c * y;
+              }
+            __syncthreads();
+            // rows p, q of A
+            for (int idx = tid; idx < npair * m; idx += RZ_BLOCK)
+              {
+                const int k = idx / m, j = idx - k * m, p = s_p[k], q = s_q[k];
+                if (p < 0)
+                  continue;
+                const double c = s_c[k], s = s_s[k];
+                const double x = A[p * RZ_LD + j], y = A[q * RZ_LD + j];
+                A[p * RZ_LD + j] = c * x - s * y;
+                A[q * RZ_LD + j] = s * x + c * y;
+              }
+            __syncthreads();
+          }
+      }
+    // ---- sort, Q = L^-T U
+    if (tid < m)
+      s_d[tid] = A[tid * RZ_LD + tid];
+    __syncthreads();
+    if (tid < m)
+      {
+        const double v = s_d[tid];
+        int          rank = 0;
+        for (int k = 0; k < m; ++k)
+          rank += (s_d[k] < v || (s_d[k] == v && k < tid)) ? 1 : 0;
+        s_perm[rank] = tid;
+      }
+    __syncthreads();
+    if (tid < m)
+      {
+        const int src = s_perm[tid];
+        for (int i = m - 1; i >= 0; --i)
+          {
+            double acc = U[i * RZ_LD + src];
+            for (int k = i + 1; k < m; ++k)
+              acc = fma(-L[k * RZ_LD + i], A[k * RZ_LD + tid], acc);
+            A[i * RZ_LD + tid] = acc / L[i * RZ_LD + i];
+          }
+        theta[tid] = s_d[src];
+      }
+    __syncthreads();
+    for (int idx = tid; idx < mm; idx += RZ_BLOCK)
+      Q[idx] = A[(idx / m) * RZ_LD + idx % m];
+    if (tid == 0)
+      *status = 0;
+  }
+
+  // ---------------------------------------------------------------------------------
+  // [X | AX | MX] = [Z | W | V] Q: Q and a slab of RT_ROWS rows in LDS (72 KiB with the residual buffers), an item is
+  // one (row, column) with its three fma chains over k ascending.  X goes to d_x; AX and MX are consumed at once:
+  // (AX - theta MX)^2 and MX^2, summed over the rows of the slab in ascending order into one partial per
+  // (slab, column); k_eig_residual adds the slabs in ascending order.  Nothing is written after a failed Ritz step.
+  // ---------------------------------------------------------------------------------
+  constexpr int RT_ROWS = 16, RT_BLOCK = 256, RT_MAX_BLOCKS = 1024;
+
+  __global__ __launch_bounds__(RT_BLOCK) void k_eig_rotate(int nrow, int m, int nslab, const double *__restrict__ Z,
+                                                          const double *__restrict__ W, const double *__restrict__ V,
+                                                          const double *__restrict__ Q, const double *__restrict__ theta,
+                                                          const int *__restrict__ status, double *__restrict__ x, size_t ld_x,
+                                                          double *__restrict__ p_rr, double *__restrict__ p_mm)
+  {
+    __shared__ double sq[EG_COLS][EG_COLS];
+    __shared__ double sz[RT_ROWS][EG_COLS], sw[RT_ROWS][EG_COLS], sv[RT_ROWS][EG_COLS];
+    __shared__ double b_rr[RT_ROWS][EG_COLS], b_mm[RT_ROWS][EG_COLS];
+    if (*status != 0)
+      return;
+    for (int idx = threadIdx.x; idx < m * m; idx += RT_BLOCK)
+      sq[idx / m][idx % m] = Q[idx];
+    for (int g = blockIdx.x; g < nslab; g += gridDim.x)
+      {
+        for (int idx = threadIdx.x; idx < RT_ROWS * m; idx += RT_BLOCK)
+          {
+            const int    lr = idx / m, c = idx - lr * m, i = g * RT_ROWS + lr;
+            const size_t at = (size_t)i * m + c;
+            sz[lr][c]       = i < nrow ? Z[at] : 0.0;
+            sw[lr][c]       = i < nrow ? W[at] : 0.0;
+            sv[lr][c]       = i < nrow ? V[at] : 0.0;
+          }
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < RT_ROWS * m; idx += RT_BLOCK)
+          {
+            const int lr = idx / m, j = idx - lr * m, i = g * RT_ROWS + lr;
+            double    xv = 0.0, ax = 0.0, mx = 0.0;
+            for (int k = 0; k < m; ++k)
+              {
+                const double q = sq[k][j];
+                xv             = fma(sz[lr][k], q, xv);
+                ax             = fma(sw[lr][k], q, ax);
+                mx             = fma(sv[lr][k], q, mx);
+              }
+            double rr = 0.0, mm = 0.0;
+            if (i < nrow)
+              {
+                x[(size_t)i * ld_x + j] = xv;
+                const double r          = fma(-theta[j], mx, ax);
+                rr                      = r * r;
+                mm                      = mx * mx;
+              }
+            b_rr[lr][j] = rr;
+            b_mm[lr][j] = mm;
+          }
+        __syncthreads();
+        if ((int)threadIdx.x < m)
+          {
+            double rr = b_rr[0][threadIdx.x], mm = b_mm[0][threadIdx.x];
+#pragma unroll
+            for (int r = 1; r < RT_ROWS; ++r)
+              {
+                rr += b_rr[r][threadIdx.x];
+                mm += b_mm[r][threadIdx.x];
+              }
+            p_rr[(size_t)g * m + threadIdx.x] = rr;
+            p_mm[(size_t)g * m + threadIdx.x] = mm;
+          }
+        __syncthreads();
+      }
+  }
+
+  // res_j = ||AX_j - theta_j MX_j|| / (|theta_j| ||MX_j||), one thread per column
+  __global__ void k_eig_residual(int m, int nslab, const double *__restrict__ p_rr, const double *__restrict__ p_mm,
+                                 const double *__restrict__ theta, const int *__restrict__ status, double *__restrict__ res)
+  {
+    const int j = threadIdx.x;
+    if (j >= m || *status != 0)
+      return;
+    double rr = 0.0, mm = 0.0;
+    for (int g = 0; g < nslab; ++g)
+      {
+        rr += p_rr[(size_t)g * m + j];
+        mm += p_mm[(size_t)g * m + j];
+      }
+    res[j] = sqrt(rr) / (fabs(theta[j]) * sqrt(mm));
+  }
+} // namespace
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int slod_lod_matrix_symmetrize(slod_handle *h, const double *d_values, const uint32_t *d_cols, double *d_out, void *hip_stream)
+{
+  if (!h || !d_values || !d_cols || !d_out)
+    return SLOD_ERR_ARGUMENT;
+  if (d_out == d_values)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_matrix_symmetrize: a row reads other rows, the call cannot run in place");
+  if (const int rc = slod_ensure_device(h))
+    return rc;
+  (void)hipSetDevice(h->cfg.device);
+  const int    s = h->cfg.spacedim, cap = slod_lod_row_capacity(h);
+  const size_t n = (size_t)h->NP * cap * s * s;
+  hipLaunchKernelGGL(k_lod_symmetrize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hip_stream ? (hipStream_t)hip_stream : h->stream,
+                     h->NP, s, cap, d_values, d_cols, d_out);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_matrix_symmetrize");
+}
+
+int slod_lod_eigs(slod_handle *h, const double *d_stiffness, const double *d_mass, const uint32_t *d_cols, int n_eig, int n_block,
+                  int start, double *d_x, size_t ld_x, double tol, int max_outer, double inner_rel_tol, int inner_max_iterations,
+                  double *eigenvalues, double *residuals, int *inner_iterations)
+{
+  if (!h || !d_stiffness || !d_mass || !d_cols || !d_x || !eigenvalues || !residuals)
+    return SLOD_ERR_ARGUMENT;
+  const int s = h->cfg.spacedim, nrow = h->NP * s, m = n_block;
+  if (n_eig < 1 || n_block < n_eig)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_eigs: n_eig < 1 or n_block < n_eig");
+  if (n_block > EG_COLS || n_block > nrow)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_eigs: n_block above 64 or above the number of rows");
+  if (ld_x < (size_t)n_block)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_eigs: leading dimension below n_block");
+  if (start != 0 && start != 1)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_eigs: start is neither 0 nor 1");
+  if (!(tol > 0.0) || !(inner_rel_tol > 0.0))
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_eigs: tol or inner_rel_tol is not positive");
+  if (max_outer < 1 || inner_max_iterations < 0)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_eigs: max_outer < 1 or inner_max_iterations < 0");
+  if (const int rc = slod_ensure_device(h))
+    return rc;
+  (void)hipSetDevice(h->cfg.device);
+  hipStream_t  st = h->stream;
+  const int    n_gslab = (nrow + GR_ROWS - 1) / GR_ROWS, n_rslab = (nrow + RT_ROWS - 1) / RT_ROWS;
+  const size_t nvec = (size_t)nrow * m, mm = (size_t)m * m;
+  // one allocation for the whole loop: Y, Z, W, V, the slab partials, Ga | Gm, Q, theta | residuals | status, the CG
+  const size_t n_work = 4 * nvec + 2 * mm * n_gslab + 3 * mm + 2 * (size_t)m * n_rslab + 2 * (size_t)m + 1;
+  double      *work = nullptr;
+  int         *d_active = nullptr;
+  hipError_t   e = hipMalloc((void **)&work, (n_work + slod_mcg_work_doubles(h, m)) * sizeof(double));
+  if (e == hipSuccess)
+    e = hipMalloc((void **)&d_active, (size_t)m * sizeof(int));
+  int outer = 0, failed_column = 0;
+  if (e == hipSuccess)
+    {
+      double *Y = work, *Z = Y + nvec, *W = Z + nvec, *V = W + nvec, *partial = V + nvec, *G = partial + 2 * mm * n_gslab;
+      double *Q = G + 2 * mm, *p_rr = Q + mm, *p_mm = p_rr + (size_t)m * n_rslab, *scal = p_mm + (size_t)m * n_rslab;
+      double *theta = scal, *res = scal + m, *cg = scal + 2 * m + 1;
+      int    *status = (int *)(scal + 2 * m);
+      if (start == 0)
+        {
+          // the pairs (a, b) of {1..N}^2 in ascending a^2 + b^2, ties by ascending a
+          const int                        side = std::min(h->N, EG_COLS), n_modes = (m + s - 1) / s;
+          std::vector<std::pair<int, int>> ab;
+          for (int a = 1; a <= side; ++a)
+            for (int b = 1; b <= side; ++b)
+              ab.emplace_back(a, b);
+          std::sort(ab.begin(), ab.end(), [](const std::pair<int, int> &u, const std::pair<int, int> &v) {
+            const int nu = u.first * u.first + u.second * u.second, nv = v.first * v.first + v.second * v.second;
+            return nu != nv ? nu < nv : u.first < v.first;
+          });
+          EigModes md{};
+          for (int t = 0; t < n_modes; ++t)
+            {
+              md.a[t] = (unsigned char)ab[t].first;
+              md.b[t] = (unsigned char)ab[t].second;
+            }
+          hipLaunchKernelGGL(k_eig_start, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, st, slod_grid_of(h), h->NP, s, m, md,
+                             d_x, ld_x);
+          e = hipGetLastError();
+        }
+      std::vector<int>    its((size_t)m);
+      std::vector<double> host(2 * (size_t)m + 1);
+      bool                done = false;
+      while (e == hipSuccess && !done && outer < max_outer)
+        {
+          slod_lod_apply_launch(h, st, d_mass, d_cols, d_x, ld_x, m, Y, (size_t)m);
+          e = hipGetLastError();
+          if (e == hipSuccess)
+            e = slod_mcg_solve(h, d_stiffness, d_cols, Y, (size_t)m, m, Z, (size_t)m, inner_rel_tol, inner_max_iterations, cg,
+                               d_active, its.data(), nullptr);
+          if (e != hipSuccess)
+            break;
+          slod_lod_apply_launch(h, st, d_stiffness, d_cols, Z, (size_t)m, m, W, (size_t)m);
+          slod_lod_apply_launch(h, st, d_mass, d_cols, Z, (size_t)m, m, V, (size_t)m);
+          hipLaunchKernelGGL(k_eig_gram, dim3((unsigned)std::min(n_gslab, GR_MAX_BLOCKS)), dim3(GR_BLOCK), 0, st, nrow, m, n_gslab, Z, W,
+                             V, partial);
+          hipLaunchKernelGGL(k_eig_gram_sum, dim3((unsigned)((2 * mm + 255) / 256)), dim3(256), 0, st, m, n_gslab, partial, G);
+          hipLaunchKernelGGL(k_eig_ritz, dim3(1), dim3(RZ_BLOCK), 0, st, m, G, Q, theta, status);
+          hipLaunchKernelGGL(k_eig_rotate, dim3((unsigned)std::min(n_rslab, RT_MAX_BLOCKS)), dim3(RT_BLOCK), 0, st, nrow, m, n_rslab, Z,
+                             W, V, Q, theta, status, d_x, ld_x, p_rr, p_mm);
+          hipLaunchKernelGGL(k_eig_residual, dim3(1), dim3(EG_COLS), 0, st, m, n_rslab, p_rr, p_mm, theta, status, res);
+          e = hipGetLastError();
+          if (e == hipSuccess)
+            e = hipMemcpyAsync(host.data(), scal, host.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+          if (e == hipSuccess)
+            e = hipStreamSynchronize(st);
+          if (e != hipSuccess)
+            break;
+          if (inner_iterations)
+            inner_iterations[outer] = *std::max_element(its.begin(), its.end());
+          ++outer;
+          std::memcpy(&failed_column, &host[2 * (size_t)m], sizeof(int));
+          if (failed_column != 0)
+            break;
+          std::copy(host.begin(), host.begin() + m, eigenvalues);
+          std::copy(host.begin() + m, host.begin() + 2 * m, residuals);
+          done = true;
+          for (int j = 0; j < n_eig; ++j)
+            done = done && residuals[j] <= tol;
+        }
+    }
+  if (work)
+    (void)hipFree(work);
+  if (d_active)
+    (void)hipFree(d_active);
+  if (e != hipSuccess)
+    return slod_hip_fail(h, e, "slod_lod_eigs");
+  if (failed_column != 0)
+    return slod_fail(h, SLOD_ERR_NUMERIC,
+                     "slod_lod_eigs: non-positive pivot in the Cholesky of Gm = Z^T M Z at column " + std::to_string(failed_column - 1) +
+                       " of outer iteration " + std::to_string(outer) + " (rank-deficient block)");
+  return outer;
+}
+
+} // extern "C"
+#pragma GCC visibility pop

@@ -205,6 +205,13 @@ namespace
   }
 } // namespace
 
+// k_lod_apply for the other loops of the library (slod_lod_eig.hip); arguments are checked by the caller
+void slod_lod_apply_launch(const slod_handle *h, hipStream_t st, const double *d_values, const uint32_t *d_cols, const double *d_x,
+                           size_t ld_x, int n_rhs, double *d_y, size_t ld_y)
+{
+  launch_apply(h, st, d_values, d_cols, d_x, ld_x, n_rhs, d_y, ld_y);
+}
+
 #pragma GCC visibility push(default)
 extern "C" {
 

@@ -445,6 +445,44 @@ namespace slod
           "slod_compute_error_norms");
   }
 
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_eigenproblem(const unsigned int n_eig)
+  {
+    if (!d_lod_mass)
+      throw std::runtime_error("solve_eigenproblem: assemble_global_matrix and assemble_mass_matrix come first");
+    const unsigned int n_patches = (unsigned int)patches.size();
+    const std::size_t  n_coarse = (std::size_t)n_patches * spacedim;
+    if (n_eig < 1 || n_eig > n_coarse || n_eig > 64)
+      throw std::runtime_error("solve_eigenproblem: n_eig outside 1 .. min(64, unknowns)");
+    const std::size_t NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+    const std::size_t fine_size = (NE + 1) * (NE + 1) * spacedim;
+    const int         cap = slod_lod_row_capacity(handle);
+    check(cap, "slod_lod_row_capacity");
+    // the defaults of the Python binding
+    const int n_block = (int)std::min(std::min<std::size_t>(64, n_coarse), n_eig + std::max<std::size_t>(4, n_eig / 2));
+    const int max_outer = 200;
+    if (!d_lod_sym)
+      d_lod_sym = device_alloc<double>((std::size_t)n_patches * cap * spacedim * spacedim);
+    d_eig_x    = device_alloc<double>(n_coarse * n_block);
+    d_eig_fine = device_alloc<double>(n_eig * fine_size);
+    check(slod_lod_matrix_symmetrize(handle, d_lod_values, d_lod_cols, d_lod_sym, nullptr), "slod_lod_matrix_symmetrize");
+    lod_eigenvalues.assign(n_block, 0.0);
+    lod_eig_residuals.assign(n_block, 0.0);
+    lod_eig_inner_iterations.assign(max_outer, 0);
+    const int outer = slod_lod_eigs(handle, d_lod_sym, d_lod_mass, d_lod_cols, (int)n_eig, n_block, 0, d_eig_x, (std::size_t)n_block,
+                                    1e-10, max_outer, 1e-12, 2000, lod_eigenvalues.data(), lod_eig_residuals.data(),
+                                    lod_eig_inner_iterations.data());
+    check(outer < 0 ? outer : 0, "slod_lod_eigs");
+    lod_eig_inner_iterations.resize(outer);
+    check(slod_lod_reconstruct_multi(handle, d_basis, basis_stride, d_eig_x, (std::size_t)n_block, (int)n_eig, d_eig_fine, fine_size,
+                                     nullptr),
+          "slod_lod_reconstruct_multi");
+    lod_eig_norms.assign(n_eig, slod_error_norms{});
+    for (unsigned int k = 0; k < n_eig; ++k)
+      check(slod_compute_error_norms(handle, 0, d_eig_fine + k * fine_size, nullptr, nullptr, nullptr, &lod_eig_norms[k], nullptr),
+            "slod_compute_error_norms");
+  }
+
   // LOD.cc:1103-1237 with f = 1.  The reference solves with SolverDirect; the CG of the fine problem runs on the
   // coarse grid to the tolerance of the fine solve.
   template <int dim, int spacedim>

@@ -132,6 +132,15 @@ namespace slod
     void compare_heat_with_lod();
     const slod_error_norms &error_heat_LOD() const { return heat_lod_error; }
     const slod_error_norms &norms_LOD() const { return lod_norms; }
+    // The lowest n_eig eigenpairs of A_LOD u = lambda M_LOD u after assemble_mass_matrix() (the reference has no
+    // counterpart): A_LOD symmetrised (slod_lod_matrix_symmetrize), slod_lod_eigs with its documented defaults
+    // (n_eig + max(4, n_eig / 2) block columns, tol 1e-10, inner tolerance 1e-12), then the eigenfunctions C x_k on the
+    // fine grid (slod_lod_reconstruct_multi) and their norms (slod_compute_error_norms)
+    void solve_eigenproblem(const unsigned int n_eig);
+    const std::vector<double>           &eigenvalues() const { return lod_eigenvalues; }   // all block columns
+    const std::vector<double>           &eigen_residuals() const { return lod_eig_residuals; }
+    const std::vector<int>              &eigen_inner_iterations() const { return lod_eig_inner_iterations; } // per outer iteration
+    const std::vector<slod_error_norms> &eigenfunction_norms() const { return lod_eig_norms; } // n_eig entries
     const slod_error_norms &error_LOD_FEMh() const { return lod_fem_error; }
     // the same norms of u_h alone (the denominators of relative errors)
     const slod_error_norms &norms_FEMh() const { return fem_norms; }
@@ -185,6 +194,11 @@ namespace slod
     std::vector<int>    lod_heat_iterations;
     std::vector<double> lod_heat_residuals;
     slod_error_norms    heat_lod_error{}, lod_norms{};
+    // solve_eigenproblem: the symmetrised stiffness, the block X and the reconstructed eigenfunctions
+    double                       *d_lod_sym = nullptr, *d_eig_x = nullptr, *d_eig_fine = nullptr;
+    std::vector<double>           lod_eigenvalues, lod_eig_residuals;
+    std::vector<int>              lod_eig_inner_iterations;
+    std::vector<slod_error_norms> lod_eig_norms;
     // solve_multi: fine load vectors and reconstructions, field k at + k * fine_size
     double                       *d_multi_fem_rhs = nullptr, *d_multi_fine = nullptr;
     std::vector<int>              lod_multi_iterations;

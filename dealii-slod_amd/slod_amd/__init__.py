@@ -122,6 +122,9 @@ def load():
     lib.slod_lod_matrix_combine.argtypes = [vp, C.c_double, vp, C.c_double, vp, vp, vp]
     lib.slod_lod_theta_steps.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.c_size_t, vp,
                                          C.c_size_t, C.c_size_t, C.c_double, C.c_int, C.POINTER(C.c_int), dp]
+    lib.slod_lod_matrix_symmetrize.argtypes = [vp, vp, vp, vp, vp]
+    lib.slod_lod_eigs.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_double, C.c_int, C.c_double,
+                                  C.c_int, dp, dp, C.POINTER(C.c_int)]
     lib.slod_fem_rhs.argtypes = [vp, vp, vp, vp]
     lib.slod_fem_solve.argtypes = [vp, C.c_uint32, vp, vp, C.c_double, C.c_int, dp]
     lib.slod_coarse_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, vp]
@@ -410,6 +413,29 @@ class Slod:
         if rc < 0:
             self._check(rc)
         return its[:n_steps], res[:n_steps]
+
+    # ---- the eigenvalue problem A_LOD u = lambda M_LOD u ----
+    def lod_matrix_symmetrize(self, d_values, d_cols, d_out, stream=None):
+        """out = 0.5 * (A + A^T) on a full set of block rows, bit-symmetric; not in place.  Asynchronous."""
+        self._check(self.lib.slod_lod_matrix_symmetrize(self.h, d_values, d_cols, d_out, stream))
+
+    def lod_eigs(self, d_stiffness, d_mass, d_cols, n_eig, d_x, n_block=None, ld_x=None, start=0, tol=1e-10, max_outer=200,
+                 inner_rel_tol=1e-12, inner_max_iterations=2000):
+        """The lowest n_eig eigenpairs of the symmetric pencil (A, M) by block inverse iteration with Rayleigh-Ritz on
+        n_block columns (default: n_eig and a few guard columns); d_x receives the M-orthonormal block.  Returns
+        (eigenvalues[n_block], residuals[n_block], inner_iterations[outer]); len(inner_iterations) is the C call's
+        return value.  The guard columns n_eig .. n_block-1 are less converged."""
+        if n_block is None:
+            n_block = min(64, self.num_patches * self.spacedim, n_eig + max(4, n_eig // 2))
+        lam = np.zeros(max(n_block, 1))
+        res = np.zeros(max(n_block, 1))
+        its = np.zeros(max(max_outer, 1), dtype=np.intc)
+        rc = self.lib.slod_lod_eigs(self.h, d_stiffness, d_mass, d_cols, n_eig, n_block, start, d_x,
+                                    n_block if ld_x is None else ld_x, tol, max_outer, inner_rel_tol, inner_max_iterations,
+                                    _dp(lam), _dp(res), its.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc < 0:
+            self._check(rc)
+        return lam[:n_block], res[:n_block], its[:rc]
 
     def fem_rhs(self, d_f_qp, d_fine_rhs, stream=None):
         """Fine FEM load vector (d_f_qp = None: f = 1)."""

@@ -321,6 +321,55 @@ int slod_lod_theta_steps(slod_handle *h, const double *d_stiffness, const double
                          int *iterations /* HOST [n_steps], may be NULL */,
                          double *rel_residual /* HOST [n_steps], may be NULL */);
 
+/* ---- the eigenvalue problem  A_LOD u = lambda M_LOD u  on the device ---------------------
+ * The lowest vibration modes or heat-decay rates of the medium, on the LOD space (the reference has no counterpart).
+ * Matrices are full sets of block rows (rows 0 .. num_patches-1) in the layout of slod_lod_matrix, coarse multi-vectors
+ * those of the _multi calls.  Argument checks come before any device work; SLOD_ERR_DEVICE without a usable GPU. */
+/* d_out = (A + A^T) / 2 on the block rows: for every used slot (p, j), q = d_cols[p * cap + j], and every (d, e)
+ *   d_out[(p * cap + j) * s * s + d * s + e] = 0.5 * (A[p,j][d][e] + A[q,j'][e][d]),  j' the slot of p in row q
+ * (0 for the transposed entry if row q does not hold p; the pattern of slod_lod_matrix is symmetric).  The sum is
+ * rounded once and the halving is exact, so d_out is symmetric bit for bit and equals numpy's 0.5 * (A + A.T) of the
+ * densified rows bit for bit.  Unused slots are written as +0.  slod_lod_matrix gives A_LOD symmetric only up to the
+ * basis accuracy (~1e-9 of its scale); that skew part would set a floor under every eigen-residual.
+ * SLOD_ERR_ARGUMENT: NULL handle or array; d_out == d_values (a row reads other rows, the call cannot run in place).
+ * Asynchronous on hip_stream. */
+int slod_lod_matrix_symmetrize(slod_handle *h, const double *d_values, const uint32_t *d_cols, double *d_out, void *hip_stream);
+/* The lowest n_eig eigenpairs of the symmetric pencil (A, M) by block inverse iteration with Rayleigh-Ritz on
+ * m = n_block columns, 1 <= n_eig <= n_block <= min(64, num_patches * s); the n_block - n_eig extra columns are guard
+ * vectors (the error of column j contracts by about lambda_j / lambda_{m+1} per outer iteration).
+ * d_stiffness must be symmetric: the output of slod_lod_matrix_symmetrize (not checked).  d_mass: the output of
+ * slod_lod_mass_matrix, which is bit-symmetric already.
+ * start = 1: d_x holds the start block on entry.  start = 0: the call writes one: column j, with t = j / s and
+ * d = j % s, has the entry  delta_de sin(a_t pi (cx + 1/2) / N) sin(b_t pi (cy + 1/2) / N)  for (patch p, component e),
+ * (cx, cy) the centre cell of p and (a_t, b_t) the t-th pair of {1..N}^2 in ascending a^2 + b^2, ties by ascending a
+ * (the discrete sine modes on the cell centres).
+ * Outer iteration k = 1, 2, ..; only the n_block residuals and the inner solve's flags are read back per iteration:
+ *   Y = M X;  A Z = Y from Z = 0 (the recurrence of slod_lod_solve_multi with inner_rel_tol, inner_max_iterations);
+ *   W = A Z, V = M Z (exact products: the residual below is honest whatever the inner tolerance was);
+ *   Ga = sym(Z^T W), Gm = sym(Z^T V);  Ga Q = Gm Q Theta with Q^T Gm Q = I, Theta ascending (Cholesky of Gm,
+ *   cyclic Jacobi);  X = Z Q;  res_j = ||A X_j - theta_j M X_j||_2 / (theta_j ||M X_j||_2) from W Q and V Q;
+ *   stop when res_j <= tol for all j < n_eig, or at k = max_outer (not an error, as in slod_lod_solve).
+ * On return d_x holds X, M-orthonormal, column j at d_x[i * ld_x + j] (entries j >= n_block of a row are never read or
+ * written); HOST eigenvalues[n_block] and residuals[n_block] hold all n_block columns: the guard columns
+ * j >= n_eig are less converged than the first n_eig and their residuals are not bounded by tol.
+ * HOST inner_iterations[k] (max_outer entries, may be NULL): the largest per-column CG count of outer iteration k + 1.
+ * Returns the number of outer iterations run (>= 1) or a negative slod_status.  SLOD_ERR_NUMERIC: a pivot of the
+ * Cholesky of Gm is not above 4 m eps times its diagonal entry (rank-deficient block, e.g. two equal start columns);
+ * d_x then holds the block the failed iteration started from.
+ * Sums have a fixed order (no atomics): the same inputs give the same bits of X, Theta, the residuals and all counts,
+ * run after run.  Unlike the _multi calls this is a block method: the columns are NOT independent of each other, a
+ * column's result depends on n_block and on the other columns.  Device workspace (8 vectors of n_block columns and the
+ * slab partials of the Gram products) allocated once per call.
+ * SLOD_ERR_ARGUMENT: NULL handle, matrix, d_cols, d_x, eigenvalues or residuals; n_eig < 1; n_block < n_eig;
+ * n_block > 64 or > num_patches * s; ld_x < n_block; start not 0 or 1; tol or inner_rel_tol <= 0 or NaN; max_outer < 1;
+ * inner_max_iterations < 0.  Runs on the handle's stream; synchronises. */
+int slod_lod_eigs(slod_handle *h, const double *d_stiffness, const double *d_mass, const uint32_t *d_cols,
+                  int n_eig, int n_block, int start, double *d_x, size_t ld_x,
+                  double tol, int max_outer, double inner_rel_tol, int inner_max_iterations,
+                  double *eigenvalues      /* HOST [n_block] */,
+                  double *residuals        /* HOST [n_block] */,
+                  int    *inner_iterations /* HOST [max_outer], may be NULL */);
+
 /* ---- fine FEM reference problem (assemble_and_solve_fem_problem, LOD.cc:1004-1094) ----
  * What the reference compares the LOD solution with (compare_lod_with_fem, LOD.cc:1240-1378).
  * fem_rhs of assemble_stiffness (Diffusion.h:149-193) on the global fine grid, [(NE+1)^2][s],
