@@ -208,14 +208,13 @@ int slod_compute_error_norms(slod_handle *h, uint32_t problem, const double *d_u
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_compute_error_norms: exact-solution arrays must be 16-byte aligned");
   if (problem >= (uint32_t)h->cfg.n_problems)
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_compute_error_norms: problem out of range");
-  if (const int rc = slod_ensure_device(h))
+  hipStream_t st;
+  if (const int rc = slod_enter(h, hip_stream, &st))
     return rc;
   const int s = h->cfg.spacedim;
   for (int f = 0; f < s; ++f)
     if (!h->coef_set[(size_t)problem * 2 + f])
       return slod_fail(h, SLOD_ERR_STATE, "slod_compute_error_norms: coefficient not set");
-  (void)hipSetDevice(h->cfg.device);
-  hipStream_t    st   = hip_stream ? (hipStream_t)hip_stream : h->stream;
   // runs of ERR_BLOCK elements per block: 1 up to 2048 blocks, then as many as keep the partials at <= 2048
   // blocks (NE = 2048: 8).  A function of NE alone, so the summation order is fixed for the handle.
   const size_t   nel  = (size_t)h->NE * h->NE, runs = (nel + ERR_BLOCK - 1) / ERR_BLOCK;

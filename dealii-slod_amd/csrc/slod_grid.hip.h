@@ -1,5 +1,5 @@
-// Index calculus on the coarse grid shared by host and device code of the global steps (slod_global.hip,
-// slod_lod_time.hip): patch id <-> centre cell, and the extent of a patch in coarse cells.  The overlap of two
+// Index calculus on the coarse grid shared by host and device code of the global steps (slod_lod_system.hip,
+// slod_plan_build.hip, slod_lod_time.hip): patch id <-> centre cell, and the extent of a patch in coarse cells.  The overlap of two
 // patches is a rectangle of global fine nodes; everything derives from the scalars of SlodGrid (slod_host.h).
 #ifndef SLOD_GRID_HIP_H
 #define SLOD_GRID_HIP_H

@@ -1,5 +1,5 @@
-// Host-side internals of libslod_hip.so shared by slod_api.cpp and slod_global.hip (not part of
-// the public ABI).
+// Host-side internals of libslod_hip.so shared by slod_api.cpp and the .hip units of the global steps
+// (not part of the public ABI).
 #ifndef SLOD_HOST_H
 #define SLOD_HOST_H
 #pragma GCC visibility push(default)
@@ -7,7 +7,9 @@
 #pragma GCC visibility pop
 #include "slod_device.h"
 
+#include <algorithm>
 #include <string>
+#include <utility>
 #include <vector>
 
 struct slod_handle
@@ -41,6 +43,55 @@ inline int slod_hip_fail(const slod_handle *h, hipError_t e, const char *what)
 }
 // stream + coefficient storage; called by every entry point that touches the device (slod_api.cpp)
 int slod_ensure_device(slod_handle *h);
+// The prologue of an entry point once its argument checks have passed: the device exists and is current,
+// *st (st may be null) is the caller's stream or, for a null hip_stream, the handle's.  0 or the status to return.
+inline int slod_enter(slod_handle *h, void *hip_stream, hipStream_t *st)
+{
+  if (const int rc = slod_ensure_device(h))
+    return rc;
+  (void)hipSetDevice(h->cfg.device);
+  if (st)
+    *st = hip_stream ? (hipStream_t)hip_stream : h->stream;
+  return SLOD_OK;
+}
+// Move-only owner of one hipMalloc, freed when it leaves scope: the stream that used the memory must have
+// been synchronised by then.
+template <typename T>
+class SlodDevBuf
+{
+public:
+  SlodDevBuf() = default;
+  SlodDevBuf(SlodDevBuf &&o) noexcept : p(std::exchange(o.p, nullptr)) {}
+  ~SlodDevBuf() { if (p) (void)hipFree(p); }
+  // count objects of T, uninitialised; once per owner
+  hipError_t alloc(size_t count) { return hipMalloc((void **)&p, count * sizeof(T)); }
+  T         *get() const { return p; }
+
+private:
+  T *p = nullptr;
+};
+// A caller-owned host array of row patch ids.  slod_check_rows: an id that is no patch of the handle is
+// SLOD_ERR_ARGUMENT, "<who>: row patch id out of range" (who NULL: no prefix).  slod_upload_rows: that check,
+// then the copy to d_rows, synchronised on st.
+inline int slod_check_rows(const slod_handle *h, const char *who, const uint32_t *rows, size_t n)
+{
+  for (size_t k = 0; k < n; ++k)
+    if (rows[k] >= (uint32_t)h->NP)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, (who ? std::string(who) + ": " : std::string()) + "row patch id out of range");
+  return SLOD_OK;
+}
+inline int slod_upload_rows(slod_handle *h, const char *who, const uint32_t *rows, size_t n, hipStream_t st,
+                            SlodDevBuf<uint32_t> *d_rows)
+{
+  if (const int rc = slod_check_rows(h, who, rows, n))
+    return rc;
+  hipError_t e = d_rows->alloc(std::max<size_t>(n, 1));
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(d_rows->get(), rows, n * sizeof(uint32_t), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(st); // rows is a caller-owned host array
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, who ? who : "row upload");
+}
 // Device copy of the index calculus a kernel needs: everything derives from these scalars.
 struct SlodGrid
 {
@@ -58,7 +109,7 @@ inline SlodGrid slod_grid_of(const slod_handle *h)
   g.lod_stabilization = h->cfg.lod_stabilization;
   return g;
 }
-// plan construction on the device (slod_global.hip: k_make_desc, k_balance_order)
+// plan construction on the device (slod_plan_build.hip: k_make_desc, k_balance_order)
 struct SlodPlanSummary
 {
   int32_t            m_max, L_max, nc_max, nb_max, nn_max, error;

@@ -464,13 +464,12 @@ int slod_lod_matrix_symmetrize(slod_handle *h, const double *d_values, const uin
     return SLOD_ERR_ARGUMENT;
   if (d_out == d_values)
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_matrix_symmetrize: a row reads other rows, the call cannot run in place");
-  if (const int rc = slod_ensure_device(h))
+  hipStream_t st;
+  if (const int rc = slod_enter(h, hip_stream, &st))
     return rc;
-  (void)hipSetDevice(h->cfg.device);
   const int    s = h->cfg.spacedim, cap = slod_lod_row_capacity(h);
   const size_t n = (size_t)h->NP * cap * s * s;
-  hipLaunchKernelGGL(k_lod_symmetrize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hip_stream ? (hipStream_t)hip_stream : h->stream,
-                     h->NP, s, cap, d_values, d_cols, d_out);
+  hipLaunchKernelGGL(k_lod_symmetrize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, h->NP, s, cap, d_values, d_cols, d_out);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_matrix_symmetrize");
 }
@@ -494,23 +493,22 @@ int slod_lod_eigs(slod_handle *h, const double *d_stiffness, const double *d_mas
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_eigs: tol or inner_rel_tol is not positive");
   if (max_outer < 1 || inner_max_iterations < 0)
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_eigs: max_outer < 1 or inner_max_iterations < 0");
-  if (const int rc = slod_ensure_device(h))
+  hipStream_t st;
+  if (const int rc = slod_enter(h, nullptr, &st))
     return rc;
-  (void)hipSetDevice(h->cfg.device);
-  hipStream_t  st = h->stream;
   const int    n_gslab = (nrow + GR_ROWS - 1) / GR_ROWS, n_rslab = (nrow + RT_ROWS - 1) / RT_ROWS;
   const size_t nvec = (size_t)nrow * m, mm = (size_t)m * m;
   // one allocation for the whole loop: Y, Z, W, V, the slab partials, Ga | Gm, Q, theta | residuals | status, the CG
   const size_t n_work = 4 * nvec + 2 * mm * n_gslab + 3 * mm + 2 * (size_t)m * n_rslab + 2 * (size_t)m + 1;
-  double      *work = nullptr;
-  int         *d_active = nullptr;
-  hipError_t   e = hipMalloc((void **)&work, (n_work + slod_mcg_work_doubles(h, m)) * sizeof(double));
+  SlodDevBuf<double> work;
+  SlodDevBuf<int>    d_active;
+  hipError_t         e = work.alloc(n_work + slod_mcg_work_doubles(h, m));
   if (e == hipSuccess)
-    e = hipMalloc((void **)&d_active, (size_t)m * sizeof(int));
+    e = d_active.alloc((size_t)m);
   int outer = 0, failed_column = 0;
   if (e == hipSuccess)
     {
-      double *Y = work, *Z = Y + nvec, *W = Z + nvec, *V = W + nvec, *partial = V + nvec, *G = partial + 2 * mm * n_gslab;
+      double *Y = work.get(), *Z = Y + nvec, *W = Z + nvec, *V = W + nvec, *partial = V + nvec, *G = partial + 2 * mm * n_gslab;
       double *Q = G + 2 * mm, *p_rr = Q + mm, *p_mm = p_rr + (size_t)m * n_rslab, *scal = p_mm + (size_t)m * n_rslab;
       double *theta = scal, *res = scal + m, *cg = scal + 2 * m + 1;
       int    *status = (int *)(scal + 2 * m);
@@ -545,7 +543,7 @@ int slod_lod_eigs(slod_handle *h, const double *d_stiffness, const double *d_mas
           e = hipGetLastError();
           if (e == hipSuccess)
             e = slod_mcg_solve(h, d_stiffness, d_cols, Y, (size_t)m, m, Z, (size_t)m, inner_rel_tol, inner_max_iterations, cg,
-                               d_active, its.data(), nullptr);
+                               d_active.get(), its.data(), nullptr);
           if (e != hipSuccess)
             break;
           slod_lod_apply_launch(h, st, d_stiffness, d_cols, Z, (size_t)m, m, W, (size_t)m);
@@ -577,10 +575,7 @@ int slod_lod_eigs(slod_handle *h, const double *d_stiffness, const double *d_mas
             done = done && residuals[j] <= tol;
         }
     }
-  if (work)
-    (void)hipFree(work);
-  if (d_active)
-    (void)hipFree(d_active);
+  // (every completed pass of the loop ends on a synchronised stream: work and d_active are idle when they are freed)
   if (e != hipSuccess)
     return slod_hip_fail(h, e, "slod_lod_eigs");
   if (failed_column != 0)

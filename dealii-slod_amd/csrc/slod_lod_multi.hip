@@ -315,25 +315,20 @@ int slod_lod_solve_multi(slod_handle *h, const double *d_values, const uint32_t 
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_solve_multi: n_rhs < 1 or max_iterations < 0");
   if (ld_rhs < (size_t)n_rhs || ld_u < (size_t)n_rhs)
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_solve_multi: leading dimension below n_rhs");
-  if (const int rc = slod_ensure_device(h))
+  if (const int rc = slod_enter(h, nullptr, nullptr))
     return rc;
-  (void)hipSetDevice(h->cfg.device);
-  // workspace allocated per call
-  double    *work = nullptr;
-  int       *d_active = nullptr;
-  hipError_t e = hipMalloc((void **)&work, slod_mcg_work_doubles(h, n_rhs) * sizeof(double));
+  // workspace allocated per call; slod_mcg_solve synchronises the stream before it returns
+  SlodDevBuf<double> work;
+  SlodDevBuf<int>    d_active;
+  hipError_t         e = work.alloc(slod_mcg_work_doubles(h, n_rhs));
   if (e == hipSuccess)
-    e = hipMalloc((void **)&d_active, (size_t)n_rhs * sizeof(int));
+    e = d_active.alloc((size_t)n_rhs);
   std::vector<int> its((size_t)n_rhs, 0);
   if (e == hipSuccess)
-    e = slod_mcg_solve(h, d_values, d_cols, d_rhs, ld_rhs, n_rhs, d_u, ld_u, rel_tol, max_iterations, work, d_active, its.data(),
-                       rel_residual);
+    e = slod_mcg_solve(h, d_values, d_cols, d_rhs, ld_rhs, n_rhs, d_u, ld_u, rel_tol, max_iterations, work.get(), d_active.get(),
+                       its.data(), rel_residual);
   if (e == hipSuccess && iterations)
     std::copy(its.begin(), its.end(), iterations);
-  if (work)
-    (void)hipFree(work);
-  if (d_active)
-    (void)hipFree(d_active);
   if (e != hipSuccess)
     return slod_hip_fail(h, e, "slod_lod_solve_multi");
   return *std::max_element(its.begin(), its.end());

@@ -4,7 +4,7 @@
 //   slod_lod_apply_multi     Y = A X for any matrix in that layout, columns on lanes
 //   slod_lod_matrix_combine  out = alpha A + beta B on two values arrays of one pattern
 //   slod_lod_theta_steps     n_steps of the theta scheme for  M u' + A u = b(t), the state stays on the device
-// The mass kernel is an L2/HBM-bound gather like k_lod_matrix (slod_global.hip) and shares its index calculus
+// The mass kernel is an L2/HBM-bound gather like k_lod_matrix (slod_lod_system.hip) and shares its index calculus
 // (slod_grid.hip.h); the solve of a step is the recurrence of slod_lod_solve_multi (slod_lod_multi.hip) on a
 // workspace this file owns for the whole loop.
 #include "slod_host.h"
@@ -220,36 +220,27 @@ int slod_lod_mass_matrix(slod_handle *h, const uint32_t *rows, size_t n_rows, co
 {
   if (!h || (n_rows && (!rows || !d_basis || !d_values || !d_cols)))
     return SLOD_ERR_ARGUMENT;
-  for (size_t k = 0; k < n_rows; ++k)
-    if (rows[k] >= (uint32_t)h->NP)
-      return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_mass_matrix: row patch id out of range");
+  // (the ids are checked here as well as by the upload: a bad id is refused before any device work)
+  if (const int rc = slod_check_rows(h, "slod_lod_mass_matrix", rows, n_rows))
+    return rc;
   if (n_rows == 0)
     return SLOD_OK;
-  if (const int rc = slod_ensure_device(h))
+  hipStream_t st;
+  if (const int rc = slod_enter(h, hip_stream, &st))
     return rc;
-  (void)hipSetDevice(h->cfg.device);
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : h->stream;
-  uint32_t   *d_rows = nullptr;
-  hipError_t  e = hipMalloc((void **)&d_rows, n_rows * sizeof(uint32_t));
+  SlodDevBuf<uint32_t> d_rows;
+  if (const int rc = slod_upload_rows(h, "slod_lod_mass_matrix", rows, n_rows, st, &d_rows))
+    return rc;
+  const double hf = 1.0 / h->NE, scale = hf * hf / 36.0;
+  if (h->cfg.spacedim == 1)
+    hipLaunchKernelGGL(k_lod_mass<1>, dim3((unsigned)n_rows), dim3(256), 0, st, slod_grid_of(h), d_rows.get(), d_basis, stride,
+                       d_rho, scale, d_values, d_cols);
+  else
+    hipLaunchKernelGGL(k_lod_mass<2>, dim3((unsigned)n_rows), dim3(256), 0, st, slod_grid_of(h), d_rows.get(), d_basis, stride,
+                       d_rho, scale, d_values, d_cols);
+  hipError_t e = hipGetLastError();
   if (e == hipSuccess)
-    e = hipMemcpyAsync(d_rows, rows, n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st); // rows is a caller-owned host array
-  if (e == hipSuccess)
-    {
-      const double hf = 1.0 / h->NE, scale = hf * hf / 36.0;
-      if (h->cfg.spacedim == 1)
-        hipLaunchKernelGGL(k_lod_mass<1>, dim3((unsigned)n_rows), dim3(256), 0, st, slod_grid_of(h), d_rows, d_basis, stride,
-                           d_rho, scale, d_values, d_cols);
-      else
-        hipLaunchKernelGGL(k_lod_mass<2>, dim3((unsigned)n_rows), dim3(256), 0, st, slod_grid_of(h), d_rows, d_basis, stride,
-                           d_rho, scale, d_values, d_cols);
-      e = hipGetLastError();
-    }
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st); // d_rows is freed below
-  if (d_rows)
-    (void)hipFree(d_rows);
+    e = hipStreamSynchronize(st); // d_rows is freed on return
   return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_mass_matrix");
 }
 
@@ -264,10 +255,10 @@ int slod_lod_apply_multi(slod_handle *h, const double *d_values, const uint32_t 
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_apply_multi: leading dimension below n_rhs");
   if (d_x == d_y)
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_apply_multi: the product cannot run in place");
-  if (const int rc = slod_ensure_device(h))
+  hipStream_t st;
+  if (const int rc = slod_enter(h, hip_stream, &st))
     return rc;
-  (void)hipSetDevice(h->cfg.device);
-  launch_apply(h, hip_stream ? (hipStream_t)hip_stream : h->stream, d_values, d_cols, d_x, ld_x, n_rhs, d_y, ld_y);
+  launch_apply(h, st, d_values, d_cols, d_x, ld_x, n_rhs, d_y, ld_y);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_apply_multi");
 }
@@ -277,13 +268,12 @@ int slod_lod_matrix_combine(slod_handle *h, double alpha, const double *d_a, dou
 {
   if (!h || !d_a || !d_b || !d_out)
     return SLOD_ERR_ARGUMENT;
-  if (const int rc = slod_ensure_device(h))
+  hipStream_t st;
+  if (const int rc = slod_enter(h, hip_stream, &st))
     return rc;
-  (void)hipSetDevice(h->cfg.device);
   const int    s = h->cfg.spacedim;
   const size_t n = (size_t)h->NP * slod_lod_row_capacity(h) * s * s;
-  hipLaunchKernelGGL(k_lod_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hip_stream ? (hipStream_t)hip_stream : h->stream,
-                     n, alpha, d_a, beta, d_b, d_out);
+  hipLaunchKernelGGL(k_lod_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, alpha, d_a, beta, d_b, d_out);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_matrix_combine");
 }
@@ -300,22 +290,21 @@ int slod_lod_theta_steps(slod_handle *h, const double *d_stiffness, const double
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_theta_steps: n_steps < 1, n_rhs < 1 or max_iterations < 0");
   if (ld_u < (size_t)n_rhs || (d_load && ld_load < (size_t)n_rhs))
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_theta_steps: leading dimension below n_rhs");
-  if (const int rc = slod_ensure_device(h))
+  hipStream_t st;
+  if (const int rc = slod_enter(h, nullptr, &st))
     return rc;
-  (void)hipSetDevice(h->cfg.device);
-  hipStream_t  st = h->stream;
   const int    s = h->cfg.spacedim, nrow = h->NP * s;
   const size_t nmat = (size_t)h->NP * slod_lod_row_capacity(h) * s * s, nvec = (size_t)nrow * n_rhs;
   // one allocation for the whole loop: S, g, delta and the workspace of the solve
-  double    *work = nullptr;
-  int       *d_active = nullptr;
-  hipError_t e = hipMalloc((void **)&work, (nmat + 2 * nvec + slod_mcg_work_doubles(h, n_rhs)) * sizeof(double));
+  SlodDevBuf<double> work;
+  SlodDevBuf<int>    d_active;
+  hipError_t         e = work.alloc(nmat + 2 * nvec + slod_mcg_work_doubles(h, n_rhs));
   if (e == hipSuccess)
-    e = hipMalloc((void **)&d_active, (size_t)n_rhs * sizeof(int));
+    e = d_active.alloc((size_t)n_rhs);
   int worst = 0;
   if (e == hipSuccess)
     {
-      double        *S = work, *g = S + nmat, *delta = g + nvec, *cg = delta + nvec;
+      double        *S = work.get(), *g = S + nmat, *delta = g + nvec, *cg = delta + nvec;
       const unsigned nblk = (unsigned)((nvec + 255) / 256);
       hipLaunchKernelGGL(k_lod_combine, dim3((unsigned)((nmat + 255) / 256)), dim3(256), 0, st, nmat, 1.0, d_mass, theta * dt,
                          d_stiffness, S);
@@ -330,8 +319,8 @@ int slod_lod_theta_steps(slod_handle *h, const double *d_stiffness, const double
           hipLaunchKernelGGL(k_theta_rhs, dim3(nblk), dim3(256), 0, st, nrow, n_rhs, dt, theta, b0, b1, ld_load, g);
           e = hipGetLastError();
           if (e == hipSuccess)
-            e = slod_mcg_solve(h, S, d_cols, g, (size_t)n_rhs, n_rhs, delta, (size_t)n_rhs, rel_tol, max_iterations, cg, d_active,
-                               its.data(), res.data());
+            e = slod_mcg_solve(h, S, d_cols, g, (size_t)n_rhs, n_rhs, delta, (size_t)n_rhs, rel_tol, max_iterations, cg,
+                               d_active.get(), its.data(), res.data());
           if (e != hipSuccess)
             break;
           hipLaunchKernelGGL(k_theta_advance, dim3(nblk), dim3(256), 0, st, nrow, n_rhs, delta, d_u, ld_u);
@@ -344,12 +333,8 @@ int slod_lod_theta_steps(slod_handle *h, const double *d_stiffness, const double
             rel_residual[k] = *std::max_element(res.begin(), res.end());
         }
       if (e == hipSuccess)
-        e = hipStreamSynchronize(st);
+        e = hipStreamSynchronize(st); // work and d_active are freed on return
     }
-  if (work)
-    (void)hipFree(work);
-  if (d_active)
-    (void)hipFree(d_active);
   if (e != hipSuccess)
     return slod_hip_fail(h, e, "slod_lod_theta_steps");
   return worst;
