@@ -3,6 +3,7 @@
 // HIP device and fails with SLOD_ERR_DEVICE otherwise.
 // only the C-ABI of include/slod.h is exported (the library is built with -fvisibility=hidden)
 #include "slod_host.h"
+#include "slod_grid.hip.h"
 
 #include <algorithm>
 #include <cmath>
@@ -49,6 +50,7 @@ struct slod_plan
   slod_handle               *h = nullptr;
   size_t                     n = 0;
   std::vector<SlodPatchDesc> desc;
+  std::vector<uint32_t>      gids;                 // the caller's list (slod_plan_patch_layout)
   SlodPatchDesc             *d_desc = nullptr;     // the caller's order (pieces of slod_plan_execute_allgather)
   SlodPatchDesc             *d_desc_bal = nullptr; // launch order balanced over the CUs (slod_plan_execute)
   int                        m_max = 0, L_max = 0, nc_max = 0, nb_max = 0, nn_max = 0, nf_max = 0;
@@ -588,6 +590,7 @@ int slod_plan_create(slod_handle *h, const uint32_t *gids, size_t n, const uint6
       slod_plan_destroy(p);
       return fail(h, SLOD_ERR_ARGUMENT, "slod_plan_create: patch id out of range");
     }
+  p->gids.assign(gids, gids + n);
   p->m_max    = sum.m_max;
   p->L_max    = sum.L_max;
   p->nc_max   = sum.nc_max;
@@ -818,7 +821,9 @@ int slod_plan_patch_layout(slod_plan *p, size_t k, int launch_order, slod_patch_
   const SlodPatchDesc *src = (launch_order && p->d_desc_bal ? p->d_desc_bal : p->d_desc) + k;
   if (hipMemcpy(&d, src, sizeof(d), hipMemcpyDeviceToHost) != hipSuccess)
     return hip_fail(p->h, hipGetLastError(), "slod_plan_patch_layout");
-  slod_desc_to_info(p->h, d, info);
+  if (d.plan_index >= p->n)
+    return fail(p->h, SLOD_ERR_DEVICE, "slod_plan_patch_layout: descriptor read-back");
+  slod_desc_to_info(p->h, p->gids[d.plan_index] % (uint32_t)p->h->NP, d, info);
   if (plan_index)
     *plan_index = d.plan_index;
   return SLOD_OK;

@@ -47,5 +47,38 @@ namespace
     e.my         = y1 - e.y0 + 1;
     return e;
   }
+  // descriptor -> public patch layout (slod_plan_patch_layout, slod_device_patch_layout), everything from the
+  // descriptor the device built -- except the position of a full patch under the reuse quirk Q1: there
+  // k_make_desc stores the first full patch's coefficient origin in (ox, oy), and the patch's own origin is
+  // recomputed from its id.
+  inline void slod_desc_to_info(const slod_handle *h, uint32_t pid, const SlodPatchDesc &d, slod_patch_info *info)
+  {
+    const int n = h->cfg.n_subdivisions, s = h->cfg.spacedim, full = 2 * h->cfg.oversampling + 1;
+    *info       = slod_patch_info();
+    info->x0    = d.ox / n;
+    info->y0    = d.oy / n;
+    if (h->cfg.constant_coefficients && h->first_full >= 0 && d.mx == full && d.my == full)
+      {
+        const SlodGrid G = slod_grid_of(h);
+        int            cx, cy;
+        grid_centre(G, pid, cx, cy);
+        const Extent e = grid_extent(G, cx, cy);
+        info->x0       = e.x0;
+        info->y0       = e.y0;
+      }
+    info->cx = info->x0 + d.ccx;
+    info->cy = info->y0 + d.ccy;
+    info->mx = d.mx;
+    info->my = d.my;
+    info->nx = d.nx;
+    info->ny = d.ny;
+    for (int k = 0; k < 4; ++k)
+      info->side_domain[k] = (d.flags >> k) & 1;
+    info->n_fine     = s * (d.nx + 1) * (d.ny + 1);
+    info->n_internal = s * (d.nx - 1) * (d.ny - 1);
+    info->n_boundary = d.n_b;
+    info->n_coarse   = d.n_c;
+    info->is_lod     = (d.flags & SLOD_F_LOD) ? 1 : 0;
+  }
 } // namespace
 #endif

@@ -224,7 +224,7 @@ int slod_device_patch_layout(slod_handle *h, const uint32_t *patch_ids, size_t n
     {
       if (desc[k].prob != 0)
         return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_device_patch_layout: patch id out of range");
-      slod_desc_to_info(h, desc[k], &out[k]);
+      slod_desc_to_info(h, patch_ids[k], desc[k], &out[k]);
     }
   return SLOD_OK;
 }

@@ -1,6 +1,7 @@
 """GPU parity for the vector-valued (elasticity) path, the reference quirk switches, the
 non-2^k golden geometry and ragged / edge-case plans.  Same tolerances as test_gpu_parity."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -165,18 +166,25 @@ def test_size_independent_properties_at_full_size(so):
 
 @pytest.mark.parametrize("mode", ["mf", "tw", "coop", "nd"])
 @pytest.mark.parametrize("spacedim", [1, 2])
-def test_all_solver_kernels(so, mode, spacedim, monkeypatch):
+def test_all_solver_kernels(so, mode, spacedim, monkeypatch, capfd):
     """The patch-solve kernel families (twisted wave-specialised = default, MFMA-factorised,
     cooperative, nested dissection -- scalar problems only, vector plans fall back
-    to the default) must all meet the parity bar; SLOD_SOLVE selects one per plan."""
+    to the default) must all meet the parity bar; SLOD_SOLVE selects one per plan, and the launch
+    log (SLOD_DEBUG=1) names the family that ran."""
     monkeypatch.setenv("SLOD_SOLVE", mode)
+    monkeypatch.setenv("SLOD_DEBUG", "1")
     kw = dict(nref=3, n_sub=4, oversampling=1, stabilize=1) if spacedim == 1 else \
         dict(nref=2, n_sub=4, oversampling=1, spacedim=2, stabilize=1)
     cfg, g = _mk(so, **kw)
     fields = make_fields(so, cfg, "D100")
     _upload(g, fields)
     ids = np.arange(g.num_patches)
+    capfd.readouterr()
     basis, premult, offs = g.compute_basis(ids)
+    launched = set(re.findall(r"\[slod\] (k_solve(?:_tw|_mf|_nd)?<)", capfd.readouterr().err))
+    # nd takes scalar problems only: the vector plan (22 dofs per line) gets the automatic kernel, tw
+    family = {"mf": "k_solve_mf<", "tw": "k_solve_tw<", "coop": "k_solve<", "nd": "k_solve_nd<" if spacedim == 1 else "k_solve_tw<"}
+    assert launched == {family[mode]}, launched
     for k, pid in enumerate(ids):
         _check_patch(so, cfg, fields, int(pid), basis, premult, int(offs[k]), mode)
 

@@ -188,7 +188,10 @@ def test_device_patch_layout_matches_host_and_golden():
         pid = int(ln.split(":")[0][2:])
         cnt = int(ln.split("{")[1].split("}")[0])
         assert dev_infos[pid].mx * dev_infos[pid].my == cnt
-    for kw in (dict(nref=3, n_sub=4, oversampling=2, spacedim=2), dict(n_cells=6, n_sub=3, oversampling=1), dict(nref=2, n_sub=2, oversampling=2, stabilize=0)):
+    # (reuse_full: under quirk Q1 the descriptors of all full patches carry the first one's coefficient origin;
+    # the layout reported is the patch's own all the same)
+    for kw in (dict(nref=3, n_sub=4, oversampling=2, spacedim=2), dict(n_cells=6, n_sub=3, oversampling=1), dict(nref=2, n_sub=2, oversampling=2, stabilize=0),
+               dict(nref=3, n_sub=4, oversampling=1, reuse_full=1)):
         g = slod_amd.Slod(**kw)
         ids = np.arange(g.num_patches, dtype=np.uint32)
         for pid, di in zip(ids, g.device_patch_layout(ids)):
@@ -220,7 +223,7 @@ def test_plan_descriptors_are_device_built_and_match_golden():
         info, idx = plan.patch_layout(int(pid))
         assert bytes(info) == bytes(dinfo[pid]) == bytes(g.patch_layout(int(pid))) and idx == pid
     for kw in (dict(nref=3, n_sub=4, oversampling=2, spacedim=2), dict(n_cells=6, n_sub=3, oversampling=1),
-               dict(nref=2, n_sub=2, oversampling=2, stabilize=0)):
+               dict(nref=2, n_sub=2, oversampling=2, stabilize=0), dict(nref=3, n_sub=4, oversampling=1, reuse_full=1)):
         g2 = slod_amd.Slod(**kw)
         ids2 = np.arange(g2.num_patches, dtype=np.uint32)[::-1].copy()
         plan2 = g2.plan(ids2)
