@@ -1,6 +1,6 @@
 // Counterpart of reference app/main_Diffusion.cc for the basis-construction path:
 //   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare] [--coarse] [--loads K]
-//                  [--heat STEPS DT] [--eigs K]
+//                  [--heat STEPS DT] [--eigs K] [--wave STEPS DT]
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
 // file name it dumps, per patch, phi and psi in patch-lexicographic order (parity tests).
 // --compare (anywhere on the command line): after run(), the rest of the reference run() -- global
@@ -17,6 +17,10 @@
 // --eigs K: the K lowest eigenpairs of  A_LOD u = lambda M_LOD u  (A_LOD symmetrised, slod_lod_eigs with its defaults): one
 // line per pair with its eigenvalue and residual, the outer and inner iteration counts, and the fine-grid L2 norm of
 // every reconstructed eigenfunction.
+// --wave STEPS DT: the wave equation  M u'' + A u = C^T f  (f = 1, constant in time, A_LOD symmetrised) from rest by STEPS
+// steps of the trapezoidal rule (Newmark gamma = 1/2, beta = 1/4, slod_lod_newmark_steps): one line per step with its
+// iterations, relative residual, kinetic and potential energy and the work u^T b (kinetic + potential = work from rest
+// under a constant load), then the fine-grid L2 norm of the reconstructed final state.
 #include "../host/Diffusion.h"
 
 #include <cstdio>
@@ -70,8 +74,8 @@ int main(int argc_all, char **argv_all)
 {
   // --compare and --coarse are taken out wherever they stand; the positional arguments keep their meaning
   bool               compare = false, coarse = false;
-  int                n_loads = 0, heat_steps = 0, n_eigs = 0;
-  double             heat_dt = 0.0;
+  int                n_loads = 0, heat_steps = 0, n_eigs = 0, wave_steps = 0;
+  double             heat_dt = 0.0, wave_dt = 0.0;
   std::vector<char *> args;
   for (int i = 0; i < argc_all; ++i)
     if (i > 0 && !std::strcmp(argv_all[i], "--compare"))
@@ -87,6 +91,11 @@ int main(int argc_all, char **argv_all)
       }
     else if (i > 0 && !std::strcmp(argv_all[i], "--eigs") && i + 1 < argc_all)
       n_eigs = std::atoi(argv_all[++i]);
+    else if (i > 0 && !std::strcmp(argv_all[i], "--wave") && i + 2 < argc_all)
+      {
+        wave_steps = std::atoi(argv_all[++i]);
+        wave_dt    = std::atof(argv_all[++i]);
+      }
     else
       args.push_back(argv_all[i]);
   const int argc = (int)args.size();
@@ -201,6 +210,23 @@ int main(int argc_all, char **argv_all)
           std::printf("\n");
           for (int k = 0; k < n_eigs; ++k)
             std::printf("eigenfunction %d: L2 norm = %.12e\n", k + 1, problem.eigenfunction_norms()[k].l2[0]);
+        }
+      if (wave_steps > 0)
+        {
+          if (!compare && heat_steps <= 0)
+            {
+              if (n_loads <= 0 && n_eigs <= 0)
+                problem.assemble_global_matrix();
+              problem.assemble_and_solve_fem_problem();
+            }
+          if (heat_steps <= 0 && n_eigs <= 0)
+            problem.assemble_mass_matrix();
+          problem.solve_wave((unsigned int)wave_steps, wave_dt, 0.25, 0.5);
+          for (int k = 0; k < wave_steps; ++k)
+            std::printf("wave step %d: iterations = %d, relative residual = %.6e, kinetic = %.12e, potential = %.12e, work = %.12e\n",
+                        k + 1, problem.wave_iterations()[k], problem.wave_rel_residuals()[k], problem.wave_kinetic()[k + 1],
+                        problem.wave_potential()[k + 1], problem.wave_work()[k + 1]);
+          std::printf("SLOD wave at T = %g: L2 norm = %.12e\n", wave_steps * wave_dt, problem.norms_wave().l2[0]);
         }
     }
   catch (std::exception &exc)

@@ -137,4 +137,6 @@ hipError_t slod_mcg_solve(slod_handle *h, const double *d_values, const uint32_t
 // Y = A X on a full set of block rows, the launch of slod_lod_apply_multi (slod_lod_time.hip; used by slod_lod_eig.hip)
 void slod_lod_apply_launch(const slod_handle *h, hipStream_t st, const double *d_values, const uint32_t *d_cols, const double *d_x,
                            size_t ld_x, int n_rhs, double *d_y, size_t ld_y);
+// out = alpha a + beta b on n values, the launch of slod_lod_matrix_combine (slod_lod_time.hip; used by slod_lod_wave.hip)
+void slod_lod_combine_launch(hipStream_t st, size_t n, double alpha, const double *d_a, double beta, const double *d_b, double *d_out);
 #endif

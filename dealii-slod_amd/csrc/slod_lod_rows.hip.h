@@ -1,6 +1,7 @@
 // The product of one block row with one column of a coarse multi-vector, shared by the CG of slod_lod_solve_multi
-// (slod_lod_multi.hip) and by slod_lod_apply_multi / slod_lod_theta_steps (slod_lod_time.hip): one fma chain over the
-// slots of the row in ascending order, so both give the same bits for the same matrix and column.
+// (slod_lod_multi.hip), by slod_lod_apply_multi / slod_lod_theta_steps (slod_lod_time.hip) and by the bilinear form and
+// the right-hand side of the Newmark stepper (slod_lod_wave.hip): one fma chain over the slots of the row in ascending
+// order, so all give the same bits for the same matrix and column.
 #ifndef SLOD_LOD_ROWS_HIP_H
 #define SLOD_LOD_ROWS_HIP_H
 #include <hip/hip_runtime.h>

@@ -212,6 +212,12 @@ void slod_lod_apply_launch(const slod_handle *h, hipStream_t st, const double *d
   launch_apply(h, st, d_values, d_cols, d_x, ld_x, n_rhs, d_y, ld_y);
 }
 
+// k_lod_combine on n values for the other loops of the library (slod_lod_wave.hip)
+void slod_lod_combine_launch(hipStream_t st, size_t n, double alpha, const double *d_a, double beta, const double *d_b, double *d_out)
+{
+  hipLaunchKernelGGL(k_lod_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, alpha, d_a, beta, d_b, d_out);
+}
+
 #pragma GCC visibility push(default)
 extern "C" {
 

@@ -1,0 +1,350 @@
+// Second-order time stepping on the LOD space,  M u'' + C u' + A u = b(t)  with Rayleigh damping
+// C = damp_mass M + damp_stiff A  (the reference has no counterpart: it solves one stationary problem,
+// LOD.cc:976-1002):
+//   slod_lod_inner_multi    out[c] = x_c^T (A y_c), the energies of the stepper
+//   slod_lod_newmark_accel  M a = b^0 - A (u + damp_stiff v) - damp_mass M v, the consistent initial acceleration
+//   slod_lod_newmark_steps  n_steps of Newmark-beta in acceleration form, the state stays on the device
+// The solves are the recurrence of slod_lod_solve_multi (slod_mcg_solve, slod_lod_multi.hip) on a workspace this
+// file owns for the whole loop, every one from zero; row products are slod_lod_row_product (slod_lod_rows.hip.h).
+// Everything else is elementwise with fp contract off, so the bits of a column depend on that column alone.
+#include "slod_host.h"
+#include "slod_lod_rows.hip.h"
+
+#include <algorithm>
+#include <vector>
+
+namespace
+{
+  // the tiling and the summation order of the multi-vector CG (slod_lod_multi.hip): the order hangs on WV_ROWS
+  constexpr int WV_COLS = 64, WV_ROWS = 16, WV_BLOCK = 256, WV_MAX_BLOCKS = 256;
+
+  // one bilinear form x^T (A y) per blockIdx.z; partial: [ngroup][n_rhs]
+  struct InnerJob
+  {
+    const double *values, *x, *y;
+    size_t        ld_x, ld_y;
+    double       *partial;
+  };
+
+  // partial[g][col] = sum over the rows i of group g, ascending, of  x[i,col] * (A y)[i,col].  (A y)[i,col] is the fma
+  // chain of k_lod_apply, the product with x is rounded on its own.  Columns in chunks of 64 on lanes (blockIdx.y), a
+  // block walks the groups blockIdx.x, blockIdx.x + gridDim.x, ...
+  __global__ __launch_bounds__(WV_BLOCK) void k_lod_inner(int nrow, int s, int cap, int NP, int n_rhs, int ngroup,
+                                                         const uint32_t *__restrict__ cols, InnerJob j0, InnerJob j1)
+  {
+#pragma clang fp contract(off)
+    __shared__ double buf[WV_ROWS][WV_COLS];
+    const InnerJob    J = blockIdx.z ? j1 : j0;
+    const int         c0 = blockIdx.y * WV_COLS, nb = min(WV_COLS, n_rhs - c0);
+    for (int g = blockIdx.x; g < ngroup; g += gridDim.x)
+      {
+        for (int idx = threadIdx.x; idx < WV_ROWS * nb; idx += WV_BLOCK)
+          {
+            const int lr = idx / nb, c = idx - lr * nb, i = g * WV_ROWS + lr, col = c0 + c;
+            double    prod = 0.0;
+            if (i < nrow)
+              {
+                const double acc = slod_lod_row_product(i, s, cap, NP, J.values, cols, J.y, J.ld_y, col);
+                prod             = J.x[(size_t)i * J.ld_x + col] * acc;
+              }
+            buf[lr][c] = prod;
+          }
+        __syncthreads();
+        if ((int)threadIdx.x < nb)
+          {
+            double sum = buf[0][threadIdx.x];
+#pragma unroll
+            for (int r = 1; r < WV_ROWS; ++r)
+              sum += buf[r][threadIdx.x];
+            J.partial[(size_t)g * n_rhs + c0 + threadIdx.x] = sum;
+          }
+        __syncthreads();
+      }
+  }
+
+  // out[z][col] = scale * sum of partial_z[g][col], g ascending: one thread per (form z, column)
+  __global__ __launch_bounds__(WV_BLOCK) void k_lod_inner_sum(int n_rhs, int ngroup, int nform, const double *p0, const double *p1,
+                                                             double scale, double *out)
+  {
+#pragma clang fp contract(off)
+    const int w = blockIdx.x * WV_BLOCK + threadIdx.x;
+    if (w >= nform * n_rhs)
+      return;
+    const int     z = w / n_rhs, col = w - z * n_rhs;
+    const double *partial = z ? p1 : p0;
+    double        sum = 0.0;
+    for (int g = 0; g < ngroup; ++g)
+      sum += partial[(size_t)g * n_rhs + col];
+    out[w] = scale * sum;
+  }
+
+  // w = u + damp_stiff v, the argument of A in the right-hand side of the initial acceleration
+  __global__ __launch_bounds__(256) void k_nm_shift(int nrow, int n_rhs, double damp_stiff, const double *u, size_t ld_u,
+                                                   const double *v, size_t ld_v, double *w)
+  {
+#pragma clang fp contract(off)
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (size_t)nrow * n_rhs)
+      return;
+    const size_t i = t / n_rhs, c = t - i * n_rhs;
+    const double dv = damp_stiff * v[i * ld_v + c];
+    w[t]            = u[i * ld_u + c] + dv;
+  }
+
+  // predictor in place,  u~ = u + dt v + dt^2 (1/2 - beta) a,  v~ = v + dt (1 - gamma) a,  and  w = u~ + damp_stiff v~
+  // (cv = dt, ca = dt^2 (1/2 - beta), cg = dt (1 - gamma))
+  __global__ __launch_bounds__(256) void k_nm_predict(int nrow, int n_rhs, double cv, double ca, double cg, double damp_stiff, double *u,
+                                                     size_t ld_u, double *v, size_t ld_v, const double *a, size_t ld_a, double *w)
+  {
+#pragma clang fp contract(off)
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (size_t)nrow * n_rhs)
+      return;
+    const size_t i = t / n_rhs, c = t - i * n_rhs;
+    const double ui = u[i * ld_u + c], vi = v[i * ld_v + c], ai = a[i * ld_a + c];
+    const double tv = cv * vi, ta = ca * ai, tg = cg * ai;
+    const double up = (ui + tv) + ta, vp = vi + tg;
+    const double dv = damp_stiff * vp;
+    u[i * ld_u + c] = up;
+    v[i * ld_v + c] = vp;
+    w[t]            = up + dv;
+  }
+
+  // g = (b - A w) - damp_mass (M v) per (row, column); load NULL: b = 0; mass NULL: no mass term (damp_mass = 0)
+  __global__ __launch_bounds__(256) void k_nm_rhs(int nrow, int s, int cap, int NP, int n_rhs, const double *__restrict__ stiffness,
+                                                 const double *__restrict__ mass, const uint32_t *__restrict__ cols, double damp_mass,
+                                                 const double *load, size_t ld_load, const double *w, const double *v, size_t ld_v,
+                                                 double *g)
+  {
+#pragma clang fp contract(off)
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (size_t)nrow * n_rhs)
+      return;
+    const int    i = (int)(t / n_rhs), c = (int)(t - (size_t)i * n_rhs);
+    const double Aw = slod_lod_row_product(i, s, cap, NP, stiffness, cols, w, (size_t)n_rhs, c);
+    double       r = (load ? load[(size_t)i * ld_load + c] : 0.0) - Aw;
+    if (mass)
+      {
+        const double Mv = slod_lod_row_product(i, s, cap, NP, mass, cols, v, ld_v, c);
+        const double dm = damp_mass * Mv;
+        r               = r - dm;
+      }
+    g[t] = r;
+  }
+
+  // corrector in place,  u = u~ + beta dt^2 a,  v = v~ + gamma dt a  (cu = beta dt^2, cv = gamma dt)
+  __global__ __launch_bounds__(256) void k_nm_correct(int nrow, int n_rhs, double cu, double cv, double *u, size_t ld_u, double *v,
+                                                     size_t ld_v, const double *a, size_t ld_a)
+  {
+#pragma clang fp contract(off)
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (size_t)nrow * n_rhs)
+      return;
+    const size_t i = t / n_rhs, c = t - i * n_rhs;
+    const double ai = a[i * ld_a + c];
+    const double tu = cu * ai, tv = cv * ai;
+    u[i * ld_u + c] = u[i * ld_u + c] + tu;
+    v[i * ld_v + c] = v[i * ld_v + c] + tv;
+  }
+
+  struct WaveShape
+  {
+    int s, cap, NP, nrow, ngroup, nchunk;
+  };
+  WaveShape shape_of(const slod_handle *h, int n_rhs)
+  {
+    WaveShape w;
+    w.s      = h->cfg.spacedim;
+    w.cap    = slod_lod_row_capacity(h);
+    w.NP     = h->NP;
+    w.nrow   = w.NP * w.s;
+    w.ngroup = (w.nrow + WV_ROWS - 1) / WV_ROWS;
+    w.nchunk = (n_rhs + WV_COLS - 1) / WV_COLS;
+    return w;
+  }
+
+  // nform (1 or 2) bilinear forms in one launch of k_lod_inner, then their ordered sums: out[z * n_rhs + col]
+  void launch_inner(const WaveShape &w, hipStream_t st, const uint32_t *cols, int n_rhs, int nform, const InnerJob &j0,
+                    const InnerJob &j1, double scale, double *out)
+  {
+    const dim3 grid((unsigned)std::min(w.ngroup, WV_MAX_BLOCKS), (unsigned)w.nchunk, (unsigned)nform);
+    hipLaunchKernelGGL(k_lod_inner, grid, dim3(WV_BLOCK), 0, st, w.nrow, w.s, w.cap, w.NP, n_rhs, w.ngroup, cols, j0, j1);
+    hipLaunchKernelGGL(k_lod_inner_sum, dim3((unsigned)((nform * n_rhs + WV_BLOCK - 1) / WV_BLOCK)), dim3(WV_BLOCK), 0, st, n_rhs,
+                       w.ngroup, nform, j0.partial, j1.partial, scale, out);
+  }
+
+  bool bad_damping(double damp_mass, double damp_stiff) { return !(damp_mass >= 0.0) || !(damp_stiff >= 0.0); }
+} // namespace
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int slod_lod_inner_multi(slod_handle *h, const double *d_values, const uint32_t *d_cols, const double *d_x, size_t ld_x,
+                         const double *d_y, size_t ld_y, int n_rhs, double *out, void *hip_stream)
+{
+  if (!h)
+    return SLOD_ERR_ARGUMENT;
+  if (!d_values || !d_cols || !d_x || !d_y || !out)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_inner_multi: NULL array");
+  if (n_rhs < 1)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_inner_multi: n_rhs < 1");
+  if (ld_x < (size_t)n_rhs || ld_y < (size_t)n_rhs)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_inner_multi: leading dimension below n_rhs");
+  hipStream_t st;
+  if (const int rc = slod_enter(h, hip_stream, &st))
+    return rc;
+  const WaveShape    w = shape_of(h, n_rhs);
+  SlodDevBuf<double> work; // the partials, then the n_rhs sums
+  hipError_t         e = work.alloc((size_t)w.ngroup * n_rhs + (size_t)n_rhs);
+  if (e == hipSuccess)
+    {
+      const InnerJob job{d_values, d_x, d_y, ld_x, ld_y, work.get()};
+      double        *d_out = work.get() + (size_t)w.ngroup * n_rhs;
+      launch_inner(w, st, d_cols, n_rhs, 1, job, job, 1.0, d_out);
+      e = hipGetLastError();
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(out, d_out, (size_t)n_rhs * sizeof(double), hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess)
+        e = hipStreamSynchronize(st); // work is freed on return
+    }
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_inner_multi");
+}
+
+int slod_lod_newmark_accel(slod_handle *h, const double *d_stiffness, const double *d_mass, const uint32_t *d_cols, double damp_mass,
+                           double damp_stiff, int n_rhs, const double *d_u, size_t ld_u, const double *d_v, size_t ld_v,
+                           const double *d_load, size_t ld_load, double *d_a, size_t ld_a, double rel_tol, int max_iterations,
+                           int *iterations, double *rel_residual)
+{
+  if (!h)
+    return SLOD_ERR_ARGUMENT;
+  if (!d_stiffness || !d_mass || !d_cols || !d_u || !d_v || !d_a)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_accel: NULL matrix, d_cols or state");
+  if (bad_damping(damp_mass, damp_stiff))
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_accel: negative or NaN damping coefficient");
+  if (n_rhs < 1 || max_iterations < 0)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_accel: n_rhs < 1 or max_iterations < 0");
+  if (ld_u < (size_t)n_rhs || ld_v < (size_t)n_rhs || ld_a < (size_t)n_rhs || (d_load && ld_load < (size_t)n_rhs))
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_accel: leading dimension below n_rhs");
+  hipStream_t st;
+  if (const int rc = slod_enter(h, nullptr, &st))
+    return rc;
+  const WaveShape w = shape_of(h, n_rhs);
+  const size_t    nvec = (size_t)w.nrow * n_rhs;
+  // w = u + damp_stiff v, g, and the workspace of the solve
+  SlodDevBuf<double> work;
+  SlodDevBuf<int>    d_active;
+  hipError_t         e = work.alloc(2 * nvec + slod_mcg_work_doubles(h, n_rhs));
+  if (e == hipSuccess)
+    e = d_active.alloc((size_t)n_rhs);
+  std::vector<int> its((size_t)n_rhs, 0);
+  if (e == hipSuccess)
+    {
+      double        *arg = work.get(), *g = arg + nvec, *cg = g + nvec;
+      const unsigned nblk = (unsigned)((nvec + 255) / 256);
+      hipLaunchKernelGGL(k_nm_shift, dim3(nblk), dim3(256), 0, st, w.nrow, n_rhs, damp_stiff, d_u, ld_u, d_v, ld_v, arg);
+      hipLaunchKernelGGL(k_nm_rhs, dim3(nblk), dim3(256), 0, st, w.nrow, w.s, w.cap, w.NP, n_rhs, d_stiffness,
+                         damp_mass != 0.0 ? d_mass : nullptr, d_cols, damp_mass, d_load, ld_load, arg, d_v, ld_v, g);
+      e = hipGetLastError();
+      if (e == hipSuccess)
+        e = slod_mcg_solve(h, d_mass, d_cols, g, (size_t)n_rhs, n_rhs, d_a, ld_a, rel_tol, max_iterations, cg, d_active.get(),
+                           its.data(), rel_residual); // synchronises: work and d_active are freed on return
+    }
+  if (e != hipSuccess)
+    return slod_hip_fail(h, e, "slod_lod_newmark_accel");
+  if (iterations)
+    std::copy(its.begin(), its.end(), iterations);
+  return *std::max_element(its.begin(), its.end());
+}
+
+int slod_lod_newmark_steps(slod_handle *h, const double *d_stiffness, const double *d_mass, const uint32_t *d_cols, double dt,
+                           double beta, double gamma, double damp_mass, double damp_stiff, int n_steps, int n_rhs, double *d_u,
+                           size_t ld_u, double *d_v, size_t ld_v, double *d_a, size_t ld_a, const double *d_load, size_t ld_load,
+                           size_t load_step_stride, double rel_tol, int max_iterations, int *iterations, double *rel_residual,
+                           double *kinetic, double *potential)
+{
+  if (!h)
+    return SLOD_ERR_ARGUMENT;
+  if (!d_stiffness || !d_mass || !d_cols || !d_u || !d_v || !d_a)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_steps: NULL matrix, d_cols or state");
+  if (!(dt > 0.0) || !(beta >= 0.0 && beta <= 0.5) || !(gamma >= 0.0 && gamma <= 1.0))
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_steps: dt <= 0, beta outside [0, 1/2] or gamma outside [0, 1]");
+  if (bad_damping(damp_mass, damp_stiff))
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_steps: negative or NaN damping coefficient");
+  if (n_steps < 1 || n_rhs < 1 || max_iterations < 0)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_steps: n_steps < 1, n_rhs < 1 or max_iterations < 0");
+  if (ld_u < (size_t)n_rhs || ld_v < (size_t)n_rhs || ld_a < (size_t)n_rhs || (d_load && ld_load < (size_t)n_rhs))
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_steps: leading dimension below n_rhs");
+  if ((kinetic == nullptr) != (potential == nullptr))
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_steps: kinetic and potential come together or not at all");
+  hipStream_t st;
+  if (const int rc = slod_enter(h, nullptr, &st))
+    return rc;
+  const WaveShape w = shape_of(h, n_rhs);
+  const bool      energies = kinetic != nullptr;
+  const size_t    nmat = (size_t)w.NP * w.cap * w.s * w.s, nvec = (size_t)w.nrow * n_rhs, npart = (size_t)w.ngroup * n_rhs;
+  const size_t    nenergy = energies ? 2 * (size_t)(n_steps + 1) * n_rhs : 0;
+  // one allocation for the whole loop: S, w = u~ + damp_stiff v~, g, the workspace of the solve, and for the
+  // energies two arrays of partials and [level][kinetic, potential][column]
+  SlodDevBuf<double> work;
+  SlodDevBuf<int>    d_active;
+  hipError_t         e = work.alloc(nmat + 2 * nvec + slod_mcg_work_doubles(h, n_rhs) + (energies ? 2 * npart : 0) + nenergy);
+  if (e == hipSuccess)
+    e = d_active.alloc((size_t)n_rhs);
+  int worst = 0;
+  if (e == hipSuccess)
+    {
+      double        *S = work.get(), *arg = S + nmat, *g = arg + nvec, *cg = g + nvec;
+      double        *part = cg + slod_mcg_work_doubles(h, n_rhs), *d_energy = part + (energies ? 2 * npart : 0);
+      const unsigned nblk = (unsigned)((nvec + 255) / 256);
+      const InnerJob jk{d_mass, d_v, d_v, ld_v, ld_v, part}, jp{d_stiffness, d_u, d_u, ld_u, ld_u, part + npart};
+      const double   gdt = gamma * dt, bdt2 = beta * dt * dt;
+      slod_lod_combine_launch(st, nmat, 1.0 + gdt * damp_mass, d_mass, bdt2 + gdt * damp_stiff, d_stiffness, S);
+      if (energies)
+        launch_inner(w, st, d_cols, n_rhs, 2, jk, jp, 0.5, d_energy);
+      e = hipGetLastError();
+      std::vector<int>    its((size_t)n_rhs);
+      std::vector<double> res((size_t)n_rhs);
+      for (int k = 0; k < n_steps && e == hipSuccess; ++k)
+        {
+          const double *b1 = d_load ? d_load + (size_t)(k + 1) * load_step_stride : nullptr;
+          hipLaunchKernelGGL(k_nm_predict, dim3(nblk), dim3(256), 0, st, w.nrow, n_rhs, dt, dt * dt * (0.5 - beta), dt * (1.0 - gamma),
+                             damp_stiff, d_u, ld_u, d_v, ld_v, d_a, ld_a, arg);
+          hipLaunchKernelGGL(k_nm_rhs, dim3(nblk), dim3(256), 0, st, w.nrow, w.s, w.cap, w.NP, n_rhs, d_stiffness,
+                             damp_mass != 0.0 ? d_mass : nullptr, d_cols, damp_mass, b1, ld_load, arg, d_v, ld_v, g);
+          e = hipGetLastError();
+          if (e == hipSuccess)
+            e = slod_mcg_solve(h, S, d_cols, g, (size_t)n_rhs, n_rhs, d_a, ld_a, rel_tol, max_iterations, cg, d_active.get(),
+                               its.data(), res.data());
+          if (e != hipSuccess)
+            break;
+          hipLaunchKernelGGL(k_nm_correct, dim3(nblk), dim3(256), 0, st, w.nrow, n_rhs, bdt2, gdt, d_u, ld_u, d_v, ld_v, d_a, ld_a);
+          if (energies)
+            launch_inner(w, st, d_cols, n_rhs, 2, jk, jp, 0.5, d_energy + 2 * (size_t)(k + 1) * n_rhs);
+          e = hipGetLastError();
+          const int step_its = *std::max_element(its.begin(), its.end());
+          worst              = std::max(worst, step_its);
+          if (iterations)
+            iterations[k] = step_its;
+          if (rel_residual)
+            rel_residual[k] = *std::max_element(res.begin(), res.end());
+        }
+      std::vector<double> host(nenergy);
+      if (e == hipSuccess && energies)
+        e = hipMemcpyAsync(host.data(), d_energy, nenergy * sizeof(double), hipMemcpyDeviceToHost, st);
+      if (e == hipSuccess)
+        e = hipStreamSynchronize(st); // work and d_active are freed on return
+      if (e == hipSuccess && energies)
+        for (size_t k = 0; k <= (size_t)n_steps; ++k)
+          for (size_t c = 0; c < (size_t)n_rhs; ++c)
+            {
+              kinetic[k * n_rhs + c]   = host[2 * k * n_rhs + c];
+              potential[k * n_rhs + c] = host[(2 * k + 1) * n_rhs + c];
+            }
+    }
+  if (e != hipSuccess)
+    return slod_hip_fail(h, e, "slod_lod_newmark_steps");
+  return worst;
+}
+
+} // extern "C"
+#pragma GCC visibility pop

@@ -483,6 +483,69 @@ namespace slod
             "slod_compute_error_norms");
   }
 
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_wave(const unsigned int n_steps, const double dt, const double beta, const double gamma)
+  {
+    if (!d_lod_mass || !d_fem_rhs)
+      throw std::runtime_error("solve_wave: assemble_mass_matrix and assemble_and_solve_fem_problem come first");
+    const unsigned int n_patches = (unsigned int)patches.size();
+    const std::size_t  n_coarse = (std::size_t)n_patches * spacedim;
+    const std::size_t  NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+    const std::size_t  fine_size = (NE + 1) * (NE + 1) * spacedim;
+    const int          cap = slod_lod_row_capacity(handle);
+    check(cap, "slod_lod_row_capacity");
+    std::vector<uint32_t> rows(n_patches);
+    for (unsigned int p = 0; p < n_patches; ++p)
+      rows[p] = p;
+    // allocated on the first call, re-used by later ones
+    if (!d_lod_sym)
+      d_lod_sym = device_alloc<double>((std::size_t)n_patches * cap * spacedim * spacedim);
+    if (!d_wave_state)
+      d_wave_state = device_alloc<double>(4 * n_coarse);
+    if (!d_wave_fine)
+      d_wave_fine = device_alloc<double>(fine_size);
+    double *d_u = d_wave_state, *d_v = d_u + n_coarse, *d_a = d_v + n_coarse, *d_b = d_a + n_coarse;
+    check(slod_lod_matrix_symmetrize(handle, d_lod_values, d_lod_cols, d_lod_sym, nullptr), "slod_lod_matrix_symmetrize");
+    check(slod_lod_rhs(handle, rows.data(), n_patches, d_basis, basis_stride, d_fem_rhs, d_b, nullptr), "slod_lod_rhs");
+    if (hipMemset(d_wave_state, 0, 3 * n_coarse * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+      throw std::runtime_error("solve_wave: clearing the initial state failed");
+    std::vector<double> b(n_coarse), u(n_coarse);
+    if (hipMemcpy(b.data(), d_b, n_coarse * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      throw std::runtime_error("solve_wave: download of the load failed");
+    const int rc = slod_lod_newmark_accel(handle, d_lod_sym, d_lod_mass, d_lod_cols, 0.0, 0.0, 1, d_u, 1, d_v, 1, d_b, 1, d_a, 1,
+                                          lod_rel_tol, lod_max_iterations, nullptr, nullptr);
+    check(rc < 0 ? rc : 0, "slod_lod_newmark_accel");
+    lod_wave_iterations.assign(n_steps, 0);
+    lod_wave_residuals.assign(n_steps, 0.0);
+    lod_wave_kinetic.assign(n_steps + 1, 0.0);
+    lod_wave_potential.assign(n_steps + 1, 0.0);
+    lod_wave_work.assign(n_steps + 1, 0.0);
+    for (unsigned int k = 0; k < n_steps; ++k)
+      {
+        double    kinetic[2], potential[2];
+        const int its = slod_lod_newmark_steps(handle, d_lod_sym, d_lod_mass, d_lod_cols, dt, beta, gamma, 0.0, 0.0, 1, 1, d_u, 1,
+                                               d_v, 1, d_a, 1, d_b, 1, 0, lod_rel_tol, lod_max_iterations, &lod_wave_iterations[k],
+                                               &lod_wave_residuals[k], kinetic, potential);
+        check(its < 0 ? its : 0, "slod_lod_newmark_steps");
+        if (hipMemcpy(u.data(), d_u, n_coarse * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+          throw std::runtime_error("solve_wave: download of the state failed");
+        if (k == 0)
+          {
+            lod_wave_kinetic[0]   = kinetic[0];
+            lod_wave_potential[0] = potential[0];
+          }
+        lod_wave_kinetic[k + 1]   = kinetic[1];
+        lod_wave_potential[k + 1] = potential[1];
+        double work = 0.0;
+        for (std::size_t i = 0; i < n_coarse; ++i)
+          work += u[i] * b[i];
+        lod_wave_work[k + 1] = work;
+      }
+    check(slod_lod_reconstruct(handle, d_basis, basis_stride, d_u, d_wave_fine, nullptr), "slod_lod_reconstruct");
+    check(slod_compute_error_norms(handle, 0, d_wave_fine, nullptr, nullptr, nullptr, &wave_norms, nullptr),
+          "slod_compute_error_norms");
+  }
+
   // LOD.cc:1103-1237 with f = 1.  The reference solves with SolverDirect; the CG of the fine problem runs on the
   // coarse grid to the tolerance of the fine solve.
   template <int dim, int spacedim>

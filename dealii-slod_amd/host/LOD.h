@@ -141,6 +141,19 @@ namespace slod
     const std::vector<double>           &eigen_residuals() const { return lod_eig_residuals; }
     const std::vector<int>              &eigen_inner_iterations() const { return lod_eig_inner_iterations; } // per outer iteration
     const std::vector<slod_error_norms> &eigenfunction_norms() const { return lod_eig_norms; } // n_eig entries
+    // n_steps of Newmark-beta for M u'' + A u = C^T f_h from rest (u = v = 0, M a = C^T f_h through
+    // slod_lod_newmark_accel) with the load of solve(), constant in time and undamped, on the symmetrised A_LOD; after
+    // assemble_mass_matrix() and assemble_and_solve_fem_problem().  One slod_lod_newmark_steps call per step (the calls
+    // compose bit for bit), so that the work u^T b of every state can be formed on the host; then the final state on the
+    // fine grid and its norms.
+    void solve_wave(const unsigned int n_steps, const double dt, const double beta, const double gamma);
+    const std::vector<int>    &wave_iterations() const { return lod_wave_iterations; }   // per step
+    const std::vector<double> &wave_rel_residuals() const { return lod_wave_residuals; } // per step
+    // n_steps + 1 entries each, entry 0 the state at rest: v^T M v / 2, u^T A u / 2 and u^T b
+    const std::vector<double> &wave_kinetic() const { return lod_wave_kinetic; }
+    const std::vector<double> &wave_potential() const { return lod_wave_potential; }
+    const std::vector<double> &wave_work() const { return lod_wave_work; }
+    const slod_error_norms    &norms_wave() const { return wave_norms; }
     const slod_error_norms &error_LOD_FEMh() const { return lod_fem_error; }
     // the same norms of u_h alone (the denominators of relative errors)
     const slod_error_norms &norms_FEMh() const { return fem_norms; }
@@ -199,6 +212,11 @@ namespace slod
     std::vector<double>           lod_eigenvalues, lod_eig_residuals;
     std::vector<int>              lod_eig_inner_iterations;
     std::vector<slod_error_norms> lod_eig_norms;
+    // solve_wave: u, v, a and the load (4 coarse vectors), the final state on the fine grid
+    double             *d_wave_state = nullptr, *d_wave_fine = nullptr;
+    std::vector<int>    lod_wave_iterations;
+    std::vector<double> lod_wave_residuals, lod_wave_kinetic, lod_wave_potential, lod_wave_work;
+    slod_error_norms    wave_norms{};
     // solve_multi: fine load vectors and reconstructions, field k at + k * fine_size
     double                       *d_multi_fem_rhs = nullptr, *d_multi_fine = nullptr;
     std::vector<int>              lod_multi_iterations;

@@ -125,6 +125,12 @@ def load():
     lib.slod_lod_matrix_symmetrize.argtypes = [vp, vp, vp, vp, vp]
     lib.slod_lod_eigs.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_double, C.c_int, C.c_double,
                                   C.c_int, dp, dp, C.POINTER(C.c_int)]
+    lib.slod_lod_inner_multi.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, dp, vp]
+    lib.slod_lod_newmark_accel.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, C.c_size_t, vp, C.c_size_t,
+                                           vp, C.c_size_t, vp, C.c_size_t, C.c_double, C.c_int, C.POINTER(C.c_int), dp]
+    lib.slod_lod_newmark_steps.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                           C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t,
+                                           C.c_size_t, C.c_double, C.c_int, C.POINTER(C.c_int), dp, dp, dp]
     lib.slod_fem_rhs.argtypes = [vp, vp, vp, vp]
     lib.slod_fem_solve.argtypes = [vp, C.c_uint32, vp, vp, C.c_double, C.c_int, dp]
     lib.slod_coarse_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, vp]
@@ -436,6 +442,48 @@ class Slod:
         if rc < 0:
             self._check(rc)
         return lam[:n_block], res[:n_block], its[:rc]
+
+    # ---- second-order time stepping: M u'' + C u' + A u = b(t), C = damp_mass M + damp_stiff A ----
+    def lod_inner(self, d_values, d_cols, d_x, d_y, n_rhs=1, ld_x=None, ld_y=None, stream=None):
+        """out[c] = x_c^T (A y_c) per column, in a fixed summation order; d_x may be d_y.  Returns an array [n_rhs]."""
+        out = np.zeros(max(n_rhs, 1))
+        self._check(self.lib.slod_lod_inner_multi(self.h, d_values, d_cols, d_x, n_rhs if ld_x is None else ld_x, d_y,
+                                                  n_rhs if ld_y is None else ld_y, n_rhs, _dp(out), stream))
+        return out[:n_rhs]
+
+    def lod_newmark_accel(self, d_stiffness, d_mass, d_cols, d_u, d_v, d_a, n_rhs=1, ld_u=None, ld_v=None, ld_a=None,
+                          d_load=None, ld_load=None, damp_mass=0.0, damp_stiff=0.0, rel_tol=1e-12, max_iterations=2000):
+        """d_a = the solution of M a = b^0 - A (u + damp_stiff v) - damp_mass M v per column.  Returns
+        (iterations, rel_residual), one entry per column; max(iterations) is the C call's return value."""
+        its = np.zeros(max(n_rhs, 1), dtype=np.intc)
+        res = np.zeros(max(n_rhs, 1))
+        rc = self.lib.slod_lod_newmark_accel(self.h, d_stiffness, d_mass, d_cols, damp_mass, damp_stiff, n_rhs, d_u,
+                                             n_rhs if ld_u is None else ld_u, d_v, n_rhs if ld_v is None else ld_v, d_load,
+                                             n_rhs if ld_load is None else ld_load, d_a, n_rhs if ld_a is None else ld_a,
+                                             rel_tol, max_iterations, its.ctypes.data_as(C.POINTER(C.c_int)), _dp(res))
+        if rc < 0:
+            self._check(rc)
+        return its[:n_rhs], res[:n_rhs]
+
+    def lod_newmark_steps(self, d_stiffness, d_mass, d_cols, dt, n_steps, d_u, d_v, d_a, beta=0.25, gamma=0.5, n_rhs=1,
+                          ld_u=None, ld_v=None, ld_a=None, d_load=None, ld_load=None, load_step_stride=0, damp_mass=0.0,
+                          damp_stiff=0.0, rel_tol=1e-12, max_iterations=2000, energies=True):
+        """n_steps of Newmark-beta on d_u, d_v, d_a in place.  Returns (iterations, rel_residual, kinetic, potential):
+        the first two with one entry per step, the energies as arrays [n_steps + 1, n_rhs] (row 0: the entry state), or
+        None for both with energies=False; max(iterations) is the C call's return value."""
+        its = np.zeros(max(n_steps, 1), dtype=np.intc)
+        res = np.zeros(max(n_steps, 1))
+        shape = (max(n_steps, 0) + 1, max(n_rhs, 1))
+        kin, pot = (np.zeros(shape), np.zeros(shape)) if energies else (None, None)
+        rc = self.lib.slod_lod_newmark_steps(self.h, d_stiffness, d_mass, d_cols, dt, beta, gamma, damp_mass, damp_stiff,
+                                             n_steps, n_rhs, d_u, n_rhs if ld_u is None else ld_u, d_v,
+                                             n_rhs if ld_v is None else ld_v, d_a, n_rhs if ld_a is None else ld_a, d_load,
+                                             n_rhs if ld_load is None else ld_load, load_step_stride, rel_tol, max_iterations,
+                                             its.ctypes.data_as(C.POINTER(C.c_int)), _dp(res),
+                                             _dp(kin) if energies else None, _dp(pot) if energies else None)
+        if rc < 0:
+            self._check(rc)
+        return its[:n_steps], res[:n_steps], kin, pot
 
     def fem_rhs(self, d_f_qp, d_fine_rhs, stream=None):
         """Fine FEM load vector (d_f_qp = None: f = 1)."""

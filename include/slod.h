@@ -370,6 +370,68 @@ int slod_lod_eigs(slod_handle *h, const double *d_stiffness, const double *d_mas
                   double *residuals        /* HOST [n_block] */,
                   int    *inner_iterations /* HOST [max_outer], may be NULL */);
 
+/* ---- second-order time stepping on the LOD space:  M u'' + C u' + A u = b(t)  -------------
+ * Wave propagation through the medium, with Rayleigh damping C = damp_mass M + damp_stiff A (the reference has no
+ * counterpart).  Matrices are full sets of block rows (rows 0 .. num_patches-1) in the layout of slod_lod_matrix, coarse
+ * multi-vectors those of the _multi calls.  d_stiffness should be the output of slod_lod_matrix_symmetrize (not
+ * checked, as in slod_lod_eigs): the energy identities of the scheme hold for a symmetric A.  Argument checks come
+ * before any device work; SLOD_ERR_DEVICE without a usable GPU. */
+/* out[c] = sum_i x[i,c] (A y)[i,c], the bilinear form of a block-row matrix per column; d_x == d_y gives the quadratic
+ * form (u^T A u, v^T M v).  (A y)[i,c] is the fma chain of slod_lod_apply_multi (the same bits); the product with
+ * x[i,c] is rounded on its own; the sum has the fixed order of slod_lod_solve_multi: the 16 rows of a group ascending
+ * into one partial per (group, column), then the partials in ascending group order (a second, per-column launch).  No
+ * atomics: the bits of out[c] depend only on the matrix and on column c of x and y, not on n_rhs, ld, the column's
+ * position or the run.  SLOD_ERR_ARGUMENT: NULL handle or array, n_rhs < 1, ld < n_rhs.  Synchronises hip_stream. */
+int slod_lod_inner_multi(slod_handle *h, const double *d_values, const uint32_t *d_cols, const double *d_x, size_t ld_x,
+                         const double *d_y, size_t ld_y, int n_rhs, double *out /* HOST [n_rhs] */, void *hip_stream);
+/* The acceleration consistent with a state (u, v) and the load b^0, per column:
+ *   M a = b^0 - A (u + damp_stiff v) - damp_mass M v
+ * by the recurrence of slod_lod_solve_multi from a = 0 (per-column freeze, rel_tol relative to the norm of the
+ * right-hand side; a zero column gives a = 0 and 0 iterations).  d_load = NULL: b^0 = 0 (ld_load ignored).  u and v are
+ * read only.  Returns the largest per-column iteration count or a negative slod_status; reaching max_iterations is not
+ * an error.  SLOD_ERR_ARGUMENT: NULL handle, matrix, d_cols, u, v or a; a negative or NaN damping coefficient;
+ * n_rhs < 1; a leading dimension below n_rhs (ld_load only with a load); max_iterations < 0.  Runs on the handle's
+ * stream; synchronises. */
+int slod_lod_newmark_accel(slod_handle *h, const double *d_stiffness, const double *d_mass, const uint32_t *d_cols,
+                           double damp_mass, double damp_stiff, int n_rhs, const double *d_u, size_t ld_u,
+                           const double *d_v, size_t ld_v, const double *d_load /* b^0, NULL = 0 */, size_t ld_load,
+                           double *d_a, size_t ld_a, double rel_tol, int max_iterations,
+                           int *iterations /* HOST [n_rhs], may be NULL */,
+                           double *rel_residual /* HOST [n_rhs], may be NULL */);
+/* n_steps of Newmark-beta in acceleration form on n_rhs independent columns, the whole loop on the device.  On entry
+ * u, v, a hold the state at level k0 (a from slod_lod_newmark_accel, or from the previous call), on return the state
+ * n_steps later.  For k = 0 .. n_steps-1:
+ *   S  = (1 + gamma dt damp_mass) M + (beta dt^2 + gamma dt damp_stiff) A     (once per call, workspace of the call)
+ *   u~ = u + dt v + dt^2 (1/2 - beta) a ;  v~ = v + dt (1 - gamma) a           (predictor, in place)
+ *   g  = b^{k+1} - A (u~ + damp_stiff v~) - damp_mass M v~
+ *   S a+ = g                                 (the recurrence of slod_lod_solve_multi from 0, rel_tol relative to ||g_c||)
+ *   u+ = u~ + beta dt^2 a+ ;  v+ = v~ + gamma dt a+
+ * gamma = 1/2, beta = 1/4: the trapezoidal rule (unconditionally stable, conserves v^T M v / 2 + u^T A u / 2 without
+ * load and damping).  gamma = 1/2, beta = 0: central differences (S is a multiple of M when damp_stiff = 0; stable for
+ * omega_max dt < 2).  For 0 < beta < 1/4 the limit is omega_max dt < 2 / sqrt(1 - 4 beta).  Every solve starts from
+ * zero (no warm start from a): a column's bits depend only on the matrices, the parameters and that column's state and
+ * loads, and one call with n_steps = 2 equals two calls with n_steps = 1 carrying u, v, a over.  Products and sums of
+ * the elementwise work are rounded separately (no fma).
+ * d_load: b^k at d_load + k * load_step_stride (doubles), k = 0 .. n_steps, ld_load >= n_rhs, as in
+ * slod_lod_theta_steps; step k reads b^{k+1} only; load_step_stride = 0: one load, constant in time; NULL: zero load.
+ * HOST iterations[n_steps] / rel_residual[n_steps]: the largest per-column iteration count and the worst column's
+ * ||r|| / ||g|| of each step.  HOST kinetic / potential [(n_steps + 1) * n_rhs]: entry [k * n_rhs + c] is
+ * v_c^T M v_c / 2 and u_c^T A u_c / 2 (the sums of slod_lod_inner_multi, halved), k = 0 the entry state, k = 1 .. n_steps
+ * the state after each step; kept on the device and copied once at the end; both NULL: not computed.
+ * Returns the largest entry of iterations or a negative slod_status; reaching max_iterations is not an error.  Device
+ * workspace (one matrix, 6 vectors of n_rhs columns, the energies) allocated once per call.
+ * SLOD_ERR_ARGUMENT: NULL handle, matrix, d_cols, u, v or a; dt <= 0 or NaN; beta outside [0, 1/2] or gamma outside
+ * [0, 1]; a negative or NaN damping coefficient; n_steps < 1; n_rhs < 1; a leading dimension below n_rhs (ld_load only
+ * with a load); max_iterations < 0; exactly one of kinetic / potential given.  Runs on the handle's stream; synchronises. */
+int slod_lod_newmark_steps(slod_handle *h, const double *d_stiffness, const double *d_mass, const uint32_t *d_cols, double dt,
+                           double beta, double gamma, double damp_mass, double damp_stiff, int n_steps, int n_rhs,
+                           double *d_u, size_t ld_u, double *d_v, size_t ld_v, double *d_a, size_t ld_a,
+                           const double *d_load, size_t ld_load, size_t load_step_stride, double rel_tol, int max_iterations,
+                           int *iterations      /* HOST [n_steps], may be NULL */,
+                           double *rel_residual /* HOST [n_steps], may be NULL */,
+                           double *kinetic      /* HOST [(n_steps + 1) * n_rhs], may be NULL */,
+                           double *potential    /* HOST [(n_steps + 1) * n_rhs], may be NULL */);
+
 /* ---- fine FEM reference problem (assemble_and_solve_fem_problem, LOD.cc:1004-1094) ----
  * What the reference compares the LOD solution with (compare_lod_with_fem, LOD.cc:1240-1378).
  * fem_rhs of assemble_stiffness (Diffusion.h:149-193) on the global fine grid, [(NE+1)^2][s],
