@@ -47,6 +47,37 @@ namespace
     e.my         = y1 - e.y0 + 1;
     return e;
   }
+  // Slot j of the block row of a patch p is the candidate neighbour q whose centre cell lies at offset
+  // (j % span, j / span) - span / 2 from p's, span = 4 l + 3 (patches further apart share no node); a row has span^2
+  // slots.  The overlap of the two closed patches is w x hgt global fine nodes from (xa, ya): a pair that shares only a
+  // line of nodes has w or hgt = 1, a pair that shares none has one <= 0, a centre outside the domain gives w = hgt = 0.
+  __host__ __device__ inline int grid_row_capacity(const SlodGrid &G) { return (4 * G.oversampling + 3) * (4 * G.oversampling + 3); }
+  struct PairGeom
+  {
+    uint32_t q;
+    Extent   qe;
+    int      xa, ya, w, hgt;
+    // the column the slot holds in the pattern of A_LOD and M_LOD: q when the patches share a node
+    __host__ __device__ uint32_t col() const { return w > 0 && hgt > 0 ? q : 0xffffffffu; }
+  };
+  __host__ __device__ inline PairGeom grid_pair(const SlodGrid &G, int pcx, int pcy, const Extent &pe, int j)
+  {
+    PairGeom  g{};
+    const int n = G.n_sub, span = 4 * G.oversampling + 3;
+    const int qcx = pcx + j % span - (span / 2), qcy = pcy + j / span - (span / 2);
+    if (qcx < 0 || qcx >= G.N || qcy < 0 || qcy >= G.N)
+      return g;
+    g.q  = grid_pid(G, qcx, qcy);
+    g.qe = grid_extent(G, qcx, qcy);
+    // overlap in global fine-node coordinates (inclusive)
+    const Extent &qe = g.qe;
+    const int     xb = min(pe.x0 + pe.mx, qe.x0 + qe.mx) * n, yb = min(pe.y0 + pe.my, qe.y0 + qe.my) * n;
+    g.xa  = max(pe.x0, qe.x0) * n;
+    g.ya  = max(pe.y0, qe.y0) * n;
+    g.w   = xb - g.xa + 1;
+    g.hgt = yb - g.ya + 1;
+    return g;
+  }
   // descriptor -> public patch layout (slod_plan_patch_layout, slod_device_patch_layout), everything from the
   // descriptor the device built -- except the position of a full patch under the reuse quirk Q1: there
   // k_make_desc stores the first full patch's coefficient origin in (ox, oy), and the patch's own origin is

@@ -8,6 +8,7 @@
 #include "slod_device.h"
 
 #include <algorithm>
+#include <initializer_list>
 #include <string>
 #include <utility>
 #include <vector>
@@ -129,14 +130,81 @@ struct SlodPlanBuild
 hipError_t slod_build_descriptors(const slod_handle *h, const uint32_t *gids, size_t n, const uint64_t *offsets, size_t stride,
                                   int n_cu, bool balance, SlodPatchDesc *d_desc, SlodPatchDesc *d_desc_bal, SlodPlanSummary *sum,
                                   std::vector<char> *prob_used);
-// slod_lod_solve_multi on a workspace the caller owns (slod_lod_multi.hip; used by the time loop of slod_lod_time.hip)
-size_t     slod_mcg_work_doubles(const slod_handle *h, int n_rhs);
-hipError_t slod_mcg_solve(slod_handle *h, const double *d_values, const uint32_t *d_cols, const double *d_rhs, size_t ld_rhs,
-                          int n_rhs, double *d_u, size_t ld_u, double rel_tol, int max_iterations, double *work, int *d_active,
-                          int *its, double *rel_residual);
-// Y = A X on a full set of block rows, the launch of slod_lod_apply_multi (slod_lod_time.hip; used by slod_lod_eig.hip)
+// ---- shared by the units of the LOD space (slod_lod_multi/time/wave/eig.hip)
+// Y = A X on a full set of block rows, the launch of slod_lod_apply_multi (slod_lod_time.hip)
 void slod_lod_apply_launch(const slod_handle *h, hipStream_t st, const double *d_values, const uint32_t *d_cols, const double *d_x,
                            size_t ld_x, int n_rhs, double *d_y, size_t ld_y);
-// out = alpha a + beta b on n values, the launch of slod_lod_matrix_combine (slod_lod_time.hip; used by slod_lod_wave.hip)
+// out = alpha a + beta b on n values, the launch of slod_lod_matrix_combine (slod_lod_time.hip)
 void slod_lod_combine_launch(hipStream_t st, size_t n, double alpha, const double *d_a, double beta, const double *d_b, double *d_out);
+// SLOD_ERR_ARGUMENT, "<who>: leading dimension below <what>", when one of lds is below n; else SLOD_OK
+inline int slod_check_ld(const slod_handle *h, const char *who, const char *what, int n, std::initializer_list<size_t> lds)
+{
+  for (const size_t ld : lds)
+    if (ld < (size_t)n)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": leading dimension below " + what);
+  return SLOD_OK;
+}
+// Hands out consecutive pieces of one array of doubles.  Without a base it only counts, so a function that names its
+// pieces by take() gives the size of the array on a first run and the pointers on a second: the two cannot disagree.
+struct SlodCarver
+{
+  double *base = nullptr;
+  size_t  used = 0;
+  double *take(size_t count) { used += count; return base ? base + (used - count) : nullptr; }
+  template <typename T> // one object of T in a slot of its own, whole doubles
+  T *take_as() { return (T *)take((sizeof(T) + sizeof(double) - 1) / sizeof(double)); }
+};
+// The device workspace of a call that runs the solve of slod_lod_solve_multi, once or in a loop: one array of doubles and
+// the active flags of the columns, one hipMalloc each per call, freed when the owner leaves scope (the stream must have
+// been synchronised by then; solve() does).
+struct SlodLodWork
+{
+  std::vector<int>    its;                 // HOST [n_rhs], of the last solve
+  std::vector<double> res;                 // HOST [n_rhs], relative residuals of the last solve
+  int                 last = 0, worst = 0; // the largest its[] of the last solve, of all solves
+  // carve(SlodCarver &) names every piece of the array, take_solve() among them; it runs twice, first to count
+  template <typename Carve>
+  hipError_t alloc(int n_rhs, Carve &&carve)
+  {
+    its.assign((size_t)n_rhs, 0);
+    res.assign((size_t)n_rhs, 0.0);
+    SlodCarver count, hand;
+    carve(count);
+    hipError_t e = work.alloc(count.used);
+    if (e == hipSuccess)
+      e = active.alloc((size_t)n_rhs);
+    if (e != hipSuccess)
+      return e;
+    hand.base = work.get();
+    carve(hand);
+    return hipSuccess;
+  }
+  // the pieces of the solve, placed where the caller's carve calls it (slod_lod_multi.hip)
+  void take_solve(SlodCarver &c, const slod_handle *h);
+  // A U = RHS for the n_rhs columns, every one from zero (slod_lod_multi.hip).  Arguments are checked by the caller; the
+  // handle's device is current.  Synchronises h->stream.
+  hipError_t solve(slod_handle *h, const double *d_values, const uint32_t *d_cols, const double *d_rhs, size_t ld_rhs, double *d_u,
+                   size_t ld_u, double rel_tol, int max_iterations);
+  // what a time loop reports of step k, HOST arrays, either may be NULL: the maxima over the columns of the last solve
+  void record(int k, int *iterations, double *rel_residual) const
+  {
+    if (iterations)
+      iterations[k] = last;
+    if (rel_residual)
+      rel_residual[k] = *std::max_element(res.begin(), res.end());
+  }
+  // what a single solve reports per column, HOST [n_rhs], either may be NULL
+  void report(int *iterations, double *rel_residual) const
+  {
+    if (iterations)
+      std::copy(its.begin(), its.end(), iterations);
+    if (rel_residual)
+      std::copy(res.begin(), res.end(), rel_residual);
+  }
+
+private:
+  SlodDevBuf<double> work;
+  SlodDevBuf<int>    active;
+  double            *cg = nullptr; // the pieces of the solve
+};
 #endif

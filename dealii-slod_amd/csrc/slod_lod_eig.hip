@@ -9,8 +9,8 @@
 //   k_eig_ritz                   Ga Q = Gm Q Theta, Q^T Gm Q = I in one workgroup out of LDS
 //   k_eig_rotate                 X = Z Q; AX = W Q and MX = V Q stay in registers for the residual partials
 // Every reduction has a fixed order (no atomics): the same inputs give the same bits.
-#include "slod_host.h"
 #include "slod_grid.hip.h"
+#include "slod_lod_tile.hip.h"
 
 #include <algorithm>
 #include <cmath>
@@ -21,7 +21,7 @@
 
 namespace
 {
-  constexpr int    EG_COLS = 64; // block columns: the column chunk of k_lod_apply / k_mcg_spmv, and what fits the Ritz LDS
+  constexpr int    EG_COLS = LOD_COLS; // block columns: one column chunk (slod_lod_tile.hip.h), and what fits the Ritz LDS
   constexpr double EG_EPS  = 2.220446049250313e-16;
 
   // out[p,j][d][e] = (A[p,j][d][e] + A[q,j'][e][d]) / 2, q = cols[p,j], j' the slot of p in row q (0 when there is none).
@@ -373,7 +373,7 @@ namespace
   // (AX - theta MX)^2 and MX^2, summed over the rows of the slab in ascending order into one partial per
   // (slab, column); k_eig_residual adds the slabs in ascending order.  Nothing is written after a failed Ritz step.
   // ---------------------------------------------------------------------------------
-  constexpr int RT_ROWS = 16, RT_BLOCK = 256, RT_MAX_BLOCKS = 1024;
+  constexpr int RT_ROWS = LOD_ROWS, RT_BLOCK = LOD_BLOCK, RT_MAX_BLOCKS = 1024; // a slab is a reduction group
 
   __global__ __launch_bounds__(RT_BLOCK) void k_eig_rotate(int nrow, int m, int nslab, const double *__restrict__ Z,
                                                           const double *__restrict__ W, const double *__restrict__ V,
@@ -424,15 +424,8 @@ namespace
         __syncthreads();
         if ((int)threadIdx.x < m)
           {
-            double rr = b_rr[0][threadIdx.x], mm = b_mm[0][threadIdx.x];
-#pragma unroll
-            for (int r = 1; r < RT_ROWS; ++r)
-              {
-                rr += b_rr[r][threadIdx.x];
-                mm += b_mm[r][threadIdx.x];
-              }
-            p_rr[(size_t)g * m + threadIdx.x] = rr;
-            p_mm[(size_t)g * m + threadIdx.x] = mm;
+            p_rr[(size_t)g * m + threadIdx.x] = slod_lod_group_sum(b_rr, threadIdx.x);
+            p_mm[(size_t)g * m + threadIdx.x] = slod_lod_group_sum(b_mm, threadIdx.x);
           }
         __syncthreads();
       }
@@ -445,14 +438,10 @@ namespace
     const int j = threadIdx.x;
     if (j >= m || *status != 0)
       return;
-    double rr = 0.0, mm = 0.0;
-    for (int g = 0; g < nslab; ++g)
-      {
-        rr += p_rr[(size_t)g * m + j];
-        mm += p_mm[(size_t)g * m + j];
-      }
-    res[j] = sqrt(rr) / (fabs(theta[j]) * sqrt(mm));
+    const double rr = slod_lod_ordered_sum(p_rr, nslab, m, j), mm = slod_lod_ordered_sum(p_mm, nslab, m, j);
+    res[j]          = sqrt(rr) / (fabs(theta[j]) * sqrt(mm));
   }
+
 } // namespace
 
 #pragma GCC visibility push(default)
@@ -467,9 +456,8 @@ int slod_lod_matrix_symmetrize(slod_handle *h, const double *d_values, const uin
   hipStream_t st;
   if (const int rc = slod_enter(h, hip_stream, &st))
     return rc;
-  const int    s = h->cfg.spacedim, cap = slod_lod_row_capacity(h);
-  const size_t n = (size_t)h->NP * cap * s * s;
-  hipLaunchKernelGGL(k_lod_symmetrize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, h->NP, s, cap, d_values, d_cols, d_out);
+  const LodShape w = lod_shape(h, 1);
+  hipLaunchKernelGGL(k_lod_symmetrize, lod_flat_grid((size_t)w.NP * w.cap * w.s * w.s), dim3(256), 0, st, w.NP, w.s, w.cap, d_values, d_cols, d_out);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_matrix_symmetrize");
 }
@@ -485,8 +473,8 @@ int slod_lod_eigs(slod_handle *h, const double *d_stiffness, const double *d_mas
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_eigs: n_eig < 1 or n_block < n_eig");
   if (n_block > EG_COLS || n_block > nrow)
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_eigs: n_block above 64 or above the number of rows");
-  if (ld_x < (size_t)n_block)
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_eigs: leading dimension below n_block");
+  if (const int rc = slod_check_ld(h, "slod_lod_eigs", "n_block", n_block, {ld_x}))
+    return rc;
   if (start != 0 && start != 1)
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_eigs: start is neither 0 nor 1");
   if (!(tol > 0.0) || !(inner_rel_tol > 0.0))
@@ -496,22 +484,23 @@ int slod_lod_eigs(slod_handle *h, const double *d_stiffness, const double *d_mas
   hipStream_t st;
   if (const int rc = slod_enter(h, nullptr, &st))
     return rc;
-  const int    n_gslab = (nrow + GR_ROWS - 1) / GR_ROWS, n_rslab = (nrow + RT_ROWS - 1) / RT_ROWS;
-  const size_t nvec = (size_t)nrow * m, mm = (size_t)m * m;
-  // one allocation for the whole loop: Y, Z, W, V, the slab partials, Ga | Gm, Q, theta | residuals | status, the CG
-  const size_t n_work = 4 * nvec + 2 * mm * n_gslab + 3 * mm + 2 * (size_t)m * n_rslab + 2 * (size_t)m + 1;
-  SlodDevBuf<double> work;
-  SlodDevBuf<int>    d_active;
-  hipError_t         e = work.alloc(n_work + slod_mcg_work_doubles(h, m));
-  if (e == hipSuccess)
-    e = d_active.alloc((size_t)m);
+  const LodShape w = lod_shape(h, m); // its groups are the slabs of k_eig_rotate
+  const int      n_gslab = (nrow + GR_ROWS - 1) / GR_ROWS, n_rslab = w.ngroup;
+  const size_t   nvec = (size_t)nrow * m, mm = (size_t)m * m;
+  // one allocation for the whole loop: Y, Z, W, V, the slab partials, Ga | Gm, Q, theta | residuals | status (consecutive: the
+  // host reads them in one copy), the workspace of the solve
+  double     *Y, *Z, *W, *V, *partial, *G, *Q, *p_rr, *p_mm, *theta, *res;
+  int        *status;
+  SlodLodWork work;
+  hipError_t  e = work.alloc(m, [&](SlodCarver &c) {
+    Y = c.take(nvec), Z = c.take(nvec), W = c.take(nvec), V = c.take(nvec);
+    partial = c.take(2 * mm * n_gslab), G = c.take(2 * mm), Q = c.take(mm);
+    p_rr = c.take((size_t)m * n_rslab), p_mm = c.take((size_t)m * n_rslab);
+    theta = c.take(m), res = c.take(m), status = c.take_as<int>(), work.take_solve(c, h);
+  });
   int outer = 0, failed_column = 0;
   if (e == hipSuccess)
     {
-      double *Y = work.get(), *Z = Y + nvec, *W = Z + nvec, *V = W + nvec, *partial = V + nvec, *G = partial + 2 * mm * n_gslab;
-      double *Q = G + 2 * mm, *p_rr = Q + mm, *p_mm = p_rr + (size_t)m * n_rslab, *scal = p_mm + (size_t)m * n_rslab;
-      double *theta = scal, *res = scal + m, *cg = scal + 2 * m + 1;
-      int    *status = (int *)(scal + 2 * m);
       if (start == 0)
         {
           // the pairs (a, b) of {1..N}^2 in ascending a^2 + b^2, ties by ascending a
@@ -534,16 +523,14 @@ int slod_lod_eigs(slod_handle *h, const double *d_stiffness, const double *d_mas
                              d_x, ld_x);
           e = hipGetLastError();
         }
-      std::vector<int>    its((size_t)m);
-      std::vector<double> host(2 * (size_t)m + 1);
+      std::vector<double> host(2 * (size_t)m + 1); // the last slot holds the int
       bool                done = false;
       while (e == hipSuccess && !done && outer < max_outer)
         {
           slod_lod_apply_launch(h, st, d_mass, d_cols, d_x, ld_x, m, Y, (size_t)m);
           e = hipGetLastError();
           if (e == hipSuccess)
-            e = slod_mcg_solve(h, d_stiffness, d_cols, Y, (size_t)m, m, Z, (size_t)m, inner_rel_tol, inner_max_iterations, cg,
-                               d_active.get(), its.data(), nullptr);
+            e = work.solve(h, d_stiffness, d_cols, Y, (size_t)m, Z, (size_t)m, inner_rel_tol, inner_max_iterations);
           if (e != hipSuccess)
             break;
           slod_lod_apply_launch(h, st, d_stiffness, d_cols, Z, (size_t)m, m, W, (size_t)m);
@@ -552,18 +539,18 @@ int slod_lod_eigs(slod_handle *h, const double *d_stiffness, const double *d_mas
                              V, partial);
           hipLaunchKernelGGL(k_eig_gram_sum, dim3((unsigned)((2 * mm + 255) / 256)), dim3(256), 0, st, m, n_gslab, partial, G);
           hipLaunchKernelGGL(k_eig_ritz, dim3(1), dim3(RZ_BLOCK), 0, st, m, G, Q, theta, status);
-          hipLaunchKernelGGL(k_eig_rotate, dim3((unsigned)std::min(n_rslab, RT_MAX_BLOCKS)), dim3(RT_BLOCK), 0, st, nrow, m, n_rslab, Z,
-                             W, V, Q, theta, status, d_x, ld_x, p_rr, p_mm);
+          hipLaunchKernelGGL(k_eig_rotate, lod_grid(w, RT_MAX_BLOCKS), dim3(RT_BLOCK), 0, st, nrow, m, n_rslab, Z, W, V, Q, theta, status,
+                             d_x, ld_x, p_rr, p_mm);
           hipLaunchKernelGGL(k_eig_residual, dim3(1), dim3(EG_COLS), 0, st, m, n_rslab, p_rr, p_mm, theta, status, res);
           e = hipGetLastError();
           if (e == hipSuccess)
-            e = hipMemcpyAsync(host.data(), scal, host.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+            e = hipMemcpyAsync(host.data(), theta, host.size() * sizeof(double), hipMemcpyDeviceToHost, st);
           if (e == hipSuccess)
             e = hipStreamSynchronize(st);
           if (e != hipSuccess)
             break;
           if (inner_iterations)
-            inner_iterations[outer] = *std::max_element(its.begin(), its.end());
+            inner_iterations[outer] = work.last;
           ++outer;
           std::memcpy(&failed_column, &host[2 * (size_t)m], sizeof(int));
           if (failed_column != 0)
@@ -575,7 +562,7 @@ int slod_lod_eigs(slod_handle *h, const double *d_stiffness, const double *d_mas
             done = done && residuals[j] <= tol;
         }
     }
-  // (every completed pass of the loop ends on a synchronised stream: work and d_active are idle when they are freed)
+  // (every completed pass of the loop ends on a synchronised stream: the workspace is idle when it is freed)
   if (e != hipSuccess)
     return slod_hip_fail(h, e, "slod_lod_eigs");
   if (failed_column != 0)

@@ -2,24 +2,16 @@
 // Every column runs the Jacobi-preconditioned CG recurrence of slod_lod_solve with scalars of its own; the
 // columns share the reads of the block rows and the launches, nothing else.
 //
-// Layout of the work: coarse multi-vectors are interleaved ([row][column]), so columns sit on lanes.  The
-// columns are cut into chunks of MCG_COLS = 64 (blockIdx.y); a block takes MCG_ROWS = 16 consecutive rows of
-// one chunk and spreads the (row, column) items over its 256 threads, row-major: with 64 columns a wave is one
-// row (its values[] and cols[] loads are wave-uniform, its reads of P one contiguous 512 bytes per slot), with
-// fewer columns a wave holds 64 / nb rows.
-//
-// Dot products have a fixed order that does not depend on n_rhs, on the column's position or on ld: the
-// products of one column over the MCG_ROWS rows of a group are summed in ascending row order into one partial
-// per (group, column), and whoever needs the scalar sums the partials in ascending group order (every block
-// for itself: no atomics, no fourth launch).  An iteration is three launches for all columns:
+// Tiling and summation order are those of slod_lod_tile.hip.h: a dot product is one partial per (group, column),
+// and whoever needs the scalar sums the partials in ascending group order (every block for itself: no atomics, no
+// fourth launch).  An iteration is three launches for all columns:
 //   k_mcg_spmv       Y = A P, partials of p.Ap
 //   k_mcg_update_xr  alpha = r.z / p.Ap;  x += alpha p, r -= alpha Ap, z = D^-1 r; partials of r.z and r.r
 //   k_mcg_update_p   beta = r.z_new / r.z;  p = z + beta p
 // The r.z partials are double-buffered by iteration parity, which replaces k_cg_rotate.  Every 8 iterations
 // k_mcg_check sums the r.r partials and freezes the columns that have converged (their u is not written
 // again); the host reads the flags back.
-#include "slod_host.h"
-#include "slod_lod_rows.hip.h"
+#include "slod_lod_tile.hip.h"
 
 #include <algorithm>
 #include <cmath>
@@ -27,10 +19,7 @@
 
 namespace
 {
-  constexpr int MCG_COLS  = 64;  // columns per chunk (one wave wide)
-  constexpr int MCG_ROWS  = 16;  // rows per reduction group: fixed, the summation order hangs on it
-  constexpr int MCG_BLOCK = 256;
-  constexpr int MCG_MAX_BLOCKS = 256; // blocks per chunk; a block walks several groups beyond that
+  constexpr int SOLVE_MAX_BLOCKS = 256; // blocks per chunk
 
   struct McgVectors
   {
@@ -41,27 +30,9 @@ namespace
     int    *active;         // [n_rhs]
   };
 
-  // buf[row][c] over the rows of the group, ascending, for column c = threadIdx.x < nb
-  __device__ __forceinline__ double group_sum(const double (*buf)[MCG_COLS], int c)
-  {
-    double s = buf[0][c];
-#pragma unroll
-    for (int i = 1; i < MCG_ROWS; ++i)
-      s += buf[i][c];
-    return s;
-  }
-  // sum of partial[g][col], g ascending
-  __device__ __forceinline__ double ordered_sum(const double *partial, int ngroup, int n_rhs, int col)
-  {
-    double s = 0.0;
-    for (int g = 0; g < ngroup; ++g)
-      s += partial[(size_t)g * n_rhs + col];
-    return s;
-  }
-
   __global__ void k_mcg_diag(int nrow, int s, int cap, const double *values, const uint32_t *cols, double *dinv)
   {
-    const int i = blockIdx.x * MCG_BLOCK + threadIdx.x;
+    const int i = blockIdx.x * LOD_BLOCK + threadIdx.x;
     if (i >= nrow)
       return;
     const int p = i / s, d = i - p * s;
@@ -73,16 +44,16 @@ namespace
   }
 
   // x = 0, r = rhs, z = D^-1 r, p = z; partials of r.z (parity 0) and r.r
-  __global__ __launch_bounds__(MCG_BLOCK) void k_mcg_init(int nrow, int n_rhs, int ngroup, const double *rhs, size_t ld_rhs,
+  __global__ __launch_bounds__(LOD_BLOCK) void k_mcg_init(int nrow, int n_rhs, int ngroup, const double *rhs, size_t ld_rhs,
                                                          double *x, size_t ld_x, McgVectors V)
   {
-    __shared__ double b_rz[MCG_ROWS][MCG_COLS], b_rr[MCG_ROWS][MCG_COLS];
-    const int c0 = blockIdx.y * MCG_COLS, nb = min(MCG_COLS, n_rhs - c0);
+    __shared__ double b_rz[LOD_ROWS][LOD_COLS], b_rr[LOD_ROWS][LOD_COLS];
+    const int c0 = blockIdx.y * LOD_COLS, nb = min(LOD_COLS, n_rhs - c0);
     for (int g = blockIdx.x; g < ngroup; g += gridDim.x)
       {
-        for (int idx = threadIdx.x; idx < MCG_ROWS * nb; idx += MCG_BLOCK)
+        for (int idx = threadIdx.x; idx < LOD_ROWS * nb; idx += LOD_BLOCK)
           {
-            const int lr = idx / nb, c = idx - lr * nb, i = g * MCG_ROWS + lr, col = c0 + c;
+            const int lr = idx / nb, c = idx - lr * nb, i = g * LOD_ROWS + lr, col = c0 + c;
             double    a = 0.0, b = 0.0;
             if (i < nrow)
               {
@@ -102,25 +73,25 @@ namespace
         if ((int)threadIdx.x < nb)
           {
             const size_t at = (size_t)g * n_rhs + c0 + threadIdx.x;
-            V.rz[0][at]     = group_sum(b_rz, threadIdx.x);
-            V.rr[at]        = group_sum(b_rr, threadIdx.x);
+            V.rz[0][at]     = slod_lod_group_sum(b_rz, threadIdx.x);
+            V.rr[at]        = slod_lod_group_sum(b_rr, threadIdx.x);
           }
         __syncthreads();
       }
   }
 
   // Y = A P on the block rows for the active columns; partials of p.Ap
-  __global__ __launch_bounds__(MCG_BLOCK) void k_mcg_spmv(int nrow, int s, int cap, int NP, int n_rhs, int ngroup,
+  __global__ __launch_bounds__(LOD_BLOCK) void k_mcg_spmv(int nrow, int s, int cap, int NP, int n_rhs, int ngroup,
                                                          const double *__restrict__ values, const uint32_t *__restrict__ cols,
                                                          McgVectors V)
   {
-    __shared__ double b_pAp[MCG_ROWS][MCG_COLS];
-    const int c0 = blockIdx.y * MCG_COLS, nb = min(MCG_COLS, n_rhs - c0);
+    __shared__ double b_pAp[LOD_ROWS][LOD_COLS];
+    const int c0 = blockIdx.y * LOD_COLS, nb = min(LOD_COLS, n_rhs - c0);
     for (int g = blockIdx.x; g < ngroup; g += gridDim.x)
       {
-        for (int idx = threadIdx.x; idx < MCG_ROWS * nb; idx += MCG_BLOCK)
+        for (int idx = threadIdx.x; idx < LOD_ROWS * nb; idx += LOD_BLOCK)
           {
-            const int lr = idx / nb, c = idx - lr * nb, i = g * MCG_ROWS + lr, col = c0 + c;
+            const int lr = idx / nb, c = idx - lr * nb, i = g * LOD_ROWS + lr, col = c0 + c;
             double    prod = 0.0;
             if (i < nrow && V.active[col])
               {
@@ -133,28 +104,28 @@ namespace
           }
         __syncthreads();
         if ((int)threadIdx.x < nb && V.active[c0 + threadIdx.x])
-          V.pAp[(size_t)g * n_rhs + c0 + threadIdx.x] = group_sum(b_pAp, threadIdx.x);
+          V.pAp[(size_t)g * n_rhs + c0 + threadIdx.x] = slod_lod_group_sum(b_pAp, threadIdx.x);
         __syncthreads();
       }
   }
 
   // alpha = r.z / p.Ap from the partials; x += alpha p, r -= alpha Ap, z = D^-1 r; partials of the new r.z
   // (parity par ^ 1) and of r.r
-  __global__ __launch_bounds__(MCG_BLOCK) void k_mcg_update_xr(int nrow, int n_rhs, int ngroup, int par, double *x, size_t ld_x,
+  __global__ __launch_bounds__(LOD_BLOCK) void k_mcg_update_xr(int nrow, int n_rhs, int ngroup, int par, double *x, size_t ld_x,
                                                               McgVectors V)
   {
-    __shared__ double b_rz[MCG_ROWS][MCG_COLS], b_rr[MCG_ROWS][MCG_COLS], s_sum[2][MCG_COLS];
-    const int c0 = blockIdx.y * MCG_COLS, nb = min(MCG_COLS, n_rhs - c0);
+    __shared__ double b_rz[LOD_ROWS][LOD_COLS], b_rr[LOD_ROWS][LOD_COLS], s_sum[2][LOD_COLS];
+    const int c0 = blockIdx.y * LOD_COLS, nb = min(LOD_COLS, n_rhs - c0);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     // wave 0 sums the partials of p.Ap, wave 1 those of r.z, both in ascending group order
     if (wave < 2 && lane < nb && V.active[c0 + lane])
-      s_sum[wave][lane] = ordered_sum(wave == 0 ? V.pAp : V.rz[par], ngroup, n_rhs, c0 + lane);
+      s_sum[wave][lane] = slod_lod_ordered_sum(wave == 0 ? V.pAp : V.rz[par], ngroup, n_rhs, c0 + lane);
     __syncthreads();
     for (int g = blockIdx.x; g < ngroup; g += gridDim.x)
       {
-        for (int idx = threadIdx.x; idx < MCG_ROWS * nb; idx += MCG_BLOCK)
+        for (int idx = threadIdx.x; idx < LOD_ROWS * nb; idx += LOD_BLOCK)
           {
-            const int lr = idx / nb, c = idx - lr * nb, i = g * MCG_ROWS + lr, col = c0 + c;
+            const int lr = idx / nb, c = idx - lr * nb, i = g * LOD_ROWS + lr, col = c0 + c;
             double    a = 0.0, b = 0.0;
             if (i < nrow && V.active[col])
               {
@@ -174,26 +145,26 @@ namespace
         if ((int)threadIdx.x < nb && V.active[c0 + threadIdx.x])
           {
             const size_t at   = (size_t)g * n_rhs + c0 + threadIdx.x;
-            V.rz[par ^ 1][at] = group_sum(b_rz, threadIdx.x);
-            V.rr[at]          = group_sum(b_rr, threadIdx.x);
+            V.rz[par ^ 1][at] = slod_lod_group_sum(b_rz, threadIdx.x);
+            V.rr[at]          = slod_lod_group_sum(b_rr, threadIdx.x);
           }
         __syncthreads();
       }
   }
 
   // beta = r.z_new / r.z from the partials of both parities; p = z + beta p
-  __global__ __launch_bounds__(MCG_BLOCK) void k_mcg_update_p(int nrow, int n_rhs, int ngroup, int par, McgVectors V)
+  __global__ __launch_bounds__(LOD_BLOCK) void k_mcg_update_p(int nrow, int n_rhs, int ngroup, int par, McgVectors V)
   {
-    __shared__ double s_sum[2][MCG_COLS];
-    const int c0 = blockIdx.y * MCG_COLS, nb = min(MCG_COLS, n_rhs - c0);
+    __shared__ double s_sum[2][LOD_COLS];
+    const int c0 = blockIdx.y * LOD_COLS, nb = min(LOD_COLS, n_rhs - c0);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (wave < 2 && lane < nb && V.active[c0 + lane])
-      s_sum[wave][lane] = ordered_sum(V.rz[wave == 0 ? par : par ^ 1], ngroup, n_rhs, c0 + lane);
+      s_sum[wave][lane] = slod_lod_ordered_sum(V.rz[wave == 0 ? par : par ^ 1], ngroup, n_rhs, c0 + lane);
     __syncthreads();
     for (int g = blockIdx.x; g < ngroup; g += gridDim.x)
-      for (int idx = threadIdx.x; idx < MCG_ROWS * nb; idx += MCG_BLOCK)
+      for (int idx = threadIdx.x; idx < LOD_ROWS * nb; idx += LOD_BLOCK)
         {
-          const int lr = idx / nb, c = idx - lr * nb, i = g * MCG_ROWS + lr, col = c0 + c;
+          const int lr = idx / nb, c = idx - lr * nb, i = g * LOD_ROWS + lr, col = c0 + c;
           if (i < nrow && V.active[col])
             {
               const double rz = s_sum[0][c], beta = rz != 0.0 ? s_sum[1][c] / rz : 0.0;
@@ -207,10 +178,10 @@ namespace
   // column with r.r <= tol^2 ||rhs||^2 is frozen (a zero column at once: 0 iterations, residual 0).
   __global__ void k_mcg_check(int n_rhs, int ngroup, double tol2, int first, McgVectors V)
   {
-    const int col = blockIdx.x * MCG_BLOCK + threadIdx.x;
+    const int col = blockIdx.x * LOD_BLOCK + threadIdx.x;
     if (col >= n_rhs || (!first && !V.active[col]))
       return;
-    const double rr = ordered_sum(V.rr, ngroup, n_rhs, col);
+    const double rr = slod_lod_ordered_sum(V.rr, ngroup, n_rhs, col);
     if (first)
       V.rhs2[col] = rr;
     V.rr_last[col] = rr;
@@ -218,54 +189,51 @@ namespace
   }
 } // namespace
 
-// Doubles of device workspace one solve needs: 4 vectors, D^-1, 4 partial arrays, 2 per-column scalars.
-size_t slod_mcg_work_doubles(const slod_handle *h, int n_rhs)
+// The pieces of the workspace of one solve: 4 vectors, D^-1, 4 partial arrays, 2 per-column scalars.
+static McgVectors mcg_carve(SlodCarver &c, const LodShape &w, int n_rhs)
 {
-  const size_t nrow = (size_t)h->NP * h->cfg.spacedim, ngroup = (nrow + MCG_ROWS - 1) / MCG_ROWS;
-  return 4 * nrow * n_rhs + nrow + 4 * ngroup * n_rhs + 2 * (size_t)n_rhs;
+  const size_t nvec = (size_t)w.nrow * n_rhs, npart = (size_t)w.ngroup * n_rhs;
+  McgVectors   V{};
+  V.r = c.take(nvec), V.z = c.take(nvec), V.p = c.take(nvec), V.Ap = c.take(nvec);
+  V.dinv = c.take((size_t)w.nrow);
+  V.pAp = c.take(npart), V.rz[0] = c.take(npart), V.rz[1] = c.take(npart), V.rr = c.take(npart);
+  V.rhs2 = c.take((size_t)n_rhs), V.rr_last = c.take((size_t)n_rhs); // read back in one copy
+  return V;
 }
 
-// The solve of slod_lod_solve_multi on a workspace the caller owns (work: slod_mcg_work_doubles() doubles, d_active:
-// n_rhs ints), so that a time loop allocates once (slod_lod_theta_steps).  Arguments are checked by the caller; the
-// handle's device is current.  its: HOST [n_rhs]; rel_residual: HOST [n_rhs] or NULL.  Synchronises h->stream.
-hipError_t slod_mcg_solve(slod_handle *h, const double *d_values, const uint32_t *d_cols, const double *d_rhs, size_t ld_rhs,
-                          int n_rhs, double *d_u, size_t ld_u, double rel_tol, int max_iterations, double *work, int *d_active,
-                          int *its, double *rel_residual)
+void SlodLodWork::take_solve(SlodCarver &c, const slod_handle *h)
 {
-  hipStream_t  st = h->stream;
-  const int    s = h->cfg.spacedim, cap = slod_lod_row_capacity(h), NP = h->NP, nrow = NP * s;
-  const int    ngroup = (nrow + MCG_ROWS - 1) / MCG_ROWS, nchunk = (n_rhs + MCG_COLS - 1) / MCG_COLS;
-  const size_t nvec = (size_t)nrow * n_rhs, npart = (size_t)ngroup * n_rhs;
-  const dim3   grid((unsigned)std::min(ngroup, MCG_MAX_BLOCKS), (unsigned)nchunk), block(MCG_BLOCK);
-  std::vector<int> active((size_t)n_rhs, 1);
-  std::fill(its, its + n_rhs, 0);
+  cg = mcg_carve(c, lod_shape(h, (int)its.size()), (int)its.size()).r;
+}
+
+// The solve of slod_lod_solve_multi on a workspace the caller owns, so that a time loop allocates once.
+hipError_t SlodLodWork::solve(slod_handle *h, const double *d_values, const uint32_t *d_cols, const double *d_rhs, size_t ld_rhs,
+                              double *d_u, size_t ld_u, double rel_tol, int max_iterations)
+{
+  hipStream_t    st = h->stream;
+  const int      n_rhs = (int)its.size();
+  int           *d_active = active.get();
+  const LodShape w = lod_shape(h, n_rhs);
+  const int      s = w.s, cap = w.cap, NP = w.NP, nrow = w.nrow, ngroup = w.ngroup;
+  const dim3     grid = lod_grid(w, SOLVE_MAX_BLOCKS), block(LOD_BLOCK);
+  std::vector<int> flags((size_t)n_rhs, 1);
+  std::fill(its.begin(), its.end(), 0);
   int        it = 0;
-  McgVectors V{};
-  V.r       = work;
-  V.z       = V.r + nvec;
-  V.p       = V.z + nvec;
-  V.Ap      = V.p + nvec;
-  V.dinv    = V.Ap + nvec;
-  V.pAp     = V.dinv + nrow;
-  V.rz[0]   = V.pAp + npart;
-  V.rz[1]   = V.rz[0] + npart;
-  V.rr      = V.rz[1] + npart;
-  V.rhs2    = V.rr + npart;
-  V.rr_last = V.rhs2 + n_rhs;
-  V.active  = d_active;
-  const double   tol2 = rel_tol * rel_tol;
-  const unsigned ncheck = (unsigned)((n_rhs + MCG_BLOCK - 1) / MCG_BLOCK);
-  hipLaunchKernelGGL(k_mcg_diag, dim3((unsigned)((nrow + MCG_BLOCK - 1) / MCG_BLOCK)), block, 0, st, nrow, s, cap, d_values, d_cols,
-                     V.dinv);
+  SlodCarver hand{cg};
+  McgVectors V = mcg_carve(hand, w, n_rhs);
+  V.active     = d_active;
+  const double tol2 = rel_tol * rel_tol;
+  const dim3   ncheck = lod_flat_grid((size_t)n_rhs);
+  hipLaunchKernelGGL(k_mcg_diag, lod_flat_grid((size_t)nrow), block, 0, st, nrow, s, cap, d_values, d_cols, V.dinv);
   hipLaunchKernelGGL(k_mcg_init, grid, block, 0, st, nrow, n_rhs, ngroup, d_rhs, ld_rhs, d_u, ld_u, V);
-  hipLaunchKernelGGL(k_mcg_check, dim3(ncheck), block, 0, st, n_rhs, ngroup, tol2, 1, V);
+  hipLaunchKernelGGL(k_mcg_check, ncheck, block, 0, st, n_rhs, ngroup, tol2, 1, V);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess)
-    e = hipMemcpyAsync(active.data(), d_active, (size_t)n_rhs * sizeof(int), hipMemcpyDeviceToHost, st);
+    e = hipMemcpyAsync(flags.data(), d_active, (size_t)n_rhs * sizeof(int), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess)
     e = hipStreamSynchronize(st);
-  std::vector<int> was_active = active;
-  bool             any = e == hipSuccess && std::find(active.begin(), active.end(), 1) != active.end();
+  std::vector<int> was_active = flags;
+  bool             any = e == hipSuccess && std::find(flags.begin(), flags.end(), 1) != flags.end();
   while (e == hipSuccess && any && it < max_iterations)
     {
       // a few iterations per convergence check: the scalars stay on the device in between
@@ -278,27 +246,30 @@ hipError_t slod_mcg_solve(slod_handle *h, const double *d_values, const uint32_t
           hipLaunchKernelGGL(k_mcg_update_p, grid, block, 0, st, nrow, n_rhs, ngroup, par, V);
         }
       it += burst;
-      hipLaunchKernelGGL(k_mcg_check, dim3(ncheck), block, 0, st, n_rhs, ngroup, tol2, 0, V);
+      hipLaunchKernelGGL(k_mcg_check, ncheck, block, 0, st, n_rhs, ngroup, tol2, 0, V);
       e = hipGetLastError();
       if (e == hipSuccess)
-        e = hipMemcpyAsync(active.data(), d_active, (size_t)n_rhs * sizeof(int), hipMemcpyDeviceToHost, st);
+        e = hipMemcpyAsync(flags.data(), d_active, (size_t)n_rhs * sizeof(int), hipMemcpyDeviceToHost, st);
       if (e == hipSuccess)
         e = hipStreamSynchronize(st);
       // a column that was active during the burst has done `it` iterations, frozen now or not
       for (int c = 0; c < n_rhs && e == hipSuccess; ++c)
         if (was_active[c])
           its[c] = it;
-      was_active = active;
-      any        = e == hipSuccess && std::find(active.begin(), active.end(), 1) != active.end();
+      was_active = flags;
+      any        = e == hipSuccess && std::find(flags.begin(), flags.end(), 1) != flags.end();
     }
   std::vector<double> sc(2 * (size_t)n_rhs);
   if (e == hipSuccess)
     e = hipMemcpyAsync(sc.data(), V.rhs2, sc.size() * sizeof(double), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess)
     e = hipStreamSynchronize(st);
-  if (e == hipSuccess && rel_residual)
-    for (int c = 0; c < n_rhs; ++c)
-      rel_residual[c] = sc[c] > 0.0 ? std::sqrt(sc[(size_t)n_rhs + c] / sc[c]) : 0.0;
+  if (e != hipSuccess)
+    return e;
+  for (int c = 0; c < n_rhs; ++c)
+    res[c] = sc[c] > 0.0 ? std::sqrt(sc[(size_t)n_rhs + c] / sc[c]) : 0.0;
+  last  = *std::max_element(its.begin(), its.end());
+  worst = std::max(worst, last);
   return e;
 }
 
@@ -313,25 +284,19 @@ int slod_lod_solve_multi(slod_handle *h, const double *d_values, const uint32_t 
     return SLOD_ERR_ARGUMENT;
   if (n_rhs < 1 || max_iterations < 0)
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_solve_multi: n_rhs < 1 or max_iterations < 0");
-  if (ld_rhs < (size_t)n_rhs || ld_u < (size_t)n_rhs)
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_solve_multi: leading dimension below n_rhs");
+  if (const int rc = slod_check_ld(h, "slod_lod_solve_multi", "n_rhs", n_rhs, {ld_rhs, ld_u}))
+    return rc;
   if (const int rc = slod_enter(h, nullptr, nullptr))
     return rc;
-  // workspace allocated per call; slod_mcg_solve synchronises the stream before it returns
-  SlodDevBuf<double> work;
-  SlodDevBuf<int>    d_active;
-  hipError_t         e = work.alloc(slod_mcg_work_doubles(h, n_rhs));
+  // workspace allocated per call; the solve synchronises the stream before it returns
+  SlodLodWork work;
+  hipError_t  e = work.alloc(n_rhs, [&](SlodCarver &c) { work.take_solve(c, h); });
   if (e == hipSuccess)
-    e = d_active.alloc((size_t)n_rhs);
-  std::vector<int> its((size_t)n_rhs, 0);
-  if (e == hipSuccess)
-    e = slod_mcg_solve(h, d_values, d_cols, d_rhs, ld_rhs, n_rhs, d_u, ld_u, rel_tol, max_iterations, work.get(), d_active.get(),
-                       its.data(), rel_residual);
-  if (e == hipSuccess && iterations)
-    std::copy(its.begin(), its.end(), iterations);
+    e = work.solve(h, d_values, d_cols, d_rhs, ld_rhs, d_u, ld_u, rel_tol, max_iterations);
   if (e != hipSuccess)
     return slod_hip_fail(h, e, "slod_lod_solve_multi");
-  return *std::max_element(its.begin(), its.end());
+  work.report(iterations, rel_residual);
+  return work.last;
 }
 
 } // extern "C"

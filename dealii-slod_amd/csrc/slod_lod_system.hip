@@ -22,7 +22,7 @@ namespace
                                                      uint32_t *cols)
   {
     const int      lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int      s = G.spacedim, n = G.n_sub, span = 4 * G.oversampling + 3, cap = span * span;
+    const int      s = G.spacedim, n = G.n_sub, cap = grid_row_capacity(G);
     const uint32_t p = rows[blockIdx.x];
     int            pcx, pcy;
     grid_centre(G, p, pcx, pcy);
@@ -31,23 +31,12 @@ namespace
     const double *phi = basis + (size_t)p * stride;
     for (int j = wave; j < cap; j += 4)
       {
-        const int    qcx = pcx + j % span - (span / 2), qcy = pcy + j / span - (span / 2);
-        const size_t out = (size_t)blockIdx.x * cap + j;
-        if (qcx < 0 || qcx >= G.N || qcy < 0 || qcy >= G.N)
-          {
-            if (lane == 0)
-              cols[out] = 0xffffffffu;
-            if (lane < s * s)
-              values[out * s * s + lane] = 0.0;
-            continue;
-          }
-        const uint32_t q  = grid_pid(G, qcx, qcy);
-        const Extent   qe = grid_extent(G, qcx, qcy);
+        const size_t   out = (size_t)blockIdx.x * cap + j;
+        const PairGeom pg = grid_pair(G, pcx, pcy, pe, j);
+        const uint32_t q  = pg.q;
+        const Extent   qe = pg.qe;
         const int      qnx = qe.mx * n + 1, qny = qe.my * n + 1, qnf = s * qnx * qny;
-        // overlap in global fine-node coordinates (inclusive)
-        const int xa = max(pe.x0, qe.x0) * n, xb = min(pe.x0 + pe.mx, qe.x0 + qe.mx) * n;
-        const int ya = max(pe.y0, qe.y0) * n, yb = min(pe.y0 + pe.my, qe.y0 + qe.my) * n;
-        const int w = xb - xa + 1, hgt = yb - ya + 1;
+        const int      xa = pg.xa, ya = pg.ya, w = pg.w, hgt = pg.hgt;
         double    acc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
         if (w > 0 && hgt > 0)
           {
@@ -76,7 +65,7 @@ namespace
                 values[out * s * s + d * s + e] = v;
             }
         if (lane == 0)
-          cols[out] = (w > 0 && hgt > 0) ? q : 0xffffffffu;
+          cols[out] = pg.col();
       }
   }
 
@@ -350,8 +339,7 @@ int slod_lod_row_capacity(const slod_handle *h)
 {
   if (!h)
     return SLOD_ERR_ARGUMENT;
-  const int span = 4 * h->cfg.oversampling + 3;
-  return span * span;
+  return grid_row_capacity(slod_grid_of(h));
 }
 
 int slod_lod_pattern(const slod_handle *h, uint32_t patch_id, uint32_t *neighbours, size_t capacity)
@@ -365,19 +353,12 @@ int slod_lod_pattern(const slod_handle *h, uint32_t patch_id, uint32_t *neighbou
   grid_centre(G, patch_id, cx, cy);
   const Extent          pe = grid_extent(G, cx, cy);
   std::vector<uint32_t> nb;
-  const int             half = 2 * h->cfg.oversampling + 1;
-  for (int dy = -half; dy <= half; ++dy)
-    for (int dx = -half; dx <= half; ++dx)
-      {
-        const int qx = cx + dx, qy = cy + dy;
-        if (qx < 0 || qx >= h->N || qy < 0 || qy >= h->N)
-          continue;
-        const Extent qe = grid_extent(G, qx, qy);
-        if (std::max(pe.x0, qe.x0) > std::min(pe.x0 + pe.mx, qe.x0 + qe.mx) ||
-            std::max(pe.y0, qe.y0) > std::min(pe.y0 + pe.my, qe.y0 + qe.my))
-          continue;
-        nb.push_back(grid_pid(G, qx, qy));
-      }
+  for (int j = 0; j < grid_row_capacity(G); ++j)
+    {
+      const uint32_t q = grid_pair(G, cx, cy, pe, j).col();
+      if (q != 0xffffffffu)
+        nb.push_back(q);
+    }
   std::sort(nb.begin(), nb.end());
   if (capacity < nb.size())
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_pattern: buffer too small");

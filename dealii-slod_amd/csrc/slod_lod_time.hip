@@ -7,9 +7,8 @@
 // The mass kernel is an L2/HBM-bound gather like k_lod_matrix (slod_lod_system.hip) and shares its index calculus
 // (slod_grid.hip.h); the solve of a step is the recurrence of slod_lod_solve_multi (slod_lod_multi.hip) on a
 // workspace this file owns for the whole loop.
-#include "slod_host.h"
 #include "slod_grid.hip.h"
-#include "slod_lod_rows.hip.h"
+#include "slod_lod_tile.hip.h"
 
 #include <algorithm>
 #include <vector>
@@ -34,7 +33,7 @@ namespace
   {
 #pragma clang fp contract(off)
     const int      lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int      n = G.n_sub, NE = G.N * n, span = 4 * G.oversampling + 3, cap = span * span;
+    const int      n = G.n_sub, NE = G.N * n, cap = grid_row_capacity(G);
     const uint32_t p = rows[blockIdx.x];
     int            pcx, pcy;
     grid_centre(G, p, pcx, pcy);
@@ -43,23 +42,13 @@ namespace
     const double *phi = basis + (size_t)p * stride;
     for (int j = wave; j < cap; j += 4)
       {
-        const int    qcx = pcx + j % span - (span / 2), qcy = pcy + j / span - (span / 2);
-        const size_t out = (size_t)blockIdx.x * cap + j;
-        if (qcx < 0 || qcx >= G.N || qcy < 0 || qcy >= G.N)
-          {
-            if (lane == 0)
-              cols[out] = 0xffffffffu;
-            if (lane < S * S)
-              values[out * S * S + lane] = 0.0;
-            continue;
-          }
-        const uint32_t q  = grid_pid(G, qcx, qcy);
-        const Extent   qe = grid_extent(G, qcx, qcy);
+        const size_t   out = (size_t)blockIdx.x * cap + j;
+        const PairGeom pg = grid_pair(G, pcx, pcy, pe, j);
+        // the overlap is w x hgt nodes, (w - 1) x (hgt - 1) elements
+        const uint32_t q  = pg.q;
+        const Extent   qe = pg.qe;
         const int      qnx = qe.mx * n + 1, qny = qe.my * n + 1, qnf = S * qnx * qny;
-        // overlap in global fine-node coordinates (inclusive): w x hgt nodes, (w - 1) x (hgt - 1) elements
-        const int xa = max(pe.x0, qe.x0) * n, xb = min(pe.x0 + pe.mx, qe.x0 + qe.mx) * n;
-        const int ya = max(pe.y0, qe.y0) * n, yb = min(pe.y0 + pe.my, qe.y0 + qe.my) * n;
-        const int w = xb - xa + 1, hgt = yb - ya + 1;
+        const int      xa = pg.xa, ya = pg.ya, w = pg.w, hgt = pg.hgt;
         double    acc[S][S];
 #pragma unroll
         for (int d = 0; d < S; ++d)
@@ -126,27 +115,26 @@ namespace
             }
         // the pattern is that of k_lod_matrix: a pair that shares only a line of nodes keeps its column, value 0
         if (lane == 0)
-          cols[out] = (w > 0 && hgt > 0) ? q : 0xffffffffu;
+          cols[out] = pg.col();
       }
   }
 
   // ---------------------------------------------------------------------------------
-  // Y = A X on the block rows, the tiling of k_mcg_spmv: columns in chunks of 64 on lanes (blockIdx.y), a block
-  // takes groups of 16 consecutive rows and spreads the (row, column) items over its threads, row-major.  The row
-  // product is the one the CG uses (slod_lod_rows.hip.h): the bits of a column depend on the matrix and that column.
+  // Y = A X on the block rows, the tiling and the row product of k_mcg_spmv (slod_lod_tile.hip.h): the bits of a
+  // column depend on the matrix and that column.
   // ---------------------------------------------------------------------------------
-  constexpr int AP_COLS = 64, AP_ROWS = 16, AP_BLOCK = 256, AP_MAX_BLOCKS = 1024;
+  constexpr int APPLY_MAX_BLOCKS = 1024; // blocks per chunk
 
-  __global__ __launch_bounds__(AP_BLOCK) void k_lod_apply(int nrow, int s, int cap, int NP, int n_rhs, int ngroup,
+  __global__ __launch_bounds__(LOD_BLOCK) void k_lod_apply(int nrow, int s, int cap, int NP, int n_rhs, int ngroup,
                                                          const double *__restrict__ values, const uint32_t *__restrict__ cols,
                                                          const double *__restrict__ x, size_t ld_x, double *__restrict__ y,
                                                          size_t ld_y)
   {
-    const int c0 = blockIdx.y * AP_COLS, nb = min(AP_COLS, n_rhs - c0);
+    const int c0 = blockIdx.y * LOD_COLS, nb = min(LOD_COLS, n_rhs - c0);
     for (int g = blockIdx.x; g < ngroup; g += gridDim.x)
-      for (int idx = threadIdx.x; idx < AP_ROWS * nb; idx += AP_BLOCK)
+      for (int idx = threadIdx.x; idx < LOD_ROWS * nb; idx += LOD_BLOCK)
         {
-          const int lr = idx / nb, c = idx - lr * nb, i = g * AP_ROWS + lr, col = c0 + c;
+          const int lr = idx / nb, c = idx - lr * nb, i = g * LOD_ROWS + lr, col = c0 + c;
           if (i >= nrow)
             continue;
           const double acc = slod_lod_row_product(i, s, cap, NP, values, cols, x, ld_x, col);
@@ -194,28 +182,21 @@ namespace
     const size_t i = w / n_rhs, c = w - i * n_rhs;
     u[i * ld_u + c] += delta[w];
   }
-
-  void launch_apply(const slod_handle *h, hipStream_t st, const double *values, const uint32_t *cols, const double *x, size_t ld_x,
-                    int n_rhs, double *y, size_t ld_y)
-  {
-    const int  s = h->cfg.spacedim, cap = slod_lod_row_capacity(h), NP = h->NP, nrow = NP * s;
-    const int  ngroup = (nrow + AP_ROWS - 1) / AP_ROWS, nchunk = (n_rhs + AP_COLS - 1) / AP_COLS;
-    const dim3 grid((unsigned)std::min(ngroup, AP_MAX_BLOCKS), (unsigned)nchunk);
-    hipLaunchKernelGGL(k_lod_apply, grid, dim3(AP_BLOCK), 0, st, nrow, s, cap, NP, n_rhs, ngroup, values, cols, x, ld_x, y, ld_y);
-  }
 } // namespace
 
 // k_lod_apply for the other loops of the library (slod_lod_eig.hip); arguments are checked by the caller
 void slod_lod_apply_launch(const slod_handle *h, hipStream_t st, const double *d_values, const uint32_t *d_cols, const double *d_x,
                            size_t ld_x, int n_rhs, double *d_y, size_t ld_y)
 {
-  launch_apply(h, st, d_values, d_cols, d_x, ld_x, n_rhs, d_y, ld_y);
+  const LodShape w = lod_shape(h, n_rhs);
+  hipLaunchKernelGGL(k_lod_apply, lod_grid(w, APPLY_MAX_BLOCKS), dim3(LOD_BLOCK), 0, st, w.nrow, w.s, w.cap, w.NP, n_rhs, w.ngroup,
+                     d_values, d_cols, d_x, ld_x, d_y, ld_y);
 }
 
 // k_lod_combine on n values for the other loops of the library (slod_lod_wave.hip)
 void slod_lod_combine_launch(hipStream_t st, size_t n, double alpha, const double *d_a, double beta, const double *d_b, double *d_out)
 {
-  hipLaunchKernelGGL(k_lod_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, alpha, d_a, beta, d_b, d_out);
+  hipLaunchKernelGGL(k_lod_combine, lod_flat_grid(n), dim3(LOD_BLOCK), 0, st, n, alpha, d_a, beta, d_b, d_out);
 }
 
 #pragma GCC visibility push(default)
@@ -257,14 +238,14 @@ int slod_lod_apply_multi(slod_handle *h, const double *d_values, const uint32_t 
     return SLOD_ERR_ARGUMENT;
   if (n_rhs < 1)
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_apply_multi: n_rhs < 1");
-  if (ld_x < (size_t)n_rhs || ld_y < (size_t)n_rhs)
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_apply_multi: leading dimension below n_rhs");
+  if (const int rc = slod_check_ld(h, "slod_lod_apply_multi", "n_rhs", n_rhs, {ld_x, ld_y}))
+    return rc;
   if (d_x == d_y)
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_apply_multi: the product cannot run in place");
   hipStream_t st;
   if (const int rc = slod_enter(h, hip_stream, &st))
     return rc;
-  launch_apply(h, st, d_values, d_cols, d_x, ld_x, n_rhs, d_y, ld_y);
+  slod_lod_apply_launch(h, st, d_values, d_cols, d_x, ld_x, n_rhs, d_y, ld_y);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_apply_multi");
 }
@@ -277,9 +258,8 @@ int slod_lod_matrix_combine(slod_handle *h, double alpha, const double *d_a, dou
   hipStream_t st;
   if (const int rc = slod_enter(h, hip_stream, &st))
     return rc;
-  const int    s = h->cfg.spacedim;
-  const size_t n = (size_t)h->NP * slod_lod_row_capacity(h) * s * s;
-  hipLaunchKernelGGL(k_lod_combine, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, alpha, d_a, beta, d_b, d_out);
+  const int s = h->cfg.spacedim;
+  slod_lod_combine_launch(st, (size_t)h->NP * slod_lod_row_capacity(h) * s * s, alpha, d_a, beta, d_b, d_out);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_matrix_combine");
 }
@@ -294,56 +274,42 @@ int slod_lod_theta_steps(slod_handle *h, const double *d_stiffness, const double
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_theta_steps: dt <= 0 or theta outside [0, 1]");
   if (n_steps < 1 || n_rhs < 1 || max_iterations < 0)
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_theta_steps: n_steps < 1, n_rhs < 1 or max_iterations < 0");
-  if (ld_u < (size_t)n_rhs || (d_load && ld_load < (size_t)n_rhs))
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_theta_steps: leading dimension below n_rhs");
+  if (const int rc = slod_check_ld(h, "slod_lod_theta_steps", "n_rhs", n_rhs, {ld_u, d_load ? ld_load : ld_u}))
+    return rc;
   hipStream_t st;
   if (const int rc = slod_enter(h, nullptr, &st))
     return rc;
-  const int    s = h->cfg.spacedim, nrow = h->NP * s;
-  const size_t nmat = (size_t)h->NP * slod_lod_row_capacity(h) * s * s, nvec = (size_t)nrow * n_rhs;
+  const LodShape w = lod_shape(h, n_rhs);
+  const size_t   nmat = (size_t)w.NP * w.cap * w.s * w.s, nvec = (size_t)w.nrow * n_rhs;
   // one allocation for the whole loop: S, g, delta and the workspace of the solve
-  SlodDevBuf<double> work;
-  SlodDevBuf<int>    d_active;
-  hipError_t         e = work.alloc(nmat + 2 * nvec + slod_mcg_work_doubles(h, n_rhs));
-  if (e == hipSuccess)
-    e = d_active.alloc((size_t)n_rhs);
-  int worst = 0;
+  double     *S, *g, *delta;
+  SlodLodWork work;
+  hipError_t  e = work.alloc(n_rhs, [&](SlodCarver &c) { S = c.take(nmat), g = c.take(nvec), delta = c.take(nvec), work.take_solve(c, h); });
   if (e == hipSuccess)
     {
-      double        *S = work.get(), *g = S + nmat, *delta = g + nvec, *cg = delta + nvec;
-      const unsigned nblk = (unsigned)((nvec + 255) / 256);
-      hipLaunchKernelGGL(k_lod_combine, dim3((unsigned)((nmat + 255) / 256)), dim3(256), 0, st, nmat, 1.0, d_mass, theta * dt,
-                         d_stiffness, S);
+      slod_lod_combine_launch(st, nmat, 1.0, d_mass, theta * dt, d_stiffness, S);
       e = hipGetLastError();
-      std::vector<int>    its((size_t)n_rhs);
-      std::vector<double> res((size_t)n_rhs);
       for (int k = 0; k < n_steps && e == hipSuccess; ++k)
         {
           const double *b0 = d_load ? d_load + (size_t)k * load_step_stride : nullptr;
           const double *b1 = d_load ? d_load + (size_t)(k + 1) * load_step_stride : nullptr;
-          launch_apply(h, st, d_stiffness, d_cols, d_u, ld_u, n_rhs, g, (size_t)n_rhs);
-          hipLaunchKernelGGL(k_theta_rhs, dim3(nblk), dim3(256), 0, st, nrow, n_rhs, dt, theta, b0, b1, ld_load, g);
+          slod_lod_apply_launch(h, st, d_stiffness, d_cols, d_u, ld_u, n_rhs, g, (size_t)n_rhs);
+          hipLaunchKernelGGL(k_theta_rhs, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n_rhs, dt, theta, b0, b1, ld_load, g);
           e = hipGetLastError();
           if (e == hipSuccess)
-            e = slod_mcg_solve(h, S, d_cols, g, (size_t)n_rhs, n_rhs, delta, (size_t)n_rhs, rel_tol, max_iterations, cg,
-                               d_active.get(), its.data(), res.data());
+            e = work.solve(h, S, d_cols, g, (size_t)n_rhs, delta, (size_t)n_rhs, rel_tol, max_iterations);
           if (e != hipSuccess)
             break;
-          hipLaunchKernelGGL(k_theta_advance, dim3(nblk), dim3(256), 0, st, nrow, n_rhs, delta, d_u, ld_u);
+          work.record(k, iterations, rel_residual);
+          hipLaunchKernelGGL(k_theta_advance, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n_rhs, delta, d_u, ld_u);
           e = hipGetLastError();
-          const int step_its = *std::max_element(its.begin(), its.end());
-          worst              = std::max(worst, step_its);
-          if (iterations)
-            iterations[k] = step_its;
-          if (rel_residual)
-            rel_residual[k] = *std::max_element(res.begin(), res.end());
         }
       if (e == hipSuccess)
-        e = hipStreamSynchronize(st); // work and d_active are freed on return
+        e = hipStreamSynchronize(st); // the workspace is freed on return
     }
   if (e != hipSuccess)
     return slod_hip_fail(h, e, "slod_lod_theta_steps");
-  return worst;
+  return work.worst;
 }
 
 } // extern "C"

@@ -4,19 +4,17 @@
 //   slod_lod_inner_multi    out[c] = x_c^T (A y_c), the energies of the stepper
 //   slod_lod_newmark_accel  M a = b^0 - A (u + damp_stiff v) - damp_mass M v, the consistent initial acceleration
 //   slod_lod_newmark_steps  n_steps of Newmark-beta in acceleration form, the state stays on the device
-// The solves are the recurrence of slod_lod_solve_multi (slod_mcg_solve, slod_lod_multi.hip) on a workspace this
-// file owns for the whole loop, every one from zero; row products are slod_lod_row_product (slod_lod_rows.hip.h).
+// The solves are the recurrence of slod_lod_solve_multi (SlodLodWork::solve, slod_lod_multi.hip) on a workspace this
+// file owns for the whole loop, every one from zero; row products, tiling and sums are those of slod_lod_tile.hip.h.
 // Everything else is elementwise with fp contract off, so the bits of a column depend on that column alone.
-#include "slod_host.h"
-#include "slod_lod_rows.hip.h"
+#include "slod_lod_tile.hip.h"
 
 #include <algorithm>
 #include <vector>
 
 namespace
 {
-  // the tiling and the summation order of the multi-vector CG (slod_lod_multi.hip): the order hangs on WV_ROWS
-  constexpr int WV_COLS = 64, WV_ROWS = 16, WV_BLOCK = 256, WV_MAX_BLOCKS = 256;
+  constexpr int INNER_MAX_BLOCKS = 256; // blocks per chunk
 
   // one bilinear form x^T (A y) per blockIdx.z; partial: [ngroup][n_rhs]
   struct InnerJob
@@ -27,20 +25,19 @@ namespace
   };
 
   // partial[g][col] = sum over the rows i of group g, ascending, of  x[i,col] * (A y)[i,col].  (A y)[i,col] is the fma
-  // chain of k_lod_apply, the product with x is rounded on its own.  Columns in chunks of 64 on lanes (blockIdx.y), a
-  // block walks the groups blockIdx.x, blockIdx.x + gridDim.x, ...
-  __global__ __launch_bounds__(WV_BLOCK) void k_lod_inner(int nrow, int s, int cap, int NP, int n_rhs, int ngroup,
+  // chain of k_lod_apply, the product with x is rounded on its own.
+  __global__ __launch_bounds__(LOD_BLOCK) void k_lod_inner(int nrow, int s, int cap, int NP, int n_rhs, int ngroup,
                                                          const uint32_t *__restrict__ cols, InnerJob j0, InnerJob j1)
   {
 #pragma clang fp contract(off)
-    __shared__ double buf[WV_ROWS][WV_COLS];
+    __shared__ double buf[LOD_ROWS][LOD_COLS];
     const InnerJob    J = blockIdx.z ? j1 : j0;
-    const int         c0 = blockIdx.y * WV_COLS, nb = min(WV_COLS, n_rhs - c0);
+    const int         c0 = blockIdx.y * LOD_COLS, nb = min(LOD_COLS, n_rhs - c0);
     for (int g = blockIdx.x; g < ngroup; g += gridDim.x)
       {
-        for (int idx = threadIdx.x; idx < WV_ROWS * nb; idx += WV_BLOCK)
+        for (int idx = threadIdx.x; idx < LOD_ROWS * nb; idx += LOD_BLOCK)
           {
-            const int lr = idx / nb, c = idx - lr * nb, i = g * WV_ROWS + lr, col = c0 + c;
+            const int lr = idx / nb, c = idx - lr * nb, i = g * LOD_ROWS + lr, col = c0 + c;
             double    prod = 0.0;
             if (i < nrow)
               {
@@ -51,31 +48,21 @@ namespace
           }
         __syncthreads();
         if ((int)threadIdx.x < nb)
-          {
-            double sum = buf[0][threadIdx.x];
-#pragma unroll
-            for (int r = 1; r < WV_ROWS; ++r)
-              sum += buf[r][threadIdx.x];
-            J.partial[(size_t)g * n_rhs + c0 + threadIdx.x] = sum;
-          }
+          J.partial[(size_t)g * n_rhs + c0 + threadIdx.x] = slod_lod_group_sum(buf, threadIdx.x);
         __syncthreads();
       }
   }
 
   // out[z][col] = scale * sum of partial_z[g][col], g ascending: one thread per (form z, column)
-  __global__ __launch_bounds__(WV_BLOCK) void k_lod_inner_sum(int n_rhs, int ngroup, int nform, const double *p0, const double *p1,
+  __global__ __launch_bounds__(LOD_BLOCK) void k_lod_inner_sum(int n_rhs, int ngroup, int nform, const double *p0, const double *p1,
                                                              double scale, double *out)
   {
 #pragma clang fp contract(off)
-    const int w = blockIdx.x * WV_BLOCK + threadIdx.x;
+    const int w = blockIdx.x * LOD_BLOCK + threadIdx.x;
     if (w >= nform * n_rhs)
       return;
-    const int     z = w / n_rhs, col = w - z * n_rhs;
-    const double *partial = z ? p1 : p0;
-    double        sum = 0.0;
-    for (int g = 0; g < ngroup; ++g)
-      sum += partial[(size_t)g * n_rhs + col];
-    out[w] = scale * sum;
+    const int z = w / n_rhs, col = w - z * n_rhs;
+    out[w]      = scale * slod_lod_ordered_sum(z ? p1 : p0, ngroup, n_rhs, col);
   }
 
   // w = u + damp_stiff v, the argument of A in the right-hand side of the initial acceleration
@@ -147,30 +134,14 @@ namespace
     v[i * ld_v + c] = v[i * ld_v + c] + tv;
   }
 
-  struct WaveShape
-  {
-    int s, cap, NP, nrow, ngroup, nchunk;
-  };
-  WaveShape shape_of(const slod_handle *h, int n_rhs)
-  {
-    WaveShape w;
-    w.s      = h->cfg.spacedim;
-    w.cap    = slod_lod_row_capacity(h);
-    w.NP     = h->NP;
-    w.nrow   = w.NP * w.s;
-    w.ngroup = (w.nrow + WV_ROWS - 1) / WV_ROWS;
-    w.nchunk = (n_rhs + WV_COLS - 1) / WV_COLS;
-    return w;
-  }
-
   // nform (1 or 2) bilinear forms in one launch of k_lod_inner, then their ordered sums: out[z * n_rhs + col]
-  void launch_inner(const WaveShape &w, hipStream_t st, const uint32_t *cols, int n_rhs, int nform, const InnerJob &j0,
+  void launch_inner(const LodShape &w, hipStream_t st, const uint32_t *cols, int n_rhs, int nform, const InnerJob &j0,
                     const InnerJob &j1, double scale, double *out)
   {
-    const dim3 grid((unsigned)std::min(w.ngroup, WV_MAX_BLOCKS), (unsigned)w.nchunk, (unsigned)nform);
-    hipLaunchKernelGGL(k_lod_inner, grid, dim3(WV_BLOCK), 0, st, w.nrow, w.s, w.cap, w.NP, n_rhs, w.ngroup, cols, j0, j1);
-    hipLaunchKernelGGL(k_lod_inner_sum, dim3((unsigned)((nform * n_rhs + WV_BLOCK - 1) / WV_BLOCK)), dim3(WV_BLOCK), 0, st, n_rhs,
-                       w.ngroup, nform, j0.partial, j1.partial, scale, out);
+    hipLaunchKernelGGL(k_lod_inner, lod_grid(w, INNER_MAX_BLOCKS, nform), dim3(LOD_BLOCK), 0, st, w.nrow, w.s, w.cap, w.NP, n_rhs,
+                       w.ngroup, cols, j0, j1);
+    hipLaunchKernelGGL(k_lod_inner_sum, lod_flat_grid((size_t)nform * n_rhs), dim3(LOD_BLOCK), 0, st, n_rhs, w.ngroup, nform,
+                       j0.partial, j1.partial, scale, out);
   }
 
   bool bad_damping(double damp_mass, double damp_stiff) { return !(damp_mass >= 0.0) || !(damp_stiff >= 0.0); }
@@ -188,12 +159,12 @@ int slod_lod_inner_multi(slod_handle *h, const double *d_values, const uint32_t 
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_inner_multi: NULL array");
   if (n_rhs < 1)
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_inner_multi: n_rhs < 1");
-  if (ld_x < (size_t)n_rhs || ld_y < (size_t)n_rhs)
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_inner_multi: leading dimension below n_rhs");
+  if (const int rc = slod_check_ld(h, "slod_lod_inner_multi", "n_rhs", n_rhs, {ld_x, ld_y}))
+    return rc;
   hipStream_t st;
   if (const int rc = slod_enter(h, hip_stream, &st))
     return rc;
-  const WaveShape    w = shape_of(h, n_rhs);
+  const LodShape     w = lod_shape(h, n_rhs);
   SlodDevBuf<double> work; // the partials, then the n_rhs sums
   hipError_t         e = work.alloc((size_t)w.ngroup * n_rhs + (size_t)n_rhs);
   if (e == hipSuccess)
@@ -223,37 +194,30 @@ int slod_lod_newmark_accel(slod_handle *h, const double *d_stiffness, const doub
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_accel: negative or NaN damping coefficient");
   if (n_rhs < 1 || max_iterations < 0)
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_accel: n_rhs < 1 or max_iterations < 0");
-  if (ld_u < (size_t)n_rhs || ld_v < (size_t)n_rhs || ld_a < (size_t)n_rhs || (d_load && ld_load < (size_t)n_rhs))
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_accel: leading dimension below n_rhs");
+  if (const int rc = slod_check_ld(h, "slod_lod_newmark_accel", "n_rhs", n_rhs, {ld_u, ld_v, ld_a, d_load ? ld_load : ld_u}))
+    return rc;
   hipStream_t st;
   if (const int rc = slod_enter(h, nullptr, &st))
     return rc;
-  const WaveShape w = shape_of(h, n_rhs);
-  const size_t    nvec = (size_t)w.nrow * n_rhs;
+  const LodShape w = lod_shape(h, n_rhs);
+  const size_t   nvec = (size_t)w.nrow * n_rhs;
   // w = u + damp_stiff v, g, and the workspace of the solve
-  SlodDevBuf<double> work;
-  SlodDevBuf<int>    d_active;
-  hipError_t         e = work.alloc(2 * nvec + slod_mcg_work_doubles(h, n_rhs));
-  if (e == hipSuccess)
-    e = d_active.alloc((size_t)n_rhs);
-  std::vector<int> its((size_t)n_rhs, 0);
+  double     *arg, *g;
+  SlodLodWork work;
+  hipError_t  e = work.alloc(n_rhs, [&](SlodCarver &c) { arg = c.take(nvec), g = c.take(nvec), work.take_solve(c, h); });
   if (e == hipSuccess)
     {
-      double        *arg = work.get(), *g = arg + nvec, *cg = g + nvec;
-      const unsigned nblk = (unsigned)((nvec + 255) / 256);
-      hipLaunchKernelGGL(k_nm_shift, dim3(nblk), dim3(256), 0, st, w.nrow, n_rhs, damp_stiff, d_u, ld_u, d_v, ld_v, arg);
-      hipLaunchKernelGGL(k_nm_rhs, dim3(nblk), dim3(256), 0, st, w.nrow, w.s, w.cap, w.NP, n_rhs, d_stiffness,
+      hipLaunchKernelGGL(k_nm_shift, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n_rhs, damp_stiff, d_u, ld_u, d_v, ld_v, arg);
+      hipLaunchKernelGGL(k_nm_rhs, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, w.s, w.cap, w.NP, n_rhs, d_stiffness,
                          damp_mass != 0.0 ? d_mass : nullptr, d_cols, damp_mass, d_load, ld_load, arg, d_v, ld_v, g);
       e = hipGetLastError();
-      if (e == hipSuccess)
-        e = slod_mcg_solve(h, d_mass, d_cols, g, (size_t)n_rhs, n_rhs, d_a, ld_a, rel_tol, max_iterations, cg, d_active.get(),
-                           its.data(), rel_residual); // synchronises: work and d_active are freed on return
+      if (e == hipSuccess) // the solve synchronises: the workspace is freed on return
+        e = work.solve(h, d_mass, d_cols, g, (size_t)n_rhs, d_a, ld_a, rel_tol, max_iterations);
     }
   if (e != hipSuccess)
     return slod_hip_fail(h, e, "slod_lod_newmark_accel");
-  if (iterations)
-    std::copy(its.begin(), its.end(), iterations);
-  return *std::max_element(its.begin(), its.end());
+  work.report(iterations, rel_residual);
+  return work.last;
 }
 
 int slod_lod_newmark_steps(slod_handle *h, const double *d_stiffness, const double *d_mass, const uint32_t *d_cols, double dt,
@@ -272,67 +236,57 @@ int slod_lod_newmark_steps(slod_handle *h, const double *d_stiffness, const doub
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_steps: negative or NaN damping coefficient");
   if (n_steps < 1 || n_rhs < 1 || max_iterations < 0)
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_steps: n_steps < 1, n_rhs < 1 or max_iterations < 0");
-  if (ld_u < (size_t)n_rhs || ld_v < (size_t)n_rhs || ld_a < (size_t)n_rhs || (d_load && ld_load < (size_t)n_rhs))
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_steps: leading dimension below n_rhs");
+  if (const int rc = slod_check_ld(h, "slod_lod_newmark_steps", "n_rhs", n_rhs, {ld_u, ld_v, ld_a, d_load ? ld_load : ld_u}))
+    return rc;
   if ((kinetic == nullptr) != (potential == nullptr))
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_steps: kinetic and potential come together or not at all");
   hipStream_t st;
   if (const int rc = slod_enter(h, nullptr, &st))
     return rc;
-  const WaveShape w = shape_of(h, n_rhs);
-  const bool      energies = kinetic != nullptr;
-  const size_t    nmat = (size_t)w.NP * w.cap * w.s * w.s, nvec = (size_t)w.nrow * n_rhs, npart = (size_t)w.ngroup * n_rhs;
-  const size_t    nenergy = energies ? 2 * (size_t)(n_steps + 1) * n_rhs : 0;
+  const LodShape w = lod_shape(h, n_rhs);
+  const bool     energies = kinetic != nullptr;
+  const size_t   nmat = (size_t)w.NP * w.cap * w.s * w.s, nvec = (size_t)w.nrow * n_rhs, npart = (size_t)w.ngroup * n_rhs;
+  const size_t   nenergy = energies ? 2 * (size_t)(n_steps + 1) * n_rhs : 0;
   // one allocation for the whole loop: S, w = u~ + damp_stiff v~, g, the workspace of the solve, and for the
   // energies two arrays of partials and [level][kinetic, potential][column]
-  SlodDevBuf<double> work;
-  SlodDevBuf<int>    d_active;
-  hipError_t         e = work.alloc(nmat + 2 * nvec + slod_mcg_work_doubles(h, n_rhs) + (energies ? 2 * npart : 0) + nenergy);
-  if (e == hipSuccess)
-    e = d_active.alloc((size_t)n_rhs);
-  int worst = 0;
+  double     *S, *arg, *g, *part_k, *part_p, *d_energy;
+  SlodLodWork work;
+  hipError_t  e = work.alloc(n_rhs, [&](SlodCarver &c) {
+    S = c.take(nmat), arg = c.take(nvec), g = c.take(nvec), work.take_solve(c, h);
+    part_k = c.take(energies ? npart : 0), part_p = c.take(energies ? npart : 0), d_energy = c.take(nenergy);
+  });
   if (e == hipSuccess)
     {
-      double        *S = work.get(), *arg = S + nmat, *g = arg + nvec, *cg = g + nvec;
-      double        *part = cg + slod_mcg_work_doubles(h, n_rhs), *d_energy = part + (energies ? 2 * npart : 0);
-      const unsigned nblk = (unsigned)((nvec + 255) / 256);
-      const InnerJob jk{d_mass, d_v, d_v, ld_v, ld_v, part}, jp{d_stiffness, d_u, d_u, ld_u, ld_u, part + npart};
+      const dim3     nblk = lod_flat_grid(nvec);
+      const InnerJob jk{d_mass, d_v, d_v, ld_v, ld_v, part_k}, jp{d_stiffness, d_u, d_u, ld_u, ld_u, part_p};
       const double   gdt = gamma * dt, bdt2 = beta * dt * dt;
       slod_lod_combine_launch(st, nmat, 1.0 + gdt * damp_mass, d_mass, bdt2 + gdt * damp_stiff, d_stiffness, S);
       if (energies)
         launch_inner(w, st, d_cols, n_rhs, 2, jk, jp, 0.5, d_energy);
       e = hipGetLastError();
-      std::vector<int>    its((size_t)n_rhs);
-      std::vector<double> res((size_t)n_rhs);
       for (int k = 0; k < n_steps && e == hipSuccess; ++k)
         {
           const double *b1 = d_load ? d_load + (size_t)(k + 1) * load_step_stride : nullptr;
-          hipLaunchKernelGGL(k_nm_predict, dim3(nblk), dim3(256), 0, st, w.nrow, n_rhs, dt, dt * dt * (0.5 - beta), dt * (1.0 - gamma),
+          hipLaunchKernelGGL(k_nm_predict, nblk, dim3(256), 0, st, w.nrow, n_rhs, dt, dt * dt * (0.5 - beta), dt * (1.0 - gamma),
                              damp_stiff, d_u, ld_u, d_v, ld_v, d_a, ld_a, arg);
-          hipLaunchKernelGGL(k_nm_rhs, dim3(nblk), dim3(256), 0, st, w.nrow, w.s, w.cap, w.NP, n_rhs, d_stiffness,
+          hipLaunchKernelGGL(k_nm_rhs, nblk, dim3(256), 0, st, w.nrow, w.s, w.cap, w.NP, n_rhs, d_stiffness,
                              damp_mass != 0.0 ? d_mass : nullptr, d_cols, damp_mass, b1, ld_load, arg, d_v, ld_v, g);
           e = hipGetLastError();
           if (e == hipSuccess)
-            e = slod_mcg_solve(h, S, d_cols, g, (size_t)n_rhs, n_rhs, d_a, ld_a, rel_tol, max_iterations, cg, d_active.get(),
-                               its.data(), res.data());
+            e = work.solve(h, S, d_cols, g, (size_t)n_rhs, d_a, ld_a, rel_tol, max_iterations);
           if (e != hipSuccess)
             break;
-          hipLaunchKernelGGL(k_nm_correct, dim3(nblk), dim3(256), 0, st, w.nrow, n_rhs, bdt2, gdt, d_u, ld_u, d_v, ld_v, d_a, ld_a);
+          work.record(k, iterations, rel_residual);
+          hipLaunchKernelGGL(k_nm_correct, nblk, dim3(256), 0, st, w.nrow, n_rhs, bdt2, gdt, d_u, ld_u, d_v, ld_v, d_a, ld_a);
           if (energies)
             launch_inner(w, st, d_cols, n_rhs, 2, jk, jp, 0.5, d_energy + 2 * (size_t)(k + 1) * n_rhs);
           e = hipGetLastError();
-          const int step_its = *std::max_element(its.begin(), its.end());
-          worst              = std::max(worst, step_its);
-          if (iterations)
-            iterations[k] = step_its;
-          if (rel_residual)
-            rel_residual[k] = *std::max_element(res.begin(), res.end());
         }
       std::vector<double> host(nenergy);
       if (e == hipSuccess && energies)
         e = hipMemcpyAsync(host.data(), d_energy, nenergy * sizeof(double), hipMemcpyDeviceToHost, st);
       if (e == hipSuccess)
-        e = hipStreamSynchronize(st); // work and d_active are freed on return
+        e = hipStreamSynchronize(st); // the workspace is freed on return
       if (e == hipSuccess && energies)
         for (size_t k = 0; k <= (size_t)n_steps; ++k)
           for (size_t c = 0; c < (size_t)n_rhs; ++c)
@@ -343,7 +297,7 @@ int slod_lod_newmark_steps(slod_handle *h, const double *d_stiffness, const doub
     }
   if (e != hipSuccess)
     return slod_hip_fail(h, e, "slod_lod_newmark_steps");
-  return worst;
+  return work.worst;
 }
 
 } // extern "C"

@@ -1,0 +1,247 @@
+"""Helpers shared by the GPU test modules (a plain module like fixture_utils.py, not a conftest): handles and
+coefficient upload, the parity check of one patch, dense copies of the block rows of the LOD matrices, the fine FEM
+reference, and the cases (basis, stiffness, mass, pencil) the tests of the LOD-space entry points build on.  Test
+modules import from here and never from each other."""
+import numpy as np
+
+from conftest import make_fields
+
+NAN = float("nan")
+TOL_PHI = 1e-10
+MASS_CONFIGS = {"s1": dict(nref=2, n_sub=2, oversampling=1, spacedim=1),
+                "clipped": dict(nref=2, n_sub=4, oversampling=2, spacedim=1),
+                "s2": dict(nref=2, n_sub=2, oversampling=1, spacedim=2),
+                "rowmajor": dict(n_cells=5, n_sub=3, oversampling=1, spacedim=1)}
+
+
+def _torch():
+    import torch
+    return torch, torch.device("cuda", 0)
+
+
+def _bits(t):
+    return t.contiguous().cpu().numpy().view(np.uint64)
+
+
+def _mk(so, **kw):
+    import slod_amd
+    cfg = so.make_cfg(**kw)
+    g = slod_amd.Slod(nref=kw.get("nref", 0), n_sub=kw["n_sub"], oversampling=kw["oversampling"],
+                      spacedim=kw.get("spacedim", 1), stabilize=kw.get("stabilize", 1),
+                      reuse_full=kw.get("reuse_full", 0), proj_quirk=kw.get("proj_quirk", 0),
+                      n_cells=kw.get("n_cells", 0))
+    return cfg, g
+
+
+def _upload(g, fields):
+    for f, a in enumerate(fields):
+        g.set_coefficient(f, a)
+
+
+def _check_patch(so, cfg, fields, pid, basis, premult, off, label=""):
+    p = so.patch_info(cfg, pid)
+    s = cfg.spacedim
+    phi, psi, _ = so.patch_basis(cfg, fields, pid)
+    st = so.assemble_patch(cfg, fields, pid)
+    a_inf = np.abs(st).sum(axis=(1, 3)).max()
+    n = s * p.n_f
+    gphi = basis[off:off + n].reshape(s, p.n_f)
+    gpsi = premult[off:off + n].reshape(s, p.n_f)
+    ephi = np.abs(gphi - phi).max()
+    epsi = np.abs(gpsi - psi).max()
+    assert np.isfinite(gphi).all() and np.isfinite(gpsi).all(), label
+    assert ephi <= TOL_PHI, "%s patch %d: |dphi| = %.3e" % (label, pid, ephi)
+    assert epsi <= TOL_PHI * a_inf, "%s patch %d: |dpsi| = %.3e (tol %.3e)" % (label, pid, epsi, TOL_PHI * a_inf)
+    return ephi, epsi / a_inf
+
+
+def _decisions(g, ids, offs):
+    """slod_plan_diagnostics of the same patches (plan path; outputs must equal the host-buffer path)"""
+    import torch
+    plan = g.plan(ids, offs)
+    dev = torch.device("cuda", 0)
+    b = torch.zeros(max(plan.output_size, 1), dtype=torch.float64, device=dev)
+    q = torch.zeros_like(b)
+    plan.execute(b.data_ptr(), q.data_ptr())
+    torch.cuda.synchronize()
+    plan.status()
+    return plan.diagnostics()
+
+
+def _global_dense(g, cfg_s, basis, premult, stride):
+    """Scatter every patch vector to the global fine grid: (N_patches*s) x (NEp^2 * s) dense arrays."""
+    s, n, NP = cfg_s, g.cfg.n_subdivisions, g.num_patches
+    NEp = g.NE + 1
+    Phi = np.zeros((NP * s, NEp * NEp * s))
+    Psi = np.zeros_like(Phi)
+    for p in range(NP):
+        info = g.patch_layout(p)
+        nxp, nyp = info.nx + 1, info.ny + 1
+        for d in range(s):
+            vphi = basis[p * stride + d * info.n_fine:p * stride + (d + 1) * info.n_fine].reshape(nyp, nxp, s)
+            vpsi = premult[p * stride + d * info.n_fine:p * stride + (d + 1) * info.n_fine].reshape(nyp, nxp, s)
+            G1 = Phi[p * s + d].reshape(NEp, NEp, s)
+            G2 = Psi[p * s + d].reshape(NEp, NEp, s)
+            G1[info.y0 * n:info.y0 * n + nyp, info.x0 * n:info.x0 * n + nxp, :] = vphi
+            G2[info.y0 * n:info.y0 * n + nyp, info.x0 * n:info.x0 * n + nxp, :] = vpsi
+    return Phi, Psi
+
+
+def _rows_to_dense(g, values, cols, s):
+    NP, cap = g.num_patches, g.lod_row_capacity()
+    A = np.zeros((NP * s, NP * s))
+    v = values.reshape(NP, cap, s, s)
+    c = cols.reshape(NP, cap)
+    for p in range(NP):
+        for j in range(cap):
+            if c[p, j] != 0xffffffff:
+                q = int(c[p, j])
+                A[p * s:(p + 1) * s, q * s:(q + 1) * s] = v[p, j]
+    return A
+
+
+def _lod_matrix(g, basis_t, premult_t, stride, s):
+    torch, dev = _torch()
+    NP, cap = g.num_patches, g.lod_row_capacity()
+    values = torch.zeros(NP * cap * s * s, dtype=torch.float64, device=dev)
+    cols = torch.zeros(NP * cap, dtype=torch.int32, device=dev)
+    g.lod_matrix(np.arange(NP), basis_t.data_ptr(), premult_t.data_ptr(), stride, values.data_ptr(), cols.data_ptr())
+    torch.cuda.synchronize()
+    return values, cols
+
+
+def _fem_reference(NE, s, fields, fq=None):
+    """Global fine stiffness and load vector with scipy (element matrices of oracle/slod_numpy.py),
+    Dirichlet rows/columns removed; returns (A_II, f_I, interior index array)."""
+    import scipy.sparse as sp
+    import slod_numpy as sn
+    NEp = NE + 1
+    rows, cols, vals = [], [], []
+    f = np.zeros(NEp * NEp * s)
+    hf = 1.0 / NE
+    g = (sn.G0, sn.G1)
+    for ey in range(NE):
+        for ex in range(NE):
+            ge = (ey * NE + ex) * 4
+            K = sn.element_matrix(s, [fld[ge:ge + 4] for fld in fields])
+            nodes = [ex + ey * NEp, ex + 1 + ey * NEp, ex + (ey + 1) * NEp, ex + 1 + (ey + 1) * NEp]
+            dofs = [nd * s + c for nd in nodes for c in range(s)]
+            for i, di in enumerate(dofs):
+                for j, dj in enumerate(dofs):
+                    rows.append(di), cols.append(dj), vals.append(K[i, j])
+            for a, nd in enumerate(nodes):
+                for q in range(4):
+                    xi, eta = g[q & 1], g[(q >> 1) & 1]
+                    N = (xi if a & 1 else 1 - xi) * (eta if a & 2 else 1 - eta)
+                    for c in range(s):
+                        fv = 1.0 if fq is None else fq[c * NE * NE * 4 + ge + q]
+                        f[nd * s + c] += N * fv * hf * hf * 0.25
+    A = sp.csr_matrix((vals, (rows, cols)), shape=(NEp * NEp * s, NEp * NEp * s))
+    ix, iy = np.meshgrid(np.arange(NEp), np.arange(NEp))
+    interior = ((ix > 0) & (ix < NE) & (iy > 0) & (iy < NE)).ravel()
+    idx = np.nonzero(np.repeat(interior, s))[0]
+    return A[idx][:, idx].tocsc(), f[idx], idx
+
+
+def _gauss():
+    g0 = 0.5 * (1.0 - 1.0 / np.sqrt(3.0))
+    return (g0, 1.0 - g0)
+
+
+def _exact_at_qp(NE):
+    """w = sin(pi x) sin(pi y), its gradient and f = 2 pi^2 w at the quadrature points (layout 1)."""
+    g = _gauss()
+    h = 1.0 / NE
+    ey, ex, q = np.meshgrid(np.arange(NE), np.arange(NE), np.arange(4), indexing="ij")
+    x = (ex + np.where(q & 1, g[1], g[0])) * h
+    y = (ey + np.where(q & 2, g[1], g[0])) * h
+    w = np.sin(np.pi * x) * np.sin(np.pi * y)
+    wx = np.pi * np.cos(np.pi * x) * np.sin(np.pi * y)
+    wy = np.pi * np.sin(np.pi * x) * np.cos(np.pi * y)
+    return w.ravel(), np.concatenate([wx.ravel(), wy.ravel()]), (2 * np.pi ** 2 * w).ravel()
+
+
+def _mass_fine(NE, rho=None):
+    """Consistent Q1 mass of the global fine grid, dense [(NE+1)^2]^2, element matrix rho_e h^2/36 [[4,2,2,1],...]."""
+    NEp, h = NE + 1, 1.0 / NE
+    Me = np.array([[4, 2, 2, 1], [2, 4, 1, 2], [2, 1, 4, 2], [1, 2, 2, 4]], dtype=np.float64) * (h * h / 36.0)
+    M = np.zeros((NEp * NEp, NEp * NEp))
+    for ey in range(NE):
+        for ex in range(NE):
+            nodes = np.array([ex + ey * NEp, ex + 1 + ey * NEp, ex + (ey + 1) * NEp, ex + 1 + (ey + 1) * NEp])
+            M[np.ix_(nodes, nodes)] += Me * (1.0 if rho is None else rho[ey * NE + ex])
+    return M
+
+
+class _Case:
+    pass
+
+
+def _build(so, kw, dist="D100", fields=None):
+    """Handle, basis slab, premultiplied slab and the stiffness block rows of one configuration."""
+    torch, dev = _torch()
+    c = _Case()
+    c.kw, c.s = kw, kw.get("spacedim", 1)
+    cfg, g = _mk(so, stabilize=1, **kw)
+    _upload(g, fields if fields is not None else make_fields(so, cfg, dist))
+    c.g, c.ids = g, np.arange(g.num_patches, dtype=np.uint32)
+    plan = g.plan(c.ids)
+    c.stride = plan.stride
+    c.b = torch.zeros(len(c.ids) * c.stride, dtype=torch.float64, device=dev)
+    c.q = torch.zeros_like(c.b)
+    plan.execute(c.b.data_ptr(), c.q.data_ptr())
+    plan.status()
+    c.values, c.cols = _lod_matrix(g, c.b, c.q, c.stride, c.s)
+    c.nrow = g.num_patches * c.s
+    return c
+
+
+def _mass(c, rho_t=None, basis=None):
+    torch, dev = _torch()
+    NP, cap, s = c.g.num_patches, c.g.lod_row_capacity(), c.s
+    values = torch.full((NP * cap * s * s,), NAN, dtype=torch.float64, device=dev)
+    cols = torch.zeros(NP * cap, dtype=torch.int32, device=dev)
+    c.g.lod_mass_matrix(c.ids, (c.b if basis is None else basis).data_ptr(), c.stride, values.data_ptr(), cols.data_ptr(),
+                        d_rho=None if rho_t is None else rho_t.data_ptr())
+    torch.cuda.synchronize()
+    return values, cols
+
+
+def _apply(c, values, X, n_rhs, ld_x=None, ld_y=None, first=0):
+    torch, dev = _torch()
+    ld_y = n_rhs if ld_y is None else ld_y
+    Y = torch.full((c.nrow, ld_y), NAN, dtype=torch.float64, device=dev)
+    c.g.lod_apply(values.data_ptr(), c.cols.data_ptr(), X.data_ptr() + 8 * first, Y.data_ptr(), n_rhs=n_rhs,
+                  ld_x=X.shape[1] if ld_x is None else ld_x, ld_y=ld_y)
+    torch.cuda.synchronize()
+    return Y
+
+
+PENCIL_CONFIGS = dict(MASS_CONFIGS,
+                      step64=dict(nref=3, n_sub=2, oversampling=1, spacedim=1),   # 64 rows: the cap on the block columns
+                      const=dict(nref=2, n_sub=4, oversampling=2, spacedim=1))    # coefficient 1: lambda_2 = lambda_3
+_cache = {}
+
+
+def _symmetrize(c):
+    torch, dev = _torch()
+    out = torch.full_like(c.values, NAN)
+    c.g.lod_matrix_symmetrize(c.values.data_ptr(), c.cols.data_ptr(), out.data_ptr())
+    torch.cuda.synchronize()
+    return out
+
+
+def _pencil(so, name):
+    """Block rows of sym(A_LOD) and M_LOD of one configuration, dense copies, and the dense spectrum; built once."""
+    import scipy.linalg as sl
+    if name not in _cache:
+        c = _build(so, PENCIL_CONFIGS[name], dist="const" if name == "const" else "D100")
+        c.mvalues, _ = _mass(c)
+        c.sym = _symmetrize(c)
+        hc = c.cols.cpu().numpy().view(np.uint32)
+        c.A = _rows_to_dense(c.g, c.sym.cpu().numpy(), hc, c.s)
+        c.M = _rows_to_dense(c.g, c.mvalues.cpu().numpy(), hc, c.s)
+        assert np.array_equal(c.A, c.A.T) and np.array_equal(c.M, c.M.T)
+        c.lam, c.vec = sl.eigh(c.A, c.M)                   # vec^T M vec = I
+        _cache[name] = c
+    return _cache[name]

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import make_fields
-from test_gpu_parity import TOL_PHI, _mk, _upload
+from lod_cases import TOL_PHI, _mk, _upload
 
 pytestmark = pytest.mark.gpu
 

@@ -8,8 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import SEED, make_fields
-from test_gpu_lod_system import _lod_matrix, _torch
-from test_gpu_parity import _mk, _upload
+from lod_cases import _lod_matrix, _mk, _torch, _upload
 
 pytestmark = pytest.mark.gpu
 

@@ -23,8 +23,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
-from test_gpu_error_norms import _exact_at_qp
-from test_gpu_lod_system import _lod_matrix
+from lod_cases import _exact_at_qp, _lod_matrix, _torch
 
 pytestmark = pytest.mark.gpu
 
@@ -35,11 +34,6 @@ FEM_SOLVE_RTOL = 1e-8                       # test_fem_solve_matches_sparse_dire
 L2_RATE, H1_RATE = (3.6, 4.4), (1.8, 2.2)   # test_fem_error_against_exact_solution_converges
 G0 = 0.5 * (1.0 - 1.0 / np.sqrt(3.0))
 GP = (G0, 1.0 - G0)
-
-
-def _torch():
-    import torch
-    return torch, torch.device("cuda", 0)
 
 
 def _slod(**kw):

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, make_fields
-from test_gpu_parity import TOL_PHI, _check_patch, _mk, _upload
+from lod_cases import TOL_PHI, _check_patch, _decisions, _mk, _upload
 
 pytestmark = pytest.mark.gpu
 
@@ -316,20 +316,6 @@ def test_selection_decisions_match_oracle(so, kw, dist):
         if dg[k].path == 1:   # proven decision-free: the oracle agrees
             assert d0.n_cut[0] == 0 and d0.n_dropped[0] == 0
     print("%s %s: %d of %d patches replayed the truncation loop" % (kw, dist, n_path2, len(ids)))
-
-
-
-def _decisions(g, ids, offs):
-    """slod_plan_diagnostics of the same patches (plan path; outputs must equal the host-buffer path)"""
-    import torch
-    plan = g.plan(ids, offs)
-    dev = torch.device("cuda", 0)
-    b = torch.zeros(max(plan.output_size, 1), dtype=torch.float64, device=dev)
-    q = torch.zeros_like(b)
-    plan.execute(b.data_ptr(), q.data_ptr())
-    torch.cuda.synchronize()
-    plan.status()
-    return plan.diagnostics()
 
 
 def test_c3_patch_shapes(so):

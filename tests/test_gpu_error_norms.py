@@ -10,23 +10,12 @@ import numpy as np
 import pytest
 
 from conftest import make_fields
-from test_gpu_lod_system import _fem_reference, _lod_matrix
-from test_gpu_parity import _mk, _upload
+from lod_cases import _exact_at_qp, _fem_reference, _gauss, _lod_matrix, _mk, _torch, _upload
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "dealii-slod_amd", "bin", "main_Diffusion")
-
-
-def _torch():
-    import torch
-    return torch, torch.device("cuda", 0)
-
-
-def _gauss():
-    g0 = 0.5 * (1.0 - 1.0 / np.sqrt(3.0))
-    return (g0, 1.0 - g0)
 
 
 def _np_norms(NE, s, e, fields, wq=None, wg=None):
@@ -139,19 +128,6 @@ def test_error_norms_need_the_coefficient(so):
     assert e.value.code == -4
     _upload(g, make_fields(so, cfg, "D100"))
     assert g.error_norms(u.data_ptr())["energy"] == 0.0
-
-
-def _exact_at_qp(NE):
-    """w = sin(pi x) sin(pi y), its gradient and f = 2 pi^2 w at the quadrature points (layout 1)."""
-    g = _gauss()
-    h = 1.0 / NE
-    ey, ex, q = np.meshgrid(np.arange(NE), np.arange(NE), np.arange(4), indexing="ij")
-    x = (ex + np.where(q & 1, g[1], g[0])) * h
-    y = (ey + np.where(q & 2, g[1], g[0])) * h
-    w = np.sin(np.pi * x) * np.sin(np.pi * y)
-    wx = np.pi * np.cos(np.pi * x) * np.sin(np.pi * y)
-    wy = np.pi * np.sin(np.pi * x) * np.cos(np.pi * y)
-    return w.ravel(), np.concatenate([wx.ravel(), wy.ravel()]), (2 * np.pi ** 2 * w).ravel()
 
 
 def test_fem_error_against_exact_solution_converges(so):

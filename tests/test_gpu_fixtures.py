@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 
 from fixture_utils import fixtures, global_fields, tolerances
-from test_gpu_parity import _mk
+from lod_cases import _mk
 
 pytestmark = pytest.mark.gpu
 

@@ -22,8 +22,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_gpu_lod_system import _fem_reference
-from test_gpu_lod_time import MASS_CONFIGS, _bits, _build, _mass, _mass_fine, _rows_to_dense, _torch
+from lod_cases import _bits, _build, _fem_reference, _mass, _mass_fine, _pencil, _rows_to_dense, _symmetrize, _torch
 
 pytestmark = pytest.mark.gpu
 
@@ -32,34 +31,6 @@ BIN = os.path.join(ROOT, "dealii-slod_amd", "bin", "main_Diffusion")
 UNUSED = 0xffffffff
 NAN = float("nan")
 TOL = 1e-10
-CONFIGS = dict(MASS_CONFIGS,
-               step64=dict(nref=3, n_sub=2, oversampling=1, spacedim=1),      # 64 rows: the cap on the block columns
-               const=dict(nref=2, n_sub=4, oversampling=2, spacedim=1))       # coefficient 1: lambda_2 = lambda_3
-_cache = {}
-
-
-def _symmetrize(c):
-    torch, dev = _torch()
-    out = torch.full_like(c.values, NAN)
-    c.g.lod_matrix_symmetrize(c.values.data_ptr(), c.cols.data_ptr(), out.data_ptr())
-    torch.cuda.synchronize()
-    return out
-
-
-def _pencil(so, name):
-    """Block rows of sym(A_LOD) and M_LOD of one configuration, dense copies, and the dense spectrum; built once."""
-    import scipy.linalg as sl
-    if name not in _cache:
-        c = _build(so, CONFIGS[name], dist="const" if name == "const" else "D100")
-        c.mvalues, _ = _mass(c)
-        c.sym = _symmetrize(c)
-        hc = c.cols.cpu().numpy().view(np.uint32)
-        c.A = _rows_to_dense(c.g, c.sym.cpu().numpy(), hc, c.s)
-        c.M = _rows_to_dense(c.g, c.mvalues.cpu().numpy(), hc, c.s)
-        assert np.array_equal(c.A, c.A.T) and np.array_equal(c.M, c.M.T)
-        c.lam, c.vec = sl.eigh(c.A, c.M)                   # vec^T M vec = I
-        _cache[name] = c
-    return _cache[name]
 
 
 def _eigs(c, n_eig, m, start=0, X=None, ld=None, **kw):

@@ -23,8 +23,7 @@ import numpy as np
 import pytest
 
 from conftest import make_fields
-from test_gpu_lod_system import _global_dense, _lod_matrix, _rows_to_dense
-from test_gpu_parity import _mk, _upload
+from lod_cases import _Case, _bits, _global_dense, _lod_matrix, _mk, _rows_to_dense, _torch, _upload
 
 pytestmark = pytest.mark.gpu
 
@@ -36,11 +35,6 @@ CONFIGS = {"P": dict(nref=3, n_sub=4, oversampling=1, spacedim=1),
            "E": dict(nref=4, n_sub=4, oversampling=1, spacedim=2)}
 REL_TOL = 1e-12
 NAN = float("nan")
-
-
-def _torch():
-    import torch
-    return torch, torch.device("cuda", 0)
 
 
 def _qp_coordinates(NE):
@@ -69,10 +63,6 @@ def _loads(NE, s):
     f[SCALED] = f[RANDOM] * 2.0 ** 20
     f[COMBO] = 2.0 * f[SINE0] - 3.0 * f[SINE0 + 1]
     return f
-
-
-class _Case:
-    pass
 
 
 @pytest.fixture(scope="module", params=sorted(CONFIGS))
@@ -125,10 +115,6 @@ def _solve(c, B, n_rhs, ld_u, rel_tol=REL_TOL, max_iterations=5000, first=0, fil
                                        its.ctypes.data_as(C.POINTER(C.c_int)), res.ctypes.data_as(C.POINTER(C.c_double)))
     assert ret >= 0, c.g.lib.slod_last_error(c.g.h).decode()
     return U, its, res, ret
-
-
-def _bits(t):
-    return t.contiguous().cpu().numpy().view(np.uint64)
 
 
 def _nonzero():

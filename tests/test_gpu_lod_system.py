@@ -14,56 +14,9 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, make_fields
-from test_gpu_parity import _mk, _upload
+from lod_cases import _fem_reference, _global_dense, _lod_matrix, _mk, _rows_to_dense, _torch, _upload
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch():
-    import torch
-    return torch, torch.device("cuda", 0)
-
-
-def _global_dense(g, cfg_s, basis, premult, stride):
-    """Scatter every patch vector to the global fine grid: (N_patches*s) x (NEp^2 * s) dense arrays."""
-    s, n, NP = cfg_s, g.cfg.n_subdivisions, g.num_patches
-    NEp = g.NE + 1
-    Phi = np.zeros((NP * s, NEp * NEp * s))
-    Psi = np.zeros_like(Phi)
-    for p in range(NP):
-        info = g.patch_layout(p)
-        nxp, nyp = info.nx + 1, info.ny + 1
-        for d in range(s):
-            vphi = basis[p * stride + d * info.n_fine:p * stride + (d + 1) * info.n_fine].reshape(nyp, nxp, s)
-            vpsi = premult[p * stride + d * info.n_fine:p * stride + (d + 1) * info.n_fine].reshape(nyp, nxp, s)
-            G1 = Phi[p * s + d].reshape(NEp, NEp, s)
-            G2 = Psi[p * s + d].reshape(NEp, NEp, s)
-            G1[info.y0 * n:info.y0 * n + nyp, info.x0 * n:info.x0 * n + nxp, :] = vphi
-            G2[info.y0 * n:info.y0 * n + nyp, info.x0 * n:info.x0 * n + nxp, :] = vpsi
-    return Phi, Psi
-
-
-def _rows_to_dense(g, values, cols, s):
-    NP, cap = g.num_patches, g.lod_row_capacity()
-    A = np.zeros((NP * s, NP * s))
-    v = values.reshape(NP, cap, s, s)
-    c = cols.reshape(NP, cap)
-    for p in range(NP):
-        for j in range(cap):
-            if c[p, j] != 0xffffffff:
-                q = int(c[p, j])
-                A[p * s:(p + 1) * s, q * s:(q + 1) * s] = v[p, j]
-    return A
-
-
-def _lod_matrix(g, basis_t, premult_t, stride, s):
-    torch, dev = _torch()
-    NP, cap = g.num_patches, g.lod_row_capacity()
-    values = torch.zeros(NP * cap * s * s, dtype=torch.float64, device=dev)
-    cols = torch.zeros(NP * cap, dtype=torch.int32, device=dev)
-    g.lod_matrix(np.arange(NP), basis_t.data_ptr(), premult_t.data_ptr(), stride, values.data_ptr(), cols.data_ptr())
-    torch.cuda.synchronize()
-    return values, cols
 
 
 def test_parallel_assembly_golden(so):
@@ -295,38 +248,6 @@ def test_execute_allgather_single_rank(so, n_pieces):
 
 
 # ---- fine FEM reference problem (assemble_and_solve_fem_problem, LOD.cc:1004-1094)
-
-def _fem_reference(NE, s, fields, fq=None):
-    """Global fine stiffness and load vector with scipy (element matrices of oracle/slod_numpy.py),
-    Dirichlet rows/columns removed; returns (A_II, f_I, interior index array)."""
-    import scipy.sparse as sp
-    import slod_numpy as sn
-    NEp = NE + 1
-    rows, cols, vals = [], [], []
-    f = np.zeros(NEp * NEp * s)
-    hf = 1.0 / NE
-    g = (sn.G0, sn.G1)
-    for ey in range(NE):
-        for ex in range(NE):
-            ge = (ey * NE + ex) * 4
-            K = sn.element_matrix(s, [fld[ge:ge + 4] for fld in fields])
-            nodes = [ex + ey * NEp, ex + 1 + ey * NEp, ex + (ey + 1) * NEp, ex + 1 + (ey + 1) * NEp]
-            dofs = [nd * s + c for nd in nodes for c in range(s)]
-            for i, di in enumerate(dofs):
-                for j, dj in enumerate(dofs):
-                    rows.append(di), cols.append(dj), vals.append(K[i, j])
-            for a, nd in enumerate(nodes):
-                for q in range(4):
-                    xi, eta = g[q & 1], g[(q >> 1) & 1]
-                    N = (xi if a & 1 else 1 - xi) * (eta if a & 2 else 1 - eta)
-                    for c in range(s):
-                        fv = 1.0 if fq is None else fq[c * NE * NE * 4 + ge + q]
-                        f[nd * s + c] += N * fv * hf * hf * 0.25
-    A = sp.csr_matrix((vals, (rows, cols)), shape=(NEp * NEp * s, NEp * NEp * s))
-    ix, iy = np.meshgrid(np.arange(NEp), np.arange(NEp))
-    interior = ((ix > 0) & (ix < NE) & (iy > 0) & (iy < NE)).ravel()
-    idx = np.nonzero(np.repeat(interior, s))[0]
-    return A[idx][:, idx].tocsc(), f[idx], idx
 
 
 def test_fem_rhs_matches_example_golden(so):

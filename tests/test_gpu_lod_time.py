@@ -22,8 +22,8 @@ import numpy as np
 import pytest
 
 from conftest import make_fields
-from test_gpu_lod_system import _fem_reference, _global_dense, _lod_matrix, _rows_to_dense
-from test_gpu_parity import _mk, _upload
+from lod_cases import (MASS_CONFIGS, _Case, _apply, _bits, _build, _fem_reference, _global_dense, _mass, _mass_fine, _mk,
+                       _rows_to_dense, _torch)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,65 +31,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "dealii-slod_amd", "bin", "main_Diffusion")
 UNUSED = 0xffffffff
 NAN = float("nan")
-MASS_CONFIGS = {"s1": dict(nref=2, n_sub=2, oversampling=1, spacedim=1),
-                "clipped": dict(nref=2, n_sub=4, oversampling=2, spacedim=1),
-                "s2": dict(nref=2, n_sub=2, oversampling=1, spacedim=2),
-                "rowmajor": dict(n_cells=5, n_sub=3, oversampling=1, spacedim=1)}
-
-
-def _torch():
-    import torch
-    return torch, torch.device("cuda", 0)
-
-
-def _bits(t):
-    return t.contiguous().cpu().numpy().view(np.uint64)
-
-
-def _mass_fine(NE, rho=None):
-    """Consistent Q1 mass of the global fine grid, dense [(NE+1)^2]^2, element matrix rho_e h^2/36 [[4,2,2,1],...]."""
-    NEp, h = NE + 1, 1.0 / NE
-    Me = np.array([[4, 2, 2, 1], [2, 4, 1, 2], [2, 1, 4, 2], [1, 2, 2, 4]], dtype=np.float64) * (h * h / 36.0)
-    M = np.zeros((NEp * NEp, NEp * NEp))
-    for ey in range(NE):
-        for ex in range(NE):
-            nodes = np.array([ex + ey * NEp, ex + 1 + ey * NEp, ex + (ey + 1) * NEp, ex + 1 + (ey + 1) * NEp])
-            M[np.ix_(nodes, nodes)] += Me * (1.0 if rho is None else rho[ey * NE + ex])
-    return M
-
-
-class _Case:
-    pass
-
-
-def _build(so, kw, dist="D100", fields=None):
-    """Handle, basis slab, premultiplied slab and the stiffness block rows of one configuration."""
-    torch, dev = _torch()
-    c = _Case()
-    c.kw, c.s = kw, kw.get("spacedim", 1)
-    cfg, g = _mk(so, stabilize=1, **kw)
-    _upload(g, fields if fields is not None else make_fields(so, cfg, dist))
-    c.g, c.ids = g, np.arange(g.num_patches, dtype=np.uint32)
-    plan = g.plan(c.ids)
-    c.stride = plan.stride
-    c.b = torch.zeros(len(c.ids) * c.stride, dtype=torch.float64, device=dev)
-    c.q = torch.zeros_like(c.b)
-    plan.execute(c.b.data_ptr(), c.q.data_ptr())
-    plan.status()
-    c.values, c.cols = _lod_matrix(g, c.b, c.q, c.stride, c.s)
-    c.nrow = g.num_patches * c.s
-    return c
-
-
-def _mass(c, rho_t=None, basis=None):
-    torch, dev = _torch()
-    NP, cap, s = c.g.num_patches, c.g.lod_row_capacity(), c.s
-    values = torch.full((NP * cap * s * s,), NAN, dtype=torch.float64, device=dev)
-    cols = torch.zeros(NP * cap, dtype=torch.int32, device=dev)
-    c.g.lod_mass_matrix(c.ids, (c.b if basis is None else basis).data_ptr(), c.stride, values.data_ptr(), cols.data_ptr(),
-                        d_rho=None if rho_t is None else rho_t.data_ptr())
-    torch.cuda.synchronize()
-    return values, cols
 
 
 def _rho(NE):
@@ -187,16 +128,6 @@ def step_case(so):
     M = _rows_to_dense(c.g, c.mvalues.cpu().numpy(), hc, 1)
     c.A, c.M = 0.5 * (A + A.T), 0.5 * (M + M.T)
     return c
-
-
-def _apply(c, values, X, n_rhs, ld_x=None, ld_y=None, first=0):
-    torch, dev = _torch()
-    ld_y = n_rhs if ld_y is None else ld_y
-    Y = torch.full((c.nrow, ld_y), NAN, dtype=torch.float64, device=dev)
-    c.g.lod_apply(values.data_ptr(), c.cols.data_ptr(), X.data_ptr() + 8 * first, Y.data_ptr(), n_rhs=n_rhs,
-                  ld_x=X.shape[1] if ld_x is None else ld_x, ld_y=ld_y)
-    torch.cuda.synchronize()
-    return Y
 
 
 @pytest.mark.parametrize("which", ["step", "s2"])

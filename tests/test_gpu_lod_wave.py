@@ -29,9 +29,7 @@ import numpy as np
 import pytest
 
 from conftest import make_fields
-from test_gpu_lod_eig import _pencil, _symmetrize
-from test_gpu_lod_system import _fem_reference
-from test_gpu_lod_time import _apply, _bits, _build, _mass, _mass_fine, _torch
+from lod_cases import _apply, _bits, _build, _fem_reference, _mass, _mass_fine, _pencil, _symmetrize, _torch
 
 pytestmark = pytest.mark.gpu
 

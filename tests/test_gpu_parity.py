@@ -9,42 +9,9 @@ import numpy as np
 import pytest
 
 from conftest import make_fields
+from lod_cases import _check_patch, _mk, _upload
 
 pytestmark = pytest.mark.gpu
-
-TOL_PHI = 1e-10
-
-
-def _mk(so, **kw):
-    import slod_amd
-    cfg = so.make_cfg(**kw)
-    g = slod_amd.Slod(nref=kw.get("nref", 0), n_sub=kw["n_sub"], oversampling=kw["oversampling"],
-                      spacedim=kw.get("spacedim", 1), stabilize=kw.get("stabilize", 1),
-                      reuse_full=kw.get("reuse_full", 0), proj_quirk=kw.get("proj_quirk", 0),
-                      n_cells=kw.get("n_cells", 0))
-    return cfg, g
-
-
-def _upload(g, fields):
-    for f, a in enumerate(fields):
-        g.set_coefficient(f, a)
-
-
-def _check_patch(so, cfg, fields, pid, basis, premult, off, label=""):
-    p = so.patch_info(cfg, pid)
-    s = cfg.spacedim
-    phi, psi, _ = so.patch_basis(cfg, fields, pid)
-    st = so.assemble_patch(cfg, fields, pid)
-    a_inf = np.abs(st).sum(axis=(1, 3)).max()
-    n = s * p.n_f
-    gphi = basis[off:off + n].reshape(s, p.n_f)
-    gpsi = premult[off:off + n].reshape(s, p.n_f)
-    ephi = np.abs(gphi - phi).max()
-    epsi = np.abs(gpsi - psi).max()
-    assert np.isfinite(gphi).all() and np.isfinite(gpsi).all(), label
-    assert ephi <= TOL_PHI, "%s patch %d: |dphi| = %.3e" % (label, pid, ephi)
-    assert epsi <= TOL_PHI * a_inf, "%s patch %d: |dpsi| = %.3e (tol %.3e)" % (label, pid, epsi, TOL_PHI * a_inf)
-    return ephi, epsi / a_inf
 
 
 def test_stencil_matches_oracle(so):

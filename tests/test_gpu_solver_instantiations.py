@@ -13,7 +13,7 @@ m_max = S * (min(mx, my) * n_sub - 1) over the plan's patches; tw takes T = the 
 
 Bars (the project's, flat -- every configuration here has oversampling <= 2 and is well conditioned: the
 oracle's spread under 1e-13 solver noise is at most 1.4e-11 on every patch, so.selection_conditioning):
-  |dphi| <= 1e-10, |dpsi| <= 1e-10 * ||A||_inf           test_gpu_parity._check_patch
+  |dphi| <= 1e-10, |dpsi| <= 1e-10 * ||A||_inf           lod_cases._check_patch
   (n_cut, n_dropped) equal to the oracle's               where the oracle's decisions are stable
   |dX| <= 1e-11 * max|X|                                 test_gpu_parity.test_patch_solution_matches_oracle
 """
@@ -23,8 +23,7 @@ import numpy as np
 import pytest
 
 from conftest import make_fields
-from test_gpu_elasticity_and_quirks import _decisions
-from test_gpu_parity import _check_patch, _mk, _upload
+from lod_cases import _check_patch, _decisions, _mk, _upload
 
 TOL_X = 1e-11
 
