@@ -1,6 +1,6 @@
 // Counterpart of reference app/main_Diffusion.cc for the basis-construction path:
 //   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare] [--coarse] [--loads K]
-//                  [--heat STEPS DT] [--eigs K] [--wave STEPS DT]
+//                  [--heat STEPS DT] [--eigs K] [--wave STEPS DT] [--ensemble K]
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
 // file name it dumps, per patch, phi and psi in patch-lexicographic order (parity tests).
 // --compare (anywhere on the command line): after run(), the rest of the reference run() -- global
@@ -21,6 +21,10 @@
 // steps of the trapezoidal rule (Newmark gamma = 1/2, beta = 1/4, slod_lod_newmark_steps): one line per step with its
 // iterations, relative residual, kinetic and potential energy and the work u^T b (kinetic + potential = work from rest
 // under a constant load), then the fine-grid L2 norm of the reconstructed final state.
+// --ensemble K: K realisations of the run's random coefficient (member 0 is the coefficient of a run without the flag,
+// the others are drawn after it), f = 1: one plan for all K * patches bases, then the K LOD systems in one call per step
+// (slod_lod_matrix_ensemble, _rhs_, _solve_, _reconstruct_ensemble, slod_ensemble_moments): one line per member with its
+// iterations and relative residual, then the fine-grid L2 norms of the mean and of the standard deviation.
 #include "../host/Diffusion.h"
 
 #include <cstdio>
@@ -74,7 +78,7 @@ int main(int argc_all, char **argv_all)
 {
   // --compare and --coarse are taken out wherever they stand; the positional arguments keep their meaning
   bool               compare = false, coarse = false;
-  int                n_loads = 0, heat_steps = 0, n_eigs = 0, wave_steps = 0;
+  int                n_loads = 0, heat_steps = 0, n_eigs = 0, wave_steps = 0, n_members = 0;
   double             heat_dt = 0.0, wave_dt = 0.0;
   std::vector<char *> args;
   for (int i = 0; i < argc_all; ++i)
@@ -96,6 +100,8 @@ int main(int argc_all, char **argv_all)
         wave_steps = std::atoi(argv_all[++i]);
         wave_dt    = std::atof(argv_all[++i]);
       }
+    else if (i > 0 && !std::strcmp(argv_all[i], "--ensemble") && i + 1 < argc_all)
+      n_members = std::atoi(argv_all[++i]);
     else
       args.push_back(argv_all[i]);
   const int argc = (int)args.size();
@@ -108,6 +114,7 @@ int main(int argc_all, char **argv_all)
       par.oversampling          = argc > 3 ? std::atoi(argv[3]) : 1;
       par.LOD_stabilization     = argc > 4 ? std::atoi(argv[4]) != 0 : true;
       par.constant_coefficients = false;
+      par.n_members             = n_members > 0 ? (unsigned int)n_members : 1u;
       std::srand(1);
       Problem problem(par, 1, 100, 3);
       problem.run();
@@ -227,6 +234,15 @@ int main(int argc_all, char **argv_all)
                         k + 1, problem.wave_iterations()[k], problem.wave_rel_residuals()[k], problem.wave_kinetic()[k + 1],
                         problem.wave_potential()[k + 1], problem.wave_work()[k + 1]);
           std::printf("SLOD wave at T = %g: L2 norm = %.12e\n", wave_steps * wave_dt, problem.norms_wave().l2[0]);
+        }
+      if (n_members > 0)
+        {
+          problem.solve_ensemble();
+          for (int k = 0; k < n_members; ++k)
+            std::printf("member %d: iterations = %d, relative residual = %.6e\n", k, problem.ensemble_iterations()[k],
+                        problem.ensemble_rel_residuals()[k]);
+          std::printf("SLOD ensemble of %d: L2 norm of the mean = %.12e, of the standard deviation = %.12e\n", n_members,
+                      problem.norms_ensemble_mean().l2[0], problem.norms_ensemble_deviation().l2[0]);
         }
     }
   catch (std::exception &exc)

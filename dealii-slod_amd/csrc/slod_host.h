@@ -179,12 +179,14 @@ struct SlodLodWork
     carve(hand);
     return hipSuccess;
   }
-  // the pieces of the solve, placed where the caller's carve calls it (slod_lod_multi.hip)
-  void take_solve(SlodCarver &c, const slod_handle *h);
+  // the pieces of the solve, placed where the caller's carve calls it (slod_lod_multi.hip).  matrix_per_column: for
+  // solves on an ensemble matrix (include/slod.h), which need D^-1 per column: nrow * n_rhs doubles more.
+  void take_solve(SlodCarver &c, const slod_handle *h, bool matrix_per_column = false);
   // A U = RHS for the n_rhs columns, every one from zero (slod_lod_multi.hip).  Arguments are checked by the caller; the
-  // handle's device is current.  Synchronises h->stream.
+  // handle's device is current.  Synchronises h->stream.  After take_solve(.., true) d_values is an ensemble matrix with
+  // leading dimension ld_m and column k is solved with matrix k; else ld_m is not used.
   hipError_t solve(slod_handle *h, const double *d_values, const uint32_t *d_cols, const double *d_rhs, size_t ld_rhs, double *d_u,
-                   size_t ld_u, double rel_tol, int max_iterations);
+                   size_t ld_u, double rel_tol, int max_iterations, size_t ld_m = 1);
   // what a time loop reports of step k, HOST arrays, either may be NULL: the maxima over the columns of the last solve
   void record(int k, int *iterations, double *rel_residual) const
   {
@@ -206,5 +208,6 @@ private:
   SlodDevBuf<double> work;
   SlodDevBuf<int>    active;
   double            *cg = nullptr; // the pieces of the solve
+  bool               per_col = false; // as given to take_solve
 };
 #endif

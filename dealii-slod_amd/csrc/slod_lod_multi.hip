@@ -11,6 +11,10 @@
 // The r.z partials are double-buffered by iteration parity, which replaces k_cg_rotate.  Every 8 iterations
 // k_mcg_check sums the r.r partials and freezes the columns that have converged (their u is not written
 // again); the host reads the flags back.
+//
+// PER_COL (slod_lod_solve_ensemble): column k reads a matrix of its own on the shared pattern, entry e at
+// values[e ld_m + k], and a D^-1 of its own.  The kernels that touch the matrix or D^-1 carry the parameter; the
+// recurrence, the tiling and every summation order are the same code.
 #include "slod_lod_tile.hip.h"
 
 #include <algorithm>
@@ -24,26 +28,33 @@ namespace
   struct McgVectors
   {
     double *r, *z, *p, *Ap; // [nrow][n_rhs]
-    double *dinv;           // [nrow]
+    double *dinv;           // [nrow], PER_COL: [nrow][n_rhs]
     double *pAp, *rz[2], *rr; // partials [ngroup][n_rhs]
     double *rhs2, *rr_last; // [n_rhs]
     int    *active;         // [n_rhs]
   };
 
-  __global__ void k_mcg_diag(int nrow, int s, int cap, const double *values, const uint32_t *cols, double *dinv)
+  template <bool PER_COL>
+  __global__ void k_mcg_diag(int nrow, int s, int cap, int n_rhs, const double *values, size_t ld_m, const uint32_t *cols,
+                             double *dinv)
   {
-    const int i = blockIdx.x * LOD_BLOCK + threadIdx.x;
-    if (i >= nrow)
+    const size_t w = (size_t)blockIdx.x * LOD_BLOCK + threadIdx.x; // PER_COL: (row, column), else the row
+    if (w >= (PER_COL ? (size_t)nrow * n_rhs : (size_t)nrow))
       return;
+    const int i = PER_COL ? (int)(w / n_rhs) : (int)w, col = PER_COL ? (int)(w - (size_t)i * n_rhs) : 0;
     const int p = i / s, d = i - p * s;
     double    diag = 1.0;
     for (int j = 0; j < cap; ++j)
       if (cols[(size_t)p * cap + j] == (uint32_t)p)
-        diag = values[((size_t)p * cap + j) * s * s + d * s + d];
-    dinv[i] = diag != 0.0 ? 1.0 / diag : 1.0;
+        {
+          const size_t e = ((size_t)p * cap + j) * s * s + d * s + d;
+          diag           = PER_COL ? values[e * ld_m + col] : values[e];
+        }
+    dinv[w] = diag != 0.0 ? 1.0 / diag : 1.0;
   }
 
   // x = 0, r = rhs, z = D^-1 r, p = z; partials of r.z (parity 0) and r.r
+  template <bool PER_COL>
   __global__ __launch_bounds__(LOD_BLOCK) void k_mcg_init(int nrow, int n_rhs, int ngroup, const double *rhs, size_t ld_rhs,
                                                          double *x, size_t ld_x, McgVectors V)
   {
@@ -58,7 +69,7 @@ namespace
             if (i < nrow)
               {
                 const size_t w = (size_t)i * n_rhs + col;
-                const double f = rhs[(size_t)i * ld_rhs + col], zi = V.dinv[i] * f;
+                const double f = rhs[(size_t)i * ld_rhs + col], zi = V.dinv[PER_COL ? w : (size_t)i] * f;
                 x[(size_t)i * ld_x + col] = 0.0;
                 V.r[w]                    = f;
                 V.z[w]                    = zi;
@@ -81,9 +92,10 @@ namespace
   }
 
   // Y = A P on the block rows for the active columns; partials of p.Ap
+  template <bool PER_COL>
   __global__ __launch_bounds__(LOD_BLOCK) void k_mcg_spmv(int nrow, int s, int cap, int NP, int n_rhs, int ngroup,
-                                                         const double *__restrict__ values, const uint32_t *__restrict__ cols,
-                                                         McgVectors V)
+                                                         const double *__restrict__ values, size_t ld_m,
+                                                         const uint32_t *__restrict__ cols, McgVectors V)
   {
     __shared__ double b_pAp[LOD_ROWS][LOD_COLS];
     const int c0 = blockIdx.y * LOD_COLS, nb = min(LOD_COLS, n_rhs - c0);
@@ -95,7 +107,7 @@ namespace
             double    prod = 0.0;
             if (i < nrow && V.active[col])
               {
-                const double acc = slod_lod_row_product(i, s, cap, NP, values, cols, V.p, (size_t)n_rhs, col);
+                const double acc = slod_lod_row_product<PER_COL>(i, s, cap, NP, values, cols, V.p, (size_t)n_rhs, col, ld_m);
                 const size_t w = (size_t)i * n_rhs + col;
                 V.Ap[w]        = acc;
                 prod           = acc * V.p[w];
@@ -111,6 +123,7 @@ namespace
 
   // alpha = r.z / p.Ap from the partials; x += alpha p, r -= alpha Ap, z = D^-1 r; partials of the new r.z
   // (parity par ^ 1) and of r.r
+  template <bool PER_COL>
   __global__ __launch_bounds__(LOD_BLOCK) void k_mcg_update_xr(int nrow, int n_rhs, int ngroup, int par, double *x, size_t ld_x,
                                                               McgVectors V)
   {
@@ -131,7 +144,7 @@ namespace
               {
                 const double pAp = s_sum[0][c], alpha = pAp != 0.0 ? s_sum[1][c] / pAp : 0.0;
                 const size_t w = (size_t)i * n_rhs + col, xi = (size_t)i * ld_x + col;
-                const double ri = fma(-alpha, V.Ap[w], V.r[w]), zi = V.dinv[i] * ri;
+                const double ri = fma(-alpha, V.Ap[w], V.r[w]), zi = V.dinv[PER_COL ? w : (size_t)i] * ri;
                 x[xi]  = fma(alpha, V.p[w], x[xi]);
                 V.r[w] = ri;
                 V.z[w] = zi;
@@ -189,26 +202,45 @@ namespace
   }
 } // namespace
 
-// The pieces of the workspace of one solve: 4 vectors, D^-1, 4 partial arrays, 2 per-column scalars.
-static McgVectors mcg_carve(SlodCarver &c, const LodShape &w, int n_rhs)
+// The pieces of the workspace of one solve: 4 vectors, D^-1 (per_col: one per column), 4 partial arrays, 2 per-column
+// scalars.
+static McgVectors mcg_carve(SlodCarver &c, const LodShape &w, int n_rhs, bool per_col)
 {
   const size_t nvec = (size_t)w.nrow * n_rhs, npart = (size_t)w.ngroup * n_rhs;
   McgVectors   V{};
   V.r = c.take(nvec), V.z = c.take(nvec), V.p = c.take(nvec), V.Ap = c.take(nvec);
-  V.dinv = c.take((size_t)w.nrow);
+  V.dinv = c.take(per_col ? nvec : (size_t)w.nrow);
   V.pAp = c.take(npart), V.rz[0] = c.take(npart), V.rz[1] = c.take(npart), V.rr = c.take(npart);
   V.rhs2 = c.take((size_t)n_rhs), V.rr_last = c.take((size_t)n_rhs); // read back in one copy
   return V;
 }
 
-void SlodLodWork::take_solve(SlodCarver &c, const slod_handle *h)
+void SlodLodWork::take_solve(SlodCarver &c, const slod_handle *h, bool matrix_per_column)
 {
-  cg = mcg_carve(c, lod_shape(h, (int)its.size()), (int)its.size()).r;
+  per_col = matrix_per_column;
+  cg      = mcg_carve(c, lod_shape(h, (int)its.size()), (int)its.size(), per_col).r;
 }
+
+namespace
+{
+  // The launches of one solve that touch the matrix or D^-1, for one value of PER_COL
+  struct McgKernels
+  {
+    decltype(&k_mcg_diag<false>)      diag;
+    decltype(&k_mcg_init<false>)      init;
+    decltype(&k_mcg_spmv<false>)      spmv;
+    decltype(&k_mcg_update_xr<false>) update_xr;
+  };
+  template <bool PER_COL>
+  constexpr McgKernels mcg_kernels()
+  {
+    return {k_mcg_diag<PER_COL>, k_mcg_init<PER_COL>, k_mcg_spmv<PER_COL>, k_mcg_update_xr<PER_COL>};
+  }
+} // namespace
 
 // The solve of slod_lod_solve_multi on a workspace the caller owns, so that a time loop allocates once.
 hipError_t SlodLodWork::solve(slod_handle *h, const double *d_values, const uint32_t *d_cols, const double *d_rhs, size_t ld_rhs,
-                              double *d_u, size_t ld_u, double rel_tol, int max_iterations)
+                              double *d_u, size_t ld_u, double rel_tol, int max_iterations, size_t ld_m)
 {
   hipStream_t    st = h->stream;
   const int      n_rhs = (int)its.size();
@@ -220,12 +252,14 @@ hipError_t SlodLodWork::solve(slod_handle *h, const double *d_values, const uint
   std::fill(its.begin(), its.end(), 0);
   int        it = 0;
   SlodCarver hand{cg};
-  McgVectors V = mcg_carve(hand, w, n_rhs);
+  McgVectors V = mcg_carve(hand, w, n_rhs, per_col);
+  const McgKernels K = per_col ? mcg_kernels<true>() : mcg_kernels<false>();
   V.active     = d_active;
   const double tol2 = rel_tol * rel_tol;
   const dim3   ncheck = lod_flat_grid((size_t)n_rhs);
-  hipLaunchKernelGGL(k_mcg_diag, lod_flat_grid((size_t)nrow), block, 0, st, nrow, s, cap, d_values, d_cols, V.dinv);
-  hipLaunchKernelGGL(k_mcg_init, grid, block, 0, st, nrow, n_rhs, ngroup, d_rhs, ld_rhs, d_u, ld_u, V);
+  hipLaunchKernelGGL(K.diag, lod_flat_grid(per_col ? (size_t)nrow * n_rhs : (size_t)nrow), block, 0, st, nrow, s, cap, n_rhs,
+                     d_values, ld_m, d_cols, V.dinv);
+  hipLaunchKernelGGL(K.init, grid, block, 0, st, nrow, n_rhs, ngroup, d_rhs, ld_rhs, d_u, ld_u, V);
   hipLaunchKernelGGL(k_mcg_check, ncheck, block, 0, st, n_rhs, ngroup, tol2, 1, V);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess)
@@ -241,8 +275,8 @@ hipError_t SlodLodWork::solve(slod_handle *h, const double *d_values, const uint
       for (int b = 0; b < burst; ++b)
         {
           const int par = (it + b) & 1;
-          hipLaunchKernelGGL(k_mcg_spmv, grid, block, 0, st, nrow, s, cap, NP, n_rhs, ngroup, d_values, d_cols, V);
-          hipLaunchKernelGGL(k_mcg_update_xr, grid, block, 0, st, nrow, n_rhs, ngroup, par, d_u, ld_u, V);
+          hipLaunchKernelGGL(K.spmv, grid, block, 0, st, nrow, s, cap, NP, n_rhs, ngroup, d_values, ld_m, d_cols, V);
+          hipLaunchKernelGGL(K.update_xr, grid, block, 0, st, nrow, n_rhs, ngroup, par, d_u, ld_u, V);
           hipLaunchKernelGGL(k_mcg_update_p, grid, block, 0, st, nrow, n_rhs, ngroup, par, V);
         }
       it += burst;

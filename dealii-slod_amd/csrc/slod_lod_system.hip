@@ -6,139 +6,34 @@
 // reductions (no MFMA shape in them); one wave per patch pair keeps every reduction inside a wave.
 #include "slod_host.h"
 #include "slod_cg.hip.h"
-#include "slod_grid.hip.h"
+#include "slod_lod_system.hip.h"
 
 #include <algorithm>
 #include <vector>
 
 namespace
 {
-  // ---------------------------------------------------------------------------------
-  // A_LOD block rows.  Block = one row patch p, wave w = the candidate neighbours j = w, w+4, ...
-  // (offsets of the centre cell in [-(2l+1), 2l+1]^2: patches further apart share no node).
-  // ---------------------------------------------------------------------------------
+  // The three kernels of one problem; their bodies are slod_lod_system.hip.h.  Block = one row patch.
   __global__ __launch_bounds__(256) void k_lod_matrix(const SlodGrid G, const uint32_t *rows, const double *basis,
                                                      const double *premult, size_t stride, double *values,
                                                      uint32_t *cols)
   {
-    const int      lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int      s = G.spacedim, n = G.n_sub, cap = grid_row_capacity(G);
-    const uint32_t p = rows[blockIdx.x];
-    int            pcx, pcy;
-    grid_centre(G, p, pcx, pcy);
-    const Extent  pe = grid_extent(G, pcx, pcy);
-    const int     pnx = pe.mx * n + 1, pny = pe.my * n + 1, pnf = s * pnx * pny;
-    const double *phi = basis + (size_t)p * stride;
-    for (int j = wave; j < cap; j += 4)
-      {
-        const size_t   out = (size_t)blockIdx.x * cap + j;
-        const PairGeom pg = grid_pair(G, pcx, pcy, pe, j);
-        const uint32_t q  = pg.q;
-        const Extent   qe = pg.qe;
-        const int      qnx = qe.mx * n + 1, qny = qe.my * n + 1, qnf = s * qnx * qny;
-        const int      xa = pg.xa, ya = pg.ya, w = pg.w, hgt = pg.hgt;
-        double    acc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
-        if (w > 0 && hgt > 0)
-          {
-            const double *psi = premult + (size_t)q * stride;
-            for (int idx = lane; idx < w * hgt; idx += 64)
-              {
-                const int iy = idx / w, ix = idx - iy * w;
-                const int np = (xa + ix - pe.x0 * n) + (ya + iy - pe.y0 * n) * pnx;
-                const int nq = (xa + ix - qe.x0 * n) + (ya + iy - qe.y0 * n) * qnx;
-                for (int c = 0; c < s; ++c)
-                  for (int d = 0; d < s; ++d)
-                    {
-                      const double ph = phi[(size_t)d * pnf + s * np + c];
-                      for (int e = 0; e < s; ++e)
-                        acc[d][e] = fma(ph, psi[(size_t)e * qnf + s * nq + c], acc[d][e]);
-                    }
-              }
-          }
-        for (int d = 0; d < s; ++d)
-          for (int e = 0; e < s; ++e)
-            {
-              double v = acc[d][e];
-              for (int off = 32; off > 0; off >>= 1)
-                v += __shfl_xor(v, off, 64);
-              if (lane == 0)
-                values[out * s * s + d * s + e] = v;
-            }
-        if (lane == 0)
-          cols[out] = pg.col();
-      }
+    lod_matrix_row(G, rows[blockIdx.x], blockIdx.x, basis, premult, stride, values, 1, cols);
   }
 
-  // C^T f for the row patches: block = one patch, all its nodes
   __global__ __launch_bounds__(256) void k_lod_rhs(const SlodGrid G, const uint32_t *rows, const double *basis,
                                                   size_t stride, const double *frhs, double *out)
   {
-    __shared__ double red[4][2];
-    const int         s = G.spacedim, n = G.n_sub, NEp = G.N * n + 1;
-    const uint32_t    p = rows[blockIdx.x];
-    int               pcx, pcy;
-    grid_centre(G, p, pcx, pcy);
-    const Extent  pe = grid_extent(G, pcx, pcy);
-    const int     pnx = pe.mx * n + 1, pny = pe.my * n + 1, pnf = s * pnx * pny;
-    const double *phi = basis + (size_t)p * stride;
-    double        acc[2] = {0.0, 0.0};
-    for (int node = threadIdx.x; node < pnx * pny; node += 256)
-      {
-        const int iy = node / pnx, ix = node - iy * pnx;
-        const int gn = (pe.x0 * n + ix) + (pe.y0 * n + iy) * NEp;
-        for (int c = 0; c < s; ++c)
-          {
-            const double f = frhs[(size_t)gn * s + c];
-            for (int d = 0; d < s; ++d)
-              acc[d] = fma(phi[(size_t)d * pnf + s * node + c], f, acc[d]);
-          }
-      }
-    for (int d = 0; d < s; ++d)
-      {
-        double v = acc[d];
-        for (int off = 32; off > 0; off >>= 1)
-          v += __shfl_xor(v, off, 64);
-        if ((threadIdx.x & 63) == 0)
-          red[threadIdx.x >> 6][d] = v;
-      }
-    __syncthreads();
-    if (threadIdx.x < s)
-      out[(size_t)blockIdx.x * s + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] +
-                                                  red[3][threadIdx.x];
+    lod_rhs_row(G, rows[blockIdx.x], blockIdx.x, basis, stride, frhs, out, 1);
   }
 
-  // u_fine = C u_H: one thread per global fine node, gather over the patches that contain it
+  // one thread per global fine node
   __global__ __launch_bounds__(256) void k_lod_reconstruct(const SlodGrid G, const double *basis, size_t stride,
                                                           const double *u, double *fine)
   {
-    const int s = G.spacedim, n = G.n_sub, NEp = G.N * n + 1, l = G.oversampling;
-    const int gn = blockIdx.x * 256 + threadIdx.x;
-    if (gn >= NEp * NEp)
-      return;
-    const int X = gn % NEp, Y = gn / NEp;
-    // cells whose closure contains the node, widened by the oversampling
-    const int cxl = max((X + n - 1) / n - 1 - l, 0), cxh = min(X / n + l, G.N - 1);
-    const int cyl = max((Y + n - 1) / n - 1 - l, 0), cyh = min(Y / n + l, G.N - 1);
-    double    acc[2] = {0.0, 0.0};
-    for (int cy = cyl; cy <= cyh; ++cy)
-      for (int cx = cxl; cx <= cxh; ++cx)
-        {
-          const Extent e = grid_extent(G, cx, cy);
-          const int    ix = X - e.x0 * n, iy = Y - e.y0 * n;
-          if (ix < 0 || ix > e.mx * n || iy < 0 || iy > e.my * n)
-            continue;
-          const uint32_t p   = grid_pid(G, cx, cy);
-          const int      pnx = e.mx * n + 1, pnf = s * pnx * (e.my * n + 1);
-          const double  *phi = basis + (size_t)p * stride;
-          for (int d = 0; d < s; ++d)
-            {
-              const double ud = u[(size_t)p * s + d];
-              for (int c = 0; c < s; ++c)
-                acc[c] = fma(phi[(size_t)d * pnf + s * (ix + iy * pnx) + c], ud, acc[c]);
-            }
-        }
-    for (int c = 0; c < s; ++c)
-      fine[(size_t)gn * s + c] = acc[c];
+    const int NEp = G.N * G.n_sub + 1, gn = blockIdx.x * 256 + threadIdx.x;
+    if (gn < NEp * NEp)
+      lod_reconstruct_node(G, gn, basis, stride, u, 1, fine);
   }
 
   // ---- the same two products for n_rhs load vectors at once (slod_lod_rhs_multi, slod_lod_reconstruct_multi).

@@ -33,14 +33,63 @@ namespace
 } // namespace
 
 // sum_j sum_e values[(p cap + j) s s + d s + e] x[(cols[p cap + j] s + e) ld + col] for row i = p s + d: one fma chain
-// over the slots of the row in ascending order
+// over the slots of the row in ascending order.
+// PER_COL: a matrix per column on the one pattern (the ensemble layout of include/slod.h), entry e of column col's matrix
+// at values[e ld_m + col].  The chain is the same, on other operands; the lanes of a wave, which hold consecutive columns
+// of one row, read 64 consecutive words where the shared matrix gives them one.  There every (row, column) streams its
+// own values, so the loads of LOD_SLOTS slots are issued before the first fma needs one (they do not depend on acc): a
+// wave otherwise waits out a memory latency per slot.
+constexpr int LOD_SLOTS = 8; // slots whose loads are in flight together in the PER_COL product
+
+template <int S> // S = s, a constant here so that nothing stands between the loads
+__device__ __forceinline__ double slod_lod_row_product_per_col(int p, int d, int cap, int NP, const double *__restrict__ values,
+                                                               size_t ld_m, const uint32_t *__restrict__ cols,
+                                                               const double *__restrict__ x, size_t ld, int col)
+{
+  const size_t slot0 = (size_t)p * cap;
+  double       acc = 0.0;
+  for (int j0 = 0; j0 < cap; j0 += LOD_SLOTS)
+    {
+      bool   used[LOD_SLOTS];
+      double a[LOD_SLOTS][S], xv[LOD_SLOTS][S];
+#pragma unroll
+      for (int u = 0; u < LOD_SLOTS; ++u)
+        {
+          // a slot past the end of the row reads the last one and adds nothing, like an unused slot
+          const int      j = min(j0 + u, cap - 1);
+          const uint32_t q = cols[slot0 + j];
+          used[u]          = q < (uint32_t)NP && j0 + u < cap;
+          const size_t qs = (size_t)(used[u] ? q : (uint32_t)p) * S, at = (slot0 + j) * S * S + d * S;
+#pragma unroll
+          for (int e = 0; e < S; ++e)
+            {
+              a[u][e]  = values[(at + e) * ld_m + col];
+              xv[u][e] = x[(qs + e) * ld + col];
+            }
+        }
+#pragma unroll
+      for (int u = 0; u < LOD_SLOTS; ++u)
+#pragma unroll
+        for (int e = 0; e < S; ++e)
+          {
+            const double t = fma(a[u][e], xv[u][e], acc);
+            acc            = used[u] ? t : acc;
+          }
+    }
+  return acc;
+}
+
+template <bool PER_COL = false>
 __device__ __forceinline__ double slod_lod_row_product(int i, int s, int cap, int NP, const double *__restrict__ values,
                                                        const uint32_t *__restrict__ cols, const double *__restrict__ x, size_t ld,
-                                                       int col)
+                                                       int col, size_t ld_m = 1)
 {
   const int    p = i / s, d = i - p * s;
   const size_t slot0 = (size_t)p * cap;
   double       acc = 0.0;
+  if constexpr (PER_COL)
+    return s == 1 ? slod_lod_row_product_per_col<1>(p, d, cap, NP, values, ld_m, cols, x, ld, col)
+                  : slod_lod_row_product_per_col<2>(p, d, cap, NP, values, ld_m, cols, x, ld, col);
   for (int j = 0; j < cap; ++j)
     {
       // an unused slot (0xffffffff; anything >= NP) reads the row's own patch and adds nothing:

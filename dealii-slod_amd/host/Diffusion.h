@@ -60,15 +60,26 @@ namespace slod
                      unsigned int r = 8)
       : LOD<dim, spacedim>(par)
       , Alpha(amin, amax, r)
-    {}
+    {
+      // further realisations of the same field for an ensemble, drawn after Alpha: member 0 is what a problem with
+      // one member has
+      for (unsigned int k = 1; k < par.n_members; ++k)
+        members.emplace_back(amin, amax, r);
+    }
 
   protected:
     problem_parameter<dim> Alpha; // reference: Alpha(1, 100, 8), Diffusion.h:62
+    std::vector<problem_parameter<dim>> members; // realisations 1 .. n_members-1
 
     void coefficients_at_quadrature_points(const unsigned int, const std::vector<Point<dim>> &points,
                                            std::vector<double> &values) override
     {
       Alpha.value_list(points, values); // Diffusion.h:154
+    }
+    void member_coefficients_at_quadrature_points(const unsigned int member, const unsigned int,
+                                                  const std::vector<Point<dim>> &points, std::vector<double> &values) override
+    {
+      members.at(member - 1).value_list(points, values);
     }
   };
 } // namespace slod

@@ -60,7 +60,7 @@ namespace slod
     cfg.lod_stabilization     = par.LOD_stabilization;
     cfg.constant_coefficients = par.constant_coefficients;
     cfg.projection_quirk      = par.projection_quirk;
-    cfg.n_problems            = 1;
+    cfg.n_problems            = (int32_t)par.n_members;
     cfg.device                = par.device;
     slod_handle *h            = nullptr;
     if (slod_create(&cfg, &h) != SLOD_OK)
@@ -370,6 +370,80 @@ namespace slod
                                        &lod_multi_fem_error[k], nullptr),
               "slod_compute_error_norms");
       }
+  }
+
+  // plan -> matrix -> load -> solve -> reconstruct -> moments for all members, everything on the device
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_ensemble()
+  {
+    const int          K = (int)par.n_members;
+    const unsigned int n_patches = (unsigned int)patches.size();
+    if (!handle || locally_owned_patches.first != 0 || locally_owned_patches.second != n_patches)
+      throw std::runtime_error("solve_ensemble: run() comes first, with every patch in this process");
+    const std::size_t NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+    const std::size_t fine_size = (NE + 1) * (NE + 1) * spacedim, n_coarse = (std::size_t)n_patches * spacedim;
+    // member 0 holds the coefficient of run(); the others are drawn now, at the same quadrature points
+    const double            hf = 1.0 / NE, g0 = 0.5 * (1.0 - 1.0 / std::sqrt(3.0)), g1 = 0.5 * (1.0 + 1.0 / std::sqrt(3.0));
+    std::vector<Point<dim>> points(NE * NE * 4);
+    for (std::size_t ey = 0; ey < NE; ++ey)
+      for (std::size_t ex = 0; ex < NE; ++ex)
+        for (unsigned int q = 0; q < 4; ++q)
+          {
+            Point<dim> &p = points[(ey * NE + ex) * 4 + q];
+            p(0)          = (ex + ((q & 1) ? g1 : g0)) * hf;
+            p(1)          = (ey + ((q & 2) ? g1 : g0)) * hf;
+          }
+    std::vector<double> values;
+    for (int k = 1; k < K; ++k)
+      for (unsigned int field = 0; field < (unsigned int)spacedim; ++field)
+        {
+          member_coefficients_at_quadrature_points((unsigned int)k, field, points, values);
+          check(slod_set_coefficient(handle, (uint32_t)k, (int)field, values.data(), 1, values.size(), 0), "slod_set_coefficient");
+        }
+    // one plan over gid = member * n_patches + patch: the ensemble slab, member k at k * n_patches * stride
+    std::vector<uint32_t> gids((std::size_t)K * n_patches);
+    for (std::size_t i = 0; i < gids.size(); ++i)
+      gids[i] = (uint32_t)i;
+    slod_plan *plan = nullptr;
+    check(slod_plan_create(handle, gids.data(), gids.size(), nullptr, &plan), "slod_plan_create");
+    const std::size_t stride = slod_plan_stride(plan), member_stride = n_patches * stride;
+    double           *d_b = device_alloc<double>(K * member_stride), *d_q = device_alloc<double>(K * member_stride);
+    int               rc = slod_plan_execute(plan, d_b, d_q, nullptr);
+    if (rc == SLOD_OK)
+      rc = slod_plan_status(plan);
+    slod_plan_destroy(plan);
+    check(rc, "slod_plan_execute");
+    const int cap = slod_lod_row_capacity(handle);
+    check(cap, "slod_lod_row_capacity");
+    double   *d_values = device_alloc<double>((std::size_t)n_patches * cap * spacedim * spacedim * K);
+    uint32_t *d_cols   = device_alloc<uint32_t>((std::size_t)n_patches * cap);
+    double   *d_load = device_alloc<double>(fine_size), *d_rhs = device_alloc<double>(n_coarse * K);
+    double   *d_u = device_alloc<double>(n_coarse * K), *d_fine = device_alloc<double>(fine_size * K);
+    double   *d_mean = device_alloc<double>(fine_size), *d_var = device_alloc<double>(fine_size);
+    check(slod_lod_matrix_ensemble(handle, d_b, d_q, stride, member_stride, K, d_values, (std::size_t)K, d_cols, nullptr),
+          "slod_lod_matrix_ensemble");
+    check(slod_fem_rhs(handle, nullptr, d_load, nullptr), "slod_fem_rhs");
+    check(slod_lod_rhs_ensemble(handle, d_b, stride, member_stride, K, d_load, 0, d_rhs, (std::size_t)K, nullptr),
+          "slod_lod_rhs_ensemble");
+    lod_ens_iterations.assign(K, 0);
+    lod_ens_residuals.assign(K, 0.0);
+    check(slod_lod_solve_ensemble(handle, d_values, (std::size_t)K, d_cols, d_rhs, (std::size_t)K, K, d_u, (std::size_t)K,
+                                  lod_rel_tol, lod_max_iterations, lod_ens_iterations.data(), lod_ens_residuals.data()),
+          "slod_lod_solve_ensemble");
+    check(slod_lod_reconstruct_ensemble(handle, d_b, stride, member_stride, K, d_u, (std::size_t)K, d_fine, fine_size, nullptr),
+          "slod_lod_reconstruct_ensemble");
+    check(slod_ensemble_moments(handle, d_fine, fine_size, K, fine_size, d_mean, d_var, nullptr), "slod_ensemble_moments");
+    check(slod_compute_error_norms(handle, 0, d_mean, nullptr, nullptr, nullptr, &ens_mean_norms, nullptr),
+          "slod_compute_error_norms"); // synchronises the handle's stream
+    std::vector<double> dev(fine_size);
+    if (hipMemcpy(dev.data(), d_var, fine_size * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      throw std::runtime_error("solve_ensemble: variance download failed");
+    for (double &v : dev)
+      v = std::sqrt(v);
+    if (hipMemcpy(d_var, dev.data(), fine_size * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+      throw std::runtime_error("solve_ensemble: deviation upload failed");
+    check(slod_compute_error_norms(handle, 0, d_var, nullptr, nullptr, nullptr, &ens_dev_norms, nullptr),
+          "slod_compute_error_norms");
   }
 
   template <int dim, int spacedim>

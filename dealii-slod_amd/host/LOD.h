@@ -84,6 +84,9 @@ namespace slod
     bool         constant_coefficients = true; // quirk Q1 when the coefficient is not constant
     bool         projection_quirk      = false; // quirk Q2 (LODtools.h:43-67), spacedim 2 only
     int          device                = 0;
+    // coefficient realisations the handle holds (slod_config.n_problems); member 0 is the problem of run(), the others
+    // are used by solve_ensemble() only
+    unsigned int n_members             = 1;
   };
 
   template <int dim, int spacedim>
@@ -154,6 +157,16 @@ namespace slod
     const std::vector<double> &wave_potential() const { return lod_wave_potential; }
     const std::vector<double> &wave_work() const { return lod_wave_work; }
     const slod_error_norms    &norms_wave() const { return wave_norms; }
+    // The LOD systems of all par.n_members coefficient realisations with the load f = 1, after run() (the reference
+    // solves one problem, LOD.cc:976-1002): the coefficients of members 1 .. K-1, one plan over all K * n_patches bases
+    // into an ensemble slab on the device, then slod_lod_matrix_ensemble, slod_lod_rhs_ensemble (one load shared),
+    // slod_lod_solve_ensemble, slod_lod_reconstruct_ensemble and slod_ensemble_moments; the norms of the mean and of the
+    // standard deviation (the square root of the variance, taken on the host) by slod_compute_error_norms with v = 0.
+    void solve_ensemble();
+    const std::vector<int>    &ensemble_iterations() const { return lod_ens_iterations; }      // per member
+    const std::vector<double> &ensemble_rel_residuals() const { return lod_ens_residuals; }    // per member
+    const slod_error_norms    &norms_ensemble_mean() const { return ens_mean_norms; }
+    const slod_error_norms    &norms_ensemble_deviation() const { return ens_dev_norms; }
     const slod_error_norms &error_LOD_FEMh() const { return lod_fem_error; }
     // the same norms of u_h alone (the denominators of relative errors)
     const slod_error_norms &norms_FEMh() const { return fem_norms; }
@@ -182,6 +195,13 @@ namespace slod
     virtual void coefficients_at_quadrature_points(const unsigned int          field,
                                                    const std::vector<Point<dim>> &points,
                                                    std::vector<double> &        values) = 0;
+    // The same for realisation `member` >= 1 of an ensemble; a problem class that can draw further realisations of
+    // its coefficient overrides it.
+    virtual void member_coefficients_at_quadrature_points(const unsigned int member, const unsigned int,
+                                                          const std::vector<Point<dim>> &, std::vector<double> &)
+    {
+      throw std::runtime_error("this problem class has no coefficient for ensemble member " + std::to_string(member));
+    }
     // assemble_stiffness(patch_stiffness_matrix, dummy, dh_fine_patch, empty_constraints)
     // (LOD.cc:440-444) for one patch: the unconstrained 9-point block stencil
     // stencil[node][dir][a][b] computed on the GPU.
@@ -222,6 +242,10 @@ namespace slod
     std::vector<int>              lod_multi_iterations;
     std::vector<double>           lod_multi_residuals;
     std::vector<slod_error_norms> lod_multi_fem_error;
+    // solve_ensemble
+    std::vector<int>    lod_ens_iterations;
+    std::vector<double> lod_ens_residuals;
+    slod_error_norms    ens_mean_norms{}, ens_dev_norms{};
 
     void check(const int status, const char *what) const;
     template <typename T>

@@ -131,6 +131,13 @@ def load():
     lib.slod_lod_newmark_steps.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                            C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t,
                                            C.c_size_t, C.c_double, C.c_int, C.POINTER(C.c_int), dp, dp, dp]
+    lib.slod_lod_matrix_ensemble.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, vp, vp]
+    lib.slod_lod_rhs_ensemble.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp]
+    lib.slod_lod_apply_ensemble.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp]
+    lib.slod_lod_solve_ensemble.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_double,
+                                            C.c_int, C.POINTER(C.c_int), dp]
+    lib.slod_lod_reconstruct_ensemble.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp]
+    lib.slod_ensemble_moments.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_size_t, vp, vp, vp]
     lib.slod_fem_rhs.argtypes = [vp, vp, vp, vp]
     lib.slod_fem_solve.argtypes = [vp, C.c_uint32, vp, vp, C.c_double, C.c_int, dp]
     lib.slod_coarse_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, vp]
@@ -484,6 +491,57 @@ class Slod:
         if rc < 0:
             self._check(rc)
         return its[:n_steps], res[:n_steps], kin, pot
+
+    # ---- the LOD systems of a coefficient ensemble: member k = problem k of the handle = column k of the coarse
+    # multi-vectors; matrix values member-minor, entry e of member k at [e * ld_m + k] (include/slod.h) ----
+    def lod_matrix_ensemble(self, d_basis, d_premult, stride, n_members, d_values, d_cols, member_stride=None, ld_m=None,
+                            stream=None):
+        """Block rows of every member on the shared pattern; member_stride defaults to num_patches * stride, ld_m to
+        n_members.  Asynchronous."""
+        self._check(self.lib.slod_lod_matrix_ensemble(
+            self.h, d_basis, d_premult, stride, self.num_patches * stride if member_stride is None else member_stride,
+            n_members, d_values, n_members if ld_m is None else ld_m, d_cols, stream))
+
+    def lod_rhs_ensemble(self, d_basis, stride, n_members, d_fine_rhs, d_out, ld_fine=0, member_stride=None, ld_out=None,
+                         stream=None):
+        """C_k^T f_k per member; ld_fine = 0: one load shared by all members.  Asynchronous."""
+        self._check(self.lib.slod_lod_rhs_ensemble(
+            self.h, d_basis, stride, self.num_patches * stride if member_stride is None else member_stride, n_members,
+            d_fine_rhs, ld_fine, d_out, n_members if ld_out is None else ld_out, stream))
+
+    def lod_apply_ensemble(self, d_values, d_cols, d_x, d_y, n_members, ld_m=None, ld_x=None, ld_y=None, stream=None):
+        """Y_k = A_k X_k; every ld defaults to n_members.  Asynchronous."""
+        self._check(self.lib.slod_lod_apply_ensemble(
+            self.h, d_values, n_members if ld_m is None else ld_m, d_cols, d_x, n_members if ld_x is None else ld_x,
+            n_members, d_y, n_members if ld_y is None else ld_y, stream))
+
+    def lod_solve_ensemble(self, d_values, d_cols, d_rhs, d_u, n_members, ld_m=None, ld_rhs=None, ld_u=None, rel_tol=1e-12,
+                           max_iterations=2000):
+        """A_k u_k = rhs_k for every member.  Returns (iterations, rel_residual), one entry per member;
+        max(iterations) is the C call's return value."""
+        its = np.zeros(max(n_members, 1), dtype=np.intc)
+        res = np.zeros(max(n_members, 1))
+        rc = self.lib.slod_lod_solve_ensemble(
+            self.h, d_values, n_members if ld_m is None else ld_m, d_cols, d_rhs, n_members if ld_rhs is None else ld_rhs,
+            n_members, d_u, n_members if ld_u is None else ld_u, rel_tol, max_iterations,
+            its.ctypes.data_as(C.POINTER(C.c_int)), _dp(res))
+        if rc < 0:
+            self._check(rc)
+        return its[:n_members], res[:n_members]
+
+    def lod_reconstruct_ensemble(self, d_basis, stride, n_members, d_u, d_fine, ld_fine=None, member_stride=None, ld_u=None,
+                                 stream=None):
+        """Field k of d_fine = C_k u_k; ld_fine defaults to the length of a fine field.  Asynchronous."""
+        field = (self.NE + 1) ** 2 * self.spacedim
+        self._check(self.lib.slod_lod_reconstruct_ensemble(
+            self.h, d_basis, stride, self.num_patches * stride if member_stride is None else member_stride, n_members,
+            d_u, n_members if ld_u is None else ld_u, d_fine, field if ld_fine is None else ld_fine, stream))
+
+    def ensemble_moments(self, d_fields, n_members, count, d_mean, d_var=None, ld_fine=None, stream=None):
+        """Mean and unbiased variance over the members of `count` entries per field; ld_fine defaults to count.
+        Asynchronous."""
+        self._check(self.lib.slod_ensemble_moments(self.h, d_fields, count if ld_fine is None else ld_fine, n_members, count,
+                                                   d_mean, d_var, stream))
 
     def fem_rhs(self, d_f_qp, d_fine_rhs, stream=None):
         """Fine FEM load vector (d_f_qp = None: f = 1)."""

@@ -432,6 +432,68 @@ int slod_lod_newmark_steps(slod_handle *h, const double *d_stiffness, const doub
                            double *kinetic      /* HOST [(n_steps + 1) * n_rhs], may be NULL */,
                            double *potential    /* HOST [(n_steps + 1) * n_rhs], may be NULL */);
 
+/* ---- the LOD systems of a coefficient ensemble, one call per step for all members --------------
+ * A handle with n_problems = K builds the bases of K coefficient realisations in one plan; these calls carry the
+ * ensemble through the LOD space: K matrices, K loads, K solves, K reconstructions, then mean and variance (the
+ * reference solves one problem, LOD.cc:976-1002).  The members share the grid, hence d_cols; they share no value.
+ * Layouts:
+ *   ensemble slab     member k in the single-problem slab layout at d_basis + k * member_stride (doubles), the same
+ *                     for d_premult; member_stride = num_patches * stride is what a plan over the gids
+ *                     0 .. K * num_patches - 1 with NULL offsets writes.
+ *   ensemble matrix   one d_cols, word for word what slod_lod_matrix writes for rows 0 .. num_patches-1.  Values
+ *                     member-minor: entry e of the single-matrix values array (e = (p * cap + j) * s * s + d * s + e')
+ *                     of member k at d_values[e * ld_m + k], ld_m >= n_members, so that the lanes of a wave, which
+ *                     hold consecutive members, read consecutive words.  n_members = 1, ld_m = 1 is the layout of
+ *                     slod_lod_matrix; a member sub-range of a wider array is base + first member.
+ *   coarse vectors    the coarse multi-vectors of the _multi calls, column k = member k (entry (i, k) at
+ *                     base[i * ld + k]); fine fields field-major, member k at base + k * ld_fine.
+ * Entries k >= n_members inside an ld are never read or written.  Every result of member k has the bits of the
+ * single-problem call on member k's slab, matrix and vectors: the kernels are the same bodies and the same summation
+ * orders with the member on a grid axis, and nothing depends on n_members, an ld, the member's position or the other
+ * members.  Argument checks come before any device work (SLOD_ERR_ARGUMENT, with the call's name in slod_last_error):
+ * NULL handle or array; n_members < 1 or > 65535; an ld below n_members; member_stride < num_patches * stride when
+ * n_members > 1; and what a call lists.  SLOD_ERR_DEVICE without a usable GPU. */
+/* Block rows of all num_patches patches for every member: member k's values are those of slod_lod_matrix with rows
+ * 0 .. num_patches-1 on its slab, bit for bit.  d_cols is written once.  No row list is uploaded: fully ASYNCHRONOUS on
+ * hip_stream (unlike slod_lod_matrix, which synchronises). */
+int slod_lod_matrix_ensemble(slod_handle *h, const double *d_basis, const double *d_premult, size_t stride,
+                             size_t member_stride, int n_members, double *d_values, size_t ld_m, uint32_t *d_cols,
+                             void *hip_stream);
+/* d_out[(p * s + d) * ld_out + k] = sum_i phi^(k)_{p,d}(i) f_k(i)  (slod_lod_rhs on member k's slab, bit for bit).
+ * f_k = d_fine_rhs + k * ld_fine; ld_fine = 0: one load shared by all members; SLOD_ERR_ARGUMENT if ld_fine is neither 0
+ * nor at least (NE+1)^2 * s.  Asynchronous on hip_stream. */
+int slod_lod_rhs_ensemble(slod_handle *h, const double *d_basis, size_t stride, size_t member_stride, int n_members,
+                          const double *d_fine_rhs, size_t ld_fine, double *d_out, size_t ld_out, void *hip_stream);
+/* Y_k = A_k X_k: the fma chain of slod_lod_apply_multi over the slots of a row in ascending order, with member k's
+ * matrix (the same bits).  SLOD_ERR_ARGUMENT also for d_x == d_y.  Asynchronous on hip_stream. */
+int slod_lod_apply_ensemble(slod_handle *h, const double *d_values, size_t ld_m, const uint32_t *d_cols,
+                            const double *d_x, size_t ld_x, int n_members, double *d_y, size_t ld_y, void *hip_stream);
+/* A_k u_k = rhs_k for every member: the recurrence of slod_lod_solve_multi (per-column scalars, freeze check every 8
+ * iterations, fixed summation orders, no atomics) in which column k reads matrix k and the inverse diagonal of matrix k;
+ * three launches per iteration for all members.  Column k of d_u, iterations[k] and rel_residual[k] are bit-identical
+ * to slod_lod_solve_multi(n_rhs = 1) on member k's de-interleaved matrix and rhs.  Device workspace of
+ * 5 * num_patches * s * n_members doubles, allocated per call.  Returns the largest per-member iteration count or a
+ * negative slod_status; reaching max_iterations is not an error; SLOD_ERR_ARGUMENT also for max_iterations < 0.  Runs on
+ * the handle's stream; synchronises. */
+int slod_lod_solve_ensemble(slod_handle *h, const double *d_values, size_t ld_m, const uint32_t *d_cols,
+                            const double *d_rhs, size_t ld_rhs, int n_members, double *d_u, size_t ld_u,
+                            double rel_tol, int max_iterations,
+                            int *iterations /* HOST [n_members], may be NULL */,
+                            double *rel_residual /* HOST [n_members], may be NULL */);
+/* field k of d_fine = C_k u_k  (slod_lod_reconstruct on member k, bit for bit); ld_fine >= (NE+1)^2 * s.
+ * Asynchronous on hip_stream. */
+int slod_lod_reconstruct_ensemble(slod_handle *h, const double *d_basis, size_t stride, size_t member_stride,
+                                  int n_members, const double *d_u, size_t ld_u, double *d_fine, size_t ld_fine,
+                                  void *hip_stream);
+/* Sample mean and unbiased variance over the members of the first `count` entries of n_members fields (field k at
+ * d_fields + k * ld_fine, ld_fine >= count), per entry i:
+ *   mean = (x_0 + x_1 + ..) / K  summed in ascending k;   var = sum_k (x_k - mean)^2 / (K - 1)  in ascending k,
+ * difference, product and sum each rounded on its own (no fma): the bits of the obvious float64 loop.  K = 1: var = 0.
+ * d_var may be NULL.  SLOD_ERR_ARGUMENT: NULL handle, d_fields or d_mean; n_members < 1; count = 0; ld_fine < count.
+ * Asynchronous on hip_stream. */
+int slod_ensemble_moments(slod_handle *h, const double *d_fields, size_t ld_fine, int n_members, size_t count,
+                          double *d_mean, double *d_var /* may be NULL */, void *hip_stream);
+
 /* ---- fine FEM reference problem (assemble_and_solve_fem_problem, LOD.cc:1004-1094) ----
  * What the reference compares the LOD solution with (compare_lod_with_fem, LOD.cc:1240-1378).
  * fem_rhs of assemble_stiffness (Diffusion.h:149-193) on the global fine grid, [(NE+1)^2][s],
