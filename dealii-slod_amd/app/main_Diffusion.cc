@@ -1,6 +1,6 @@
 // Counterpart of reference app/main_Diffusion.cc for the basis-construction path:
 //   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare] [--coarse] [--loads K]
-//                  [--heat STEPS DT] [--eigs K] [--wave STEPS DT] [--ensemble K]
+//                  [--heat STEPS DT] [--eigs K] [--wave STEPS DT] [--ensemble K] [--perturb K]
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
 // file name it dumps, per patch, phi and psi in patch-lexicographic order (parity tests).
 // --compare (anywhere on the command line): after run(), the rest of the reference run() -- global
@@ -25,8 +25,15 @@
 // the others are drawn after it), f = 1: one plan for all K * patches bases, then the K LOD systems in one call per step
 // (slod_lod_matrix_ensemble, _rhs_, _solve_, _reconstruct_ensemble, slod_ensemble_moments): one line per member with its
 // iterations and relative residual, then the fine-grid L2 norms of the mean and of the standard deviation.
+// --perturb K: a local coefficient change after everything else.  K cells of the coefficient's 2^r x 2^r grid, picked by a
+// fixed linear congruential generator, flip between min and max; the basis and A_LOD are refreshed in place
+// (refresh_after_coefficient_change: only the patches that see a changed fine element, only the matrix entries with such a
+// row or column) and the system is solved (f = 1).  Then a second problem with the changed coefficient is built from
+// scratch.  Prints the dirty count "D of NP", max |A_refresh - A_rebuild| over the block rows and max |u_refresh -
+// u_rebuild| of the coarse solutions, each with the scale it is relative to.
 #include "../host/Diffusion.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -78,7 +85,7 @@ int main(int argc_all, char **argv_all)
 {
   // --compare and --coarse are taken out wherever they stand; the positional arguments keep their meaning
   bool               compare = false, coarse = false;
-  int                n_loads = 0, heat_steps = 0, n_eigs = 0, wave_steps = 0, n_members = 0;
+  int                n_loads = 0, heat_steps = 0, n_eigs = 0, wave_steps = 0, n_members = 0, n_perturb = 0;
   double             heat_dt = 0.0, wave_dt = 0.0;
   std::vector<char *> args;
   for (int i = 0; i < argc_all; ++i)
@@ -102,6 +109,8 @@ int main(int argc_all, char **argv_all)
       }
     else if (i > 0 && !std::strcmp(argv_all[i], "--ensemble") && i + 1 < argc_all)
       n_members = std::atoi(argv_all[++i]);
+    else if (i > 0 && !std::strcmp(argv_all[i], "--perturb") && i + 1 < argc_all)
+      n_perturb = std::atoi(argv_all[++i]);
     else
       args.push_back(argv_all[i]);
   const int argc = (int)args.size();
@@ -243,6 +252,42 @@ int main(int argc_all, char **argv_all)
                         problem.ensemble_rel_residuals()[k]);
           std::printf("SLOD ensemble of %d: L2 norm of the mean = %.12e, of the standard deviation = %.12e\n", n_members,
                       problem.norms_ensemble_mean().l2[0], problem.norms_ensemble_deviation().l2[0]);
+        }
+      if (n_perturb > 0)
+        {
+          if (!compare && n_loads <= 0 && heat_steps <= 0 && n_eigs <= 0 && wave_steps <= 0)
+            problem.assemble_global_matrix();
+          if (!compare && heat_steps <= 0 && wave_steps <= 0)
+            problem.assemble_and_solve_fem_problem(); // the load C^T f of solve(); f = 1 does not see the coefficient
+          problem.flip_coefficient_cells((unsigned int)n_perturb);
+          const unsigned int n_dirty = problem.refresh_after_coefficient_change();
+          problem.solve();
+          const std::vector<double> a_refresh = problem.lod_matrix_values(), u_refresh = problem.lod_solution();
+          std::printf("perturbation of %d coefficient cells: dirty patches = %u of %u\n", n_perturb, n_dirty,
+                      (unsigned int)problem.get_patches().size());
+          std::printf("rebuild from scratch:\n");
+          std::srand(1); // the draws of the first problem, then the same flips
+          Problem rebuilt(par, 1, 100, 3);
+          rebuilt.flip_coefficient_cells((unsigned int)n_perturb);
+          rebuilt.run();
+          rebuilt.assemble_global_matrix();
+          rebuilt.assemble_and_solve_fem_problem();
+          rebuilt.solve();
+          const std::vector<double> a_rebuild = rebuilt.lod_matrix_values(), u_rebuild = rebuilt.lod_solution();
+          const auto max_diff = [](const std::vector<double> &a, const std::vector<double> &b, double &scale) {
+            double d = 0.0;
+            scale    = 0.0;
+            for (std::size_t i = 0; i < a.size(); ++i)
+              {
+                d     = std::max(d, std::fabs(a[i] - b[i]));
+                scale = std::max(scale, std::fabs(b[i]));
+              }
+            return d;
+          };
+          double       a_scale = 0.0, u_scale = 0.0;
+          const double a_diff = max_diff(a_refresh, a_rebuild, a_scale), u_diff = max_diff(u_refresh, u_rebuild, u_scale);
+          std::printf("  max |A_refresh - A_rebuild| = %.6e  (max |A_rebuild| = %.6e)\n", a_diff, a_scale);
+          std::printf("  max |u_refresh - u_rebuild| = %.6e  (max |u_rebuild| = %.6e)\n", u_diff, u_scale);
         }
     }
   catch (std::exception &exc)

@@ -546,9 +546,9 @@ int slod_plan_create(slod_handle *h, const uint32_t *gids, size_t n, const uint6
   slod_plan       *p      = new slod_plan;
   p->h                    = h;
   p->n                    = n;
-  const int s = h->cfg.spacedim, n_sub = h->cfg.n_subdivisions, full = 2 * h->cfg.oversampling + 1;
+  const int s = h->cfg.spacedim, n_sub = h->cfg.n_subdivisions;
   // uniform stride = the full patch's s vectors of n_fine (what an all-gather slab uses)
-  p->stride         = (size_t)s * s * (size_t)(n_sub * full + 1) * (size_t)(n_sub * full + 1);
+  p->stride         = slod_uniform_stride(h);
   p->uniform_stride = offsets == nullptr;
   if (n == 0)
     {

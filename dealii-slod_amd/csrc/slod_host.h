@@ -110,6 +110,12 @@ inline SlodGrid slod_grid_of(const slod_handle *h)
   g.lod_stabilization = h->cfg.lod_stabilization;
   return g;
 }
+// doubles per patch of a uniform-stride slab (slod_plan_stride()): the full patch's s vectors of n_fine
+inline size_t slod_uniform_stride(const slod_handle *h)
+{
+  const size_t s = (size_t)h->cfg.spacedim, side = (size_t)h->cfg.n_subdivisions * (2 * (size_t)h->cfg.oversampling + 1) + 1;
+  return s * s * side * side;
+}
 // plan construction on the device (slod_plan_build.hip: k_make_desc, k_balance_order)
 struct SlodPlanSummary
 {

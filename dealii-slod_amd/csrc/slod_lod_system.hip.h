@@ -1,6 +1,8 @@
 // The bodies of the three kernels of the global LOD system (A_LOD block rows, C^T f, C u_H), defined once for the
 // single-problem kernels of slod_lod_system.hip and the ensemble kernels of slod_lod_ensemble.hip: the two differ in
 // which slab, load and output a block works on and in the stride of its stores, never in an order of summation.
+// The entries of A_LOD and M_LOD are per-slot bodies: the full-row kernels and the in-place update after a local
+// coefficient change (slod_lod_update.hip) call the same one.
 #ifndef SLOD_LOD_SYSTEM_HIP_H
 #define SLOD_LOD_SYSTEM_HIP_H
 #include "slod_host.h"
@@ -8,6 +10,51 @@
 
 namespace
 {
+  // ---------------------------------------------------------------------------------
+  // One entry of A_LOD: slot `out` = (row, j) of the block row of patch p (extent pe, vectors phi), pair geometry pg
+  // of the slot, computed by ONE wave in a fixed order (lanes over the nodes of the overlap rectangle, then the
+  // butterfly), so that an entry recomputed alone (slod_lod_update.hip) has the bits of the full row.  Entry e of the
+  // slot goes to values[(out s s + e) ld].
+  // ---------------------------------------------------------------------------------
+  __device__ __forceinline__ void lod_matrix_slot(const SlodGrid &G, const Extent &pe, const double *phi, const PairGeom &pg,
+                                                  const double *premult, size_t stride, size_t out, double *values, size_t ld)
+  {
+    const int      lane = threadIdx.x & 63;
+    const int      s = G.spacedim, n = G.n_sub;
+    const int      pnx = pe.mx * n + 1, pny = pe.my * n + 1, pnf = s * pnx * pny;
+    const uint32_t q  = pg.q;
+    const Extent   qe = pg.qe;
+    const int      qnx = qe.mx * n + 1, qny = qe.my * n + 1, qnf = s * qnx * qny;
+    const int      xa = pg.xa, ya = pg.ya, w = pg.w, hgt = pg.hgt;
+    double    acc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+    if (w > 0 && hgt > 0)
+      {
+        const double *psi = premult + (size_t)q * stride;
+        for (int idx = lane; idx < w * hgt; idx += 64)
+          {
+            const int iy = idx / w, ix = idx - iy * w;
+            const int np = (xa + ix - pe.x0 * n) + (ya + iy - pe.y0 * n) * pnx;
+            const int nq = (xa + ix - qe.x0 * n) + (ya + iy - qe.y0 * n) * qnx;
+            for (int c = 0; c < s; ++c)
+              for (int d = 0; d < s; ++d)
+                {
+                  const double ph = phi[(size_t)d * pnf + s * np + c];
+                  for (int e = 0; e < s; ++e)
+                    acc[d][e] = fma(ph, psi[(size_t)e * qnf + s * nq + c], acc[d][e]);
+                }
+          }
+      }
+    for (int d = 0; d < s; ++d)
+      for (int e = 0; e < s; ++e)
+        {
+          double v = acc[d][e];
+          for (int off = 32; off > 0; off >>= 1)
+            v += __shfl_xor(v, off, 64);
+          if (lane == 0)
+            values[(out * s * s + d * s + e) * ld] = v;
+        }
+  }
+
   // ---------------------------------------------------------------------------------
   // A_LOD block row `row` = patch p.  Block of 256 threads, wave w = the candidate neighbours j = w, w+4, ...
   // (offsets of the centre cell in [-(2l+1), 2l+1]^2: patches further apart share no node).  Entry e of the row's
@@ -18,50 +65,111 @@ namespace
                                                  uint32_t *cols)
   {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int s = G.spacedim, n = G.n_sub, cap = grid_row_capacity(G);
+    const int cap = grid_row_capacity(G);
     int       pcx, pcy;
     grid_centre(G, p, pcx, pcy);
     const Extent  pe = grid_extent(G, pcx, pcy);
-    const int     pnx = pe.mx * n + 1, pny = pe.my * n + 1, pnf = s * pnx * pny;
     const double *phi = basis + (size_t)p * stride;
     for (int j = wave; j < cap; j += 4)
       {
         const size_t   out = row * cap + j;
         const PairGeom pg = grid_pair(G, pcx, pcy, pe, j);
-        const uint32_t q  = pg.q;
-        const Extent   qe = pg.qe;
-        const int      qnx = qe.mx * n + 1, qny = qe.my * n + 1, qnf = s * qnx * qny;
-        const int      xa = pg.xa, ya = pg.ya, w = pg.w, hgt = pg.hgt;
-        double    acc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
-        if (w > 0 && hgt > 0)
-          {
-            const double *psi = premult + (size_t)q * stride;
-            for (int idx = lane; idx < w * hgt; idx += 64)
-              {
-                const int iy = idx / w, ix = idx - iy * w;
-                const int np = (xa + ix - pe.x0 * n) + (ya + iy - pe.y0 * n) * pnx;
-                const int nq = (xa + ix - qe.x0 * n) + (ya + iy - qe.y0 * n) * qnx;
-                for (int c = 0; c < s; ++c)
-                  for (int d = 0; d < s; ++d)
-                    {
-                      const double ph = phi[(size_t)d * pnf + s * np + c];
-                      for (int e = 0; e < s; ++e)
-                        acc[d][e] = fma(ph, psi[(size_t)e * qnf + s * nq + c], acc[d][e]);
-                    }
-              }
-          }
-        for (int d = 0; d < s; ++d)
-          for (int e = 0; e < s; ++e)
-            {
-              double v = acc[d][e];
-              for (int off = 32; off > 0; off >>= 1)
-                v += __shfl_xor(v, off, 64);
-              if (lane == 0)
-                values[(out * s * s + d * s + e) * ld] = v;
-            }
+        lod_matrix_slot(G, pe, phi, pg, premult, stride, out, values, ld);
         if (lane == 0 && cols)
           cols[out] = pg.col();
       }
+  }
+
+  // ---------------------------------------------------------------------------------
+  // One entry of M_LOD, the counterpart of lod_matrix_slot for k_lod_mass (slod_lod_time.hip): lanes = the fine
+  // elements of the intersection rectangle of the two closed patches (phi vanishes on every patch rim, so these
+  // elements carry the whole integral).  Lanes run along ix: the corner loads of neighbouring lanes are neighbouring
+  // doubles (spacedim 1) or neighbouring pairs (spacedim 2).
+  //
+  // Element form, Q1 consistent mass rho h^2/36 [[4,2,2,1],[2,4,1,2],[2,1,4,2],[1,2,2,4]] = rho h^2/36 (J+I)x(J+I):
+  //   p^T (J+I)x(J+I) q = (sum p)(sum q) + sum_rows (row sum p)(row sum q) + sum_cols (col sum p)(col sum q) + p.q
+  // Every product pairs a quantity of p with the same quantity of q and nothing is contracted into an fma, so the
+  // form is symmetric in (p, q) bit for bit; with the same lanes, the same component order and the same wave
+  // reduction on both sides, M[(p,d),(q,e)] and M[(q,e),(p,d)] are the same bits.
+  // ---------------------------------------------------------------------------------
+  template <int S>
+  __device__ __forceinline__ void lod_mass_slot(const SlodGrid &G, const Extent &pe, const double *phi, const PairGeom &pg,
+                                                const double *basis, size_t stride, const double *rho, double scale, size_t out,
+                                                double *values)
+  {
+#pragma clang fp contract(off)
+    const int      lane = threadIdx.x & 63;
+    const int      n = G.n_sub, NE = G.N * n;
+    const int      pnx = pe.mx * n + 1, pny = pe.my * n + 1, pnf = S * pnx * pny;
+    // the overlap is w x hgt nodes, (w - 1) x (hgt - 1) elements
+    const uint32_t q  = pg.q;
+    const Extent   qe = pg.qe;
+    const int      qnx = qe.mx * n + 1, qny = qe.my * n + 1, qnf = S * qnx * qny;
+    const int      xa = pg.xa, ya = pg.ya, w = pg.w, hgt = pg.hgt;
+    double    acc[S][S];
+#pragma unroll
+    for (int d = 0; d < S; ++d)
+#pragma unroll
+      for (int e = 0; e < S; ++e)
+        acc[d][e] = 0.0;
+    if (w > 1 && hgt > 1)
+      {
+        const double *phq = basis + (size_t)q * stride;
+        const int     we = w - 1;
+        for (int idx = lane; idx < we * (hgt - 1); idx += 64)
+          {
+            const int    iy = idx / we, ix = idx - iy * we;
+            const int    np = (xa + ix - pe.x0 * n) + (ya + iy - pe.y0 * n) * pnx;
+            const int    nq = (xa + ix - qe.x0 * n) + (ya + iy - qe.y0 * n) * qnx;
+            const double r  = rho ? rho[(size_t)(ya + iy) * NE + (xa + ix)] : 1.0;
+#pragma unroll
+            for (int c = 0; c < S; ++c)
+              {
+                // corner values and their sums, [d] of the row patch, [e] of the column patch
+                double a[S][4], b[S][4];
+#pragma unroll
+                for (int d = 0; d < S; ++d)
+                  {
+                    const double *v = phi + (size_t)d * pnf + c;
+                    a[d][0]         = v[S * np];
+                    a[d][1]         = v[S * (np + 1)];
+                    a[d][2]         = v[S * (np + pnx)];
+                    a[d][3]         = v[S * (np + pnx + 1)];
+                    const double *u = phq + (size_t)d * qnf + c;
+                    b[d][0]         = u[S * nq];
+                    b[d][1]         = u[S * (nq + 1)];
+                    b[d][2]         = u[S * (nq + qnx)];
+                    b[d][3]         = u[S * (nq + qnx + 1)];
+                  }
+#pragma unroll
+                for (int d = 0; d < S; ++d)
+#pragma unroll
+                  for (int e = 0; e < S; ++e)
+                    {
+                      const double ar0 = a[d][0] + a[d][1], ar1 = a[d][2] + a[d][3];
+                      const double ac0 = a[d][0] + a[d][2], ac1 = a[d][1] + a[d][3];
+                      const double br0 = b[e][0] + b[e][1], br1 = b[e][2] + b[e][3];
+                      const double bc0 = b[e][0] + b[e][2], bc1 = b[e][1] + b[e][3];
+                      const double all = (ar0 + ar1) * (br0 + br1);
+                      const double row = ar0 * br0 + ar1 * br1;
+                      const double col = ac0 * bc0 + ac1 * bc1;
+                      const double dot = (a[d][0] * b[e][0] + a[d][1] * b[e][1]) + (a[d][2] * b[e][2] + a[d][3] * b[e][3]);
+                      acc[d][e]        = acc[d][e] + r * ((all + dot) + (row + col));
+                    }
+              }
+          }
+      }
+#pragma unroll
+    for (int d = 0; d < S; ++d)
+#pragma unroll
+      for (int e = 0; e < S; ++e)
+        {
+          double v = acc[d][e];
+          for (int off = 32; off > 0; off >>= 1)
+            v += __shfl_xor(v, off, 64);
+          if (lane == 0)
+            values[out * S * S + d * S + e] = v * scale;
+        }
   }
 
   // C^T f for block row `row` = patch p: block of 256 threads over all its nodes; out[(row s + d) ld]

@@ -7,7 +7,7 @@
 // The mass kernel is an L2/HBM-bound gather like k_lod_matrix (slod_lod_system.hip) and shares its index calculus
 // (slod_grid.hip.h); the solve of a step is the recurrence of slod_lod_solve_multi (slod_lod_multi.hip) on a
 // workspace this file owns for the whole loop.
-#include "slod_grid.hip.h"
+#include "slod_lod_system.hip.h"
 #include "slod_lod_tile.hip.h"
 
 #include <algorithm>
@@ -15,104 +15,24 @@
 
 namespace
 {
-  // ---------------------------------------------------------------------------------
   // M_LOD block rows.  Block = one row patch p, wave w = the candidate neighbours j = w, w+4, ... as in
-  // k_lod_matrix; lanes = the fine elements of the intersection rectangle of the two closed patches (phi vanishes
-  // on every patch rim, so these elements carry the whole integral).  Lanes run along ix: the corner loads of
-  // neighbouring lanes are neighbouring doubles (spacedim 1) or neighbouring pairs (spacedim 2).
-  //
-  // Element form, Q1 consistent mass rho h^2/36 [[4,2,2,1],[2,4,1,2],[2,1,4,2],[1,2,2,4]] = rho h^2/36 (J+I)x(J+I):
-  //   p^T (J+I)x(J+I) q = (sum p)(sum q) + sum_rows (row sum p)(row sum q) + sum_cols (col sum p)(col sum q) + p.q
-  // Every product pairs a quantity of p with the same quantity of q and nothing is contracted into an fma, so the
-  // form is symmetric in (p, q) bit for bit; with the same lanes, the same component order and the same wave
-  // reduction on both sides, M[(p,d),(q,e)] and M[(q,e),(p,d)] are the same bits.
-  // ---------------------------------------------------------------------------------
+  // k_lod_matrix; the entry of a slot is lod_mass_slot (slod_lod_system.hip.h).
   template <int S>
   __global__ __launch_bounds__(256) void k_lod_mass(const SlodGrid G, const uint32_t *rows, const double *basis, size_t stride,
                                                    const double *rho, double scale, double *values, uint32_t *cols)
   {
-#pragma clang fp contract(off)
     const int      lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int      n = G.n_sub, NE = G.N * n, cap = grid_row_capacity(G);
+    const int      cap = grid_row_capacity(G);
     const uint32_t p = rows[blockIdx.x];
     int            pcx, pcy;
     grid_centre(G, p, pcx, pcy);
     const Extent  pe = grid_extent(G, pcx, pcy);
-    const int     pnx = pe.mx * n + 1, pny = pe.my * n + 1, pnf = S * pnx * pny;
     const double *phi = basis + (size_t)p * stride;
     for (int j = wave; j < cap; j += 4)
       {
         const size_t   out = (size_t)blockIdx.x * cap + j;
         const PairGeom pg = grid_pair(G, pcx, pcy, pe, j);
-        // the overlap is w x hgt nodes, (w - 1) x (hgt - 1) elements
-        const uint32_t q  = pg.q;
-        const Extent   qe = pg.qe;
-        const int      qnx = qe.mx * n + 1, qny = qe.my * n + 1, qnf = S * qnx * qny;
-        const int      xa = pg.xa, ya = pg.ya, w = pg.w, hgt = pg.hgt;
-        double    acc[S][S];
-#pragma unroll
-        for (int d = 0; d < S; ++d)
-#pragma unroll
-          for (int e = 0; e < S; ++e)
-            acc[d][e] = 0.0;
-        if (w > 1 && hgt > 1)
-          {
-            const double *phq = basis + (size_t)q * stride;
-            const int     we = w - 1;
-            for (int idx = lane; idx < we * (hgt - 1); idx += 64)
-              {
-                const int    iy = idx / we, ix = idx - iy * we;
-                const int    np = (xa + ix - pe.x0 * n) + (ya + iy - pe.y0 * n) * pnx;
-                const int    nq = (xa + ix - qe.x0 * n) + (ya + iy - qe.y0 * n) * qnx;
-                const double r  = rho ? rho[(size_t)(ya + iy) * NE + (xa + ix)] : 1.0;
-#pragma unroll
-                for (int c = 0; c < S; ++c)
-                  {
-                    // corner values and their sums, [d] of the row patch, [e] of the column patch
-                    double a[S][4], b[S][4];
-#pragma unroll
-                    for (int d = 0; d < S; ++d)
-                      {
-                        const double *v = phi + (size_t)d * pnf + c;
-                        a[d][0]         = v[S * np];
-                        a[d][1]         = v[S * (np + 1)];
-                        a[d][2]         = v[S * (np + pnx)];
-                        a[d][3]         = v[S * (np + pnx + 1)];
-                        const double *u = phq + (size_t)d * qnf + c;
-                        b[d][0]         = u[S * nq];
-                        b[d][1]         = u[S * (nq + 1)];
-                        b[d][2]         = u[S * (nq + qnx)];
-                        b[d][3]         = u[S * (nq + qnx + 1)];
-                      }
-#pragma unroll
-                    for (int d = 0; d < S; ++d)
-#pragma unroll
-                      for (int e = 0; e < S; ++e)
-                        {
-                          const double ar0 = a[d][0] + a[d][1], ar1 = a[d][2] + a[d][3];
-                          const double ac0 = a[d][0] + a[d][2], ac1 = a[d][1] + a[d][3];
-                          const double br0 = b[e][0] + b[e][1], br1 = b[e][2] + b[e][3];
-                          const double bc0 = b[e][0] + b[e][2], bc1 = b[e][1] + b[e][3];
-                          const double all = (ar0 + ar1) * (br0 + br1);
-                          const double row = ar0 * br0 + ar1 * br1;
-                          const double col = ac0 * bc0 + ac1 * bc1;
-                          const double dot = (a[d][0] * b[e][0] + a[d][1] * b[e][1]) + (a[d][2] * b[e][2] + a[d][3] * b[e][3]);
-                          acc[d][e]        = acc[d][e] + r * ((all + dot) + (row + col));
-                        }
-                  }
-              }
-          }
-#pragma unroll
-        for (int d = 0; d < S; ++d)
-#pragma unroll
-          for (int e = 0; e < S; ++e)
-            {
-              double v = acc[d][e];
-              for (int off = 32; off > 0; off >>= 1)
-                v += __shfl_xor(v, off, 64);
-              if (lane == 0)
-                values[out * S * S + d * S + e] = v * scale;
-            }
+        lod_mass_slot<S>(G, pe, phi, pg, basis, stride, rho, scale, out, values);
         // the pattern is that of k_lod_matrix: a pair that shares only a line of nodes keeps its column, value 0
         if (lane == 0)
           cols[out] = pg.col();

@@ -44,6 +44,14 @@ namespace slod
     }
 
     unsigned int grid_cells_per_side() const { return cells_per_side; }
+    // the value of grid cell `cell` (x fastest); a constant field has no table
+    double cell_value(std::size_t cell) const { return constant ? constant_value : table.at(cell); }
+    void   set_cell_value(std::size_t cell, double v)
+    {
+      if (constant)
+        throw std::runtime_error("problem_parameter: a constant field has no cells to change");
+      table.at(cell) = v;
+    }
 
   private:
     unsigned int        cells_per_side;
@@ -60,6 +68,8 @@ namespace slod
                      unsigned int r = 8)
       : LOD<dim, spacedim>(par)
       , Alpha(amin, amax, r)
+      , alpha_min(amin)
+      , alpha_max(amax)
     {
       // further realisations of the same field for an ensemble, drawn after Alpha: member 0 is what a problem with
       // one member has
@@ -67,8 +77,25 @@ namespace slod
         members.emplace_back(amin, amax, r);
     }
 
+    // A local change of the coefficient: n_cells cells of Alpha's grid, picked by a fixed linear congruential
+    // generator, flip between the extremes (a value in the lower half of [amin, amax] becomes amax, one in the upper
+    // half amin).  Before run() it changes the problem; after assemble_global_matrix() it is followed by
+    // refresh_after_coefficient_change().
+    void flip_coefficient_cells(const unsigned int n_cells)
+    {
+      const std::size_t total = (std::size_t)Alpha.grid_cells_per_side() * Alpha.grid_cells_per_side();
+      uint32_t          state = 12345u;
+      for (unsigned int k = 0; k < n_cells; ++k)
+        {
+          state                  = state * 1664525u + 1013904223u;
+          const std::size_t cell = (state >> 8) % total;
+          Alpha.set_cell_value(cell, Alpha.cell_value(cell) < 0.5 * (alpha_min + alpha_max) ? alpha_max : alpha_min);
+        }
+    }
+
   protected:
     problem_parameter<dim> Alpha; // reference: Alpha(1, 100, 8), Diffusion.h:62
+    double                 alpha_min, alpha_max;
     std::vector<problem_parameter<dim>> members; // realisations 1 .. n_members-1
 
     void coefficients_at_quadrature_points(const unsigned int, const std::vector<Point<dim>> &points,

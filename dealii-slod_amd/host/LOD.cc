@@ -144,13 +144,10 @@ namespace slod
           "slod_assemble_stiffness_for_patch");
   }
 
-  // LOD.cc:296-768: the whole patch loop runs on the GPU
+  // the points of QIterated(QGauss<1>(2), n) on every fine element of the global grid, index (ey NE + ex) 4 + q
   template <int dim, int spacedim>
-  void LOD<dim, spacedim>::compute_basis_function_candidates()
+  std::vector<Point<dim>> LOD<dim, spacedim>::fine_quadrature_points() const
   {
-    // coefficient at the quadrature points of QIterated(QGauss<1>(2), n) on every fine
-    // element of the global grid (what FEValues::get_quadrature_points feeds to
-    // Alpha.value_list in Diffusion.h:154)
     const unsigned int N  = 1u << par.n_global_refinements;
     const unsigned int NE = N * par.n_subdivisions;
     const double       hf = 1.0 / NE, g0 = 0.5 * (1.0 - 1.0 / std::sqrt(3.0)),
@@ -164,7 +161,18 @@ namespace slod
             p(0)          = (ex + ((q & 1) ? g1 : g0)) * hf;
             p(1)          = (ey + ((q & 2) ? g1 : g0)) * hf;
           }
-    std::vector<double> values;
+    return points;
+  }
+
+  // LOD.cc:296-768: the whole patch loop runs on the GPU
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::compute_basis_function_candidates()
+  {
+    // coefficient at the quadrature points of QIterated(QGauss<1>(2), n) on every fine
+    // element of the global grid (what FEValues::get_quadrature_points feeds to
+    // Alpha.value_list in Diffusion.h:154)
+    const std::vector<Point<dim>> points = fine_quadrature_points();
+    std::vector<double>           values;
     for (unsigned int field = 0; field < (unsigned int)spacedim; ++field)
       {
         coefficients_at_quadrature_points(field, points, values);
@@ -226,9 +234,14 @@ namespace slod
     const unsigned int n_patches = (unsigned int)patches.size();
     if (locally_owned_patches.first != 0 || locally_owned_patches.second != n_patches)
       throw std::runtime_error("assemble_global_matrix: the global steps need every patch in this process");
-    basis_stride = 0;
-    for (const auto &patch : patches)
-      basis_stride = std::max(basis_stride, (std::size_t)spacedim * patch.dealii_to_lexicographic.size());
+    // the uniform stride of the library's slabs (the full patch's vectors, also where the grid clips every patch): what
+    // the plan of refresh_after_coefficient_change() writes to
+    {
+      slod_plan *empty = nullptr;
+      check(slod_plan_create(handle, nullptr, 0, nullptr, &empty), "slod_plan_create");
+      basis_stride = slod_plan_stride(empty);
+      slod_plan_destroy(empty);
+    }
     std::vector<double> basis(n_patches * basis_stride, 0.0), premult(basis.size(), 0.0);
     for (unsigned int p = 0; p < n_patches; ++p)
       {
@@ -257,6 +270,86 @@ namespace slod
     check(slod_lod_matrix(handle, rows.data(), n_patches, d_basis, d_premult, basis_stride, d_lod_values, d_lod_cols,
                           nullptr),
           "slod_lod_matrix");
+  }
+
+  // The coefficient changed in part of the domain: only the patches that see the change are rebuilt, and only the
+  // entries of A_LOD (and M_LOD) with such a patch as row or column are recomputed, all in place on the device.
+  template <int dim, int spacedim>
+  unsigned int LOD<dim, spacedim>::refresh_after_coefficient_change()
+  {
+    if (!d_lod_values)
+      throw std::runtime_error("refresh_after_coefficient_change: assemble_global_matrix comes first");
+    const unsigned int n_patches = (unsigned int)patches.size();
+    uint32_t          *d_dirty   = device_alloc<uint32_t>(n_patches);
+    if (hipMemset(d_dirty, 0, n_patches * sizeof(uint32_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+      throw std::runtime_error("refresh_after_coefficient_change: clearing the dirty array failed");
+    const std::vector<Point<dim>> points = fine_quadrature_points();
+    std::vector<double>           values;
+    for (unsigned int field = 0; field < (unsigned int)spacedim; ++field)
+      {
+        coefficients_at_quadrature_points(field, points, values);
+        check(slod_update_coefficient(handle, 0, (int)field, values.data(), 1, values.size(), 0, d_dirty),
+              "slod_update_coefficient");
+      }
+    slod_plan *plan = nullptr;
+    const int  n_dirty = slod_plan_create_dirty(handle, 0, d_dirty, &plan);
+    check(n_dirty, "slod_plan_create_dirty");
+    int rc = slod_plan_execute(plan, d_basis, d_premult, nullptr);
+    if (rc == SLOD_OK)
+      rc = slod_plan_status(plan);
+    slod_plan_destroy(plan);
+    check(rc, "slod_plan_execute");
+    check(slod_lod_matrix_update(handle, d_dirty, d_basis, d_premult, basis_stride, d_lod_values, 1, nullptr),
+          "slod_lod_matrix_update");
+    if (d_lod_mass)
+      check(slod_lod_mass_matrix_update(handle, d_dirty, d_basis, basis_stride, nullptr, d_lod_mass, nullptr),
+            "slod_lod_mass_matrix_update");
+    // Patch::basis_function(_premultiplied) of the rebuilt patches, as compute_basis_function_candidates() leaves them
+    std::vector<uint32_t> dirty((std::size_t)n_dirty);
+    check(slod_dirty_patches(handle, d_dirty, dirty.data(), dirty.size()), "slod_dirty_patches"); // synchronises
+    std::vector<double> basis, premult;
+    for (const uint32_t p : dirty)
+      {
+        Patch<dim>       &patch  = patches[p];
+        const std::size_t n_fine = patch.dealii_to_lexicographic.size();
+        basis.resize(spacedim * n_fine);
+        premult.resize(spacedim * n_fine);
+        if (hipMemcpy(basis.data(), d_basis + p * basis_stride, basis.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(premult.data(), d_premult + p * basis_stride, premult.size() * sizeof(double), hipMemcpyDeviceToHost) !=
+              hipSuccess)
+          throw std::runtime_error("refresh_after_coefficient_change: basis download failed");
+        for (int d = 0; d < spacedim; ++d)
+          for (std::size_t i = 0; i < n_fine; ++i)
+            {
+              const std::size_t lex                    = d * n_fine + patch.dealii_to_lexicographic[i];
+              patch.basis_function[d][i]               = basis[lex];
+              patch.basis_function_premultiplied[d][i] = premult[lex];
+            }
+      }
+    return (unsigned int)n_dirty;
+  }
+
+  template <int dim, int spacedim>
+  std::vector<double> LOD<dim, spacedim>::lod_matrix_values() const
+  {
+    if (!d_lod_values)
+      throw std::runtime_error("lod_matrix_values: assemble_global_matrix comes first");
+    std::vector<double> v(patches.size() * (std::size_t)slod_lod_row_capacity(handle) * spacedim * spacedim);
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(v.data(), d_lod_values, v.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      throw std::runtime_error("lod_matrix_values: download failed");
+    return v;
+  }
+
+  template <int dim, int spacedim>
+  std::vector<double> LOD<dim, spacedim>::lod_solution() const
+  {
+    if (!d_lod_u)
+      throw std::runtime_error("lod_solution: solve comes first");
+    std::vector<double> v(patches.size() * (std::size_t)spacedim);
+    if (hipMemcpy(v.data(), d_lod_u, v.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      throw std::runtime_error("lod_solution: download failed");
+    return v;
   }
 
   // LOD.cc:1004-1094 with the example's f = 1
@@ -383,17 +476,8 @@ namespace slod
     const std::size_t NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
     const std::size_t fine_size = (NE + 1) * (NE + 1) * spacedim, n_coarse = (std::size_t)n_patches * spacedim;
     // member 0 holds the coefficient of run(); the others are drawn now, at the same quadrature points
-    const double            hf = 1.0 / NE, g0 = 0.5 * (1.0 - 1.0 / std::sqrt(3.0)), g1 = 0.5 * (1.0 + 1.0 / std::sqrt(3.0));
-    std::vector<Point<dim>> points(NE * NE * 4);
-    for (std::size_t ey = 0; ey < NE; ++ey)
-      for (std::size_t ex = 0; ex < NE; ++ex)
-        for (unsigned int q = 0; q < 4; ++q)
-          {
-            Point<dim> &p = points[(ey * NE + ex) * 4 + q];
-            p(0)          = (ex + ((q & 1) ? g1 : g0)) * hf;
-            p(1)          = (ey + ((q & 2) ? g1 : g0)) * hf;
-          }
-    std::vector<double> values;
+    const std::vector<Point<dim>> points = fine_quadrature_points();
+    std::vector<double>           values;
     for (int k = 1; k < K; ++k)
       for (unsigned int field = 0; field < (unsigned int)spacedim; ++field)
         {

@@ -167,6 +167,16 @@ namespace slod
     const std::vector<double> &ensemble_rel_residuals() const { return lod_ens_residuals; }    // per member
     const slod_error_norms    &norms_ensemble_mean() const { return ens_mean_norms; }
     const slod_error_norms    &norms_ensemble_deviation() const { return ens_dev_norms; }
+    // After assemble_global_matrix(), when the coefficient of the problem class has changed in part of the domain (the
+    // reference has no counterpart): re-samples it (slod_update_coefficient finds the patches that see a changed fine
+    // element), rebuilds those patches in place on the device slab (slod_plan_create_dirty), recomputes the entries of
+    // A_LOD with such a row or column (slod_lod_matrix_update), those of M_LOD if assemble_mass_matrix() has run
+    // (slod_lod_mass_matrix_update), and brings Patch::basis_function of the rebuilt patches up to date.  Returns the
+    // number of rebuilt patches.  solve() and the other consumers then see the new coefficient.
+    unsigned int refresh_after_coefficient_change();
+    // values of the block rows of A_LOD (the layout of slod_lod_matrix) and u_H of the last solve(), copied from the device
+    std::vector<double> lod_matrix_values() const;
+    std::vector<double> lod_solution() const;
     const slod_error_norms &error_LOD_FEMh() const { return lod_fem_error; }
     // the same norms of u_h alone (the denominators of relative errors)
     const slod_error_norms &norms_FEMh() const { return fem_norms; }
@@ -248,6 +258,7 @@ namespace slod
     slod_error_norms    ens_mean_norms{}, ens_dev_norms{};
 
     void check(const int status, const char *what) const;
+    std::vector<Point<dim>> fine_quadrature_points() const;
     template <typename T>
     T *device_alloc(std::size_t n);
   };

@@ -138,6 +138,11 @@ def load():
                                             C.c_int, C.POINTER(C.c_int), dp]
     lib.slod_lod_reconstruct_ensemble.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp]
     lib.slod_ensemble_moments.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_size_t, vp, vp, vp]
+    lib.slod_update_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, C.c_int, C.c_size_t, C.c_int, vp]
+    lib.slod_dirty_patches.argtypes = [vp, vp, u32p, C.c_size_t]
+    lib.slod_plan_create_dirty.argtypes = [vp, C.c_uint32, vp, C.POINTER(vp)]
+    lib.slod_lod_matrix_update.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp]
+    lib.slod_lod_mass_matrix_update.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp]
     lib.slod_fem_rhs.argtypes = [vp, vp, vp, vp]
     lib.slod_fem_solve.argtypes = [vp, C.c_uint32, vp, vp, C.c_double, C.c_int, dp]
     lib.slod_coarse_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, vp]
@@ -212,9 +217,24 @@ class Comm:
 
 
 class Plan:
-    def __init__(self, slod, gids, offsets=None):
+    def __init__(self, slod, gids, offsets=None, dirty=None):
+        """dirty = (problem, d_dirty): the plan of slod_plan_create_dirty; gids are then read from the dirty array."""
         self.slod = slod
         self.lib = slod.lib
+        if dirty is not None:
+            problem, d_dirty = dirty
+            self.p = C.c_void_p()
+            n = self.lib.slod_plan_create_dirty(slod.h, problem, d_dirty, C.byref(self.p))
+            if n < 0:
+                slod._check(n)
+            ids = np.zeros(max(n, 1), dtype=np.uint32)
+            m = self.lib.slod_dirty_patches(slod.h, d_dirty, ids.ctypes.data_as(C.POINTER(C.c_uint32)), n)
+            assert m == n, "the dirty array changed under the plan"
+            self.gids = ids[:n] + np.uint32(problem * slod.num_patches)
+            self.stride = self.lib.slod_plan_stride(self.p)
+            self.offsets = (self.gids % np.uint32(slod.num_patches)).astype(np.uint64) * np.uint64(self.stride)
+            self.output_size = self.lib.slod_plan_output_size(self.p)
+            return
         self.gids = np.ascontiguousarray(gids, dtype=np.uint32)
         off_p = None
         if offsets is not None:
@@ -345,6 +365,42 @@ class Slod:
 
     def plan(self, gids, offsets=None):
         return Plan(self, gids, offsets)
+
+    # ---- refresh after a local coefficient change; d_dirty: device array of num_patches uint32 (raw pointer) ----
+    def update_coefficient(self, field, data, d_dirty, problem=0, per_qp=True):
+        """set_coefficient that also flags, in d_dirty, the patches whose extent holds a changed fine element."""
+        a = np.ascontiguousarray(data, dtype=np.float64).ravel()
+        self._check(self.lib.slod_update_coefficient(self.h, problem, field, a.ctypes.data, 1 if per_qp else 0, a.size, 0,
+                                                     d_dirty))
+
+    def update_coefficient_device(self, field, dev_ptr, count, d_dirty, problem=0, per_qp=True):
+        self._check(self.lib.slod_update_coefficient(self.h, problem, field, dev_ptr, 1 if per_qp else 0, count, 1, d_dirty))
+
+    def dirty_patches(self, d_dirty, count_only=False):
+        """Ascending ids of the dirty patches (an int64 array), or their number with count_only.  Synchronises."""
+        n = self.lib.slod_dirty_patches(self.h, d_dirty, None, 0)
+        if n < 0:
+            self._check(n)
+        if count_only:
+            return n
+        buf = np.zeros(max(n, 1), dtype=np.uint32)
+        m = self.lib.slod_dirty_patches(self.h, d_dirty, buf.ctypes.data_as(C.POINTER(C.c_uint32)), n)
+        if m < 0:
+            self._check(m)
+        return buf[:m].astype(np.int64)
+
+    def plan_dirty(self, d_dirty, problem=0):
+        """The plan that overwrites the dirty patches of the problem's uniform-stride slab in place
+        (slod_plan_create_dirty); len(plan.gids) is the C call's return value."""
+        return Plan(self, None, dirty=(problem, d_dirty))
+
+    def lod_matrix_update(self, d_dirty, d_basis, d_premult, stride, d_values, ld_m=1, stream=None):
+        """Recomputes in place the entries of A_LOD with a dirty row or column.  Asynchronous."""
+        self._check(self.lib.slod_lod_matrix_update(self.h, d_dirty, d_basis, d_premult, stride, d_values, ld_m, stream))
+
+    def lod_mass_matrix_update(self, d_dirty, d_basis, stride, d_values, d_rho=None, stream=None):
+        """Recomputes in place the entries of M_LOD with a dirty row or column.  Asynchronous."""
+        self._check(self.lib.slod_lod_mass_matrix_update(self.h, d_dirty, d_basis, stride, d_rho, d_values, stream))
 
     # ---- consumers of (phi, psi): the global LOD system (raw device pointers as ints) ----
     def lod_row_capacity(self):

@@ -494,6 +494,56 @@ int slod_lod_reconstruct_ensemble(slod_handle *h, const double *d_basis, size_t 
 int slod_ensemble_moments(slod_handle *h, const double *d_fields, size_t ld_fine, int n_members, size_t count,
                           double *d_mean, double *d_var /* may be NULL */, void *hip_stream);
 
+/* ---- refresh after a local coefficient change ----------------------------------------------
+ * Every entry point above takes the coefficient as fixed for the life of a basis (the reference does too: one
+ * compute_basis_function_candidates per run, LOD.cc:1425-1433).  When it changes in a small part of the domain -- a
+ * moving inclusion, a growing damage zone, a local perturbation in a parameter study -- only the patches whose extent
+ * holds a changed fine element have another basis, and only the entries of A_LOD and M_LOD with such a patch as row or
+ * column have another value.  These calls find those patches, rebuild them in place and recompute those entries in
+ * place, each with the bits a full rebuild gives (see slod_plan_create_dirty for the one exception).
+ * A DIRTY ARRAY is a caller-owned DEVICE array of num_patches uint32_t, one word per patch of ONE problem; a non-zero
+ * word means the patch is dirty.  The caller zeroes it (hipMemsetAsync) and may set words by hand.
+ * Not covered: a change of rho (rebuild M_LOD), C^T f of the dirty rows (slod_lod_rhs with the list of
+ * slod_dirty_patches, or the whole load: either is one read of the slab), handles with constant_coefficients = 1. */
+/* slod_set_coefficient (same arguments, layouts, host or device data; runs on the handle's stream and synchronises)
+ * that also ORs 1 into d_dirty[p] for every patch p whose extent, the fine elements [x0 n, (x0 + mx) n) x
+ * [y0 n, (y0 + my) n) with n = n_subdivisions, holds a changed element.  An element is changed when at least one of
+ * its four stored values differs from the stored field AS A 64-BIT WORD: no tolerance, 1.0 -> nextafter(1.0) is a
+ * change, the same bits are none.  Words of clean patches are left as they are, so flags accumulate over calls: the
+ * two Lame fields take two calls on one array.
+ * Checked in this order, all before any device work: SLOD_ERR_ARGUMENT: what slod_set_coefficient refuses, or a NULL
+ * d_dirty; SLOD_ERR_UNSUPPORTED: constant_coefficients = 1 (under quirk Q1 every full patch reads the first full
+ * patch's tile, so its basis does not depend on its own elements); SLOD_ERR_STATE: (problem, field) has never been
+ * set; SLOD_ERR_DEVICE without a usable GPU. */
+int slod_update_coefficient(slod_handle *h, uint32_t problem, int field, const double *data, int layout,
+                            size_t count, int on_device, uint32_t *d_dirty);
+/* Number of dirty patches; `patches` (HOST, may be NULL) receives their ids in ascending order.  SLOD_ERR_ARGUMENT
+ * when capacity is below the count; patches = NULL, capacity = 0 only counts.  Synchronises the handle's stream and
+ * reads the array back with a blocking copy. */
+int slod_dirty_patches(slod_handle *h, const uint32_t *d_dirty, uint32_t *patches /* HOST, may be NULL */, size_t capacity);
+/* Returns the number n >= 0 of dirty patches and sets *out to the plan slod_plan_create gives for the gids
+ * problem * num_patches + p of the dirty patches p, ascending, with offsets[k] = p * slod_plan_stride(): executed on the
+ * uniform-stride slab of the problem it overwrites the dirty patches in place and writes nothing else (not the gap up
+ * to the stride either).  n = 0: the empty plan, whose execute does nothing.  Synchronises like slod_dirty_patches.
+ * Contract on the bits: they are those of that slod_plan_create call.  The patch-solve kernel of a plan is chosen from
+ * the plan's maxima over its patches (line length, coarse dofs, ...), so a dirty list without a full patch may run
+ * another kernel instantiation than the plan over all patches and then differs from a full rebuild in the last bits;
+ * a list that holds a full patch has the maxima of the full plan. */
+int slod_plan_create_dirty(slod_handle *h, uint32_t problem, const uint32_t *d_dirty, slod_plan **out);
+/* In place on a full set of block rows (rows 0 .. num_patches-1 in the layout of slod_lod_matrix, or one member of an
+ * ensemble matrix: d_values + k, ld_m, with that member's slabs): recomputes every used entry (p, j) with
+ * d_dirty[p] != 0 or d_dirty[q] != 0, q the column of slot j.  Each recomputed entry has the bits of slod_lod_matrix /
+ * slod_lod_matrix_ensemble on the current slabs; no other word of d_values is written.  d_cols is not needed: it
+ * depends on the grid only.  One block per row; a clean row far from any dirty patch costs its row-capacity flag loads.
+ * Uploads nothing: ASYNCHRONOUS on hip_stream.  SLOD_ERR_ARGUMENT: NULL handle or array, ld_m < 1. */
+int slod_lod_matrix_update(slod_handle *h, const uint32_t *d_dirty, const double *d_basis, const double *d_premult,
+                           size_t stride, double *d_values, size_t ld_m, void *hip_stream);
+/* The same for M_LOD: the used entries with a dirty p or q get the bits of slod_lod_mass_matrix with the same d_rho
+ * (NULL = 1).  (p, q) and (q, p) are always recomputed together, so the matrix stays symmetric bit for bit.
+ * Asynchronous on hip_stream.  SLOD_ERR_ARGUMENT: NULL handle, d_dirty, d_basis or d_values. */
+int slod_lod_mass_matrix_update(slod_handle *h, const uint32_t *d_dirty, const double *d_basis, size_t stride,
+                                const double *d_rho, double *d_values, void *hip_stream);
+
 /* ---- fine FEM reference problem (assemble_and_solve_fem_problem, LOD.cc:1004-1094) ----
  * What the reference compares the LOD solution with (compare_lod_with_fem, LOD.cc:1240-1378).
  * fem_rhs of assemble_stiffness (Diffusion.h:149-193) on the global fine grid, [(NE+1)^2][s],
