@@ -1,6 +1,6 @@
 // Counterpart of reference app/main_Diffusion.cc for the basis-construction path:
 //   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare] [--coarse] [--loads K]
-//                  [--heat STEPS DT] [--eigs K] [--wave STEPS DT] [--ensemble K] [--perturb K]
+//                  [--heat STEPS DT] [--eigs K] [--wave STEPS DT] [--direct] [--ensemble K] [--perturb K]
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
 // file name it dumps, per patch, phi and psi in patch-lexicographic order (parity tests).
 // --compare (anywhere on the command line): after run(), the rest of the reference run() -- global
@@ -21,6 +21,10 @@
 // steps of the trapezoidal rule (Newmark gamma = 1/2, beta = 1/4, slod_lod_newmark_steps): one line per step with its
 // iterations, relative residual, kinetic and potential energy and the work u^T b (kinetic + potential = work from rest
 // under a constant load), then the fine-grid L2 norm of the reconstructed final state.
+// --direct: the time loops of --heat and --wave run on a banded Cholesky factor of their matrix S instead of CG
+// (slod_lod_factor_create once, slod_lod_theta_steps_direct / slod_lod_newmark_steps_direct): one line "factor: n = ..,
+// half bandwidth = .., bytes = .., pivots in [.., ..]" per loop, then the same per-step lines without iterations and
+// residuals (the heat loop has none left: "heat step K").
 // --ensemble K: K realisations of the run's random coefficient (member 0 is the coefficient of a run without the flag,
 // the others are drawn after it), f = 1: one plan for all K * patches bases, then the K LOD systems in one call per step
 // (slod_lod_matrix_ensemble, _rhs_, _solve_, _reconstruct_ensemble, slod_ensemble_moments): one line per member with its
@@ -81,10 +85,16 @@ private:
   int k;
 };
 
+static void print_factor(const slod_lod_factor_info &f)
+{
+  std::printf("factor: n = %d, half bandwidth = %d, bytes = %llu, pivots in [%.6e, %.6e]\n", f.n, f.half_bandwidth,
+              (unsigned long long)f.bytes, f.min_pivot, f.max_pivot);
+}
+
 int main(int argc_all, char **argv_all)
 {
   // --compare and --coarse are taken out wherever they stand; the positional arguments keep their meaning
-  bool               compare = false, coarse = false;
+  bool               compare = false, coarse = false, direct = false;
   int                n_loads = 0, heat_steps = 0, n_eigs = 0, wave_steps = 0, n_members = 0, n_perturb = 0;
   double             heat_dt = 0.0, wave_dt = 0.0;
   std::vector<char *> args;
@@ -93,6 +103,8 @@ int main(int argc_all, char **argv_all)
       compare = true;
     else if (i > 0 && !std::strcmp(argv_all[i], "--coarse"))
       compare = coarse = true;
+    else if (i > 0 && !std::strcmp(argv_all[i], "--direct"))
+      direct = true;
     else if (i > 0 && !std::strcmp(argv_all[i], "--loads") && i + 1 < argc_all)
       n_loads = std::atoi(argv_all[++i]);
     else if (i > 0 && !std::strcmp(argv_all[i], "--heat") && i + 2 < argc_all)
@@ -197,11 +209,16 @@ int main(int argc_all, char **argv_all)
               problem.solve();
             }
           problem.assemble_mass_matrix();
-          problem.solve_heat((unsigned int)heat_steps, heat_dt, 1.0);
+          problem.solve_heat((unsigned int)heat_steps, heat_dt, 1.0, direct);
           problem.compare_heat_with_lod();
+          if (direct)
+            print_factor(problem.last_factor_info());
           for (int k = 0; k < heat_steps; ++k)
-            std::printf("heat step %d: iterations = %d, relative residual = %.6e\n", k + 1, problem.heat_iterations()[k],
-                        problem.heat_rel_residuals()[k]);
+            if (direct)
+              std::printf("heat step %d\n", k + 1);
+            else
+              std::printf("heat step %d: iterations = %d, relative residual = %.6e\n", k + 1, problem.heat_iterations()[k],
+                          problem.heat_rel_residuals()[k]);
           const slod_error_norms &e = problem.error_heat_LOD(), &u = problem.norms_LOD();
           const double h1 = std::sqrt(e.l2[0] * e.l2[0] + e.h1_semi[0] * e.h1_semi[0]),
                        uh1 = std::sqrt(u.l2[0] * u.l2[0] + u.h1_semi[0] * u.h1_semi[0]);
@@ -237,9 +254,15 @@ int main(int argc_all, char **argv_all)
             }
           if (heat_steps <= 0 && n_eigs <= 0)
             problem.assemble_mass_matrix();
-          problem.solve_wave((unsigned int)wave_steps, wave_dt, 0.25, 0.5);
+          problem.solve_wave((unsigned int)wave_steps, wave_dt, 0.25, 0.5, direct);
+          if (direct)
+            print_factor(problem.last_factor_info());
           for (int k = 0; k < wave_steps; ++k)
-            std::printf("wave step %d: iterations = %d, relative residual = %.6e, kinetic = %.12e, potential = %.12e, work = %.12e\n",
+            if (direct)
+              std::printf("wave step %d: kinetic = %.12e, potential = %.12e, work = %.12e\n", k + 1, problem.wave_kinetic()[k + 1],
+                          problem.wave_potential()[k + 1], problem.wave_work()[k + 1]);
+            else
+              std::printf("wave step %d: iterations = %d, relative residual = %.6e, kinetic = %.12e, potential = %.12e, work = %.12e\n",
                         k + 1, problem.wave_iterations()[k], problem.wave_rel_residuals()[k], problem.wave_kinetic()[k + 1],
                         problem.wave_potential()[k + 1], problem.wave_work()[k + 1]);
           std::printf("SLOD wave at T = %g: L2 norm = %.12e\n", wave_steps * wave_dt, problem.norms_wave().l2[0]);

@@ -216,4 +216,22 @@ private:
   double            *cg = nullptr; // the pieces of the solve
   bool               per_col = false; // as given to take_solve
 };
+// The banded Cholesky factor of a full set of block rows (slod_lod_factor.hip): 16 x 16 tiles, nb block rows, bb block
+// sub-diagonals; the pointers are pieces of mem.
+struct slod_lod_factor
+{
+  slod_handle     *h = nullptr;
+  int              n = 0, b = 0, nb = 0, bb = 0; // rows, half bandwidth, block rows, block sub-diagonals
+  size_t           bytes = 0;
+  double           min_pivot = 0.0, max_pivot = 0.0;
+  double          *band = nullptr, *diag = nullptr, *piv = nullptr, *dinv = nullptr;
+  int             *rowmap = nullptr, *status = nullptr;
+  SlodDevBuf<char> mem;
+};
+// the launch of slod_lod_factor_solve for the time loops on a factor (slod_lod_time.hip, slod_lod_wave.hip); arguments
+// are checked by the caller
+void slod_lod_factor_solve_launch(const slod_lod_factor *f, hipStream_t st, const double *d_rhs, size_t ld_rhs, int n_rhs, double *d_u,
+                                  size_t ld_u);
+// SLOD_ERR_ARGUMENT, "<who>: NULL factor" or "<who>: factor of another handle / row count"; else SLOD_OK
+int slod_lod_factor_check(const slod_handle *h, const char *who, const slod_lod_factor *f);
 #endif

@@ -1,0 +1,404 @@
+// Direct solver on the LOD space: banded Cholesky  A = L L^T  of a full set of block rows, factored once and used by
+// any number of solves (the reference has no counterpart: it runs CG + SSOR once, LOD.cc:990-998):
+//   slod_lod_factor_create   band storage, the left-looking factorisation, pivot range and status
+//   slod_lod_factor_solve    U = A^-1 RHS on coarse multi-vectors, asynchronous, no allocation, no read-back
+// Ordering: unknown (p, d) has the index r = (cy N + cx) s + d, (cx, cy) the centre cell of p, so the block stencil of a
+// row (slot j = cell offset (j % span, j / span) - span / 2, slod_grid.hip.h) is a band of half width
+// b = s (w N + w) + s - 1, w = 2 l + 1.
+// Storage: tiles of FB x FB = 16 x 16, nb = ceil(n / 16) block rows, bb = (b + 15) / 16 block sub-diagonals; tile
+// (I, I - k), k = 1 .. bb, at band[(I (bb + 1) + k) 256] (k = 0 keeps A_II; L_II has an array of its own), column-major inside (entry (r, c) at [c 16 + r]), so the lanes
+// of the A operand of v_mfma_f64_16x16x4_f64 (lane l feeds A[l & 15][l >> 4]) read 16 consecutive doubles.  Rows
+// n .. 16 nb - 1 are padding with a unit diagonal: their pivots are 1 and their solution is 0.
+// Factorisation: one launch per block column K in stream order, no dependency inside a launch (left-looking).  Block
+// K + x of the launch forms  T = A_rK - sum_J L_rJ L_KJ^T  on the matrix pipe and, redundantly, the diagonal tile
+// A_KK - sum_J L_KJ L_KJ^T, factors that tile in LDS and solves  L_rK L_KK^T = T  by rows.
+// Solve: one block of four waves per chunk of 16 columns walks the block rows forwards (L y = b), then backwards
+// (L^T x = y).  The tiles of a block row are dealt to the waves round-robin (tile k to wave (k - 1) & 3), every wave
+// accumulates its tiles in ascending k, the four partial tiles are added in wave order: a fixed order of summation, and
+// a column of an MFMA result depends on its own input column only, so the bits of a column of U depend on the factor and
+// that column of RHS alone.  X lives in the caller's d_u (through the row map), which is L2-resident; there is no LDS
+// window and so no size-dependent path.
+#include "slod_grid.hip.h"
+#include "slod_common.hip.h"
+
+#include <cstdio>
+#include <vector>
+
+namespace
+{
+  constexpr int FB = 16, FT = FB * FB; // tile edge (one MFMA M / N), doubles per tile
+
+  __device__ __forceinline__ double4_t mfma(double a, double b, double4_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+
+  // factor index of unknown (p, d)
+  __device__ __forceinline__ int factor_index(const SlodGrid &G, uint32_t p, int d)
+  {
+    int cx, cy;
+    grid_centre(G, p, cx, cy);
+    return (cy * G.N + cx) * G.spacedim + d;
+  }
+
+  // rowmap[r] = p s + d, the caller's row of factor index r (-1: padding), and the unit diagonal of the padding
+  __global__ __launch_bounds__(256) void k_factor_rowmap(const SlodGrid G, int n, int npad, int bb, int *rowmap, double *band)
+  {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= npad)
+      return;
+    if (r >= n)
+      {
+        rowmap[r]                                                              = -1;
+        band[(size_t)(r / FB) * (bb + 1) * FT + (size_t)(r % FB) * FB + r % FB] = 1.0;
+        return;
+      }
+    const int s = G.spacedim, cell = r / s, d = r - cell * s;
+    rowmap[r]   = (int)grid_pid(G, cell % G.N, cell / G.N) * s + d;
+  }
+
+  // the lower triangle of the block rows into the zeroed band: entry ((p, d), (q, e)) with r(q, e) <= r(p, d)
+  __global__ __launch_bounds__(256) void k_factor_scatter(const SlodGrid G, int NP, int cap, int bb, const double *__restrict__ values,
+                                                         const uint32_t *__restrict__ cols, double *band)
+  {
+    const int    s = G.spacedim;
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (size_t)NP * cap * s * s)
+      return;
+    const size_t   slot = t / (s * s);
+    const int      de = (int)(t - slot * s * s), d = de / s, e = de - d * s;
+    const uint32_t p = (uint32_t)(slot / cap), q = cols[slot];
+    if (q >= (uint32_t)NP)
+      return;
+    const int r = factor_index(G, p, d), c = factor_index(G, q, e);
+    const int I = r / FB, k = I - c / FB;
+    if (c > r || k > bb)
+      return;
+    band[((size_t)I * (bb + 1) + k) * FT + (size_t)(c % FB) * FB + r % FB] = values[t];
+  }
+
+  // Block column K of the factorisation; block x = block row r = K + x.  status[0]: the index of the first pivot that is
+  // not > 0, or -1; a column after a failed one does nothing.  The factored diagonal tile goes to diag[K], not over A_KK in
+  // the band: the other blocks of the launch read A_KK.
+  __global__ __launch_bounds__(64) void k_factor_column(int K, int bb, double *band, double *diag, double *piv, double *dinv,
+                                                       int *status)
+  {
+    __shared__ double sD[FB][FB + 1], sT[FB][FB + 1];
+    const int         bad = status[0];
+    if (bad >= 0 && bad < K * FB) // set by an earlier launch: the same answer in every block
+      return;
+    const int    lane = threadIdx.x, li = lane & 15, lk = lane >> 4;
+    const int    r = K + blockIdx.x, J0 = max(0, K - bb), Jr = max(0, r - bb);
+    const size_t ldb = (size_t)(bb + 1) * FT;
+    auto         tile = [&](int I, int J) { return band + (size_t)I * ldb + (size_t)(I - J) * FT; };
+    // accumulator layout: lane holds D[lk + 4 q][li]
+    double4_t     accD, accT;
+    const double *aD = tile(K, K), *aT = tile(r, K);
+    for (int q = 0; q < 4; ++q)
+      {
+        accD[q] = aD[li * FB + lk + 4 * q];
+        accT[q] = aT[li * FB + lk + 4 * q];
+      }
+    for (int J = J0; J < K; ++J)
+      {
+        const double *lk_ = tile(K, J);
+        double        bk[4];
+        for (int kk = 0; kk < 4; ++kk)
+          bk[kk] = lk_[(4 * kk + lk) * FB + li]; // B[k][j] = L_KJ[j][k]; as an A operand the same word is L_KJ[i][k]
+        for (int kk = 0; kk < 4; ++kk)
+          accD = mfma(-bk[kk], bk[kk], accD);
+        if (r != K && J >= Jr)
+          {
+            const double *lr = tile(r, J);
+            for (int kk = 0; kk < 4; ++kk)
+              accT = mfma(-lr[(4 * kk + lk) * FB + li], bk[kk], accT);
+          }
+      }
+    for (int q = 0; q < 4; ++q)
+      {
+        sD[lk + 4 * q][li] = accD[q];
+        sT[lk + 4 * q][li] = accT[q];
+      }
+    __syncthreads();
+    // Cholesky of the diagonal tile, lower triangle of sD in place; the reciprocal diagonal goes to sD[j][FB]
+    for (int j = 0; j < FB; ++j)
+      {
+        const double p = sD[j][j];
+        const bool   ok = p > 0.0; // false for NaN too
+        const double dj = sqrt(ok ? p : 1.0);
+        __syncthreads();
+        if (lane == 0)
+          {
+            sD[j][j]  = dj;
+            sD[j][FB] = 1.0 / dj;
+            if (blockIdx.x == 0)
+              {
+                piv[K * FB + j] = p;
+                if (!ok && status[0] < 0)
+                  status[0] = K * FB + j;
+              }
+          }
+        else if (lane > j && lane < FB)
+          sD[lane][j] = sD[lane][j] / dj;
+        __syncthreads();
+        for (int idx = lane; idx < FT; idx += 64)
+          {
+            const int i = idx >> 4, c = idx & 15;
+            if (c > j && i >= c)
+              sD[i][c] = fma(-sD[i][j], sD[c][j], sD[i][c]);
+          }
+        __syncthreads();
+      }
+    double *out = blockIdx.x == 0 ? diag + (size_t)K * FT : tile(r, K);
+    if (blockIdx.x == 0)
+      {
+        for (int idx = lane; idx < FT; idx += 64)
+          {
+            const int c = idx >> 4, i = idx & 15;
+            out[idx]    = i >= c ? sD[i][c] : 0.0;
+          }
+        if (lane < FB)
+          dinv[K * FB + lane] = sD[lane][FB];
+        return;
+      }
+    // L_rK L_KK^T = T by rows: lane i < 16 holds row i
+    if (lane < FB)
+      {
+        double x[FB];
+#pragma unroll
+        for (int j = 0; j < FB; ++j)
+          {
+            double v = sT[lane][j];
+#pragma unroll
+            for (int m = 0; m < j; ++m)
+              v = fma(-x[m], sD[j][m], v);
+            x[j] = v * sD[j][FB];
+          }
+#pragma unroll
+        for (int j = 0; j < FB; ++j)
+          sT[lane][j] = x[j];
+      }
+    __syncthreads();
+    for (int idx = lane; idx < FT; idx += 64)
+      out[idx] = sT[idx & 15][idx >> 4];
+  }
+
+  // Both sweeps for the 16 columns from blockIdx.x * 16.  rhs and u may be the same array: a block row of rhs is read
+  // before the same rows of u are written, and a block touches its own columns only.
+  __global__ __launch_bounds__(256) void k_factor_solve(int nb, int bb, const double *__restrict__ band, const double *__restrict__ diag,
+                                                       const double *__restrict__ dinv, const int *__restrict__ rowmap, int n_rhs,
+                                                       const double *rhs, size_t ld_rhs, double *u, size_t ld_u)
+  {
+    __shared__ double sP[4][FB][FB + 1], sL[FB][FB + 1];
+    const int         tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4;
+    const int         c0 = blockIdx.x * FB;
+    const bool        col_ok = c0 + li < n_rhs;
+    const size_t      ldb = (size_t)(bb + 1) * FT;
+    // entry (row 16 I + i, this lane's column) of a multi-vector; padding rows and columns read as 0
+    auto load = [&](const double *x, size_t ld, int I, int i) {
+      const int row = rowmap[I * FB + i];
+      return col_ok && row >= 0 ? x[(size_t)row * ld + c0 + li] : 0.0;
+    };
+    for (int sweep = 0; sweep < 2; ++sweep)
+      for (int step = 0; step < nb; ++step)
+        {
+          const int     I = sweep == 0 ? step : nb - 1 - step;
+          const int     nk = sweep == 0 ? min(bb, I) : min(bb, nb - 1 - I); // tiles left (right, transposed) of the diagonal
+          const double *src = sweep == 0 ? rhs : u;
+          const size_t  ld_src = sweep == 0 ? ld_rhs : ld_u;
+          double4_t     acc = {0.0, 0.0, 0.0, 0.0};
+          if (wave == 0)
+            for (int q = 0; q < 4; ++q)
+              acc[q] = load(src, ld_src, I, lk + 4 * q);
+          for (int k = 1 + wave; k <= nk; k += 4)
+            {
+              // forward: tile (I, I - k) times X_{I-k}; backward: tile (I + k, I) transposed times X_{I+k}
+              const int     X = sweep == 0 ? I - k : I + k;
+              const double *t = band + (size_t)(sweep == 0 ? I : X) * ldb + (size_t)k * FT;
+              for (int kk = 0; kk < 4; ++kk)
+                {
+                  const double a = sweep == 0 ? t[(4 * kk + lk) * FB + li] : t[li * FB + 4 * kk + lk];
+                  acc            = mfma(-a, load(u, ld_u, X, 4 * kk + lk), acc);
+                }
+            }
+          for (int q = 0; q < 4; ++q)
+            sP[wave][lk + 4 * q][li] = acc[q];
+          sL[tid >> 4][tid & 15] = diag[(size_t)I * FT + (size_t)(tid & 15) * FB + (tid >> 4)]; // sL[r][c] = L_II[r][c]
+          __syncthreads();
+          if (tid < FB)
+            {
+              double x[FB];
+#pragma unroll
+              for (int i = 0; i < FB; ++i)
+                x[i] = ((sP[0][i][tid] + sP[1][i][tid]) + sP[2][i][tid]) + sP[3][i][tid];
+              if (sweep == 0)
+                {
+#pragma unroll
+                  for (int i = 0; i < FB; ++i)
+                    {
+                      double v = x[i];
+#pragma unroll
+                      for (int m = 0; m < i; ++m)
+                        v = fma(-sL[i][m], x[m], v);
+                      x[i] = v * dinv[I * FB + i];
+                    }
+                }
+              else
+                {
+#pragma unroll
+                  for (int i = FB - 1; i >= 0; --i)
+                    {
+                      double v = x[i];
+#pragma unroll
+                      for (int m = FB - 1; m > i; --m)
+                        v = fma(-sL[m][i], x[m], v);
+                      x[i] = v * dinv[I * FB + i];
+                    }
+                }
+              if (c0 + tid < n_rhs)
+                {
+#pragma unroll
+                  for (int i = 0; i < FB; ++i)
+                    {
+                      const int row = rowmap[I * FB + i];
+                      if (row >= 0)
+                        u[(size_t)row * ld_u + c0 + tid] = x[i];
+                    }
+                }
+            }
+          __syncthreads(); // the rows of X just written are read by all waves in the next steps
+        }
+  }
+} // namespace
+
+void slod_lod_factor_solve_launch(const slod_lod_factor *f, hipStream_t st, const double *d_rhs, size_t ld_rhs, int n_rhs, double *d_u,
+                                  size_t ld_u)
+{
+  hipLaunchKernelGGL(k_factor_solve, dim3((unsigned)((n_rhs + FB - 1) / FB)), dim3(256), 0, st, f->nb, f->bb, f->band, f->diag, f->dinv,
+                     f->rowmap, n_rhs, d_rhs, ld_rhs, d_u, ld_u);
+}
+
+int slod_lod_factor_check(const slod_handle *h, const char *who, const slod_lod_factor *f)
+{
+  if (!f)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": NULL factor");
+  if (f->h != h || f->n != h->NP * h->cfg.spacedim)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": factor of another handle / row count");
+  return SLOD_OK;
+}
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int slod_lod_factor_create(slod_handle *h, const double *d_values, const uint32_t *d_cols, slod_lod_factor **out)
+{
+  if (out)
+    *out = nullptr;
+  if (!h)
+    return SLOD_ERR_ARGUMENT;
+  if (!d_values || !d_cols || !out)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_factor_create: NULL array or out");
+  hipStream_t st;
+  if (const int rc = slod_enter(h, nullptr, &st))
+    return rc;
+  const SlodGrid G = slod_grid_of(h);
+  const int      s = G.spacedim, w = 2 * G.oversampling + 1, cap = slod_lod_row_capacity(h);
+  slod_lod_factor f;
+  f.h    = h;
+  f.n    = h->NP * s;
+  f.b    = s * (w * G.N + w) + s - 1;
+  f.nb   = (f.n + FB - 1) / FB;
+  f.bb   = (f.b + FB - 1) / FB;
+  // one allocation: the band, the factored diagonal tiles, the pivots, the reciprocal diagonal of L, then the row map
+  // and the status word
+  const size_t npad = (size_t)f.nb * FB, nband = (size_t)f.nb * (f.bb + 1) * FT, nd = nband + (size_t)f.nb * FT + 2 * npad;
+  f.bytes = nd * sizeof(double) + (npad + 1) * sizeof(int);
+  hipError_t e = f.mem.alloc(f.bytes); // freed with f on every error return below
+  if (e != hipSuccess)
+    return slod_hip_fail(h, e, "slod_lod_factor_create");
+  f.band   = (double *)f.mem.get();
+  f.diag   = f.band + nband;
+  f.piv    = f.diag + (size_t)f.nb * FT;
+  f.dinv   = f.piv + npad;
+  f.rowmap = (int *)(f.dinv + npad);
+  f.status = f.rowmap + npad;
+  std::vector<double> piv(npad);
+  int                 bad = -1;
+  e = hipMemsetAsync(f.band, 0, nd * sizeof(double), st);
+  if (e == hipSuccess)
+    e = hipMemsetAsync(f.status, 0xff, sizeof(int), st); // -1
+  if (e == hipSuccess)
+    {
+      const size_t nval = (size_t)h->NP * cap * s * s;
+      hipLaunchKernelGGL(k_factor_rowmap, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, st, G, f.n, (int)npad, f.bb, f.rowmap, f.band);
+      hipLaunchKernelGGL(k_factor_scatter, dim3((unsigned)((nval + 255) / 256)), dim3(256), 0, st, G, h->NP, cap, f.bb, d_values, d_cols,
+                         f.band);
+      for (int K = 0; K < f.nb; ++K)
+        hipLaunchKernelGGL(k_factor_column, dim3((unsigned)(std::min(f.bb, f.nb - 1 - K) + 1)), dim3(64), 0, st, K, f.bb, f.band, f.diag,
+                           f.piv, f.dinv, f.status);
+      e = hipGetLastError();
+    }
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(piv.data(), f.piv, npad * sizeof(double), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(&bad, f.status, sizeof(int), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(st);
+  if (e != hipSuccess)
+    {
+      (void)hipStreamSynchronize(st); // nothing may still run on the band when f frees it
+      return slod_hip_fail(h, e, "slod_lod_factor_create");
+    }
+  if (bad >= 0)
+    {
+      char msg[160];
+      std::snprintf(msg, sizeof msg, "slod_lod_factor_create: pivot %d of %d is not positive (%g): the matrix is not positive definite",
+                    bad, f.n, piv[(size_t)bad]);
+      return slod_fail(h, SLOD_ERR_NUMERIC, msg);
+    }
+  f.min_pivot = *std::min_element(piv.begin(), piv.begin() + f.n);
+  f.max_pivot = *std::max_element(piv.begin(), piv.begin() + f.n);
+  *out        = new slod_lod_factor(std::move(f));
+  return SLOD_OK;
+}
+
+int slod_lod_factor_get_info(const slod_lod_factor *f, slod_lod_factor_info *info)
+{
+  if (!f || !info)
+    return SLOD_ERR_ARGUMENT;
+  info->n              = f->n;
+  info->half_bandwidth = f->b;
+  info->block          = FB;
+  info->bytes          = f->bytes;
+  info->min_pivot      = f->min_pivot;
+  info->max_pivot      = f->max_pivot;
+  return SLOD_OK;
+}
+
+int slod_lod_factor_solve(slod_lod_factor *f, const double *d_rhs, size_t ld_rhs, int n_rhs, double *d_u, size_t ld_u, void *hip_stream)
+{
+  if (!f)
+    return SLOD_ERR_ARGUMENT;
+  slod_handle *h = f->h;
+  if (!d_rhs || !d_u)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_factor_solve: NULL array");
+  if (n_rhs < 1)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_factor_solve: n_rhs < 1");
+  if (const int rc = slod_check_ld(h, "slod_lod_factor_solve", "n_rhs", n_rhs, {ld_rhs, ld_u}))
+    return rc;
+  hipStream_t st;
+  if (const int rc = slod_enter(h, hip_stream, &st))
+    return rc;
+  slod_lod_factor_solve_launch(f, st, d_rhs, ld_rhs, n_rhs, d_u, ld_u);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_factor_solve");
+}
+
+void slod_lod_factor_destroy(slod_lod_factor *f)
+{
+  if (!f)
+    return;
+  (void)hipSetDevice(f->h->cfg.device);
+  (void)hipStreamSynchronize(f->h->stream); // a solve on the handle's stream may still read the band
+  delete f;
+}
+
+} // extern "C"
+#pragma GCC visibility pop

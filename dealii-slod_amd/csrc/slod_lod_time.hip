@@ -232,5 +232,50 @@ int slod_lod_theta_steps(slod_handle *h, const double *d_stiffness, const double
   return work.worst;
 }
 
+// The loop of slod_lod_theta_steps with the factor's two sweeps in place of the CG recurrence: the whole loop is queued
+// and the stream is waited for once.
+int slod_lod_theta_steps_direct(slod_handle *h, slod_lod_factor *f_S, const double *d_stiffness, const uint32_t *d_cols, double dt,
+                                double theta, int n_steps, int n_rhs, double *d_u, size_t ld_u, const double *d_load, size_t ld_load,
+                                size_t load_step_stride)
+{
+  if (!h)
+    return SLOD_ERR_ARGUMENT;
+  if (!d_stiffness || !d_cols || !d_u)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_theta_steps_direct: NULL matrix, d_cols or d_u");
+  if (!(dt > 0.0) || !(theta >= 0.0 && theta <= 1.0))
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_theta_steps_direct: dt <= 0 or theta outside [0, 1]");
+  if (n_steps < 1 || n_rhs < 1)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_theta_steps_direct: n_steps < 1 or n_rhs < 1");
+  if (const int rc = slod_check_ld(h, "slod_lod_theta_steps_direct", "n_rhs", n_rhs, {ld_u, d_load ? ld_load : ld_u}))
+    return rc;
+  if (const int rc = slod_lod_factor_check(h, "slod_lod_theta_steps_direct", f_S)) // last: it reads the factor
+    return rc;
+  hipStream_t st;
+  if (const int rc = slod_enter(h, nullptr, &st))
+    return rc;
+  const LodShape     w = lod_shape(h, n_rhs);
+  const size_t       nvec = (size_t)w.nrow * n_rhs;
+  SlodDevBuf<double> work; // g, delta
+  hipError_t         e = work.alloc(2 * nvec);
+  if (e == hipSuccess)
+    {
+      double *g = work.get(), *delta = g + nvec;
+      for (int k = 0; k < n_steps && e == hipSuccess; ++k)
+        {
+          const double *b0 = d_load ? d_load + (size_t)k * load_step_stride : nullptr;
+          const double *b1 = d_load ? d_load + (size_t)(k + 1) * load_step_stride : nullptr;
+          slod_lod_apply_launch(h, st, d_stiffness, d_cols, d_u, ld_u, n_rhs, g, (size_t)n_rhs);
+          hipLaunchKernelGGL(k_theta_rhs, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n_rhs, dt, theta, b0, b1, ld_load, g);
+          slod_lod_factor_solve_launch(f_S, st, g, (size_t)n_rhs, n_rhs, delta, (size_t)n_rhs);
+          hipLaunchKernelGGL(k_theta_advance, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n_rhs, delta, d_u, ld_u);
+          e = hipGetLastError();
+        }
+      const hipError_t es = hipStreamSynchronize(st); // the workspace is freed on return
+      if (e == hipSuccess)
+        e = es;
+    }
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_theta_steps_direct");
+}
+
 } // extern "C"
 #pragma GCC visibility pop

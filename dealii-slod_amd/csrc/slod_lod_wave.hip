@@ -300,5 +300,116 @@ int slod_lod_newmark_steps(slod_handle *h, const double *d_stiffness, const doub
   return work.worst;
 }
 
+// slod_lod_newmark_accel with the factor of M in place of the CG recurrence
+int slod_lod_newmark_accel_direct(slod_handle *h, slod_lod_factor *f_M, const double *d_stiffness, const double *d_mass,
+                                  const uint32_t *d_cols, double damp_mass, double damp_stiff, int n_rhs, const double *d_u, size_t ld_u,
+                                  const double *d_v, size_t ld_v, const double *d_load, size_t ld_load, double *d_a, size_t ld_a)
+{
+  if (!h)
+    return SLOD_ERR_ARGUMENT;
+  if (!d_stiffness || !d_mass || !d_cols || !d_u || !d_v || !d_a)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_accel_direct: NULL matrix, d_cols or state");
+  if (bad_damping(damp_mass, damp_stiff))
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_accel_direct: negative or NaN damping coefficient");
+  if (n_rhs < 1)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_accel_direct: n_rhs < 1");
+  if (const int rc = slod_check_ld(h, "slod_lod_newmark_accel_direct", "n_rhs", n_rhs, {ld_u, ld_v, ld_a, d_load ? ld_load : ld_u}))
+    return rc;
+  if (const int rc = slod_lod_factor_check(h, "slod_lod_newmark_accel_direct", f_M)) // last: it reads the factor
+    return rc;
+  hipStream_t st;
+  if (const int rc = slod_enter(h, nullptr, &st))
+    return rc;
+  const LodShape     w = lod_shape(h, n_rhs);
+  const size_t       nvec = (size_t)w.nrow * n_rhs;
+  SlodDevBuf<double> work; // w = u + damp_stiff v, g
+  hipError_t         e = work.alloc(2 * nvec);
+  if (e == hipSuccess)
+    {
+      double *arg = work.get(), *g = arg + nvec;
+      hipLaunchKernelGGL(k_nm_shift, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n_rhs, damp_stiff, d_u, ld_u, d_v, ld_v, arg);
+      hipLaunchKernelGGL(k_nm_rhs, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, w.s, w.cap, w.NP, n_rhs, d_stiffness,
+                         damp_mass != 0.0 ? d_mass : nullptr, d_cols, damp_mass, d_load, ld_load, arg, d_v, ld_v, g);
+      slod_lod_factor_solve_launch(f_M, st, g, (size_t)n_rhs, n_rhs, d_a, ld_a);
+      e = hipGetLastError();
+      const hipError_t es = hipStreamSynchronize(st); // the workspace is freed on return
+      if (e == hipSuccess)
+        e = es;
+    }
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_newmark_accel_direct");
+}
+
+// The loop of slod_lod_newmark_steps with the factor's two sweeps in place of the CG recurrence: the whole loop is queued
+// and the stream is waited for once.
+int slod_lod_newmark_steps_direct(slod_handle *h, slod_lod_factor *f_S, const double *d_stiffness, const double *d_mass,
+                                  const uint32_t *d_cols, double dt, double beta, double gamma, double damp_mass, double damp_stiff,
+                                  int n_steps, int n_rhs, double *d_u, size_t ld_u, double *d_v, size_t ld_v, double *d_a, size_t ld_a,
+                                  const double *d_load, size_t ld_load, size_t load_step_stride, double *kinetic, double *potential)
+{
+  if (!h)
+    return SLOD_ERR_ARGUMENT;
+  if (!d_stiffness || !d_mass || !d_cols || !d_u || !d_v || !d_a)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_steps_direct: NULL matrix, d_cols or state");
+  if (!(dt > 0.0) || !(beta >= 0.0 && beta <= 0.5) || !(gamma >= 0.0 && gamma <= 1.0))
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_steps_direct: dt <= 0, beta outside [0, 1/2] or gamma outside [0, 1]");
+  if (bad_damping(damp_mass, damp_stiff))
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_steps_direct: negative or NaN damping coefficient");
+  if (n_steps < 1 || n_rhs < 1)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_steps_direct: n_steps < 1 or n_rhs < 1");
+  if (const int rc = slod_check_ld(h, "slod_lod_newmark_steps_direct", "n_rhs", n_rhs, {ld_u, ld_v, ld_a, d_load ? ld_load : ld_u}))
+    return rc;
+  if ((kinetic == nullptr) != (potential == nullptr))
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_newmark_steps_direct: kinetic and potential come together or not at all");
+  if (const int rc = slod_lod_factor_check(h, "slod_lod_newmark_steps_direct", f_S)) // last: it reads the factor
+    return rc;
+  hipStream_t st;
+  if (const int rc = slod_enter(h, nullptr, &st))
+    return rc;
+  const LodShape w = lod_shape(h, n_rhs);
+  const bool     energies = kinetic != nullptr;
+  const size_t   nvec = (size_t)w.nrow * n_rhs, npart = energies ? (size_t)w.ngroup * n_rhs : 0;
+  const size_t   nenergy = energies ? 2 * (size_t)(n_steps + 1) * n_rhs : 0;
+  // w = u~ + damp_stiff v~, g, and for the energies two arrays of partials and [level][kinetic, potential][column]
+  SlodDevBuf<double> work;
+  hipError_t         e = work.alloc(2 * nvec + 2 * npart + nenergy);
+  if (e == hipSuccess)
+    {
+      double        *arg = work.get(), *g = arg + nvec, *part_k = g + nvec, *part_p = part_k + npart, *d_energy = part_p + npart;
+      const dim3     nblk = lod_flat_grid(nvec);
+      const InnerJob jk{d_mass, d_v, d_v, ld_v, ld_v, part_k}, jp{d_stiffness, d_u, d_u, ld_u, ld_u, part_p};
+      const double   gdt = gamma * dt, bdt2 = beta * dt * dt;
+      if (energies)
+        launch_inner(w, st, d_cols, n_rhs, 2, jk, jp, 0.5, d_energy);
+      e = hipGetLastError();
+      for (int k = 0; k < n_steps && e == hipSuccess; ++k)
+        {
+          const double *b1 = d_load ? d_load + (size_t)(k + 1) * load_step_stride : nullptr;
+          hipLaunchKernelGGL(k_nm_predict, nblk, dim3(256), 0, st, w.nrow, n_rhs, dt, dt * dt * (0.5 - beta), dt * (1.0 - gamma),
+                             damp_stiff, d_u, ld_u, d_v, ld_v, d_a, ld_a, arg);
+          hipLaunchKernelGGL(k_nm_rhs, nblk, dim3(256), 0, st, w.nrow, w.s, w.cap, w.NP, n_rhs, d_stiffness,
+                             damp_mass != 0.0 ? d_mass : nullptr, d_cols, damp_mass, b1, ld_load, arg, d_v, ld_v, g);
+          slod_lod_factor_solve_launch(f_S, st, g, (size_t)n_rhs, n_rhs, d_a, ld_a);
+          hipLaunchKernelGGL(k_nm_correct, nblk, dim3(256), 0, st, w.nrow, n_rhs, bdt2, gdt, d_u, ld_u, d_v, ld_v, d_a, ld_a);
+          if (energies)
+            launch_inner(w, st, d_cols, n_rhs, 2, jk, jp, 0.5, d_energy + 2 * (size_t)(k + 1) * n_rhs);
+          e = hipGetLastError();
+        }
+      std::vector<double> host(nenergy);
+      if (e == hipSuccess && energies)
+        e = hipMemcpyAsync(host.data(), d_energy, nenergy * sizeof(double), hipMemcpyDeviceToHost, st);
+      const hipError_t es = hipStreamSynchronize(st); // the workspace is freed on return
+      if (e == hipSuccess)
+        e = es;
+      if (e == hipSuccess && energies)
+        for (size_t k = 0; k <= (size_t)n_steps; ++k)
+          for (size_t c = 0; c < (size_t)n_rhs; ++c)
+            {
+              kinetic[k * n_rhs + c]   = host[2 * k * n_rhs + c];
+              potential[k * n_rhs + c] = host[(2 * k + 1) * n_rhs + c];
+            }
+    }
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_newmark_steps_direct");
+}
+
 } // extern "C"
 #pragma GCC visibility pop

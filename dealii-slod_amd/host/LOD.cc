@@ -24,6 +24,8 @@ namespace slod
   template <int dim, int spacedim>
   LOD<dim, spacedim>::~LOD()
   {
+    for (slod_lod_factor *f : factors)
+      slod_lod_factor_destroy(f);
     for (void *p : device_arrays)
       (void)hipFree(p);
     slod_destroy(handle);
@@ -561,7 +563,17 @@ namespace slod
   }
 
   template <int dim, int spacedim>
-  void LOD<dim, spacedim>::solve_heat(const unsigned int n_steps, const double dt, const double theta)
+  slod_lod_factor *LOD<dim, spacedim>::factor_lod_matrix(const double *d_values)
+  {
+    slod_lod_factor *f = nullptr;
+    check(slod_lod_factor_create(handle, d_values, d_lod_cols, &f), "slod_lod_factor_create");
+    factors.push_back(f);
+    check(slod_lod_factor_get_info(f, &lod_factor_info), "slod_lod_factor_get_info");
+    return f;
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_heat(const unsigned int n_steps, const double dt, const double theta, const bool direct)
   {
     if (!d_lod_mass || !d_fem_rhs)
       throw std::runtime_error("solve_heat: assemble_mass_matrix and assemble_and_solve_fem_problem come first");
@@ -580,6 +592,22 @@ namespace slod
       throw std::runtime_error("solve_heat: clearing the initial state failed");
     lod_heat_iterations.assign(n_steps, 0);
     lod_heat_residuals.assign(n_steps, 0.0);
+    if (direct)
+      {
+        // S = M + theta dt A_LOD with the coefficients of slod_lod_theta_steps; the factor reads its lower triangle
+        const int cap = slod_lod_row_capacity(handle);
+        check(cap, "slod_lod_row_capacity");
+        if (!d_lod_shifted)
+          d_lod_shifted = device_alloc<double>((std::size_t)n_patches * cap * spacedim * spacedim);
+        check(slod_lod_matrix_combine(handle, 1.0, d_lod_mass, theta * dt, d_lod_values, d_lod_shifted, nullptr),
+              "slod_lod_matrix_combine");
+        if (hipDeviceSynchronize() != hipSuccess)
+          throw std::runtime_error("solve_heat: forming S failed");
+        slod_lod_factor *f = factor_lod_matrix(d_lod_shifted);
+        check(slod_lod_theta_steps_direct(handle, f, d_lod_values, d_lod_cols, dt, theta, (int)n_steps, 1, d_heat_u, 1, d_heat_rhs, 1, 0),
+              "slod_lod_theta_steps_direct");
+        return;
+      }
     check(slod_lod_theta_steps(handle, d_lod_values, d_lod_mass, d_lod_cols, dt, theta, (int)n_steps, 1, d_heat_u, 1, d_heat_rhs, 1,
                                0, lod_rel_tol, lod_max_iterations, lod_heat_iterations.data(), lod_heat_residuals.data()),
           "slod_lod_theta_steps");
@@ -642,7 +670,8 @@ namespace slod
   }
 
   template <int dim, int spacedim>
-  void LOD<dim, spacedim>::solve_wave(const unsigned int n_steps, const double dt, const double beta, const double gamma)
+  void LOD<dim, spacedim>::solve_wave(const unsigned int n_steps, const double dt, const double beta, const double gamma,
+                                      const bool direct)
   {
     if (!d_lod_mass || !d_fem_rhs)
       throw std::runtime_error("solve_wave: assemble_mass_matrix and assemble_and_solve_fem_problem come first");
@@ -670,9 +699,27 @@ namespace slod
     std::vector<double> b(n_coarse), u(n_coarse);
     if (hipMemcpy(b.data(), d_b, n_coarse * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
       throw std::runtime_error("solve_wave: download of the load failed");
-    const int rc = slod_lod_newmark_accel(handle, d_lod_sym, d_lod_mass, d_lod_cols, 0.0, 0.0, 1, d_u, 1, d_v, 1, d_b, 1, d_a, 1,
-                                          lod_rel_tol, lod_max_iterations, nullptr, nullptr);
-    check(rc < 0 ? rc : 0, "slod_lod_newmark_accel");
+    slod_lod_factor *f_S = nullptr;
+    if (direct)
+      {
+        // the factor of M for the initial acceleration, then that of S = M + beta dt^2 A (no damping) for every step
+        check(slod_lod_newmark_accel_direct(handle, factor_lod_matrix(d_lod_mass), d_lod_sym, d_lod_mass, d_lod_cols, 0.0, 0.0, 1, d_u,
+                                            1, d_v, 1, d_b, 1, d_a, 1),
+              "slod_lod_newmark_accel_direct");
+        if (!d_lod_shifted)
+          d_lod_shifted = device_alloc<double>((std::size_t)n_patches * cap * spacedim * spacedim);
+        check(slod_lod_matrix_combine(handle, 1.0, d_lod_mass, beta * dt * dt, d_lod_sym, d_lod_shifted, nullptr),
+              "slod_lod_matrix_combine");
+        if (hipDeviceSynchronize() != hipSuccess)
+          throw std::runtime_error("solve_wave: forming S failed");
+        f_S = factor_lod_matrix(d_lod_shifted);
+      }
+    else
+      {
+        const int rc = slod_lod_newmark_accel(handle, d_lod_sym, d_lod_mass, d_lod_cols, 0.0, 0.0, 1, d_u, 1, d_v, 1, d_b, 1, d_a, 1,
+                                              lod_rel_tol, lod_max_iterations, nullptr, nullptr);
+        check(rc < 0 ? rc : 0, "slod_lod_newmark_accel");
+      }
     lod_wave_iterations.assign(n_steps, 0);
     lod_wave_residuals.assign(n_steps, 0.0);
     lod_wave_kinetic.assign(n_steps + 1, 0.0);
@@ -681,10 +728,17 @@ namespace slod
     for (unsigned int k = 0; k < n_steps; ++k)
       {
         double    kinetic[2], potential[2];
-        const int its = slod_lod_newmark_steps(handle, d_lod_sym, d_lod_mass, d_lod_cols, dt, beta, gamma, 0.0, 0.0, 1, 1, d_u, 1,
-                                               d_v, 1, d_a, 1, d_b, 1, 0, lod_rel_tol, lod_max_iterations, &lod_wave_iterations[k],
-                                               &lod_wave_residuals[k], kinetic, potential);
-        check(its < 0 ? its : 0, "slod_lod_newmark_steps");
+        if (direct)
+          check(slod_lod_newmark_steps_direct(handle, f_S, d_lod_sym, d_lod_mass, d_lod_cols, dt, beta, gamma, 0.0, 0.0, 1, 1, d_u, 1,
+                                              d_v, 1, d_a, 1, d_b, 1, 0, kinetic, potential),
+                "slod_lod_newmark_steps_direct");
+        else
+          {
+            const int its = slod_lod_newmark_steps(handle, d_lod_sym, d_lod_mass, d_lod_cols, dt, beta, gamma, 0.0, 0.0, 1, 1, d_u, 1,
+                                                   d_v, 1, d_a, 1, d_b, 1, 0, lod_rel_tol, lod_max_iterations,
+                                                   &lod_wave_iterations[k], &lod_wave_residuals[k], kinetic, potential);
+            check(its < 0 ? its : 0, "slod_lod_newmark_steps");
+          }
         if (hipMemcpy(u.data(), d_u, n_coarse * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
           throw std::runtime_error("solve_wave: download of the state failed");
         if (k == 0)

@@ -128,7 +128,14 @@ namespace slod
     void assemble_mass_matrix();
     // n_steps of the theta scheme for M u' + A u = C^T f_h from u = 0 with the load of solve(), constant in time,
     // through slod_lod_theta_steps; after assemble_mass_matrix() and assemble_and_solve_fem_problem()
-    void solve_heat(const unsigned int n_steps, const double dt, const double theta);
+    // direct: the steps run on the banded Cholesky factor of S = M + theta dt A_LOD (lower triangle; factor_lod_matrix,
+    // slod_lod_theta_steps_direct) and there are no iteration counts or residuals
+    void solve_heat(const unsigned int n_steps, const double dt, const double theta, const bool direct = false);
+    // The banded Cholesky factor of a symmetric positive definite matrix on the pattern of A_LOD (device values in the
+    // layout of slod_lod_matrix): slod_lod_factor_create; the object owns the factor and frees it with itself.
+    // last_factor_info() describes the factor made last.
+    slod_lod_factor            *factor_lod_matrix(const double *d_values);
+    const slod_lod_factor_info &last_factor_info() const { return lod_factor_info; }
     const std::vector<int>    &heat_iterations() const { return lod_heat_iterations; }
     const std::vector<double> &heat_rel_residuals() const { return lod_heat_residuals; }
     // norms of C u_H - C u_heat: the final state against the elliptic SLOD solution of solve(), and of C u_H alone
@@ -148,8 +155,9 @@ namespace slod
     // slod_lod_newmark_accel) with the load of solve(), constant in time and undamped, on the symmetrised A_LOD; after
     // assemble_mass_matrix() and assemble_and_solve_fem_problem().  One slod_lod_newmark_steps call per step (the calls
     // compose bit for bit), so that the work u^T b of every state can be formed on the host; then the final state on the
-    // fine grid and its norms.
-    void solve_wave(const unsigned int n_steps, const double dt, const double beta, const double gamma);
+    // fine grid and its norms.  direct: the initial acceleration on the factor of M_LOD and the steps on the factor of
+    // S = M + beta dt^2 sym(A_LOD) (slod_lod_newmark_accel_direct, slod_lod_newmark_steps_direct); no iteration counts.
+    void solve_wave(const unsigned int n_steps, const double dt, const double beta, const double gamma, const bool direct = false);
     const std::vector<int>    &wave_iterations() const { return lod_wave_iterations; }   // per step
     const std::vector<double> &wave_rel_residuals() const { return lod_wave_residuals; } // per step
     // n_steps + 1 entries each, entry 0 the state at rest: v^T M v / 2, u^T A u / 2 and u^T b
@@ -247,6 +255,10 @@ namespace slod
     std::vector<int>    lod_wave_iterations;
     std::vector<double> lod_wave_residuals, lod_wave_kinetic, lod_wave_potential, lod_wave_work;
     slod_error_norms    wave_norms{};
+    // factor_lod_matrix: the factors this object owns, the matrix S of a direct time loop
+    std::vector<slod_lod_factor *> factors;
+    slod_lod_factor_info           lod_factor_info{};
+    double                        *d_lod_shifted = nullptr;
     // solve_multi: fine load vectors and reconstructions, field k at + k * fine_size
     double                       *d_multi_fem_rhs = nullptr, *d_multi_fine = nullptr;
     std::vector<int>              lod_multi_iterations;

@@ -6,6 +6,7 @@ compute entry points raise SlodError if no HIP device is usable.
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -44,6 +45,12 @@ class ErrorNorms(C.Structure):
     """slod_error_norms: per-component L2, H1-seminorm and max-norm of e = u - v - w, and a(e,e)^{1/2}."""
     _fields_ = [("l2", C.c_double * 2), ("h1_semi", C.c_double * 2), ("linf", C.c_double * 2),
                 ("energy", C.c_double), ("reserved", C.c_double * 3)]
+
+
+class FactorInfo(C.Structure):
+    """slod_lod_factor_info: rows, half bandwidth, tile edge, device bytes, pivot range of the banded Cholesky factor."""
+    _fields_ = [("n", C.c_int32), ("half_bandwidth", C.c_int32), ("block", C.c_int32), ("bytes", C.c_uint64),
+                ("min_pivot", C.c_double), ("max_pivot", C.c_double)]
 
 
 _lib = None
@@ -131,6 +138,18 @@ def load():
     lib.slod_lod_newmark_steps.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                            C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t,
                                            C.c_size_t, C.c_double, C.c_int, C.POINTER(C.c_int), dp, dp, dp]
+    lib.slod_lod_factor_create.argtypes = [vp, vp, vp, C.POINTER(vp)]
+    lib.slod_lod_factor_get_info.argtypes = [vp, C.POINTER(FactorInfo)]
+    lib.slod_lod_factor_solve.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp]
+    lib.slod_lod_factor_destroy.argtypes = [vp]
+    lib.slod_lod_factor_destroy.restype = None
+    lib.slod_lod_theta_steps_direct.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.c_size_t, vp,
+                                                C.c_size_t, C.c_size_t]
+    lib.slod_lod_newmark_accel_direct.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, C.c_size_t, vp,
+                                                  C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]
+    lib.slod_lod_newmark_steps_direct.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                  C.c_double, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t,
+                                                  vp, C.c_size_t, C.c_size_t, dp, dp]
     lib.slod_lod_matrix_ensemble.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, vp, vp]
     lib.slod_lod_rhs_ensemble.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp]
     lib.slod_lod_apply_ensemble.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp]
@@ -301,6 +320,38 @@ class Plan:
             pass
 
 
+class Factor:
+    """slod_lod_factor: the banded Cholesky factor of a full set of block rows; factor once, solve many."""
+
+    def __init__(self, slod, d_values, d_cols):
+        self.slod, self.lib = slod, slod.lib
+        self.f = C.c_void_p()
+        slod._check(self.lib.slod_lod_factor_create(slod.h, d_values, d_cols, C.byref(self.f)))
+        self.info = FactorInfo()
+        slod._check(self.lib.slod_lod_factor_get_info(self.f, C.byref(self.info)))
+        slod._factors.add(self)                        # the handle closes its factors before itself
+
+    def solve(self, d_rhs, d_u, n_rhs=1, ld_rhs=None, ld_u=None, stream=None):
+        """U = A^-1 RHS on coarse multi-vectors (ld defaults to n_rhs); d_u may be d_rhs.  Asynchronous."""
+        self.slod._check(self.lib.slod_lod_factor_solve(self.f, d_rhs, n_rhs if ld_rhs is None else ld_rhs, n_rhs, d_u,
+                                                        n_rhs if ld_u is None else ld_u, stream))
+
+    def close(self):
+        if self.f:
+            self.lib.slod_lod_factor_destroy(self.f)
+            self.f = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _factor_ptr(f):
+    return f.f if isinstance(f, Factor) else f
+
+
 class Slod:
     """Thin OO wrapper over a slod_handle."""
 
@@ -310,6 +361,7 @@ class Slod:
         self.cfg = Config(2, spacedim, nref, n_cells, n_sub, oversampling, stabilize, reuse_full,
                           proj_quirk, n_problems, device, 0)
         self.h = C.c_void_p()
+        self._factors = weakref.WeakSet()
         rc = self.lib.slod_create(C.byref(self.cfg), C.byref(self.h))
         if rc:
             raise SlodError(rc, self.lib.slod_last_error(None).decode())
@@ -324,6 +376,8 @@ class Slod:
 
     def close(self):
         if self.h:
+            for f in list(self._factors):
+                f.close()
             self.lib.slod_destroy(self.h)
             self.h = None
 
@@ -547,6 +601,42 @@ class Slod:
         if rc < 0:
             self._check(rc)
         return its[:n_steps], res[:n_steps], kin, pot
+
+    # ---- the direct solver: banded Cholesky of a full set of block rows, and the time loops on a factor ----
+    def lod_factor(self, d_values, d_cols):
+        """The Cholesky factor of a symmetric positive definite matrix in block rows: an object with .info (n,
+        half_bandwidth, block, bytes, min_pivot, max_pivot), .solve(d_rhs, d_u, n_rhs, ...) and .close().
+        SlodError(-5) when a pivot is not positive."""
+        return Factor(self, d_values, d_cols)
+
+    def lod_theta_steps_direct(self, factor, d_stiffness, d_cols, dt, theta, n_steps, d_u, n_rhs=1, ld_u=None, d_load=None,
+                               ld_load=None, load_step_stride=0):
+        """lod_theta_steps on the factor of S = M + theta dt A (lod_matrix_combine(1, M, theta * dt, A))."""
+        self._check(self.lib.slod_lod_theta_steps_direct(self.h, _factor_ptr(factor), d_stiffness, d_cols, dt, theta, n_steps,
+                                                         n_rhs, d_u, n_rhs if ld_u is None else ld_u, d_load,
+                                                         n_rhs if ld_load is None else ld_load, load_step_stride))
+
+    def lod_newmark_accel_direct(self, factor, d_stiffness, d_mass, d_cols, d_u, d_v, d_a, n_rhs=1, ld_u=None, ld_v=None,
+                                 ld_a=None, d_load=None, ld_load=None, damp_mass=0.0, damp_stiff=0.0):
+        """lod_newmark_accel on the factor of M."""
+        self._check(self.lib.slod_lod_newmark_accel_direct(
+            self.h, _factor_ptr(factor), d_stiffness, d_mass, d_cols, damp_mass, damp_stiff, n_rhs, d_u,
+            n_rhs if ld_u is None else ld_u, d_v, n_rhs if ld_v is None else ld_v, d_load,
+            n_rhs if ld_load is None else ld_load, d_a, n_rhs if ld_a is None else ld_a))
+
+    def lod_newmark_steps_direct(self, factor, d_stiffness, d_mass, d_cols, dt, n_steps, d_u, d_v, d_a, beta=0.25, gamma=0.5,
+                                 n_rhs=1, ld_u=None, ld_v=None, ld_a=None, d_load=None, ld_load=None, load_step_stride=0,
+                                 damp_mass=0.0, damp_stiff=0.0, energies=True):
+        """lod_newmark_steps on the factor of S = (1 + gamma dt damp_mass) M + (beta dt^2 + gamma dt damp_stiff) A.
+        Returns (kinetic, potential) as arrays [n_steps + 1, n_rhs], or (None, None) with energies=False."""
+        shape = (max(n_steps, 0) + 1, max(n_rhs, 1))
+        kin, pot = (np.zeros(shape), np.zeros(shape)) if energies else (None, None)
+        self._check(self.lib.slod_lod_newmark_steps_direct(
+            self.h, _factor_ptr(factor), d_stiffness, d_mass, d_cols, dt, beta, gamma, damp_mass, damp_stiff, n_steps, n_rhs,
+            d_u, n_rhs if ld_u is None else ld_u, d_v, n_rhs if ld_v is None else ld_v, d_a, n_rhs if ld_a is None else ld_a,
+            d_load, n_rhs if ld_load is None else ld_load, load_step_stride, _dp(kin) if energies else None,
+            _dp(pot) if energies else None))
+        return kin, pot
 
     # ---- the LOD systems of a coefficient ensemble: member k = problem k of the handle = column k of the coarse
     # multi-vectors; matrix values member-minor, entry e of member k at [e * ld_m + k] (include/slod.h) ----

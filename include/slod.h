@@ -432,6 +432,70 @@ int slod_lod_newmark_steps(slod_handle *h, const double *d_stiffness, const doub
                            double *kinetic      /* HOST [(n_steps + 1) * n_rhs], may be NULL */,
                            double *potential    /* HOST [(n_steps + 1) * n_rhs], may be NULL */);
 
+/* ---- a direct solver on the LOD space: banded Cholesky, factor once, solve many --------------
+ * The systems of the LOD space are small and, inside a time loop, never change.  In row-major cell order a block row
+ * (slot j = the neighbour at cell offset (j % span, j / span) - span / 2, span = 4 l + 3) is a band of half width
+ *   b = s (w N + w) + s - 1,  w = 2 l + 1,
+ * and  A = L L^T  in band storage serves every later solve with two sweeps and no tolerance to tune (the reference has
+ * no counterpart).  Factor ordering: unknown (p, d) has the index r = (cy N + cx) s + d, (cx, cy) the centre cell of
+ * patch p, for Morton and for row-major patch ids alike; the permutation is internal, callers keep their patch order. */
+typedef struct slod_lod_factor slod_lod_factor;
+typedef struct
+{
+  int32_t  n, half_bandwidth, block; /* rows; b above; the edge of the square tiles of the band (16)                  */
+  uint64_t bytes;                    /* device bytes the factor owns                                                  */
+  double   min_pivot, max_pivot;     /* the smallest and largest diagonal entry of L, squared                         */
+} slod_lod_factor_info;
+/* Factors a symmetric positive definite matrix given as a full set of block rows (rows 0 .. num_patches-1 in the layout
+ * of slod_lod_matrix: the output of slod_lod_matrix_symmetrize, slod_lod_mass_matrix, or a slod_lod_matrix_combine of
+ * the two).  ONLY THE LOWER TRIANGLE IN FACTOR ORDER IS READ: an entry ((p, d), (q, e)) with r(q, e) <= r(p, d), taken
+ * from the block row of its row's patch p; for a bit-symmetric input that makes no difference.  Allocates everything the
+ * factor will ever need (the band in 16 x 16 tiles, at most about 8 n (b + 48) bytes), runs on the handle's stream (one launch
+ * per block column of 16, queued without a host wait) and synchronises.
+ * SLOD_ERR_NUMERIC: a pivot is not > 0 (an indefinite matrix, NaN in the input); slod_last_error names the call and the
+ * index r of the first such pivot; *out stays NULL and nothing stays allocated.  SLOD_ERR_ARGUMENT (before any device
+ * work): NULL handle, array or out.  SLOD_ERR_DEVICE without a usable GPU.  The factor belongs to the handle and must be
+ * destroyed before it. */
+int slod_lod_factor_create(slod_handle *h, const double *d_values, const uint32_t *d_cols, slod_lod_factor **out);
+int slod_lod_factor_get_info(const slod_lod_factor *f, slod_lod_factor_info *info);
+/* U = A^-1 RHS for n_rhs >= 1 columns, coarse multi-vectors of the _multi calls (entry (i, c) at base[i * ld + c], rows
+ * in the caller's patch order).  d_u == d_rhs is allowed.  Asynchronous on hip_stream (NULL: the handle's); allocates
+ * nothing and reads nothing back, so it can be captured like slod_plan_execute.  Entries c >= n_rhs of a row are never
+ * read or written.  One block per 16 columns walks the block rows forwards, then backwards; every sum has a fixed order
+ * (no atomics): the bits of column c of U depend only on the factor and on column c of RHS, not on n_rhs, an ld, the
+ * column's position or the run.  The intermediate vector of the sweeps lives in d_u.  The factor is read only: solves
+ * on several streams may share it.  SLOD_ERR_ARGUMENT: NULL factor or array, n_rhs < 1, ld < n_rhs. */
+int slod_lod_factor_solve(slod_lod_factor *f, const double *d_rhs, size_t ld_rhs, int n_rhs, double *d_u, size_t ld_u,
+                          void *hip_stream);
+/* Waits for the handle's stream, then frees the factor.  NULL is allowed. */
+void slod_lod_factor_destroy(slod_lod_factor *f);
+/* The recursions of slod_lod_theta_steps, slod_lod_newmark_accel and slod_lod_newmark_steps (above, the same elementwise,
+ * product and energy kernels) with the solve of a step done by slod_lod_factor_solve on a factor the caller built:
+ *   slod_lod_theta_steps_direct    f_S factors  S = slod_lod_matrix_combine(1, M, theta dt, A)
+ *   slod_lod_newmark_accel_direct  f_M factors  M
+ *   slod_lod_newmark_steps_direct  f_S factors  S = slod_lod_matrix_combine(1 + gamma dt damp_mass, M,
+ *                                                                          beta dt^2 + gamma dt damp_stiff, A)
+ * with A the symmetrised stiffness; that the factor belongs to these coefficients is not checked.  One factor serves
+ * any number of calls with the same dt and parameters.  There is no tolerance and no iteration count; nothing is read
+ * back per step: the loop is queued on the handle's stream and waited for once, the energies are copied once at the
+ * end.  A column's bits depend only on the factor, the matrices, the parameters and that column's state and loads, and
+ * one call with n_steps = 2 equals two calls with n_steps = 1.  Return SLOD_OK or a negative slod_status.
+ * SLOD_ERR_ARGUMENT: as the call without _direct, less rel_tol / max_iterations; a NULL factor; the factor of another
+ * handle or row count.  Run on the handle's stream; synchronise. */
+int slod_lod_theta_steps_direct(slod_handle *h, slod_lod_factor *f_S, const double *d_stiffness, const uint32_t *d_cols,
+                                double dt, double theta, int n_steps, int n_rhs, double *d_u, size_t ld_u,
+                                const double *d_load, size_t ld_load, size_t load_step_stride);
+int slod_lod_newmark_accel_direct(slod_handle *h, slod_lod_factor *f_M, const double *d_stiffness, const double *d_mass,
+                                  const uint32_t *d_cols, double damp_mass, double damp_stiff, int n_rhs,
+                                  const double *d_u, size_t ld_u, const double *d_v, size_t ld_v,
+                                  const double *d_load /* b^0, NULL = 0 */, size_t ld_load, double *d_a, size_t ld_a);
+int slod_lod_newmark_steps_direct(slod_handle *h, slod_lod_factor *f_S, const double *d_stiffness, const double *d_mass,
+                                  const uint32_t *d_cols, double dt, double beta, double gamma, double damp_mass,
+                                  double damp_stiff, int n_steps, int n_rhs, double *d_u, size_t ld_u, double *d_v, size_t ld_v,
+                                  double *d_a, size_t ld_a, const double *d_load, size_t ld_load, size_t load_step_stride,
+                                  double *kinetic   /* HOST [(n_steps + 1) * n_rhs], may be NULL */,
+                                  double *potential /* HOST [(n_steps + 1) * n_rhs], may be NULL */);
+
 /* ---- the LOD systems of a coefficient ensemble, one call per step for all members --------------
  * A handle with n_problems = K builds the bases of K coefficient realisations in one plan; these calls carry the
  * ensemble through the LOD space: K matrices, K loads, K solves, K reconstructions, then mean and variance (the
