@@ -83,6 +83,8 @@ struct SlodKernelArgs
                     // is there, 0.0: the patch fell back); stride slod_mt_stride, not the stamps of ms
   int32_t m_tw;     // 1: k_solve_tw builds M in its sweeps where the patch allows it
   int32_t bwd_ksplit; // 1: k_solve_tw splits the backward sweep's GEMM by K half between the chain's two waves
+  int32_t svd_regs; // 1: the SVD fallback of the selection stage keeps a Jacobi pair's rows and the pivoted QR's column
+                    // order in registers (patches of at most 32 columns; 0: the loops that go through LDS)
   int32_t nb_buf;   // rows of the selection stage's boundary-trace buffer
   int32_t nf_max;   // largest n_fine of the plan
   int32_t fuse_select; // set by slod_launch_solve: the solve kernel also ran the selection stage
@@ -110,13 +112,14 @@ struct SlodTuning
   int twisted = -1;      // coop kernel only: -1 = automatic
   int balance = 1;       // launch order balanced over the CUs (SLOD_BALANCE=0: the caller's order)
   int bwd_ksplit = 1;    // k_solve_tw backward sweep: K split over the chain's two waves (SLOD_BWD_KSPLIT=0: column split)
+  int svd_regs = 1;      // selection stage, SVD fallback: Jacobi pairs and the pivot order in registers (SLOD_SVD_REGS=0: LDS loops)
   int debug = 0;
 };
 struct SlodSolveChoice
 {
   int    kind = 0;
   size_t lds  = 0;
-  int    fuse_select = 0, fuse_assemble = 0, m_tw = 0, bwd_ksplit = 0, twisted = 0, debug = 0;
+  int    fuse_select = 0, fuse_assemble = 0, m_tw = 0, bwd_ksplit = 0, svd_regs = 0, twisted = 0, debug = 0;
   int    v_line_pad = 0; // rows = columns of a V line as the kernel sees it
   size_t v_line_elems = 0; // doubles per stored V line (k_solve_tw: the 8 x 8 lane tiles, both triangles)
   int    nv = 0;            // k_solve_nd: cell size

@@ -16,6 +16,9 @@
 //                             selection stage computes M from X again (for A/B timing)
 //   SLOD_BWD_KSPLIT=0|1       tw backward sweep (lines of at most three row tiles, nc_max <= 32): K of X = Z - V Y
 //                             split between the chain's two waves (default) or, 0, the column-tile split
+//   SLOD_SVD_REGS=0|1         SVD fallback of the selection stage (scalar patches of at most 32 columns after the QR): a Jacobi
+//                             pair's rows and the pivoted QR's column order live in registers (default) or, 0, the
+//                             loops that read them from LDS (what every other patch shape runs; same bits)
 //   SLOD_TWISTED=0|1 (coop only) SLOD_DEBUG=1 print the choice
 //   SLOD_BALANCE=0            launch the patches in the caller's order (default: balanced over the CUs)
 SlodTuning slod_read_tuning()
@@ -32,6 +35,8 @@ SlodTuning slod_read_tuning()
     t.fuse_m = atoi(e) ? 1 : 0;
   if (const char *e = getenv("SLOD_BWD_KSPLIT"))
     t.bwd_ksplit = atoi(e) ? 1 : 0;
+  if (const char *e = getenv("SLOD_SVD_REGS"))
+    t.svd_regs = atoi(e) ? 1 : 0;
   if (const char *e = getenv("SLOD_TWISTED"))
     t.twisted = atoi(e) ? 1 : 0;
   if (const char *e = getenv("SLOD_BALANCE"))
@@ -63,6 +68,7 @@ bool slod_choose_solver(int S, int n_sub, int m_max, int L_max, int nc_max, int 
   if (t.solver == SLOD_K_ND && nd_nv == 0)
     t.solver = 0; // nested dissection does not take this plan (vector problem, cell size): automatic choice
   c.debug = t.debug;
+  c.svd_regs = t.svd_regs ? 1 : 0;
   // Kernel families:
   //   tw   twisted + wave-specialised VALU Gauss-Jordan (default: fastest on every BASELINE size,
   //        tools/solver_compare.py)
@@ -153,6 +159,7 @@ hipError_t slod_launch_solve(int S, const SlodSolveChoice &c, SlodKernelArgs &a,
 {
   a.m_tw          = c.m_tw;
   a.bwd_ksplit    = c.bwd_ksplit;
+  a.svd_regs      = c.svd_regs;
   a.fuse_select   = c.fuse_select;
   a.fuse_assemble = c.fuse_assemble;
   a.debug         = c.debug;

@@ -806,6 +806,12 @@ namespace
                 int        pb     = 0;               // current buffer of the column order pcol
                 for (int j = tid; j < nn1; j += 256)
                   pcol[j] = j;
+                // at most 32 columns after the QR (nn1 <= 31, and the nn1 + 1 <= 32 rows that take the
+                // rotations are two per lane of a 16-lane group): the pivoted QR keeps its column order and
+                // the sweeps keep the rows of a pair in registers (A.svd_regs = 0: the loops through LDS,
+                // which every other shape runs; the arithmetic and its order are the same).  Scalar problems
+                // only: k_select<2> sits at its 256-VGPR cap and would pay for the variant with 20 B more scratch
+                const bool regs = S == 1 && tposed && nc <= 32 && A.svd_regs;
                 if (tposed && nc <= 32 && !(SLOD_DG(A, 65536)))
                   {
                     // Second-stage QR of R WITH column pivoting, R P = Q' R' (Drmac/Veselic
@@ -831,6 +837,9 @@ namespace
                           sig[j] = nrm;
                       }
                     __syncthreads();
+                    // regs: lane j of every wave holds the column at position j (every wave searches on its own
+                    // and makes the same swaps); pcol is written once, behind the loop
+                    int mypc = lane < nn1 ? lane : 0;
                     for (int k = 0; k < nn1; ++k)
                       {
                         const int    *pc  = pcol + pb * ncm;
@@ -846,7 +855,7 @@ namespace
                         double best;
                         {
                           const bool pin = lane >= k && lane < nn1;
-                          double     v   = cnc[pc[pin ? lane : k]];
+                          double     v   = regs ? cnc[mypc] : cnc[pc[pin ? lane : k]];
                           int        q   = pin ? lane : 64;
                           v              = pin ? v : -1.0; // (norms^2 are >= 0)
                           auto step = [&](auto CTRL_) __attribute__((always_inline)) {
@@ -872,21 +881,43 @@ namespace
                         }
                         if (!(best > 0.0))
                           break; // the trailing block is zero (uniform decision)
-                        const int cp = pc[p];
-                        if (tid < nn1)
-                          pn[tid] = (tid == k) ? cp : (tid == p ? pc[k] : pc[tid]);
-                        const int    ccp   = cix(cp);
-                        const double x0    = BD[k * ncm + ccp];
+                        int    cp;
+                        double x0, vr[2];
+                        if (regs)
+                          {
+                            cp           = __builtin_amdgcn_readlane(mypc, p);
+                            const int ck = __builtin_amdgcn_readlane(mypc, k);
+                            mypc         = (lane == k) ? cp : (lane == p ? ck : mypc);
+                            // x0 and this lane's two rows of the pivot column in one batch: clamped addresses,
+                            // the rows outside k < r < nn1 are replaced below
+                            const int ccp = cix(cp);
+                            x0            = BD[k * ncm + ccp];
+                            vr[0]         = BD[min(l16, nn1 - 1) * ncm + ccp];
+                            vr[1]         = BD[min(l16 + 16, nn1 - 1) * ncm + ccp];
+                          }
+                        else
+                          {
+                            cp = pc[p];
+                            if (tid < nn1)
+                              pn[tid] = (tid == k) ? cp : (tid == p ? pc[k] : pc[tid]);
+                            const int ccp = cix(cp);
+                            x0            = BD[k * ncm + ccp];
+#pragma unroll
+                            for (int i = 0; i < 2; ++i)
+                              {
+                                const int r = l16 + 16 * i;
+                                vr[i]       = (r > k && r < nn1) ? BD[r * ncm + ccp] : 0.0;
+                              }
+                          }
                         const double sq    = best * fast_rsqrt(best);
                         const double alpha = (x0 >= 0.0) ? -sq : sq;
                         const double v0    = x0 - alpha;
                         const double beta  = fast_rcp(best - alpha * x0);
-                        double       vr[2];
 #pragma unroll
                         for (int i = 0; i < 2; ++i)
                           {
                             const int r = l16 + 16 * i;
-                            vr[i]       = (r == k) ? v0 : ((r > k && r < nn1) ? BD[r * ncm + ccp] : 0.0);
+                            vr[i]       = (r == k) ? v0 : ((r > k && r < nn1) ? vr[i] : 0.0);
                           }
 #pragma unroll
                         for (int sl = 0; sl < 2; ++sl)
@@ -926,8 +957,11 @@ namespace
                               }
                           }
                         __syncthreads();
-                        pb ^= 1;
+                        if (!regs)
+                          pb ^= 1;
                       }
+                    if (regs && tid < nn1) // (also after the break on a zero trailing block; pb is still 0)
+                      pcol[tid] = mypc;
 #pragma unroll
                     for (int sl = 0; sl < 2; ++sl)
                       {
@@ -963,7 +997,8 @@ namespace
                 const int wru = tposed ? wr + 1 : wr; // rows that take the rotations
                 auto wcol = [&](int j) { return tposed ? j : cix(j); };
                 const int nev = (nn1 + 1) & ~1;
-                for (int idx = tid; idx < nn1 * nn1; idx += 256)
+                // (after the QR nothing accumulates or reads V: the term vectors are the columns of W)
+                for (int idx = tid; idx < (tposed ? 0 : nn1 * nn1); idx += 256)
                   Vj[idx] = ((idx / nn1) == (idx % nn1)) ? 1.0 : 0.0;
                 // Frobenius norm^2 (rotation invariant): columns below 1e-22 of it are numerically
                 // zero -- seven orders under the reference's 1e-15 cutoff on sigma(G).  A pair of
@@ -979,79 +1014,86 @@ namespace
                     fro            = fma(w, w, fro);
                   }
                 const double tiny = 1e-22 * block_sum(fro);
-                if (nev / 2 <= 16 && (SLOD_DG(A, 131072)))
+                if (regs)
                   {
-                    // All nev/2 <= 16 column pairs of a round fit ONE wave (4 lanes per pair): wave 0
-                    // runs the sweeps alone, LDS accesses of one wave execute in order, so a round
-                    // needs no workgroup barrier at all (the round trip through four waves cost more
-                    // than the rotation arithmetic).
-                    if (wave == 0)
+                    // One pair per 16-lane group (nev / 2 <= 16).  Lane l16 holds rows l16 and l16 + 16 of both
+                    // columns of its pair; they are loaded in one batch without control dependence (clamped
+                    // addresses, zero by select outside the wru rows and for a group without a pair), the dot
+                    // products run over them in the order of the loop below (row l16, then row l16 + 16, then
+                    // the group sum; the row c'^T rides along with weight zero), the rotation is decided by a
+                    // predicate and applied to the registers, and only a rotated pair is stored: one LDS round
+                    // trip per round.  "Some pair was rotated" is a bool per thread that meets the other waves'
+                    // once per sweep, in flag[wave], on the barrier of the sweep's last round.
+                    const int  o0 = min(l16, nn1) * ncm, o1 = min(l16 + 16, nn1) * ncm;
+                    const bool u0 = l16 < wru, u1 = l16 + 16 < wru; // rows that take the rotation
+                    const bool d0 = l16 < wr, d1 = l16 + 16 < wr;   // rows of the dot products
+                    for (int sweep = 0; sweep < ((SLOD_DG(A, 8192)) ? 3 : 40); ++sweep)
                       {
-                        const int l4 = lane & 3, pr = lane >> 2;
-                        for (int sweep = 0; sweep < ((SLOD_DG(A, 8192)) ? 3 : 40); ++sweep)
+                        bool anyt = false;
+                        for (int round = 0; round < nev - 1; ++round)
                           {
-                            bool any = false;
-                            for (int round = 0; round < nev - 1; ++round)
+#pragma clang fp contract(off) // every fma below is written out: the bits are those of the loop through LDS
+                            int pa, pb;
+                            if (grp == 0)
                               {
-                                int pa, pb2;
-                                if (pr == 0)
-                                  {
-                                    pa  = nev - 1;
-                                    pb2 = round;
-                                  }
-                                else
-                                  {
-                                    pa  = round + pr;
-                                    pa  = pa >= nev - 1 ? pa - (nev - 1) : pa;
-                                    pb2 = round - pr;
-                                    pb2 = pb2 < 0 ? pb2 + (nev - 1) : pb2;
-                                  }
-                                const bool valid = pr < nev / 2 && pa < nn1 && pb2 < nn1;
-                                const int  p = valid ? (pa < pb2 ? pa : pb2) : 0, q = valid ? (pa < pb2 ? pb2 : pa) : 0;
-                                const int  cp = wcol(p), cq = wcol(q);
-                                double     app = 0, aqq = 0, apq = 0;
-                                for (int r = l4; r < wr; r += 4)
-                                  {
-                                    const double wp = Wm[r * ncm + cp], wq = Wm[r * ncm + cq];
-                                    app = fma(wp, wp, app);
-                                    aqq = fma(wq, wq, aqq);
-                                    apq = fma(wp, wq, apq);
-                                  }
-                                app += dpp_rot<0xB1>(app); // quad_perm [1,0,3,2]
-                                aqq += dpp_rot<0xB1>(aqq);
-                                apq += dpp_rot<0xB1>(apq);
-                                app += dpp_rot<0x4E>(app); // quad_perm [2,3,0,1]
-                                aqq += dpp_rot<0x4E>(aqq);
-                                apq += dpp_rot<0x4E>(apq);
-                                const bool rot = valid && !(apq == 0.0 || apq * apq <= 1e-30 * (app * aqq) ||
-                                                            fmax(app, aqq) <= tiny);
-                                if (rot)
-                                  {
-                                    const double dd = aqq - app;
-                                    const double hh = fma(dd, dd, 4.0 * apq * apq);
-                                    const double hy = hh * fast_rsqrt(hh); // sqrt(dd^2 + 4 apq^2)
-                                    const double t  = (dd >= 0.0 ? 2.0 : -2.0) * apq * fast_rcp(fabs(dd) + hy);
-                                    const double cs = fast_rsqrt(fma(t, t, 1.0)), sn = cs * t;
-                                    for (int r = l4; r < wru; r += 4)
-                                      {
-                                        const double wp = Wm[r * ncm + cp], wq = Wm[r * ncm + cq];
-                                        Wm[r * ncm + cp] = cs * wp - sn * wq;
-                                        Wm[r * ncm + cq] = sn * wp + cs * wq;
-                                      }
-                                    for (int r = l4; r < (tposed ? 0 : nn1); r += 4)
-                                      {
-                                        const double vp = Vj[r * nn1 + p], vq = Vj[r * nn1 + q];
-                                        Vj[r * nn1 + p] = cs * vp - sn * vq;
-                                        Vj[r * nn1 + q] = sn * vp + cs * vq;
-                                      }
-                                    any = true;
-                                  }
+                                pa = nev - 1;
+                                pb = round;
                               }
-                            if (!__any(any))
-                              break;
+                            else
+                              {
+                                pa = round + grp;
+                                pa = pa >= nev - 1 ? pa - (nev - 1) : pa;
+                                pb = round - grp;
+                                pb = pb < 0 ? pb + (nev - 1) : pb;
+                              }
+                            const bool valid = (grp < nev / 2) & (pa < nn1) & (pb < nn1);
+                            const int  p = valid ? (pa < pb ? pa : pb) : 0, q = valid ? (pa < pb ? pb : pa) : 0;
+                            double     wp0 = Wm[o0 + p], wq0 = Wm[o0 + q], wp1 = Wm[o1 + p], wq1 = Wm[o1 + q];
+                            wp0 = (valid & u0) ? wp0 : 0.0;
+                            wq0 = (valid & u0) ? wq0 : 0.0;
+                            wp1 = (valid & u1) ? wp1 : 0.0;
+                            wq1 = (valid & u1) ? wq1 : 0.0;
+                            const double xp0 = d0 ? wp0 : 0.0, xq0 = d0 ? wq0 : 0.0;
+                            const double xp1 = d1 ? wp1 : 0.0, xq1 = d1 ? wq1 : 0.0;
+                            const double app = group16_sum(fma(xp1, xp1, fma(xp0, xp0, 0.0)));
+                            const double aqq = group16_sum(fma(xq1, xq1, fma(xq0, xq0, 0.0)));
+                            const double apq = group16_sum(fma(xp1, xq1, fma(xp0, xq0, 0.0)));
+                            const bool   rot = valid & !((apq == 0.0) | (apq * apq <= 1e-30 * (app * aqq)) |
+                                                       (fmax(app, aqq) <= tiny));
+                            // t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)), zeta = (aqq-app)/(2 apq), written
+                            // without the division by apq; c = 1/sqrt(1+t^2), s = c t (unused where !rot)
+                            const double dd = aqq - app;
+                            const double hh = fma(dd, dd, (4.0 * apq) * apq);
+                            const double t  = ((dd >= 0.0 ? 2.0 : -2.0) * apq) * fast_rcp(fma(hh, fast_rsqrt(hh), fabs(dd)));
+                            const double cs = fast_rsqrt(fma(t, t, 1.0)), sn = cs * t;
+                            const double np0 = fma(cs, wp0, -(sn * wq0)), nq0 = fma(sn, wp0, cs * wq0);
+                            const double np1 = fma(cs, wp1, -(sn * wq1)), nq1 = fma(sn, wp1, cs * wq1);
+                            if (rot & u0)
+                              {
+                                Wm[o0 + p] = np0;
+                                Wm[o0 + q] = nq0;
+                              }
+                            if (rot & u1)
+                              {
+                                Wm[o1 + p] = np1;
+                                Wm[o1 + q] = nq1;
+                              }
+                            anyt |= rot;
+                            if (round == nev - 2)
+                              {
+                                const int wany = __any(anyt) ? 1 : 0;
+                                if (lane == 0)
+                                  flag[wave] = wany;
+                              }
+                            __syncthreads();
                           }
+                        const int any = flag[0] | flag[1] | flag[2] | flag[3];
+                        if (nev == 2)
+                          __syncthreads(); // a sweep of one round: the next write of flag[] follows no other barrier
+                        ++pdg.sweeps;
+                        if (!any)
+                          break;
                       }
-                    __syncthreads();
                   }
                 else
                   for (int sweep = 0; sweep < ((SLOD_DG(A, 8192)) ? 3 : 40); ++sweep)
