@@ -1,6 +1,7 @@
 // Counterpart of reference app/main_Diffusion.cc for the basis-construction path:
 //   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare] [--coarse] [--loads K]
 //                  [--heat STEPS DT] [--eigs K] [--wave STEPS DT] [--direct] [--ensemble K] [--perturb K]
+//                  [--member K]
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
 // file name it dumps, per patch, phi and psi in patch-lexicographic order (parity tests).
 // --compare (anywhere on the command line): after run(), the rest of the reference run() -- global
@@ -29,6 +30,14 @@
 // the others are drawn after it), f = 1: one plan for all K * patches bases, then the K LOD systems in one call per step
 // (slod_lod_matrix_ensemble, _rhs_, _solve_, _reconstruct_ensemble, slod_ensemble_moments): one line per member with its
 // iterations and relative residual, then the fine-grid L2 norms of the mean and of the standard deviation.
+// --ensemble K --heat STEPS DT --direct: after the lines above, the heat flow of every member on banded Cholesky factors,
+// one per member in one factor object (slod_lod_mass_matrix_ensemble, slod_lod_matrix_combine_ensemble,
+// slod_lod_factor_create_ensemble, slod_lod_theta_steps_ensemble_direct): the factor line (pivots over all members), one
+// line "member K heat step J: L2 distance = .., energy distance = .." per member and step with the distance to that
+// member's elliptic solution, then the L2 norms of the mean and of the standard deviation of the final states.  Without
+// --direct the two flags act independently, as before.
+// --member K: a run without --ensemble on the coefficient that is member K of an ensemble run (K fields are drawn and
+// dropped before the problem draws its own).
 // --perturb K: a local coefficient change after everything else.  K cells of the coefficient's 2^r x 2^r grid, picked by a
 // fixed linear congruential generator, flip between min and max; the basis and A_LOD are refreshed in place
 // (refresh_after_coefficient_change: only the patches that see a changed fine element, only the matrix entries with such a
@@ -95,7 +104,7 @@ int main(int argc_all, char **argv_all)
 {
   // --compare and --coarse are taken out wherever they stand; the positional arguments keep their meaning
   bool               compare = false, coarse = false, direct = false;
-  int                n_loads = 0, heat_steps = 0, n_eigs = 0, wave_steps = 0, n_members = 0, n_perturb = 0;
+  int                n_loads = 0, heat_steps = 0, n_eigs = 0, wave_steps = 0, n_members = 0, n_perturb = 0, member = 0;
   double             heat_dt = 0.0, wave_dt = 0.0;
   std::vector<char *> args;
   for (int i = 0; i < argc_all; ++i)
@@ -121,6 +130,8 @@ int main(int argc_all, char **argv_all)
       }
     else if (i > 0 && !std::strcmp(argv_all[i], "--ensemble") && i + 1 < argc_all)
       n_members = std::atoi(argv_all[++i]);
+    else if (i > 0 && !std::strcmp(argv_all[i], "--member") && i + 1 < argc_all)
+      member = std::atoi(argv_all[++i]);
     else if (i > 0 && !std::strcmp(argv_all[i], "--perturb") && i + 1 < argc_all)
       n_perturb = std::atoi(argv_all[++i]);
     else
@@ -137,6 +148,8 @@ int main(int argc_all, char **argv_all)
       par.constant_coefficients = false;
       par.n_members             = n_members > 0 ? (unsigned int)n_members : 1u;
       std::srand(1);
+      for (int k = 0; k < member; ++k)
+        problem_parameter<2>(1, 100, 3); // the draws of the members before this one
       Problem problem(par, 1, 100, 3);
       problem.run();
       double s1 = 0, s2 = 0;
@@ -275,6 +288,21 @@ int main(int argc_all, char **argv_all)
                         problem.ensemble_rel_residuals()[k]);
           std::printf("SLOD ensemble of %d: L2 norm of the mean = %.12e, of the standard deviation = %.12e\n", n_members,
                       problem.norms_ensemble_mean().l2[0], problem.norms_ensemble_deviation().l2[0]);
+          if (heat_steps > 0 && direct)
+            {
+              problem.assemble_mass_matrix_ensemble();
+              problem.solve_heat_ensemble((unsigned int)heat_steps, heat_dt, 1.0);
+              print_factor(problem.last_factor_info());
+              for (int j = 0; j < heat_steps; ++j)
+                for (int k = 0; k < n_members; ++k)
+                  {
+                    const slod_error_norms &e = problem.error_heat_ensemble()[(std::size_t)j * n_members + k];
+                    std::printf("member %d heat step %d: L2 distance = %.12e, energy distance = %.12e\n", k, j + 1, e.l2[0], e.energy);
+                  }
+              std::printf("SLOD heat ensemble of %d at T = %g: L2 norm of the mean = %.12e, of the standard deviation = %.12e\n",
+                          n_members, heat_steps * heat_dt, problem.norms_heat_ensemble_mean().l2[0],
+                          problem.norms_heat_ensemble_deviation().l2[0]);
+            }
         }
       if (n_perturb > 0)
         {

@@ -216,22 +216,30 @@ private:
   double            *cg = nullptr; // the pieces of the solve
   bool               per_col = false; // as given to take_solve
 };
-// The banded Cholesky factor of a full set of block rows (slod_lod_factor.hip): 16 x 16 tiles, nb block rows, bb block
-// sub-diagonals; the pointers are pieces of mem.
+// Y_k = A_k X_k on an ensemble matrix, the launch of slod_lod_apply_ensemble (slod_lod_ensemble.hip)
+void slod_lod_apply_ensemble_launch(const slod_handle *h, hipStream_t st, const double *d_values, size_t ld_m, const uint32_t *d_cols,
+                                    const double *d_x, size_t ld_x, int n_members, double *d_y, size_t ld_y);
+// The banded Cholesky factors of the full sets of block rows of n_members matrices on one pattern (slod_lod_factor.hip;
+// a single factor has one member): 16 x 16 tiles, nb block rows, bb block sub-diagonals.  mem holds n_members copies of
+// member_doubles doubles (band, factored diagonal tiles, pivots, reciprocal diagonal of L; the pointers are member 0's),
+// then the row map, which all members share, and a status word per member.
 struct slod_lod_factor
 {
-  slod_handle     *h = nullptr;
-  int              n = 0, b = 0, nb = 0, bb = 0; // rows, half bandwidth, block rows, block sub-diagonals
-  size_t           bytes = 0;
-  double           min_pivot = 0.0, max_pivot = 0.0;
-  double          *band = nullptr, *diag = nullptr, *piv = nullptr, *dinv = nullptr;
-  int             *rowmap = nullptr, *status = nullptr;
-  SlodDevBuf<char> mem;
+  slod_handle        *h = nullptr;
+  int                 n = 0, b = 0, nb = 0, bb = 0; // rows, half bandwidth, block rows, block sub-diagonals
+  int                 n_members = 1;
+  size_t              member_doubles = 0, bytes = 0;
+  double              min_pivot = 0.0, max_pivot = 0.0; // over all members
+  std::vector<double> member_min, member_max;           // HOST [n_members]
+  double             *band = nullptr, *diag = nullptr, *piv = nullptr, *dinv = nullptr;
+  int                *rowmap = nullptr, *status = nullptr;
+  SlodDevBuf<char>    mem;
 };
-// the launch of slod_lod_factor_solve for the time loops on a factor (slod_lod_time.hip, slod_lod_wave.hip); arguments
-// are checked by the caller
+// The launch of slod_lod_factor_solve_ensemble for the time loops on a factor (slod_lod_time.hip, slod_lod_wave.hip):
+// member first_member + k solves the columns k n_rhs .. k n_rhs + n_rhs - 1; arguments are checked by the caller
 void slod_lod_factor_solve_launch(const slod_lod_factor *f, hipStream_t st, const double *d_rhs, size_t ld_rhs, int n_rhs, double *d_u,
-                                  size_t ld_u);
-// SLOD_ERR_ARGUMENT, "<who>: NULL factor" or "<who>: factor of another handle / row count"; else SLOD_OK
-int slod_lod_factor_check(const slod_handle *h, const char *who, const slod_lod_factor *f);
+                                  size_t ld_u, int first_member = 0, int n_members = 1);
+// SLOD_ERR_ARGUMENT, "<who>: NULL factor", "<who>: factor of another handle / row count" or "<who>: factor of another
+// member count" (the time loops on one matrix take a factor of one member); else SLOD_OK
+int slod_lod_factor_check(const slod_handle *h, const char *who, const slod_lod_factor *f, int n_members = 1);
 #endif

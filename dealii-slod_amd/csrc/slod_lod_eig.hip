@@ -9,7 +9,7 @@
 //   k_eig_ritz                   Ga Q = Gm Q Theta, Q^T Gm Q = I in one workgroup out of LDS
 //   k_eig_rotate                 X = Z Q; AX = W Q and MX = V Q stay in registers for the residual partials
 // Every reduction has a fixed order (no atomics): the same inputs give the same bits.
-#include "slod_grid.hip.h"
+#include "slod_lod_system.hip.h"
 #include "slod_lod_tile.hip.h"
 
 #include <algorithm>
@@ -24,31 +24,13 @@ namespace
   constexpr int    EG_COLS = LOD_COLS; // block columns: one column chunk (slod_lod_tile.hip.h), and what fits the Ritz LDS
   constexpr double EG_EPS  = 2.220446049250313e-16;
 
-  // out[p,j][d][e] = (A[p,j][d][e] + A[q,j'][e][d]) / 2, q = cols[p,j], j' the slot of p in row q (0 when there is none).
-  // One rounding of the sum, an exact halving, both commutative: out is symmetric bit for bit.
+  // out = (A + A^T) / 2 per word (lod_symmetrize_word, slod_lod_system.hip.h)
   __global__ __launch_bounds__(256) void k_lod_symmetrize(int NP, int s, int cap, const double *__restrict__ values,
                                                          const uint32_t *__restrict__ cols, double *__restrict__ out)
   {
-#pragma clang fp contract(off)
-    const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x, ss = (size_t)s * s;
-    if (w >= (size_t)NP * cap * ss)
-      return;
-    const size_t   slot = w / ss;
-    const int      de = (int)(w - slot * ss), d = de / s, e = de - d * s;
-    const uint32_t p = (uint32_t)(slot / cap), q = cols[slot];
-    if (q >= (uint32_t)NP)
-      {
-        out[w] = 0.0;
-        return;
-      }
-    double t = 0.0;
-    for (int j = 0; j < cap; ++j)
-      if (cols[(size_t)q * cap + j] == p)
-        {
-          t = values[((size_t)q * cap + j) * ss + e * s + d];
-          break;
-        }
-    out[w] = 0.5 * (values[w] + t);
+    const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (w < (size_t)NP * cap * s * s)
+      out[w] = lod_symmetrize_word(NP, s, cap, values, 1, cols, w);
   }
 
   // ---------------------------------------------------------------------------------

@@ -7,6 +7,9 @@
 // Nothing is summed in a new order.  Matrix, load and reconstruction run the bodies of slod_lod_system.hip.h with the
 // member on blockIdx.y; the product is slod_lod_row_product<true>; the solve is SlodLodWork::solve with a matrix per
 // column (slod_lod_multi.hip).  Every member's result has the bits of the single-problem call on its slab.
+// The L2 side (mass matrix, symmetrised stiffness, combinations) follows the same rule: the row of k_lod_mass and the
+// words of k_lod_symmetrize and k_lod_combine (slod_lod_system.hip.h) with the member on a grid axis or on the fastest
+// thread index.
 #include "slod_lod_system.hip.h"
 #include "slod_lod_tile.hip.h"
 
@@ -22,6 +25,36 @@ namespace
     const size_t k = blockIdx.y;
     lod_matrix_row(G, blockIdx.x, blockIdx.x, basis + k * member_stride, premult + k * member_stride, stride, values + k, ld_m,
                    k == 0 ? cols : nullptr);
+  }
+
+  // the row of k_lod_mass (slod_lod_time.hip); ld_rho = 0: one density for all members, rho NULL: density 1
+  template <int S>
+  __global__ __launch_bounds__(256) void k_ens_mass(const SlodGrid G, const double *basis, size_t stride, size_t member_stride,
+                                                   const double *rho, size_t ld_rho, double scale, double *values, size_t ld_m,
+                                                   uint32_t *cols)
+  {
+    const size_t k = blockIdx.y;
+    lod_mass_row<S>(G, blockIdx.x, blockIdx.x, basis + k * member_stride, stride, rho ? rho + k * ld_rho : nullptr, scale,
+                    values + k, ld_m, k == 0 ? cols : nullptr);
+  }
+
+  // one thread per (word w, member k), k fastest: the lanes of a wave read consecutive doubles
+  __global__ __launch_bounds__(256) void k_ens_symmetrize(int NP, int s, int cap, int n_members, const double *__restrict__ values,
+                                                         size_t ld_in, const uint32_t *__restrict__ cols, double *__restrict__ out,
+                                                         size_t ld_out)
+  {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x, w = t / n_members, k = t - w * n_members;
+    if (w < (size_t)NP * cap * s * s)
+      out[w * ld_out + k] = lod_symmetrize_word(NP, s, cap, values + k, ld_in, cols, w);
+  }
+
+  // a, b and out may be one array when their leading dimensions agree: a thread reads its two words, then writes its own
+  __global__ __launch_bounds__(256) void k_ens_combine(size_t n, int n_members, double alpha, const double *a, size_t ld_a,
+                                                      double beta, const double *b, size_t ld_b, double *out, size_t ld_out)
+  {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x, w = t / n_members, k = t - w * n_members;
+    if (w < n)
+      out[w * ld_out + k] = lod_combine_word(alpha, a[w * ld_a + k], beta, b[w * ld_b + k]);
   }
 
   // ld_fine = 0: one load for all members
@@ -103,7 +136,21 @@ namespace
     return SLOD_OK;
   }
   size_t ens_field(const slod_handle *h) { return (size_t)(h->NE + 1) * (h->NE + 1) * h->cfg.spacedim; }
+  size_t ens_words(const slod_handle *h)
+  {
+    const size_t s = (size_t)h->cfg.spacedim;
+    return (size_t)h->NP * slod_lod_row_capacity(h) * s * s;
+  }
 } // namespace
+
+// k_ens_apply for the time loop on an ensemble factor (slod_lod_time.hip); arguments are checked by the caller
+void slod_lod_apply_ensemble_launch(const slod_handle *h, hipStream_t st, const double *d_values, size_t ld_m, const uint32_t *d_cols,
+                                    const double *d_x, size_t ld_x, int n_members, double *d_y, size_t ld_y)
+{
+  const LodShape w = lod_shape(h, n_members);
+  hipLaunchKernelGGL(k_ens_apply, lod_grid(w, APPLY_MAX_BLOCKS), dim3(LOD_BLOCK), 0, st, w.nrow, w.s, w.cap, w.NP, n_members, w.ngroup,
+                     d_values, ld_m, d_cols, d_x, ld_x, d_y, ld_y);
+}
 
 #pragma GCC visibility push(default)
 extern "C" {
@@ -121,6 +168,67 @@ int slod_lod_matrix_ensemble(slod_handle *h, const double *d_basis, const double
     return rc;
   hipLaunchKernelGGL(k_ens_matrix, dim3((unsigned)h->NP, (unsigned)n_members), dim3(256), 0, st, slod_grid_of(h), d_basis, d_premult,
                      stride, member_stride, d_values, ld_m, d_cols);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, who);
+}
+
+int slod_lod_mass_matrix_ensemble(slod_handle *h, const double *d_basis, size_t stride, size_t member_stride, int n_members,
+                                  const double *d_rho, size_t ld_rho, double *d_values, size_t ld_m, uint32_t *d_cols, void *hip_stream)
+{
+  const char *who = "slod_lod_mass_matrix_ensemble";
+  if (const int rc = ens_check(h, who, d_basis && d_values && d_cols, n_members, {ld_m}))
+    return rc;
+  if (const int rc = ens_check_slab(h, who, stride, member_stride, n_members))
+    return rc;
+  if (d_rho && ld_rho != 0 && ld_rho < (size_t)h->NE * h->NE)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": ld_rho not 0 and shorter than a density field");
+  hipStream_t st;
+  if (const int rc = slod_enter(h, hip_stream, &st))
+    return rc;
+  const double hf = 1.0 / h->NE, scale = hf * hf / 36.0; // as slod_lod_mass_matrix
+  const dim3   grid((unsigned)h->NP, (unsigned)n_members);
+  if (h->cfg.spacedim == 1)
+    hipLaunchKernelGGL(k_ens_mass<1>, grid, dim3(256), 0, st, slod_grid_of(h), d_basis, stride, member_stride, d_rho, ld_rho, scale,
+                       d_values, ld_m, d_cols);
+  else
+    hipLaunchKernelGGL(k_ens_mass<2>, grid, dim3(256), 0, st, slod_grid_of(h), d_basis, stride, member_stride, d_rho, ld_rho, scale,
+                       d_values, ld_m, d_cols);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, who);
+}
+
+int slod_lod_matrix_symmetrize_ensemble(slod_handle *h, const double *d_values, size_t ld_in, const uint32_t *d_cols, int n_members,
+                                        double *d_out, size_t ld_out, void *hip_stream)
+{
+  const char *who = "slod_lod_matrix_symmetrize_ensemble";
+  if (const int rc = ens_check(h, who, d_values && d_cols && d_out, n_members, {ld_in, ld_out}))
+    return rc;
+  if (d_out == d_values)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": a row reads other rows, the call cannot run in place");
+  hipStream_t st;
+  if (const int rc = slod_enter(h, hip_stream, &st))
+    return rc;
+  const LodShape w = lod_shape(h, 1);
+  hipLaunchKernelGGL(k_ens_symmetrize, lod_flat_grid(ens_words(h) * n_members), dim3(256), 0, st, w.NP, w.s, w.cap, n_members, d_values,
+                     ld_in, d_cols, d_out, ld_out);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, who);
+}
+
+int slod_lod_matrix_combine_ensemble(slod_handle *h, double alpha, const double *d_a, size_t ld_a, double beta, const double *d_b,
+                                     size_t ld_b, int n_members, double *d_out, size_t ld_out, void *hip_stream)
+{
+  const char *who = "slod_lod_matrix_combine_ensemble";
+  if (const int rc = ens_check(h, who, d_a && d_b && d_out, n_members, {ld_a, ld_b, ld_out}))
+    return rc;
+  if ((d_out == d_a && ld_out != ld_a) || (d_out == d_b && ld_out != ld_b))
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": in place needs equal leading dimensions");
+  hipStream_t st;
+  if (const int rc = slod_enter(h, hip_stream, &st))
+    return rc;
+  const size_t n = ens_words(h);
+  hipLaunchKernelGGL(k_ens_combine, lod_flat_grid(n * n_members), dim3(256), 0, st, n, n_members, alpha, d_a, ld_a, beta, d_b, ld_b,
+                     d_out, ld_out);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, who);
 }
@@ -155,9 +263,7 @@ int slod_lod_apply_ensemble(slod_handle *h, const double *d_values, size_t ld_m,
   hipStream_t st;
   if (const int rc = slod_enter(h, hip_stream, &st))
     return rc;
-  const LodShape w = lod_shape(h, n_members);
-  hipLaunchKernelGGL(k_ens_apply, lod_grid(w, APPLY_MAX_BLOCKS), dim3(LOD_BLOCK), 0, st, w.nrow, w.s, w.cap, w.NP, n_members,
-                     w.ngroup, d_values, ld_m, d_cols, d_x, ld_x, d_y, ld_y);
+  slod_lod_apply_ensemble_launch(h, st, d_values, ld_m, d_cols, d_x, ld_x, n_members, d_y, ld_y);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, who);
 }

@@ -2,6 +2,9 @@
 // any number of solves (the reference has no counterpart: it runs CG + SSOR once, LOD.cc:990-998):
 //   slod_lod_factor_create   band storage, the left-looking factorisation, pivot range and status
 //   slod_lod_factor_solve    U = A^-1 RHS on coarse multi-vectors, asynchronous, no allocation, no read-back
+//   slod_lod_factor_create_ensemble / _solve_ensemble  the same for the K matrices of a coefficient ensemble: one
+//                            allocation of K copies of the storage below, the same kernels with the member on blockIdx.y
+//                            (a single factor is the ensemble of one member)
 // Ordering: unknown (p, d) has the index r = (cy N + cx) s + d, (cx, cy) the centre cell of p, so the block stencil of a
 // row (slot j = cell offset (j % span, j / span) - span / 2, slod_grid.hip.h) is a band of half width
 // b = s (w N + w) + s - 1, w = 2 l + 1.
@@ -39,27 +42,34 @@ namespace
   }
 
   // rowmap[r] = p s + d, the caller's row of factor index r (-1: padding), and the unit diagonal of the padding
-  __global__ __launch_bounds__(256) void k_factor_rowmap(const SlodGrid G, int n, int npad, int bb, int *rowmap, double *band)
+  // of every member (blockIdx.y, copies mstride doubles apart)
+  __global__ __launch_bounds__(256) void k_factor_rowmap(const SlodGrid G, int n, int npad, int bb, int *rowmap, double *band,
+                                                        size_t mstride)
   {
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r >= npad)
       return;
     if (r >= n)
       {
-        rowmap[r]                                                              = -1;
-        band[(size_t)(r / FB) * (bb + 1) * FT + (size_t)(r % FB) * FB + r % FB] = 1.0;
+        if (blockIdx.y == 0)
+          rowmap[r] = -1;
+        band[blockIdx.y * mstride + (size_t)(r / FB) * (bb + 1) * FT + (size_t)(r % FB) * FB + r % FB] = 1.0;
         return;
       }
+    if (blockIdx.y != 0)
+      return;
     const int s = G.spacedim, cell = r / s, d = r - cell * s;
     rowmap[r]   = (int)grid_pid(G, cell % G.N, cell / G.N) * s + d;
   }
 
-  // the lower triangle of the block rows into the zeroed band: entry ((p, d), (q, e)) with r(q, e) <= r(p, d)
-  __global__ __launch_bounds__(256) void k_factor_scatter(const SlodGrid G, int NP, int cap, int bb, const double *__restrict__ values,
-                                                         const uint32_t *__restrict__ cols, double *band)
+  // the lower triangle of the block rows into the zeroed band: entry ((p, d), (q, e)) with r(q, e) <= r(p, d).  One thread
+  // per (word t, member k), k fastest as in the ensemble matrix: word t of member k is values[t ld_m + k]
+  __global__ __launch_bounds__(256) void k_factor_scatter(const SlodGrid G, int NP, int cap, int bb, int n_members,
+                                                         const double *__restrict__ values, size_t ld_m,
+                                                         const uint32_t *__restrict__ cols, double *band, size_t mstride)
   {
     const int    s = G.spacedim;
-    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x, t = w / n_members, k = w - t * n_members;
     if (t >= (size_t)NP * cap * s * s)
       return;
     const size_t   slot = t / (s * s);
@@ -68,20 +78,23 @@ namespace
     if (q >= (uint32_t)NP)
       return;
     const int r = factor_index(G, p, d), c = factor_index(G, q, e);
-    const int I = r / FB, k = I - c / FB;
-    if (c > r || k > bb)
+    const int I = r / FB, kb = I - c / FB;
+    if (c > r || kb > bb)
       return;
-    band[((size_t)I * (bb + 1) + k) * FT + (size_t)(c % FB) * FB + r % FB] = values[t];
+    band[k * mstride + ((size_t)I * (bb + 1) + kb) * FT + (size_t)(c % FB) * FB + r % FB] = values[t * ld_m + k];
   }
 
   // Block column K of the factorisation; block x = block row r = K + x.  status[0]: the index of the first pivot that is
   // not > 0, or -1; a column after a failed one does nothing.  The factored diagonal tile goes to diag[K], not over A_KK in
-  // the band: the other blocks of the launch read A_KK.
+  // the band: the other blocks of the launch read A_KK.  blockIdx.y = the member: its copy of the storage (mstride doubles
+  // from the last) and its status word, nothing of another member.
   __global__ __launch_bounds__(64) void k_factor_column(int K, int bb, double *band, double *diag, double *piv, double *dinv,
-                                                       int *status)
+                                                       int *status, size_t mstride)
   {
     __shared__ double sD[FB][FB + 1], sT[FB][FB + 1];
-    const int         bad = status[0];
+    band += blockIdx.y * mstride, diag += blockIdx.y * mstride, piv += blockIdx.y * mstride, dinv += blockIdx.y * mstride;
+    status += blockIdx.y;
+    const int bad = status[0];
     if (bad >= 0 && bad < K * FB) // set by an earlier launch: the same answer in every block
       return;
     const int    lane = threadIdx.x, li = lane & 15, lk = lane >> 4;
@@ -180,13 +193,16 @@ namespace
       out[idx] = sT[idx & 15][idx >> 4];
   }
 
-  // Both sweeps for the 16 columns from blockIdx.x * 16.  rhs and u may be the same array: a block row of rhs is read
-  // before the same rows of u are written, and a block touches its own columns only.
+  // Both sweeps for the 16 columns from blockIdx.x * 16 of the window of member blockIdx.y: its n_rhs columns from
+  // blockIdx.y * n_rhs, on its copy of the factor.  rhs and u may be the same array: a block row of rhs is read before the
+  // same rows of u are written, and a block touches its own columns only.
   __global__ __launch_bounds__(256) void k_factor_solve(int nb, int bb, const double *__restrict__ band, const double *__restrict__ diag,
-                                                       const double *__restrict__ dinv, const int *__restrict__ rowmap, int n_rhs,
-                                                       const double *rhs, size_t ld_rhs, double *u, size_t ld_u)
+                                                       const double *__restrict__ dinv, size_t mstride, const int *__restrict__ rowmap,
+                                                       int n_rhs, const double *rhs, size_t ld_rhs, double *u, size_t ld_u)
   {
     __shared__ double sP[4][FB][FB + 1], sL[FB][FB + 1];
+    band += blockIdx.y * mstride, diag += blockIdx.y * mstride, dinv += blockIdx.y * mstride;
+    rhs += (size_t)blockIdx.y * n_rhs, u += (size_t)blockIdx.y * n_rhs;
     const int         tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4;
     const int         c0 = blockIdx.x * FB;
     const bool        col_ok = c0 + li < n_rhs;
@@ -269,20 +285,115 @@ namespace
 } // namespace
 
 void slod_lod_factor_solve_launch(const slod_lod_factor *f, hipStream_t st, const double *d_rhs, size_t ld_rhs, int n_rhs, double *d_u,
-                                  size_t ld_u)
+                                  size_t ld_u, int first_member, int n_members)
 {
-  hipLaunchKernelGGL(k_factor_solve, dim3((unsigned)((n_rhs + FB - 1) / FB)), dim3(256), 0, st, f->nb, f->bb, f->band, f->diag, f->dinv,
-                     f->rowmap, n_rhs, d_rhs, ld_rhs, d_u, ld_u);
+  const size_t first = (size_t)first_member * f->member_doubles;
+  hipLaunchKernelGGL(k_factor_solve, dim3((unsigned)((n_rhs + FB - 1) / FB), (unsigned)n_members), dim3(256), 0, st, f->nb, f->bb,
+                     f->band + first, f->diag + first, f->dinv + first, f->member_doubles, f->rowmap, n_rhs, d_rhs, ld_rhs, d_u, ld_u);
 }
 
-int slod_lod_factor_check(const slod_handle *h, const char *who, const slod_lod_factor *f)
+int slod_lod_factor_check(const slod_handle *h, const char *who, const slod_lod_factor *f, int n_members)
 {
   if (!f)
     return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": NULL factor");
   if (f->h != h || f->n != h->NP * h->cfg.spacedim)
     return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": factor of another handle / row count");
+  if (f->n_members != n_members)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": factor of another member count");
   return SLOD_OK;
 }
+
+namespace
+{
+  constexpr int MAX_MEMBERS = 65535; // members sit on blockIdx.y
+
+  // slod_lod_factor_create is the call with ld_m = 1, n_members = 1 and no bad_pivot; arguments are checked by the caller
+  int factor_create(slod_handle *h, const char *who, bool ensemble, const double *d_values, size_t ld_m, int n_members,
+                    const uint32_t *d_cols, int32_t *bad_pivot, slod_lod_factor **out)
+  {
+    hipStream_t st;
+    if (const int rc = slod_enter(h, nullptr, &st))
+      return rc;
+    const SlodGrid G = slod_grid_of(h);
+    const int      s = G.spacedim, w = 2 * G.oversampling + 1, cap = slod_lod_row_capacity(h);
+    slod_lod_factor f;
+    f.h         = h;
+    f.n         = h->NP * s;
+    f.b         = s * (w * G.N + w) + s - 1;
+    f.nb        = (f.n + FB - 1) / FB;
+    f.bb        = (f.b + FB - 1) / FB;
+    f.n_members = n_members;
+    // one allocation: per member the band, the factored diagonal tiles, the pivots and the reciprocal diagonal of L, then
+    // the row map and the status words
+    const size_t npad = (size_t)f.nb * FB, nband = (size_t)f.nb * (f.bb + 1) * FT, nd = nband + (size_t)f.nb * FT + 2 * npad;
+    const size_t K    = (size_t)n_members;
+    f.member_doubles  = nd;
+    f.bytes           = K * nd * sizeof(double) + (npad + K) * sizeof(int);
+    hipError_t e      = f.mem.alloc(f.bytes); // freed with f on every error return below
+    if (e != hipSuccess)
+      return slod_hip_fail(h, e, who);
+    f.band   = (double *)f.mem.get();
+    f.diag   = f.band + nband;
+    f.piv    = f.diag + (size_t)f.nb * FT;
+    f.dinv   = f.piv + npad;
+    f.rowmap = (int *)(f.band + K * nd);
+    f.status = f.rowmap + npad;
+    std::vector<double> piv(K * npad);
+    std::vector<int>    bad(K, -1);
+    e = hipMemsetAsync(f.band, 0, K * nd * sizeof(double), st);
+    if (e == hipSuccess)
+      e = hipMemsetAsync(f.status, 0xff, K * sizeof(int), st); // -1
+    if (e == hipSuccess)
+      {
+        const size_t nval = (size_t)h->NP * cap * s * s;
+        hipLaunchKernelGGL(k_factor_rowmap, dim3((unsigned)((npad + 255) / 256), (unsigned)K), dim3(256), 0, st, G, f.n, (int)npad, f.bb,
+                           f.rowmap, f.band, nd);
+        hipLaunchKernelGGL(k_factor_scatter, dim3((unsigned)((nval * K + 255) / 256)), dim3(256), 0, st, G, h->NP, cap, f.bb, n_members,
+                           d_values, ld_m, d_cols, f.band, nd);
+        for (int col = 0; col < f.nb; ++col)
+          hipLaunchKernelGGL(k_factor_column, dim3((unsigned)(std::min(f.bb, f.nb - 1 - col) + 1), (unsigned)K), dim3(64), 0, st, col, f.bb,
+                             f.band, f.diag, f.piv, f.dinv, f.status, nd);
+        e = hipGetLastError();
+      }
+    // one read-back: the pivots of every member (npad doubles every nd) and the status words
+    if (e == hipSuccess)
+      e = hipMemcpy2DAsync(piv.data(), npad * sizeof(double), f.piv, nd * sizeof(double), npad * sizeof(double), K, hipMemcpyDeviceToHost,
+                           st);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(bad.data(), f.status, K * sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess)
+      e = hipStreamSynchronize(st);
+    if (e != hipSuccess)
+      {
+        (void)hipStreamSynchronize(st); // nothing may still run on the band when f frees it
+        return slod_hip_fail(h, e, who);
+      }
+    if (bad_pivot)
+      std::copy(bad.begin(), bad.end(), bad_pivot);
+    for (size_t k = 0; k < K; ++k)
+      if (bad[k] >= 0)
+        {
+          char msg[200];
+          if (ensemble)
+            std::snprintf(msg, sizeof msg, "%s: member %zu: pivot %d of %d is not positive (%g): the matrix is not positive definite", who,
+                          k, bad[k], f.n, piv[k * npad + (size_t)bad[k]]);
+          else
+            std::snprintf(msg, sizeof msg, "%s: pivot %d of %d is not positive (%g): the matrix is not positive definite", who, bad[k],
+                          f.n, piv[(size_t)bad[k]]);
+          return slod_fail(h, SLOD_ERR_NUMERIC, msg);
+        }
+    f.member_min.resize(K), f.member_max.resize(K);
+    for (size_t k = 0; k < K; ++k)
+      {
+        f.member_min[k] = *std::min_element(piv.begin() + k * npad, piv.begin() + k * npad + f.n);
+        f.member_max[k] = *std::max_element(piv.begin() + k * npad, piv.begin() + k * npad + f.n);
+      }
+    f.min_pivot = *std::min_element(f.member_min.begin(), f.member_min.end());
+    f.max_pivot = *std::max_element(f.member_max.begin(), f.member_max.end());
+    *out        = new slod_lod_factor(std::move(f));
+    return SLOD_OK;
+  }
+} // namespace
 
 #pragma GCC visibility push(default)
 extern "C" {
@@ -295,68 +406,22 @@ int slod_lod_factor_create(slod_handle *h, const double *d_values, const uint32_
     return SLOD_ERR_ARGUMENT;
   if (!d_values || !d_cols || !out)
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_factor_create: NULL array or out");
-  hipStream_t st;
-  if (const int rc = slod_enter(h, nullptr, &st))
+  return factor_create(h, "slod_lod_factor_create", false, d_values, 1, 1, d_cols, nullptr, out);
+}
+
+int slod_lod_factor_create_ensemble(slod_handle *h, const double *d_values, size_t ld_m, int n_members, const uint32_t *d_cols,
+                                    int32_t *bad_pivot, slod_lod_factor **out)
+{
+  const char *who = "slod_lod_factor_create_ensemble";
+  if (out)
+    *out = nullptr;
+  if (!h || !d_values || !d_cols || !out)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": NULL handle, array or out");
+  if (n_members < 1 || n_members > MAX_MEMBERS)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": n_members < 1 or > 65535");
+  if (const int rc = slod_check_ld(h, who, "n_members", n_members, {ld_m}))
     return rc;
-  const SlodGrid G = slod_grid_of(h);
-  const int      s = G.spacedim, w = 2 * G.oversampling + 1, cap = slod_lod_row_capacity(h);
-  slod_lod_factor f;
-  f.h    = h;
-  f.n    = h->NP * s;
-  f.b    = s * (w * G.N + w) + s - 1;
-  f.nb   = (f.n + FB - 1) / FB;
-  f.bb   = (f.b + FB - 1) / FB;
-  // one allocation: the band, the factored diagonal tiles, the pivots, the reciprocal diagonal of L, then the row map
-  // and the status word
-  const size_t npad = (size_t)f.nb * FB, nband = (size_t)f.nb * (f.bb + 1) * FT, nd = nband + (size_t)f.nb * FT + 2 * npad;
-  f.bytes = nd * sizeof(double) + (npad + 1) * sizeof(int);
-  hipError_t e = f.mem.alloc(f.bytes); // freed with f on every error return below
-  if (e != hipSuccess)
-    return slod_hip_fail(h, e, "slod_lod_factor_create");
-  f.band   = (double *)f.mem.get();
-  f.diag   = f.band + nband;
-  f.piv    = f.diag + (size_t)f.nb * FT;
-  f.dinv   = f.piv + npad;
-  f.rowmap = (int *)(f.dinv + npad);
-  f.status = f.rowmap + npad;
-  std::vector<double> piv(npad);
-  int                 bad = -1;
-  e = hipMemsetAsync(f.band, 0, nd * sizeof(double), st);
-  if (e == hipSuccess)
-    e = hipMemsetAsync(f.status, 0xff, sizeof(int), st); // -1
-  if (e == hipSuccess)
-    {
-      const size_t nval = (size_t)h->NP * cap * s * s;
-      hipLaunchKernelGGL(k_factor_rowmap, dim3((unsigned)((npad + 255) / 256)), dim3(256), 0, st, G, f.n, (int)npad, f.bb, f.rowmap, f.band);
-      hipLaunchKernelGGL(k_factor_scatter, dim3((unsigned)((nval + 255) / 256)), dim3(256), 0, st, G, h->NP, cap, f.bb, d_values, d_cols,
-                         f.band);
-      for (int K = 0; K < f.nb; ++K)
-        hipLaunchKernelGGL(k_factor_column, dim3((unsigned)(std::min(f.bb, f.nb - 1 - K) + 1)), dim3(64), 0, st, K, f.bb, f.band, f.diag,
-                           f.piv, f.dinv, f.status);
-      e = hipGetLastError();
-    }
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(piv.data(), f.piv, npad * sizeof(double), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(&bad, f.status, sizeof(int), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  if (e != hipSuccess)
-    {
-      (void)hipStreamSynchronize(st); // nothing may still run on the band when f frees it
-      return slod_hip_fail(h, e, "slod_lod_factor_create");
-    }
-  if (bad >= 0)
-    {
-      char msg[160];
-      std::snprintf(msg, sizeof msg, "slod_lod_factor_create: pivot %d of %d is not positive (%g): the matrix is not positive definite",
-                    bad, f.n, piv[(size_t)bad]);
-      return slod_fail(h, SLOD_ERR_NUMERIC, msg);
-    }
-  f.min_pivot = *std::min_element(piv.begin(), piv.begin() + f.n);
-  f.max_pivot = *std::max_element(piv.begin(), piv.begin() + f.n);
-  *out        = new slod_lod_factor(std::move(f));
-  return SLOD_OK;
+  return factor_create(h, who, true, d_values, ld_m, n_members, d_cols, bad_pivot, out);
 }
 
 int slod_lod_factor_get_info(const slod_lod_factor *f, slod_lod_factor_info *info)
@@ -372,6 +437,18 @@ int slod_lod_factor_get_info(const slod_lod_factor *f, slod_lod_factor_info *inf
   return SLOD_OK;
 }
 
+int slod_lod_factor_get_info_member(const slod_lod_factor *f, int member, slod_lod_factor_info *info)
+{
+  if (!f || !info)
+    return slod_fail(f ? f->h : nullptr, SLOD_ERR_ARGUMENT, "slod_lod_factor_get_info_member: NULL factor or info");
+  if (member < 0 || member >= f->n_members)
+    return slod_fail(f->h, SLOD_ERR_ARGUMENT, "slod_lod_factor_get_info_member: no such member");
+  slod_lod_factor_get_info(f, info);
+  info->min_pivot = f->member_min[(size_t)member];
+  info->max_pivot = f->member_max[(size_t)member];
+  return SLOD_OK;
+}
+
 int slod_lod_factor_solve(slod_lod_factor *f, const double *d_rhs, size_t ld_rhs, int n_rhs, double *d_u, size_t ld_u, void *hip_stream)
 {
   if (!f)
@@ -383,12 +460,38 @@ int slod_lod_factor_solve(slod_lod_factor *f, const double *d_rhs, size_t ld_rhs
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_factor_solve: n_rhs < 1");
   if (const int rc = slod_check_ld(h, "slod_lod_factor_solve", "n_rhs", n_rhs, {ld_rhs, ld_u}))
     return rc;
+  if (f->n_members != 1)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_factor_solve: an ensemble factor of several members; use slod_lod_factor_solve_ensemble");
   hipStream_t st;
   if (const int rc = slod_enter(h, hip_stream, &st))
     return rc;
   slod_lod_factor_solve_launch(f, st, d_rhs, ld_rhs, n_rhs, d_u, ld_u);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_factor_solve");
+}
+
+int slod_lod_factor_solve_ensemble(slod_lod_factor *f, int first_member, int n_members, const double *d_rhs, size_t ld_rhs, int n_rhs,
+                                   double *d_u, size_t ld_u, void *hip_stream)
+{
+  const char *who = "slod_lod_factor_solve_ensemble";
+  if (!f)
+    return slod_fail(nullptr, SLOD_ERR_ARGUMENT, std::string(who) + ": NULL factor");
+  slod_handle *h = f->h;
+  if (!d_rhs || !d_u)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": NULL array");
+  if (n_rhs < 1 || n_members < 1)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": n_rhs < 1 or n_members < 1");
+  if (first_member < 0 || first_member > f->n_members - n_members)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": members outside the factor");
+  for (const size_t ld : {ld_rhs, ld_u})
+    if (ld / (size_t)n_rhs < (size_t)n_members)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": leading dimension below n_members * n_rhs");
+  hipStream_t st;
+  if (const int rc = slod_enter(h, hip_stream, &st))
+    return rc;
+  slod_lod_factor_solve_launch(f, st, d_rhs, ld_rhs, n_rhs, d_u, ld_u, first_member, n_members);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, who);
 }
 
 void slod_lod_factor_destroy(slod_lod_factor *f)

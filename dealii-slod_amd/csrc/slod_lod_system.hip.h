@@ -90,12 +90,13 @@ namespace
   //   p^T (J+I)x(J+I) q = (sum p)(sum q) + sum_rows (row sum p)(row sum q) + sum_cols (col sum p)(col sum q) + p.q
   // Every product pairs a quantity of p with the same quantity of q and nothing is contracted into an fma, so the
   // form is symmetric in (p, q) bit for bit; with the same lanes, the same component order and the same wave
-  // reduction on both sides, M[(p,d),(q,e)] and M[(q,e),(p,d)] are the same bits.
+  // reduction on both sides, M[(p,d),(q,e)] and M[(q,e),(p,d)] are the same bits.  Entry e of the slot goes to
+  // values[(out S S + e) ld].
   // ---------------------------------------------------------------------------------
   template <int S>
   __device__ __forceinline__ void lod_mass_slot(const SlodGrid &G, const Extent &pe, const double *phi, const PairGeom &pg,
                                                 const double *basis, size_t stride, const double *rho, double scale, size_t out,
-                                                double *values)
+                                                double *values, size_t ld)
   {
 #pragma clang fp contract(off)
     const int      lane = threadIdx.x & 63;
@@ -168,8 +169,60 @@ namespace
           for (int off = 32; off > 0; off >>= 1)
             v += __shfl_xor(v, off, 64);
           if (lane == 0)
-            values[out * S * S + d * S + e] = v * scale;
+            values[(out * S * S + d * S + e) * ld] = v * scale;
         }
+  }
+
+  // M_LOD block row `row` = patch p, the counterpart of lod_matrix_row: wave w = the candidate neighbours j = w, w+4, ...
+  // The pattern is that of lod_matrix_row: a pair that shares only a line of nodes keeps its column, value 0.
+  template <int S>
+  __device__ __forceinline__ void lod_mass_row(const SlodGrid &G, uint32_t p, size_t row, const double *basis, size_t stride,
+                                               const double *rho, double scale, double *values, size_t ld, uint32_t *cols)
+  {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cap = grid_row_capacity(G);
+    int       pcx, pcy;
+    grid_centre(G, p, pcx, pcy);
+    const Extent  pe = grid_extent(G, pcx, pcy);
+    const double *phi = basis + (size_t)p * stride;
+    for (int j = wave; j < cap; j += 4)
+      {
+        const size_t   out = row * cap + j;
+        const PairGeom pg = grid_pair(G, pcx, pcy, pe, j);
+        lod_mass_slot<S>(G, pe, phi, pg, basis, stride, rho, scale, out, values, ld);
+        if (lane == 0 && cols)
+          cols[out] = pg.col();
+      }
+  }
+
+  // Word w = ((p cap + j) s + d) s + e of (A + A^T) / 2 on a full set of block rows whose words are ld apart: the partner
+  // is A[q,j'][e][d], q = cols[p,j], j' the slot of p in row q (0 when there is none).  One rounding of the sum, an exact
+  // halving, both commutative: the result is symmetric bit for bit.
+  __device__ __forceinline__ double lod_symmetrize_word(int NP, int s, int cap, const double *values, size_t ld, const uint32_t *cols,
+                                                        size_t w)
+  {
+#pragma clang fp contract(off)
+    const size_t   ss = (size_t)s * s, slot = w / ss;
+    const int      de = (int)(w - slot * ss), d = de / s, e = de - d * s;
+    const uint32_t p = (uint32_t)(slot / cap), q = cols[slot];
+    if (q >= (uint32_t)NP)
+      return 0.0;
+    double t = 0.0;
+    for (int j = 0; j < cap; ++j)
+      if (cols[(size_t)q * cap + j] == p)
+        {
+          t = values[(((size_t)q * cap + j) * ss + e * s + d) * ld];
+          break;
+        }
+    return 0.5 * (values[w * ld] + t);
+  }
+
+  // alpha a + beta b, two roundings of the products and one of the sum (no fma)
+  __device__ __forceinline__ double lod_combine_word(double alpha, double a, double beta, double b)
+  {
+#pragma clang fp contract(off)
+    const double ta = alpha * a, tb = beta * b;
+    return ta + tb;
   }
 
   // C^T f for block row `row` = patch p: block of 256 threads over all its nodes; out[(row s + d) ld]

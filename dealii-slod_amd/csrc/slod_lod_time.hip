@@ -15,28 +15,12 @@
 
 namespace
 {
-  // M_LOD block rows.  Block = one row patch p, wave w = the candidate neighbours j = w, w+4, ... as in
-  // k_lod_matrix; the entry of a slot is lod_mass_slot (slod_lod_system.hip.h).
+  // M_LOD block rows.  Block = one row patch p; the row is lod_mass_row (slod_lod_system.hip.h).
   template <int S>
   __global__ __launch_bounds__(256) void k_lod_mass(const SlodGrid G, const uint32_t *rows, const double *basis, size_t stride,
                                                    const double *rho, double scale, double *values, uint32_t *cols)
   {
-    const int      lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int      cap = grid_row_capacity(G);
-    const uint32_t p = rows[blockIdx.x];
-    int            pcx, pcy;
-    grid_centre(G, p, pcx, pcy);
-    const Extent  pe = grid_extent(G, pcx, pcy);
-    const double *phi = basis + (size_t)p * stride;
-    for (int j = wave; j < cap; j += 4)
-      {
-        const size_t   out = (size_t)blockIdx.x * cap + j;
-        const PairGeom pg = grid_pair(G, pcx, pcy, pe, j);
-        lod_mass_slot<S>(G, pe, phi, pg, basis, stride, rho, scale, out, values);
-        // the pattern is that of k_lod_matrix: a pair that shares only a line of nodes keeps its column, value 0
-        if (lane == 0)
-          cols[out] = pg.col();
-      }
+    lod_mass_row<S>(G, rows[blockIdx.x], blockIdx.x, basis, stride, rho, scale, values, 1, cols);
   }
 
   // ---------------------------------------------------------------------------------
@@ -62,17 +46,13 @@ namespace
         }
   }
 
-  // out = alpha a + beta b, two roundings of the products and one of the sum (no fma)
+  // out = alpha a + beta b per word (lod_combine_word, slod_lod_system.hip.h)
   __global__ __launch_bounds__(256) void k_lod_combine(size_t n, double alpha, const double *a, double beta, const double *b,
                                                       double *out)
   {
-#pragma clang fp contract(off)
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n)
-      {
-        const double ta = alpha * a[i], tb = beta * b[i];
-        out[i]          = ta + tb;
-      }
+      out[i] = lod_combine_word(alpha, a[i], beta, b[i]);
   }
 
   // g = dt (theta b1 + (1 - theta) b0 - g) per (row, column); g holds A u on entry.  b0 / b1 NULL: zero load.
@@ -275,6 +255,51 @@ int slod_lod_theta_steps_direct(slod_handle *h, slod_lod_factor *f_S, const doub
         e = es;
     }
   return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_theta_steps_direct");
+}
+
+// The loop of slod_lod_theta_steps_direct with a matrix and a factor per column: the product is k_ens_apply
+// (slod_lod_ensemble.hip), the solve the member axis of k_factor_solve with one column per member; k_theta_rhs and
+// k_theta_advance work per (row, column) and serve as they are.
+int slod_lod_theta_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, const double *d_stiffness, size_t ld_m,
+                                         const uint32_t *d_cols, double dt, double theta, int n_steps, int n_members, double *d_u,
+                                         size_t ld_u, const double *d_load, size_t ld_load, size_t load_step_stride)
+{
+  const char *who = "slod_lod_theta_steps_ensemble_direct";
+  if (!h || !d_stiffness || !d_cols || !d_u)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": NULL handle, matrix, d_cols or d_u");
+  if (!(dt > 0.0) || !(theta >= 0.0 && theta <= 1.0))
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": dt <= 0 or theta outside [0, 1]");
+  if (n_steps < 1 || n_members < 1 || n_members > 65535)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": n_steps < 1, n_members < 1 or > 65535");
+  if (const int rc = slod_check_ld(h, who, "n_members", n_members, {ld_m, ld_u, d_load ? ld_load : ld_u}))
+    return rc;
+  if (const int rc = slod_lod_factor_check(h, who, f_S, n_members)) // last: it reads the factor
+    return rc;
+  hipStream_t st;
+  if (const int rc = slod_enter(h, nullptr, &st))
+    return rc;
+  const LodShape     w = lod_shape(h, n_members);
+  const size_t       nvec = (size_t)w.nrow * n_members;
+  SlodDevBuf<double> work; // g, delta
+  hipError_t         e = work.alloc(2 * nvec);
+  if (e == hipSuccess)
+    {
+      double *g = work.get(), *delta = g + nvec;
+      for (int k = 0; k < n_steps && e == hipSuccess; ++k)
+        {
+          const double *b0 = d_load ? d_load + (size_t)k * load_step_stride : nullptr;
+          const double *b1 = d_load ? d_load + (size_t)(k + 1) * load_step_stride : nullptr;
+          slod_lod_apply_ensemble_launch(h, st, d_stiffness, ld_m, d_cols, d_u, ld_u, n_members, g, (size_t)n_members);
+          hipLaunchKernelGGL(k_theta_rhs, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n_members, dt, theta, b0, b1, ld_load, g);
+          slod_lod_factor_solve_launch(f_S, st, g, (size_t)n_members, 1, delta, (size_t)n_members, 0, n_members);
+          hipLaunchKernelGGL(k_theta_advance, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n_members, delta, d_u, ld_u);
+          e = hipGetLastError();
+        }
+      const hipError_t es = hipStreamSynchronize(st); // the workspace is freed on return
+      if (e == hipSuccess)
+        e = es;
+    }
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, who);
 }
 
 } // extern "C"

@@ -100,7 +100,7 @@ namespace
         const uint32_t q  = pg.col();
         if (q == 0xffffffffu || !(row_dirty | dirty[q]))
           continue; // wave-uniform
-        lod_mass_slot<S>(G, pe, phi, pg, basis, stride, rho, scale, (size_t)p * cap + j, values);
+        lod_mass_slot<S>(G, pe, phi, pg, basis, stride, rho, scale, (size_t)p * cap + j, values, 1);
       }
   }
 

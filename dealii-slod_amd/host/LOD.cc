@@ -518,18 +518,133 @@ namespace slod
           "slod_lod_solve_ensemble");
     check(slod_lod_reconstruct_ensemble(handle, d_b, stride, member_stride, K, d_u, (std::size_t)K, d_fine, fine_size, nullptr),
           "slod_lod_reconstruct_ensemble");
-    check(slod_ensemble_moments(handle, d_fine, fine_size, K, fine_size, d_mean, d_var, nullptr), "slod_ensemble_moments");
-    check(slod_compute_error_norms(handle, 0, d_mean, nullptr, nullptr, nullptr, &ens_mean_norms, nullptr),
+    ensemble_moment_norms(d_fine, d_mean, d_var, ens_mean_norms, ens_dev_norms);
+    ens_stride = stride, ens_member_stride = member_stride;
+    d_ens_basis = d_b, d_ens_values = d_values, d_ens_cols = d_cols, d_ens_rhs = d_rhs;
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::ensemble_moment_norms(const double *d_fine, double *d_mean, double *d_var, slod_error_norms &mean,
+                                                 slod_error_norms &dev_norms)
+  {
+    const std::size_t NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+    const std::size_t fine_size = (NE + 1) * (NE + 1) * spacedim;
+    check(slod_ensemble_moments(handle, d_fine, fine_size, (int)par.n_members, fine_size, d_mean, d_var, nullptr),
+          "slod_ensemble_moments");
+    check(slod_compute_error_norms(handle, 0, d_mean, nullptr, nullptr, nullptr, &mean, nullptr),
           "slod_compute_error_norms"); // synchronises the handle's stream
     std::vector<double> dev(fine_size);
     if (hipMemcpy(dev.data(), d_var, fine_size * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-      throw std::runtime_error("solve_ensemble: variance download failed");
+      throw std::runtime_error("ensemble_moment_norms: variance download failed");
     for (double &v : dev)
       v = std::sqrt(v);
     if (hipMemcpy(d_var, dev.data(), fine_size * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-      throw std::runtime_error("solve_ensemble: deviation upload failed");
-    check(slod_compute_error_norms(handle, 0, d_var, nullptr, nullptr, nullptr, &ens_dev_norms, nullptr),
-          "slod_compute_error_norms");
+      throw std::runtime_error("ensemble_moment_norms: deviation upload failed");
+    check(slod_compute_error_norms(handle, 0, d_var, nullptr, nullptr, nullptr, &dev_norms, nullptr), "slod_compute_error_norms");
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::assemble_mass_matrix_ensemble()
+  {
+    if (!d_ens_values)
+      throw std::runtime_error("assemble_mass_matrix_ensemble: solve_ensemble comes first");
+    const int          K = (int)par.n_members;
+    const unsigned int n_patches = (unsigned int)patches.size();
+    const int          cap = slod_lod_row_capacity(handle);
+    check(cap, "slod_lod_row_capacity");
+    const std::size_t n_slots = (std::size_t)n_patches * cap;
+    if (!d_ens_mass)
+      d_ens_mass = device_alloc<double>(n_slots * spacedim * spacedim * K);
+    // the call writes its columns; they must be those of the stiffness ensemble, which the loop uses for both matrices
+    uint32_t *d_m_cols = nullptr;
+    if (hipMalloc((void **)&d_m_cols, n_slots * sizeof(uint32_t)) != hipSuccess)
+      throw std::runtime_error("assemble_mass_matrix_ensemble: hipMalloc of the columns failed");
+    const int rc = slod_lod_mass_matrix_ensemble(handle, d_ens_basis, ens_stride, ens_member_stride, K, nullptr, 0, d_ens_mass,
+                                                 (std::size_t)K, d_m_cols, nullptr);
+    std::vector<uint32_t> m_cols(n_slots), a_cols(n_slots);
+    const bool            copied = rc == SLOD_OK &&
+                        hipMemcpy(m_cols.data(), d_m_cols, n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess &&
+                        hipMemcpy(a_cols.data(), d_ens_cols, n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(d_m_cols);
+    check(rc, "slod_lod_mass_matrix_ensemble");
+    if (!copied || m_cols != a_cols)
+      throw std::runtime_error("assemble_mass_matrix_ensemble: the pattern of M_LOD differs from that of A_LOD");
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_heat_ensemble(const unsigned int n_steps, const double dt, const double theta)
+  {
+    if (!d_ens_mass)
+      throw std::runtime_error("solve_heat_ensemble: assemble_mass_matrix_ensemble comes first");
+    const int          K = (int)par.n_members;
+    const unsigned int n_patches = (unsigned int)patches.size();
+    const std::size_t  NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+    const std::size_t  fine_size = (NE + 1) * (NE + 1) * spacedim, n_coarse = (std::size_t)n_patches * spacedim;
+    const int          cap = slod_lod_row_capacity(handle);
+    check(cap, "slod_lod_row_capacity");
+    const std::size_t n_words = (std::size_t)n_patches * cap * spacedim * spacedim;
+    if (!d_ens_shifted)
+      d_ens_shifted = device_alloc<double>(n_words * K);
+    double *d_u = device_alloc<double>(n_coarse * K), *d_ell = device_alloc<double>(n_coarse * K);
+    double *d_fine = device_alloc<double>(fine_size * K), *d_ell_fine = device_alloc<double>(fine_size * K);
+    double *d_mean = device_alloc<double>(fine_size), *d_var = device_alloc<double>(fine_size);
+    double *d_one = device_alloc<double>(n_words + 2 * n_coarse); // one member's matrix, load and elliptic solution
+    // the elliptic solution of member k as solve() finds it: slod_lod_solve on the de-interleaved matrix and load
+    // (the copies go through the host: this is the driver's reference, not the loop)
+    std::vector<double> all_values(n_words * K), all_rhs(n_coarse * K), all_ell(n_coarse * K), one(n_words + n_coarse), u1(n_coarse);
+    double             *d_rhs1 = d_one + n_words, *d_u1 = d_rhs1 + n_coarse;
+    if (hipMemcpy(all_values.data(), d_ens_values, all_values.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(all_rhs.data(), d_ens_rhs, all_rhs.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      throw std::runtime_error("solve_heat_ensemble: downloading the ensemble matrix failed");
+    for (int k = 0; k < K; ++k)
+      {
+        for (std::size_t i = 0; i < n_words; ++i)
+          one[i] = all_values[i * K + k];
+        for (std::size_t i = 0; i < n_coarse; ++i)
+          one[n_words + i] = all_rhs[i * K + k];
+        if (hipMemcpy(d_one, one.data(), one.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+          throw std::runtime_error("solve_heat_ensemble: uploading a member failed");
+        check(slod_lod_solve(handle, d_one, d_ens_cols, d_rhs1, d_u1, lod_rel_tol, lod_max_iterations, nullptr), "slod_lod_solve");
+        if (hipMemcpy(u1.data(), d_u1, n_coarse * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+          throw std::runtime_error("solve_heat_ensemble: downloading a solution failed");
+        for (std::size_t i = 0; i < n_coarse; ++i)
+          all_ell[i * K + k] = u1[i];
+      }
+    if (hipMemcpy(d_ell, all_ell.data(), all_ell.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+      throw std::runtime_error("solve_heat_ensemble: uploading the elliptic solutions failed");
+    check(slod_lod_reconstruct_ensemble(handle, d_ens_basis, ens_stride, ens_member_stride, K, d_ell, (std::size_t)K, d_ell_fine,
+                                        fine_size, nullptr),
+          "slod_lod_reconstruct_ensemble");
+    ens_lod_norms.assign(K, slod_error_norms{});
+    for (int k = 0; k < K; ++k)
+      check(slod_compute_error_norms(handle, (uint32_t)k, d_ell_fine + k * fine_size, nullptr, nullptr, nullptr, &ens_lod_norms[k], nullptr),
+            "slod_compute_error_norms");
+    // S_k = M_k + theta dt A_k, one factor object, the loop
+    check(slod_lod_matrix_combine_ensemble(handle, 1.0, d_ens_mass, (std::size_t)K, theta * dt, d_ens_values, (std::size_t)K, K,
+                                           d_ens_shifted, (std::size_t)K, nullptr),
+          "slod_lod_matrix_combine_ensemble");
+    slod_lod_factor *f = nullptr;
+    check(slod_lod_factor_create_ensemble(handle, d_ens_shifted, (std::size_t)K, K, d_ens_cols, nullptr, &f),
+          "slod_lod_factor_create_ensemble");
+    factors.push_back(f);
+    check(slod_lod_factor_get_info(f, &lod_factor_info), "slod_lod_factor_get_info");
+    if (hipMemset(d_u, 0, n_coarse * K * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+      throw std::runtime_error("solve_heat_ensemble: clearing the initial state failed");
+    ens_heat_error.assign((std::size_t)n_steps * K, slod_error_norms{});
+    for (unsigned int step = 0; step < n_steps; ++step)
+      {
+        check(slod_lod_theta_steps_ensemble_direct(handle, f, d_ens_values, (std::size_t)K, d_ens_cols, dt, theta, 1, K, d_u,
+                                                   (std::size_t)K, d_ens_rhs, (std::size_t)K, 0),
+              "slod_lod_theta_steps_ensemble_direct");
+        check(slod_lod_reconstruct_ensemble(handle, d_ens_basis, ens_stride, ens_member_stride, K, d_u, (std::size_t)K, d_fine, fine_size,
+                                            nullptr),
+              "slod_lod_reconstruct_ensemble");
+        for (int k = 0; k < K; ++k)
+          check(slod_compute_error_norms(handle, (uint32_t)k, d_ell_fine + k * fine_size, d_fine + k * fine_size, nullptr, nullptr,
+                                         &ens_heat_error[(std::size_t)step * K + k], nullptr),
+                "slod_compute_error_norms");
+      }
+    ensemble_moment_norms(d_fine, d_mean, d_var, ens_heat_mean_norms, ens_heat_dev_norms);
   }
 
   template <int dim, int spacedim>

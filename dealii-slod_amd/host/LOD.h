@@ -175,6 +175,23 @@ namespace slod
     const std::vector<double> &ensemble_rel_residuals() const { return lod_ens_residuals; }    // per member
     const slod_error_norms    &norms_ensemble_mean() const { return ens_mean_norms; }
     const slod_error_norms    &norms_ensemble_deviation() const { return ens_dev_norms; }
+    // M_LOD of every member on the ensemble slab of solve_ensemble() (slod_lod_mass_matrix_ensemble, density 1); after
+    // solve_ensemble()
+    void assemble_mass_matrix_ensemble();
+    // solve_heat(.., direct = true) for all members at once, after assemble_mass_matrix_ensemble(): S_k = M_k + theta dt A_k
+    // (slod_lod_matrix_combine_ensemble), one factor object for all members (slod_lod_factor_create_ensemble; the lower
+    // triangle is read, as in solve_heat) and n_steps calls of slod_lod_theta_steps_ensemble_direct with one step each
+    // (the calls compose bit for bit), from u = 0 with the load of solve_ensemble().  After every step the states are
+    // reconstructed and compared with the members' elliptic solutions: member k's elliptic solution is slod_lod_solve
+    // on its de-interleaved matrix, so that the distances are those of solve_heat + compare_heat_with_lod of a problem
+    // with member k's coefficient.  Then the moments of the final states as in solve_ensemble().  last_factor_info() is
+    // the range over all members.
+    void solve_heat_ensemble(const unsigned int n_steps, const double dt, const double theta);
+    // [step * n_members + member]: the norms of C_k u_k - C_k u_k^heat after step + 1 steps; [member]: those of C_k u_k
+    const std::vector<slod_error_norms> &error_heat_ensemble() const { return ens_heat_error; }
+    const std::vector<slod_error_norms> &norms_LOD_ensemble() const { return ens_lod_norms; }
+    const slod_error_norms              &norms_heat_ensemble_mean() const { return ens_heat_mean_norms; }
+    const slod_error_norms              &norms_heat_ensemble_deviation() const { return ens_heat_dev_norms; }
     // After assemble_global_matrix(), when the coefficient of the problem class has changed in part of the domain (the
     // reference has no counterpart): re-samples it (slod_update_coefficient finds the patches that see a changed fine
     // element), rebuilds those patches in place on the device slab (slod_plan_create_dirty), recomputes the entries of
@@ -268,6 +285,14 @@ namespace slod
     std::vector<int>    lod_ens_iterations;
     std::vector<double> lod_ens_residuals;
     slod_error_norms    ens_mean_norms{}, ens_dev_norms{};
+    // what solve_ensemble leaves for the ensemble time loop: slab, matrices, columns, coarse loads; then M and S
+    std::size_t ens_stride = 0, ens_member_stride = 0;
+    double     *d_ens_basis = nullptr, *d_ens_values = nullptr, *d_ens_rhs = nullptr, *d_ens_mass = nullptr, *d_ens_shifted = nullptr;
+    uint32_t   *d_ens_cols = nullptr;
+    std::vector<slod_error_norms> ens_heat_error, ens_lod_norms;
+    slod_error_norms              ens_heat_mean_norms{}, ens_heat_dev_norms{};
+    // mean and standard deviation of n_members fine fields: slod_ensemble_moments, the square root on the host, the norms
+    void ensemble_moment_norms(const double *d_fine, double *d_mean, double *d_var, slod_error_norms &mean, slod_error_norms &dev);
 
     void check(const int status, const char *what) const;
     std::vector<Point<dim>> fine_quadrature_points() const;

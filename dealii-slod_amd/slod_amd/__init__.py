@@ -157,6 +157,15 @@ def load():
                                             C.c_int, C.POINTER(C.c_int), dp]
     lib.slod_lod_reconstruct_ensemble.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp]
     lib.slod_ensemble_moments.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_size_t, vp, vp, vp]
+    lib.slod_lod_mass_matrix_ensemble.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, vp]
+    lib.slod_lod_matrix_symmetrize_ensemble.argtypes = [vp, vp, C.c_size_t, vp, C.c_int, vp, C.c_size_t, vp]
+    lib.slod_lod_matrix_combine_ensemble.argtypes = [vp, C.c_double, vp, C.c_size_t, C.c_double, vp, C.c_size_t, C.c_int, vp,
+                                                     C.c_size_t, vp]
+    lib.slod_lod_factor_create_ensemble.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(vp)]
+    lib.slod_lod_factor_get_info_member.argtypes = [vp, C.c_int, C.POINTER(FactorInfo)]
+    lib.slod_lod_factor_solve_ensemble.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp]
+    lib.slod_lod_theta_steps_ensemble_direct.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_double, C.c_double, C.c_int, C.c_int, vp,
+                                                         C.c_size_t, vp, C.c_size_t, C.c_size_t]
     lib.slod_update_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, C.c_int, C.c_size_t, C.c_int, vp]
     lib.slod_dirty_patches.argtypes = [vp, vp, u32p, C.c_size_t]
     lib.slod_plan_create_dirty.argtypes = [vp, C.c_uint32, vp, C.POINTER(vp)]
@@ -346,6 +355,38 @@ class Factor:
             self.close()
         except Exception:
             pass
+
+
+class EnsembleFactor(Factor):
+    """slod_lod_factor of an ensemble matrix: a factor per member in one object.  .info is the range over all members,
+    .member_info(k) that of member k, .bad_pivot the first non-positive pivot per member (-1 everywhere on success).
+    When a member fails, SlodError(-5) carries .bad_pivot; drop those members and factor again."""
+
+    def __init__(self, slod, d_values, d_cols, n_members, ld_m=None):
+        self.slod, self.lib, self.n_members = slod, slod.lib, n_members
+        self.f = C.c_void_p()
+        self.bad_pivot = np.full(max(n_members, 1), -1, dtype=np.int32)
+        rc = self.lib.slod_lod_factor_create_ensemble(slod.h, d_values, n_members if ld_m is None else ld_m, n_members, d_cols,
+                                                      self.bad_pivot.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(self.f))
+        if rc:
+            err = SlodError(rc, self.lib.slod_last_error(slod.h).decode())
+            err.bad_pivot = self.bad_pivot[:max(n_members, 0)].copy()
+            raise err
+        self.info = FactorInfo()
+        slod._check(self.lib.slod_lod_factor_get_info(self.f, C.byref(self.info)))
+        slod._factors.add(self)
+
+    def member_info(self, member):
+        info = FactorInfo()
+        self.slod._check(self.lib.slod_lod_factor_get_info_member(self.f, member, C.byref(info)))
+        return info
+
+    def solve(self, d_rhs, d_u, n_rhs=1, first_member=0, n_members=None, ld_rhs=None, ld_u=None, stream=None):
+        """Member first_member + k solves the columns k * n_rhs .. of d_rhs into d_u (ld defaults to n_members * n_rhs);
+        d_u may be d_rhs.  Asynchronous."""
+        K = self.n_members - first_member if n_members is None else n_members
+        self.slod._check(self.lib.slod_lod_factor_solve_ensemble(self.f, first_member, K, d_rhs, K * n_rhs if ld_rhs is None else ld_rhs,
+                                                                 n_rhs, d_u, K * n_rhs if ld_u is None else ld_u, stream))
 
 
 def _factor_ptr(f):
@@ -688,6 +729,37 @@ class Slod:
         Asynchronous."""
         self._check(self.lib.slod_ensemble_moments(self.h, d_fields, count if ld_fine is None else ld_fine, n_members, count,
                                                    d_mean, d_var, stream))
+
+    # ---- the L2 side and the direct solver of an ensemble: a factor per member, the theta scheme with a column per member ----
+    def lod_mass_matrix_ensemble(self, d_basis, stride, n_members, d_values, d_cols, d_rho=None, ld_rho=0, member_stride=None,
+                                 ld_m=None, stream=None):
+        """Block rows of M_LOD of every member; d_rho None = 1, ld_rho = 0: one density for all members.  Asynchronous."""
+        self._check(self.lib.slod_lod_mass_matrix_ensemble(
+            self.h, d_basis, stride, self.num_patches * stride if member_stride is None else member_stride, n_members, d_rho,
+            ld_rho, d_values, n_members if ld_m is None else ld_m, d_cols, stream))
+
+    def lod_matrix_symmetrize_ensemble(self, d_values, d_cols, n_members, d_out, ld_in=None, ld_out=None, stream=None):
+        """out_k = 0.5 * (A_k + A_k^T) per member; not in place.  Asynchronous."""
+        self._check(self.lib.slod_lod_matrix_symmetrize_ensemble(self.h, d_values, n_members if ld_in is None else ld_in, d_cols,
+                                                                 n_members, d_out, n_members if ld_out is None else ld_out, stream))
+
+    def lod_matrix_combine_ensemble(self, alpha, d_a, beta, d_b, n_members, d_out, ld_a=None, ld_b=None, ld_out=None, stream=None):
+        """out_k = alpha * A_k + beta * B_k per member (out may be an input of the same ld).  Asynchronous."""
+        self._check(self.lib.slod_lod_matrix_combine_ensemble(
+            self.h, alpha, d_a, n_members if ld_a is None else ld_a, beta, d_b, n_members if ld_b is None else ld_b, n_members,
+            d_out, n_members if ld_out is None else ld_out, stream))
+
+    def lod_factor_ensemble(self, d_values, d_cols, n_members, ld_m=None):
+        """The Cholesky factors of the members of an ensemble matrix in one object (EnsembleFactor)."""
+        return EnsembleFactor(self, d_values, d_cols, n_members, ld_m)
+
+    def lod_theta_steps_ensemble_direct(self, factor, d_stiffness, d_cols, dt, theta, n_steps, n_members, d_u, ld_m=None,
+                                        ld_u=None, d_load=None, ld_load=None, load_step_stride=0):
+        """lod_theta_steps_direct with a column, a matrix and a factor per member; the factor is that of
+        lod_matrix_combine_ensemble(1, M, theta * dt, A)."""
+        self._check(self.lib.slod_lod_theta_steps_ensemble_direct(
+            self.h, _factor_ptr(factor), d_stiffness, n_members if ld_m is None else ld_m, d_cols, dt, theta, n_steps, n_members,
+            d_u, n_members if ld_u is None else ld_u, d_load, n_members if ld_load is None else ld_load, load_step_stride))
 
     def fem_rhs(self, d_f_qp, d_fine_rhs, stream=None):
         """Fine FEM load vector (d_f_qp = None: f = 1)."""

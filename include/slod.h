@@ -558,6 +558,72 @@ int slod_lod_reconstruct_ensemble(slod_handle *h, const double *d_basis, size_t 
 int slod_ensemble_moments(slod_handle *h, const double *d_fields, size_t ld_fine, int n_members, size_t count,
                           double *d_mean, double *d_var /* may be NULL */, void *hip_stream);
 
+/* ---- ensemble time stepping on banded Cholesky factors, one per member ---------------------------
+ * The L2 side and the direct solver for a coefficient ensemble, in the layouts above: M_LOD of every member, the
+ * symmetrised stiffness, S = M + theta dt A, one factor object that holds a factor per member, and the theta scheme on
+ * it with one column per member.  The kernels are those of the single-problem calls (the row of slod_lod_mass_matrix,
+ * the words of slod_lod_matrix_symmetrize and slod_lod_matrix_combine, the block column and the two sweeps of the
+ * factor) with the member on a grid axis; a single-problem call is the instance n_members = 1, ld = 1.  Every result
+ * of member k has the bits of the single-problem call on member k's de-interleaved data.  The common argument checks are
+ * those of the ensemble block above.  Not built: Newmark on an ensemble factor, a CG ensemble stepper, the ensemble
+ * eigensolver, refactoring after slod_lod_matrix_update, members spread over ranks, several columns per member in the
+ * stepper. */
+/* Block rows of M_LOD of all num_patches patches for every member: member k's values are those of slod_lod_mass_matrix
+ * with rows 0 .. num_patches-1 on its slab, bit for bit.  d_cols is written once.  d_rho NULL: density 1; ld_rho = 0: one
+ * density [NE][NE] shared by all members; else member k's density at d_rho + k * ld_rho.  SLOD_ERR_ARGUMENT also for a
+ * d_rho with ld_rho neither 0 nor at least NE^2.  No row list is uploaded: ASYNCHRONOUS on hip_stream. */
+int slod_lod_mass_matrix_ensemble(slod_handle *h, const double *d_basis, size_t stride, size_t member_stride, int n_members,
+                                  const double *d_rho /* may be NULL */, size_t ld_rho, double *d_values, size_t ld_m,
+                                  uint32_t *d_cols, void *hip_stream);
+/* d_out = (A_k + A_k^T) / 2 per member, the bits of slod_lod_matrix_symmetrize.  SLOD_ERR_ARGUMENT also for
+ * d_out == d_values.  Asynchronous on hip_stream. */
+int slod_lod_matrix_symmetrize_ensemble(slod_handle *h, const double *d_values, size_t ld_in, const uint32_t *d_cols,
+                                        int n_members, double *d_out, size_t ld_out, void *hip_stream);
+/* d_out = alpha a + beta b per entry and member, (alpha a) + (beta b) rounded as in slod_lod_matrix_combine.  d_out may be
+ * d_a or d_b when the leading dimensions of the two are equal; SLOD_ERR_ARGUMENT otherwise.  Asynchronous on hip_stream. */
+int slod_lod_matrix_combine_ensemble(slod_handle *h, double alpha, const double *d_a, size_t ld_a, double beta,
+                                     const double *d_b, size_t ld_b, int n_members, double *d_out, size_t ld_out,
+                                     void *hip_stream);
+/* slod_lod_factor_create for every member of an ensemble matrix: one allocation of n_members copies of the single
+ * factor's storage (band tiles, diagonal tiles, pivots, reciprocal diagonal) and one row map; nb launches, each with the
+ * block rows of a block column on blockIdx.x and the member on blockIdx.y.  Member k reads and writes its own copy and its
+ * own status word only: a member that fails skips its later columns, the others finish, and member k's factor has the
+ * bits of slod_lod_factor_create on member k's de-interleaved matrix.  One read-back at the end.  bad_pivot[k]: the
+ * index of member k's first pivot that is not > 0, or -1; filled on SLOD_OK and on SLOD_ERR_NUMERIC.
+ * SLOD_ERR_NUMERIC: a member failed; *out stays NULL, nothing stays allocated, slod_last_error names the call, the lowest
+ * failing member, its pivot index and its value; the caller drops the members listed in bad_pivot and calls again.
+ * SLOD_ERR_ARGUMENT (before any device work): NULL handle, array or out; n_members < 1 or > 65535; ld_m < n_members.
+ * SLOD_ERR_DEVICE without a usable GPU.  Runs on the handle's stream; synchronises. */
+int slod_lod_factor_create_ensemble(slod_handle *h, const double *d_values, size_t ld_m, int n_members,
+                                    const uint32_t *d_cols, int32_t *bad_pivot /* HOST [n_members], may be NULL */,
+                                    slod_lod_factor **out);
+/* slod_lod_factor_get_info with the pivot range of one member (bytes: the whole allocation); slod_lod_factor_get_info
+ * itself reports the range over all members.  A factor of slod_lod_factor_create has the one member 0.
+ * SLOD_ERR_ARGUMENT: NULL factor or info, member < 0 or >= the factor's members. */
+int slod_lod_factor_get_info_member(const slod_lod_factor *f, int member, slod_lod_factor_info *info);
+/* Member first_member + k, k = 0 .. n_members-1, solves the n_rhs columns k * n_rhs .. k * n_rhs + n_rhs - 1 of d_rhs
+ * into the same columns of d_u; with n_rhs = 1 column k is member k, the layout of the other ensemble calls.  One block
+ * per 16 columns of a member and per member: the sweeps of slod_lod_factor_solve on that member's factor, so the bits of
+ * a column depend only on its member's factor and that column.  d_u == d_rhs is allowed.  Asynchronous on hip_stream;
+ * allocates nothing and reads nothing back.  slod_lod_factor_solve on a factor of more than one member is refused
+ * (SLOD_ERR_ARGUMENT), as are the time loops of one matrix (slod_lod_theta_steps_direct, slod_lod_newmark_*_direct).
+ * SLOD_ERR_ARGUMENT: NULL factor or array; n_rhs < 1; n_members < 1; first_member < 0 or first_member + n_members beyond
+ * the factor's members; an ld below n_members * n_rhs. */
+int slod_lod_factor_solve_ensemble(slod_lod_factor *f, int first_member, int n_members, const double *d_rhs, size_t ld_rhs,
+                                   int n_rhs, double *d_u, size_t ld_u, void *hip_stream);
+/* The loop of slod_lod_theta_steps_direct with one column per member: column k is advanced with matrix k of the ensemble
+ * matrix d_stiffness (slod_lod_apply_ensemble) and member k of f_S, which factors
+ * slod_lod_matrix_combine_ensemble(1, M, theta dt, A).  The loop is queued on the handle's stream and waited for once.
+ * Column k has the bits of slod_lod_theta_steps_direct(n_rhs = 1) on member k's single factor and matrix; n_steps = 2
+ * equals two calls with n_steps = 1.  Loads as in slod_lod_theta_steps (d_load NULL: none), column k = member k.
+ * SLOD_ERR_ARGUMENT: NULL handle, matrix, d_cols or d_u; dt <= 0; theta outside [0, 1]; n_steps < 1; n_members < 1 or
+ * > 65535; ld_m, ld_u or (with a load) ld_load below n_members; a NULL factor, the factor of another handle or row count,
+ * a factor whose member count is not n_members. */
+int slod_lod_theta_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, const double *d_stiffness, size_t ld_m,
+                                         const uint32_t *d_cols, double dt, double theta, int n_steps, int n_members,
+                                         double *d_u, size_t ld_u, const double *d_load, size_t ld_load,
+                                         size_t load_step_stride);
+
 /* ---- refresh after a local coefficient change ----------------------------------------------
  * Every entry point above takes the coefficient as fixed for the life of a basis (the reference does too: one
  * compute_basis_function_candidates per run, LOD.cc:1425-1433).  When it changes in a small part of the domain -- a
