@@ -39,11 +39,51 @@ struct PlanWorkspace
   double  *z = nullptr;       // k_solve_tw: Z of the forward sweep (active column prefix per line)
   double  *m = nullptr;       // [chunk][nc_max^2]: nothing but the clock stamps of the diag build, then
                               // [chunk][nc_max^2 + 1]: k_solve_tw's M + flag
-  int32_t *status = nullptr;
+  int32_t *status = nullptr;  // [0]: the word the kernels OR into, [1]: arrivals of k_workspace_reset's blocks
+  size_t   st_elems = 0, v_elems = 0, x_elems = 0, z_elems = 0, m_elems = 0; // doubles behind st, v, x_alloc, z, m
   // all of it for p.chunk patches, zero-filled where the kernels need it, or nothing (and the HIP error)
   hipError_t allocate(const slod_plan &p, bool own_z);
   void       release();
+  // first launch of an execute on `stream`: clears the status word and, if the last execute in this workspace
+  // left it set, zero-fills the arrays first
+  hipError_t reset(hipStream_t stream) const;
 };
+
+namespace
+{
+  struct WorkspaceSpans
+  {
+    double *p[5];
+    size_t  n[5];
+  };
+
+  // A failed execute leaves Inf/NaN in its workspace, and the sweeps and the selection stage read the banded
+  // neighbours of a line without range tests (0 x what is there must be 0): the next execute would inherit them.
+  // Every block reads the status word; if it is set the grid zero-fills the arrays and the block that arrives last
+  // clears it (no block can still be ahead of its read then).  A healthy workspace costs one load per block: no
+  // host synchronisation, and this launch stands where the hipMemsetAsync of the word stood.
+  __global__ void __launch_bounds__(256) k_workspace_reset(int32_t *status, WorkspaceSpans w)
+  {
+    if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
+      return;
+    for (int k = 0; k < 5; ++k)
+      for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < w.n[k]; i += (size_t)gridDim.x * 256)
+        w.p[k][i] = 0.0;
+    __syncthreads();
+    if (threadIdx.x == 0 && atomicAdd(status + 1, 1) == (int)gridDim.x - 1)
+      {
+        __hip_atomic_store(status + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(status, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+  }
+} // namespace
+
+hipError_t PlanWorkspace::reset(hipStream_t stream) const
+{
+  const WorkspaceSpans w = {{st, v, x_alloc, z, m}, {st_elems, v_elems, x_elems, z ? z_elems : 0, m_elems}};
+  hipLaunchKernelGGL(k_workspace_reset, dim3(256), dim3(256), 0, stream, status, w);
+  return hipGetLastError();
+}
 
 struct slod_plan
 {
@@ -80,8 +120,8 @@ hipError_t PlanWorkspace::allocate(const slod_plan &p, bool own_z)
 {
   // Guards: the kernels read the banded neighbours of a row / node without range tests (the
   // matching band coefficient is zero, or the result is dropped), so up to a few rows before the
-  // first and after the last slot are touched.  X is zero-filled once: a skipped product must meet
-  // a finite number.
+  // first and after the last slot are touched.  X is zero-filled here, and again by reset() after an
+  // execute that failed: a skipped product must meet a finite number.
   const size_t st_bytes = (p.chunk * p.st_stride + (size_t)4 * p.nn_max) * sizeof(double);
   const size_t v_bytes  = std::max<size_t>(1, p.chunk * p.v_stride) * sizeof(double);
   const size_t x_bytes  = (p.chunk * p.x_stride + 2 * p.guard) * sizeof(double);
@@ -97,7 +137,7 @@ hipError_t PlanWorkspace::allocate(const slod_plan &p, bool own_z)
   if (e == hipSuccess)
     e = hipMalloc((void **)&m, m_bytes);
   if (e == hipSuccess)
-    e = hipMalloc((void **)&status, sizeof(int32_t));
+    e = hipMalloc((void **)&status, 2 * sizeof(int32_t));
   if (e == hipSuccess)
     e = hipMemset(st, 0, st_bytes);
   if (e == hipSuccess)
@@ -105,9 +145,16 @@ hipError_t PlanWorkspace::allocate(const slod_plan &p, bool own_z)
   if (e == hipSuccess && own_z)
     e = hipMemset(z, 0, z_bytes);
   if (e == hipSuccess)
-    e = hipMemset(status, 0, sizeof(int32_t));
+    e = hipMemset(status, 0, 2 * sizeof(int32_t));
   if (e == hipSuccess)
-    x = x_alloc + p.guard;
+    {
+      x        = x_alloc + p.guard;
+      st_elems = st_bytes / sizeof(double);
+      v_elems  = v_bytes / sizeof(double);
+      x_elems  = x_bytes / sizeof(double);
+      z_elems  = z_bytes / sizeof(double);
+      m_elems  = m_bytes / sizeof(double);
+    }
   else
     release();
   return e;
@@ -740,7 +787,7 @@ int slod_plan_execute(slod_plan *p, double *d_basis, double *d_premult, void *hi
       st = own;
     }
   if (e == hipSuccess)
-    e = hipMemsetAsync(p->ws[slot].status, 0, sizeof(int32_t), st);
+    e = p->ws[slot].reset(st);
   size_t ci = 0;
   for (size_t first = 0; first < p->n && e == hipSuccess; first += p->chunk, ++ci)
     e = launch_range(p, first, (int)std::min(p->chunk, p->n - first), d_basis, d_premult, st,
@@ -1256,7 +1303,7 @@ int slod_plan_execute_allgather(slod_plan *p, slod_comm *c, double *d_basis_all,
   hipStream_t  cs = (hipStream_t)compute_stream, ns = (hipStream_t)comm_stream;
   const size_t slab = patches_per_rank * p->stride;
   double      *mb = d_basis_all + (size_t)c->rank * slab, *mp = d_premult_all + (size_t)c->rank * slab;
-  hipError_t   e  = p->n ? hipMemsetAsync(p->ws[0].status, 0, sizeof(int32_t), cs) : hipSuccess;
+  hipError_t   e  = p->n ? p->ws[0].reset(cs) : hipSuccess;
   Rccl        &r  = rccl();
   for (int piece = 0; piece < n_pieces && e == hipSuccess; ++piece)
     {

@@ -1188,14 +1188,17 @@ namespace
                 // term vectors: V_j (no QR) or w_j (after the QR); element a2 of term j
                 auto tvec = [&](int a2, int j) { return tposed ? Wm[a2 * ncm + j] : Vj[a2 * nn1 + j]; };
                 // descending sigma (stable: ties keep the column order), pseudo-inverse cutoff
-                // (LOD.cc:667): thread j ranks its own singular value
+                // (LOD.cc:667): thread j ranks its own singular value.  A NaN (the patch solve met a bad
+                // pivot, the status word says so) ranks as -1, below every sum of squares: the ranks stay a
+                // permutation, so every ord[] the loops below index with was written in this pass
+                auto key = [](double s) { return s == s ? s : -1.0; };
                 for (int j = tid; j < nn1; j += 256)
                   {
-                    const double sj = sig[j];
+                    const double sj = key(sig[j]);
                     int          rank = 0;
                     for (int i = 0; i < nn1; ++i)
                       {
-                        const double si = sig[i];
+                        const double si = key(sig[i]);
                         rank += (si > sj || (si == sj && i < j)) ? 1 : 0;
                       }
                     ord[rank] = j;

@@ -151,7 +151,16 @@ int slod_plan_join(slod_plan *p, void *hip_stream);
  * LOD.cc:122-244,770-858).  launch_order = 0: the caller's order; 1: the balanced launch order
  * (plan_index then tells which entry of the caller's list sits at launch position k). */
 int slod_plan_patch_layout(slod_plan *p, size_t k, int launch_order, slod_patch_info *info, uint32_t *plan_index);
-/* numerical status of the last execute (0 or SLOD_ERR_NUMERIC); synchronises. */
+/* numerical status of the last execute (0 or SLOD_ERR_NUMERIC); synchronises.
+ * SLOD_ERR_NUMERIC (here and from slod_compute_basis): at least one patch of the last execute met a pivot that is
+ * not positive or not finite, in its patch solve or in the inversion of M = P^T A^-1 P (an indefinite or singular
+ * patch matrix, NaN or Inf in the coefficient).  ALL outputs and diagnostics of that execute are undefined, those
+ * of the other patches included: the kernels read the workspace of neighbouring patches unchecked.  (The
+ * reference aborts the whole run here: AssertThrow after the patch solve, LODtools.h:416-428.)
+ * The plan and the handle remain usable: the next execute on valid coefficients gives the results of a fresh
+ * plan, bit for bit (it starts by zero-filling the workspace the failed one left; no host synchronisation).
+ * With slod_plan_set_overlap(2) the status covers the most recent execute of EACH of the two workspaces:
+ * directly after a failed execute and ONE good one it still reports the failure, after two good ones it is 0. */
 int slod_plan_status(slod_plan *p);
 
 /* Decisions the SLOD selection stage took for one (patch, component): the discontinuous part

@@ -1,6 +1,7 @@
 """Helpers shared by the GPU test modules (a plain module like fixture_utils.py, not a conftest): handles and
 coefficient upload, the parity check of one patch, dense copies of the block rows of the LOD matrices, the fine FEM
-reference, and the cases (basis, stiffness, mass, pencil) the tests of the LOD-space entry points build on.  Test
+reference, the cases (basis, stiffness, mass, pencil) the tests of the LOD-space entry points build on, and the
+coefficient fields on which a patch solve must fail (NUMERIC_CONFIGS, _bad_fields).  Test
 modules import from here and never from each other."""
 import numpy as np
 
@@ -175,6 +176,128 @@ def _mass_fine(NE, rho=None):
 
 class _Case:
     pass
+
+
+# ---- the failure path of the patch solve (test_gpu_numeric_status.py): coefficient fields on which some patch
+# matrices are not positive definite, the patches they hit, and a plan run that never raises ----
+NUMERIC_CONFIGS = {"scalar": dict(nref=3, n_sub=4, oversampling=1, spacedim=1, stabilize=1),
+                   "elasticity": dict(nref=2, n_sub=4, oversampling=1, spacedim=2, stabilize=1)}
+# an interior coarse cell: with oversampling 1 the 3 x 3 patch centres around it all exist.  On the scalar grid
+# (8 x 8 cells) all nine are full patches, so the cell takes every one of the nine positions in a 3 x 3 patch
+BAD_CELL = {"scalar": (3, 3), "elasticity": (1, 1)}
+BAD_KINDS = ("negative", "nan", "zero")
+BAD_VALUE = {"negative": -1.0, "nan": NAN, "zero": 0.0}
+ERR_NUMERIC = -5
+
+
+def _bad_fields(base, cfg_kw, kind, block=0, cell=None):
+    """(fields, bad coarse cells): copies of the base fields [NE][NE][4] with BAD_VALUE[kind] written to every field.
+    negative / nan: one 2 x 2 block of fine cells of the coarse cell, fine cells {0,1}^2 (block 0) or {2,3}^2
+    (block 1): the fine node in its middle is strictly inside the coarse cell.  zero: every fine cell of the 3 x 3
+    coarse cells around the cell (a full patch)."""
+    n = cfg_kw["n_sub"]
+    N = cfg_kw["n_cells"] if cfg_kw.get("n_cells", 0) > 0 else 1 << cfg_kw["nref"]
+    NE = N * n
+    cx, cy = cell if cell is not None else BAD_CELL["scalar" if cfg_kw.get("spacedim", 1) == 1 else "elasticity"]
+    if kind == "zero":
+        assert 1 <= cx < N - 1 and 1 <= cy < N - 1
+        x0, x1, y0, y1 = (cx - 1) * n, (cx + 2) * n, (cy - 1) * n, (cy + 2) * n
+        cells = {(i, j) for i in range(cx - 1, cx + 2) for j in range(cy - 1, cy + 2)}
+    else:
+        assert n == 4 and block in (0, 1)
+        x0, y0 = cx * n + 2 * block, cy * n + 2 * block
+        x1, y1 = x0 + 2, y0 + 2
+        cells = {(cx, cy)}
+    out = []
+    for a in base:
+        f = np.array(a, dtype=np.float64).reshape(NE, NE, 4)
+        f[y0:y1, x0:x1, :] = BAD_VALUE[kind]
+        out.append(f.ravel())
+    return out, cells
+
+
+def _patches_with_cells(so, cfg, cells):
+    """Ids of the patches whose extent holds one of the coarse cells (cx, cy), ascending."""
+    hit = []
+    for pid in range(so.num_patches(cfg)):
+        p = so.patch_info(cfg, pid)
+        if any(p.x0 <= i < p.x0 + p.mx and p.y0 <= j < p.y0 + p.my for i, j in cells):
+            hit.append(pid)
+    return hit
+
+
+def _internal_matrix(so, cfg, fields, pid):
+    """Dense A_II of one patch from the oracle's stencil [node][9][s][s], internal dofs in (node, component) order."""
+    p, s = so.patch_info(cfg, pid), cfg.spacedim
+    st = so.assemble_patch(cfg, fields, pid)
+    npx = p.nx + 1
+    idx = -np.ones((p.ny + 1, npx), dtype=np.int64)
+    idx[1:p.ny, 1:p.nx] = np.arange((p.ny - 1) * (p.nx - 1)).reshape(p.ny - 1, p.nx - 1)
+    A = np.zeros((s * (p.nx - 1) * (p.ny - 1),) * 2)
+    for iy in range(1, p.ny):
+        for ix in range(1, p.nx):
+            for dy in (-1, 0, 1):
+                for dx in (-1, 0, 1):
+                    j = idx[iy + dy, ix + dx]
+                    if j >= 0:
+                        i = idx[iy, ix]
+                        A[i * s:(i + 1) * s, j * s:(j + 1) * s] = st[ix + iy * npx, (dy + 1) * 3 + dx + 1]
+    return A
+
+
+class _BaseOracle:
+    """The oracle on the base fields of one NUMERIC_CONFIGS entry, every patch computed once and read-only.  It ignores
+    the fields it is handed: a patch that holds no bad cell has the base field's result bit for bit
+    (test_bad_fields_hit_exactly_the_patches_with_the_bad_cell), and that is the only kind _check_patch is asked about."""
+    _store = {}
+
+    def __init__(self, so, name):
+        self._so, self._name = so, name
+        self.cfg = so.make_cfg(**NUMERIC_CONFIGS[name])
+        self.base = make_fields(so, self.cfg, "D100")
+
+    def __getattr__(self, attr):
+        return getattr(self._so, attr)
+
+    def _memo(self, what, pid, fn):
+        k = (self._name, what, pid)
+        if k not in self._store:
+            v = fn()
+            for a in (v if isinstance(v, tuple) else (v,)):
+                if isinstance(a, np.ndarray):
+                    a.setflags(write=False)
+            self._store[k] = v
+        return self._store[k]
+
+    def patch_basis(self, cfg, fields, pid):
+        return self._memo("basis", pid, lambda: self._so.patch_basis(self.cfg, self.base, pid))
+
+    def assemble_patch(self, cfg, fields, pid):
+        return self._memo("stencil", pid, lambda: self._so.assemble_patch(self.cfg, self.base, pid))
+
+
+def _status_of(plan):
+    """(code, message) of slod_plan_status: (0, "") when the last execute was fine."""
+    import slod_amd
+    try:
+        plan.status()
+    except slod_amd.SlodError as e:
+        return e.code, str(e)
+    return 0, ""
+
+
+def _run(plan, stream=None):
+    """One execute into fresh NaN-filled slabs (what the plan does not write stays NaN); returns (basis, premult)."""
+    torch, dev = _torch()
+    b = torch.full((max(plan.output_size, 1),), NAN, dtype=torch.float64, device=dev)
+    q = torch.full_like(b, NAN)
+    plan.execute(b.data_ptr(), q.data_ptr(), stream)
+    return b, q
+
+
+def _patch_bits(plan, t, k, n):
+    """The 64-bit words of the k-th patch of a uniform-stride slab."""
+    return _bits(t[k * plan.stride:k * plan.stride + n])
 
 
 def _build(so, kw, dist="D100", fields=None):
