@@ -193,7 +193,8 @@ int slod_compute_basis(slod_handle *h, const uint32_t *gids, size_t n, double *b
  * sit in a slab with uniform stride (slod_plan_stride(): what a plan with NULL offsets
  * writes and what the all-gather of the multi-GPU path produces): patch p at
  * d_basis[p * stride + d * n_fine(p) + dof].  Overlaps of patches are index arithmetic on
- * the patch-lexicographic layout; no deal.II numbering is involved. */
+ * the patch-lexicographic layout; no deal.II numbering is involved.  Any stride >= s * max_p n_fine(p)
+ * is accepted: the words of a patch between its s vectors and the stride are never read. */
 /* Upper bound of patches q whose node set meets that of one patch: (4 l + 3)^2 (the closed patches
  * of two cells share a node as soon as their centres are at most 2 l + 1 cells apart per axis). */
 int slod_lod_row_capacity(const slod_handle *h);

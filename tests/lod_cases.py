@@ -1,7 +1,8 @@
 """Helpers shared by the GPU test modules (a plain module like fixture_utils.py, not a conftest): handles and
 coefficient upload, the parity check of one patch, dense copies of the block rows of the LOD matrices, the fine FEM
 reference, the cases (basis, stiffness, mass, pencil) the tests of the LOD-space entry points build on, and the
-coefficient fields on which a patch solve must fail (NUMERIC_CONFIGS, _bad_fields).  Test
+coefficient fields on which a patch solve must fail (NUMERIC_CONFIGS, _bad_fields), and the random slabs, geometries
+and extended-precision references of the slab consumers (SLAB_CONFIGS, _random_slab, _ref_*; pure numpy).  Test
 modules import from here and never from each other."""
 import numpy as np
 
@@ -368,3 +369,224 @@ def _pencil(so, name):
         c.lam, c.vec = sl.eigh(c.A, c.M)                   # vec^T M vec = I
         _cache[name] = c
     return _cache[name]
+
+
+# ---- slabs that are non-zero on patch rims (test_lod_slab_reference.py on the CPU, test_gpu_lod_slabs.py): geometry as
+# plain numbers, random slabs with NaN wherever a consumer must not read, and references of the four slab consumers
+# accumulated in np.longdouble.  Nothing here calls the library: the same code takes the extents of a GPU handle
+# (g.patch_layout) or of the oracle (so.patch_info). ----
+SLAB_CONFIGS = {"golden": dict(nref=2, n_sub=2, oversampling=1, spacedim=2),     # the all-ones geometry of parallel_assembly
+                "rowmajor": dict(n_cells=5, n_sub=3, oversampling=1, spacedim=1),   # row-major ids, odd n_sub, odd N
+                "wide": dict(nref=2, n_sub=1, oversampling=2, spacedim=2),          # 2 l + 1 > N, a fine element = a coarse cell
+                "mixed": dict(nref=3, n_sub=2, oversampling=2, spacedim=1),         # full and clipped patches, pairs sharing a line / nothing
+                "whole": dict(n_cells=3, n_sub=2, oversampling=3, spacedim=1)}      # l >= N: every patch is the domain
+U53 = 2.0 ** -53
+Q1_MASS = np.array([[4, 2, 2, 1], [2, 4, 1, 2], [2, 1, 4, 2], [1, 2, 2, 4]])   # nodes (0,0), (1,0), (0,1), (1,1)
+UNUSED = 0xffffffff
+
+
+def _slab_geometry(N, n, l, s, extents, centres):
+    """Per patch the extent (x0, y0, mx, my) in coarse cells, the centre cell, the node count (mx n + 1)(my n + 1) and
+    n_fine = s * nodes, the words of one of its s vectors ([node][component], nodes lexicographic, x fastest)."""
+    geom = _Case()
+    geom.N, geom.n, geom.l, geom.s = N, n, l, s
+    geom.NE, geom.NEp = N * n, N * n + 1
+    geom.ext = np.array(extents, dtype=np.int64).reshape(-1, 4)
+    geom.centres = np.array(centres, dtype=np.int64).reshape(-1, 2)
+    geom.NP = len(geom.ext)
+    assert geom.NP == N * N == len(geom.centres)
+    geom.nnode = (geom.ext[:, 2] * n + 1) * (geom.ext[:, 3] * n + 1)
+    geom.n_fine = s * geom.nnode
+    geom.span = 4 * l + 3
+    geom.cap = geom.span ** 2
+    geom.field = geom.NEp * geom.NEp * s
+    geom.pid = {(int(x), int(y)): p for p, (x, y) in enumerate(geom.centres)}
+    assert len(geom.pid) == geom.NP
+    return geom
+
+
+def _layout_geometry(kw, layout):
+    """_slab_geometry of one configuration; layout(p) has x0, y0, mx, my, cx, cy (g.patch_layout or so.patch_info)."""
+    N = kw["n_cells"] if kw.get("n_cells", 0) > 0 else 1 << kw["nref"]
+    infos = [layout(p) for p in range(N * N)]
+    return _slab_geometry(N, kw["n_sub"], kw["oversampling"], kw.get("spacedim", 1), [(i.x0, i.y0, i.mx, i.my) for i in infos],
+                          [(i.cx, i.cy) for i in infos])
+
+
+def _rim_mask(ny, nx):
+    rim = np.zeros((ny, nx), dtype=bool)
+    rim[0, :] = rim[-1, :] = rim[:, 0] = rim[:, -1] = True
+    return rim
+
+
+def _random_slab(geom, stride, seed, members=1, member_gap=0):
+    """(slab, vecs): vecs[k][p][d, iy, ix, c], every word uniform in [-1, 1] and none 0 on a rim; the values depend on
+    the seed alone, not on the stride.  slab: member k from k (NP stride + member_gap), patch p at + p stride, NaN in
+    every word between s n_fine(p) and the stride and between the members."""
+    s, n = geom.s, geom.n
+    assert stride >= s * geom.n_fine.max()
+    rng = np.random.default_rng(seed)
+    mstride = geom.NP * stride + member_gap
+    slab = np.full(members * mstride, NAN)
+    vecs = []
+    for k in range(members):
+        vecs.append([])
+        for p in range(geom.NP):
+            nx, ny = geom.ext[p, 2] * n + 1, geom.ext[p, 3] * n + 1
+            v = rng.uniform(-1.0, 1.0, (s, ny, nx, s))
+            assert (v[:, _rim_mask(ny, nx), :] != 0.0).all()
+            vecs[k].append(v)
+            off = k * mstride + p * stride
+            slab[off:off + v.size] = v.ravel()
+    assert np.isfinite(slab).sum() == members * s * geom.n_fine.sum()
+    return slab, vecs
+
+
+def _overlap(geom, p, q):
+    """The closed rectangles of p and q in global fine nodes: (xa, xb, ya, yb) inclusive, or None when they do not meet."""
+    n = geom.n
+    px0, py0, pmx, pmy = geom.ext[p]
+    qx0, qy0, qmx, qmy = geom.ext[q]
+    xa, xb = max(px0, qx0) * n, min(px0 + pmx, qx0 + qmx) * n
+    ya, yb = max(py0, qy0) * n, min(py0 + pmy, qy0 + qmy) * n
+    return None if xa > xb or ya > yb else (xa, xb, ya, yb)
+
+
+def _window(geom, v, p, rect):
+    """The nodes of rect of the vectors v[d, iy, ix, c] of patch p, in extended precision."""
+    xa, xb, ya, yb = rect
+    ox, oy = geom.ext[p, 0] * geom.n, geom.ext[p, 1] * geom.n
+    return v[:, ya - oy:yb - oy + 1, xa - ox:xb - ox + 1, :].astype(np.longdouble)
+
+
+def _ref_matrix(geom, Phi, Psi):
+    """A[(p,d),(q,e)] = sum over the shared nodes i and the components c of phi_{p,d}(i,c) psi_{q,e}(i,c).  Returns
+    (ref, S_abs, m, shared): [NP][NP][s][s] values, the same sums over absolute values, the number of products per entry
+    [NP][NP], and the pattern [NP][NP] (closed rectangles intersect)."""
+    NP, s = geom.NP, geom.s
+    ref = np.zeros((NP, NP, s, s), dtype=np.longdouble)
+    sabs = np.zeros_like(ref)
+    m = np.zeros((NP, NP), dtype=np.int64)
+    shared = np.zeros((NP, NP), dtype=bool)
+    for p in range(NP):
+        for q in range(NP):
+            rect = _overlap(geom, p, q)
+            if rect is None:
+                continue
+            shared[p, q] = True
+            a, b = _window(geom, Phi[p], p, rect), _window(geom, Psi[q], q, rect)
+            ref[p, q] = (a[:, None] * b[None, :]).sum(axis=(2, 3, 4))
+            sabs[p, q] = (np.abs(a)[:, None] * np.abs(b)[None, :]).sum(axis=(2, 3, 4))
+            m[p, q] = a[0].size
+    return ref, sabs, m, shared
+
+
+def _ref_mass(geom, Phi, rho=None):
+    """M[(p,d),(q,e)] = sum over the fine elements E of the intersection rectangle and the components c of
+    rho_E h^2 / 36  a^T Q1_MASS b,  a, b the corner values of phi_{p,d}(., c) and phi_{q,e}(., c) on E; rho [NE][NE], None = 1.
+    Returns (ref, S_abs, m, shared) as _ref_matrix, m = elements x components (the roundings inside one element form
+    are the + 16 of the bar); a pair that shares only a line has ref = S_abs = m = 0."""
+    NP, s, NE = geom.NP, geom.s, geom.NE
+    ref = np.zeros((NP, NP, s, s), dtype=np.longdouble)
+    sabs = np.zeros_like(ref)
+    m = np.zeros((NP, NP), dtype=np.int64)
+    shared = np.zeros((NP, NP), dtype=bool)
+    scale = (np.longdouble(1) / np.longdouble(NE)) ** 2 / np.longdouble(36)
+    r_all = np.ones((NE, NE), dtype=np.longdouble) if rho is None else np.asarray(rho).reshape(NE, NE).astype(np.longdouble)
+
+    def corners(v):
+        return [v[:, :-1, :-1], v[:, :-1, 1:], v[:, 1:, :-1], v[:, 1:, 1:]]
+
+    for p in range(NP):
+        for q in range(NP):
+            rect = _overlap(geom, p, q)
+            if rect is None:
+                continue
+            shared[p, q] = True
+            xa, xb, ya, yb = rect
+            if xa == xb or ya == yb:
+                continue
+            a, b = corners(_window(geom, Phi[p], p, rect)), corners(_window(geom, Phi[q], q, rect))
+            r = r_all[ya:yb, xa:xb][None, None, :, :, None]
+            for i in range(4):
+                mb = sum(int(Q1_MASS[i, j]) * b[j] for j in range(4))
+                mb_abs = sum(int(Q1_MASS[i, j]) * np.abs(b[j]) for j in range(4))
+                ref[p, q] += (a[i][:, None] * mb[None, :] * r).sum(axis=(2, 3, 4))
+                sabs[p, q] += (np.abs(a[i])[:, None] * mb_abs[None, :] * r).sum(axis=(2, 3, 4))
+            ref[p, q] *= scale
+            sabs[p, q] *= scale
+            m[p, q] = (xb - xa) * (yb - ya) * s
+    return ref, sabs, m, shared
+
+
+def _ref_rhs(geom, Phi, F):
+    """(C^T f)[p s + d] = sum over every node i of patch p and the components c of phi_{p,d}(i,c) f(i,c); F [NEp][NEp][s].
+    Returns (ref, S_abs, m), each [NP s]."""
+    NP, s, n = geom.NP, geom.s, geom.n
+    F = np.asarray(F).reshape(geom.NEp, geom.NEp, s).astype(np.longdouble)
+    ref = np.zeros(NP * s, dtype=np.longdouble)
+    sabs = np.zeros_like(ref)
+    m = np.zeros(NP * s, dtype=np.int64)
+    for p in range(NP):
+        x0, y0, mx, my = geom.ext[p]
+        f = F[y0 * n:(y0 + my) * n + 1, x0 * n:(x0 + mx) * n + 1, :]
+        v = Phi[p].astype(np.longdouble)
+        ref[p * s:(p + 1) * s] = (v * f[None]).sum(axis=(1, 2, 3))
+        sabs[p * s:(p + 1) * s] = (np.abs(v) * np.abs(f)[None]).sum(axis=(1, 2, 3))
+        m[p * s:(p + 1) * s] = f.size
+    return ref, sabs, m
+
+
+def _ref_reconstruct(geom, Phi, U):
+    """(C u)(i, c) = sum over every patch p that covers the node i and its vectors d of phi_{p,d}(i,c) u[p s + d].
+    Returns (ref, S_abs, m), each [NEp][NEp][s]."""
+    NP, s, n = geom.NP, geom.s, geom.n
+    U = np.asarray(U).reshape(NP, s).astype(np.longdouble)
+    ref = np.zeros((geom.NEp, geom.NEp, s), dtype=np.longdouble)
+    sabs = np.zeros_like(ref)
+    m = np.zeros((geom.NEp, geom.NEp, s), dtype=np.int64)
+    for p in range(NP):
+        x0, y0, mx, my = geom.ext[p]
+        win = (slice(y0 * n, (y0 + my) * n + 1), slice(x0 * n, (x0 + mx) * n + 1))
+        v = Phi[p].astype(np.longdouble)
+        for d in range(s):
+            ref[win] += v[d] * U[p, d]
+            sabs[win] += np.abs(v[d]) * np.abs(U[p, d])
+            m[win] += 1
+    return ref, sabs, m
+
+
+def _slab_bar(got, ref, sabs, m):
+    """The one bar of every value comparison: |got - ref| <= (m + 16) 2^-53 S_abs, the bound of a sum of m products in
+    any order (Higham, Accuracy and Stability, sections 3.1 and 4.2) plus the 16 roundings inside one term.  Returns
+    (ok, worst |got - ref| / bound); where the bound is 0 the value must be the reference exactly."""
+    err = np.abs(np.asarray(got).astype(np.longdouble) - ref)
+    bound = (np.asarray(m).astype(np.longdouble) + 16) * np.longdouble(U53) * sabs
+    ok = bool((err <= bound).all())
+    pos = bound > 0
+    return ok, float((err[pos] / bound[pos]).max()) if pos.any() else 0.0
+
+
+def _slot_columns(geom, shared):
+    """cols[p][j] of a block row from the pattern alone: slot j of row p is the patch whose centre cell lies at
+    (j % span, j / span) - span / 2 from p's (include/slod.h), UNUSED when there is none or the two share no node."""
+    cols = np.full((geom.NP, geom.cap), UNUSED, dtype=np.uint32)
+    for p in range(geom.NP):
+        cx, cy = geom.centres[p]
+        for j in range(geom.cap):
+            q = geom.pid.get((int(cx) + j % geom.span - geom.span // 2, int(cy) + j // geom.span - geom.span // 2))
+            if q is not None and shared[p, q]:
+                cols[p, j] = q
+    assert ((cols != UNUSED).sum(axis=1) == shared.sum(axis=1)).all()   # every coupled patch has a slot
+    return cols
+
+
+def _blocks_by_column(geom, values, cols):
+    """[NP][NP][s][s] copy of block rows [NP][cap][s][s]; unused slots are left out."""
+    s = geom.s
+    v = np.asarray(values).reshape(geom.NP, geom.cap, s, s)
+    out = np.zeros((geom.NP, geom.NP, s, s))
+    used = np.asarray(cols).reshape(geom.NP, geom.cap) != UNUSED
+    rows = np.repeat(np.arange(geom.NP), geom.cap).reshape(geom.NP, geom.cap)
+    out[rows[used], np.asarray(cols).reshape(geom.NP, geom.cap)[used].astype(np.int64)] = v[used]
+    return out

@@ -11,6 +11,9 @@ Cases (n rows, half bandwidth b = s (w N + w) + s - 1, w = 2 l + 1):
   c2geom    nref 5, n_sub 2, l 2, s 1   n = 1024, b = 165  no basis: a synthetic matrix on the pattern of slod_lod_pattern,
             symmetric off-diagonal entries uniform in [-1, 1], diagonal = absolute row sum + 1 (no decay across the band:
             a missing or misplaced term anywhere moves the solution by about 1e-3)
+  wide4     nref 2, n_sub 1, l 2, s 1   n = 16,   b = 25   synthetic; 2 l + 1 > N: the band is wider than the matrix
+            (bb = 2 > nb = 1, a single block row)
+  wide5     5 cells, n_sub 1, l 2, s 2  n = 50,   b = 61   synthetic, s x s blocks; bb = 4 = nb
 The first four carry three matrices each: sym(A_LOD), M_LOD and M + 0.01 A.
 
 Bars:
@@ -41,7 +44,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "dealii-slod_amd", "bin", "main_Diffusion")
 NAN = float("nan")
 U = 2.0 ** -53
-CASES = ("dense", "rowmajor", "s2", "morton16", "c2geom")
+CASES = ("dense", "rowmajor", "s2", "morton16", "c2geom", "wide4", "wide5")
 _cases = {}
 
 
@@ -73,17 +76,25 @@ def _order(c):
     return perm
 
 
-def _synthetic(so):
-    """c2geom: the handle alone, columns by slot from the pattern, values from a seeded default_rng."""
+SYNTHETIC = {"c2geom": dict(nref=5, n_sub=2, oversampling=2, spacedim=1),
+             "wide4": dict(nref=2, n_sub=1, oversampling=2, spacedim=1),
+             "wide5": dict(n_cells=5, n_sub=1, oversampling=2, spacedim=2)}
+
+
+def _synthetic(so, kw):
+    """The handle alone, columns by slot from the pattern, values from a seeded default_rng: a symmetric matrix of
+    s x s blocks on the pattern of slod_lod_pattern, off-diagonal entries uniform in [-1, 1], diagonal = absolute row
+    sum + 1."""
     import slod_amd
     torch, dev = _torch()
 
     class C:
         pass
     c = C()
-    c.g = g = slod_amd.Slod(nref=5, n_sub=2, oversampling=2, spacedim=1)
-    c.s, c.nrow = 1, g.num_patches
-    NP, cap, span = g.num_patches, g.lod_row_capacity(), 4 * 2 + 3
+    c.g = g = slod_amd.Slod(**kw)
+    c.s = s = kw["spacedim"]
+    c.nrow = g.num_patches * s
+    NP, cap, span = g.num_patches, g.lod_row_capacity(), 4 * kw["oversampling"] + 3
     centre = np.array([(g.patch_layout(p).cx, g.patch_layout(p).cy) for p in range(NP)])
     pid = {(int(x), int(y)): p for p, (x, y) in enumerate(centre)}
     cols = np.full((NP, cap), 0xffffffff, dtype=np.uint32)
@@ -95,17 +106,17 @@ def _synthetic(so):
                 cols[p, j] = q
         assert (cols[p] != 0xffffffff).sum() == len(coupled)
     rng = np.random.default_rng(20251019)
-    W = np.tril(rng.uniform(-1.0, 1.0, (NP, NP)), -1)
+    W = np.tril(rng.uniform(-1.0, 1.0, (c.nrow, c.nrow)), -1)
     mask = np.zeros((NP, NP), dtype=bool)
     rows = np.repeat(np.arange(NP), cap).reshape(NP, cap)
     used = cols != 0xffffffff
     mask[rows[used], cols[used].astype(np.int64)] = True
     assert np.array_equal(mask, mask.T)
-    A = (W + W.T) * mask
+    A = (W + W.T) * np.kron(mask, np.ones((s, s), dtype=bool))
     np.fill_diagonal(A, 0.0)
     np.fill_diagonal(A, np.abs(A).sum(axis=1) + 1.0)
-    vals = np.zeros((NP, cap))
-    vals[used] = A[rows[used], cols[used].astype(np.int64)]
+    vals = np.zeros((NP, cap, s, s))
+    vals[used] = A.reshape(NP, s, NP, s).transpose(0, 2, 1, 3)[rows[used], cols[used].astype(np.int64)]
     c.cols = torch.from_numpy(cols.view(np.int32).ravel()).to(dev)
     c.mats = [("synthetic", _dev(vals.ravel()), A)]
     assert np.array_equal(_dense(c, c.mats[0][1]), A)
@@ -115,8 +126,8 @@ def _synthetic(so):
 def _case(so, name):
     """Handle, columns, and the matrices of a case as (label, device values, dense copy); built once."""
     if name not in _cases:
-        if name == "c2geom":
-            c = _synthetic(so)
+        if name in SYNTHETIC:
+            c = _synthetic(so, SYNTHETIC[name])
         else:
             if name in ("dense", "rowmajor"):
                 c = _pencil(so, "s1" if name == "dense" else "rowmajor")
