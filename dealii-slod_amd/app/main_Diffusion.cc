@@ -36,6 +36,12 @@
 // line "member K heat step J: L2 distance = .., energy distance = .." per member and step with the distance to that
 // member's elliptic solution, then the L2 norms of the mean and of the standard deviation of the final states.  Without
 // --direct the two flags act independently, as before.
+// --ensemble K --wave STEPS DT --direct: after the lines above, the wave of every member from rest by the trapezoidal rule on
+// banded Cholesky factors (slod_lod_matrix_symmetrize_ensemble, one factor object of M and one of S,
+// slod_lod_newmark_accel_ensemble_direct, slod_lod_newmark_steps_ensemble_direct): the factor line of S (pivots over all
+// members), one line "member K wave step J: kinetic = .., potential = .., work = .." per member and step, the numbers of
+// the "wave step J" line of a --member K --wave STEPS DT --direct run, then the L2 norms of the mean and of the standard
+// deviation of the final states.  Without --direct the two flags act independently.
 // --member K: a run without --ensemble on the coefficient that is member K of an ensemble run (K fields are drawn and
 // dropped before the problem draws its own).
 // --perturb K: a local coefficient change after everything else.  K cells of the coefficient's 2^r x 2^r grid, picked by a
@@ -288,9 +294,10 @@ int main(int argc_all, char **argv_all)
                         problem.ensemble_rel_residuals()[k]);
           std::printf("SLOD ensemble of %d: L2 norm of the mean = %.12e, of the standard deviation = %.12e\n", n_members,
                       problem.norms_ensemble_mean().l2[0], problem.norms_ensemble_deviation().l2[0]);
+          if ((heat_steps > 0 || wave_steps > 0) && direct)
+            problem.assemble_mass_matrix_ensemble();
           if (heat_steps > 0 && direct)
             {
-              problem.assemble_mass_matrix_ensemble();
               problem.solve_heat_ensemble((unsigned int)heat_steps, heat_dt, 1.0);
               print_factor(problem.last_factor_info());
               for (int j = 0; j < heat_steps; ++j)
@@ -302,6 +309,22 @@ int main(int argc_all, char **argv_all)
               std::printf("SLOD heat ensemble of %d at T = %g: L2 norm of the mean = %.12e, of the standard deviation = %.12e\n",
                           n_members, heat_steps * heat_dt, problem.norms_heat_ensemble_mean().l2[0],
                           problem.norms_heat_ensemble_deviation().l2[0]);
+            }
+          if (wave_steps > 0 && direct)
+            {
+              problem.solve_wave_ensemble((unsigned int)wave_steps, wave_dt, 0.25, 0.5);
+              print_factor(problem.last_factor_info());
+              for (int k = 0; k < n_members; ++k)
+                for (int j = 1; j <= wave_steps; ++j)
+                  {
+                    const std::size_t at = (std::size_t)j * n_members + k;
+                    std::printf("member %d wave step %d: kinetic = %.12e, potential = %.12e, work = %.12e\n", k, j,
+                                problem.wave_ensemble_kinetic()[at], problem.wave_ensemble_potential()[at],
+                                problem.wave_ensemble_work()[at]);
+                  }
+              std::printf("SLOD wave ensemble of %d at T = %g: L2 norm of the mean = %.12e, of the standard deviation = %.12e\n",
+                          n_members, wave_steps * wave_dt, problem.norms_wave_ensemble_mean().l2[0],
+                          problem.norms_wave_ensemble_deviation().l2[0]);
             }
         }
       if (n_perturb > 0)

@@ -101,8 +101,10 @@ namespace
     if (e == hipSuccess)
       e = hipStreamSynchronize(st);
     const double rhs2 = hs.rhs2;
-    double       rr   = hs.rr;
-    // rr of the initial residual was accumulated by the init kernel; clear the per-iteration sums
+    // The init kernel added the same per-wave partials to rhs2 and to rr, but by two atomicAdds each, whose order over
+    // the waves is not fixed: the two sums can differ in the last bits.  The initial residual is the right-hand side, so
+    // it takes the one sum; clear the per-iteration sums
+    double rr = rhs2;
     if (e == hipSuccess)
       {
         hs.rr = 0.0;

@@ -648,6 +648,75 @@ namespace slod
   }
 
   template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_wave_ensemble(const unsigned int n_steps, const double dt, const double beta, const double gamma)
+  {
+    if (!d_ens_mass)
+      throw std::runtime_error("solve_wave_ensemble: assemble_mass_matrix_ensemble comes first");
+    const int          K = (int)par.n_members;
+    const std::size_t  ld = (std::size_t)K;
+    const unsigned int n_patches = (unsigned int)patches.size();
+    const std::size_t  NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+    const std::size_t  fine_size = (NE + 1) * (NE + 1) * spacedim, n_coarse = (std::size_t)n_patches * spacedim;
+    const int          cap = slod_lod_row_capacity(handle);
+    check(cap, "slod_lod_row_capacity");
+    const std::size_t n_words = (std::size_t)n_patches * cap * spacedim * spacedim;
+    if (!d_ens_sym)
+      d_ens_sym = device_alloc<double>(n_words * K);
+    if (!d_ens_shifted)
+      d_ens_shifted = device_alloc<double>(n_words * K);
+    double *d_state = device_alloc<double>(3 * n_coarse * K), *d_u = d_state, *d_v = d_u + n_coarse * K, *d_a = d_v + n_coarse * K;
+    double *d_fine = device_alloc<double>(fine_size * K), *d_mean = device_alloc<double>(fine_size), *d_var = device_alloc<double>(fine_size);
+    check(slod_lod_matrix_symmetrize_ensemble(handle, d_ens_values, ld, d_ens_cols, K, d_ens_sym, ld, nullptr),
+          "slod_lod_matrix_symmetrize_ensemble");
+    if (hipMemset(d_state, 0, 3 * n_coarse * K * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+      throw std::runtime_error("solve_wave_ensemble: clearing the initial state failed");
+    std::vector<double> b(n_coarse * K), u(n_coarse * K);
+    if (hipMemcpy(b.data(), d_ens_rhs, b.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      throw std::runtime_error("solve_wave_ensemble: download of the loads failed");
+    // the factors of M for the initial acceleration, then those of S = M + beta dt^2 A (no damping) for every step
+    slod_lod_factor *f_M = nullptr, *f_S = nullptr;
+    check(slod_lod_factor_create_ensemble(handle, d_ens_mass, ld, K, d_ens_cols, nullptr, &f_M), "slod_lod_factor_create_ensemble");
+    factors.push_back(f_M);
+    check(slod_lod_newmark_accel_ensemble_direct(handle, f_M, d_ens_sym, ld, d_ens_mass, ld, d_ens_cols, 0.0, 0.0, K, d_u, ld, d_v, ld,
+                                                 d_ens_rhs, ld, d_a, ld),
+          "slod_lod_newmark_accel_ensemble_direct");
+    check(slod_lod_matrix_combine_ensemble(handle, 1.0, d_ens_mass, ld, beta * dt * dt, d_ens_sym, ld, K, d_ens_shifted, ld, nullptr),
+          "slod_lod_matrix_combine_ensemble");
+    check(slod_lod_factor_create_ensemble(handle, d_ens_shifted, ld, K, d_ens_cols, nullptr, &f_S), "slod_lod_factor_create_ensemble");
+    factors.push_back(f_S);
+    check(slod_lod_factor_get_info(f_S, &lod_factor_info), "slod_lod_factor_get_info");
+    ens_wave_kinetic.assign((std::size_t)(n_steps + 1) * K, 0.0);
+    ens_wave_potential.assign((std::size_t)(n_steps + 1) * K, 0.0);
+    ens_wave_work.assign((std::size_t)(n_steps + 1) * K, 0.0);
+    std::vector<double> kinetic(2 * ld), potential(2 * ld);
+    for (unsigned int step = 0; step < n_steps; ++step)
+      {
+        check(slod_lod_newmark_steps_ensemble_direct(handle, f_S, d_ens_sym, ld, d_ens_mass, ld, d_ens_cols, dt, beta, gamma, 0.0, 0.0, 1,
+                                                     K, d_u, ld, d_v, ld, d_a, ld, d_ens_rhs, ld, 0, kinetic.data(), potential.data()),
+              "slod_lod_newmark_steps_ensemble_direct");
+        if (hipMemcpy(u.data(), d_u, u.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+          throw std::runtime_error("solve_wave_ensemble: download of the states failed");
+        for (int k = 0; k < K; ++k)
+          {
+            if (step == 0)
+              {
+                ens_wave_kinetic[k]   = kinetic[k];
+                ens_wave_potential[k] = potential[k];
+              }
+            ens_wave_kinetic[(std::size_t)(step + 1) * K + k]   = kinetic[ld + k];
+            ens_wave_potential[(std::size_t)(step + 1) * K + k] = potential[ld + k];
+            double work = 0.0;
+            for (std::size_t i = 0; i < n_coarse; ++i)
+              work += u[i * K + k] * b[i * K + k];
+            ens_wave_work[(std::size_t)(step + 1) * K + k] = work;
+          }
+      }
+    check(slod_lod_reconstruct_ensemble(handle, d_ens_basis, ens_stride, ens_member_stride, K, d_u, ld, d_fine, fine_size, nullptr),
+          "slod_lod_reconstruct_ensemble");
+    ensemble_moment_norms(d_fine, d_mean, d_var, ens_wave_mean_norms, ens_wave_dev_norms);
+  }
+
+  template <int dim, int spacedim>
   void LOD<dim, spacedim>::assemble_mass_matrix()
   {
     if (!d_lod_values)

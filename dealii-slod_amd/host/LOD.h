@@ -192,6 +192,20 @@ namespace slod
     const std::vector<slod_error_norms> &norms_LOD_ensemble() const { return ens_lod_norms; }
     const slod_error_norms              &norms_heat_ensemble_mean() const { return ens_heat_mean_norms; }
     const slod_error_norms              &norms_heat_ensemble_deviation() const { return ens_heat_dev_norms; }
+    // solve_wave(.., direct = true) for all members at once, after assemble_mass_matrix_ensemble(): the symmetrised
+    // stiffness of every member (slod_lod_matrix_symmetrize_ensemble), one factor object of M for the initial
+    // acceleration (slod_lod_newmark_accel_ensemble_direct) and one of S_k = M_k + beta dt^2 sym(A_k), then n_steps calls
+    // of slod_lod_newmark_steps_ensemble_direct with one step each (the calls compose bit for bit), from rest with the
+    // load of solve_ensemble(), undamped.  Member k's energies are those of solve_wave of a problem with member k's
+    // coefficient.  Then the final states on the fine grid and their moments as in solve_ensemble().
+    // last_factor_info() is that of S, the range over all members.
+    void solve_wave_ensemble(const unsigned int n_steps, const double dt, const double beta, const double gamma);
+    // [step * n_members + member], step = 0 .. n_steps, step 0 the state at rest: v^T M v / 2, u^T A u / 2 and u^T b
+    const std::vector<double> &wave_ensemble_kinetic() const { return ens_wave_kinetic; }
+    const std::vector<double> &wave_ensemble_potential() const { return ens_wave_potential; }
+    const std::vector<double> &wave_ensemble_work() const { return ens_wave_work; }
+    const slod_error_norms    &norms_wave_ensemble_mean() const { return ens_wave_mean_norms; }
+    const slod_error_norms    &norms_wave_ensemble_deviation() const { return ens_wave_dev_norms; }
     // After assemble_global_matrix(), when the coefficient of the problem class has changed in part of the domain (the
     // reference has no counterpart): re-samples it (slod_update_coefficient finds the patches that see a changed fine
     // element), rebuilds those patches in place on the device slab (slod_plan_create_dirty), recomputes the entries of
@@ -291,6 +305,10 @@ namespace slod
     uint32_t   *d_ens_cols = nullptr;
     std::vector<slod_error_norms> ens_heat_error, ens_lod_norms;
     slod_error_norms              ens_heat_mean_norms{}, ens_heat_dev_norms{};
+    // solve_wave_ensemble: the symmetrised stiffness of the members
+    double             *d_ens_sym = nullptr;
+    std::vector<double> ens_wave_kinetic, ens_wave_potential, ens_wave_work;
+    slod_error_norms    ens_wave_mean_norms{}, ens_wave_dev_norms{};
     // mean and standard deviation of n_members fine fields: slod_ensemble_moments, the square root on the host, the norms
     void ensemble_moment_norms(const double *d_fine, double *d_mean, double *d_var, slod_error_norms &mean, slod_error_norms &dev);
 

@@ -166,6 +166,12 @@ def load():
     lib.slod_lod_factor_solve_ensemble.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp]
     lib.slod_lod_theta_steps_ensemble_direct.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_double, C.c_double, C.c_int, C.c_int, vp,
                                                          C.c_size_t, vp, C.c_size_t, C.c_size_t]
+    lib.slod_lod_inner_ensemble.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, dp, vp]
+    lib.slod_lod_newmark_accel_ensemble_direct.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_double, C.c_double,
+                                                           C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]
+    lib.slod_lod_newmark_steps_ensemble_direct.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_double, C.c_double,
+                                                           C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.c_size_t,
+                                                           vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, dp, dp]
     lib.slod_update_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, C.c_int, C.c_size_t, C.c_int, vp]
     lib.slod_dirty_patches.argtypes = [vp, vp, u32p, C.c_size_t]
     lib.slod_plan_create_dirty.argtypes = [vp, C.c_uint32, vp, C.POINTER(vp)]
@@ -760,6 +766,42 @@ class Slod:
         self._check(self.lib.slod_lod_theta_steps_ensemble_direct(
             self.h, _factor_ptr(factor), d_stiffness, n_members if ld_m is None else ld_m, d_cols, dt, theta, n_steps, n_members,
             d_u, n_members if ld_u is None else ld_u, d_load, n_members if ld_load is None else ld_load, load_step_stride))
+
+    # ---- the wave equation on an ensemble: Newmark with a column, two matrices and a factor per member ----
+    def lod_inner_ensemble(self, d_values, d_cols, d_x, d_y, n_members, ld_m=None, ld_x=None, ld_y=None, stream=None):
+        """out[k] = x_k^T (A_k y_k) with member k's matrix; d_x may be d_y.  Returns an array [n_members]."""
+        out = np.zeros(max(n_members, 1))
+        self._check(self.lib.slod_lod_inner_ensemble(
+            self.h, d_values, n_members if ld_m is None else ld_m, d_cols, d_x, n_members if ld_x is None else ld_x, d_y,
+            n_members if ld_y is None else ld_y, n_members, _dp(out), stream))
+        return out[:n_members]
+
+    def lod_newmark_accel_ensemble_direct(self, factor, d_stiffness, d_mass, d_cols, n_members, d_u, d_v, d_a, ld_a_m=None,
+                                          ld_m_m=None, ld_u=None, ld_v=None, ld_a=None, d_load=None, ld_load=None,
+                                          damp_mass=0.0, damp_stiff=0.0):
+        """lod_newmark_accel_direct with a column, two matrices and a factor per member; the factor is that of M."""
+        self._check(self.lib.slod_lod_newmark_accel_ensemble_direct(
+            self.h, _factor_ptr(factor), d_stiffness, n_members if ld_a_m is None else ld_a_m, d_mass,
+            n_members if ld_m_m is None else ld_m_m, d_cols, damp_mass, damp_stiff, n_members, d_u,
+            n_members if ld_u is None else ld_u, d_v, n_members if ld_v is None else ld_v, d_load,
+            n_members if ld_load is None else ld_load, d_a, n_members if ld_a is None else ld_a))
+
+    def lod_newmark_steps_ensemble_direct(self, factor, d_stiffness, d_mass, d_cols, dt, n_steps, n_members, d_u, d_v, d_a,
+                                          beta=0.25, gamma=0.5, ld_a_m=None, ld_m_m=None, ld_u=None, ld_v=None, ld_a=None,
+                                          d_load=None, ld_load=None, load_step_stride=0, damp_mass=0.0, damp_stiff=0.0,
+                                          energies=True):
+        """lod_newmark_steps_direct with a column, two matrices and a factor per member; the factor is that of
+        lod_matrix_combine_ensemble(1 + gamma dt damp_mass, M, beta dt^2 + gamma dt damp_stiff, A).  Returns
+        (kinetic, potential) as arrays [n_steps + 1, n_members], or (None, None) with energies=False."""
+        shape = (max(n_steps, 0) + 1, max(n_members, 1))
+        kin, pot = (np.zeros(shape), np.zeros(shape)) if energies else (None, None)
+        self._check(self.lib.slod_lod_newmark_steps_ensemble_direct(
+            self.h, _factor_ptr(factor), d_stiffness, n_members if ld_a_m is None else ld_a_m, d_mass,
+            n_members if ld_m_m is None else ld_m_m, d_cols, dt, beta, gamma, damp_mass, damp_stiff, n_steps, n_members,
+            d_u, n_members if ld_u is None else ld_u, d_v, n_members if ld_v is None else ld_v, d_a,
+            n_members if ld_a is None else ld_a, d_load, n_members if ld_load is None else ld_load, load_step_stride,
+            _dp(kin) if energies else None, _dp(pot) if energies else None))
+        return kin, pot
 
     def fem_rhs(self, d_f_qp, d_fine_rhs, stream=None):
         """Fine FEM load vector (d_f_qp = None: f = 1)."""

@@ -575,9 +575,9 @@ int slod_ensemble_moments(slod_handle *h, const double *d_fields, size_t ld_fine
  * the words of slod_lod_matrix_symmetrize and slod_lod_matrix_combine, the block column and the two sweeps of the
  * factor) with the member on a grid axis; a single-problem call is the instance n_members = 1, ld = 1.  Every result
  * of member k has the bits of the single-problem call on member k's de-interleaved data.  The common argument checks are
- * those of the ensemble block above.  Not built: Newmark on an ensemble factor, a CG ensemble stepper, the ensemble
- * eigensolver, refactoring after slod_lod_matrix_update, members spread over ranks, several columns per member in the
- * stepper. */
+ * those of the ensemble block above.  Newmark on an ensemble factor is the block after this one.  Not built: a CG
+ * ensemble stepper, the ensemble eigensolver, refactoring after slod_lod_matrix_update, members spread over ranks,
+ * several columns per member in a stepper. */
 /* Block rows of M_LOD of all num_patches patches for every member: member k's values are those of slod_lod_mass_matrix
  * with rows 0 .. num_patches-1 on its slab, bit for bit.  d_cols is written once.  d_rho NULL: density 1; ld_rho = 0: one
  * density [NE][NE] shared by all members; else member k's density at d_rho + k * ld_rho.  SLOD_ERR_ARGUMENT also for a
@@ -633,6 +633,51 @@ int slod_lod_theta_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, c
                                          const uint32_t *d_cols, double dt, double theta, int n_steps, int n_members,
                                          double *d_u, size_t ld_u, const double *d_load, size_t ld_load,
                                          size_t load_step_stride);
+
+/* ---- the wave equation on a coefficient ensemble: Newmark on a factor per member -----------------
+ * The second-order time stepper for  M_k u_k'' + C_k u_k' + A_k u_k = b_k(t),  C_k = damp_mass M_k + damp_stiff A_k, with
+ * member k of an ensemble in column k: the recursions of slod_lod_newmark_accel_direct and slod_lod_newmark_steps_direct
+ * in which column k reads member k of the ensemble matrices d_stiffness (leading dimension ld_a_m) and d_mass (ld_m_m;
+ * the two may differ) and is solved on member k of the factor.  The product and energy kernels are those of the single
+ * calls with a matrix per column (the chain of slod_lod_apply_ensemble); predictor, corrector, the sums of the energies
+ * and the sweeps of the factor are the same launches.  Column k of every result has the bits of the single-problem call
+ * with n_rhs = 1 on member k's de-interleaved matrices, single factor, state and loads; nothing depends on n_members, an
+ * ld, the member's position or the other members; entries k >= n_members inside an ld are never read or written.
+ * Argument checks come before any device work (SLOD_ERR_ARGUMENT, the call's name in slod_last_error): what the single
+ * call refuses, and n_members < 1 or > 65535, a matrix or vector ld below n_members (ld_load only with a load), a NULL
+ * factor, the factor of another handle or row count, a factor whose member count is not n_members (checked last).
+ * slod_lod_newmark_*_direct on a factor of several members stays refused.  Not built: these loops on CG, several columns
+ * per member. */
+/* out[k] = x_k^T (A_k y_k): slod_lod_inner_multi with member k's matrix, the same bits (the fma chain over the slots,
+ * the product with x rounded on its own, 16 rows into a partial, the partials in ascending group order).  d_x == d_y
+ * gives the quadratic form.  A member sub-range is d_values + first member with the vectors' base moved alike.
+ * Synchronises hip_stream. */
+int slod_lod_inner_ensemble(slod_handle *h, const double *d_values, size_t ld_m, const uint32_t *d_cols, const double *d_x,
+                            size_t ld_x, const double *d_y, size_t ld_y, int n_members,
+                            double *out /* HOST [n_members] */, void *hip_stream);
+/* M_k a_k = b^0_k - A_k (u_k + damp_stiff v_k) - damp_mass M_k v_k on member k of f_M, which factors the ensemble matrix
+ * d_mass.  d_load NULL: b^0 = 0.  With damp_mass = 0 the mass product is skipped and d_mass is not read.  u and v are read
+ * only.  Runs on the handle's stream; synchronises. */
+int slod_lod_newmark_accel_ensemble_direct(slod_handle *h, slod_lod_factor *f_M, const double *d_stiffness, size_t ld_a_m,
+                                           const double *d_mass, size_t ld_m_m, const uint32_t *d_cols, double damp_mass,
+                                           double damp_stiff, int n_members, const double *d_u, size_t ld_u,
+                                           const double *d_v, size_t ld_v, const double *d_load /* b^0, NULL = 0 */,
+                                           size_t ld_load, double *d_a, size_t ld_a);
+/* The loop of slod_lod_newmark_steps_direct, one column per member, on member k of f_S, which factors
+ *   slod_lod_matrix_combine_ensemble(1 + gamma dt damp_mass, M, beta dt^2 + gamma dt damp_stiff, A)
+ * with A the symmetrised ensemble stiffness; that the factor belongs to these coefficients is not checked.  Loads as in
+ * slod_lod_newmark_steps, column k = member k.  kinetic / potential: entry [step * n_members + k], both or neither; with
+ * both NULL and damp_mass = 0 d_mass is not read.  The loop is queued on the handle's stream and waited for once, the
+ * energies stay on the device and are copied once at the end; device workspace (2 vectors of n_members columns, the
+ * partials and the energies) is allocated once per call.  n_steps = 2 equals two calls with n_steps = 1 carrying u, v, a
+ * over. */
+int slod_lod_newmark_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, const double *d_stiffness, size_t ld_a_m,
+                                           const double *d_mass, size_t ld_m_m, const uint32_t *d_cols, double dt,
+                                           double beta, double gamma, double damp_mass, double damp_stiff, int n_steps,
+                                           int n_members, double *d_u, size_t ld_u, double *d_v, size_t ld_v, double *d_a,
+                                           size_t ld_a, const double *d_load, size_t ld_load, size_t load_step_stride,
+                                           double *kinetic   /* HOST [(n_steps + 1) * n_members], may be NULL */,
+                                           double *potential /* HOST [(n_steps + 1) * n_members], may be NULL */);
 
 /* ---- refresh after a local coefficient change ----------------------------------------------
  * Every entry point above takes the coefficient as fixed for the life of a basis (the reference does too: one
