@@ -1,6 +1,6 @@
 // Counterpart of reference app/main_Diffusion.cc for the basis-construction path:
 //   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare] [--coarse] [--loads K]
-//                  [--heat STEPS DT] [--eigs K] [--wave STEPS DT] [--direct] [--ensemble K] [--perturb K]
+//                  [--heat STEPS DT] [--eigs K] [--shift SIGMA] [--wave STEPS DT] [--direct] [--ensemble K] [--perturb K]
 //                  [--member K]
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
 // file name it dumps, per patch, phi and psi in patch-lexicographic order (parity tests).
@@ -18,6 +18,13 @@
 // --eigs K: the K lowest eigenpairs of  A_LOD u = lambda M_LOD u  (A_LOD symmetrised, slod_lod_eigs with its defaults): one
 // line per pair with its eigenvalue and residual, the outer and inner iteration counts, and the fine-grid L2 norm of
 // every reconstructed eigenfunction.
+// --eigs K --direct [--shift SIGMA]: the same pairs with the inner solve on the banded Cholesky factor of
+// S = sym(A_LOD) - SIGMA M_LOD (slod_lod_eigs_direct; SIGMA below the lowest eigenvalue, default 0): the eigenvalue lines,
+// "eigensolver: outer iterations = N, direct", the factor line in place of the inner iteration counts, the norms.
+// --ensemble K --eigs N --direct: after the lines of --ensemble, the N lowest pairs of every member on one factor object
+// (slod_lod_eigs_ensemble_direct): the factor line (pivots over all members), per member "member K eigenvalue J = ..,
+// residual = .." and "member K eigensolver: outer iterations = .., direct", the numbers of a --member K --eigs N --direct
+// run, then per eigenvalue "eigenvalue J over the ensemble of K: mean = .., standard deviation = ..".
 // --wave STEPS DT: the wave equation  M u'' + A u = C^T f  (f = 1, constant in time, A_LOD symmetrised) from rest by STEPS
 // steps of the trapezoidal rule (Newmark gamma = 1/2, beta = 1/4, slod_lod_newmark_steps): one line per step with its
 // iterations, relative residual, kinetic and potential energy and the work u^T b (kinetic + potential = work from rest
@@ -111,7 +118,7 @@ int main(int argc_all, char **argv_all)
   // --compare and --coarse are taken out wherever they stand; the positional arguments keep their meaning
   bool               compare = false, coarse = false, direct = false;
   int                n_loads = 0, heat_steps = 0, n_eigs = 0, wave_steps = 0, n_members = 0, n_perturb = 0, member = 0;
-  double             heat_dt = 0.0, wave_dt = 0.0;
+  double             heat_dt = 0.0, wave_dt = 0.0, shift = 0.0;
   std::vector<char *> args;
   for (int i = 0; i < argc_all; ++i)
     if (i > 0 && !std::strcmp(argv_all[i], "--compare"))
@@ -129,6 +136,8 @@ int main(int argc_all, char **argv_all)
       }
     else if (i > 0 && !std::strcmp(argv_all[i], "--eigs") && i + 1 < argc_all)
       n_eigs = std::atoi(argv_all[++i]);
+    else if (i > 0 && !std::strcmp(argv_all[i], "--shift") && i + 1 < argc_all)
+      shift = std::atof(argv_all[++i]);
     else if (i > 0 && !std::strcmp(argv_all[i], "--wave") && i + 2 < argc_all)
       {
         wave_steps = std::atoi(argv_all[++i]);
@@ -253,13 +262,21 @@ int main(int argc_all, char **argv_all)
             problem.assemble_global_matrix();
           if (heat_steps <= 0)
             problem.assemble_mass_matrix();
-          problem.solve_eigenproblem((unsigned int)n_eigs);
+          problem.solve_eigenproblem((unsigned int)n_eigs, direct, shift);
           for (int k = 0; k < n_eigs; ++k)
             std::printf("eigenvalue %d = %.12e, residual = %.3e\n", k + 1, problem.eigenvalues()[k], problem.eigen_residuals()[k]);
-          std::printf("eigensolver: outer iterations = %d, inner iterations =", (int)problem.eigen_inner_iterations().size());
-          for (const int it : problem.eigen_inner_iterations())
-            std::printf(" %d", it);
-          std::printf("\n");
+          if (direct)
+            {
+              std::printf("eigensolver: outer iterations = %d, direct\n", problem.eigen_outer_iterations());
+              print_factor(problem.last_factor_info());
+            }
+          else
+            {
+              std::printf("eigensolver: outer iterations = %d, inner iterations =", (int)problem.eigen_inner_iterations().size());
+              for (const int it : problem.eigen_inner_iterations())
+                std::printf(" %d", it);
+              std::printf("\n");
+            }
           for (int k = 0; k < n_eigs; ++k)
             std::printf("eigenfunction %d: L2 norm = %.12e\n", k + 1, problem.eigenfunction_norms()[k].l2[0]);
         }
@@ -294,7 +311,7 @@ int main(int argc_all, char **argv_all)
                         problem.ensemble_rel_residuals()[k]);
           std::printf("SLOD ensemble of %d: L2 norm of the mean = %.12e, of the standard deviation = %.12e\n", n_members,
                       problem.norms_ensemble_mean().l2[0], problem.norms_ensemble_deviation().l2[0]);
-          if ((heat_steps > 0 || wave_steps > 0) && direct)
+          if ((heat_steps > 0 || wave_steps > 0 || n_eigs > 0) && direct)
             problem.assemble_mass_matrix_ensemble();
           if (heat_steps > 0 && direct)
             {
@@ -325,6 +342,35 @@ int main(int argc_all, char **argv_all)
               std::printf("SLOD wave ensemble of %d at T = %g: L2 norm of the mean = %.12e, of the standard deviation = %.12e\n",
                           n_members, wave_steps * wave_dt, problem.norms_wave_ensemble_mean().l2[0],
                           problem.norms_wave_ensemble_deviation().l2[0]);
+            }
+        }
+      if (n_members > 0 && n_eigs > 0 && direct)
+        {
+          problem.solve_eigenproblem_ensemble((unsigned int)n_eigs, shift);
+          print_factor(problem.last_factor_info());
+          const int m = problem.eigen_ensemble_block();
+          for (int k = 0; k < n_members; ++k)
+            {
+              for (int j = 0; j < n_eigs; ++j)
+                std::printf("member %d eigenvalue %d = %.12e, residual = %.3e\n", k, j + 1,
+                            problem.eigenvalues_ensemble()[(std::size_t)k * m + j], problem.eigen_residuals_ensemble()[(std::size_t)k * m + j]);
+              std::printf("member %d eigensolver: outer iterations = %d, direct\n", k, problem.eigen_outer_iterations_ensemble()[k]);
+            }
+          for (int j = 0; j < n_eigs; ++j)
+            {
+              // sample mean and unbiased standard deviation over the members, summed in ascending member order
+              double mean = 0.0, var = 0.0;
+              for (int k = 0; k < n_members; ++k)
+                mean += problem.eigenvalues_ensemble()[(std::size_t)k * m + j];
+              mean /= n_members;
+              for (int k = 0; k < n_members; ++k)
+                {
+                  const double d = problem.eigenvalues_ensemble()[(std::size_t)k * m + j] - mean;
+                  var += d * d;
+                }
+              var = n_members > 1 ? var / (n_members - 1) : 0.0;
+              std::printf("eigenvalue %d over the ensemble of %d: mean = %.12e, standard deviation = %.12e\n", j + 1, n_members, mean,
+                          std::sqrt(var));
             }
         }
       if (n_perturb > 0)

@@ -9,6 +9,12 @@
 //   k_eig_ritz                   Ga Q = Gm Q Theta, Q^T Gm Q = I in one workgroup out of LDS
 //   k_eig_rotate                 X = Z Q; AX = W Q and MX = V Q stay in registers for the residual partials
 // Every reduction has a fixed order (no atomics): the same inputs give the same bits.
+//   slod_lod_eigs_direct / slod_lod_eigs_ensemble_direct   the same outer iteration with  S Z = Y  on a banded Cholesky
+//                                factor of S = A - sigma M (slod_lod_factor.hip) in place of the CG, for one pencil or for
+//                                the K pencils of a coefficient ensemble
+// The kernels of this file carry the member on blockIdx.y: member k works on columns k m .. k m + m - 1 of the block
+// vectors and on its own partials, G, Q, theta, residuals, status and done word.  A single pencil is the ensemble of one
+// member.  k_eig_apply is the product of a member's matrix with its m columns.
 #include "slod_lod_system.hip.h"
 #include "slod_lod_tile.hip.h"
 
@@ -47,6 +53,7 @@ namespace
     const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (w >= (size_t)NP * s * m)
       return;
+    x += (size_t)blockIdx.y * m; // the member's columns
     const size_t i = w / m;
     const int    j = (int)(w - i * m), e = (int)(i % s), t = j / s, d = j - t * s;
     int          cx, cy;
@@ -64,10 +71,12 @@ namespace
   constexpr int GR_ROWS = 32, GR_BLOCK = 256, GR_MAX_BLOCKS = 512;
 
   __global__ __launch_bounds__(GR_BLOCK) void k_eig_gram(int nrow, int m, int nslab, const double *__restrict__ Z,
-                                                        const double *__restrict__ W, const double *__restrict__ V,
+                                                        const double *__restrict__ W, const double *__restrict__ V, size_t ld,
                                                         double *__restrict__ partial)
   {
     __shared__ double sz[GR_ROWS][EG_COLS], sw[GR_ROWS][EG_COLS], sv[GR_ROWS][EG_COLS];
+    Z += (size_t)blockIdx.y * m, W += (size_t)blockIdx.y * m, V += (size_t)blockIdx.y * m;
+    partial += (size_t)blockIdx.y * nslab * 2 * m * m;
     const int i0 = 4 * (threadIdx.x >> 4), j0 = 4 * (threadIdx.x & 15), m4 = (m + 3) & ~3;
     for (int g = blockIdx.x; g < nslab; g += gridDim.x)
       {
@@ -76,7 +85,7 @@ namespace
           {
             const int    lr = idx / m4, c = idx - lr * m4;
             const bool   in = lr < nr && c < m; // the columns m .. m4 pad the last tile with zeros
-            const size_t at = (size_t)(r0 + lr) * m + c;
+            const size_t at = (size_t)(r0 + lr) * ld + c;
             sz[lr][c]       = in ? Z[at] : 0.0;
             sw[lr][c]       = in ? W[at] : 0.0;
             sv[lr][c]       = in ? V[at] : 0.0;
@@ -131,6 +140,7 @@ namespace
     const int idx = blockIdx.x * 256 + threadIdx.x, mm = m * m;
     if (idx >= 2 * mm)
       return;
+    partial += (size_t)blockIdx.y * nslab * 2 * mm, G += (size_t)blockIdx.y * 2 * mm;
     const int which = idx / mm, ij = idx - which * mm, i = ij / m, j = ij - i * m;
     double    a = 0.0, b = 0.0;
     for (int g = 0; g < nslab; ++g)
@@ -157,12 +167,16 @@ namespace
   constexpr int RZ_LD = EG_COLS + 1, RZ_BLOCK = 256, RZ_SWEEPS = 30;
 
   __global__ __launch_bounds__(RZ_BLOCK) void k_eig_ritz(int m, const double *__restrict__ G, double *__restrict__ Q,
-                                                        double *__restrict__ theta, int *__restrict__ status)
+                                                        double *__restrict__ theta, int *__restrict__ status,
+                                                        const int *__restrict__ done)
   {
     __shared__ double A[EG_COLS * RZ_LD], L[EG_COLS * RZ_LD], U[EG_COLS * RZ_LD];
     __shared__ double s_c[EG_COLS / 2], s_s[EG_COLS / 2], s_d[EG_COLS], s_off[EG_COLS], s_fro[EG_COLS];
     __shared__ int    s_p[EG_COLS / 2], s_q[EG_COLS / 2], s_perm[EG_COLS], s_stop;
     const int tid = threadIdx.x, mm = m * m;
+    if (done[blockIdx.y]) // a member that has stopped keeps its last Q and theta
+      return;
+    G += (size_t)blockIdx.y * 2 * mm, Q += (size_t)blockIdx.y * mm, theta += (size_t)blockIdx.y * m, status += blockIdx.y;
     for (int idx = tid; idx < mm; idx += RZ_BLOCK)
       {
         const int i = idx / m, j = idx - i * m;
@@ -178,9 +192,15 @@ namespace
           {
             const double piv = L[k * RZ_LD + k], orig = G[mm + k * m + k];
             const bool   ok = piv > 0.0 && piv > (4 * m * EG_EPS) * orig;
-            s_stop          = ok ? 0 : k + 1;
+            // (one store per branch: with `s_stop = ok ? 0 : k + 1` ahead of the branch, hipcc of ROCm 7 selected the value on
+            // SCC, which the vector compare of the threshold does not set, and a positive pivot below the threshold went on)
             if (ok)
-              L[k * RZ_LD + k] = sqrt(piv);
+              {
+                L[k * RZ_LD + k] = sqrt(piv);
+                s_stop           = 0;
+              }
+            else
+              s_stop = k + 1;
           }
         __syncthreads();
         if (s_stop)
@@ -360,14 +380,18 @@ namespace
   __global__ __launch_bounds__(RT_BLOCK) void k_eig_rotate(int nrow, int m, int nslab, const double *__restrict__ Z,
                                                           const double *__restrict__ W, const double *__restrict__ V,
                                                           const double *__restrict__ Q, const double *__restrict__ theta,
-                                                          const int *__restrict__ status, double *__restrict__ x, size_t ld_x,
-                                                          double *__restrict__ p_rr, double *__restrict__ p_mm)
+                                                          const int *__restrict__ status, const int *__restrict__ done, size_t ld,
+                                                          double *__restrict__ x, size_t ld_x, double *__restrict__ p_rr,
+                                                          double *__restrict__ p_mm)
   {
     __shared__ double sq[EG_COLS][EG_COLS];
     __shared__ double sz[RT_ROWS][EG_COLS], sw[RT_ROWS][EG_COLS], sv[RT_ROWS][EG_COLS];
     __shared__ double b_rr[RT_ROWS][EG_COLS], b_mm[RT_ROWS][EG_COLS];
-    if (*status != 0)
+    if (done[blockIdx.y] || status[blockIdx.y] != 0)
       return;
+    Z += (size_t)blockIdx.y * m, W += (size_t)blockIdx.y * m, V += (size_t)blockIdx.y * m, x += (size_t)blockIdx.y * m;
+    Q += (size_t)blockIdx.y * m * m, theta += (size_t)blockIdx.y * m;
+    p_rr += (size_t)blockIdx.y * nslab * m, p_mm += (size_t)blockIdx.y * nslab * m;
     for (int idx = threadIdx.x; idx < m * m; idx += RT_BLOCK)
       sq[idx / m][idx % m] = Q[idx];
     for (int g = blockIdx.x; g < nslab; g += gridDim.x)
@@ -375,7 +399,7 @@ namespace
         for (int idx = threadIdx.x; idx < RT_ROWS * m; idx += RT_BLOCK)
           {
             const int    lr = idx / m, c = idx - lr * m, i = g * RT_ROWS + lr;
-            const size_t at = (size_t)i * m + c;
+            const size_t at = (size_t)i * ld + c;
             sz[lr][c]       = i < nrow ? Z[at] : 0.0;
             sw[lr][c]       = i < nrow ? W[at] : 0.0;
             sv[lr][c]       = i < nrow ? V[at] : 0.0;
@@ -413,15 +437,228 @@ namespace
       }
   }
 
-  // res_j = ||AX_j - theta_j MX_j|| / (|theta_j| ||MX_j||), one thread per column
-  __global__ void k_eig_residual(int m, int nslab, const double *__restrict__ p_rr, const double *__restrict__ p_mm,
-                                 const double *__restrict__ theta, const int *__restrict__ status, double *__restrict__ res)
+  // res_j = ||AX_j - theta_j MX_j|| / (|theta_j| ||MX_j||), one thread per column.  The member stops (done = 1: its Ritz,
+  // rotate and residual kernels return at entry from then on) when res_j <= tol for all j < n_eig, or when its Ritz step
+  // failed; its X, theta and residuals stay those of this iteration.
+  __global__ __launch_bounds__(EG_COLS) void k_eig_residual(int m, int n_eig, int nslab, double tol, const double *__restrict__ p_rr,
+                                                          const double *__restrict__ p_mm, const double *__restrict__ theta,
+                                                          const int *__restrict__ status, double *__restrict__ res,
+                                                          int *__restrict__ done)
   {
-    const int j = threadIdx.x;
-    if (j >= m || *status != 0)
+    __shared__ int s_open;
+    const int      j = threadIdx.x, k = blockIdx.y;
+    if (done[k])
       return;
-    const double rr = slod_lod_ordered_sum(p_rr, nslab, m, j), mm = slod_lod_ordered_sum(p_mm, nslab, m, j);
-    res[j]          = sqrt(rr) / (fabs(theta[j]) * sqrt(mm));
+    if (status[k] != 0)
+      {
+        if (j == 0)
+          done[k] = 1;
+        return;
+      }
+    p_rr += (size_t)k * nslab * m, p_mm += (size_t)k * nslab * m, theta += (size_t)k * m, res += (size_t)k * m;
+    if (j == 0)
+      s_open = 0;
+    __syncthreads();
+    if (j < m)
+      {
+        const double rr = slod_lod_ordered_sum(p_rr, nslab, m, j), mm = slod_lod_ordered_sum(p_mm, nslab, m, j);
+        const double r  = sqrt(rr) / (fabs(theta[j]) * sqrt(mm));
+        res[j]          = r;
+        if (j < n_eig && !(r <= tol))
+          s_open = 1;
+      }
+    __syncthreads();
+    if (j == 0 && !s_open)
+      done[k] = 1;
+  }
+
+  // ---------------------------------------------------------------------------------
+  // Y_k = A_k X_k for the m columns of member k = blockIdx.y: the tiling of k_lod_apply (slod_lod_time.hip) with the m
+  // columns on lanes, and its fma chain (slod_lod_row_product<false>, slod_lod_tile.hip.h: slots ascending, an unused slot
+  // reads the row's own patch and adds nothing, no branch) on the words of member k of an ensemble matrix, ld_m apart:
+  // the lanes of a row share one word, and a column has the bits slod_lod_apply_multi gives on the de-interleaved matrix.
+  // ---------------------------------------------------------------------------------
+  constexpr int AP_MAX_BLOCKS = 1024; // blocks per member, as k_lod_apply per chunk
+
+  __global__ __launch_bounds__(LOD_BLOCK) void k_eig_apply(int nrow, int s, int cap, int NP, int m, int ngroup,
+                                                         const double *__restrict__ values, size_t ld_m,
+                                                         const uint32_t *__restrict__ cols, const double *__restrict__ x, size_t ld_x,
+                                                         double *__restrict__ y, size_t ld_y)
+  {
+    values += blockIdx.y, x += (size_t)blockIdx.y * m, y += (size_t)blockIdx.y * m;
+    for (int g = blockIdx.x; g < ngroup; g += gridDim.x)
+      for (int idx = threadIdx.x; idx < LOD_ROWS * m; idx += LOD_BLOCK)
+        {
+          const int lr = idx / m, col = idx - lr * m, i = g * LOD_ROWS + lr;
+          if (i >= nrow)
+            continue;
+          const int    p = i / s, d = i - p * s;
+          const size_t slot0 = (size_t)p * cap;
+          double       acc = 0.0;
+          for (int j = 0; j < cap; ++j)
+            {
+              const uint32_t q = cols[slot0 + j];
+              const bool     used = q < (uint32_t)NP;
+              const size_t   qs = (size_t)(used ? q : (uint32_t)p) * s;
+              const double  *a = values + ((slot0 + j) * s * s + d * s) * ld_m;
+              for (int e = 0; e < s; ++e)
+                {
+                  const double t = fma(a[e * ld_m], x[(qs + e) * ld_x + col], acc);
+                  acc            = used ? t : acc;
+                }
+            }
+          y[(size_t)i * ld_y + col] = acc;
+        }
+  }
+
+  // the modes of the start block of m columns: the pairs (a, b) of {1..N}^2 in ascending a^2 + b^2, ties by ascending a
+  EigModes eig_sine_modes(const slod_handle *h, int m)
+  {
+    const int                        s = h->cfg.spacedim, side = std::min(h->N, EG_COLS), n_modes = (m + s - 1) / s;
+    std::vector<std::pair<int, int>> ab;
+    for (int a = 1; a <= side; ++a)
+      for (int b = 1; b <= side; ++b)
+        ab.emplace_back(a, b);
+    std::sort(ab.begin(), ab.end(), [](const std::pair<int, int> &u, const std::pair<int, int> &v) {
+      const int nu = u.first * u.first + u.second * u.second, nv = v.first * v.first + v.second * v.second;
+      return nu != nv ? nu < nv : u.first < v.first;
+    });
+    EigModes md{};
+    for (int t = 0; t < n_modes; ++t)
+      {
+        md.a[t] = (unsigned char)ab[t].first;
+        md.b[t] = (unsigned char)ab[t].second;
+      }
+    return md;
+  }
+
+  // The body of slod_lod_eigs_ensemble_direct; slod_lod_eigs_direct is the call with n_members = 1 and ld = 1.  Member k
+  // works on columns k m .. k m + m - 1 of d_x and of the workspace vectors.  Arguments are checked here, the factor last.
+  int eigs_direct(slod_handle *h, const char *who, bool ensemble, slod_lod_factor *f_S, const double *d_stiffness, size_t ld_a_m,
+                  const double *d_mass, size_t ld_m_m, const uint32_t *d_cols, int n_members, int n_eig, int n_block, int start,
+                  double *d_x, size_t ld_x, double tol, int max_outer, double *eigenvalues, double *residuals, int *member_status)
+  {
+    const std::string name(who);
+    if (!h || !d_stiffness || !d_mass || !d_cols || !d_x || !eigenvalues || !residuals)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, name + ": NULL handle, matrix, d_cols, d_x, eigenvalues or residuals");
+    const int s = h->cfg.spacedim, nrow = h->NP * s, m = n_block, K = n_members;
+    if (n_eig < 1 || n_block < n_eig)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, name + ": n_eig < 1 or n_block < n_eig");
+    if (n_block > EG_COLS || n_block > nrow)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, name + ": n_block above 64 or above the number of rows");
+    if (start != 0 && start != 1)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, name + ": start is neither 0 nor 1");
+    if (!(tol > 0.0))
+      return slod_fail(h, SLOD_ERR_ARGUMENT, name + ": tol is not positive");
+    if (max_outer < 1)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, name + ": max_outer < 1");
+    if (K < 1 || K > 65535)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, name + ": n_members < 1 or > 65535");
+    if (const int rc = slod_check_ld(h, who, "n_members", K, {ld_a_m, ld_m_m}))
+      return rc;
+    if (ld_x < (size_t)K * m)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, name + (ensemble ? ": leading dimension below n_members * n_block" : ": leading dimension below n_block"));
+    if (!member_status)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, name + ": NULL member_status");
+    if (const int rc = slod_lod_factor_check(h, who, f_S, K)) // last: it reads the factor
+      return rc;
+    hipStream_t st;
+    if (const int rc = slod_enter(h, nullptr, &st))
+      return rc;
+    const LodShape w = lod_shape(h, m); // its groups are the slabs of k_eig_rotate and of k_eig_apply
+    const int      n_gslab = (nrow + GR_ROWS - 1) / GR_ROWS, n_rslab = w.ngroup;
+    const size_t   ldw = (size_t)K * m, nvec = (size_t)nrow * ldw, mm = (size_t)m * m, nint = ((size_t)K + 1) / 2;
+    // one allocation for the whole loop: Y, Z, W, V of K m columns, per member the slab partials, Ga | Gm and Q, then
+    // theta | residuals | status | done of all members (consecutive: the host reads them in one copy)
+    double            *Y, *Z, *W, *V, *partial, *G, *Q, *p_rr, *p_mm, *theta, *res;
+    int               *status, *d_done;
+    SlodDevBuf<double> work;
+    SlodCarver         count, hand;
+    auto               carve = [&](SlodCarver &c) {
+      Y = c.take(nvec), Z = c.take(nvec), W = c.take(nvec), V = c.take(nvec);
+      partial = c.take(K * 2 * mm * n_gslab), G = c.take(K * 2 * mm), Q = c.take(K * mm);
+      p_rr = c.take(ldw * n_rslab), p_mm = c.take(ldw * n_rslab);
+      theta = c.take(ldw), res = c.take(ldw), status = (int *)c.take(nint), d_done = (int *)c.take(nint);
+    };
+    carve(count);
+    hipError_t e = work.alloc(count.used);
+    hand.base    = work.get();
+    if (e == hipSuccess)
+      {
+        carve(hand);
+        e = hipMemsetAsync(theta, 0, (2 * ldw + 2 * nint) * sizeof(double), st);
+      }
+    const size_t        nread = 2 * ldw + 2 * nint;
+    std::vector<double> host(nread);
+    std::vector<int>    ran((size_t)K, 0), failed_column((size_t)K, 0); // outer iterations of a stopped member, 0 = still open
+    int                 outer = 0, open = K;
+    if (e == hipSuccess)
+      {
+        if (start == 0)
+          {
+            hipLaunchKernelGGL(k_eig_start, dim3((unsigned)(((size_t)nrow * m + 255) / 256), (unsigned)K), dim3(256), 0, st,
+                               slod_grid_of(h), h->NP, s, m, eig_sine_modes(h, m), d_x, ld_x);
+            e = hipGetLastError();
+          }
+        const dim3 apply_grid((unsigned)std::min(w.ngroup, AP_MAX_BLOCKS), (unsigned)K);
+        auto       apply = [&](const double *values, size_t ld_m, const double *x, size_t ldx, double *y) {
+          hipLaunchKernelGGL(k_eig_apply, apply_grid, dim3(LOD_BLOCK), 0, st, nrow, s, w.cap, w.NP, m, w.ngroup, values, ld_m, d_cols, x,
+                             ldx, y, ldw);
+        };
+        while (e == hipSuccess && open > 0 && outer < max_outer)
+          {
+            apply(d_mass, ld_m_m, d_x, ld_x, Y);
+            slod_lod_factor_solve_launch(f_S, st, Y, ldw, m, Z, ldw, 0, K);
+            apply(d_stiffness, ld_a_m, Z, ldw, W);
+            apply(d_mass, ld_m_m, Z, ldw, V);
+            hipLaunchKernelGGL(k_eig_gram, dim3((unsigned)std::min(n_gslab, GR_MAX_BLOCKS), (unsigned)K), dim3(GR_BLOCK), 0, st, nrow, m,
+                               n_gslab, Z, W, V, ldw, partial);
+            hipLaunchKernelGGL(k_eig_gram_sum, dim3((unsigned)((2 * mm + 255) / 256), (unsigned)K), dim3(256), 0, st, m, n_gslab, partial, G);
+            hipLaunchKernelGGL(k_eig_ritz, dim3(1, (unsigned)K), dim3(RZ_BLOCK), 0, st, m, G, Q, theta, status, d_done);
+            hipLaunchKernelGGL(k_eig_rotate, dim3((unsigned)std::min(n_rslab, RT_MAX_BLOCKS), (unsigned)K), dim3(RT_BLOCK), 0, st, nrow, m,
+                               n_rslab, Z, W, V, Q, theta, status, d_done, ldw, d_x, ld_x, p_rr, p_mm);
+            hipLaunchKernelGGL(k_eig_residual, dim3(1, (unsigned)K), dim3(EG_COLS), 0, st, m, n_eig, n_rslab, tol, p_rr, p_mm, theta,
+                               status, res, d_done);
+            e = hipGetLastError();
+            if (e == hipSuccess)
+              e = hipMemcpyAsync(host.data(), theta, nread * sizeof(double), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess)
+              e = hipStreamSynchronize(st);
+            if (e != hipSuccess)
+              break;
+            ++outer;
+            const int *h_status = (const int *)(host.data() + 2 * ldw), *h_done = (const int *)(host.data() + 2 * ldw + nint);
+            for (int k = 0; k < K; ++k)
+              if (ran[(size_t)k] == 0 && h_done[k])
+                {
+                  ran[(size_t)k]           = outer;
+                  failed_column[(size_t)k] = h_status[k];
+                  --open;
+                }
+          }
+      }
+    const hipError_t es = hipStreamSynchronize(st); // the workspace is freed on return
+    if (e == hipSuccess)
+      e = es;
+    if (e != hipSuccess)
+      return slod_hip_fail(h, e, who);
+    std::copy(host.begin(), host.begin() + ldw, eigenvalues);
+    std::copy(host.begin() + ldw, host.begin() + 2 * ldw, residuals);
+    int worst = 0, bad = -1;
+    for (int k = K - 1; k >= 0; --k)
+      {
+        const bool failed = failed_column[(size_t)k] != 0;
+        member_status[k]  = failed ? (int)SLOD_ERR_NUMERIC : (ran[(size_t)k] ? ran[(size_t)k] : outer);
+        worst             = std::max(worst, member_status[k]);
+        if (failed)
+          bad = k;
+      }
+    if (bad >= 0)
+      return slod_fail(h, SLOD_ERR_NUMERIC,
+                       name + ": " + (ensemble ? "member " + std::to_string(bad) + ": " : std::string()) +
+                         "non-positive pivot in the Cholesky of Gm = Z^T M Z at column " + std::to_string(failed_column[(size_t)bad] - 1) +
+                         " of outer iteration " + std::to_string(ran[(size_t)bad]) + " (rank-deficient block)");
+    return worst;
   }
 
 } // namespace
@@ -470,37 +707,24 @@ int slod_lod_eigs(slod_handle *h, const double *d_stiffness, const double *d_mas
   const int      n_gslab = (nrow + GR_ROWS - 1) / GR_ROWS, n_rslab = w.ngroup;
   const size_t   nvec = (size_t)nrow * m, mm = (size_t)m * m;
   // one allocation for the whole loop: Y, Z, W, V, the slab partials, Ga | Gm, Q, theta | residuals | status (consecutive: the
-  // host reads them in one copy), the workspace of the solve
+  // host reads them in one copy), the done word of the kernels, the workspace of the solve
   double     *Y, *Z, *W, *V, *partial, *G, *Q, *p_rr, *p_mm, *theta, *res;
-  int        *status;
+  int        *status, *d_done;
   SlodLodWork work;
   hipError_t  e = work.alloc(m, [&](SlodCarver &c) {
     Y = c.take(nvec), Z = c.take(nvec), W = c.take(nvec), V = c.take(nvec);
     partial = c.take(2 * mm * n_gslab), G = c.take(2 * mm), Q = c.take(mm);
     p_rr = c.take((size_t)m * n_rslab), p_mm = c.take((size_t)m * n_rslab);
-    theta = c.take(m), res = c.take(m), status = c.take_as<int>(), work.take_solve(c, h);
+    theta = c.take(m), res = c.take(m), status = c.take_as<int>(), d_done = c.take_as<int>(), work.take_solve(c, h);
   });
+  if (e == hipSuccess)
+    e = hipMemsetAsync(status, 0, 2 * sizeof(double), st); // status and done: the host decides when this loop stops
   int outer = 0, failed_column = 0;
   if (e == hipSuccess)
     {
       if (start == 0)
         {
-          // the pairs (a, b) of {1..N}^2 in ascending a^2 + b^2, ties by ascending a
-          const int                        side = std::min(h->N, EG_COLS), n_modes = (m + s - 1) / s;
-          std::vector<std::pair<int, int>> ab;
-          for (int a = 1; a <= side; ++a)
-            for (int b = 1; b <= side; ++b)
-              ab.emplace_back(a, b);
-          std::sort(ab.begin(), ab.end(), [](const std::pair<int, int> &u, const std::pair<int, int> &v) {
-            const int nu = u.first * u.first + u.second * u.second, nv = v.first * v.first + v.second * v.second;
-            return nu != nv ? nu < nv : u.first < v.first;
-          });
-          EigModes md{};
-          for (int t = 0; t < n_modes; ++t)
-            {
-              md.a[t] = (unsigned char)ab[t].first;
-              md.b[t] = (unsigned char)ab[t].second;
-            }
+          const EigModes md = eig_sine_modes(h, m);
           hipLaunchKernelGGL(k_eig_start, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, st, slod_grid_of(h), h->NP, s, m, md,
                              d_x, ld_x);
           e = hipGetLastError();
@@ -518,12 +742,12 @@ int slod_lod_eigs(slod_handle *h, const double *d_stiffness, const double *d_mas
           slod_lod_apply_launch(h, st, d_stiffness, d_cols, Z, (size_t)m, m, W, (size_t)m);
           slod_lod_apply_launch(h, st, d_mass, d_cols, Z, (size_t)m, m, V, (size_t)m);
           hipLaunchKernelGGL(k_eig_gram, dim3((unsigned)std::min(n_gslab, GR_MAX_BLOCKS)), dim3(GR_BLOCK), 0, st, nrow, m, n_gslab, Z, W,
-                             V, partial);
+                             V, (size_t)m, partial);
           hipLaunchKernelGGL(k_eig_gram_sum, dim3((unsigned)((2 * mm + 255) / 256)), dim3(256), 0, st, m, n_gslab, partial, G);
-          hipLaunchKernelGGL(k_eig_ritz, dim3(1), dim3(RZ_BLOCK), 0, st, m, G, Q, theta, status);
+          hipLaunchKernelGGL(k_eig_ritz, dim3(1), dim3(RZ_BLOCK), 0, st, m, G, Q, theta, status, d_done);
           hipLaunchKernelGGL(k_eig_rotate, lod_grid(w, RT_MAX_BLOCKS), dim3(RT_BLOCK), 0, st, nrow, m, n_rslab, Z, W, V, Q, theta, status,
-                             d_x, ld_x, p_rr, p_mm);
-          hipLaunchKernelGGL(k_eig_residual, dim3(1), dim3(EG_COLS), 0, st, m, n_rslab, p_rr, p_mm, theta, status, res);
+                             d_done, (size_t)m, d_x, ld_x, p_rr, p_mm);
+          hipLaunchKernelGGL(k_eig_residual, dim3(1), dim3(EG_COLS), 0, st, m, n_eig, n_rslab, tol, p_rr, p_mm, theta, status, res, d_done);
           e = hipGetLastError();
           if (e == hipSuccess)
             e = hipMemcpyAsync(host.data(), theta, host.size() * sizeof(double), hipMemcpyDeviceToHost, st);
@@ -552,6 +776,23 @@ int slod_lod_eigs(slod_handle *h, const double *d_stiffness, const double *d_mas
                      "slod_lod_eigs: non-positive pivot in the Cholesky of Gm = Z^T M Z at column " + std::to_string(failed_column - 1) +
                        " of outer iteration " + std::to_string(outer) + " (rank-deficient block)");
   return outer;
+}
+
+int slod_lod_eigs_direct(slod_handle *h, slod_lod_factor *f_S, const double *d_stiffness, const double *d_mass, const uint32_t *d_cols,
+                         int n_eig, int n_block, int start, double *d_x, size_t ld_x, double tol, int max_outer, double *eigenvalues,
+                         double *residuals)
+{
+  int ran = 0;
+  return eigs_direct(h, "slod_lod_eigs_direct", false, f_S, d_stiffness, 1, d_mass, 1, d_cols, 1, n_eig, n_block, start, d_x, ld_x, tol,
+                     max_outer, eigenvalues, residuals, &ran);
+}
+
+int slod_lod_eigs_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, const double *d_stiffness, size_t ld_a_m, const double *d_mass,
+                                  size_t ld_m_m, const uint32_t *d_cols, int n_members, int n_eig, int n_block, int start, double *d_x,
+                                  size_t ld_x, double tol, int max_outer, double *eigenvalues, double *residuals, int *member_status)
+{
+  return eigs_direct(h, "slod_lod_eigs_ensemble_direct", true, f_S, d_stiffness, ld_a_m, d_mass, ld_m_m, d_cols, n_members, n_eig,
+                     n_block, start, d_x, ld_x, tol, max_outer, eigenvalues, residuals, member_status);
 }
 
 } // extern "C"

@@ -717,6 +717,51 @@ namespace slod
   }
 
   template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_eigenproblem_ensemble(const unsigned int n_eig, const double sigma)
+  {
+    if (!d_ens_mass)
+      throw std::runtime_error("solve_eigenproblem_ensemble: assemble_mass_matrix_ensemble comes first");
+    const int          K = (int)par.n_members;
+    const std::size_t  ld = (std::size_t)K;
+    const unsigned int n_patches = (unsigned int)patches.size();
+    const std::size_t  n_coarse = (std::size_t)n_patches * spacedim;
+    if (n_eig < 1 || n_eig > n_coarse || n_eig > 64)
+      throw std::runtime_error("solve_eigenproblem_ensemble: n_eig outside 1 .. min(64, unknowns)");
+    const int cap = slod_lod_row_capacity(handle);
+    check(cap, "slod_lod_row_capacity");
+    const std::size_t n_words = (std::size_t)n_patches * cap * spacedim * spacedim;
+    // the defaults of solve_eigenproblem
+    const int n_block = (int)std::min(std::min<std::size_t>(64, n_coarse), n_eig + std::max<std::size_t>(4, n_eig / 2));
+    const int max_outer = 200;
+    if (!d_ens_sym)
+      d_ens_sym = device_alloc<double>(n_words * K);
+    double *d_x = device_alloc<double>(n_coarse * n_block * K);
+    check(slod_lod_matrix_symmetrize_ensemble(handle, d_ens_values, ld, d_ens_cols, K, d_ens_sym, ld, nullptr),
+          "slod_lod_matrix_symmetrize_ensemble");
+    const double *d_S = d_ens_sym;
+    if (sigma != 0.0)
+      {
+        if (!d_ens_shifted)
+          d_ens_shifted = device_alloc<double>(n_words * K);
+        check(slod_lod_matrix_combine_ensemble(handle, 1.0, d_ens_sym, ld, -sigma, d_ens_mass, ld, K, d_ens_shifted, ld, nullptr),
+              "slod_lod_matrix_combine_ensemble");
+        d_S = d_ens_shifted;
+      }
+    slod_lod_factor *f = nullptr;
+    check(slod_lod_factor_create_ensemble(handle, d_S, ld, K, d_ens_cols, nullptr, &f), "slod_lod_factor_create_ensemble");
+    factors.push_back(f);
+    check(slod_lod_factor_get_info(f, &lod_factor_info), "slod_lod_factor_get_info");
+    ens_eig_block = n_block;
+    ens_eigenvalues.assign((std::size_t)K * n_block, 0.0);
+    ens_eig_residuals.assign((std::size_t)K * n_block, 0.0);
+    ens_eig_outer.assign(K, 0);
+    const int rc = slod_lod_eigs_ensemble_direct(handle, f, d_ens_sym, ld, d_ens_mass, ld, d_ens_cols, K, (int)n_eig, n_block, 0, d_x,
+                                                 ld * n_block, 1e-10, max_outer, ens_eigenvalues.data(), ens_eig_residuals.data(),
+                                                 ens_eig_outer.data());
+    check(rc < 0 ? rc : 0, "slod_lod_eigs_ensemble_direct");
+  }
+
+  template <int dim, int spacedim>
   void LOD<dim, spacedim>::assemble_mass_matrix()
   {
     if (!d_lod_values)
@@ -816,7 +861,7 @@ namespace slod
   }
 
   template <int dim, int spacedim>
-  void LOD<dim, spacedim>::solve_eigenproblem(const unsigned int n_eig)
+  void LOD<dim, spacedim>::solve_eigenproblem(const unsigned int n_eig, const bool direct, const double sigma)
   {
     if (!d_lod_mass)
       throw std::runtime_error("solve_eigenproblem: assemble_global_matrix and assemble_mass_matrix come first");
@@ -839,11 +884,35 @@ namespace slod
     lod_eigenvalues.assign(n_block, 0.0);
     lod_eig_residuals.assign(n_block, 0.0);
     lod_eig_inner_iterations.assign(max_outer, 0);
-    const int outer = slod_lod_eigs(handle, d_lod_sym, d_lod_mass, d_lod_cols, (int)n_eig, n_block, 0, d_eig_x, (std::size_t)n_block,
-                                    1e-10, max_outer, 1e-12, 2000, lod_eigenvalues.data(), lod_eig_residuals.data(),
-                                    lod_eig_inner_iterations.data());
-    check(outer < 0 ? outer : 0, "slod_lod_eigs");
-    lod_eig_inner_iterations.resize(outer);
+    int outer;
+    if (direct)
+      {
+        // S = sym(A_LOD) - sigma M_LOD; sigma = 0: the factor of sym(A_LOD) itself
+        const double *d_S = d_lod_sym;
+        if (sigma != 0.0)
+          {
+            if (!d_lod_shifted)
+              d_lod_shifted = device_alloc<double>((std::size_t)n_patches * cap * spacedim * spacedim);
+            check(slod_lod_matrix_combine(handle, 1.0, d_lod_sym, -sigma, d_lod_mass, d_lod_shifted, nullptr), "slod_lod_matrix_combine");
+            d_S = d_lod_shifted;
+          }
+        if (hipDeviceSynchronize() != hipSuccess)
+          throw std::runtime_error("solve_eigenproblem: forming S failed");
+        slod_lod_factor *f = factor_lod_matrix(d_S);
+        outer              = slod_lod_eigs_direct(handle, f, d_lod_sym, d_lod_mass, d_lod_cols, (int)n_eig, n_block, 0, d_eig_x,
+                                                  (std::size_t)n_block, 1e-10, max_outer, lod_eigenvalues.data(), lod_eig_residuals.data());
+        check(outer < 0 ? outer : 0, "slod_lod_eigs_direct");
+        lod_eig_inner_iterations.clear();
+      }
+    else
+      {
+        outer = slod_lod_eigs(handle, d_lod_sym, d_lod_mass, d_lod_cols, (int)n_eig, n_block, 0, d_eig_x, (std::size_t)n_block, 1e-10,
+                              max_outer, 1e-12, 2000, lod_eigenvalues.data(), lod_eig_residuals.data(),
+                              lod_eig_inner_iterations.data());
+        check(outer < 0 ? outer : 0, "slod_lod_eigs");
+        lod_eig_inner_iterations.resize(outer);
+      }
+    lod_eig_outer = outer;
     check(slod_lod_reconstruct_multi(handle, d_basis, basis_stride, d_eig_x, (std::size_t)n_block, (int)n_eig, d_eig_fine, fine_size,
                                      nullptr),
           "slod_lod_reconstruct_multi");

@@ -145,8 +145,12 @@ namespace slod
     // The lowest n_eig eigenpairs of A_LOD u = lambda M_LOD u after assemble_mass_matrix() (the reference has no
     // counterpart): A_LOD symmetrised (slod_lod_matrix_symmetrize), slod_lod_eigs with its documented defaults
     // (n_eig + max(4, n_eig / 2) block columns, tol 1e-10, inner tolerance 1e-12), then the eigenfunctions C x_k on the
-    // fine grid (slod_lod_reconstruct_multi) and their norms (slod_compute_error_norms)
-    void solve_eigenproblem(const unsigned int n_eig);
+    // fine grid (slod_lod_reconstruct_multi) and their norms (slod_compute_error_norms).
+    // direct: the inner solve runs on the banded Cholesky factor of S = sym(A_LOD) - sigma M_LOD (slod_lod_matrix_combine,
+    // factor_lod_matrix, slod_lod_eigs_direct); sigma must lie below the lowest eigenvalue (the factorisation fails
+    // otherwise), there are no inner iteration counts, and eigen_outer_iterations() is the count of the outer ones.
+    void solve_eigenproblem(const unsigned int n_eig, const bool direct = false, const double sigma = 0.0);
+    int  eigen_outer_iterations() const { return lod_eig_outer; }
     const std::vector<double>           &eigenvalues() const { return lod_eigenvalues; }   // all block columns
     const std::vector<double>           &eigen_residuals() const { return lod_eig_residuals; }
     const std::vector<int>              &eigen_inner_iterations() const { return lod_eig_inner_iterations; } // per outer iteration
@@ -200,6 +204,17 @@ namespace slod
     // coefficient.  Then the final states on the fine grid and their moments as in solve_ensemble().
     // last_factor_info() is that of S, the range over all members.
     void solve_wave_ensemble(const unsigned int n_steps, const double dt, const double beta, const double gamma);
+    // solve_eigenproblem(.., direct = true) for all members at once, after assemble_mass_matrix_ensemble(): the symmetrised
+    // stiffness of every member, S_k = sym(A_k) - sigma M_k (sigma = 0: sym(A_k) itself), one factor object for all members
+    // and slod_lod_eigs_ensemble_direct with the defaults of solve_eigenproblem.  Member k's eigenvalues, residuals and
+    // outer count are those of solve_eigenproblem(.., true, sigma) of a problem with member k's coefficient.
+    // last_factor_info() is the range over all members.
+    void solve_eigenproblem_ensemble(const unsigned int n_eig, const double sigma = 0.0);
+    // [member * n_block + column], n_block = eigen_ensemble_block(); [member]
+    const std::vector<double> &eigenvalues_ensemble() const { return ens_eigenvalues; }
+    const std::vector<double> &eigen_residuals_ensemble() const { return ens_eig_residuals; }
+    const std::vector<int>    &eigen_outer_iterations_ensemble() const { return ens_eig_outer; }
+    int                        eigen_ensemble_block() const { return ens_eig_block; }
     // [step * n_members + member], step = 0 .. n_steps, step 0 the state at rest: v^T M v / 2, u^T A u / 2 and u^T b
     const std::vector<double> &wave_ensemble_kinetic() const { return ens_wave_kinetic; }
     const std::vector<double> &wave_ensemble_potential() const { return ens_wave_potential; }
@@ -280,6 +295,7 @@ namespace slod
     double                       *d_lod_sym = nullptr, *d_eig_x = nullptr, *d_eig_fine = nullptr;
     std::vector<double>           lod_eigenvalues, lod_eig_residuals;
     std::vector<int>              lod_eig_inner_iterations;
+    int                           lod_eig_outer = 0;
     std::vector<slod_error_norms> lod_eig_norms;
     // solve_wave: u, v, a and the load (4 coarse vectors), the final state on the fine grid
     double             *d_wave_state = nullptr, *d_wave_fine = nullptr;
@@ -309,6 +325,10 @@ namespace slod
     double             *d_ens_sym = nullptr;
     std::vector<double> ens_wave_kinetic, ens_wave_potential, ens_wave_work;
     slod_error_norms    ens_wave_mean_norms{}, ens_wave_dev_norms{};
+    // solve_eigenproblem_ensemble
+    std::vector<double> ens_eigenvalues, ens_eig_residuals;
+    std::vector<int>    ens_eig_outer;
+    int                 ens_eig_block = 0;
     // mean and standard deviation of n_members fine fields: slod_ensemble_moments, the square root on the host, the norms
     void ensemble_moment_norms(const double *d_fine, double *d_mean, double *d_var, slod_error_norms &mean, slod_error_norms &dev);
 

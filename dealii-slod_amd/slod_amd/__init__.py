@@ -172,6 +172,9 @@ def load():
     lib.slod_lod_newmark_steps_ensemble_direct.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_double, C.c_double,
                                                            C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.c_size_t,
                                                            vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, dp, dp]
+    lib.slod_lod_eigs_direct.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_double, C.c_int, dp, dp]
+    lib.slod_lod_eigs_ensemble_direct.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  vp, C.c_size_t, C.c_double, C.c_int, dp, dp, C.POINTER(C.c_int)]
     lib.slod_update_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, C.c_int, C.c_size_t, C.c_int, vp]
     lib.slod_dirty_patches.argtypes = [vp, vp, u32p, C.c_size_t]
     lib.slod_plan_create_dirty.argtypes = [vp, C.c_uint32, vp, C.POINTER(vp)]
@@ -802,6 +805,41 @@ class Slod:
             n_members if ld_a is None else ld_a, d_load, n_members if ld_load is None else ld_load, load_step_stride,
             _dp(kin) if energies else None, _dp(pot) if energies else None))
         return kin, pot
+
+    # ---- eigenpairs on a factor of S = A - sigma M, for one pencil and per ensemble member ----
+    def lod_eigs_direct(self, factor, d_stiffness, d_mass, d_cols, n_eig, d_x, n_block=None, ld_x=None, start=0, tol=1e-10,
+                        max_outer=200):
+        """lod_eigs with the inner CG replaced by the factor of S = sym(A) - sigma M, sigma < lambda_1
+        (lod_matrix_combine(1, A, -sigma, M)).  Returns (eigenvalues[n_block], residuals[n_block], outer iterations)."""
+        if n_block is None:
+            n_block = min(64, self.num_patches * self.spacedim, n_eig + max(4, n_eig // 2))
+        lam = np.zeros(max(n_block, 1))
+        res = np.zeros(max(n_block, 1))
+        rc = self.lib.slod_lod_eigs_direct(self.h, _factor_ptr(factor), d_stiffness, d_mass, d_cols, n_eig, n_block, start, d_x,
+                                           n_block if ld_x is None else ld_x, tol, max_outer, _dp(lam), _dp(res))
+        if rc < 0:
+            self._check(rc)
+        return lam[:n_block], res[:n_block], rc
+
+    def lod_eigs_ensemble_direct(self, factor, d_stiffness, d_mass, d_cols, n_members, n_eig, d_x, n_block=None, ld_a_m=None,
+                                 ld_m_m=None, ld_x=None, start=0, tol=1e-10, max_outer=200, check=True):
+        """lod_eigs_direct for the pencils of an ensemble: member k owns columns k * n_block .. of d_x, its matrices are member
+        k of the ensemble matrices and its factor member k of `factor`.  Returns (eigenvalues[n_members, n_block],
+        residuals[n_members, n_block], member_status[n_members], rc); member_status[k] is the outer iterations of member k
+        or -5.  check=False: a failed member (rc = -5) does not raise."""
+        if n_block is None:
+            n_block = min(64, self.num_patches * self.spacedim, n_eig + max(4, n_eig // 2))
+        shape = (max(n_members, 1), max(n_block, 1))
+        lam, res = np.zeros(shape), np.zeros(shape)
+        status = np.zeros(shape[0], dtype=np.intc)
+        rc = self.lib.slod_lod_eigs_ensemble_direct(
+            self.h, _factor_ptr(factor), d_stiffness, n_members if ld_a_m is None else ld_a_m, d_mass,
+            n_members if ld_m_m is None else ld_m_m, d_cols, n_members, n_eig, n_block, start, d_x,
+            n_members * n_block if ld_x is None else ld_x, tol, max_outer, _dp(lam), _dp(res),
+            status.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc < 0 and (check or rc != -5):
+            self._check(rc)
+        return lam, res, status, rc
 
     def fem_rhs(self, d_f_qp, d_fine_rhs, stream=None):
         """Fine FEM load vector (d_f_qp = None: f = 1)."""

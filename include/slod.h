@@ -575,9 +575,9 @@ int slod_ensemble_moments(slod_handle *h, const double *d_fields, size_t ld_fine
  * the words of slod_lod_matrix_symmetrize and slod_lod_matrix_combine, the block column and the two sweeps of the
  * factor) with the member on a grid axis; a single-problem call is the instance n_members = 1, ld = 1.  Every result
  * of member k has the bits of the single-problem call on member k's de-interleaved data.  The common argument checks are
- * those of the ensemble block above.  Newmark on an ensemble factor is the block after this one.  Not built: a CG
- * ensemble stepper, the ensemble eigensolver, refactoring after slod_lod_matrix_update, members spread over ranks,
- * several columns per member in a stepper. */
+ * those of the ensemble block above.  Newmark on an ensemble factor is the block after this one, the eigensolver on an
+ * ensemble factor the one after that.  Not built: a CG ensemble stepper, refactoring after slod_lod_matrix_update,
+ * members spread over ranks, several columns per member in a stepper. */
 /* Block rows of M_LOD of all num_patches patches for every member: member k's values are those of slod_lod_mass_matrix
  * with rows 0 .. num_patches-1 on its slab, bit for bit.  d_cols is written once.  d_rho NULL: density 1; ld_rho = 0: one
  * density [NE][NE] shared by all members; else member k's density at d_rho + k * ld_rho.  SLOD_ERR_ARGUMENT also for a
@@ -678,6 +678,66 @@ int slod_lod_newmark_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S,
                                            size_t ld_a, const double *d_load, size_t ld_load, size_t load_step_stride,
                                            double *kinetic   /* HOST [(n_steps + 1) * n_members], may be NULL */,
                                            double *potential /* HOST [(n_steps + 1) * n_members], may be NULL */);
+
+/* ---- eigenpairs on banded Cholesky factors, for one pencil and per ensemble member ----------------
+ * slod_lod_eigs with the inner CG replaced by the two sweeps of a factor: no inner tolerance, no inner iteration count.
+ * f_S factors a symmetric positive definite  S = A - sigma M  with sigma < lambda_1, built by the caller from
+ * slod_lod_matrix_combine(1, sym A, -sigma, M) (or its _ensemble form) and slod_lod_factor_create(_ensemble); sigma = 0
+ * means the factor of sym(A).  The eigensolver never sees sigma: Rayleigh-Ritz is done on the pencil (A, M) itself, so
+ * eigenvalues and residuals are those of (A, M) whatever the shift.
+ *   - That S belongs to these matrices is NOT checked, as in the time steppers on a factor.
+ *   - sigma < lambda_1 is the caller's duty: slod_lod_factor_create* answers SLOD_ERR_NUMERIC for an S that is not
+ *     positive definite, so a factor that exists is one of a definite S.
+ *   - Column j contracts by about (lambda_j - sigma) / (lambda_{m+1} - sigma) per outer iteration, m = n_block.
+ * Outer iteration k = 1, 2, ..:  Y = M X;  S Z = Y on the factor;  W = A Z, V = M Z;  Ga = sym(Z^T W), Gm = sym(Z^T V);
+ * the Ritz step;  X = Z Q;  res_j as documented for slod_lod_eigs;  stop when res_j <= tol for all j < n_eig or at
+ * k = max_outer (not an error).  The Gram, Ritz, rotate and residual kernels are those of slod_lod_eigs; the products run
+ * the fma chain of slod_lod_apply_multi.  Not built: LDL^T and eigenvalues near an interior sigma, LOBPCG, locking of
+ * converged columns, n_block > 64. */
+/* One pencil.  Arguments as in slod_lod_eigs, less the inner parameters.  Returns the number of outer iterations run
+ * (>= 1) or a negative slod_status.  SLOD_ERR_NUMERIC: rank-deficient block as in slod_lod_eigs; d_x then holds the block
+ * the failed iteration started from, eigenvalues and residuals those of the last completed iteration (0 if none).
+ * Fixed summation orders: the same inputs give the same bits, run after run.  This is the one-member instance of the
+ * ensemble call below (n_members = 1, ld = 1).
+ * SLOD_ERR_ARGUMENT (before any device work, the call's name in slod_last_error): NULL handle, matrix, d_cols, d_x,
+ * eigenvalues or residuals; n_eig < 1; n_block < n_eig; n_block > 64 or > num_patches * s; start not 0 or 1; tol <= 0 or
+ * NaN; max_outer < 1; ld_x < n_block; a NULL factor, the factor of another handle or row count, a factor of more than
+ * one member (checked last).  Runs on the handle's stream; synchronises. */
+int slod_lod_eigs_direct(slod_handle *h, slod_lod_factor *f_S,
+                         const double *d_stiffness, const double *d_mass, const uint32_t *d_cols,
+                         int n_eig, int n_block, int start, double *d_x, size_t ld_x,
+                         double tol, int max_outer,
+                         double *eigenvalues /* HOST [n_block] */,
+                         double *residuals   /* HOST [n_block] */);
+/* The n_members pencils (A_k, M_k) of a coefficient ensemble at once, member k on member k of f_S.  Layout of
+ * slod_lod_factor_solve_ensemble: member k owns columns k * n_block .. k * n_block + n_block - 1 of d_x,
+ * ld_x >= n_members * n_block, entries beyond that are never read or written; the matrices are member-minor on one
+ * pattern (ld_a_m, ld_m_m >= n_members, the two may differ).  start = 0 writes the sine block of slod_lod_eigs into every
+ * member's columns; start = 1 takes the caller's block.  HOST eigenvalues and residuals: entry [k * n_block + j].
+ * Every member stops on its own, on the device: the residual kernel compares member k's residuals with tol (the <= of
+ * slod_lod_eigs) and sets its done word when all j < n_eig pass, or when its Ritz step failed; from then on the Ritz,
+ * rotate and residual kernels skip that member, whose X, theta and residuals stay those of its last iteration (the factor
+ * solve and the products go on running on its frozen columns).  The host reads theta, residuals, status and done of all
+ * members in one copy per outer iteration and stops when every member is done, or at max_outer.
+ * member_status[k]: the outer iterations member k ran (>= 1), or SLOD_ERR_NUMERIC for a rank-deficient block; member k's
+ * columns of d_x then hold the block its failed iteration started from, its eigenvalues and residuals those of its last
+ * completed iteration (0 if none), and the other members finish and are valid.
+ * Returns the largest count if every member succeeded; SLOD_ERR_NUMERIC if a member failed (slod_last_error names the
+ * call, the lowest failing member, its column and its outer iteration); else a negative slod_status.
+ * Member k's X, eigenvalues, residuals and count have the bits of slod_lod_eigs_direct on member k's de-interleaved
+ * matrices, its single factor and its own start block: nothing depends on n_members, an ld, the member's position or the
+ * other members.  Device workspace (4 vectors of n_members * n_block columns, per member the slab partials, Ga, Gm, Q)
+ * allocated once per call.
+ * SLOD_ERR_ARGUMENT (before any device work, the call's name in slod_last_error): what slod_lod_eigs_direct refuses, and
+ * n_members < 1 or > 65535; ld_a_m or ld_m_m < n_members; ld_x < n_members * n_block; NULL member_status; a factor whose
+ * member count is not n_members (checked last).  Runs on the handle's stream; synchronises. */
+int slod_lod_eigs_ensemble_direct(slod_handle *h, slod_lod_factor *f_S,
+                                  const double *d_stiffness, size_t ld_a_m, const double *d_mass, size_t ld_m_m,
+                                  const uint32_t *d_cols, int n_members, int n_eig, int n_block, int start,
+                                  double *d_x, size_t ld_x, double tol, int max_outer,
+                                  double *eigenvalues   /* HOST [n_members * n_block] */,
+                                  double *residuals     /* HOST [n_members * n_block] */,
+                                  int    *member_status /* HOST [n_members] */);
 
 /* ---- refresh after a local coefficient change ----------------------------------------------
  * Every entry point above takes the coefficient as fixed for the life of a basis (the reference does too: one
