@@ -1,7 +1,7 @@
 // Counterpart of reference app/main_Diffusion.cc for the basis-construction path:
 //   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare] [--coarse] [--loads K]
 //                  [--heat STEPS DT] [--eigs K] [--shift SIGMA] [--wave STEPS DT] [--direct] [--ensemble K] [--perturb K]
-//                  [--member K]
+//                  [--member K] [--ldl]
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
 // file name it dumps, per patch, phi and psi in patch-lexicographic order (parity tests).
 // --compare (anywhere on the command line): after run(), the rest of the reference run() -- global
@@ -21,6 +21,11 @@
 // --eigs K --direct [--shift SIGMA]: the same pairs with the inner solve on the banded Cholesky factor of
 // S = sym(A_LOD) - SIGMA M_LOD (slod_lod_eigs_direct; SIGMA below the lowest eigenvalue, default 0): the eigenvalue lines,
 // "eigensolver: outer iterations = N, direct", the factor line in place of the inner iteration counts, the norms.
+// --eigs K --direct --shift SIGMA --ldl: SIGMA may lie inside the spectrum.  S is factored by the banded LDL^T without
+// pivoting (slod_lod_factor_create_ldl) and the K pairs NEAREST SIGMA are computed (slod_lod_eigs_shift_direct), printed in
+// order of distance from SIGMA.  The factor line reads "factor: n = .., half bandwidth = .., bytes = .., LDL^T, n_negative
+// = .. (eigenvalues below sigma), growth = ..".  With --ensemble K the same per member ("member K factor: n_negative = ..,
+// growth = .."), then the mean and standard deviation of n_negative and of each eigenvalue over the members.
 // --ensemble K --eigs N --direct: after the lines of --ensemble, the N lowest pairs of every member on one factor object
 // (slod_lod_eigs_ensemble_direct): the factor line (pivots over all members), per member "member K eigenvalue J = ..,
 // residual = .." and "member K eigensolver: outer iterations = .., direct", the numbers of a --member K --eigs N --direct
@@ -113,10 +118,29 @@ static void print_factor(const slod_lod_factor_info &f)
               (unsigned long long)f.bytes, f.min_pivot, f.max_pivot);
 }
 
+static void print_ldl_factor(const slod_lod_factor_info &f, const slod_lod_factor_inertia_info &i)
+{
+  std::printf("factor: n = %d, half bandwidth = %d, bytes = %llu, LDL^T, n_negative = %d (eigenvalues below sigma), growth = %.6e\n",
+              f.n, f.half_bandwidth, (unsigned long long)f.bytes, i.n_negative, i.norm_factor / i.norm_matrix);
+}
+
+// sample mean and unbiased standard deviation, summed in ascending order
+static void mean_and_deviation(const std::vector<double> &x, double &mean, double &dev)
+{
+  mean = 0.0;
+  for (const double v : x)
+    mean += v;
+  mean /= (double)x.size();
+  double var = 0.0;
+  for (const double v : x)
+    var += (v - mean) * (v - mean);
+  dev = std::sqrt(x.size() > 1 ? var / (double)(x.size() - 1) : 0.0);
+}
+
 int main(int argc_all, char **argv_all)
 {
   // --compare and --coarse are taken out wherever they stand; the positional arguments keep their meaning
-  bool               compare = false, coarse = false, direct = false;
+  bool               compare = false, coarse = false, direct = false, ldl = false;
   int                n_loads = 0, heat_steps = 0, n_eigs = 0, wave_steps = 0, n_members = 0, n_perturb = 0, member = 0;
   double             heat_dt = 0.0, wave_dt = 0.0, shift = 0.0;
   std::vector<char *> args;
@@ -127,6 +151,8 @@ int main(int argc_all, char **argv_all)
       compare = coarse = true;
     else if (i > 0 && !std::strcmp(argv_all[i], "--direct"))
       direct = true;
+    else if (i > 0 && !std::strcmp(argv_all[i], "--ldl"))
+      ldl = true;
     else if (i > 0 && !std::strcmp(argv_all[i], "--loads") && i + 1 < argc_all)
       n_loads = std::atoi(argv_all[++i]);
     else if (i > 0 && !std::strcmp(argv_all[i], "--heat") && i + 2 < argc_all)
@@ -262,13 +288,19 @@ int main(int argc_all, char **argv_all)
             problem.assemble_global_matrix();
           if (heat_steps <= 0)
             problem.assemble_mass_matrix();
-          problem.solve_eigenproblem((unsigned int)n_eigs, direct, shift);
+          if (direct && ldl)
+            problem.solve_eigenproblem_near(shift, (unsigned int)n_eigs);
+          else
+            problem.solve_eigenproblem((unsigned int)n_eigs, direct, shift);
           for (int k = 0; k < n_eigs; ++k)
             std::printf("eigenvalue %d = %.12e, residual = %.3e\n", k + 1, problem.eigenvalues()[k], problem.eigen_residuals()[k]);
           if (direct)
             {
               std::printf("eigensolver: outer iterations = %d, direct\n", problem.eigen_outer_iterations());
-              print_factor(problem.last_factor_info());
+              if (ldl)
+                print_ldl_factor(problem.last_factor_info(), problem.last_factor_inertia());
+              else
+                print_factor(problem.last_factor_info());
             }
           else
             {
@@ -346,15 +378,33 @@ int main(int argc_all, char **argv_all)
         }
       if (n_members > 0 && n_eigs > 0 && direct)
         {
-          problem.solve_eigenproblem_ensemble((unsigned int)n_eigs, shift);
-          print_factor(problem.last_factor_info());
+          if (ldl)
+            problem.solve_eigenproblem_ensemble_near(shift, (unsigned int)n_eigs);
+          else
+            problem.solve_eigenproblem_ensemble((unsigned int)n_eigs, shift);
+          if (ldl)
+            print_ldl_factor(problem.last_factor_info(), problem.factor_inertia_ensemble()[0]);
+          else
+            print_factor(problem.last_factor_info());
           const int m = problem.eigen_ensemble_block();
           for (int k = 0; k < n_members; ++k)
             {
+              if (ldl)
+                std::printf("member %d factor: n_negative = %d, growth = %.6e\n", k, problem.factor_inertia_ensemble()[k].n_negative,
+                            problem.factor_inertia_ensemble()[k].norm_factor / problem.factor_inertia_ensemble()[k].norm_matrix);
               for (int j = 0; j < n_eigs; ++j)
                 std::printf("member %d eigenvalue %d = %.12e, residual = %.3e\n", k, j + 1,
                             problem.eigenvalues_ensemble()[(std::size_t)k * m + j], problem.eigen_residuals_ensemble()[(std::size_t)k * m + j]);
               std::printf("member %d eigensolver: outer iterations = %d, direct\n", k, problem.eigen_outer_iterations_ensemble()[k]);
+            }
+          if (ldl)
+            {
+              std::vector<double> below;
+              for (int k = 0; k < n_members; ++k)
+                below.push_back((double)problem.factor_inertia_ensemble()[k].n_negative);
+              double mean, dev;
+              mean_and_deviation(below, mean, dev);
+              std::printf("n_negative over the ensemble of %d: mean = %.12e, standard deviation = %.12e\n", n_members, mean, dev);
             }
           for (int j = 0; j < n_eigs; ++j)
             {

@@ -222,10 +222,20 @@ void slod_lod_apply_ensemble_launch(const slod_handle *h, hipStream_t st, const 
 // The banded Cholesky factors of the full sets of block rows of n_members matrices on one pattern (slod_lod_factor.hip;
 // a single factor has one member): 16 x 16 tiles, nb block rows, bb block sub-diagonals.  mem holds n_members copies of
 // member_doubles doubles (band, factored diagonal tiles, pivots, reciprocal diagonal of L; the pointers are member 0's),
-// then the row map, which all members share, and a status word per member.
+// then the row map, which all members share, and a status word per member.  kind SLOD_FACTOR_LDL: S = L D L^T without
+// pivoting (k_ldl_column); the diagonal tiles hold the unit lower triangular L_II, piv is D (signed), dinv 1 / D, and a
+// member has two norms behind its pivots (||S||_inf, || |L| |D| |L^T| ||_inf) and two work vectors behind dinv.
+enum slod_factor_kind { SLOD_FACTOR_CHOLESKY = 0, SLOD_FACTOR_LDL = 1 };
+struct slod_lod_factor_inertia_host // HOST, per member of an LDL^T factor: slod_lod_factor_inertia_info of include/slod.h
+{
+  int    n_negative = 0, n_positive = 0;
+  double min_abs = 0.0, max_abs = 0.0, norm_matrix = 0.0, norm_factor = 0.0;
+};
 struct slod_lod_factor
 {
   slod_handle        *h = nullptr;
+  int                 kind = SLOD_FACTOR_CHOLESKY;
+  std::vector<slod_lod_factor_inertia_host> inertia; // HOST [n_members], LDL^T only
   int                 n = 0, b = 0, nb = 0, bb = 0; // rows, half bandwidth, block rows, block sub-diagonals
   int                 n_members = 1;
   size_t              member_doubles = 0, bytes = 0;

@@ -62,6 +62,22 @@ namespace
     x[i * ld_x + j] = d == e ? sx * sy : 0.0;
   }
 
+  // The start block of slod_lod_eigs_shift_direct: entry (caller's row i, column j) is the hash of include/slod.h, a
+  // splitmix64 step on (i << 32 | j) mapped to [-1, 1); the same block for every member (blockIdx.y)
+  __global__ __launch_bounds__(256) void k_eig_start_hash(int nrow, int m, double *x, size_t ld_x)
+  {
+    const size_t w = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= (size_t)nrow * m)
+      return;
+    x += (size_t)blockIdx.y * m;
+    const size_t       i = w / m, j = w - i * m;
+    unsigned long long z = ((unsigned long long)i << 32 | (unsigned long long)j) + 0x9E3779B97F4A7C15ull;
+    z                    = (z ^ z >> 30) * 0xBF58476D1CE4E5B9ull;
+    z                    = (z ^ z >> 27) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    x[i * ld_x + j] = (double)(z >> 11) * 0x1p-52 - 1.0;
+  }
+
   // ---------------------------------------------------------------------------------
   // Gram products.  A block takes slabs of GR_ROWS rows (slab g = blockIdx.x, += gridDim.x, as k_lod_apply walks its
   // groups), stages the rows of Z, W, V in LDS (48 KiB) and accumulates Z^T W and Z^T V: thread (ti, tj) of the
@@ -162,13 +178,15 @@ namespace
   //                          pairs: the rotations of a round commute, so the order is fixed and the result does not
   //                          depend on the thread that applies a rotation), until off(C) <= m eps ||C||_F at the head
   //                          of a sweep or RZ_SWEEPS sweeps
-  //   sort D ascending, ties by index;  Q = L^-T U (sorted columns)
+  //   sort D ascending, ties by index;  Q = L^-T U (sorted columns).  near != 0 (slod_lod_eigs_shift_direct): the key is
+  //   |D_j - sigma| ascending, ties by ascending D_j, then by index; with near = 0 the two keys agree and the order, hence
+  //   every word, is that of the ascending sort
   // ---------------------------------------------------------------------------------
   constexpr int RZ_LD = EG_COLS + 1, RZ_BLOCK = 256, RZ_SWEEPS = 30;
 
   __global__ __launch_bounds__(RZ_BLOCK) void k_eig_ritz(int m, const double *__restrict__ G, double *__restrict__ Q,
                                                         double *__restrict__ theta, int *__restrict__ status,
-                                                        const int *__restrict__ done)
+                                                        const int *__restrict__ done, int near, double sigma)
   {
     __shared__ double A[EG_COLS * RZ_LD], L[EG_COLS * RZ_LD], U[EG_COLS * RZ_LD];
     __shared__ double s_c[EG_COLS / 2], s_s[EG_COLS / 2], s_d[EG_COLS], s_off[EG_COLS], s_fro[EG_COLS];
@@ -343,10 +361,13 @@ namespace
     __syncthreads();
     if (tid < m)
       {
-        const double v = s_d[tid];
+        const double v = s_d[tid], key = near ? fabs(v - sigma) : v;
         int          rank = 0;
         for (int k = 0; k < m; ++k)
-          rank += (s_d[k] < v || (s_d[k] == v && k < tid)) ? 1 : 0;
+          {
+            const double dk = s_d[k], kk = near ? fabs(dk - sigma) : dk;
+            rank += (kk < key || (kk == key && (dk < v || (dk == v && k < tid)))) ? 1 : 0;
+          }
         s_perm[rank] = tid;
       }
     __syncthreads();
@@ -534,7 +555,9 @@ namespace
 
   // The body of slod_lod_eigs_ensemble_direct; slod_lod_eigs_direct is the call with n_members = 1 and ld = 1.  Member k
   // works on columns k m .. k m + m - 1 of d_x and of the workspace vectors.  Arguments are checked here, the factor last.
-  int eigs_direct(slod_handle *h, const char *who, bool ensemble, slod_lod_factor *f_S, const double *d_stiffness, size_t ld_a_m,
+  // near: the body of slod_lod_eigs_shift(_ensemble)_direct: the Ritz pairs are ordered by their distance from sigma and
+  // start = 0 writes the hashed block; without it sigma is not used.
+  int eigs_direct(slod_handle *h, const char *who, bool ensemble, bool near, double sigma, slod_lod_factor *f_S, const double *d_stiffness, size_t ld_a_m,
                   const double *d_mass, size_t ld_m_m, const uint32_t *d_cols, int n_members, int n_eig, int n_block, int start,
                   double *d_x, size_t ld_x, double tol, int max_outer, double *eigenvalues, double *residuals, int *member_status)
   {
@@ -560,6 +583,8 @@ namespace
       return slod_fail(h, SLOD_ERR_ARGUMENT, name + (ensemble ? ": leading dimension below n_members * n_block" : ": leading dimension below n_block"));
     if (!member_status)
       return slod_fail(h, SLOD_ERR_ARGUMENT, name + ": NULL member_status");
+    if (near && !(sigma - sigma == 0.0))
+      return slod_fail(h, SLOD_ERR_ARGUMENT, name + ": sigma is NaN or infinite");
     if (const int rc = slod_lod_factor_check(h, who, f_S, K)) // last: it reads the factor
       return rc;
     hipStream_t st;
@@ -596,8 +621,11 @@ namespace
       {
         if (start == 0)
           {
-            hipLaunchKernelGGL(k_eig_start, dim3((unsigned)(((size_t)nrow * m + 255) / 256), (unsigned)K), dim3(256), 0, st,
-                               slod_grid_of(h), h->NP, s, m, eig_sine_modes(h, m), d_x, ld_x);
+            const dim3 start_grid((unsigned)(((size_t)nrow * m + 255) / 256), (unsigned)K);
+            if (near)
+              hipLaunchKernelGGL(k_eig_start_hash, start_grid, dim3(256), 0, st, nrow, m, d_x, ld_x);
+            else
+              hipLaunchKernelGGL(k_eig_start, start_grid, dim3(256), 0, st, slod_grid_of(h), h->NP, s, m, eig_sine_modes(h, m), d_x, ld_x);
             e = hipGetLastError();
           }
         const dim3 apply_grid((unsigned)std::min(w.ngroup, AP_MAX_BLOCKS), (unsigned)K);
@@ -614,7 +642,8 @@ namespace
             hipLaunchKernelGGL(k_eig_gram, dim3((unsigned)std::min(n_gslab, GR_MAX_BLOCKS), (unsigned)K), dim3(GR_BLOCK), 0, st, nrow, m,
                                n_gslab, Z, W, V, ldw, partial);
             hipLaunchKernelGGL(k_eig_gram_sum, dim3((unsigned)((2 * mm + 255) / 256), (unsigned)K), dim3(256), 0, st, m, n_gslab, partial, G);
-            hipLaunchKernelGGL(k_eig_ritz, dim3(1, (unsigned)K), dim3(RZ_BLOCK), 0, st, m, G, Q, theta, status, d_done);
+            hipLaunchKernelGGL(k_eig_ritz, dim3(1, (unsigned)K), dim3(RZ_BLOCK), 0, st, m, G, Q, theta, status, d_done, near ? 1 : 0,
+                               sigma);
             hipLaunchKernelGGL(k_eig_rotate, dim3((unsigned)std::min(n_rslab, RT_MAX_BLOCKS), (unsigned)K), dim3(RT_BLOCK), 0, st, nrow, m,
                                n_rslab, Z, W, V, Q, theta, status, d_done, ldw, d_x, ld_x, p_rr, p_mm);
             hipLaunchKernelGGL(k_eig_residual, dim3(1, (unsigned)K), dim3(EG_COLS), 0, st, m, n_eig, n_rslab, tol, p_rr, p_mm, theta,
@@ -744,7 +773,7 @@ int slod_lod_eigs(slod_handle *h, const double *d_stiffness, const double *d_mas
           hipLaunchKernelGGL(k_eig_gram, dim3((unsigned)std::min(n_gslab, GR_MAX_BLOCKS)), dim3(GR_BLOCK), 0, st, nrow, m, n_gslab, Z, W,
                              V, (size_t)m, partial);
           hipLaunchKernelGGL(k_eig_gram_sum, dim3((unsigned)((2 * mm + 255) / 256)), dim3(256), 0, st, m, n_gslab, partial, G);
-          hipLaunchKernelGGL(k_eig_ritz, dim3(1), dim3(RZ_BLOCK), 0, st, m, G, Q, theta, status, d_done);
+          hipLaunchKernelGGL(k_eig_ritz, dim3(1), dim3(RZ_BLOCK), 0, st, m, G, Q, theta, status, d_done, 0, 0.0);
           hipLaunchKernelGGL(k_eig_rotate, lod_grid(w, RT_MAX_BLOCKS), dim3(RT_BLOCK), 0, st, nrow, m, n_rslab, Z, W, V, Q, theta, status,
                              d_done, (size_t)m, d_x, ld_x, p_rr, p_mm);
           hipLaunchKernelGGL(k_eig_residual, dim3(1), dim3(EG_COLS), 0, st, m, n_eig, n_rslab, tol, p_rr, p_mm, theta, status, res, d_done);
@@ -783,7 +812,7 @@ int slod_lod_eigs_direct(slod_handle *h, slod_lod_factor *f_S, const double *d_s
                          double *residuals)
 {
   int ran = 0;
-  return eigs_direct(h, "slod_lod_eigs_direct", false, f_S, d_stiffness, 1, d_mass, 1, d_cols, 1, n_eig, n_block, start, d_x, ld_x, tol,
+  return eigs_direct(h, "slod_lod_eigs_direct", false, false, 0.0, f_S, d_stiffness, 1, d_mass, 1, d_cols, 1, n_eig, n_block, start, d_x, ld_x, tol,
                      max_outer, eigenvalues, residuals, &ran);
 }
 
@@ -791,8 +820,26 @@ int slod_lod_eigs_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, const do
                                   size_t ld_m_m, const uint32_t *d_cols, int n_members, int n_eig, int n_block, int start, double *d_x,
                                   size_t ld_x, double tol, int max_outer, double *eigenvalues, double *residuals, int *member_status)
 {
-  return eigs_direct(h, "slod_lod_eigs_ensemble_direct", true, f_S, d_stiffness, ld_a_m, d_mass, ld_m_m, d_cols, n_members, n_eig,
+  return eigs_direct(h, "slod_lod_eigs_ensemble_direct", true, false, 0.0, f_S, d_stiffness, ld_a_m, d_mass, ld_m_m, d_cols, n_members, n_eig,
                      n_block, start, d_x, ld_x, tol, max_outer, eigenvalues, residuals, member_status);
+}
+
+int slod_lod_eigs_shift_direct(slod_handle *h, slod_lod_factor *f_S, double sigma, const double *d_stiffness, const double *d_mass,
+                               const uint32_t *d_cols, int n_eig, int n_block, int start, double *d_x, size_t ld_x, double tol,
+                               int max_outer, double *eigenvalues, double *residuals)
+{
+  int ran = 0;
+  return eigs_direct(h, "slod_lod_eigs_shift_direct", false, true, sigma, f_S, d_stiffness, 1, d_mass, 1, d_cols, 1, n_eig, n_block,
+                     start, d_x, ld_x, tol, max_outer, eigenvalues, residuals, &ran);
+}
+
+int slod_lod_eigs_shift_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, double sigma, const double *d_stiffness, size_t ld_a_m,
+                                        const double *d_mass, size_t ld_m_m, const uint32_t *d_cols, int n_members, int n_eig,
+                                        int n_block, int start, double *d_x, size_t ld_x, double tol, int max_outer,
+                                        double *eigenvalues, double *residuals, int *member_status)
+{
+  return eigs_direct(h, "slod_lod_eigs_shift_ensemble_direct", true, true, sigma, f_S, d_stiffness, ld_a_m, d_mass, ld_m_m, d_cols,
+                     n_members, n_eig, n_block, start, d_x, ld_x, tol, max_outer, eigenvalues, residuals, member_status);
 }
 
 } // extern "C"

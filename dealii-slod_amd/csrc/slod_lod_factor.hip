@@ -5,6 +5,10 @@
 //   slod_lod_factor_create_ensemble / _solve_ensemble  the same for the K matrices of a coefficient ensemble: one
 //                            allocation of K copies of the storage below, the same kernels with the member on blockIdx.y
 //                            (a single factor is the ensemble of one member)
+//   slod_lod_factor_create_ldl(_ensemble) / slod_lod_factor_inertia  a second kind of factor in the same storage,
+//                            S = L D L^T without pivoting for a symmetric indefinite S = sym(A) - sigma M, with the signs
+//                            of D and the growth || |L| |D| |L^T| ||_inf / ||S||_inf; the solve dispatches on the kind, so
+//                            every consumer of a factor takes either
 // Ordering: unknown (p, d) has the index r = (cy N + cx) s + d, (cx, cy) the centre cell of p, so the block stencil of a
 // row (slot j = cell offset (j % span, j / span) - span / 2, slod_grid.hip.h) is a band of half width
 // b = s (w N + w) + s - 1, w = 2 l + 1.
@@ -24,6 +28,7 @@
 #include "slod_grid.hip.h"
 #include "slod_common.hip.h"
 
+#include <cmath>
 #include <cstdio>
 #include <vector>
 
@@ -193,9 +198,211 @@ namespace
       out[idx] = sT[idx & 15][idx >> 4];
   }
 
+  // Block column K of  S = L D L^T  (L unit lower triangular, D diagonal, 1 x 1 pivots, no pivoting: a permutation would
+  // destroy the band and the tiles): the launch shape, the operands and the storage of k_factor_column.  Block K + x forms
+  // T = A_rK - sum_J L_rJ D_J L_KJ^T  with the B operand scaled by D_J (piv of the earlier columns), factors the diagonal
+  // tile in LDS without a square root and solves  L_rK = T L_KK^-T D_K^-1  by rows.  diag[K]: L_KK with its unit diagonal,
+  // piv: D (signed), dinv: 1 / D.  status[0]: the index of the first pivot that is zero, infinite or NaN, or -1.
+  __global__ __launch_bounds__(64) void k_ldl_column(int K, int bb, double *band, double *diag, double *piv, double *dinv, int *status,
+                                                    size_t mstride)
+  {
+    __shared__ double sD[FB][FB + 1], sT[FB][FB + 1];
+    band += blockIdx.y * mstride, diag += blockIdx.y * mstride, piv += blockIdx.y * mstride, dinv += blockIdx.y * mstride;
+    status += blockIdx.y;
+    const int bad = status[0];
+    if (bad >= 0 && bad < K * FB) // set by an earlier launch: the same answer in every block
+      return;
+    const int    lane = threadIdx.x, li = lane & 15, lk = lane >> 4;
+    const int    r = K + blockIdx.x, J0 = max(0, K - bb), Jr = max(0, r - bb);
+    const size_t ldb = (size_t)(bb + 1) * FT;
+    auto         tile = [&](int I, int J) { return band + (size_t)I * ldb + (size_t)(I - J) * FT; };
+    // accumulator layout: lane holds D[lk + 4 q][li]
+    double4_t     accD, accT;
+    const double *aD = tile(K, K), *aT = tile(r, K);
+    for (int q = 0; q < 4; ++q)
+      {
+        accD[q] = aD[li * FB + lk + 4 * q];
+        accT[q] = aT[li * FB + lk + 4 * q];
+      }
+    for (int J = J0; J < K; ++J)
+      {
+        const double *lk_ = tile(K, J), *dJ = piv + J * FB;
+        double        ak[4], bk[4];
+        for (int kk = 0; kk < 4; ++kk)
+          {
+            ak[kk] = lk_[(4 * kk + lk) * FB + li]; // as an A operand L_KJ[i][k], as a B operand L_KJ[j][k]
+            bk[kk] = ak[kk] * dJ[4 * kk + lk];     // B[k][j] = D_J[k] L_KJ[j][k]
+          }
+        for (int kk = 0; kk < 4; ++kk)
+          accD = mfma(-ak[kk], bk[kk], accD);
+        if (r != K && J >= Jr)
+          {
+            const double *lr = tile(r, J);
+            for (int kk = 0; kk < 4; ++kk)
+              accT = mfma(-lr[(4 * kk + lk) * FB + li], bk[kk], accT);
+          }
+      }
+    for (int q = 0; q < 4; ++q)
+      {
+        sD[lk + 4 * q][li] = accD[q];
+        sT[lk + 4 * q][li] = accT[q];
+      }
+    __syncthreads();
+    // L D L^T of the diagonal tile: column j of L goes to the lower triangle of sD, the unscaled column w = L d_j to row j of
+    // the upper triangle (the update of entry (i, c) is w_i L_cj), the reciprocal pivot to sD[j][FB]
+    for (int j = 0; j < FB; ++j)
+      {
+        const double p = sD[j][j];
+        // zero, infinite and NaN fail; every comparison is false for NaN
+        const bool   ok = (p > 0.0 && p < HUGE_VAL) || (p < 0.0 && p > -HUGE_VAL);
+        double       dj;
+        if (ok)
+          dj = p;
+        else
+          dj = 1.0;
+        __syncthreads();
+        if (lane == 0)
+          {
+            sD[j][FB] = 1.0 / dj;
+            if (blockIdx.x == 0)
+              {
+                piv[K * FB + j] = p;
+                if (!ok)
+                  {
+                    if (status[0] < 0)
+                      status[0] = K * FB + j;
+                  }
+              }
+          }
+        else if (lane > j && lane < FB)
+          {
+            const double w = sD[lane][j];
+            sD[j][lane]    = w;
+            sD[lane][j]    = w / dj;
+          }
+        __syncthreads();
+        for (int idx = lane; idx < FT; idx += 64)
+          {
+            const int i = idx >> 4, c = idx & 15;
+            if (c > j && i >= c)
+              sD[i][c] = fma(-sD[j][i], sD[c][j], sD[i][c]);
+          }
+        __syncthreads();
+      }
+    double *out = blockIdx.x == 0 ? diag + (size_t)K * FT : tile(r, K);
+    if (blockIdx.x == 0)
+      {
+        for (int idx = lane; idx < FT; idx += 64)
+          {
+            const int c = idx >> 4, i = idx & 15;
+            out[idx]    = i > c ? sD[i][c] : (i == c ? 1.0 : 0.0);
+          }
+        if (lane < FB)
+          dinv[K * FB + lane] = sD[lane][FB];
+        return;
+      }
+    // L_rK D_K L_KK^T = T by rows: lane i < 16 holds row i; y = T L_KK^-T, then the row is scaled by 1 / D_K
+    if (lane < FB)
+      {
+        double y[FB];
+#pragma unroll
+        for (int j = 0; j < FB; ++j)
+          {
+            double v = sT[lane][j];
+#pragma unroll
+            for (int m = 0; m < j; ++m)
+              v = fma(-y[m], sD[j][m], v);
+            y[j] = v;
+          }
+#pragma unroll
+        for (int j = 0; j < FB; ++j)
+          sT[lane][j] = y[j] * sD[j][FB];
+      }
+    __syncthreads();
+    for (int idx = lane; idx < FT; idx += 64)
+      out[idx] = sT[idx & 15][idx >> 4];
+  }
+
+  // The row sums behind the two norms of an LDL^T factor, in factor order: block row (or column) blockIdx.x of member
+  // blockIdx.y, entry i of it on thread (i = tid & 15, part = tid >> 4), which adds the tiles k = part, part + 16, .. in
+  // ascending k and ascending position; the 16 parts are then added in ascending order: fixed sums.
+  //   MODE 0, after k_factor_scatter:  out[r] = sum_c |S_rc|, S the symmetric matrix whose lower triangle is in the band
+  //   MODE 1, after the last column:   out[c] = |D_c| sum_r |L_rc|            = (|D| (|L^T| e))_c
+  //   MODE 2:                          out[r] = sum_c |L_rc| in[c]            = (|L| (|D| (|L^T| e)))_r
+  // k_ldl_norm_max takes the maximum over the n real rows (the padding rows and columns add nothing to a real row).
+  template <int MODE>
+  __global__ __launch_bounds__(256) void k_ldl_norms(int nb, int bb, const double *__restrict__ band, const double *__restrict__ diag,
+                                                    const double *__restrict__ piv, const double *__restrict__ in, double *__restrict__ out,
+                                                    size_t mstride)
+  {
+    __shared__ double sP[16][FB + 1];
+    band += blockIdx.y * mstride, diag += blockIdx.y * mstride, piv += blockIdx.y * mstride, out += blockIdx.y * mstride;
+    if (MODE == 2) // (the other modes read no vector: in is NULL)
+      in += blockIdx.y * mstride;
+    const int     I = blockIdx.x, tid = threadIdx.x, i = tid & 15, part = tid >> 4;
+    const size_t  ldb = (size_t)(bb + 1) * FT;
+    // the diagonal tile: the band's for S (lower triangle; the padding has its unit diagonal), L_II with its unit diagonal
+    const double *dtile = MODE == 0 ? band + (size_t)I * ldb : diag + (size_t)I * FT;
+    auto          reduce = [&](double acc) { // the 16 parts of entry i in ascending order; the sum is valid for tid < 16
+      __syncthreads();
+      sP[part][i] = acc;
+      __syncthreads();
+      double v = 0.0;
+      if (tid < FB)
+        for (int q = 0; q < 16; ++q)
+          v += sP[q][tid];
+      return v;
+    };
+    double v = 0.0;
+    if (MODE != 1) // row i of the block row: the tiles (I, I - k), of the diagonal tile the columns up to the diagonal
+      {
+        double acc = 0.0;
+        for (int k = part; k <= min(bb, I); k += 16)
+          {
+            const double *t = k == 0 ? dtile : band + (size_t)I * ldb + (size_t)k * FT;
+            for (int c = 0; c < (k == 0 ? i + 1 : FB); ++c)
+              acc += fabs(t[c * FB + i]) * (MODE == 2 ? in[(I - k) * FB + c] : 1.0);
+          }
+        v += reduce(acc);
+      }
+    if (MODE != 2) // column i of the block column: the tiles (I + k, I), of the diagonal tile the rows below the diagonal
+      {            // (S: the transposed half of the row) or from it (L: the whole column)
+        double acc = 0.0;
+        for (int k = part; k <= min(bb, nb - 1 - I); k += 16)
+          {
+            const double *t = k == 0 ? dtile : band + (size_t)(I + k) * ldb + (size_t)k * FT;
+            for (int r = k == 0 ? (MODE == 1 ? i : i + 1) : 0; r < FB; ++r)
+              acc += fabs(t[i * FB + r]);
+          }
+        v += reduce(acc);
+      }
+    if (tid < FB)
+      out[I * FB + tid] = MODE == 1 ? fabs(piv[I * FB + tid]) * v : v;
+  }
+
+  // out[0] = max_{r < n} v[r] per member (blockIdx.y); a maximum does not depend on the order it is taken in
+  __global__ __launch_bounds__(256) void k_ldl_norm_max(int n, const double *__restrict__ v, double *__restrict__ out, size_t mstride)
+  {
+    __shared__ double sM[256];
+    v += blockIdx.y * mstride, out += blockIdx.y * mstride;
+    double best = 0.0;
+    for (int r = threadIdx.x; r < n; r += 256)
+      best = fmax(best, v[r]);
+    sM[threadIdx.x] = best;
+    __syncthreads();
+    if (threadIdx.x == 0)
+      {
+        for (int q = 1; q < 256; ++q)
+          best = fmax(best, sM[q]);
+        out[0] = best;
+      }
+  }
+
   // Both sweeps for the 16 columns from blockIdx.x * 16 of the window of member blockIdx.y: its n_rhs columns from
   // blockIdx.y * n_rhs, on its copy of the factor.  rhs and u may be the same array: a block row of rhs is read before the
-  // same rows of u are written, and a block touches its own columns only.
+  // same rows of u are written, and a block touches its own columns only.  LDL: the sweeps on a factor of k_ldl_column,
+  // L y = b with the unit diagonal, then L^T x = D^-1 y: the block row of y is scaled by 1 / D as the backward sweep loads it.
+  template <bool LDL>
   __global__ __launch_bounds__(256) void k_factor_solve(int nb, int bb, const double *__restrict__ band, const double *__restrict__ diag,
                                                        const double *__restrict__ dinv, size_t mstride, const int *__restrict__ rowmap,
                                                        int n_rhs, const double *rhs, size_t ld_rhs, double *u, size_t ld_u)
@@ -222,7 +429,7 @@ namespace
           double4_t     acc = {0.0, 0.0, 0.0, 0.0};
           if (wave == 0)
             for (int q = 0; q < 4; ++q)
-              acc[q] = load(src, ld_src, I, lk + 4 * q);
+              acc[q] = LDL && sweep == 1 ? load(src, ld_src, I, lk + 4 * q) * dinv[I * FB + lk + 4 * q] : load(src, ld_src, I, lk + 4 * q);
           for (int k = 1 + wave; k <= nk; k += 4)
             {
               // forward: tile (I, I - k) times X_{I-k}; backward: tile (I + k, I) transposed times X_{I+k}
@@ -253,7 +460,7 @@ namespace
 #pragma unroll
                       for (int m = 0; m < i; ++m)
                         v = fma(-sL[i][m], x[m], v);
-                      x[i] = v * dinv[I * FB + i];
+                      x[i] = LDL ? v : v * dinv[I * FB + i];
                     }
                 }
               else
@@ -265,7 +472,7 @@ namespace
 #pragma unroll
                       for (int m = FB - 1; m > i; --m)
                         v = fma(-sL[m][i], x[m], v);
-                      x[i] = v * dinv[I * FB + i];
+                      x[i] = LDL ? v : v * dinv[I * FB + i];
                     }
                 }
               if (c0 + tid < n_rhs)
@@ -288,8 +495,13 @@ void slod_lod_factor_solve_launch(const slod_lod_factor *f, hipStream_t st, cons
                                   size_t ld_u, int first_member, int n_members)
 {
   const size_t first = (size_t)first_member * f->member_doubles;
-  hipLaunchKernelGGL(k_factor_solve, dim3((unsigned)((n_rhs + FB - 1) / FB), (unsigned)n_members), dim3(256), 0, st, f->nb, f->bb,
-                     f->band + first, f->diag + first, f->dinv + first, f->member_doubles, f->rowmap, n_rhs, d_rhs, ld_rhs, d_u, ld_u);
+  const dim3   grid((unsigned)((n_rhs + FB - 1) / FB), (unsigned)n_members);
+  if (f->kind == SLOD_FACTOR_LDL)
+    hipLaunchKernelGGL(k_factor_solve<true>, grid, dim3(256), 0, st, f->nb, f->bb, f->band + first, f->diag + first, f->dinv + first,
+                       f->member_doubles, f->rowmap, n_rhs, d_rhs, ld_rhs, d_u, ld_u);
+  else
+    hipLaunchKernelGGL(k_factor_solve<false>, grid, dim3(256), 0, st, f->nb, f->bb, f->band + first, f->diag + first, f->dinv + first,
+                       f->member_doubles, f->rowmap, n_rhs, d_rhs, ld_rhs, d_u, ld_u);
 }
 
 int slod_lod_factor_check(const slod_handle *h, const char *who, const slod_lod_factor *f, int n_members)
@@ -307,8 +519,10 @@ namespace
 {
   constexpr int MAX_MEMBERS = 65535; // members sit on blockIdx.y
 
-  // slod_lod_factor_create is the call with ld_m = 1, n_members = 1 and no bad_pivot; arguments are checked by the caller
-  int factor_create(slod_handle *h, const char *who, bool ensemble, const double *d_values, size_t ld_m, int n_members,
+  // slod_lod_factor_create is the call with ld_m = 1, n_members = 1 and no bad_pivot; arguments are checked by the caller.
+  // kind SLOD_FACTOR_LDL: the same storage with two norms behind a member's pivots and two work vectors behind its dinv,
+  // k_ldl_column in place of k_factor_column, k_ldl_norms / k_ldl_norm_max before the first and after the last column.
+  int factor_create(slod_handle *h, const char *who, bool ensemble, int kind, const double *d_values, size_t ld_m, int n_members,
                     const uint32_t *d_cols, int32_t *bad_pivot, slod_lod_factor **out)
   {
     hipStream_t st;
@@ -318,6 +532,7 @@ namespace
     const int      s = G.spacedim, w = 2 * G.oversampling + 1, cap = slod_lod_row_capacity(h);
     slod_lod_factor f;
     f.h         = h;
+    f.kind      = kind;
     f.n         = h->NP * s;
     f.b         = s * (w * G.N + w) + s - 1;
     f.nb        = (f.n + FB - 1) / FB;
@@ -325,7 +540,9 @@ namespace
     f.n_members = n_members;
     // one allocation: per member the band, the factored diagonal tiles, the pivots and the reciprocal diagonal of L, then
     // the row map and the status words
-    const size_t npad = (size_t)f.nb * FB, nband = (size_t)f.nb * (f.bb + 1) * FT, nd = nband + (size_t)f.nb * FT + 2 * npad;
+    const bool   ldl = kind == SLOD_FACTOR_LDL;
+    const size_t npad = (size_t)f.nb * FB, nband = (size_t)f.nb * (f.bb + 1) * FT, nread = npad + (ldl ? 2 : 0);
+    const size_t nd = nband + (size_t)f.nb * FT + nread + npad + (ldl ? 2 * npad : 0);
     const size_t K    = (size_t)n_members;
     f.member_doubles  = nd;
     f.bytes           = K * nd * sizeof(double) + (npad + K) * sizeof(int);
@@ -335,10 +552,10 @@ namespace
     f.band   = (double *)f.mem.get();
     f.diag   = f.band + nband;
     f.piv    = f.diag + (size_t)f.nb * FT;
-    f.dinv   = f.piv + npad;
+    f.dinv   = f.piv + nread;
     f.rowmap = (int *)(f.band + K * nd);
     f.status = f.rowmap + npad;
-    std::vector<double> piv(K * npad);
+    std::vector<double> piv(K * nread);
     std::vector<int>    bad(K, -1);
     e = hipMemsetAsync(f.band, 0, K * nd * sizeof(double), st);
     if (e == hipSuccess)
@@ -350,15 +567,35 @@ namespace
                            f.rowmap, f.band, nd);
         hipLaunchKernelGGL(k_factor_scatter, dim3((unsigned)((nval * K + 255) / 256)), dim3(256), 0, st, G, h->NP, cap, f.bb, n_members,
                            d_values, ld_m, d_cols, f.band, nd);
+        // LDL^T only: the two norms behind a member's pivots, two vectors of row sums behind its dinv
+        double    *norms = f.piv + npad, *work = f.dinv + npad, *work2 = work + npad;
+        const dim3 rows_grid((unsigned)f.nb, (unsigned)K);
+        if (ldl)
+          {
+            hipLaunchKernelGGL(k_ldl_norms<0>, rows_grid, dim3(256), 0, st, f.nb, f.bb, f.band, f.diag, f.piv, nullptr, work, nd);
+            hipLaunchKernelGGL(k_ldl_norm_max, dim3(1, (unsigned)K), dim3(256), 0, st, f.n, work, norms, nd);
+          }
         for (int col = 0; col < f.nb; ++col)
-          hipLaunchKernelGGL(k_factor_column, dim3((unsigned)(std::min(f.bb, f.nb - 1 - col) + 1), (unsigned)K), dim3(64), 0, st, col, f.bb,
-                             f.band, f.diag, f.piv, f.dinv, f.status, nd);
+          {
+            const dim3 grid((unsigned)(std::min(f.bb, f.nb - 1 - col) + 1), (unsigned)K);
+            if (ldl)
+              hipLaunchKernelGGL(k_ldl_column, grid, dim3(64), 0, st, col, f.bb, f.band, f.diag, f.piv, f.dinv, f.status, nd);
+            else
+              hipLaunchKernelGGL(k_factor_column, grid, dim3(64), 0, st, col, f.bb, f.band, f.diag, f.piv, f.dinv, f.status, nd);
+          }
+        if (ldl) // (a member that failed has not finished its factor: its second norm is not used)
+          {
+            hipLaunchKernelGGL(k_ldl_norms<1>, rows_grid, dim3(256), 0, st, f.nb, f.bb, f.band, f.diag, f.piv, nullptr, work, nd);
+            hipLaunchKernelGGL(k_ldl_norms<2>, rows_grid, dim3(256), 0, st, f.nb, f.bb, f.band, f.diag, f.piv, work, work2, nd);
+            hipLaunchKernelGGL(k_ldl_norm_max, dim3(1, (unsigned)K), dim3(256), 0, st, f.n, work2, norms + 1, nd);
+          }
         e = hipGetLastError();
       }
-    // one read-back: the pivots of every member (npad doubles every nd) and the status words
+    // one read-back: the pivots of every member (npad doubles every nd; behind them the two norms of an LDL^T factor) and
+    // the status words
     if (e == hipSuccess)
-      e = hipMemcpy2DAsync(piv.data(), npad * sizeof(double), f.piv, nd * sizeof(double), npad * sizeof(double), K, hipMemcpyDeviceToHost,
-                           st);
+      e = hipMemcpy2DAsync(piv.data(), nread * sizeof(double), f.piv, nd * sizeof(double), nread * sizeof(double), K,
+                           hipMemcpyDeviceToHost, st);
     if (e == hipSuccess)
       e = hipMemcpyAsync(bad.data(), f.status, K * sizeof(int), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess)
@@ -373,20 +610,35 @@ namespace
     for (size_t k = 0; k < K; ++k)
       if (bad[k] >= 0)
         {
-          char msg[200];
+          char        msg[200], member[40] = "";
+          const char *what = ldl ? "is zero or not finite" : "is not positive";
+          const char *why  = ldl ? "" : ": the matrix is not positive definite";
           if (ensemble)
-            std::snprintf(msg, sizeof msg, "%s: member %zu: pivot %d of %d is not positive (%g): the matrix is not positive definite", who,
-                          k, bad[k], f.n, piv[k * npad + (size_t)bad[k]]);
-          else
-            std::snprintf(msg, sizeof msg, "%s: pivot %d of %d is not positive (%g): the matrix is not positive definite", who, bad[k],
-                          f.n, piv[(size_t)bad[k]]);
+            std::snprintf(member, sizeof member, "member %zu: ", k);
+          std::snprintf(msg, sizeof msg, "%s: %spivot %d of %d %s (%g)%s", who, member, bad[k], f.n, what, piv[k * nread + (size_t)bad[k]],
+                        why);
           return slod_fail(h, SLOD_ERR_NUMERIC, msg);
         }
     f.member_min.resize(K), f.member_max.resize(K);
+    if (ldl)
+      f.inertia.resize(K);
     for (size_t k = 0; k < K; ++k)
       {
-        f.member_min[k] = *std::min_element(piv.begin() + k * npad, piv.begin() + k * npad + f.n);
-        f.member_max[k] = *std::max_element(piv.begin() + k * npad, piv.begin() + k * npad + f.n);
+        const double *d = piv.data() + k * nread;
+        f.member_min[k] = *std::min_element(d, d + f.n);
+        f.member_max[k] = *std::max_element(d, d + f.n);
+        if (!ldl)
+          continue;
+        slod_lod_factor_inertia_host &in = f.inertia[k];
+        in.min_abs = in.max_abs = std::fabs(d[0]);
+        for (int r = 0; r < f.n; ++r)
+          {
+            (d[r] < 0.0 ? in.n_negative : in.n_positive) += 1;
+            in.min_abs = std::min(in.min_abs, std::fabs(d[r]));
+            in.max_abs = std::max(in.max_abs, std::fabs(d[r]));
+          }
+        in.norm_matrix = d[npad];
+        in.norm_factor = d[npad + 1];
       }
     f.min_pivot = *std::min_element(f.member_min.begin(), f.member_min.end());
     f.max_pivot = *std::max_element(f.member_max.begin(), f.member_max.end());
@@ -406,13 +658,24 @@ int slod_lod_factor_create(slod_handle *h, const double *d_values, const uint32_
     return SLOD_ERR_ARGUMENT;
   if (!d_values || !d_cols || !out)
     return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_factor_create: NULL array or out");
-  return factor_create(h, "slod_lod_factor_create", false, d_values, 1, 1, d_cols, nullptr, out);
+  return factor_create(h, "slod_lod_factor_create", false, SLOD_FACTOR_CHOLESKY, d_values, 1, 1, d_cols, nullptr, out);
 }
 
-int slod_lod_factor_create_ensemble(slod_handle *h, const double *d_values, size_t ld_m, int n_members, const uint32_t *d_cols,
-                                    int32_t *bad_pivot, slod_lod_factor **out)
+int slod_lod_factor_create_ldl(slod_handle *h, const double *d_values, const uint32_t *d_cols, slod_lod_factor **out)
 {
-  const char *who = "slod_lod_factor_create_ensemble";
+  if (out)
+    *out = nullptr;
+  if (!h)
+    return SLOD_ERR_ARGUMENT;
+  if (!d_values || !d_cols || !out)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_factor_create_ldl: NULL array or out");
+  return factor_create(h, "slod_lod_factor_create_ldl", false, SLOD_FACTOR_LDL, d_values, 1, 1, d_cols, nullptr, out);
+}
+
+// the body of the two ensemble create calls: their argument checks, then factor_create
+static int factor_create_ensemble(const char *who, int kind, slod_handle *h, const double *d_values, size_t ld_m, int n_members,
+                                  const uint32_t *d_cols, int32_t *bad_pivot, slod_lod_factor **out)
+{
   if (out)
     *out = nullptr;
   if (!h || !d_values || !d_cols || !out)
@@ -421,7 +684,40 @@ int slod_lod_factor_create_ensemble(slod_handle *h, const double *d_values, size
     return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": n_members < 1 or > 65535");
   if (const int rc = slod_check_ld(h, who, "n_members", n_members, {ld_m}))
     return rc;
-  return factor_create(h, who, true, d_values, ld_m, n_members, d_cols, bad_pivot, out);
+  return factor_create(h, who, true, kind, d_values, ld_m, n_members, d_cols, bad_pivot, out);
+}
+
+int slod_lod_factor_create_ensemble(slod_handle *h, const double *d_values, size_t ld_m, int n_members, const uint32_t *d_cols,
+                                    int32_t *bad_pivot, slod_lod_factor **out)
+{
+  return factor_create_ensemble("slod_lod_factor_create_ensemble", SLOD_FACTOR_CHOLESKY, h, d_values, ld_m, n_members, d_cols, bad_pivot,
+                                out);
+}
+
+int slod_lod_factor_create_ldl_ensemble(slod_handle *h, const double *d_values, size_t ld_m, int n_members, const uint32_t *d_cols,
+                                        int32_t *bad_pivot, slod_lod_factor **out)
+{
+  return factor_create_ensemble("slod_lod_factor_create_ldl_ensemble", SLOD_FACTOR_LDL, h, d_values, ld_m, n_members, d_cols, bad_pivot,
+                                out);
+}
+
+int slod_lod_factor_inertia(const slod_lod_factor *f, int member, slod_lod_factor_inertia_info *out)
+{
+  const char *who = "slod_lod_factor_inertia";
+  if (!f || !out)
+    return slod_fail(nullptr, SLOD_ERR_ARGUMENT, std::string(who) + ": NULL factor or out"); // (the factor is not read)
+  if (member < 0 || member >= f->n_members)
+    return slod_fail(f->h, SLOD_ERR_ARGUMENT, std::string(who) + ": no such member");
+  if (f->kind != SLOD_FACTOR_LDL)
+    return slod_fail(f->h, SLOD_ERR_ARGUMENT, std::string(who) + ": a Cholesky factor has no inertia to report; use slod_lod_factor_create_ldl");
+  const slod_lod_factor_inertia_host &in = f->inertia[(size_t)member];
+  out->n_negative    = in.n_negative;
+  out->n_positive    = in.n_positive;
+  out->min_abs_pivot = in.min_abs;
+  out->max_abs_pivot = in.max_abs;
+  out->norm_matrix   = in.norm_matrix;
+  out->norm_factor   = in.norm_factor;
+  return SLOD_OK;
 }
 
 int slod_lod_factor_get_info(const slod_lod_factor *f, slod_lod_factor_info *info)

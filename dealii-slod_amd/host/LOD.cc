@@ -719,6 +719,18 @@ namespace slod
   template <int dim, int spacedim>
   void LOD<dim, spacedim>::solve_eigenproblem_ensemble(const unsigned int n_eig, const double sigma)
   {
+    eigenproblem_ensemble(n_eig, sigma, false, false);
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_eigenproblem_ensemble_near(const double sigma, const unsigned int n_eig, const bool ldl)
+  {
+    eigenproblem_ensemble(n_eig, sigma, true, ldl);
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::eigenproblem_ensemble(const unsigned int n_eig, const double sigma, const bool near, const bool ldl)
+  {
     if (!d_ens_mass)
       throw std::runtime_error("solve_eigenproblem_ensemble: assemble_mass_matrix_ensemble comes first");
     const int          K = (int)par.n_members;
@@ -748,17 +760,27 @@ namespace slod
         d_S = d_ens_shifted;
       }
     slod_lod_factor *f = nullptr;
-    check(slod_lod_factor_create_ensemble(handle, d_S, ld, K, d_ens_cols, nullptr, &f), "slod_lod_factor_create_ensemble");
+    if (ldl)
+      check(slod_lod_factor_create_ldl_ensemble(handle, d_S, ld, K, d_ens_cols, nullptr, &f), "slod_lod_factor_create_ldl_ensemble");
+    else
+      check(slod_lod_factor_create_ensemble(handle, d_S, ld, K, d_ens_cols, nullptr, &f), "slod_lod_factor_create_ensemble");
     factors.push_back(f);
     check(slod_lod_factor_get_info(f, &lod_factor_info), "slod_lod_factor_get_info");
+    ens_factor_inertia.assign(ldl ? K : 0, slod_lod_factor_inertia_info{});
+    for (int k = 0; k < (ldl ? K : 0); ++k)
+      check(slod_lod_factor_inertia(f, k, &ens_factor_inertia[k]), "slod_lod_factor_inertia");
     ens_eig_block = n_block;
     ens_eigenvalues.assign((std::size_t)K * n_block, 0.0);
     ens_eig_residuals.assign((std::size_t)K * n_block, 0.0);
     ens_eig_outer.assign(K, 0);
-    const int rc = slod_lod_eigs_ensemble_direct(handle, f, d_ens_sym, ld, d_ens_mass, ld, d_ens_cols, K, (int)n_eig, n_block, 0, d_x,
-                                                 ld * n_block, 1e-10, max_outer, ens_eigenvalues.data(), ens_eig_residuals.data(),
-                                                 ens_eig_outer.data());
-    check(rc < 0 ? rc : 0, "slod_lod_eigs_ensemble_direct");
+    const int rc =
+      near ? slod_lod_eigs_shift_ensemble_direct(handle, f, sigma, d_ens_sym, ld, d_ens_mass, ld, d_ens_cols, K, (int)n_eig, n_block, 0,
+                                                 d_x, ld * n_block, 1e-10, max_outer, ens_eigenvalues.data(),
+                                                 ens_eig_residuals.data(), ens_eig_outer.data()) :
+             slod_lod_eigs_ensemble_direct(handle, f, d_ens_sym, ld, d_ens_mass, ld, d_ens_cols, K, (int)n_eig, n_block, 0, d_x,
+                                           ld * n_block, 1e-10, max_outer, ens_eigenvalues.data(), ens_eig_residuals.data(),
+                                           ens_eig_outer.data());
+    check(rc < 0 ? rc : 0, near ? "slod_lod_eigs_shift_ensemble_direct" : "slod_lod_eigs_ensemble_direct");
   }
 
   template <int dim, int spacedim>
@@ -792,12 +814,17 @@ namespace slod
   }
 
   template <int dim, int spacedim>
-  slod_lod_factor *LOD<dim, spacedim>::factor_lod_matrix(const double *d_values)
+  slod_lod_factor *LOD<dim, spacedim>::factor_lod_matrix(const double *d_values, const bool ldl)
   {
     slod_lod_factor *f = nullptr;
-    check(slod_lod_factor_create(handle, d_values, d_lod_cols, &f), "slod_lod_factor_create");
+    if (ldl)
+      check(slod_lod_factor_create_ldl(handle, d_values, d_lod_cols, &f), "slod_lod_factor_create_ldl");
+    else
+      check(slod_lod_factor_create(handle, d_values, d_lod_cols, &f), "slod_lod_factor_create");
     factors.push_back(f);
     check(slod_lod_factor_get_info(f, &lod_factor_info), "slod_lod_factor_get_info");
+    if (ldl)
+      check(slod_lod_factor_inertia(f, 0, &lod_factor_inertia), "slod_lod_factor_inertia");
     return f;
   }
 
@@ -863,6 +890,19 @@ namespace slod
   template <int dim, int spacedim>
   void LOD<dim, spacedim>::solve_eigenproblem(const unsigned int n_eig, const bool direct, const double sigma)
   {
+    eigenproblem(n_eig, direct, sigma, false, false);
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_eigenproblem_near(const double sigma, const unsigned int n_eig, const bool ldl)
+  {
+    eigenproblem(n_eig, true, sigma, true, ldl);
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::eigenproblem(const unsigned int n_eig, const bool direct, const double sigma, const bool near,
+                                        const bool ldl)
+  {
     if (!d_lod_mass)
       throw std::runtime_error("solve_eigenproblem: assemble_global_matrix and assemble_mass_matrix come first");
     const unsigned int n_patches = (unsigned int)patches.size();
@@ -898,10 +938,13 @@ namespace slod
           }
         if (hipDeviceSynchronize() != hipSuccess)
           throw std::runtime_error("solve_eigenproblem: forming S failed");
-        slod_lod_factor *f = factor_lod_matrix(d_S);
-        outer              = slod_lod_eigs_direct(handle, f, d_lod_sym, d_lod_mass, d_lod_cols, (int)n_eig, n_block, 0, d_eig_x,
-                                                  (std::size_t)n_block, 1e-10, max_outer, lod_eigenvalues.data(), lod_eig_residuals.data());
-        check(outer < 0 ? outer : 0, "slod_lod_eigs_direct");
+        slod_lod_factor *f = factor_lod_matrix(d_S, ldl);
+        outer = near ? slod_lod_eigs_shift_direct(handle, f, sigma, d_lod_sym, d_lod_mass, d_lod_cols, (int)n_eig, n_block, 0, d_eig_x,
+                                                  (std::size_t)n_block, 1e-10, max_outer, lod_eigenvalues.data(),
+                                                  lod_eig_residuals.data()) :
+                       slod_lod_eigs_direct(handle, f, d_lod_sym, d_lod_mass, d_lod_cols, (int)n_eig, n_block, 0, d_eig_x,
+                                            (std::size_t)n_block, 1e-10, max_outer, lod_eigenvalues.data(), lod_eig_residuals.data());
+        check(outer < 0 ? outer : 0, near ? "slod_lod_eigs_shift_direct" : "slod_lod_eigs_direct");
         lod_eig_inner_iterations.clear();
       }
     else

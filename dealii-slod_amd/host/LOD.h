@@ -134,8 +134,11 @@ namespace slod
     // The banded Cholesky factor of a symmetric positive definite matrix on the pattern of A_LOD (device values in the
     // layout of slod_lod_matrix): slod_lod_factor_create; the object owns the factor and frees it with itself.
     // last_factor_info() describes the factor made last.
-    slod_lod_factor            *factor_lod_matrix(const double *d_values);
+    // ldl: the banded LDL^T factor of a symmetric, possibly indefinite matrix instead (slod_lod_factor_create_ldl, no
+    // pivoting); last_factor_inertia() then holds the signs of D, ||S||_inf and || |L||D||L^T| ||_inf of member 0.
+    slod_lod_factor            *factor_lod_matrix(const double *d_values, const bool ldl = false);
     const slod_lod_factor_info &last_factor_info() const { return lod_factor_info; }
+    const slod_lod_factor_inertia_info &last_factor_inertia() const { return lod_factor_inertia; }
     const std::vector<int>    &heat_iterations() const { return lod_heat_iterations; }
     const std::vector<double> &heat_rel_residuals() const { return lod_heat_residuals; }
     // norms of C u_H - C u_heat: the final state against the elliptic SLOD solution of solve(), and of C u_H alone
@@ -150,6 +153,11 @@ namespace slod
     // factor_lod_matrix, slod_lod_eigs_direct); sigma must lie below the lowest eigenvalue (the factorisation fails
     // otherwise), there are no inner iteration counts, and eigen_outer_iterations() is the count of the outer ones.
     void solve_eigenproblem(const unsigned int n_eig, const bool direct = false, const double sigma = 0.0);
+    // The n_eig eigenpairs NEAREST sigma, which may lie inside the spectrum: S = sym(A_LOD) - sigma M_LOD factored by LDL^T
+    // (ldl; a Cholesky factor serves when S is definite) and slod_lod_eigs_shift_direct from its hashed start block, with
+    // the defaults of solve_eigenproblem.  eigenvalues() are in order of distance from sigma; last_factor_inertia() gives
+    // the number of eigenvalues below sigma and the growth of the factor.
+    void solve_eigenproblem_near(const double sigma, const unsigned int n_eig, const bool ldl = true);
     int  eigen_outer_iterations() const { return lod_eig_outer; }
     const std::vector<double>           &eigenvalues() const { return lod_eigenvalues; }   // all block columns
     const std::vector<double>           &eigen_residuals() const { return lod_eig_residuals; }
@@ -210,6 +218,10 @@ namespace slod
     // outer count are those of solve_eigenproblem(.., true, sigma) of a problem with member k's coefficient.
     // last_factor_info() is the range over all members.
     void solve_eigenproblem_ensemble(const unsigned int n_eig, const double sigma = 0.0);
+    // solve_eigenproblem_near for all members at once, one sigma for all (slod_lod_factor_create_ldl_ensemble,
+    // slod_lod_eigs_shift_ensemble_direct); factor_inertia_ensemble()[k] is member k's inertia and growth.
+    void solve_eigenproblem_ensemble_near(const double sigma, const unsigned int n_eig, const bool ldl = true);
+    const std::vector<slod_lod_factor_inertia_info> &factor_inertia_ensemble() const { return ens_factor_inertia; }
     // [member * n_block + column], n_block = eigen_ensemble_block(); [member]
     const std::vector<double> &eigenvalues_ensemble() const { return ens_eigenvalues; }
     const std::vector<double> &eigen_residuals_ensemble() const { return ens_eig_residuals; }
@@ -305,6 +317,7 @@ namespace slod
     // factor_lod_matrix: the factors this object owns, the matrix S of a direct time loop
     std::vector<slod_lod_factor *> factors;
     slod_lod_factor_info           lod_factor_info{};
+    slod_lod_factor_inertia_info   lod_factor_inertia{};
     double                        *d_lod_shifted = nullptr;
     // solve_multi: fine load vectors and reconstructions, field k at + k * fine_size
     double                       *d_multi_fem_rhs = nullptr, *d_multi_fine = nullptr;
@@ -329,6 +342,10 @@ namespace slod
     std::vector<double> ens_eigenvalues, ens_eig_residuals;
     std::vector<int>    ens_eig_outer;
     int                 ens_eig_block = 0;
+    std::vector<slod_lod_factor_inertia_info> ens_factor_inertia;
+    // the bodies of solve_eigenproblem / _near and of their ensemble forms: near orders the pairs by distance from sigma
+    void eigenproblem(const unsigned int n_eig, const bool direct, const double sigma, const bool near, const bool ldl);
+    void eigenproblem_ensemble(const unsigned int n_eig, const double sigma, const bool near, const bool ldl);
     // mean and standard deviation of n_members fine fields: slod_ensemble_moments, the square root on the host, the norms
     void ensemble_moment_norms(const double *d_fine, double *d_mean, double *d_var, slod_error_norms &mean, slod_error_norms &dev);
 

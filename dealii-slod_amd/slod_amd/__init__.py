@@ -53,6 +53,17 @@ class FactorInfo(C.Structure):
                 ("min_pivot", C.c_double), ("max_pivot", C.c_double)]
 
 
+class InertiaInfo(C.Structure):
+    """slod_lod_factor_inertia_info: signs of D of an LDL^T factor, its pivot range in absolute value, ||S||_inf and
+    || |L||D||L^T| ||_inf (their ratio is the growth)."""
+    _fields_ = [("n_negative", C.c_int32), ("n_positive", C.c_int32), ("min_abs_pivot", C.c_double),
+                ("max_abs_pivot", C.c_double), ("norm_matrix", C.c_double), ("norm_factor", C.c_double)]
+
+    @property
+    def growth(self):
+        return self.norm_factor / self.norm_matrix
+
+
 _lib = None
 
 
@@ -175,6 +186,14 @@ def load():
     lib.slod_lod_eigs_direct.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, C.c_double, C.c_int, dp, dp]
     lib.slod_lod_eigs_ensemble_direct.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                                   vp, C.c_size_t, C.c_double, C.c_int, dp, dp, C.POINTER(C.c_int)]
+    lib.slod_lod_factor_create_ldl.argtypes = [vp, vp, vp, C.POINTER(vp)]
+    lib.slod_lod_factor_create_ldl_ensemble.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(vp)]
+    lib.slod_lod_factor_inertia.argtypes = [vp, C.c_int, C.POINTER(InertiaInfo)]
+    lib.slod_lod_eigs_shift_direct.argtypes = [vp, vp, C.c_double, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_size_t,
+                                               C.c_double, C.c_int, dp, dp]
+    lib.slod_lod_eigs_shift_ensemble_direct.argtypes = [vp, vp, C.c_double, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_int, C.c_int,
+                                                        C.c_int, C.c_int, vp, C.c_size_t, C.c_double, C.c_int, dp, dp,
+                                                        C.POINTER(C.c_int)]
     lib.slod_update_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, C.c_int, C.c_size_t, C.c_int, vp]
     lib.slod_dirty_patches.argtypes = [vp, vp, u32p, C.c_size_t]
     lib.slod_plan_create_dirty.argtypes = [vp, C.c_uint32, vp, C.POINTER(vp)]
@@ -339,12 +358,14 @@ class Plan:
 
 
 class Factor:
-    """slod_lod_factor: the banded Cholesky factor of a full set of block rows; factor once, solve many."""
+    """slod_lod_factor: the banded Cholesky factor of a full set of block rows; factor once, solve many.  ldl=True: the
+    banded LDL^T factor of a symmetric, possibly indefinite matrix (slod_lod_factor_create_ldl), with .inertia()."""
 
-    def __init__(self, slod, d_values, d_cols):
+    def __init__(self, slod, d_values, d_cols, ldl=False):
         self.slod, self.lib = slod, slod.lib
         self.f = C.c_void_p()
-        slod._check(self.lib.slod_lod_factor_create(slod.h, d_values, d_cols, C.byref(self.f)))
+        create = self.lib.slod_lod_factor_create_ldl if ldl else self.lib.slod_lod_factor_create
+        slod._check(create(slod.h, d_values, d_cols, C.byref(self.f)))
         self.info = FactorInfo()
         slod._check(self.lib.slod_lod_factor_get_info(self.f, C.byref(self.info)))
         slod._factors.add(self)                        # the handle closes its factors before itself
@@ -353,6 +374,13 @@ class Factor:
         """U = A^-1 RHS on coarse multi-vectors (ld defaults to n_rhs); d_u may be d_rhs.  Asynchronous."""
         self.slod._check(self.lib.slod_lod_factor_solve(self.f, d_rhs, n_rhs if ld_rhs is None else ld_rhs, n_rhs, d_u,
                                                         n_rhs if ld_u is None else ld_u, stream))
+
+    def inertia(self, member=0):
+        """slod_lod_factor_inertia of an LDL^T factor: InertiaInfo (n_negative, n_positive, min_abs_pivot, max_abs_pivot,
+        norm_matrix, norm_factor, .growth).  SlodError(-1) on a Cholesky factor."""
+        info = InertiaInfo()
+        self.slod._check(self.lib.slod_lod_factor_inertia(self.f, member, C.byref(info)))
+        return info
 
     def close(self):
         if self.f:
@@ -371,12 +399,13 @@ class EnsembleFactor(Factor):
     .member_info(k) that of member k, .bad_pivot the first non-positive pivot per member (-1 everywhere on success).
     When a member fails, SlodError(-5) carries .bad_pivot; drop those members and factor again."""
 
-    def __init__(self, slod, d_values, d_cols, n_members, ld_m=None):
+    def __init__(self, slod, d_values, d_cols, n_members, ld_m=None, ldl=False):
         self.slod, self.lib, self.n_members = slod, slod.lib, n_members
         self.f = C.c_void_p()
         self.bad_pivot = np.full(max(n_members, 1), -1, dtype=np.int32)
-        rc = self.lib.slod_lod_factor_create_ensemble(slod.h, d_values, n_members if ld_m is None else ld_m, n_members, d_cols,
-                                                      self.bad_pivot.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(self.f))
+        create = self.lib.slod_lod_factor_create_ldl_ensemble if ldl else self.lib.slod_lod_factor_create_ensemble
+        rc = create(slod.h, d_values, n_members if ld_m is None else ld_m, n_members, d_cols,
+                    self.bad_pivot.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(self.f))
         if rc:
             err = SlodError(rc, self.lib.slod_last_error(slod.h).decode())
             err.bad_pivot = self.bad_pivot[:max(n_members, 0)].copy()
@@ -396,6 +425,9 @@ class EnsembleFactor(Factor):
         K = self.n_members - first_member if n_members is None else n_members
         self.slod._check(self.lib.slod_lod_factor_solve_ensemble(self.f, first_member, K, d_rhs, K * n_rhs if ld_rhs is None else ld_rhs,
                                                                  n_rhs, d_u, K * n_rhs if ld_u is None else ld_u, stream))
+
+
+LodFactor = Factor   # the name of the object in the documents of the LDL^T factor: .inertia(member=0)
 
 
 def _factor_ptr(f):
@@ -659,6 +691,11 @@ class Slod:
         SlodError(-5) when a pivot is not positive."""
         return Factor(self, d_values, d_cols)
 
+    def lod_factor_ldl(self, d_values, d_cols):
+        """The LDL^T factor (no pivoting) of a symmetric matrix in block rows, indefinite or not: a Factor whose .info has
+        the signed range of D and whose .inertia() counts the signs of D and measures the growth."""
+        return Factor(self, d_values, d_cols, ldl=True)
+
     def lod_theta_steps_direct(self, factor, d_stiffness, d_cols, dt, theta, n_steps, d_u, n_rhs=1, ld_u=None, d_load=None,
                                ld_load=None, load_step_stride=0):
         """lod_theta_steps on the factor of S = M + theta dt A (lod_matrix_combine(1, M, theta * dt, A))."""
@@ -762,6 +799,10 @@ class Slod:
         """The Cholesky factors of the members of an ensemble matrix in one object (EnsembleFactor)."""
         return EnsembleFactor(self, d_values, d_cols, n_members, ld_m)
 
+    def lod_factor_ldl_ensemble(self, d_values, d_cols, n_members, ld_m=None):
+        """The LDL^T factors of the members of an ensemble matrix in one object (EnsembleFactor, .inertia(member))."""
+        return EnsembleFactor(self, d_values, d_cols, n_members, ld_m, ldl=True)
+
     def lod_theta_steps_ensemble_direct(self, factor, d_stiffness, d_cols, dt, theta, n_steps, n_members, d_u, ld_m=None,
                                         ld_u=None, d_load=None, ld_load=None, load_step_stride=0):
         """lod_theta_steps_direct with a column, a matrix and a factor per member; the factor is that of
@@ -834,6 +875,40 @@ class Slod:
         status = np.zeros(shape[0], dtype=np.intc)
         rc = self.lib.slod_lod_eigs_ensemble_direct(
             self.h, _factor_ptr(factor), d_stiffness, n_members if ld_a_m is None else ld_a_m, d_mass,
+            n_members if ld_m_m is None else ld_m_m, d_cols, n_members, n_eig, n_block, start, d_x,
+            n_members * n_block if ld_x is None else ld_x, tol, max_outer, _dp(lam), _dp(res),
+            status.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc < 0 and (check or rc != -5):
+            self._check(rc)
+        return lam, res, status, rc
+
+    # ---- eigenpairs nearest a shift sigma, on a factor of S = sym(A) - sigma M (LDL^T for an interior sigma) ----
+    def lod_eigs_shift_direct(self, factor, sigma, d_stiffness, d_mass, d_cols, n_eig, d_x, n_block=None, ld_x=None, start=0,
+                              tol=1e-10, max_outer=200):
+        """lod_eigs_direct with the Ritz pairs ordered by their distance from sigma: the first n_eig columns are the pairs
+        nearest sigma.  start=0 writes the hashed block of include/slod.h.  Returns (eigenvalues[n_block],
+        residuals[n_block], outer iterations)."""
+        if n_block is None:
+            n_block = min(64, self.num_patches * self.spacedim, n_eig + max(4, n_eig // 2))
+        lam = np.zeros(max(n_block, 1))
+        res = np.zeros(max(n_block, 1))
+        rc = self.lib.slod_lod_eigs_shift_direct(self.h, _factor_ptr(factor), sigma, d_stiffness, d_mass, d_cols, n_eig, n_block,
+                                                 start, d_x, n_block if ld_x is None else ld_x, tol, max_outer, _dp(lam), _dp(res))
+        if rc < 0:
+            self._check(rc)
+        return lam[:n_block], res[:n_block], rc
+
+    def lod_eigs_shift_ensemble_direct(self, factor, sigma, d_stiffness, d_mass, d_cols, n_members, n_eig, d_x, n_block=None,
+                                       ld_a_m=None, ld_m_m=None, ld_x=None, start=0, tol=1e-10, max_outer=200, check=True):
+        """lod_eigs_shift_direct for the pencils of an ensemble, one sigma for all members; layout and returns of
+        lod_eigs_ensemble_direct."""
+        if n_block is None:
+            n_block = min(64, self.num_patches * self.spacedim, n_eig + max(4, n_eig // 2))
+        shape = (max(n_members, 1), max(n_block, 1))
+        lam, res = np.zeros(shape), np.zeros(shape)
+        status = np.zeros(shape[0], dtype=np.intc)
+        rc = self.lib.slod_lod_eigs_shift_ensemble_direct(
+            self.h, _factor_ptr(factor), sigma, d_stiffness, n_members if ld_a_m is None else ld_a_m, d_mass,
             n_members if ld_m_m is None else ld_m_m, d_cols, n_members, n_eig, n_block, start, d_x,
             n_members * n_block if ld_x is None else ld_x, tol, max_outer, _dp(lam), _dp(res),
             status.ctypes.data_as(C.POINTER(C.c_int)))

@@ -454,7 +454,8 @@ typedef struct
 {
   int32_t  n, half_bandwidth, block; /* rows; b above; the edge of the square tiles of the band (16)                  */
   uint64_t bytes;                    /* device bytes the factor owns                                                  */
-  double   min_pivot, max_pivot;     /* the smallest and largest diagonal entry of L, squared                         */
+  double   min_pivot, max_pivot;     /* the smallest and largest diagonal entry of L, squared; of an LDL^T factor (below)
+                                        the smallest and largest entry of D, signed                                   */
 } slod_lod_factor_info;
 /* Factors a symmetric positive definite matrix given as a full set of block rows (rows 0 .. num_patches-1 in the layout
  * of slod_lod_matrix: the output of slod_lod_matrix_symmetrize, slod_lod_mass_matrix, or a slod_lod_matrix_combine of
@@ -479,6 +480,43 @@ int slod_lod_factor_solve(slod_lod_factor *f, const double *d_rhs, size_t ld_rhs
                           void *hip_stream);
 /* Waits for the handle's stream, then frees the factor.  NULL is allowed. */
 void slod_lod_factor_destroy(slod_lod_factor *f);
+/* ---- banded LDL^T: symmetric indefinite matrices, inertia ---------------------------------------
+ * S = L D L^T, L unit lower triangular, D diagonal, 1 x 1 pivots, NO PIVOTING, in the band storage, the ordering and the
+ * launch shape of slod_lod_factor_create (a permutation would destroy the band; LAPACK has no banded symmetric indefinite
+ * routine either).  Meant for  S = sym(A) - sigma M  with sigma inside the spectrum (slod_lod_matrix_combine(1, sym A,
+ * -sigma, M)): Helmholtz-type systems, shift-and-invert, and the count of eigenvalues below sigma.  Without pivoting the
+ * factorisation is backward stable only relative to  G = || |L| |D| |L^T| ||_inf  in place of ||S||_inf; the factor
+ * measures G (slod_lod_factor_inertia) so that the caller can judge it: a solve has a backward error of about
+ * (3 (b + 1) + 1) (b + 1) 2^-53 G / ||S||_inf relative to ||S||_inf.
+ * Every call that takes a factor takes an LDL^T factor unchanged: slod_lod_factor_solve and _solve_ensemble (L y = b,
+ * L^T x = D^-1 y, the same fixed order of summation: the bits of a column depend on the factor and that column only),
+ * slod_lod_theta_steps_direct, slod_lod_newmark_accel_direct, slod_lod_newmark_steps_direct and their _ensemble forms,
+ * slod_lod_eigs_direct and slod_lod_eigs_ensemble_direct (their duty sigma < lambda_1 stays; with an interior shift use
+ * slod_lod_eigs_shift_direct below).
+ * slod_lod_factor_get_info(_member) reports min_pivot / max_pivot as the smallest and largest entry of D, signed.
+ * SLOD_ERR_NUMERIC: a pivot is zero, infinite or NaN; slod_last_error reads
+ *   "<call>: [member k: ]pivot r of n is zero or not finite (value)";
+ * *out stays NULL and nothing stays allocated.  The other returns, and bad_pivot of the ensemble form, are
+ * those of slod_lod_factor_create / slod_lod_factor_create_ensemble; member k's factor has the bits of
+ * slod_lod_factor_create_ldl on its de-interleaved matrix. */
+int slod_lod_factor_create_ldl(slod_handle *h, const double *d_values, const uint32_t *d_cols, slod_lod_factor **out);
+int slod_lod_factor_create_ldl_ensemble(slod_handle *h, const double *d_values, size_t ld_m, int n_members,
+                                        const uint32_t *d_cols, int32_t *bad_pivot /* HOST [n_members], may be NULL */,
+                                        slod_lod_factor **out);
+typedef struct
+{
+  int32_t n_negative, n_positive;     /* signs of D over the n real rows; n_negative = eigenvalues of (A, M) below sigma
+                                         when S = sym(A) - sigma M and M is positive definite (Sylvester)            */
+  double  min_abs_pivot, max_abs_pivot;
+  double  norm_matrix, norm_factor;   /* ||S||_inf and || |L||D||L^T| ||_inf; their ratio is the growth              */
+} slod_lod_factor_inertia_info;
+/* The inertia and the growth of member `member` of an LDL^T factor (a single factor has the member 0), from the read-back
+ * of the create call: no device work.  norm_matrix is the row-sum norm of the symmetric matrix whose lower triangle was
+ * read, norm_factor = max_i (|L| (|D| (|L^T| e)))_i, both over the n real rows in factor order with fixed-order sums.
+ * norm_factor is an ORDER-OF-MAGNITUDE DIAGNOSTIC, promised to a factor of 2.  A growth norm_factor / norm_matrix above
+ * about 1 / (b eps), b the half bandwidth, means that sigma sits on an eigenvalue of a leading sub-pencil (in factor order):
+ * move the shift.  SLOD_ERR_ARGUMENT: NULL factor or out, member < 0 or >= the factor's members, a Cholesky factor. */
+int slod_lod_factor_inertia(const slod_lod_factor *f, int member, slod_lod_factor_inertia_info *out);
 /* The recursions of slod_lod_theta_steps, slod_lod_newmark_accel and slod_lod_newmark_steps (above, the same elementwise,
  * product and energy kernels) with the solve of a step done by slod_lod_factor_solve on a factor the caller built:
  *   slod_lod_theta_steps_direct    f_S factors  S = slod_lod_matrix_combine(1, M, theta dt, A)
@@ -692,8 +730,8 @@ int slod_lod_newmark_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S,
  * Outer iteration k = 1, 2, ..:  Y = M X;  S Z = Y on the factor;  W = A Z, V = M Z;  Ga = sym(Z^T W), Gm = sym(Z^T V);
  * the Ritz step;  X = Z Q;  res_j as documented for slod_lod_eigs;  stop when res_j <= tol for all j < n_eig or at
  * k = max_outer (not an error).  The Gram, Ritz, rotate and residual kernels are those of slod_lod_eigs; the products run
- * the fma chain of slod_lod_apply_multi.  Not built: LDL^T and eigenvalues near an interior sigma, LOBPCG, locking of
- * converged columns, n_block > 64. */
+ * the fma chain of slod_lod_apply_multi.  An LDL^T factor (slod_lod_factor_create_ldl) is taken as well.  Not built: LOBPCG,
+ * locking of converged columns, n_block > 64. */
 /* One pencil.  Arguments as in slod_lod_eigs, less the inner parameters.  Returns the number of outer iterations run
  * (>= 1) or a negative slod_status.  SLOD_ERR_NUMERIC: rank-deficient block as in slod_lod_eigs; d_x then holds the block
  * the failed iteration started from, eigenvalues and residuals those of the last completed iteration (0 if none).
@@ -738,6 +776,35 @@ int slod_lod_eigs_ensemble_direct(slod_handle *h, slod_lod_factor *f_S,
                                   double *eigenvalues   /* HOST [n_members * n_block] */,
                                   double *residuals     /* HOST [n_members * n_block] */,
                                   int    *member_status /* HOST [n_members] */);
+/* ---- eigenpairs nearest an interior shift --------------------------------------------------------
+ * slod_lod_eigs_direct / slod_lod_eigs_ensemble_direct with one more argument, sigma, which may lie anywhere outside the
+ * spectrum's points: f_S factors  S = sym(A) - sigma M  (slod_lod_factor_create_ldl(_ensemble); a Cholesky factor is taken
+ * too when S is definite).  The outer iteration, the Gram, rotate and residual kernels, the done words, the read-backs and
+ * member_status are those calls'; after the Ritz step the columns are ordered by |theta_j - sigma| ascending, ties by
+ * ascending theta_j, then by index.  So columns j < n_eig hold the pairs NEAREST sigma, they are the ones tested against
+ * tol, and the guard columns are the ones farthest from sigma.  Column j contracts by about
+ * |lambda_(j) - sigma| / |lambda_(m+1) - sigma| per outer iteration, the eigenvalues taken in order of distance from sigma.
+ * That the number of eigenvalues below sigma is slod_lod_factor_inertia's n_negative lets a caller check that none was
+ * missed.  The ensemble form takes one sigma for all members.
+ * start = 1 takes the caller's block.  start = 0 writes a hashed block (the sine block of slod_lod_eigs starts in the lowest
+ * modes, the wrong end for an interior shift), the same for every member: entry (caller's row i = p s + d, column j) is
+ *   z = ((uint64) i << 32 | j) + 0x9E3779B97F4A7C15;
+ *   z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;   z = (z ^ z >> 27) * 0x94D049BB133111EB;   z ^= z >> 31;
+ *   x = (double) (z >> 11) * 2^-52 - 1        (all in uint64 arithmetic, x in [-1, 1))
+ * SLOD_ERR_ARGUMENT: what the _direct calls refuse, and sigma NaN or infinite (checked before the factor). */
+int slod_lod_eigs_shift_direct(slod_handle *h, slod_lod_factor *f_S, double sigma,
+                               const double *d_stiffness, const double *d_mass, const uint32_t *d_cols,
+                               int n_eig, int n_block, int start, double *d_x, size_t ld_x,
+                               double tol, int max_outer,
+                               double *eigenvalues /* HOST [n_block] */,
+                               double *residuals   /* HOST [n_block] */);
+int slod_lod_eigs_shift_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, double sigma,
+                                        const double *d_stiffness, size_t ld_a_m, const double *d_mass, size_t ld_m_m,
+                                        const uint32_t *d_cols, int n_members, int n_eig, int n_block, int start,
+                                        double *d_x, size_t ld_x, double tol, int max_outer,
+                                        double *eigenvalues   /* HOST [n_members * n_block] */,
+                                        double *residuals     /* HOST [n_members * n_block] */,
+                                        int    *member_status /* HOST [n_members] */);
 
 /* ---- refresh after a local coefficient change ----------------------------------------------
  * Every entry point above takes the coefficient as fixed for the life of a basis (the reference does too: one
