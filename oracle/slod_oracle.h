@@ -18,6 +18,11 @@
  * Numbering: all per-patch vectors are in PATCH-LEXICOGRAPHIC node order,
  * component-minor: dof = spacedim*(ix + iy*(nx+1)) + comp, ix in [0,nx], iy in [0,ny],
  * nx = n_sub*mx fine elements across the patch.
+ *
+ * Two libraries come from the one source: libslod_oracle.so (working precision double, the
+ * fp64 oracle) and libslod_oracle_q.so (-DSO_QUAD, working precision __float128, iteration
+ * thresholds scaled to it): the truth against which the fp64 oracle's own error is measured.
+ * This API is the same in both: double in, double out, rounded once on return.
  */
 #ifndef SLOD_ORACLE_H
 #define SLOD_ORACLE_H
@@ -57,6 +62,12 @@ typedef struct
   double dinf[2];          /* final ||d||_inf                                             */
   double sigma_max[2], sigma_min[2]; /* singular values of G = BD'^T BD'                  */
   double cond_hint;
+  /* margins of the decisions, computed in the library's working precision:
+   * margin_cut  = min_j |log10(sig_j / (1e-15 sigma_max))| (decades to the cutoff),
+   * margin_half = min |  ||d||_inf - 0.5 | over the values the 0.5-loop tested.
+   * svd_mode 2 on its QR path has no singular values: sigma_* = 0 and margin_cut is the lower
+   * bound |log10(1e15 / kF^2)|.  LOD-branch patches decide nothing: both are +inf. */
+  double margin_cut[2], margin_half[2];
 } so_diag;
 
 /* ---- index calculus ---------------------------------------------------- */
@@ -109,7 +120,10 @@ int  so_patch_debug(const so_cfg *cfg, const double *const *coef, int pid,
 void so_patch_pt(const so_cfg *cfg, int pid, double *PT);
 
 /* 0 (default): one-sided Jacobi SVD of BD'; 1: literal Gram matrix G = BD'^T BD' +
- * Jacobi eigen-solver (LOD.cc:660-667 with dgesdd replaced). */
+ * Jacobi eigen-solver (LOD.cc:660-667 with dgesdd replaced); 2: the device's organisation of
+ * the selection, restated from the header of slod_select.hip.h: Householder QR of [BD' | b0],
+ * d = -R^-1 c where that provably takes the reference's decisions, else column-pivoted QR and a
+ * one-sided Jacobi on R. */
 void so_set_svd_mode(int mode);
 /* conditioning probe for the parity tests: relative noise eps on X before the selection stage
  * (0 = off); see slod_oracle.c */

@@ -11,6 +11,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libslod_oracle.so")
+_QUAD_PATH = os.path.join(_HERE, "libslod_oracle_q.so")
 
 
 class Cfg(C.Structure):
@@ -28,14 +29,42 @@ class Patch(C.Structure):
 class Diag(C.Structure):
     _fields_ = [("n_dropped", C.c_int * 2), ("n_cut", C.c_int * 2), ("dinf", C.c_double * 2),
                 ("sigma_max", C.c_double * 2), ("sigma_min", C.c_double * 2),
-                ("cond_hint", C.c_double)]
+                ("cond_hint", C.c_double),
+                ("margin_cut", C.c_double * 2), ("margin_half", C.c_double * 2)]
 
 
 def build(force=False):
-    src = os.path.join(_HERE, "slod_oracle.c")
-    if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < os.path.getmtime(src):
+    """Builds both libraries (the Makefile's default target): the fp64 oracle and its quad twin."""
+    src = [os.path.join(_HERE, f) for f in ("slod_oracle.c", "slod_oracle.h", "Makefile")]
+    newest = max(os.path.getmtime(f) for f in src)
+    if force or any(not os.path.exists(l) or os.path.getmtime(l) < newest for l in (_LIB_PATH, _QUAD_PATH)):
         subprocess.check_call(["make", "-C", _HERE, "-s", "-B"])
     return _LIB_PATH
+
+
+def _bind(path):
+    l = C.CDLL(path)
+    dp = C.POINTER(C.c_double)
+    l.so_patch_basis.argtypes = [C.POINTER(Cfg), C.POINTER(dp), C.c_int, dp, dp, C.POINTER(Diag)]
+    l.so_patch_debug.argtypes = [C.POINTER(Cfg), C.POINTER(dp), C.c_int, dp, dp, dp,
+                                 C.POINTER(C.c_int), dp]
+    l.so_basis_many.argtypes = [C.POINTER(Cfg), C.POINTER(dp), C.POINTER(C.c_int), C.c_int, dp, dp,
+                                C.POINTER(C.c_longlong), C.c_int]
+    l.so_assemble_patch.argtypes = [C.POINTER(Cfg), C.POINTER(Patch), C.POINTER(dp), dp]
+    l.so_solve_interior.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, C.c_int, dp]
+    l.so_patch_solve.argtypes = [C.POINTER(Cfg), C.POINTER(Patch), dp, dp]
+    l.so_fill_coefficient.argtypes = [C.c_ulonglong, C.c_int, C.c_double, C.c_double, C.c_int, dp]
+    l.so_fill_coefficient_rand.argtypes = [C.c_double, C.c_double, C.c_int, C.c_int, dp]
+    l.so_local_matrix_poisson.argtypes = [dp, dp]
+    l.so_local_matrix_elasticity.argtypes = [dp, dp, dp]
+    l.so_fe_q_iso_q1_cell_matrix.argtypes = [C.c_int, C.c_int, dp]
+    l.so_patch_init.argtypes = [C.POINTER(Cfg), C.c_int, C.POINTER(Patch)]
+    l.so_patch_cells.argtypes = [C.POINTER(Cfg), C.POINTER(Patch), C.POINTER(C.c_int)]
+    l.so_num_patches.argtypes = [C.POINTER(Cfg)]
+    l.so_set_svd_mode.argtypes = [C.c_int]
+    l.so_patch_pt.argtypes = [C.POINTER(Cfg), C.c_int, dp]
+    l.so_set_solver_noise.argtypes = [C.c_double, C.c_ulonglong]
+    return l
 
 
 _lib = None
@@ -45,27 +74,7 @@ def lib():
     global _lib
     if _lib is None:
         build()
-        _lib = C.CDLL(_LIB_PATH)
-        dp = C.POINTER(C.c_double)
-        _lib.so_patch_basis.argtypes = [C.POINTER(Cfg), C.POINTER(dp), C.c_int, dp, dp, C.POINTER(Diag)]
-        _lib.so_patch_debug.argtypes = [C.POINTER(Cfg), C.POINTER(dp), C.c_int, dp, dp, dp,
-                                        C.POINTER(C.c_int), dp]
-        _lib.so_basis_many.argtypes = [C.POINTER(Cfg), C.POINTER(dp), C.POINTER(C.c_int), C.c_int, dp, dp,
-                                       C.POINTER(C.c_longlong), C.c_int]
-        _lib.so_assemble_patch.argtypes = [C.POINTER(Cfg), C.POINTER(Patch), C.POINTER(dp), dp]
-        _lib.so_solve_interior.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, C.c_int, dp]
-        _lib.so_patch_solve.argtypes = [C.POINTER(Cfg), C.POINTER(Patch), dp, dp]
-        _lib.so_fill_coefficient.argtypes = [C.c_ulonglong, C.c_int, C.c_double, C.c_double, C.c_int, dp]
-        _lib.so_fill_coefficient_rand.argtypes = [C.c_double, C.c_double, C.c_int, C.c_int, dp]
-        _lib.so_local_matrix_poisson.argtypes = [dp, dp]
-        _lib.so_local_matrix_elasticity.argtypes = [dp, dp, dp]
-        _lib.so_fe_q_iso_q1_cell_matrix.argtypes = [C.c_int, C.c_int, dp]
-        _lib.so_patch_init.argtypes = [C.POINTER(Cfg), C.c_int, C.POINTER(Patch)]
-        _lib.so_patch_cells.argtypes = [C.POINTER(Cfg), C.POINTER(Patch), C.POINTER(C.c_int)]
-        _lib.so_num_patches.argtypes = [C.POINTER(Cfg)]
-        _lib.so_set_svd_mode.argtypes = [C.c_int]
-        _lib.so_patch_pt.argtypes = [C.POINTER(Cfg), C.c_int, dp]
-        _lib.so_set_solver_noise.argtypes = [C.c_double, C.c_ulonglong]
+        _lib = _bind(_LIB_PATH)
     return _lib
 
 
@@ -86,10 +95,14 @@ def num_patches(cfg):
     return lib().so_num_patches(C.byref(cfg))
 
 
-def patch_info(cfg, pid):
+def _patch_info(l, cfg, pid):
     p = Patch()
-    lib().so_patch_init(C.byref(cfg), pid, C.byref(p))
+    l.so_patch_init(C.byref(cfg), pid, C.byref(p))
     return p
+
+
+def patch_info(cfg, pid):
+    return _patch_info(lib(), cfg, pid)
 
 
 def patch_cells(cfg, pid):
@@ -122,56 +135,72 @@ def fill_coefficient_rand(lo, hi, r, n_elems, seed=1):
     return out
 
 
-def patch_basis(cfg, coefs, pid):
-    """-> (phi[s, n_f], psi[s, n_f], Diag)."""
-    p = patch_info(cfg, pid)
+def _patch_basis(l, cfg, coefs, pid):
+    p = _patch_info(l, cfg, pid)
     s = cfg.spacedim
     phi = np.zeros((s, p.n_f))
     psi = np.zeros((s, p.n_f))
     d = Diag()
     keep, ptrs = _coef_ptrs(coefs)
-    rc = lib().so_patch_basis(C.byref(cfg), ptrs, pid, _dp(phi), _dp(psi), C.byref(d))
+    rc = l.so_patch_basis(C.byref(cfg), ptrs, pid, _dp(phi), _dp(psi), C.byref(d))
     if rc:
         raise RuntimeError("so_patch_basis failed rc=%d" % rc)
     return phi, psi, d
 
 
-def patch_debug(cfg, coefs, pid):
-    p = patch_info(cfg, pid)
+def patch_basis(cfg, coefs, pid):
+    """-> (phi[s, n_f], psi[s, n_f], Diag)."""
+    return _patch_basis(lib(), cfg, coefs, pid)
+
+
+def _patch_debug(l, cfg, coefs, pid):
+    p = _patch_info(l, cfg, pid)
     M = np.zeros((p.n_c, p.n_c))
     D = np.zeros((p.n_c, p.n_c))
     BD = np.zeros((max(p.n_b, 1), p.n_c))
     X = np.zeros((p.n_f, p.n_c))
     bd = (C.c_int * max(p.n_b, 1))()
     keep, ptrs = _coef_ptrs(coefs)
-    rc = lib().so_patch_debug(C.byref(cfg), ptrs, pid, _dp(M), _dp(D), _dp(BD), bd, _dp(X))
+    rc = l.so_patch_debug(C.byref(cfg), ptrs, pid, _dp(M), _dp(D), _dp(BD), bd, _dp(X))
     if rc:
         raise RuntimeError("so_patch_debug failed rc=%d" % rc)
     return dict(M=M, D=D, BD=BD[:p.n_b], bdofs=np.array(list(bd)[:p.n_b]), X=X)
 
 
-def basis_many(cfg, coefs, ids, offsets, total, nthreads=1):
+def patch_debug(cfg, coefs, pid):
+    return _patch_debug(lib(), cfg, coefs, pid)
+
+
+def _basis_many(l, cfg, coefs, ids, offsets, total, nthreads=1):
     ids = np.ascontiguousarray(ids, dtype=np.int32)
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     phi = np.zeros(total)
     psi = np.zeros(total)
     keep, ptrs = _coef_ptrs(coefs)
-    rc = lib().so_basis_many(C.byref(cfg), ptrs, ids.ctypes.data_as(C.POINTER(C.c_int)), len(ids),
-                             _dp(phi), _dp(psi), offsets.ctypes.data_as(C.POINTER(C.c_longlong)),
-                             nthreads)
+    rc = l.so_basis_many(C.byref(cfg), ptrs, ids.ctypes.data_as(C.POINTER(C.c_int)), len(ids),
+                         _dp(phi), _dp(psi), offsets.ctypes.data_as(C.POINTER(C.c_longlong)),
+                         nthreads)
     if rc:
         raise RuntimeError("so_basis_many failed rc=%d" % rc)
     return phi, psi
 
 
-def assemble_patch(cfg, coefs, pid):
-    """-> stencil[n_nodes, 9, s, s]"""
-    p = patch_info(cfg, pid)
+def basis_many(cfg, coefs, ids, offsets, total, nthreads=1):
+    return _basis_many(lib(), cfg, coefs, ids, offsets, total, nthreads)
+
+
+def _assemble_patch(l, cfg, coefs, pid):
+    p = _patch_info(l, cfg, pid)
     s = cfg.spacedim
     st = np.zeros((p.n_f // s, 9, s, s))
     keep, ptrs = _coef_ptrs(coefs)
-    lib().so_assemble_patch(C.byref(cfg), C.byref(p), ptrs, _dp(st))
+    l.so_assemble_patch(C.byref(cfg), C.byref(p), ptrs, _dp(st))
     return st
+
+
+def assemble_patch(cfg, coefs, pid):
+    """-> stencil[n_nodes, 9, s, s]"""
+    return _assemble_patch(lib(), cfg, coefs, pid)
 
 
 def solve_interior(nx, ny, s, stencil, rhs):
@@ -237,3 +266,44 @@ def patch_pt(cfg, pid):
     PT = np.zeros((p.n_f, p.n_c))
     lib().so_patch_pt(C.byref(cfg), pid, _dp(PT))
     return PT
+
+
+class _Quad:
+    """The same calls bound to libslod_oracle_q.so: the oracle with __float128 as its working precision
+    and iteration thresholds scaled to it.  Arguments and results are float64 (rounded once on return);
+    the svd mode and the solver noise of this library are its own, separate from the fp64 oracle's."""
+
+    def __init__(self):
+        build()
+        self._l = _bind(_QUAD_PATH)
+
+    make_cfg = staticmethod(make_cfg)
+
+    def patch_info(self, cfg, pid):
+        return _patch_info(self._l, cfg, pid)
+
+    def patch_basis(self, cfg, coefs, pid):
+        return _patch_basis(self._l, cfg, coefs, pid)
+
+    def patch_debug(self, cfg, coefs, pid):
+        return _patch_debug(self._l, cfg, coefs, pid)
+
+    def assemble_patch(self, cfg, coefs, pid):
+        return _assemble_patch(self._l, cfg, coefs, pid)
+
+    def basis_many(self, cfg, coefs, ids, offsets, total, nthreads=1):
+        return _basis_many(self._l, cfg, coefs, ids, offsets, total, nthreads)
+
+    def set_svd_mode(self, mode):
+        self._l.so_set_svd_mode(mode)
+
+
+_quad = None
+
+
+def quad():
+    """-> the quad-precision oracle (built on first use; raises if it cannot be built)."""
+    global _quad
+    if _quad is None:
+        _quad = _Quad()
+    return _quad
