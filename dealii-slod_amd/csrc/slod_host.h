@@ -252,4 +252,94 @@ void slod_lod_factor_solve_launch(const slod_lod_factor *f, hipStream_t st, cons
 // SLOD_ERR_ARGUMENT, "<who>: NULL factor", "<who>: factor of another handle / row count" or "<who>: factor of another
 // member count" (the time loops on one matrix take a factor of one member); else SLOD_OK
 int slod_lod_factor_check(const slod_handle *h, const char *who, const slod_lod_factor *f, int n_members = 1);
+// ---- what the loops of the LOD space (slod_lod_time.hip, slod_lod_wave.hip) are written on, once per scheme
+// The operator of a column of a coarse multi-vector: one matrix for all columns, or (per_col) for column k member k of an
+// ensemble matrix with leading dimension ld_m (include/slod.h).
+struct SlodLodOperator
+{
+  const double *values;
+  size_t        ld_m = 1;
+  bool          per_col = false;
+};
+// Y = A X with the operator of every column: k_lod_apply (slod_lod_time.hip) or k_ens_apply (slod_lod_ensemble.hip)
+inline void slod_lod_apply_launch(const slod_handle *h, hipStream_t st, const SlodLodOperator &A, const uint32_t *d_cols,
+                                  const double *d_x, size_t ld_x, int n, double *d_y, size_t ld_y)
+{
+  if (A.per_col)
+    slod_lod_apply_ensemble_launch(h, st, A.values, A.ld_m, d_cols, d_x, ld_x, n, d_y, ld_y);
+  else
+    slod_lod_apply_launch(h, st, A.values, d_cols, d_x, ld_x, n, d_y, ld_y);
+}
+// slod_check_ld for the n columns of a loop: below "n_rhs", or with a member per column below "n_members", the
+// matrices' ld_m first
+inline int slod_check_ld_of(const slod_handle *h, const char *who, bool per_col, std::initializer_list<size_t> ld_m, int n,
+                            std::initializer_list<size_t> lds)
+{
+  const char *what = per_col ? "n_members" : "n_rhs";
+  if (const int rc = per_col ? slod_check_ld(h, who, what, n, ld_m) : SLOD_OK)
+    return rc;
+  return slod_check_ld(h, who, what, n, lds);
+}
+// How a loop solves  S u = rhs  on its n columns: the recurrence of slod_lod_solve_multi, or the two sweeps of a factor the
+// caller built, with all columns on its one member or with column k on member k.  The checks of a scheme take the kind
+// for the wording of its call: an ensemble call names the handle among its NULL arguments and counts members.
+enum SlodLodSolveKind { SLOD_SOLVE_CG, SLOD_SOLVE_FACTOR, SLOD_SOLVE_FACTOR_PER_COL };
+// The solve of a step and the one device allocation of the loop around it.  A loop on a factor is queued whole: solve()
+// only launches, and nothing of the CG workspace or of its active flags is allocated.
+struct SlodLodStepSolve
+{
+  SlodLodSolveKind kind;
+  slod_lod_factor *f = nullptr; // on a factor: the caller's
+  // CG: the matrix (a loop that builds S in its workspace sets it after alloc), the stopping rule, and the HOST arrays
+  // [n_steps], either may be NULL, where solve(k, ..) records step k
+  const uint32_t    *d_cols = nullptr;
+  const double      *S = nullptr;
+  double             rel_tol = 0.0;
+  int                max_iterations = 0;
+  int               *iterations = nullptr;
+  double            *rel_residual = nullptr;
+  SlodLodWork        work; // CG: the workspace; its last, worst and report() are those of the solves (0 on a factor)
+  SlodDevBuf<double> buf;  // on a factor: the pieces of the loop
+
+  bool cg() const { return kind == SLOD_SOLVE_CG; }
+  // carve(SlodCarver &) names the pieces of the loop and calls take() where those of the solve go, as SlodLodWork::alloc:
+  // CG that allocation (two hipMalloc), else one SlodDevBuf
+  template <typename Carve>
+  hipError_t alloc(int n, Carve &&carve)
+  {
+    if (cg())
+      return work.alloc(n, carve);
+    SlodCarver count, hand;
+    carve(count);
+    const hipError_t e = buf.alloc(count.used);
+    if (e != hipSuccess)
+      return e;
+    hand.base = buf.get();
+    carve(hand);
+    return hipSuccess;
+  }
+  void take(SlodCarver &c, const slod_handle *h)
+  {
+    if (cg())
+      work.take_solve(c, h);
+  }
+  // u = S^-1 rhs for the n columns, the solve of step k.  CG: every column from zero; synchronises h->stream (= st), then
+  // records the iterations and the residual of step k.  Factor: launches on st; a failed launch shows at the caller's
+  // next hipGetLastError.
+  hipError_t solve(slod_handle *h, hipStream_t st, int k, int n, const double *d_rhs, size_t ld_rhs, double *d_u, size_t ld_u)
+  {
+    if (cg())
+      {
+        const hipError_t e = work.solve(h, S, d_cols, d_rhs, ld_rhs, d_u, ld_u, rel_tol, max_iterations);
+        if (e == hipSuccess)
+          work.record(k, iterations, rel_residual);
+        return e;
+      }
+    if (kind == SLOD_SOLVE_FACTOR_PER_COL)
+      slod_lod_factor_solve_launch(f, st, d_rhs, ld_rhs, 1, d_u, ld_u, 0, n);
+    else
+      slod_lod_factor_solve_launch(f, st, d_rhs, ld_rhs, n, d_u, ld_u);
+    return hipSuccess;
+  }
+};
 #endif

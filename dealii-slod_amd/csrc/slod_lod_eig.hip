@@ -15,6 +15,9 @@
 // The kernels of this file carry the member on blockIdx.y: member k works on columns k m .. k m + m - 1 of the block
 // vectors and on its own partials, G, Q, theta, residuals, status and done word.  A single pencil is the ensemble of one
 // member.  k_eig_apply is the product of a member's matrix with its m columns.
+// The CG path and the paths on a factor share the workspace layout (EigSpace), the start block (eig_start_launch), the
+// five launches of the Rayleigh-Ritz pass (eig_ritz_pass), the common argument checks (eig_check) and the text of
+// SLOD_ERR_NUMERIC (eig_rank_message); product, inner solve, stop rule and read-back are each path's own.
 #include "slod_lod_system.hip.h"
 #include "slod_lod_tile.hip.h"
 
@@ -553,6 +556,92 @@ namespace
     return md;
   }
 
+  // ---------------------------------------------------------------------------------
+  // What the CG path (slod_lod_eigs) and the paths on a factor (eigs_direct) share.  Each keeps its own product
+  // (k_lod_apply or k_eig_apply), its own stop rule (the host's test of the residuals, or the done words of the device)
+  // and its own read-back.
+  // ---------------------------------------------------------------------------------
+  // The checks both paths make, in their order.  inner: the CG path, which looks at ld_x right behind n_block and names
+  // the tolerance and the limit of its inner solve along with the outer ones.
+  int eig_check(const slod_handle *h, const std::string &who, int n_eig, int n_block, int start, double tol, int max_outer,
+                bool inner = false, size_t ld_x = 0, double inner_rel_tol = 1.0, int inner_max_iterations = 0)
+  {
+    if (n_eig < 1 || n_block < n_eig)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, who + ": n_eig < 1 or n_block < n_eig");
+    if (n_block > EG_COLS || n_block > h->NP * h->cfg.spacedim)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, who + ": n_block above 64 or above the number of rows");
+    if (inner)
+      if (const int rc = slod_check_ld(h, who.c_str(), "n_block", n_block, {ld_x}))
+        return rc;
+    if (start != 0 && start != 1)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, who + ": start is neither 0 nor 1");
+    if (!(tol > 0.0) || !(inner_rel_tol > 0.0))
+      return slod_fail(h, SLOD_ERR_ARGUMENT, who + (inner ? ": tol or inner_rel_tol is not positive" : ": tol is not positive"));
+    if (max_outer < 1 || inner_max_iterations < 0)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, who + (inner ? ": max_outer < 1 or inner_max_iterations < 0" : ": max_outer < 1"));
+    return SLOD_OK;
+  }
+
+  // The device arrays of the outer iteration for K members of m columns each (one pencil: K = 1): Y, Z, W, V of K m
+  // columns, per member the slab partials, Ga | Gm and Q, then theta | residuals | status | done of all members
+  // (consecutive: the host reads them in one copy; the ints of the members in whole doubles)
+  struct EigSpace
+  {
+    int     nrow, m, K, n_gslab, n_rslab; // n_rslab: the groups of lod_shape are the slabs of k_eig_rotate and k_eig_apply
+    size_t  ldw, nint;
+    double *Y, *Z, *W, *V, *partial, *G, *Q, *p_rr, *p_mm, *theta, *res;
+    int    *status, *d_done;
+    EigSpace(const LodShape &w, int m, int K)
+      : nrow(w.nrow), m(m), K(K), n_gslab((w.nrow + GR_ROWS - 1) / GR_ROWS), n_rslab(w.ngroup), ldw((size_t)K * m), nint(((size_t)K + 1) / 2)
+    {}
+    void carve(SlodCarver &c)
+    {
+      const size_t nvec = (size_t)nrow * ldw, mm = (size_t)m * m;
+      Y = c.take(nvec), Z = c.take(nvec), W = c.take(nvec), V = c.take(nvec);
+      partial = c.take(K * 2 * mm * n_gslab), G = c.take(K * 2 * mm), Q = c.take(K * mm);
+      p_rr = c.take(ldw * n_rslab), p_mm = c.take(ldw * n_rslab);
+      theta = c.take(ldw), res = c.take(ldw), status = (int *)c.take(nint), d_done = (int *)c.take(nint);
+    }
+  };
+
+  // start = 0: the library's start block in the m columns of every member, sine modes or (hashed) the hashed block
+  void eig_start_launch(const slod_handle *h, hipStream_t st, bool hashed, int m, int K, double *d_x, size_t ld_x)
+  {
+    const int  s = h->cfg.spacedim, nrow = h->NP * s;
+    const dim3 grid((unsigned)(((size_t)nrow * m + 255) / 256), (unsigned)K);
+    if (hashed)
+      hipLaunchKernelGGL(k_eig_start_hash, grid, dim3(256), 0, st, nrow, m, d_x, ld_x);
+    else
+      hipLaunchKernelGGL(k_eig_start, grid, dim3(256), 0, st, slod_grid_of(h), h->NP, s, m, eig_sine_modes(h, m), d_x, ld_x);
+  }
+
+  // The Rayleigh-Ritz pass on [Z | W | V], five launches with the member on blockIdx.y: the Gram matrices, the Ritz pairs
+  // (near: ordered by their distance from sigma), X = Z Q, and the residuals of the first n_eig pairs against tol.  The
+  // slabs of k_eig_rotate are the groups of lod_shape(h, m) and m <= 64 is one column chunk, so its grid is
+  // lod_grid(w, RT_MAX_BLOCKS) with the members on y.
+  void eig_ritz_pass(hipStream_t st, const EigSpace &E, int n_eig, double tol, bool near, double sigma, double *d_x, size_t ld_x)
+  {
+    const int      m = E.m;
+    const unsigned K = (unsigned)E.K;
+    hipLaunchKernelGGL(k_eig_gram, dim3((unsigned)std::min(E.n_gslab, GR_MAX_BLOCKS), K), dim3(GR_BLOCK), 0, st, E.nrow, m, E.n_gslab,
+                       E.Z, E.W, E.V, E.ldw, E.partial);
+    hipLaunchKernelGGL(k_eig_gram_sum, dim3((unsigned)((2 * (size_t)m * m + 255) / 256), K), dim3(256), 0, st, m, E.n_gslab, E.partial,
+                       E.G);
+    hipLaunchKernelGGL(k_eig_ritz, dim3(1, K), dim3(RZ_BLOCK), 0, st, m, E.G, E.Q, E.theta, E.status, E.d_done, near ? 1 : 0, sigma);
+    hipLaunchKernelGGL(k_eig_rotate, dim3((unsigned)std::min(E.n_rslab, RT_MAX_BLOCKS), K), dim3(RT_BLOCK), 0, st, E.nrow, m, E.n_rslab,
+                       E.Z, E.W, E.V, E.Q, E.theta, E.status, E.d_done, E.ldw, d_x, ld_x, E.p_rr, E.p_mm);
+    hipLaunchKernelGGL(k_eig_residual, dim3(1, K), dim3(EG_COLS), 0, st, m, n_eig, E.n_rslab, tol, E.p_rr, E.p_mm, E.theta, E.status,
+                       E.res, E.d_done);
+  }
+
+  // The text of SLOD_ERR_NUMERIC: k_eig_ritz met a non-positive pivot (status = column + 1); member < 0: a single pencil
+  std::string eig_rank_message(const std::string &who, int member, int status, int outer)
+  {
+    return who + ": " + (member >= 0 ? "member " + std::to_string(member) + ": " : std::string()) +
+           "non-positive pivot in the Cholesky of Gm = Z^T M Z at column " + std::to_string(status - 1) + " of outer iteration " +
+           std::to_string(outer) + " (rank-deficient block)";
+  }
+
   // The body of slod_lod_eigs_ensemble_direct; slod_lod_eigs_direct is the call with n_members = 1 and ld = 1.  Member k
   // works on columns k m .. k m + m - 1 of d_x and of the workspace vectors.  Arguments are checked here, the factor last.
   // near: the body of slod_lod_eigs_shift(_ensemble)_direct: the Ritz pairs are ordered by their distance from sigma and
@@ -564,17 +653,9 @@ namespace
     const std::string name(who);
     if (!h || !d_stiffness || !d_mass || !d_cols || !d_x || !eigenvalues || !residuals)
       return slod_fail(h, SLOD_ERR_ARGUMENT, name + ": NULL handle, matrix, d_cols, d_x, eigenvalues or residuals");
-    const int s = h->cfg.spacedim, nrow = h->NP * s, m = n_block, K = n_members;
-    if (n_eig < 1 || n_block < n_eig)
-      return slod_fail(h, SLOD_ERR_ARGUMENT, name + ": n_eig < 1 or n_block < n_eig");
-    if (n_block > EG_COLS || n_block > nrow)
-      return slod_fail(h, SLOD_ERR_ARGUMENT, name + ": n_block above 64 or above the number of rows");
-    if (start != 0 && start != 1)
-      return slod_fail(h, SLOD_ERR_ARGUMENT, name + ": start is neither 0 nor 1");
-    if (!(tol > 0.0))
-      return slod_fail(h, SLOD_ERR_ARGUMENT, name + ": tol is not positive");
-    if (max_outer < 1)
-      return slod_fail(h, SLOD_ERR_ARGUMENT, name + ": max_outer < 1");
+    const int m = n_block, K = n_members;
+    if (const int rc = eig_check(h, name, n_eig, n_block, start, tol, max_outer))
+      return rc;
     if (K < 1 || K > 65535)
       return slod_fail(h, SLOD_ERR_ARGUMENT, name + ": n_members < 1 or > 65535");
     if (const int rc = slod_check_ld(h, who, "n_members", K, {ld_a_m, ld_m_m}))
@@ -590,30 +671,20 @@ namespace
     hipStream_t st;
     if (const int rc = slod_enter(h, nullptr, &st))
       return rc;
-    const LodShape w = lod_shape(h, m); // its groups are the slabs of k_eig_rotate and of k_eig_apply
-    const int      n_gslab = (nrow + GR_ROWS - 1) / GR_ROWS, n_rslab = w.ngroup;
-    const size_t   ldw = (size_t)K * m, nvec = (size_t)nrow * ldw, mm = (size_t)m * m, nint = ((size_t)K + 1) / 2;
-    // one allocation for the whole loop: Y, Z, W, V of K m columns, per member the slab partials, Ga | Gm and Q, then
-    // theta | residuals | status | done of all members (consecutive: the host reads them in one copy)
-    double            *Y, *Z, *W, *V, *partial, *G, *Q, *p_rr, *p_mm, *theta, *res;
-    int               *status, *d_done;
+    const LodShape w = lod_shape(h, m);
+    EigSpace       E(w, m, K);
+    const size_t   ldw = E.ldw, nint = E.nint, nread = 2 * ldw + 2 * nint; // theta | residuals | status | done
+    // one allocation for the whole loop
     SlodDevBuf<double> work;
     SlodCarver         count, hand;
-    auto               carve = [&](SlodCarver &c) {
-      Y = c.take(nvec), Z = c.take(nvec), W = c.take(nvec), V = c.take(nvec);
-      partial = c.take(K * 2 * mm * n_gslab), G = c.take(K * 2 * mm), Q = c.take(K * mm);
-      p_rr = c.take(ldw * n_rslab), p_mm = c.take(ldw * n_rslab);
-      theta = c.take(ldw), res = c.take(ldw), status = (int *)c.take(nint), d_done = (int *)c.take(nint);
-    };
-    carve(count);
+    E.carve(count);
     hipError_t e = work.alloc(count.used);
     hand.base    = work.get();
     if (e == hipSuccess)
       {
-        carve(hand);
-        e = hipMemsetAsync(theta, 0, (2 * ldw + 2 * nint) * sizeof(double), st);
+        E.carve(hand);
+        e = hipMemsetAsync(E.theta, 0, nread * sizeof(double), st);
       }
-    const size_t        nread = 2 * ldw + 2 * nint;
     std::vector<double> host(nread);
     std::vector<int>    ran((size_t)K, 0), failed_column((size_t)K, 0); // outer iterations of a stopped member, 0 = still open
     int                 outer = 0, open = K;
@@ -621,36 +692,24 @@ namespace
       {
         if (start == 0)
           {
-            const dim3 start_grid((unsigned)(((size_t)nrow * m + 255) / 256), (unsigned)K);
-            if (near)
-              hipLaunchKernelGGL(k_eig_start_hash, start_grid, dim3(256), 0, st, nrow, m, d_x, ld_x);
-            else
-              hipLaunchKernelGGL(k_eig_start, start_grid, dim3(256), 0, st, slod_grid_of(h), h->NP, s, m, eig_sine_modes(h, m), d_x, ld_x);
+            eig_start_launch(h, st, near, m, K, d_x, ld_x);
             e = hipGetLastError();
           }
         const dim3 apply_grid((unsigned)std::min(w.ngroup, AP_MAX_BLOCKS), (unsigned)K);
         auto       apply = [&](const double *values, size_t ld_m, const double *x, size_t ldx, double *y) {
-          hipLaunchKernelGGL(k_eig_apply, apply_grid, dim3(LOD_BLOCK), 0, st, nrow, s, w.cap, w.NP, m, w.ngroup, values, ld_m, d_cols, x,
-                             ldx, y, ldw);
+          hipLaunchKernelGGL(k_eig_apply, apply_grid, dim3(LOD_BLOCK), 0, st, w.nrow, w.s, w.cap, w.NP, m, w.ngroup, values, ld_m, d_cols,
+                             x, ldx, y, ldw);
         };
         while (e == hipSuccess && open > 0 && outer < max_outer)
           {
-            apply(d_mass, ld_m_m, d_x, ld_x, Y);
-            slod_lod_factor_solve_launch(f_S, st, Y, ldw, m, Z, ldw, 0, K);
-            apply(d_stiffness, ld_a_m, Z, ldw, W);
-            apply(d_mass, ld_m_m, Z, ldw, V);
-            hipLaunchKernelGGL(k_eig_gram, dim3((unsigned)std::min(n_gslab, GR_MAX_BLOCKS), (unsigned)K), dim3(GR_BLOCK), 0, st, nrow, m,
-                               n_gslab, Z, W, V, ldw, partial);
-            hipLaunchKernelGGL(k_eig_gram_sum, dim3((unsigned)((2 * mm + 255) / 256), (unsigned)K), dim3(256), 0, st, m, n_gslab, partial, G);
-            hipLaunchKernelGGL(k_eig_ritz, dim3(1, (unsigned)K), dim3(RZ_BLOCK), 0, st, m, G, Q, theta, status, d_done, near ? 1 : 0,
-                               sigma);
-            hipLaunchKernelGGL(k_eig_rotate, dim3((unsigned)std::min(n_rslab, RT_MAX_BLOCKS), (unsigned)K), dim3(RT_BLOCK), 0, st, nrow, m,
-                               n_rslab, Z, W, V, Q, theta, status, d_done, ldw, d_x, ld_x, p_rr, p_mm);
-            hipLaunchKernelGGL(k_eig_residual, dim3(1, (unsigned)K), dim3(EG_COLS), 0, st, m, n_eig, n_rslab, tol, p_rr, p_mm, theta,
-                               status, res, d_done);
+            apply(d_mass, ld_m_m, d_x, ld_x, E.Y);
+            slod_lod_factor_solve_launch(f_S, st, E.Y, ldw, m, E.Z, ldw, 0, K);
+            apply(d_stiffness, ld_a_m, E.Z, ldw, E.W);
+            apply(d_mass, ld_m_m, E.Z, ldw, E.V);
+            eig_ritz_pass(st, E, n_eig, tol, near, sigma, d_x, ld_x);
             e = hipGetLastError();
             if (e == hipSuccess)
-              e = hipMemcpyAsync(host.data(), theta, nread * sizeof(double), hipMemcpyDeviceToHost, st);
+              e = hipMemcpyAsync(host.data(), E.theta, nread * sizeof(double), hipMemcpyDeviceToHost, st);
             if (e == hipSuccess)
               e = hipStreamSynchronize(st);
             if (e != hipSuccess)
@@ -683,10 +742,7 @@ namespace
           bad = k;
       }
     if (bad >= 0)
-      return slod_fail(h, SLOD_ERR_NUMERIC,
-                       name + ": " + (ensemble ? "member " + std::to_string(bad) + ": " : std::string()) +
-                         "non-positive pivot in the Cholesky of Gm = Z^T M Z at column " + std::to_string(failed_column[(size_t)bad] - 1) +
-                         " of outer iteration " + std::to_string(ran[(size_t)bad]) + " (rank-deficient block)");
+      return slod_fail(h, SLOD_ERR_NUMERIC, eig_rank_message(name, ensemble ? bad : -1, failed_column[(size_t)bad], ran[(size_t)bad]));
     return worst;
   }
 
@@ -716,70 +772,42 @@ int slod_lod_eigs(slod_handle *h, const double *d_stiffness, const double *d_mas
 {
   if (!h || !d_stiffness || !d_mass || !d_cols || !d_x || !eigenvalues || !residuals)
     return SLOD_ERR_ARGUMENT;
-  const int s = h->cfg.spacedim, nrow = h->NP * s, m = n_block;
-  if (n_eig < 1 || n_block < n_eig)
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_eigs: n_eig < 1 or n_block < n_eig");
-  if (n_block > EG_COLS || n_block > nrow)
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_eigs: n_block above 64 or above the number of rows");
-  if (const int rc = slod_check_ld(h, "slod_lod_eigs", "n_block", n_block, {ld_x}))
+  if (const int rc = eig_check(h, "slod_lod_eigs", n_eig, n_block, start, tol, max_outer, true, ld_x, inner_rel_tol, inner_max_iterations))
     return rc;
-  if (start != 0 && start != 1)
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_eigs: start is neither 0 nor 1");
-  if (!(tol > 0.0) || !(inner_rel_tol > 0.0))
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_eigs: tol or inner_rel_tol is not positive");
-  if (max_outer < 1 || inner_max_iterations < 0)
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_eigs: max_outer < 1 or inner_max_iterations < 0");
   hipStream_t st;
   if (const int rc = slod_enter(h, nullptr, &st))
     return rc;
-  const LodShape w = lod_shape(h, m); // its groups are the slabs of k_eig_rotate
-  const int      n_gslab = (nrow + GR_ROWS - 1) / GR_ROWS, n_rslab = w.ngroup;
-  const size_t   nvec = (size_t)nrow * m, mm = (size_t)m * m;
-  // one allocation for the whole loop: Y, Z, W, V, the slab partials, Ga | Gm, Q, theta | residuals | status (consecutive: the
-  // host reads them in one copy), the done word of the kernels, the workspace of the solve
-  double     *Y, *Z, *W, *V, *partial, *G, *Q, *p_rr, *p_mm, *theta, *res;
-  int        *status, *d_done;
+  const int   m = n_block;
+  EigSpace    E(lod_shape(h, m), m, 1);
+  // one allocation for the whole loop: the arrays of the outer iteration, the workspace of the solve
   SlodLodWork work;
-  hipError_t  e = work.alloc(m, [&](SlodCarver &c) {
-    Y = c.take(nvec), Z = c.take(nvec), W = c.take(nvec), V = c.take(nvec);
-    partial = c.take(2 * mm * n_gslab), G = c.take(2 * mm), Q = c.take(mm);
-    p_rr = c.take((size_t)m * n_rslab), p_mm = c.take((size_t)m * n_rslab);
-    theta = c.take(m), res = c.take(m), status = c.take_as<int>(), d_done = c.take_as<int>(), work.take_solve(c, h);
-  });
+  hipError_t  e = work.alloc(m, [&](SlodCarver &c) { E.carve(c), work.take_solve(c, h); });
   if (e == hipSuccess)
-    e = hipMemsetAsync(status, 0, 2 * sizeof(double), st); // status and done: the host decides when this loop stops
+    e = hipMemsetAsync(E.status, 0, 2 * sizeof(double), st); // status and done: the host decides when this loop stops
   int outer = 0, failed_column = 0;
   if (e == hipSuccess)
     {
       if (start == 0)
         {
-          const EigModes md = eig_sine_modes(h, m);
-          hipLaunchKernelGGL(k_eig_start, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, st, slod_grid_of(h), h->NP, s, m, md,
-                             d_x, ld_x);
+          eig_start_launch(h, st, false, m, 1, d_x, ld_x);
           e = hipGetLastError();
         }
-      std::vector<double> host(2 * (size_t)m + 1); // the last slot holds the int
+      std::vector<double> host(2 * (size_t)m + 1); // theta | residuals | status: the last slot holds the int
       bool                done = false;
       while (e == hipSuccess && !done && outer < max_outer)
         {
-          slod_lod_apply_launch(h, st, d_mass, d_cols, d_x, ld_x, m, Y, (size_t)m);
+          slod_lod_apply_launch(h, st, d_mass, d_cols, d_x, ld_x, m, E.Y, (size_t)m);
           e = hipGetLastError();
           if (e == hipSuccess)
-            e = work.solve(h, d_stiffness, d_cols, Y, (size_t)m, Z, (size_t)m, inner_rel_tol, inner_max_iterations);
+            e = work.solve(h, d_stiffness, d_cols, E.Y, (size_t)m, E.Z, (size_t)m, inner_rel_tol, inner_max_iterations);
           if (e != hipSuccess)
             break;
-          slod_lod_apply_launch(h, st, d_stiffness, d_cols, Z, (size_t)m, m, W, (size_t)m);
-          slod_lod_apply_launch(h, st, d_mass, d_cols, Z, (size_t)m, m, V, (size_t)m);
-          hipLaunchKernelGGL(k_eig_gram, dim3((unsigned)std::min(n_gslab, GR_MAX_BLOCKS)), dim3(GR_BLOCK), 0, st, nrow, m, n_gslab, Z, W,
-                             V, (size_t)m, partial);
-          hipLaunchKernelGGL(k_eig_gram_sum, dim3((unsigned)((2 * mm + 255) / 256)), dim3(256), 0, st, m, n_gslab, partial, G);
-          hipLaunchKernelGGL(k_eig_ritz, dim3(1), dim3(RZ_BLOCK), 0, st, m, G, Q, theta, status, d_done, 0, 0.0);
-          hipLaunchKernelGGL(k_eig_rotate, lod_grid(w, RT_MAX_BLOCKS), dim3(RT_BLOCK), 0, st, nrow, m, n_rslab, Z, W, V, Q, theta, status,
-                             d_done, (size_t)m, d_x, ld_x, p_rr, p_mm);
-          hipLaunchKernelGGL(k_eig_residual, dim3(1), dim3(EG_COLS), 0, st, m, n_eig, n_rslab, tol, p_rr, p_mm, theta, status, res, d_done);
+          slod_lod_apply_launch(h, st, d_stiffness, d_cols, E.Z, (size_t)m, m, E.W, (size_t)m);
+          slod_lod_apply_launch(h, st, d_mass, d_cols, E.Z, (size_t)m, m, E.V, (size_t)m);
+          eig_ritz_pass(st, E, n_eig, tol, false, 0.0, d_x, ld_x);
           e = hipGetLastError();
           if (e == hipSuccess)
-            e = hipMemcpyAsync(host.data(), theta, host.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+            e = hipMemcpyAsync(host.data(), E.theta, host.size() * sizeof(double), hipMemcpyDeviceToHost, st);
           if (e == hipSuccess)
             e = hipStreamSynchronize(st);
           if (e != hipSuccess)
@@ -796,14 +824,15 @@ int slod_lod_eigs(slod_handle *h, const double *d_stiffness, const double *d_mas
           for (int j = 0; j < n_eig; ++j)
             done = done && residuals[j] <= tol;
         }
+      // every completed pass ends on a synchronised stream; a failed one waits here: the workspace is freed on return and a
+      // queued kernel may still touch it
+      if (e != hipSuccess)
+        (void)hipStreamSynchronize(st);
     }
-  // (every completed pass of the loop ends on a synchronised stream: the workspace is idle when it is freed)
   if (e != hipSuccess)
     return slod_hip_fail(h, e, "slod_lod_eigs");
   if (failed_column != 0)
-    return slod_fail(h, SLOD_ERR_NUMERIC,
-                     "slod_lod_eigs: non-positive pivot in the Cholesky of Gm = Z^T M Z at column " + std::to_string(failed_column - 1) +
-                       " of outer iteration " + std::to_string(outer) + " (rank-deficient block)");
+    return slod_fail(h, SLOD_ERR_NUMERIC, eig_rank_message("slod_lod_eigs", -1, failed_column, outer));
   return outer;
 }
 

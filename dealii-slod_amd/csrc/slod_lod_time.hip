@@ -4,9 +4,12 @@
 //   slod_lod_apply_multi     Y = A X for any matrix in that layout, columns on lanes
 //   slod_lod_matrix_combine  out = alpha A + beta B on two values arrays of one pattern
 //   slod_lod_theta_steps     n_steps of the theta scheme for  M u' + A u = b(t), the state stays on the device
+// and slod_lod_theta_steps_direct / _ensemble_direct, the same loop on a factor the caller built (slod_lod_factor.hip),
+// for one matrix or with a matrix, a factor and a column per member.
 // The mass kernel is an L2/HBM-bound gather like k_lod_matrix (slod_lod_system.hip) and shares its index calculus
-// (slod_grid.hip.h); the solve of a step is the recurrence of slod_lod_solve_multi (slod_lod_multi.hip) on a
-// workspace this file owns for the whole loop.
+// (slod_grid.hip.h).  The loop is written once (theta_steps) on the operator of a column and the solve of a step
+// (SlodLodOperator, SlodLodStepSolve, slod_host.h): the recurrence of slod_lod_solve_multi (slod_lod_multi.hip) on a
+// workspace the loop owns, or the two sweeps of the factor; the argument checks of the three calls are theta_check.
 #include "slod_lod_system.hip.h"
 #include "slod_lod_tile.hip.h"
 
@@ -99,6 +102,81 @@ void slod_lod_combine_launch(hipStream_t st, size_t n, double alpha, const doubl
   hipLaunchKernelGGL(k_lod_combine, lod_flat_grid(n), dim3(LOD_BLOCK), 0, st, n, alpha, d_a, beta, d_b, d_out);
 }
 
+namespace
+{
+  // The argument checks of the three theta calls, in one order; every call keeps its wording.  arrays: no array is NULL;
+  // n: n_rhs or n_members; lds: the leading dimensions of the vectors.  The factor is looked at last: only that check
+  // reads it.
+  int theta_check(const slod_handle *h, const std::string &who, const SlodLodStepSolve &solve, const SlodLodOperator &A, bool arrays,
+                  double dt, double theta, int n_steps, int n, std::initializer_list<size_t> lds)
+  {
+    const bool cg = solve.cg(), ens = A.per_col;
+    if (!ens && (!h || (cg && !arrays)))
+      return SLOD_ERR_ARGUMENT;
+    if (!h || !arrays)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, who + (ens ? ": NULL handle, matrix, d_cols or d_u" : ": NULL matrix, d_cols or d_u"));
+    if (!(dt > 0.0) || !(theta >= 0.0 && theta <= 1.0))
+      return slod_fail(h, SLOD_ERR_ARGUMENT, who + ": dt <= 0 or theta outside [0, 1]");
+    if (n_steps < 1 || n < 1 || (ens && n > 65535) || (cg && solve.max_iterations < 0))
+      return slod_fail(h, SLOD_ERR_ARGUMENT,
+                       who + (cg    ? ": n_steps < 1, n_rhs < 1 or max_iterations < 0"
+                              : ens ? ": n_steps < 1, n_members < 1 or > 65535"
+                                    : ": n_steps < 1 or n_rhs < 1"));
+    if (const int rc = slod_check_ld_of(h, who.c_str(), ens, {A.ld_m}, n, lds))
+      return rc;
+    return cg ? SLOD_OK : slod_lod_factor_check(h, who.c_str(), solve.f, ens ? n : 1);
+  }
+
+  // n_steps of the theta scheme on n columns,  S delta = dt (theta b1 + (1 - theta) b0 - A u),  u += delta,  whatever
+  // solves the step; the body of the three calls.  CG: S = M + theta dt A is built here and every solve synchronises; on a
+  // factor (of that S) the whole loop is queued and the stream is waited for once.  Returns the largest iteration count
+  // of a step (0 on a factor) or a negative status.
+  int theta_steps(slod_handle *h, const char *who, SlodLodStepSolve &&solve, const SlodLodOperator &A, const double *d_mass,
+                  const uint32_t *d_cols, double dt, double theta, int n_steps, int n, double *d_u, size_t ld_u, const double *d_load,
+                  size_t ld_load, size_t load_step_stride)
+  {
+    if (const int rc = theta_check(h, who, solve, A, A.values && (d_mass || !solve.cg()) && d_cols && d_u, dt, theta, n_steps, n,
+                                   {ld_u, d_load ? ld_load : ld_u}))
+      return rc;
+    hipStream_t st;
+    if (const int rc = slod_enter(h, nullptr, &st))
+      return rc;
+    const LodShape w = lod_shape(h, n);
+    const size_t   nmat = solve.cg() ? (size_t)w.NP * w.cap * w.s * w.s : 0, nvec = (size_t)w.nrow * n;
+    // one allocation for the whole loop: S (CG), g, delta and the workspace of the solve
+    double    *S, *g, *delta;
+    hipError_t e = solve.alloc(n, [&](SlodCarver &c) { S = c.take(nmat), g = c.take(nvec), delta = c.take(nvec), solve.take(c, h); });
+    if (e == hipSuccess)
+      {
+        if (solve.cg())
+          {
+            slod_lod_combine_launch(st, nmat, 1.0, d_mass, theta * dt, A.values, S);
+            solve.S = S;
+            e       = hipGetLastError();
+          }
+        for (int k = 0; k < n_steps && e == hipSuccess; ++k)
+          {
+            const double *b0 = d_load ? d_load + (size_t)k * load_step_stride : nullptr;
+            const double *b1 = d_load ? d_load + (size_t)(k + 1) * load_step_stride : nullptr;
+            slod_lod_apply_launch(h, st, A, d_cols, d_u, ld_u, n, g, (size_t)n);
+            hipLaunchKernelGGL(k_theta_rhs, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n, dt, theta, b0, b1, ld_load, g);
+            e = hipGetLastError();
+            if (e == hipSuccess)
+              e = solve.solve(h, st, k, n, g, (size_t)n, delta, (size_t)n);
+            if (e != hipSuccess)
+              break;
+            hipLaunchKernelGGL(k_theta_advance, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n, delta, d_u, ld_u);
+            e = hipGetLastError();
+          }
+        // on every path, a failed one too: the workspace is freed on return and a queued kernel may still touch it
+        const hipError_t es = hipStreamSynchronize(st);
+        if (e == hipSuccess)
+          e = es;
+      }
+    return e == hipSuccess ? solve.work.worst : slod_hip_fail(h, e, who);
+  }
+} // namespace
+
 #pragma GCC visibility push(default)
 extern "C" {
 
@@ -168,138 +246,28 @@ int slod_lod_theta_steps(slod_handle *h, const double *d_stiffness, const double
                          double theta, int n_steps, int n_rhs, double *d_u, size_t ld_u, const double *d_load, size_t ld_load,
                          size_t load_step_stride, double rel_tol, int max_iterations, int *iterations, double *rel_residual)
 {
-  if (!h || !d_stiffness || !d_mass || !d_cols || !d_u)
-    return SLOD_ERR_ARGUMENT;
-  if (!(dt > 0.0) || !(theta >= 0.0 && theta <= 1.0))
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_theta_steps: dt <= 0 or theta outside [0, 1]");
-  if (n_steps < 1 || n_rhs < 1 || max_iterations < 0)
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_theta_steps: n_steps < 1, n_rhs < 1 or max_iterations < 0");
-  if (const int rc = slod_check_ld(h, "slod_lod_theta_steps", "n_rhs", n_rhs, {ld_u, d_load ? ld_load : ld_u}))
-    return rc;
-  hipStream_t st;
-  if (const int rc = slod_enter(h, nullptr, &st))
-    return rc;
-  const LodShape w = lod_shape(h, n_rhs);
-  const size_t   nmat = (size_t)w.NP * w.cap * w.s * w.s, nvec = (size_t)w.nrow * n_rhs;
-  // one allocation for the whole loop: S, g, delta and the workspace of the solve
-  double     *S, *g, *delta;
-  SlodLodWork work;
-  hipError_t  e = work.alloc(n_rhs, [&](SlodCarver &c) { S = c.take(nmat), g = c.take(nvec), delta = c.take(nvec), work.take_solve(c, h); });
-  if (e == hipSuccess)
-    {
-      slod_lod_combine_launch(st, nmat, 1.0, d_mass, theta * dt, d_stiffness, S);
-      e = hipGetLastError();
-      for (int k = 0; k < n_steps && e == hipSuccess; ++k)
-        {
-          const double *b0 = d_load ? d_load + (size_t)k * load_step_stride : nullptr;
-          const double *b1 = d_load ? d_load + (size_t)(k + 1) * load_step_stride : nullptr;
-          slod_lod_apply_launch(h, st, d_stiffness, d_cols, d_u, ld_u, n_rhs, g, (size_t)n_rhs);
-          hipLaunchKernelGGL(k_theta_rhs, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n_rhs, dt, theta, b0, b1, ld_load, g);
-          e = hipGetLastError();
-          if (e == hipSuccess)
-            e = work.solve(h, S, d_cols, g, (size_t)n_rhs, delta, (size_t)n_rhs, rel_tol, max_iterations);
-          if (e != hipSuccess)
-            break;
-          work.record(k, iterations, rel_residual);
-          hipLaunchKernelGGL(k_theta_advance, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n_rhs, delta, d_u, ld_u);
-          e = hipGetLastError();
-        }
-      if (e == hipSuccess)
-        e = hipStreamSynchronize(st); // the workspace is freed on return
-    }
-  if (e != hipSuccess)
-    return slod_hip_fail(h, e, "slod_lod_theta_steps");
-  return work.worst;
+  return theta_steps(h, "slod_lod_theta_steps", {SLOD_SOLVE_CG, nullptr, d_cols, nullptr, rel_tol, max_iterations, iterations, rel_residual},
+                     {d_stiffness}, d_mass, d_cols, dt, theta, n_steps, n_rhs, d_u, ld_u, d_load, ld_load, load_step_stride);
 }
 
-// The loop of slod_lod_theta_steps with the factor's two sweeps in place of the CG recurrence: the whole loop is queued
-// and the stream is waited for once.
+// slod_lod_theta_steps with the factor's two sweeps in place of the CG recurrence
 int slod_lod_theta_steps_direct(slod_handle *h, slod_lod_factor *f_S, const double *d_stiffness, const uint32_t *d_cols, double dt,
                                 double theta, int n_steps, int n_rhs, double *d_u, size_t ld_u, const double *d_load, size_t ld_load,
                                 size_t load_step_stride)
 {
-  if (!h)
-    return SLOD_ERR_ARGUMENT;
-  if (!d_stiffness || !d_cols || !d_u)
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_theta_steps_direct: NULL matrix, d_cols or d_u");
-  if (!(dt > 0.0) || !(theta >= 0.0 && theta <= 1.0))
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_theta_steps_direct: dt <= 0 or theta outside [0, 1]");
-  if (n_steps < 1 || n_rhs < 1)
-    return slod_fail(h, SLOD_ERR_ARGUMENT, "slod_lod_theta_steps_direct: n_steps < 1 or n_rhs < 1");
-  if (const int rc = slod_check_ld(h, "slod_lod_theta_steps_direct", "n_rhs", n_rhs, {ld_u, d_load ? ld_load : ld_u}))
-    return rc;
-  if (const int rc = slod_lod_factor_check(h, "slod_lod_theta_steps_direct", f_S)) // last: it reads the factor
-    return rc;
-  hipStream_t st;
-  if (const int rc = slod_enter(h, nullptr, &st))
-    return rc;
-  const LodShape     w = lod_shape(h, n_rhs);
-  const size_t       nvec = (size_t)w.nrow * n_rhs;
-  SlodDevBuf<double> work; // g, delta
-  hipError_t         e = work.alloc(2 * nvec);
-  if (e == hipSuccess)
-    {
-      double *g = work.get(), *delta = g + nvec;
-      for (int k = 0; k < n_steps && e == hipSuccess; ++k)
-        {
-          const double *b0 = d_load ? d_load + (size_t)k * load_step_stride : nullptr;
-          const double *b1 = d_load ? d_load + (size_t)(k + 1) * load_step_stride : nullptr;
-          slod_lod_apply_launch(h, st, d_stiffness, d_cols, d_u, ld_u, n_rhs, g, (size_t)n_rhs);
-          hipLaunchKernelGGL(k_theta_rhs, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n_rhs, dt, theta, b0, b1, ld_load, g);
-          slod_lod_factor_solve_launch(f_S, st, g, (size_t)n_rhs, n_rhs, delta, (size_t)n_rhs);
-          hipLaunchKernelGGL(k_theta_advance, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n_rhs, delta, d_u, ld_u);
-          e = hipGetLastError();
-        }
-      const hipError_t es = hipStreamSynchronize(st); // the workspace is freed on return
-      if (e == hipSuccess)
-        e = es;
-    }
-  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, "slod_lod_theta_steps_direct");
+  return theta_steps(h, "slod_lod_theta_steps_direct", {SLOD_SOLVE_FACTOR, f_S}, {d_stiffness}, nullptr, d_cols, dt, theta, n_steps,
+                     n_rhs, d_u, ld_u, d_load, ld_load, load_step_stride);
 }
 
-// The loop of slod_lod_theta_steps_direct with a matrix and a factor per column: the product is k_ens_apply
-// (slod_lod_ensemble.hip), the solve the member axis of k_factor_solve with one column per member; k_theta_rhs and
-// k_theta_advance work per (row, column) and serve as they are.
+// slod_lod_theta_steps_direct with a matrix and a factor per column: the product is k_ens_apply (slod_lod_ensemble.hip),
+// the solve the member axis of k_factor_solve with one column per member; k_theta_rhs and k_theta_advance work per
+// (row, column) and serve as they are.
 int slod_lod_theta_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, const double *d_stiffness, size_t ld_m,
                                          const uint32_t *d_cols, double dt, double theta, int n_steps, int n_members, double *d_u,
                                          size_t ld_u, const double *d_load, size_t ld_load, size_t load_step_stride)
 {
-  const char *who = "slod_lod_theta_steps_ensemble_direct";
-  if (!h || !d_stiffness || !d_cols || !d_u)
-    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": NULL handle, matrix, d_cols or d_u");
-  if (!(dt > 0.0) || !(theta >= 0.0 && theta <= 1.0))
-    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": dt <= 0 or theta outside [0, 1]");
-  if (n_steps < 1 || n_members < 1 || n_members > 65535)
-    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": n_steps < 1, n_members < 1 or > 65535");
-  if (const int rc = slod_check_ld(h, who, "n_members", n_members, {ld_m, ld_u, d_load ? ld_load : ld_u}))
-    return rc;
-  if (const int rc = slod_lod_factor_check(h, who, f_S, n_members)) // last: it reads the factor
-    return rc;
-  hipStream_t st;
-  if (const int rc = slod_enter(h, nullptr, &st))
-    return rc;
-  const LodShape     w = lod_shape(h, n_members);
-  const size_t       nvec = (size_t)w.nrow * n_members;
-  SlodDevBuf<double> work; // g, delta
-  hipError_t         e = work.alloc(2 * nvec);
-  if (e == hipSuccess)
-    {
-      double *g = work.get(), *delta = g + nvec;
-      for (int k = 0; k < n_steps && e == hipSuccess; ++k)
-        {
-          const double *b0 = d_load ? d_load + (size_t)k * load_step_stride : nullptr;
-          const double *b1 = d_load ? d_load + (size_t)(k + 1) * load_step_stride : nullptr;
-          slod_lod_apply_ensemble_launch(h, st, d_stiffness, ld_m, d_cols, d_u, ld_u, n_members, g, (size_t)n_members);
-          hipLaunchKernelGGL(k_theta_rhs, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n_members, dt, theta, b0, b1, ld_load, g);
-          slod_lod_factor_solve_launch(f_S, st, g, (size_t)n_members, 1, delta, (size_t)n_members, 0, n_members);
-          hipLaunchKernelGGL(k_theta_advance, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n_members, delta, d_u, ld_u);
-          e = hipGetLastError();
-        }
-      const hipError_t es = hipStreamSynchronize(st); // the workspace is freed on return
-      if (e == hipSuccess)
-        e = es;
-    }
-  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, who);
+  return theta_steps(h, "slod_lod_theta_steps_ensemble_direct", {SLOD_SOLVE_FACTOR_PER_COL, f_S}, {d_stiffness, ld_m, true}, nullptr,
+                     d_cols, dt, theta, n_steps, n_members, d_u, ld_u, d_load, ld_load, load_step_stride);
 }
 
 } // extern "C"

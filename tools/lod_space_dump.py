@@ -12,6 +12,14 @@ stiffness and slod_lod_eigs (n_eig 4, default guard columns, the library's start
 lod_rhs_multi, lod_apply, lod_inner, lod_solve_multi, three lod_theta_steps (theta 1 and 1/2, distinct loads),
 lod_newmark_accel, three lod_newmark_steps (beta 1/4 undamped, beta 0 damped) with both energies, and
 lod_reconstruct_multi.  slod_lod_solve (scalar, atomic sums) is not bit-reproducible and is left out.
+
+The calls on banded factors, on the four small configurations (DIRECT): the pivot ranges of the Cholesky factors of M
+and of the step matrices (lod_matrix_combine of the symmetrised stiffness and M), lod_eigs_direct on the LDL^T factor of
+the stiffness and lod_eigs_shift_direct on that of A - sigma M, sigma between the second and third eigenvalue of
+lod_eigs; per n_rhs a factor solve, lod_theta_steps_direct, lod_newmark_accel_direct and lod_newmark_steps_direct with
+the parameters of the CG calls above.  Under <name>/ens/: K = 3 members of one handle with seeded D100 coefficients of
+their own, lod_inner_ensemble, lod_theta_steps_ensemble_direct, both Newmark ensemble calls and
+lod_eigs_ensemble_direct, a column per member.
 """
 import os
 import sys
@@ -27,7 +35,12 @@ CONFIGS = {"s1": dict(nref=2, n_sub=2, oversampling=1, spacedim=1),
            "s2": dict(nref=2, n_sub=2, oversampling=1, spacedim=2),
            "rowmajor": dict(n_cells=5, n_sub=3, oversampling=1, spacedim=1),
            "c1": dict(nref=3, n_sub=4, oversampling=1, spacedim=1)}
+DIRECT = ("s1", "clipped", "s2", "rowmajor")      # the configurations that also run the calls on factors
 N_RHS = (1, 3, 65)
+K_ENS = 3
+THETAS = ((1.0, 0.01), (0.5, 0.01))               # (theta, dt)
+# tag, beta, dt, damp_mass, damp_stiff (gamma = 1/2): the damped run has the mass product in its right-hand side
+NEWMARK = (("newmark_quarter_", 0.25, 0.05, 0.0, 0.0), ("newmark_central_", 0.0, 1e-4, 0.5, 1e-4))
 STEPS, TOL, MAXIT = 3, 1e-12, 5000
 
 
@@ -46,6 +59,74 @@ def dump(path):
     def host(t):
         torch.cuda.synchronize()
         return t.cpu().numpy().copy()
+
+    def step_matrices(nmat, combine, factor, A, M):
+        """The Cholesky factors of M, of M + theta dt A and of the Newmark step matrices, by tag; combine(alpha, a, beta, b,
+        out) and factor(values) are those of one matrix or of an ensemble."""
+        fac = {"mass": factor(M)}
+        coef = [("theta%g" % theta, 1.0, theta * dt) for theta, dt in THETAS]
+        coef += [(tag, 1.0 + 0.5 * dt * dm, beta * dt * dt + 0.5 * dt * ds) for tag, beta, dt, dm, ds in NEWMARK]
+        for tag, alpha, beta in coef:
+            S = f64(*nmat)
+            combine(alpha, M.data_ptr(), beta, A.data_ptr(), S.data_ptr())
+            fac[tag] = factor(S)
+        return fac
+
+    def pivots(key, fac):
+        for tag, f in fac.items():
+            out[key + "factor_pivots_" + tag.rstrip("_")] = np.array([f.info.min_pivot, f.info.max_pivot])
+
+    def ensemble(kw, key):
+        """K_ENS members of one handle, a column per member: the calls on an ensemble matrix and an ensemble factor."""
+        K, s = K_ENS, kw["spacedim"]
+        g = slod_amd.Slod(stabilize=1, n_problems=K, **kw)
+        for k in range(K):
+            for f in range(s):
+                g.set_coefficient(f, fill_coefficient(SEED + 100 * (k + 1) + f, "D100", g.NE), problem=k)
+        NP, cap = g.num_patches, g.lod_row_capacity()
+        plan = g.plan(np.arange(K * NP, dtype=np.uint32))
+        b, q = f64(K * NP * plan.stride), f64(K * NP * plan.stride)
+        plan.execute(b.data_ptr(), q.data_ptr())
+        plan.status()
+        nrow, nmat = NP * s, NP * cap * s * s
+        rng = np.random.default_rng(12)
+        raw, A, M = f64(nmat, K), f64(nmat, K), f64(nmat, K)
+        cols, mcols = (torch.zeros(NP * cap, dtype=torch.int32, device=dev) for _ in range(2))
+        g.lod_matrix_ensemble(b.data_ptr(), q.data_ptr(), plan.stride, K, raw.data_ptr(), cols.data_ptr())
+        g.lod_mass_matrix_ensemble(b.data_ptr(), plan.stride, K, M.data_ptr(), mcols.data_ptr())
+        g.lod_matrix_symmetrize_ensemble(raw.data_ptr(), cols.data_ptr(), K, A.data_ptr())
+        out[key + "matrix_values"], out[key + "mass_values"] = host(A), host(M)
+        ptr = (A.data_ptr(), M.data_ptr(), cols.data_ptr())
+        fac = step_matrices((nmat, K), lambda al, a, be, b_, o: g.lod_matrix_combine_ensemble(al, a, be, b_, K, o),
+                            lambda v: g.lod_factor_ensemble(v.data_ptr(), cols.data_ptr(), K), A, M)
+        pivots(key, fac)
+        L = torch.from_numpy(rng.uniform(-1.0, 1.0, (STEPS + 1, nrow, K))).to(dev)
+        Xr = torch.from_numpy(rng.uniform(-1.0, 1.0, (nrow, K))).to(dev)
+        Y = f64(nrow, K)
+        g.lod_apply_ensemble(A.data_ptr(), cols.data_ptr(), Xr.data_ptr(), Y.data_ptr(), K)
+        out[key + "inner"] = g.lod_inner_ensemble(A.data_ptr(), cols.data_ptr(), Xr.data_ptr(), Y.data_ptr(), K).copy()
+        for theta, dt in THETAS:
+            u = Xr.clone() * 1e-3
+            g.lod_theta_steps_ensemble_direct(fac["theta%g" % theta], A.data_ptr(), cols.data_ptr(), dt, theta, STEPS, K,
+                                              u.data_ptr(), d_load=L.data_ptr(), load_step_stride=nrow * K)
+            out[key + "theta%g_u" % theta] = host(u)
+        for tag, beta, dt, dm, ds in NEWMARK:
+            u, v, a = Xr.clone() * 1e-3, Y.clone() * 1e-3, f64(nrow, K)
+            g.lod_newmark_accel_ensemble_direct(fac["mass"], *ptr, K, u.data_ptr(), v.data_ptr(), a.data_ptr(),
+                                                d_load=L[0].data_ptr(), damp_mass=dm, damp_stiff=ds)
+            out[key + tag + "accel"] = host(a)
+            kin, pot = g.lod_newmark_steps_ensemble_direct(fac[tag], *ptr, dt, STEPS, K, u.data_ptr(), v.data_ptr(), a.data_ptr(),
+                                                           beta=beta, d_load=L.data_ptr(), load_step_stride=nrow * K,
+                                                           damp_mass=dm, damp_stiff=ds)
+            for nm, arr in (("u", host(u)), ("v", host(v)), ("a", host(a)), ("kinetic", kin), ("potential", pot)):
+                out[key + tag + nm] = arr
+        m = min(64, nrow, 8)
+        X = f64(nrow, K * m)
+        f = g.lod_factor_ldl_ensemble(A.data_ptr(), cols.data_ptr(), K)
+        el, er, status, rc = g.lod_eigs_ensemble_direct(f, *ptr, K, 4, X.data_ptr(), max_outer=20)
+        for nm, arr in (("lambda", el), ("residual", er), ("status", status), ("X", host(X))):
+            out[key + "eigs_" + nm] = arr
+        g.close()
 
     for name, kw in CONFIGS.items():
         g = slod_amd.Slod(stabilize=1, **kw)
@@ -78,6 +159,25 @@ def dump(path):
         out[name + "/eigs_lambda"], out[name + "/eigs_residual"], out[name + "/eigs_inner"] = lam, res, its
         out[name + "/eigs_X"] = host(X)
 
+        direct = name in DIRECT
+        if direct:
+            fac = step_matrices((nmat,), g.lod_matrix_combine, lambda v: g.lod_factor(v.data_ptr(), cols.data_ptr()), sym, M)
+            pivots(name + "/", fac)
+            sigma = 0.5 * (lam[1] + lam[2])
+            shifted = f64(nmat)
+            g.lod_matrix_combine(1.0, sym.data_ptr(), -sigma, M.data_ptr(), shifted.data_ptr())
+            for tag, f, sigma in (("eigs_direct_", g.lod_factor_ldl(sym.data_ptr(), cols.data_ptr()), None),
+                                  ("eigs_shift_direct_", g.lod_factor_ldl(shifted.data_ptr(), cols.data_ptr()), sigma)):
+                X.zero_()
+                if sigma is None:
+                    el, er, rc = g.lod_eigs_direct(f, *ptr, 4, X.data_ptr(), max_outer=20)
+                else:
+                    el, er, rc = g.lod_eigs_shift_direct(f, sigma, *ptr, 4, X.data_ptr(), max_outer=20)
+                for nm, arr in (("lambda", el), ("residual", er), ("outer", np.array([rc])), ("X", host(X))):
+                    out[name + "/" + tag + nm] = arr
+                f.close()
+            ensemble(kw, name + "/ens/")
+
         for n in N_RHS:
             key = "%s/n%d/" % (name, n)
             # fine loads [level][column][fine], seeded; coarse loads [level][row][column]
@@ -97,13 +197,13 @@ def dump(path):
             fine = f64(n, nfine)
             g.lod_reconstruct_multi(b.data_ptr(), plan.stride, U.data_ptr(), n, n, fine.data_ptr(), nfine)
             out[key + "reconstruct_multi"] = host(fine)
-            for theta in (1.0, 0.5):
+            for theta, dt in THETAS:
                 u = Xr.clone() * 1e-3
-                its, res = g.lod_theta_steps(*ptr, 0.01, theta, STEPS, u.data_ptr(), n_rhs=n, d_load=L.data_ptr(),
+                its, res = g.lod_theta_steps(*ptr, dt, theta, STEPS, u.data_ptr(), n_rhs=n, d_load=L.data_ptr(),
                                              load_step_stride=nrow * n, rel_tol=TOL, max_iterations=MAXIT)
                 tag = key + "theta%g_" % theta
                 out[tag + "u"], out[tag + "its"], out[tag + "res"] = host(u), its.copy(), res.copy()
-            for tag, beta, dt, dm, ds in (("newmark_quarter_", 0.25, 0.05, 0.0, 0.0), ("newmark_central_", 0.0, 1e-4, 0.5, 1e-4)):
+            for tag, beta, dt, dm, ds in NEWMARK:
                 u, v, a = Xr.clone() * 1e-3, Y.clone() * 1e-3, f64(nrow, n)
                 its, res = g.lod_newmark_accel(*ptr, u.data_ptr(), v.data_ptr(), a.data_ptr(), n_rhs=n, d_load=L[0].data_ptr(),
                                                damp_mass=dm, damp_stiff=ds, rel_tol=TOL, max_iterations=MAXIT)
@@ -113,6 +213,26 @@ def dump(path):
                                                          rel_tol=TOL, max_iterations=MAXIT)
                 for nm, arr in (("u", host(u)), ("v", host(v)), ("a", host(a)), ("its", its.copy()), ("res", res.copy()),
                                 ("kinetic", kin), ("potential", pot)):
+                    out[key + tag + nm] = arr
+            if not direct:
+                continue
+            key += "direct_"
+            fac["mass"].solve(L[0].data_ptr(), U.data_ptr(), n_rhs=n)
+            out[key + "factor_solve"] = host(U)
+            for theta, dt in THETAS:
+                u = Xr.clone() * 1e-3
+                g.lod_theta_steps_direct(fac["theta%g" % theta], sym.data_ptr(), cols.data_ptr(), dt, theta, STEPS, u.data_ptr(),
+                                         n_rhs=n, d_load=L.data_ptr(), load_step_stride=nrow * n)
+                out[key + "theta%g_u" % theta] = host(u)
+            for tag, beta, dt, dm, ds in NEWMARK:
+                u, v, a = Xr.clone() * 1e-3, Y.clone() * 1e-3, f64(nrow, n)
+                g.lod_newmark_accel_direct(fac["mass"], *ptr, u.data_ptr(), v.data_ptr(), a.data_ptr(), n_rhs=n,
+                                           d_load=L[0].data_ptr(), damp_mass=dm, damp_stiff=ds)
+                out[key + tag + "accel"] = host(a)
+                kin, pot = g.lod_newmark_steps_direct(fac[tag], *ptr, dt, STEPS, u.data_ptr(), v.data_ptr(), a.data_ptr(), beta=beta,
+                                                      n_rhs=n, d_load=L.data_ptr(), load_step_stride=nrow * n, damp_mass=dm,
+                                                      damp_stiff=ds)
+                for nm, arr in (("u", host(u)), ("v", host(v)), ("a", host(a)), ("kinetic", kin), ("potential", pot)):
                     out[key + tag + nm] = arr
     np.savez(path, **out)
     print("%d arrays -> %s" % (len(out), path))
