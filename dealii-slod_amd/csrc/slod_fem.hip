@@ -119,8 +119,12 @@ namespace
   // fine FEM reference solve (the reference uses CG + AMG, LOD.cc:1070-1075).  Levels halve the grid
   // while the number of elements per side is even; bilinear interpolation P, restriction P^T, Galerkin
   // coarse operators P^T A P (again 9-point stencils), damped-Jacobi smoothing with the same number
-  // of sweeps before and after the coarse correction (a symmetric positive definite preconditioner).
-  // Dirichlet nodes (all four sides) carry 0 on every level and are no unknowns.
+  // of sweeps before and after the coarse correction (a symmetric preconditioner).  It is positive definite
+  // because every level damps with omega_l = min(0.8, 1.6 / ||D_l^-1 A_l||_inf), D_l the diagonal (s = 1) or the
+  // 2 x 2 node blocks (s = 2): omega_l lambda_max(D_l^-1 A_l) <= 1.6 < 2 by the row sums of the level's own
+  // planes (k_mg_rowsum).  Nothing else bounds lambda_max: Galerkin levels of a high-contrast field exceed the
+  // 1.5 of a Q1 Laplacian (1.63 scalar, 3.2 for elasticity at contrast 1e4), and a constant 0.8 then makes the
+  // V-cycle indefinite.  Dirichlet nodes (all four sides) carry 0 on every level and are no unknowns.
   __device__ __forceinline__ double mg_w(int f, int c) // 1-D bilinear weight of coarse node c at fine node f
   {
     const int dlt = f - 2 * c;
@@ -191,13 +195,58 @@ namespace
         }
     return acc;
   }
-  // xo = xi + omega D^-1 (b - A xi)   (zero_in: xi = 0)
-  __global__ void k_mg_smooth(int N, int s, const double *st, const double *b, const double *xi, double *xo, double omega,
-                              int zero_in)
+  // *out = max(*out, ||D^-1 A||_inf) over the interior rows, D the s x s node blocks: one thread per node.  A maximum
+  // of non-negative doubles is the maximum of their bit patterns and does not depend on the order of the atomics.
+  __global__ void k_mg_rowsum(int N, int s, const double *st, unsigned long long *out)
+  {
+    const int np = N + 1, nn = np * np, node = blockIdx.x * 256 + threadIdx.x;
+    double    m = 0.0;
+    if (node < nn)
+      {
+        const int ix = node % np, iy = node / np;
+        if (!(ix == 0 || iy == 0 || ix == N || iy == N))
+          {
+            const double d00 = st[(size_t)((4 * s + 0) * s + 0) * nn + node];
+            double       d01 = 0.0, d10 = 0.0, d11 = 1.0;
+            if (s == 2)
+              {
+                d01 = st[(size_t)((4 * s + 0) * s + 1) * nn + node];
+                d10 = st[(size_t)((4 * s + 1) * s + 0) * nn + node];
+                d11 = st[(size_t)((4 * s + 1) * s + 1) * nn + node];
+              }
+            const double det = d00 * d11 - d01 * d10;
+            double       sum[2] = {0.0, 0.0};
+            for (int dy = -1; dy <= 1; ++dy)
+              for (int dx = -1; dx <= 1; ++dx)
+                {
+                  const int jx = ix + dx, jy = iy + dy;
+                  if (jx == 0 || jy == 0 || jx == N || jy == N)
+                    continue; // constrained neighbour: no column
+                  const int dir = (dy + 1) * 3 + dx + 1;
+                  for (int b = 0; b < s; ++b)
+                    {
+                      const double a0 = st[(size_t)((dir * s + 0) * s + b) * nn + node];
+                      const double a1 = s == 2 ? st[(size_t)((dir * s + 1) * s + b) * nn + node] : 0.0;
+                      sum[0] += fabs((d11 * a0 - d01 * a1) / det);
+                      sum[1] += fabs((d00 * a1 - d10 * a0) / det);
+                    }
+                }
+            m = fmax(sum[0], sum[1]);
+          }
+      }
+    for (int off = 32; off > 0; off >>= 1)
+      m = fmax(m, __shfl_xor(m, off, 64));
+    if ((threadIdx.x & 63) == 0 && m > 0.0)
+      atomicMax(out, (unsigned long long)__double_as_longlong(m));
+  }
+  // xo = xi + omega D^-1 (b - A xi)   (zero_in: xi = 0); omega = min(0.8, 1.6 / *rowsum), or 1 without a row sum
+  __global__ void k_mg_smooth(int N, int s, const double *st, const double *b, const double *xi, double *xo,
+                              const double *rowsum, int zero_in)
   {
     const int np = N + 1, nn = np * np, node = blockIdx.x * 256 + threadIdx.x;
     if (node >= nn)
       return;
+    const double omega = rowsum ? fmin(0.8, 1.6 / *rowsum) : 1.0;
     const int  ix = node % np, iy = node / np;
     const bool bnd = ix == 0 || iy == 0 || ix == N || iy == N;
     double     r[2] = {0.0, 0.0}, v[2] = {0.0, 0.0};
@@ -361,7 +410,7 @@ namespace
     struct Level
     {
       int     N;
-      double *st, *b, *x, *y;
+      double *st, *b, *x, *y, *rowsum; // rowsum: ||D^-1 A||_inf of the level (k_mg_rowsum), on the device
     };
     hipStream_t        st;
     int                s;
@@ -374,12 +423,14 @@ namespace
         {
           const size_t nnl = (size_t)(N + 1) * (N + 1);
           need += (N == NE ? 0 : (size_t)9 * s * s * nnl) + 3 * nnl * s;
-          lev.push_back({N, nullptr, nullptr, nullptr, nullptr});
+          lev.push_back({N, nullptr, nullptr, nullptr, nullptr, nullptr});
           if (N % 2 || N / 2 < 2)
             break;
         }
-      hipError_t e = mem.alloc(need);
+      hipError_t e = mem.alloc(need + lev.size());
       double    *q = mem.get();
+      if (e == hipSuccess)
+        e = hipMemsetAsync(q + need, 0, lev.size() * sizeof(double), st);
       for (size_t l = 0; l < lev.size() && e == hipSuccess; ++l)
         {
           const size_t nnl = (size_t)(lev[l].N + 1) * (lev[l].N + 1);
@@ -392,15 +443,18 @@ namespace
           if (l > 0)
             hipLaunchKernelGGL(k_mg_galerkin, dim3((unsigned)((nnl + 255) / 256)), dim3(256), 0, st, lev[l - 1].N, s, lev[l - 1].st,
                                lev[l].st);
+          lev[l].rowsum = mem.get() + need + l;
+          hipLaunchKernelGGL(k_mg_rowsum, dim3((unsigned)((nnl + 255) / 256)), dim3(256), 0, st, lev[l].N, s, lev[l].st,
+                             reinterpret_cast<unsigned long long *>(lev[l].rowsum));
         }
       return e == hipSuccess ? hipGetLastError() : e;
     }
 
-    // z = V-cycle(r): V(2,2), damped Jacobi (omega 0.8); the coarsest level by a fixed, even number of sweeps
+    // z = V-cycle(r): V(2,2), damped (block) Jacobi with the omega_l of the level; the coarsest level by a fixed, even
+    // number of sweeps, undamped when it has one interior node (N = 2: the first sweep solves it)
     void cycle(const double *rin, double *zout) const
     {
-      const double omega = 0.8;
-      const int    nu = 2;
+      const int nu = 2;
       for (size_t l = 0; l < lev.size(); ++l)
         {
           const Level  &L = lev[l];
@@ -411,7 +465,8 @@ namespace
           double       *xi = L.x, *xo = L.y;
           for (int k = 0; k < sweeps; ++k)
             {
-              hipLaunchKernelGGL(k_mg_smooth, dim3(nb), dim3(256), 0, st, L.N, s, L.st, bl, xi, xo, L.N <= 2 ? 1.0 : omega, k == 0 ? 1 : 0);
+              hipLaunchKernelGGL(k_mg_smooth, dim3(nb), dim3(256), 0, st, L.N, s, L.st, bl, xi, xo, L.N <= 2 ? nullptr : L.rowsum,
+                                 k == 0 ? 1 : 0);
               std::swap(xi, xo);
             }
           // sweeps is even: the current iterate is back in L.x
@@ -430,7 +485,7 @@ namespace
           double *xi = L.x, *xo = L.y;
           for (int k = 0; k < nu; ++k)
             {
-              hipLaunchKernelGGL(k_mg_smooth, dim3(nb), dim3(256), 0, st, L.N, s, L.st, bl, xi, xo, omega, 0);
+              hipLaunchKernelGGL(k_mg_smooth, dim3(nb), dim3(256), 0, st, L.N, s, L.st, bl, xi, xo, L.rowsum, 0);
               std::swap(xi, xo);
             }
         }
@@ -506,9 +561,12 @@ static int fem_solve_grid(slod_handle *h, const char *who, int NE, const double 
         e = slod_launch_assemble(s, a, 1, st);
     }
   const char *pc_env = std::getenv("SLOD_FEM_PRECOND");
-  // (scalar problems: with two independent high-contrast Lame fields the point/block-Jacobi smoothed
-  // V-cycle is a worse preconditioner than plain Jacobi -- 4500 against 1376 iterations on the 65^2
-  // grid -- so vector problems keep Jacobi unless SLOD_FEM_PRECOND=mg asks for it)
+  // (Scalar problems take the V-cycle, vector problems keep Jacobi unless SLOD_FEM_PRECOND=mg asks for it.  The
+  // 4500 against 1376 iterations once measured for elasticity at contrast 1e4 on the 65^2 grid were those of an
+  // indefinite preconditioner: with a constant omega = 0.8 and lambda_max(D^-1 A) up to 3.2 on the block-Jacobi
+  // levels, 0.8 lambda_max > 2.  With the per-level omega_l of MgHierarchy the same solve takes 104 iterations
+  // against Jacobi's 1376 (tests/test_gpu_lod_system.py).  Which of the two is faster for vector problems is a
+  // question of time per iteration and has not been decided: the default is unchanged.)
   const bool  want_mg = pc_env ? !strcmp(pc_env, "mg") : s == 1;
   const bool  use_mg = want_mg && NE >= 4 && NE % 2 == 0;
   MgHierarchy mg{st, s};

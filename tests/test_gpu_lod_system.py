@@ -15,6 +15,7 @@ import pytest
 
 from conftest import GOLDEN, make_fields
 from lod_cases import _fem_reference, _global_dense, _lod_matrix, _mk, _rows_to_dense, _torch, _upload
+from mg_cases import PREDICTED_65
 
 pytestmark = pytest.mark.gpu
 
@@ -321,6 +322,16 @@ def test_fem_multigrid_preconditioner(so, spacedim, monkeypatch):
         assert 0 < it_mg < it_j / 3, (it_mg, it_j)
     else:   # vector problems keep Jacobi by default (the V-cycle is opt-in there: SLOD_FEM_PRECOND=mg)
         assert it_mg == it_j
+        # asked for, the V-cycle reaches the same solution in fewer iterations: at most twice the share of Jacobi's
+        # count that the CPU reference predicts for this grid (mg_cases.PREDICTED_65, pinned by test_mg_reference.py)
+        monkeypatch.setenv("SLOD_FEM_PRECOND", "mg")
+        u_v = torch.zeros_like(rhs)
+        it_v, res_v = g.fem_solve(rhs.data_ptr(), u_v.data_ptr(), 1e-12, 20000)
+        print("elasticity with SLOD_FEM_PRECOND=mg: %d iterations (reference %d), Jacobi-CG %d (reference %d)"
+              % (it_v, PREDICTED_65["mg"], it_j, PREDICTED_65["jacobi"]))
+        assert res_v <= 1e-12
+        assert float((u_v - u_j).abs().max()) <= 1e-8 * float(u_j.abs().max())
+        assert 0 < it_v < it_j and it_v <= 2.0 * PREDICTED_65["mg"] / PREDICTED_65["jacobi"] * it_j, (it_v, it_j)
     print("fine FEM solve, %d components, 65^2 nodes, contrast 1e4: multigrid-CG %d iterations, Jacobi-CG %d" % (spacedim, it_mg, it_j))
 
 
