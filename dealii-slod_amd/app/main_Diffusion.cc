@@ -1,6 +1,7 @@
 // Counterpart of reference app/main_Diffusion.cc for the basis-construction path:
 //   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare] [--coarse] [--loads K]
 //                  [--heat STEPS DT] [--eigs K] [--shift SIGMA] [--wave STEPS DT] [--direct] [--ensemble K] [--perturb K]
+//                  [--reuse-factor] [--precond-member J]
 //                  [--member K] [--ldl]
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
 // file name it dumps, per patch, phi and psi in patch-lexicographic order (parity tests).
@@ -62,6 +63,13 @@
 // row or column) and the system is solved (f = 1).  Then a second problem with the changed coefficient is built from
 // scratch.  Prints the dirty count "D of NP", max |A_refresh - A_rebuild| over the block rows and max |u_refresh -
 // u_rebuild| of the coarse solutions, each with the scale it is relative to.
+// --perturb K --reuse-factor: sym(A_LOD) is factored before the flip (banded Cholesky), and after the refresh the refreshed
+// system is also solved by CG preconditioned by that stale factor (slod_lod_solve_multi_precond).  After the lines of
+// --perturb: "stale factor as preconditioner: dirty patches = D of NP, PCG iterations = I, Jacobi-CG iterations = J" (J: the
+// recurrence of slod_lod_solve_multi on the same symmetrised system) and max |u_pcg - u_rebuild| with its scale.
+// --ensemble K --precond-member J: after the lines of --ensemble, the symmetrised systems of all members by CG
+// preconditioned by the factor of member J alone (slod_lod_solve_ensemble_precond): per member "member k: PCG iterations
+// = I, Jacobi-CG iterations = J" (J: slod_lod_solve_ensemble on the same systems).
 #include "../host/Diffusion.h"
 
 #include <algorithm>
@@ -141,7 +149,8 @@ int main(int argc_all, char **argv_all)
 {
   // --compare and --coarse are taken out wherever they stand; the positional arguments keep their meaning
   bool               compare = false, coarse = false, direct = false, ldl = false;
-  int                n_loads = 0, heat_steps = 0, n_eigs = 0, wave_steps = 0, n_members = 0, n_perturb = 0, member = 0;
+  int                n_loads = 0, heat_steps = 0, n_eigs = 0, wave_steps = 0, n_members = 0, n_perturb = 0, member = 0, precond_member = -1;
+  bool               reuse_factor = false;
   double             heat_dt = 0.0, wave_dt = 0.0, shift = 0.0;
   std::vector<char *> args;
   for (int i = 0; i < argc_all; ++i)
@@ -175,6 +184,10 @@ int main(int argc_all, char **argv_all)
       member = std::atoi(argv_all[++i]);
     else if (i > 0 && !std::strcmp(argv_all[i], "--perturb") && i + 1 < argc_all)
       n_perturb = std::atoi(argv_all[++i]);
+    else if (i > 0 && !std::strcmp(argv_all[i], "--reuse-factor"))
+      reuse_factor = true;
+    else if (i > 0 && !std::strcmp(argv_all[i], "--precond-member") && i + 1 < argc_all)
+      precond_member = std::atoi(argv_all[++i]);
     else
       args.push_back(argv_all[i]);
   const int argc = (int)args.size();
@@ -343,6 +356,13 @@ int main(int argc_all, char **argv_all)
                         problem.ensemble_rel_residuals()[k]);
           std::printf("SLOD ensemble of %d: L2 norm of the mean = %.12e, of the standard deviation = %.12e\n", n_members,
                       problem.norms_ensemble_mean().l2[0], problem.norms_ensemble_deviation().l2[0]);
+          if (precond_member >= 0)
+            {
+              problem.solve_ensemble_precond((unsigned int)precond_member);
+              for (int k = 0; k < n_members; ++k)
+                std::printf("member %d: PCG iterations = %d, Jacobi-CG iterations = %d\n", k, problem.ensemble_precond_iterations()[k],
+                            problem.ensemble_precond_jacobi_iterations()[k]);
+            }
           if ((heat_steps > 0 || wave_steps > 0 || n_eigs > 0) && direct)
             problem.assemble_mass_matrix_ensemble();
           if (heat_steps > 0 && direct)
@@ -429,9 +449,13 @@ int main(int argc_all, char **argv_all)
             problem.assemble_global_matrix();
           if (!compare && heat_steps <= 0 && wave_steps <= 0)
             problem.assemble_and_solve_fem_problem(); // the load C^T f of solve(); f = 1 does not see the coefficient
+          if (reuse_factor)
+            problem.factor_for_reuse();
           problem.flip_coefficient_cells((unsigned int)n_perturb);
           const unsigned int n_dirty = problem.refresh_after_coefficient_change();
           problem.solve();
+          if (reuse_factor)
+            problem.solve_precond();
           const std::vector<double> a_refresh = problem.lod_matrix_values(), u_refresh = problem.lod_solution();
           std::printf("perturbation of %d coefficient cells: dirty patches = %u of %u\n", n_perturb, n_dirty,
                       (unsigned int)problem.get_patches().size());
@@ -458,6 +482,14 @@ int main(int argc_all, char **argv_all)
           const double a_diff = max_diff(a_refresh, a_rebuild, a_scale), u_diff = max_diff(u_refresh, u_rebuild, u_scale);
           std::printf("  max |A_refresh - A_rebuild| = %.6e  (max |A_rebuild| = %.6e)\n", a_diff, a_scale);
           std::printf("  max |u_refresh - u_rebuild| = %.6e  (max |u_rebuild| = %.6e)\n", u_diff, u_scale);
+          if (reuse_factor)
+            {
+              const double p_diff = max_diff(problem.precond_solution(), u_rebuild, u_scale);
+              std::printf("stale factor as preconditioner: dirty patches = %u of %u, PCG iterations = %d, Jacobi-CG iterations = %d\n",
+                          n_dirty, (unsigned int)problem.get_patches().size(), problem.precond_iterations(),
+                          problem.precond_jacobi_iterations());
+              std::printf("  max |u_pcg - u_rebuild| = %.6e  (max |u_rebuild| = %.6e)\n", p_diff, u_scale);
+            }
         }
     }
   catch (std::exception &exc)

@@ -193,6 +193,19 @@ struct SlodLodWork
   // leading dimension ld_m and column k is solved with matrix k; else ld_m is not used.
   hipError_t solve(slod_handle *h, const double *d_values, const uint32_t *d_cols, const double *d_rhs, size_t ld_rhs, double *d_u,
                    size_t ld_u, double rel_tol, int max_iterations, size_t ld_m = 1);
+  // The same for CG preconditioned by a banded factor (slod_lod_pcg.hip): take_precond() places the pieces of that
+  // recurrence, solve_precond() runs it with  z = P^-1 r  by the sweeps of f, on its one member for every column or, when f
+  // has several, with column k on member k.  matrix_per_column: d_values is an ensemble matrix, column k reads matrix k.
+  // Synchronises h->stream on every path.  The stop rule and the counters run on the device; its, res, last and worst are
+  // filled as by solve().  A column whose p.Ap is not > 0 or whose r.r is not finite freezes and the others finish: the
+  // lowest such column is bad_col (-1: none), with the iteration it met it in, which of the two it was, and the value.
+  void       take_precond(SlodCarver &c, const slod_handle *h);
+  hipError_t solve_precond(slod_handle *h, const slod_lod_factor *f, const double *d_values, const uint32_t *d_cols,
+                           const double *d_rhs, size_t ld_rhs, double *d_u, size_t ld_u, double rel_tol, int max_iterations,
+                           bool matrix_per_column = false, size_t ld_m = 1);
+  int        bad_col = -1, bad_it = 0;
+  bool       bad_pAp = false;
+  double     bad_value = 0.0;
   // what a time loop reports of step k, HOST arrays, either may be NULL: the maxima over the columns of the last solve
   void record(int k, int *iterations, double *rel_residual) const
   {
@@ -214,6 +227,7 @@ private:
   SlodDevBuf<double> work;
   SlodDevBuf<int>    active;
   double            *cg = nullptr; // the pieces of the solve
+  double            *pcg = nullptr; // the pieces of the preconditioned solve
   bool               per_col = false; // as given to take_solve
 };
 // Y_k = A_k X_k on an ensemble matrix, the launch of slod_lod_apply_ensemble (slod_lod_ensemble.hip)

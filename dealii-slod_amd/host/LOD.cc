@@ -383,6 +383,86 @@ namespace slod
           "slod_lod_solve");
   }
 
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::factor_for_reuse()
+  {
+    if (!d_lod_values)
+      throw std::runtime_error("factor_for_reuse: assemble_global_matrix comes first");
+    const std::size_t n_words = patches.size() * (std::size_t)slod_lod_row_capacity(handle) * spacedim * spacedim;
+    if (!d_lod_sym)
+      d_lod_sym = device_alloc<double>(n_words);
+    check(slod_lod_matrix_symmetrize(handle, d_lod_values, d_lod_cols, d_lod_sym, nullptr), "slod_lod_matrix_symmetrize");
+    reuse_factor = factor_lod_matrix(d_lod_sym, false); // synchronises; this object destroys it
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_precond()
+  {
+    if (!reuse_factor || !d_fem_rhs)
+      throw std::runtime_error("solve_precond: factor_for_reuse and assemble_and_solve_fem_problem come first");
+    const unsigned int    n_patches = (unsigned int)patches.size();
+    const std::size_t     n_coarse = (std::size_t)n_patches * spacedim;
+    std::vector<uint32_t> rows(n_patches);
+    for (unsigned int p = 0; p < n_patches; ++p)
+      rows[p] = p;
+    if (!d_pcg_u) // u, the load and the Jacobi-CG solution, kept for the next call
+      d_pcg_u = device_alloc<double>(3 * n_coarse);
+    double *d_rhs = d_pcg_u + n_coarse, *d_jacobi_u = d_pcg_u + 2 * n_coarse;
+    check(slod_lod_matrix_symmetrize(handle, d_lod_values, d_lod_cols, d_lod_sym, nullptr), "slod_lod_matrix_symmetrize");
+    check(slod_lod_rhs(handle, rows.data(), n_patches, d_basis, basis_stride, d_fem_rhs, d_rhs, nullptr), "slod_lod_rhs");
+    check(slod_lod_solve_multi_precond(handle, reuse_factor, d_lod_sym, d_lod_cols, d_rhs, 1, 1, d_pcg_u, 1, lod_rel_tol,
+                                       lod_max_iterations, &lod_pcg_iterations, nullptr),
+          "slod_lod_solve_multi_precond");
+    check(slod_lod_solve_multi(handle, d_lod_sym, d_lod_cols, d_rhs, 1, 1, d_jacobi_u, 1, lod_rel_tol, lod_max_iterations,
+                               &lod_pcg_jacobi_iterations, nullptr),
+          "slod_lod_solve_multi");
+  }
+
+  template <int dim, int spacedim>
+  std::vector<double> LOD<dim, spacedim>::precond_solution() const
+  {
+    if (!d_pcg_u)
+      throw std::runtime_error("precond_solution: solve_precond comes first");
+    std::vector<double> v(patches.size() * (std::size_t)spacedim);
+    if (hipMemcpy(v.data(), d_pcg_u, v.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      throw std::runtime_error("precond_solution: download failed");
+    return v;
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_ensemble_precond(const unsigned int member)
+  {
+    const int K = (int)par.n_members;
+    if (!d_ens_values)
+      throw std::runtime_error("solve_ensemble_precond: solve_ensemble comes first");
+    if (member >= (unsigned int)K)
+      throw std::runtime_error("solve_ensemble_precond: no such member");
+    const std::size_t n_words = patches.size() * (std::size_t)slod_lod_row_capacity(handle) * spacedim * spacedim;
+    const std::size_t n_coarse = patches.size() * (std::size_t)spacedim, ld = (std::size_t)K;
+    if (!d_ens_sym)
+      d_ens_sym = device_alloc<double>(n_words * K);
+    if (!d_ens_pcg_u)
+      d_ens_pcg_u = device_alloc<double>(n_coarse * K);
+    double *d_u = d_ens_pcg_u;
+    check(slod_lod_matrix_symmetrize_ensemble(handle, d_ens_values, ld, d_ens_cols, K, d_ens_sym, ld, nullptr),
+          "slod_lod_matrix_symmetrize_ensemble");
+    // the factor of one member: the ensemble of the one member `member` inside the wider array; freed before returning
+    // (last_factor_info() keeps describing the factor of the caller's last direct loop)
+    slod_lod_factor *f = nullptr;
+    check(slod_lod_factor_create_ensemble(handle, d_ens_sym + member, ld, 1, d_ens_cols, nullptr, &f), "slod_lod_factor_create_ensemble");
+    factors.push_back(f); // so that a throw below does not leak it
+    lod_ens_pcg_iterations.assign(K, 0);
+    lod_ens_pcg_jacobi.assign(K, 0);
+    check(slod_lod_solve_ensemble_precond(handle, f, d_ens_sym, ld, d_ens_cols, d_ens_rhs, ld, K, d_u, ld, lod_rel_tol, lod_max_iterations,
+                                          lod_ens_pcg_iterations.data(), nullptr),
+          "slod_lod_solve_ensemble_precond");
+    check(slod_lod_solve_ensemble(handle, d_ens_sym, ld, d_ens_cols, d_ens_rhs, ld, K, d_u, ld, lod_rel_tol, lod_max_iterations,
+                                  lod_ens_pcg_jacobi.data(), nullptr),
+          "slod_lod_solve_ensemble");
+    factors.pop_back();
+    slod_lod_factor_destroy(f);
+  }
+
   // LOD.cc:1240-1260: u_LOD = C u_H, then error_LOD_FEMh.difference(u_h, u_LOD) in L2, H1, Linfty and energy
   template <int dim, int spacedim>
   void LOD<dim, spacedim>::compare_lod_with_fem()

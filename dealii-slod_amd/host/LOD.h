@@ -114,6 +114,17 @@ namespace slod
     void solve();
     // u_LOD = C u_H and the norms of u_h - u_LOD (error_LOD_FEMh.difference, LOD.cc:1240-1260)
     void compare_lod_with_fem();
+    // A factor that outlives a coefficient change.  factor_for_reuse(): the banded Cholesky factor of sym(A_LOD) as it
+    // stands (slod_lod_matrix_symmetrize, slod_lod_factor_create), kept by this object.  solve_precond(): the system of
+    // solve() on sym(A_LOD) as it stands then -- after refresh_after_coefficient_change() the refreshed matrix -- by CG
+    // preconditioned by the kept, by then stale, factor (slod_lod_solve_multi_precond, n_rhs = 1), and by Jacobi-CG
+    // (slod_lod_solve_multi) on the same system for the count next to it.  solve() itself stays on Jacobi-CG, and the K
+    // loads of solve_multi() have no preconditioned form here: that is slod_lod_solve_multi_precond with n_rhs = K.
+    void                factor_for_reuse();
+    void                solve_precond();
+    int                 precond_iterations() const { return lod_pcg_iterations; }
+    int                 precond_jacobi_iterations() const { return lod_pcg_jacobi_iterations; }
+    std::vector<double> precond_solution() const;
     // solve() for K load functions at once, after assemble_global_matrix() (the reference has a single load):
     // the fine load vectors of loads[k] sampled at the quadrature points, then C^T F, A_LOD U = C^T F and
     // U_fine = C U through slod_lod_rhs_multi / slod_lod_solve_multi / slod_lod_reconstruct_multi.
@@ -187,6 +198,12 @@ namespace slod
     const std::vector<double> &ensemble_rel_residuals() const { return lod_ens_residuals; }    // per member
     const slod_error_norms    &norms_ensemble_mean() const { return ens_mean_norms; }
     const slod_error_norms    &norms_ensemble_deviation() const { return ens_dev_norms; }
+    // solve_ensemble()'s systems, symmetrised (slod_lod_matrix_symmetrize_ensemble), by CG preconditioned by the banded
+    // Cholesky factor of member `member` alone, shared by all members (slod_lod_solve_ensemble_precond), and by
+    // slod_lod_solve_ensemble on the same systems for the counts next to it; after solve_ensemble()
+    void solve_ensemble_precond(const unsigned int member);
+    const std::vector<int> &ensemble_precond_iterations() const { return lod_ens_pcg_iterations; }        // per member
+    const std::vector<int> &ensemble_precond_jacobi_iterations() const { return lod_ens_pcg_jacobi; }     // per member
     // M_LOD of every member on the ensemble slab of solve_ensemble() (slod_lod_mass_matrix_ensemble, density 1); after
     // solve_ensemble()
     void assemble_mass_matrix_ensemble();
@@ -319,6 +336,11 @@ namespace slod
     slod_lod_factor_info           lod_factor_info{};
     slod_lod_factor_inertia_info   lod_factor_inertia{};
     double                        *d_lod_shifted = nullptr;
+    // factor_for_reuse, solve_precond, solve_ensemble_precond
+    slod_lod_factor *reuse_factor = nullptr;
+    double          *d_pcg_u = nullptr, *d_ens_pcg_u = nullptr;
+    int              lod_pcg_iterations = 0, lod_pcg_jacobi_iterations = 0;
+    std::vector<int> lod_ens_pcg_iterations, lod_ens_pcg_jacobi;
     // solve_multi: fine load vectors and reconstructions, field k at + k * fine_size
     double                       *d_multi_fem_rhs = nullptr, *d_multi_fine = nullptr;
     std::vector<int>              lod_multi_iterations;

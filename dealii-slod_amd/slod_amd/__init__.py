@@ -175,6 +175,10 @@ def load():
     lib.slod_lod_factor_create_ensemble.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, C.POINTER(C.c_int32), C.POINTER(vp)]
     lib.slod_lod_factor_get_info_member.argtypes = [vp, C.c_int, C.POINTER(FactorInfo)]
     lib.slod_lod_factor_solve_ensemble.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp]
+    lib.slod_lod_solve_multi_precond.argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_double, C.c_int,
+                                                 C.POINTER(C.c_int), dp]
+    lib.slod_lod_solve_ensemble_precond.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t,
+                                                    C.c_double, C.c_int, C.POINTER(C.c_int), dp]
     lib.slod_lod_theta_steps_ensemble_direct.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_double, C.c_double, C.c_int, C.c_int, vp,
                                                          C.c_size_t, vp, C.c_size_t, C.c_size_t]
     lib.slod_lod_inner_ensemble.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, dp, vp]
@@ -802,6 +806,37 @@ class Slod:
     def lod_factor_ldl_ensemble(self, d_values, d_cols, n_members, ld_m=None):
         """The LDL^T factors of the members of an ensemble matrix in one object (EnsembleFactor, .inertia(member))."""
         return EnsembleFactor(self, d_values, d_cols, n_members, ld_m, ldl=True)
+
+    # ---- CG preconditioned by a banded factor of a nearby matrix (stale after a refresh, shared by an ensemble) ----
+    def _precond_result(self, rc, its, res, n):
+        """(iterations, rel_residual) per column; a breakdown raises SlodError(-5) that carries both arrays."""
+        if rc < 0:
+            err = SlodError(rc, self.lib.slod_last_error(self.h).decode())
+            err.iterations, err.rel_residual = its[:max(n, 0)].copy(), res[:max(n, 0)].copy()
+            raise err
+        return its[:n], res[:n]
+
+    def lod_solve_multi_precond(self, factor, d_values, d_cols, d_rhs, ld_rhs, n_rhs, d_u, ld_u, rel_tol=1e-12,
+                                max_iterations=2000):
+        """A u_c = rhs_c by CG with z = P^-1 r on `factor` (one member, for all columns).  Returns (iterations,
+        rel_residual), one entry per column, the device's counters."""
+        its = np.zeros(max(n_rhs, 1), dtype=np.intc)
+        res = np.zeros(max(n_rhs, 1))
+        rc = self.lib.slod_lod_solve_multi_precond(self.h, _factor_ptr(factor), d_values, d_cols, d_rhs, ld_rhs, n_rhs, d_u, ld_u,
+                                                   rel_tol, max_iterations, its.ctypes.data_as(C.POINTER(C.c_int)), _dp(res))
+        return self._precond_result(rc, its, res, n_rhs)
+
+    def lod_solve_ensemble_precond(self, factor, d_values, d_cols, d_rhs, d_u, n_members, ld_m=None, ld_rhs=None, ld_u=None,
+                                   rel_tol=1e-12, max_iterations=2000):
+        """A_k u_k = rhs_k for every member by CG preconditioned by `factor`: of one member (shared by all) or of n_members
+        members (member k for column k).  Returns (iterations, rel_residual), one entry per member."""
+        its = np.zeros(max(n_members, 1), dtype=np.intc)
+        res = np.zeros(max(n_members, 1))
+        rc = self.lib.slod_lod_solve_ensemble_precond(
+            self.h, _factor_ptr(factor), d_values, n_members if ld_m is None else ld_m, d_cols, d_rhs,
+            n_members if ld_rhs is None else ld_rhs, n_members, d_u, n_members if ld_u is None else ld_u, rel_tol, max_iterations,
+            its.ctypes.data_as(C.POINTER(C.c_int)), _dp(res))
+        return self._precond_result(rc, its, res, n_members)
 
     def lod_theta_steps_ensemble_direct(self, factor, d_stiffness, d_cols, dt, theta, n_steps, n_members, d_u, ld_m=None,
                                         ld_u=None, d_load=None, ld_load=None, load_step_stride=0):

@@ -614,8 +614,9 @@ int slod_ensemble_moments(slod_handle *h, const double *d_fields, size_t ld_fine
  * factor) with the member on a grid axis; a single-problem call is the instance n_members = 1, ld = 1.  Every result
  * of member k has the bits of the single-problem call on member k's de-interleaved data.  The common argument checks are
  * those of the ensemble block above.  Newmark on an ensemble factor is the block after this one, the eigensolver on an
- * ensemble factor the one after that.  Not built: a CG ensemble stepper, refactoring after slod_lod_matrix_update,
- * members spread over ranks, several columns per member in a stepper. */
+ * ensemble factor the one after that.  Not built: a CG ensemble stepper, a partial refactor after slod_lod_matrix_update
+ * (the stale factor serves as a preconditioner: slod_lod_solve_ensemble_precond), members spread over ranks, several columns
+ * per member in a stepper. */
 /* Block rows of M_LOD of all num_patches patches for every member: member k's values are those of slod_lod_mass_matrix
  * with rows 0 .. num_patches-1 on its slab, bit for bit.  d_cols is written once.  d_rho NULL: density 1; ld_rho = 0: one
  * density [NE][NE] shared by all members; else member k's density at d_rho + k * ld_rho.  SLOD_ERR_ARGUMENT also for a
@@ -659,6 +660,54 @@ int slod_lod_factor_get_info_member(const slod_lod_factor *f, int member, slod_l
  * the factor's members; an ld below n_members * n_rhs. */
 int slod_lod_factor_solve_ensemble(slod_lod_factor *f, int first_member, int n_members, const double *d_rhs, size_t ld_rhs,
                                    int n_rhs, double *d_u, size_t ld_u, void *hip_stream);
+/* ---- CG preconditioned by a banded factor, stale or shared --------------------------------------
+ * A u_c = rhs_c by the recurrence of slod_lod_solve_multi with  z = P^-1 r  (the two sweeps of slod_lod_factor_solve on
+ * f_P, out of place) where that one has  z = D^-1 r.  f_P factors a matrix NEAR the one solved: the matrix before
+ * slod_lod_matrix_update changed a few block rows (P^-1 A is then the identity plus a perturbation whose rank is bounded
+ * by the rows that changed, and in exact arithmetic the iteration ends after rank + 1 steps whatever the contrast), one
+ * member of an ensemble for all members, the step matrix of another dt, or the matrix itself (iterative refinement: one
+ * or two iterations).  The reference has no counterpart (LOD.cc:990-998 runs CG + SSOR once).
+ * Every column starts from u = 0 and has scalars of its own; five launches per iteration for all columns.  The stop rule
+ * runs on the device in EVERY iteration: a column with r.r <= rel_tol^2 ||rhs_c||^2 (the recursive residual) is frozen
+ * and never written again, any other column counts the iteration; iterations[c] is that device counter.  The host reads
+ * the active words back every 4 iterations only to decide whether to go on launching: no output depends on that.  A zero
+ * column gives u = 0, 0 iterations, residual 0.  Returns the largest per-column count or a negative slod_status; reaching
+ * max_iterations is not an error.  iterations[c] and rel_residual[c] = ||r_c|| / ||rhs_c|| are HOST arrays (either may be
+ * NULL), filled on SLOD_ERR_NUMERIC too.
+ * f_P: a Cholesky factor, or an LDL^T factor all of whose pivots are positive (min_pivot > 0); any other LDL^T factor is
+ * refused, SLOD_ERR_ARGUMENT "<call>: the preconditioner must be positive definite ..".  slod_lod_solve_multi_precond
+ * takes a factor of one member and applies it to all columns.  slod_lod_solve_ensemble_precond (column k reads matrix k of
+ * the ensemble matrix d_values, ld_m apart) takes a factor of one member, shared by all members, or a factor of exactly
+ * n_members members, member k preconditioning column k; any other member count, a factor of another handle or row count
+ * and a NULL factor are refused in the words of the calls on a factor above.  The factor is checked last and only read.
+ * SLOD_ERR_NUMERIC: an active column met a p.Ap that is not > 0 (an indefinite matrix, NaN in the matrix) or an r.r that
+ * is not finite.  That column sets its status and freezes where it stands, the other columns finish, and slod_last_error
+ * reads "<call>: column c, iteration i: p.Ap = v is not > 0 .." ("member k" in the ensemble call) for the lowest such
+ * column.  The handle and the factor stay usable.  A p.Ap that underflows to exactly 0 on a column about to converge
+ * (rel_tol near 0) is reported the same way, where slod_lod_solve_multi takes a zero step: ask for no more than the
+ * arithmetic can give.
+ * Every sum has a fixed order (no atomics, no grid barrier): the bits of column c of d_u, iterations[c] and
+ * rel_residual[c] depend only on the column's matrix, the column's factor member and column c of d_rhs -- not on n_rhs,
+ * the column's position, an ld, the other columns, the read-back interval or the run.  Column k of the ensemble call
+ * equals slod_lod_solve_multi_precond(n_rhs = 1) on member k's de-interleaved matrix with the single factor of member k's
+ * preconditioner, as 64-bit words.  Entries c >= n_rhs of a row's ld are never read or written.  Device workspace of
+ * 4 * num_patches * s * n_rhs doubles and the partial sums, one allocation per call.  Runs on the handle's stream;
+ * synchronises.  SLOD_ERR_ARGUMENT (before any device work): NULL handle, array or factor; n_rhs / n_members < 1;
+ * max_iterations < 0; an ld below the column count.  SLOD_ERR_DEVICE without a usable GPU.
+ * Not built: a partial refactor of the band from the first dirty block column, this solve inside the time loops and the
+ * eigensolvers, warm starts, a block-Krylov method. */
+int slod_lod_solve_multi_precond(slod_handle *h, slod_lod_factor *f_P,
+                                 const double *d_values, const uint32_t *d_cols,
+                                 const double *d_rhs, size_t ld_rhs, int n_rhs, double *d_u, size_t ld_u,
+                                 double rel_tol, int max_iterations,
+                                 int *iterations /* HOST [n_rhs], may be NULL */,
+                                 double *rel_residual /* HOST [n_rhs], may be NULL */);
+int slod_lod_solve_ensemble_precond(slod_handle *h, slod_lod_factor *f_P,
+                                    const double *d_values, size_t ld_m, const uint32_t *d_cols,
+                                    const double *d_rhs, size_t ld_rhs, int n_members, double *d_u, size_t ld_u,
+                                    double rel_tol, int max_iterations,
+                                    int *iterations /* HOST [n_members], may be NULL */,
+                                    double *rel_residual /* HOST [n_members], may be NULL */);
 /* The loop of slod_lod_theta_steps_direct with one column per member: column k is advanced with matrix k of the ensemble
  * matrix d_stiffness (slod_lod_apply_ensemble) and member k of f_S, which factors
  * slod_lod_matrix_combine_ensemble(1, M, theta dt, A).  The loop is queued on the handle's stream and waited for once.
