@@ -2,7 +2,7 @@
 //   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare] [--coarse] [--loads K]
 //                  [--heat STEPS DT] [--eigs K] [--shift SIGMA] [--wave STEPS DT] [--direct] [--ensemble K] [--perturb K]
 //                  [--reuse-factor] [--precond-member J]
-//                  [--member K] [--ldl]
+//                  [--member K] [--ldl] [--harmonic K W0 W1 [--damping DM DS]]
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
 // file name it dumps, per patch, phi and psi in patch-lexicographic order (parity tests).
 // --compare (anywhere on the command line): after run(), the rest of the reference run() -- global
@@ -35,6 +35,11 @@
 // steps of the trapezoidal rule (Newmark gamma = 1/2, beta = 1/4, slod_lod_newmark_steps): one line per step with its
 // iterations, relative residual, kinetic and potential energy and the work u^T b (kinetic + potential = work from rest
 // under a constant load), then the fine-grid L2 norm of the reconstructed final state.
+// --harmonic K W0 W1 [--damping DM DS]: the steady response to the load Re(C^T f e^{i omega t}) (f = 1, A_LOD symmetrised) at K
+// frequencies evenly spaced in [W0, W1] with the Rayleigh damping C = DM M + DS A (default 0 0), by one
+// slod_lod_harmonic_response call (a complex symmetric banded LDL^T per frequency); one line per frequency, "harmonic J:
+// omega = .., growth = .., relative residual = .., amplitude = .., power = ..": the growth of the factor, the true residual,
+// (u^H M u)^(1/2) and the dissipated power omega u^H C u / 2.
 // --direct: the time loops of --heat and --wave run on a banded Cholesky factor of their matrix S instead of CG
 // (slod_lod_factor_create once, slod_lod_theta_steps_direct / slod_lod_newmark_steps_direct): one line "factor: n = ..,
 // half bandwidth = .., bytes = .., pivots in [.., ..]" per loop, then the same per-step lines without iterations and
@@ -149,6 +154,8 @@ int main(int argc_all, char **argv_all)
 {
   // --compare and --coarse are taken out wherever they stand; the positional arguments keep their meaning
   bool               compare = false, coarse = false, direct = false, ldl = false;
+  int                n_harmonic = 0;
+  double             harmonic_w0 = 0.0, harmonic_w1 = 0.0, damp_mass = 0.0, damp_stiff = 0.0;
   int                n_loads = 0, heat_steps = 0, n_eigs = 0, wave_steps = 0, n_members = 0, n_perturb = 0, member = 0, precond_member = -1;
   bool               reuse_factor = false;
   double             heat_dt = 0.0, wave_dt = 0.0, shift = 0.0;
@@ -177,6 +184,17 @@ int main(int argc_all, char **argv_all)
       {
         wave_steps = std::atoi(argv_all[++i]);
         wave_dt    = std::atof(argv_all[++i]);
+      }
+    else if (i > 0 && !std::strcmp(argv_all[i], "--harmonic") && i + 3 < argc_all)
+      {
+        n_harmonic  = std::atoi(argv_all[++i]);
+        harmonic_w0 = std::atof(argv_all[++i]);
+        harmonic_w1 = std::atof(argv_all[++i]);
+      }
+    else if (i > 0 && !std::strcmp(argv_all[i], "--damping") && i + 2 < argc_all)
+      {
+        damp_mass  = std::atof(argv_all[++i]);
+        damp_stiff = std::atof(argv_all[++i]);
       }
     else if (i > 0 && !std::strcmp(argv_all[i], "--ensemble") && i + 1 < argc_all)
       n_members = std::atoi(argv_all[++i]);
@@ -348,6 +366,25 @@ int main(int argc_all, char **argv_all)
                         problem.wave_potential()[k + 1], problem.wave_work()[k + 1]);
           std::printf("SLOD wave at T = %g: L2 norm = %.12e\n", wave_steps * wave_dt, problem.norms_wave().l2[0]);
         }
+      if (n_harmonic > 0)
+        {
+          if (!compare && heat_steps <= 0 && wave_steps <= 0)
+            {
+              if (n_loads <= 0 && n_eigs <= 0)
+                problem.assemble_global_matrix();
+              problem.assemble_and_solve_fem_problem();
+            }
+          if (heat_steps <= 0 && n_eigs <= 0 && wave_steps <= 0)
+            problem.assemble_mass_matrix();
+          std::vector<double> omegas((std::size_t)n_harmonic);
+          for (int k = 0; k < n_harmonic; ++k)
+            omegas[k] = n_harmonic > 1 ? harmonic_w0 + k * ((harmonic_w1 - harmonic_w0) / (n_harmonic - 1)) : harmonic_w0;
+          problem.solve_harmonic(omegas, damp_mass, damp_stiff);
+          for (int k = 0; k < n_harmonic; ++k)
+            std::printf("harmonic %d: omega = %.12e, growth = %.6e, relative residual = %.6e, amplitude = %.12e, power = %.12e\n",
+                        k + 1, omegas[k], problem.harmonic_growth()[k], problem.harmonic_residuals()[k],
+                        problem.harmonic_amplitude()[k], problem.harmonic_power()[k]);
+        }
       if (n_members > 0)
         {
           problem.solve_ensemble();
@@ -445,9 +482,9 @@ int main(int argc_all, char **argv_all)
         }
       if (n_perturb > 0)
         {
-          if (!compare && n_loads <= 0 && heat_steps <= 0 && n_eigs <= 0 && wave_steps <= 0)
+          if (!compare && n_loads <= 0 && heat_steps <= 0 && n_eigs <= 0 && wave_steps <= 0 && n_harmonic <= 0)
             problem.assemble_global_matrix();
-          if (!compare && heat_steps <= 0 && wave_steps <= 0)
+          if (!compare && heat_steps <= 0 && wave_steps <= 0 && n_harmonic <= 0)
             problem.assemble_and_solve_fem_problem(); // the load C^T f of solve(); f = 1 does not see the coefficient
           if (reuse_factor)
             problem.factor_for_reuse();

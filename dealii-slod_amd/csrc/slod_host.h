@@ -239,7 +239,12 @@ void slod_lod_apply_ensemble_launch(const slod_handle *h, hipStream_t st, const 
 // then the row map, which all members share, and a status word per member.  kind SLOD_FACTOR_LDL: S = L D L^T without
 // pivoting (k_ldl_column); the diagonal tiles hold the unit lower triangular L_II, piv is D (signed), dinv 1 / D, and a
 // member has two norms behind its pivots (||S||_inf, || |L| |D| |L^T| ||_inf) and two work vectors behind dinv.
-enum slod_factor_kind { SLOD_FACTOR_CHOLESKY = 0, SLOD_FACTOR_LDL = 1 };
+// kind SLOD_FACTOR_ZLDL: the complex symmetric S_k = alpha_k A + beta_k B = L D L^T (plain transpose, k_zldl_column) of
+// slod_lod_factor_create_zldl.  Every array of a member is two planes, real then imaginary, in the layout of the real
+// factor: band (im_band doubles apart), diagonal tiles (im_diag), piv = D (im_vec; the two norms follow the imaginary
+// plane), dinv = 1 / D (im_vec; the two work vectors follow).  coef: (alpha_re, alpha_im, beta_re, beta_im) per member,
+// behind the last member.  member_min / member_max and the inertia's pivot range are those of |D|.
+enum slod_factor_kind { SLOD_FACTOR_CHOLESKY = 0, SLOD_FACTOR_LDL = 1, SLOD_FACTOR_ZLDL = 2 };
 struct slod_lod_factor_inertia_host // HOST, per member of an LDL^T factor: slod_lod_factor_inertia_info of include/slod.h
 {
   int    n_negative = 0, n_positive = 0;
@@ -257,14 +262,37 @@ struct slod_lod_factor
   std::vector<double> member_min, member_max;           // HOST [n_members]
   double             *band = nullptr, *diag = nullptr, *piv = nullptr, *dinv = nullptr;
   int                *rowmap = nullptr, *status = nullptr;
+  size_t              im_band = 0, im_diag = 0, im_vec = 0; // SLOD_FACTOR_ZLDL: from a real plane to its imaginary one
+  double             *coef = nullptr;                      // SLOD_FACTOR_ZLDL: DEVICE [n_members][4]
   SlodDevBuf<char>    mem;
 };
+// The parts of slod_lod_factor_create_zldl for a caller that queues more work behind the factorisation before it waits
+// (slod_lod_harmonic.hip).  launch: the allocation and every kernel on st, nothing read back; alpha, beta HOST
+// [n_members][2], read before it returns.  finish: after solves on the members were queued at will, the one read-back and
+// wait, then the host side: bad_pivot (may be NULL), the error text "<who>: <what> <first + k>: pivot r of n is zero or
+// not finite (re, im)" with SLOD_ERR_NUMERIC, or the norms and pivot ranges of every member.  Arguments are checked by
+// the caller.  A failed member's band holds unfinished values: solves on it fault nothing and mean nothing.
+struct SlodZFactorBuild
+{
+  slod_lod_factor     f;
+  std::vector<double> piv, coef; // HOST: the read-back, the coefficients on their way up
+  std::vector<int>    bad;
+};
+int slod_lod_zfactor_launch(slod_handle *h, hipStream_t st, const char *who, const double *d_a, const double *d_b,
+                            const uint32_t *d_cols, const double *alpha, const double *beta, int n_members, SlodZFactorBuild *z);
+int slod_lod_zfactor_finish(slod_handle *h, hipStream_t st, const char *who, const char *what, int first, SlodZFactorBuild *z,
+                            int32_t *bad_pivot);
+// The launch of slod_lod_factor_solve_complex; arguments are checked by the caller
+void slod_lod_zfactor_solve_launch(const slod_lod_factor *f, hipStream_t st, int first_member, int n_members, const double *d_rhs_re,
+                                   const double *d_rhs_im, size_t ld_rhs, int n_rhs, bool shared_rhs, double *d_u_re, double *d_u_im,
+                                   size_t ld_u);
 // The launch of slod_lod_factor_solve_ensemble for the time loops on a factor (slod_lod_time.hip, slod_lod_wave.hip):
 // member first_member + k solves the columns k n_rhs .. k n_rhs + n_rhs - 1; arguments are checked by the caller
 void slod_lod_factor_solve_launch(const slod_lod_factor *f, hipStream_t st, const double *d_rhs, size_t ld_rhs, int n_rhs, double *d_u,
                                   size_t ld_u, int first_member = 0, int n_members = 1);
 // SLOD_ERR_ARGUMENT, "<who>: NULL factor", "<who>: factor of another handle / row count" or "<who>: factor of another
-// member count" (the time loops on one matrix take a factor of one member); else SLOD_OK
+// member count" (the time loops on one matrix take a factor of one member) or "<who>: a complex factor
+// (slod_lod_factor_create_zldl) is solved by slod_lod_factor_solve_complex"; else SLOD_OK
 int slod_lod_factor_check(const slod_handle *h, const char *who, const slod_lod_factor *f, int n_members = 1);
 // ---- what the loops of the LOD space (slod_lod_time.hip, slod_lod_wave.hip) are written on, once per scheme
 // The operator of a column of a coarse multi-vector: one matrix for all columns, or (per_col) for column k member k of an

@@ -1046,6 +1046,52 @@ namespace slod
   }
 
   template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_harmonic(const std::vector<double> &omegas, const double damp_mass, const double damp_stiff)
+  {
+    if (!d_lod_mass || !d_fem_rhs)
+      throw std::runtime_error("solve_harmonic: assemble_mass_matrix and assemble_and_solve_fem_problem come first");
+    if (omegas.empty())
+      throw std::runtime_error("solve_harmonic: no frequency");
+    const unsigned int n_patches = (unsigned int)patches.size();
+    const std::size_t  n_coarse = (std::size_t)n_patches * spacedim, K = omegas.size();
+    const int          cap = slod_lod_row_capacity(handle);
+    check(cap, "slod_lod_row_capacity");
+    std::vector<uint32_t> rows(n_patches);
+    for (unsigned int p = 0; p < n_patches; ++p)
+      rows[p] = p;
+    if (!d_lod_sym)
+      d_lod_sym = device_alloc<double>((std::size_t)n_patches * cap * spacedim * spacedim);
+    if (harmonic_capacity < K) // (an earlier, smaller buffer stays with the object until it is destroyed)
+      {
+        d_harmonic        = device_alloc<double>((1 + 2 * K) * n_coarse);
+        harmonic_capacity = K;
+      }
+    // the response interleaved [row][frequency], as the call writes it
+    double *d_b = d_harmonic, *d_ur = d_b + n_coarse, *d_ui = d_ur + K * n_coarse;
+    check(slod_lod_matrix_symmetrize(handle, d_lod_values, d_lod_cols, d_lod_sym, nullptr), "slod_lod_matrix_symmetrize");
+    check(slod_lod_rhs(handle, rows.data(), n_patches, d_basis, basis_stride, d_fem_rhs, d_b, nullptr), "slod_lod_rhs");
+    lod_harmonic_growth.assign(K, 0.0);
+    lod_harmonic_residuals.assign(K, 0.0);
+    check(slod_lod_harmonic_response(handle, d_lod_sym, d_lod_mass, d_lod_cols, damp_mass, damp_stiff, omegas.data(), (int)K, d_b,
+                                     nullptr, 1, 1, d_ur, d_ui, K, lod_harmonic_residuals.data(), lod_harmonic_growth.data()),
+          "slod_lod_harmonic_response");
+    // u^H M u and u^H A u: the two planes add
+    std::vector<double> q[4] = {std::vector<double>(K), std::vector<double>(K), std::vector<double>(K), std::vector<double>(K)};
+    check(slod_lod_inner_multi(handle, d_lod_mass, d_lod_cols, d_ur, K, d_ur, K, (int)K, q[0].data(), nullptr), "slod_lod_inner_multi");
+    check(slod_lod_inner_multi(handle, d_lod_mass, d_lod_cols, d_ui, K, d_ui, K, (int)K, q[1].data(), nullptr), "slod_lod_inner_multi");
+    check(slod_lod_inner_multi(handle, d_lod_sym, d_lod_cols, d_ur, K, d_ur, K, (int)K, q[2].data(), nullptr), "slod_lod_inner_multi");
+    check(slod_lod_inner_multi(handle, d_lod_sym, d_lod_cols, d_ui, K, d_ui, K, (int)K, q[3].data(), nullptr), "slod_lod_inner_multi");
+    lod_harmonic_amplitude.assign(K, 0.0);
+    lod_harmonic_power.assign(K, 0.0);
+    for (std::size_t k = 0; k < K; ++k)
+      {
+        const double uMu = q[0][k] + q[1][k], uAu = q[2][k] + q[3][k];
+        lod_harmonic_amplitude[k] = std::sqrt(uMu);
+        lod_harmonic_power[k]     = 0.5 * omegas[k] * (damp_mass * uMu + damp_stiff * uAu);
+      }
+  }
+
+  template <int dim, int spacedim>
   void LOD<dim, spacedim>::solve_wave(const unsigned int n_steps, const double dt, const double beta, const double gamma,
                                       const bool direct)
   {

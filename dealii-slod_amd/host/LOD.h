@@ -188,6 +188,16 @@ namespace slod
     const std::vector<double> &wave_potential() const { return lod_wave_potential; }
     const std::vector<double> &wave_work() const { return lod_wave_work; }
     const slod_error_norms    &norms_wave() const { return wave_norms; }
+    // The steady response to the harmonic load Re(b e^{i omega t}), b the load of solve(), with the Rayleigh damping
+    // C = damp_mass M + damp_stiff sym(A): (1 + i omega damp_stiff) sym(A) u + (i omega damp_mass - omega^2) M u = b for every
+    // omega of the sweep in one slod_lod_harmonic_response call; after assemble_mass_matrix() and
+    // assemble_and_solve_fem_problem().  Per frequency the growth of its factor, the true relative residual, the amplitude
+    // (u_r^T M u_r + u_i^T M u_i)^(1/2) and the dissipated power omega u^H C u / 2, both by slod_lod_inner_multi.
+    void solve_harmonic(const std::vector<double> &omegas, const double damp_mass, const double damp_stiff);
+    const std::vector<double> &harmonic_growth() const { return lod_harmonic_growth; }       // per frequency
+    const std::vector<double> &harmonic_residuals() const { return lod_harmonic_residuals; }
+    const std::vector<double> &harmonic_amplitude() const { return lod_harmonic_amplitude; }
+    const std::vector<double> &harmonic_power() const { return lod_harmonic_power; }
     // The LOD systems of all par.n_members coefficient realisations with the load f = 1, after run() (the reference
     // solves one problem, LOD.cc:976-1002): the coefficients of members 1 .. K-1, one plan over all K * n_patches bases
     // into an ensemble slab on the device, then slod_lod_matrix_ensemble, slod_lod_rhs_ensemble (one load shared),
@@ -331,6 +341,10 @@ namespace slod
     std::vector<int>    lod_wave_iterations;
     std::vector<double> lod_wave_residuals, lod_wave_kinetic, lod_wave_potential, lod_wave_work;
     slod_error_norms    wave_norms{};
+    // solve_harmonic: the load and the two planes of the response (1 + 2 n_freq coarse vectors)
+    double             *d_harmonic = nullptr;
+    std::size_t         harmonic_capacity = 0;
+    std::vector<double> lod_harmonic_growth, lod_harmonic_residuals, lod_harmonic_amplitude, lod_harmonic_power;
     // factor_lod_matrix: the factors this object owns, the matrix S of a direct time loop
     std::vector<slod_lod_factor *> factors;
     slod_lod_factor_info           lod_factor_info{};

@@ -198,6 +198,10 @@ def load():
     lib.slod_lod_eigs_shift_ensemble_direct.argtypes = [vp, vp, C.c_double, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_int, C.c_int,
                                                         C.c_int, C.c_int, vp, C.c_size_t, C.c_double, C.c_int, dp, dp,
                                                         C.POINTER(C.c_int)]
+    lib.slod_lod_factor_create_zldl.argtypes = [vp, vp, vp, vp, dp, dp, C.c_int, C.POINTER(C.c_int32), C.POINTER(vp)]
+    lib.slod_lod_factor_solve_complex.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, C.c_size_t, vp]
+    lib.slod_lod_harmonic_response.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, dp, C.c_int, vp, vp, C.c_size_t, C.c_int,
+                                               vp, vp, C.c_size_t, dp, dp]
     lib.slod_update_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, C.c_int, C.c_size_t, C.c_int, vp]
     lib.slod_dirty_patches.argtypes = [vp, vp, u32p, C.c_size_t]
     lib.slod_plan_create_dirty.argtypes = [vp, C.c_uint32, vp, C.POINTER(vp)]
@@ -429,6 +433,44 @@ class EnsembleFactor(Factor):
         K = self.n_members - first_member if n_members is None else n_members
         self.slod._check(self.lib.slod_lod_factor_solve_ensemble(self.f, first_member, K, d_rhs, K * n_rhs if ld_rhs is None else ld_rhs,
                                                                  n_rhs, d_u, K * n_rhs if ld_u is None else ld_u, stream))
+
+
+class ComplexFactor(EnsembleFactor):
+    """slod_lod_factor of slod_lod_factor_create_zldl: the complex symmetric S_k = alpha_k A + beta_k B = L D L^T of every
+    member k in one object.  alpha, beta: complex scalars or sequences of n_members.  .info / .member_info(k) give the
+    range of |D|, .inertia(k) the two norms (n_negative = n_positive = -1), .bad_pivot as EnsembleFactor."""
+
+    def __init__(self, slod, d_a, d_b, d_cols, alpha, beta):
+        self.slod, self.lib = slod, slod.lib
+        self.alpha = np.atleast_1d(np.asarray(alpha, dtype=np.complex128)).copy()
+        self.beta = np.atleast_1d(np.asarray(beta, dtype=np.complex128)).copy()
+        if self.alpha.shape != self.beta.shape or self.alpha.ndim != 1:
+            raise ValueError("alpha and beta: one complex number per member each")
+        self.n_members = n_members = len(self.alpha)
+        self.f = C.c_void_p()
+        self.bad_pivot = np.full(max(n_members, 1), -1, dtype=np.int32)
+        rc = self.lib.slod_lod_factor_create_zldl(slod.h, d_a, d_b, d_cols, _dp(self.alpha.view(np.float64)),
+                                                  _dp(self.beta.view(np.float64)), n_members,
+                                                  self.bad_pivot.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(self.f))
+        if rc:
+            err = SlodError(rc, self.lib.slod_last_error(slod.h).decode())
+            err.bad_pivot = self.bad_pivot[:n_members].copy()
+            raise err
+        self.info = FactorInfo()
+        slod._check(self.lib.slod_lod_factor_get_info(self.f, C.byref(self.info)))
+        slod._factors.add(self)
+
+    def solve_complex(self, d_rhs_re, d_rhs_im, d_u_re, d_u_im, n_rhs=1, first_member=0, n_members=None, shared_rhs=False,
+                      ld_rhs=None, ld_u=None, stream=None):
+        """Member first_member + k solves the columns k * n_rhs .. of (d_rhs_re, d_rhs_im) into (d_u_re, d_u_im);
+        shared_rhs: every member reads the columns 0 .. n_rhs - 1.  d_rhs_im None: a real rhs.  ld defaults to
+        n_members * n_rhs (the shared rhs: n_rhs).  Asynchronous."""
+        K = self.n_members - first_member if n_members is None else n_members
+        if ld_rhs is None:
+            ld_rhs = n_rhs if shared_rhs else K * n_rhs
+        self.slod._check(self.lib.slod_lod_factor_solve_complex(self.f, first_member, K, d_rhs_re, d_rhs_im, ld_rhs, n_rhs,
+                                                                1 if shared_rhs else 0, d_u_re, d_u_im,
+                                                                K * n_rhs if ld_u is None else ld_u, stream))
 
 
 LodFactor = Factor   # the name of the object in the documents of the LDL^T factor: .inertia(member=0)
@@ -699,6 +741,24 @@ class Slod:
         """The LDL^T factor (no pivoting) of a symmetric matrix in block rows, indefinite or not: a Factor whose .info has
         the signed range of D and whose .inertia() counts the signs of D and measures the growth."""
         return Factor(self, d_values, d_cols, ldl=True)
+
+    def lod_factor_zldl(self, d_a, d_b, d_cols, alpha, beta):
+        """The complex symmetric LDL^T factors of S_k = alpha[k] A + beta[k] B (no pivoting), one member per pair of
+        complex coefficients: a ComplexFactor with .info, .inertia(member), .solve_complex(...) and .close()."""
+        return ComplexFactor(self, d_a, d_b, d_cols, alpha, beta)
+
+    def lod_harmonic_response(self, d_stiffness, d_mass, d_cols, omega, d_load_re, d_load_im, d_u_re, d_u_im, n_rhs=1,
+                              damp_mass=0.0, damp_stiff=0.0, ld_load=None, ld_u=None):
+        """S(omega_k) u = load for every frequency of omega, S = (1 + i omega damp_stiff) A + (i omega damp_mass - omega^2) M;
+        frequency k writes the columns k * n_rhs .. of (d_u_re, d_u_im).  d_load_im None: a real load.  Returns
+        (rel_residual[n_freq, n_rhs], growth[n_freq])."""
+        w = np.ascontiguousarray(np.atleast_1d(omega), dtype=np.float64)
+        res, growth = np.zeros((len(w), max(n_rhs, 1))), np.zeros(len(w))
+        self._check(self.lib.slod_lod_harmonic_response(
+            self.h, d_stiffness, d_mass, d_cols, damp_mass, damp_stiff, _dp(w), len(w), d_load_re, d_load_im,
+            n_rhs if ld_load is None else ld_load, n_rhs, d_u_re, d_u_im, len(w) * n_rhs if ld_u is None else ld_u,
+            _dp(res), _dp(growth)))
+        return res, growth
 
     def lod_theta_steps_direct(self, factor, d_stiffness, d_cols, dt, theta, n_steps, d_u, n_rhs=1, ld_u=None, d_load=None,
                                ld_load=None, load_step_stride=0):

@@ -855,6 +855,79 @@ int slod_lod_eigs_shift_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, do
                                         double *residuals     /* HOST [n_members * n_block] */,
                                         int    *member_status /* HOST [n_members] */);
 
+/* ---- the frequency response: complex symmetric banded LDL^T, a sweep of frequencies per call --------
+ * The steady response to a harmonic load: for  M u'' + C u' + A u = Re(b e^{i omega t})  with the Rayleigh damping of the
+ * Newmark calls, C = damp_mass M + damp_stiff A, the amplitude u solves
+ *   S(omega) u = b,   S(omega) = (1 + i omega damp_stiff) A + (i omega damp_mass - omega^2) M,
+ * complex SYMMETRIC (not Hermitian).  The third kind of factor is  S = L D L^T  with the plain transpose, complex 1 x 1
+ * pivots and no pivoting, in the tiles, the ordering, the row map and the padding of the real factors, every array in two
+ * planes (real, imaginary).  For omega > 0 and any positive damping the imaginary part of S is positive definite, so
+ * z^H S_k z has a non-zero imaginary part for every leading block S_k and z != 0: every leading block is non-singular and
+ * the factorisation exists without a permutation.  Its stability is measured, as for the real LDL^T: the growth
+ * || |L| |D| |L^T| ||_inf / ||S||_inf (moduli) is reported, and slod_lod_harmonic_response returns the true residual.
+ *
+ * slod_lod_factor_create_zldl factors the n_members matrices  S_k = alpha_k A + beta_k B  in one object, members as in
+ * slod_lod_factor_create_ensemble (at most 65535, one allocation): a frequency sweep is n_members pairs (alpha, beta) on
+ * one pair (A, B) = (sym(A_LOD), M_LOD).  The K matrices are never built: the band is filled with
+ *   re = (alpha_re a) + (beta_re b),   im = (alpha_im a) + (beta_im b),
+ * every product and every sum rounded on its own.  Member k's factor has the same words whatever n_members and its
+ * position are.  SLOD_ERR_NUMERIC: a pivot has both parts zero or a part that is infinite or NaN; slod_last_error reads
+ *   "slod_lod_factor_create_zldl: member k: pivot r of n is zero or not finite (re, im)",
+ * bad_pivot[k] is the first such pivot of member k (-1: none), *out stays NULL and nothing stays allocated.
+ * SLOD_ERR_ARGUMENT, before any device work: NULL handle, array, alpha, beta or out; n_members < 1 or > 65535; a NaN or
+ * infinite coefficient.
+ * On a complex factor slod_lod_factor_get_info(_member) reports min_pivot / max_pivot as the range of |D|, and
+ * slod_lod_factor_inertia fills min_abs_pivot / max_abs_pivot and the two norms (of moduli) and sets
+ * n_negative = n_positive = -1: a complex D has no signs.
+ *
+ * slod_lod_factor_solve_complex: L y = b, L^T x = D^-1 y on complex tiles, with the deal of tiles to waves and the order
+ * of summation of slod_lod_factor_solve.  The bits of a column of u depend only on its member's factor and on that column
+ * of the rhs: not on n_rhs, a leading dimension, the column's position, shared_rhs, the other members or the run.  In
+ * place (d_u_re == d_rhs_re, d_u_im == d_rhs_im) is allowed unless shared_rhs is set with more than one member.
+ * SLOD_ERR_ARGUMENT: NULL factor or array (d_rhs_im may be NULL); n_rhs < 1 or n_members < 1; a real factor; members
+ * outside the factor; ld_u < n_members n_rhs; ld_rhs < n_rhs (shared) or < n_members n_rhs; that in-place case.
+ *
+ * Every other call that takes a factor refuses a complex one (slod_lod_factor_solve(_ensemble), the theta and Newmark
+ * _direct calls, the slod_lod_eigs*_direct calls, the _precond calls): SLOD_ERR_ARGUMENT,
+ *   "<call>: a complex factor (slod_lod_factor_create_zldl) is solved by slod_lod_factor_solve_complex".
+ *
+ * S_k = alpha_k A + beta_k B, complex alpha_k, beta_k; A, B: values arrays of two full sets of block rows on one d_cols
+ * (sym(A_LOD), M_LOD); ONLY THE LOWER TRIANGLE IN FACTOR ORDER IS READ.  alpha, beta: HOST [n_members][2] (re, im). */
+int slod_lod_factor_create_zldl(slod_handle *h, const double *d_a, const double *d_b, const uint32_t *d_cols,
+                                const double *alpha, const double *beta, int n_members,
+                                int32_t *bad_pivot /* HOST [n_members], may be NULL */, slod_lod_factor **out);
+/* member first_member + k solves columns k n_rhs .. k n_rhs + n_rhs - 1 (layout of slod_lod_factor_solve_ensemble) of
+ * (d_u_re, d_u_im).  shared_rhs != 0: every member reads columns 0 .. n_rhs-1 of the rhs (ld_rhs >= n_rhs).
+ * d_rhs_im NULL = 0.  Asynchronous, allocates nothing, reads nothing back. */
+int slod_lod_factor_solve_complex(slod_lod_factor *f, int first_member, int n_members, const double *d_rhs_re,
+                                  const double *d_rhs_im, size_t ld_rhs, int n_rhs, int shared_rhs,
+                                  double *d_u_re, double *d_u_im, size_t ld_u, void *hip_stream);
+/* The sweep in one call: frequency k is the member with  alpha_k = (1, omega_k damp_stiff),
+ * beta_k = (-(omega_k omega_k), omega_k damp_mass)  (one rounding each), solved on the load, which all frequencies share,
+ * into the columns k n_rhs .. k n_rhs + n_rhs - 1 of (d_u_re, d_u_im): the words of slod_lod_factor_create_zldl +
+ * slod_lod_factor_solve_complex on these coefficients.  d_stiffness is the symmetrised stiffness.  The call factors and
+ * solves in chunks of at most 64 frequencies, which bounds the memory (one factor allocation per chunk); a chunk is queued
+ * whole on the handle's stream and waited for once, and the result does not depend on the chunking.
+ * rel_residual[k n_rhs + c] = ||b_c - S(omega_k) u||_2 / ||b_c||_2, formed after the solve from the matrices themselves,
+ * not from the factor: the four products A u_re, A u_im, M u_re, M u_im by the fma chain of slod_lod_apply_multi, combined
+ * with the complex coefficients per entry, fixed-order sums, no atomics.  A zero load column gives u = 0 and residual 0.
+ * growth[k] = norm_factor / norm_matrix of member k (slod_lod_factor_inertia).
+ * omega = 0, or no damping at all, is allowed: S is then real, the imaginary planes stay exact zeros, and the existence of
+ * the factor is the caller's risk, as with slod_lod_factor_create_ldl.
+ * Return SLOD_OK; SLOD_ERR_NUMERIC, "slod_lod_harmonic_response: frequency k: pivot r of n is zero or not finite (re, im)"
+ * (the outputs are then undefined); or another negative slod_status.  SLOD_ERR_ARGUMENT, before any device work: a NULL
+ * handle, matrix, d_cols, omega, d_load_re or u; negative, NaN or infinite damping; n_freq < 1 or n_rhs < 1; omega[k]
+ * negative, NaN or infinite (or so large that omega^2 overflows); ld_load < n_rhs; ld_u < n_freq n_rhs.
+ * Runs on the handle's stream and has finished when it returns.
+ * Not built: coefficient ensembles x frequencies, 2 x 2 pivots, damping that is not Rayleigh, adaptive frequency
+ * refinement, this factor as a preconditioner. */
+int slod_lod_harmonic_response(slod_handle *h, const double *d_stiffness, const double *d_mass, const uint32_t *d_cols,
+                               double damp_mass, double damp_stiff, const double *omega /* HOST [n_freq] */, int n_freq,
+                               const double *d_load_re, const double *d_load_im /* NULL = 0 */, size_t ld_load, int n_rhs,
+                               double *d_u_re, double *d_u_im, size_t ld_u,
+                               double *rel_residual /* HOST [n_freq * n_rhs], may be NULL */,
+                               double *growth       /* HOST [n_freq], may be NULL */);
+
 /* ---- refresh after a local coefficient change ----------------------------------------------
  * Every entry point above takes the coefficient as fixed for the life of a basis (the reference does too: one
  * compute_basis_function_candidates per run, LOD.cc:1425-1433).  When it changes in a small part of the domain -- a
