@@ -2,7 +2,7 @@
 //   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare] [--coarse] [--loads K]
 //                  [--heat STEPS DT] [--eigs K] [--shift SIGMA] [--wave STEPS DT] [--direct] [--ensemble K] [--perturb K]
 //                  [--reuse-factor] [--precond-member J]
-//                  [--member K] [--ldl] [--harmonic K W0 W1 [--damping DM DS]]
+//                  [--member K] [--ldl] [--harmonic K W0 W1 [--damping DM DS]] (with --ensemble: per member)
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
 // file name it dumps, per patch, phi and psi in patch-lexicographic order (parity tests).
 // --compare (anywhere on the command line): after run(), the rest of the reference run() -- global
@@ -40,6 +40,11 @@
 // slod_lod_harmonic_response call (a complex symmetric banded LDL^T per frequency); one line per frequency, "harmonic J:
 // omega = .., growth = .., relative residual = .., amplitude = .., power = ..": the growth of the factor, the true residual,
 // (u^H M u)^(1/2) and the dissipated power omega u^H C u / 2.
+// --ensemble K --harmonic F W0 W1 [--damping DM DS]: after the lines of --ensemble, the same sweep for every member in one
+// slod_lod_harmonic_response_ensemble call: "harmonic J member M: omega = .., growth = .., relative residual = .., amplitude
+// = .., power = ..", the numbers of the "harmonic J" line of a --member M --harmonic run; per frequency "harmonic J amplitude
+// over the ensemble of K: mean = .., standard deviation = .."; then for the frequency with the largest mean amplitude the L2
+// norms of the mean and of the standard deviation of the real and of the imaginary part on the fine grid.
 // --direct: the time loops of --heat and --wave run on a banded Cholesky factor of their matrix S instead of CG
 // (slod_lod_factor_create once, slod_lod_theta_steps_direct / slod_lod_newmark_steps_direct): one line "factor: n = ..,
 // half bandwidth = .., bytes = .., pivots in [.., ..]" per loop, then the same per-step lines without iterations and
@@ -400,8 +405,37 @@ int main(int argc_all, char **argv_all)
                 std::printf("member %d: PCG iterations = %d, Jacobi-CG iterations = %d\n", k, problem.ensemble_precond_iterations()[k],
                             problem.ensemble_precond_jacobi_iterations()[k]);
             }
-          if ((heat_steps > 0 || wave_steps > 0 || n_eigs > 0) && direct)
+          if (((heat_steps > 0 || wave_steps > 0 || n_eigs > 0) && direct) || n_harmonic > 0)
             problem.assemble_mass_matrix_ensemble();
+          if (n_harmonic > 0)
+            {
+              std::vector<double> omegas((std::size_t)n_harmonic);
+              for (int k = 0; k < n_harmonic; ++k)
+                omegas[k] = n_harmonic > 1 ? harmonic_w0 + k * ((harmonic_w1 - harmonic_w0) / (n_harmonic - 1)) : harmonic_w0;
+              problem.solve_harmonic_ensemble(omegas, damp_mass, damp_stiff);
+              for (int k = 0; k < n_harmonic; ++k)
+                {
+                  std::vector<double> amplitude;
+                  for (int m = 0; m < n_members; ++m)
+                    {
+                      const std::size_t at = (std::size_t)k * n_members + m;
+                      std::printf("harmonic %d member %d: omega = %.12e, growth = %.6e, relative residual = %.6e, amplitude = %.12e, "
+                                  "power = %.12e\n",
+                                  k + 1, m, omegas[k], problem.harmonic_ensemble_growth()[at], problem.harmonic_ensemble_residuals()[at],
+                                  problem.harmonic_ensemble_amplitude()[at], problem.harmonic_ensemble_power()[at]);
+                      amplitude.push_back(problem.harmonic_ensemble_amplitude()[at]);
+                    }
+                  double mean, dev;
+                  mean_and_deviation(amplitude, mean, dev);
+                  std::printf("harmonic %d amplitude over the ensemble of %d: mean = %.12e, standard deviation = %.12e\n", k + 1,
+                              n_members, mean, dev);
+                }
+              std::printf("SLOD harmonic ensemble of %d at omega = %.12e: L2 norm of the mean = %.12e (real), %.12e (imaginary), of the "
+                          "standard deviation = %.12e (real), %.12e (imaginary)\n",
+                          n_members, omegas[problem.harmonic_ensemble_peak()], problem.norms_harmonic_ensemble_real_mean().l2[0],
+                          problem.norms_harmonic_ensemble_imag_mean().l2[0], problem.norms_harmonic_ensemble_real_deviation().l2[0],
+                          problem.norms_harmonic_ensemble_imag_deviation().l2[0]);
+            }
           if (heat_steps > 0 && direct)
             {
               problem.solve_heat_ensemble((unsigned int)heat_steps, heat_dt, 1.0);

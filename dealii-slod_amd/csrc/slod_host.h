@@ -268,7 +268,7 @@ struct slod_lod_factor
 };
 // The parts of slod_lod_factor_create_zldl for a caller that queues more work behind the factorisation before it waits
 // (slod_lod_harmonic.hip).  launch: the allocation and every kernel on st, nothing read back; alpha, beta HOST
-// [n_members][2], read before it returns.  finish: after solves on the members were queued at will, the one read-back and
+// [(j0 + n_members - 1) / kmat + 1][2], read before it returns.  finish: after solves on the members were queued at will, the one read-back and
 // wait, then the host side: bad_pivot (may be NULL), the error text "<who>: <what> <first + k>: pivot r of n is zero or
 // not finite (re, im)" with SLOD_ERR_NUMERIC, or the norms and pivot ranges of every member.  Arguments are checked by
 // the caller.  A failed member's band holds unfinished values: solves on it fault nothing and mean nothing.
@@ -278,14 +278,19 @@ struct SlodZFactorBuild
   std::vector<double> piv, coef; // HOST: the read-back, the coefficients on their way up
   std::vector<int>    bad;
 };
-int slod_lod_zfactor_launch(slod_handle *h, hipStream_t st, const char *who, const double *d_a, const double *d_b,
-                            const uint32_t *d_cols, const double *alpha, const double *beta, int n_members, SlodZFactorBuild *z);
-int slod_lod_zfactor_finish(slod_handle *h, hipStream_t st, const char *who, const char *what, int first, SlodZFactorBuild *z,
-                            int32_t *bad_pivot);
-// The launch of slod_lod_factor_solve_complex; arguments are checked by the caller
+// d_a, d_b are ensemble matrices of kmat members (ld_a, ld_b; one matrix each: kmat = 1, ld = 1) and alpha, beta tables of
+// coefficient pairs: member k of the build is the flat member j = j0 + k, with the pair j / kmat on the matrices of member
+// j % kmat.  what_minor given: the error text names "<what> j / kmat, <what_minor> j % kmat", j = first + k.
+int slod_lod_zfactor_launch(slod_handle *h, hipStream_t st, const char *who, const double *d_a, size_t ld_a, const double *d_b,
+                            size_t ld_b, int kmat, const uint32_t *d_cols, const double *alpha, const double *beta, size_t j0,
+                            int n_members, SlodZFactorBuild *z);
+int slod_lod_zfactor_finish(slod_handle *h, hipStream_t st, const char *who, const char *what, size_t first, SlodZFactorBuild *z,
+                            int32_t *bad_pivot, const char *what_minor = nullptr, int kmat = 1);
+// The launch of slod_lod_factor_solve_complex(_ensemble): member first_member + k reads the rhs columns
+// ((rhs_first + k) % rhs_members) n_rhs .. and writes the columns k n_rhs .. of u; arguments are checked by the caller
 void slod_lod_zfactor_solve_launch(const slod_lod_factor *f, hipStream_t st, int first_member, int n_members, const double *d_rhs_re,
-                                   const double *d_rhs_im, size_t ld_rhs, int n_rhs, bool shared_rhs, double *d_u_re, double *d_u_im,
-                                   size_t ld_u);
+                                   const double *d_rhs_im, size_t ld_rhs, int n_rhs, int rhs_first, int rhs_members, double *d_u_re,
+                                   double *d_u_im, size_t ld_u);
 // The launch of slod_lod_factor_solve_ensemble for the time loops on a factor (slod_lod_time.hip, slod_lod_wave.hip):
 // member first_member + k solves the columns k n_rhs .. k n_rhs + n_rhs - 1; arguments are checked by the caller
 void slod_lod_factor_solve_launch(const slod_lod_factor *f, hipStream_t st, const double *d_rhs, size_t ld_rhs, int n_rhs, double *d_u,

@@ -536,11 +536,14 @@ namespace
   }
 
   // k_factor_scatter for the combination: word t of member k is  (alpha_re a + beta_re b, alpha_im a + beta_im b),  every
-  // product and every sum rounded on its own; a, b: one matrix each for all members.  coef: [n_members][4].
+  // product and every sum rounded on its own.  coef: [n_members][4].  a, b: ensemble matrices of kmat members (entry t of
+  // member m at a[t ld_a + m]); factor member k is the flat member j = j0 + k of a (coefficient, matrix) table and reads
+  // matrix member j % kmat.  One matrix each for all members is the launch kmat = 1, ld_a = ld_b = 1.
   __global__ __launch_bounds__(256) void k_zfactor_scatter(const SlodGrid G, int NP, int cap, int bb, int n_members,
-                                                          const double *__restrict__ a, const double *__restrict__ b,
-                                                          const double *__restrict__ coef, const uint32_t *__restrict__ cols,
-                                                          double *band, size_t im_band, size_t mstride)
+                                                          const double *__restrict__ a, size_t ld_a, const double *__restrict__ b,
+                                                          size_t ld_b, int kmat, size_t j0, const double *__restrict__ coef,
+                                                          const uint32_t *__restrict__ cols, double *band, size_t im_band,
+                                                          size_t mstride)
   {
 #pragma clang fp contract(off)
     const int    s = G.spacedim;
@@ -557,7 +560,8 @@ namespace
     if (c > r || kb > bb)
       return;
     const double *ck = coef + 4 * k;
-    const double  av = a[t], bv = b[t];
+    const size_t  m = (j0 + k) % (size_t)kmat;
+    const double  av = a[t * ld_a + m], bv = b[t * ld_b + m];
     const double  re_a = ck[0] * av, re_b = ck[2] * bv, im_a = ck[1] * av, im_b = ck[3] * bv;
     double       *out = band + k * mstride + ((size_t)I * (bb + 1) + kb) * FT + (size_t)(c % FB) * FB + r % FB;
     out[0]       = re_a + re_b;
@@ -751,22 +755,24 @@ namespace
   }
 
   // The two sweeps of k_factor_solve<true> on a complex factor: the same deal of tiles to waves and the same order of
-  // summation, a complex tile product per tile.  rhs_im NULL: a real load.  shared: every member reads the columns
-  // 0 .. n_rhs - 1 of the rhs; else member blockIdx.y its own n_rhs columns, as it writes them in u.
+  // summation, a complex tile product per tile.  rhs_im NULL: a real load.  Member blockIdx.y of the launch reads the
+  // rhs columns ((rhs_first + blockIdx.y) % rhs_members) n_rhs .. and writes the columns blockIdx.y n_rhs .. of u:
+  // period 1 is the shared rhs, a period of at least the members launched (rhs_first = 0) a rhs of their own each.
   __global__ __launch_bounds__(256) void k_zfactor_solve(int nb, int bb, const double *__restrict__ band, size_t im_band,
                                                         const double *__restrict__ diag, size_t im_diag,
                                                         const double *__restrict__ dinv, size_t im_vec, size_t mstride,
-                                                        const int *__restrict__ rowmap, int n_rhs, int shared, const double *rhs_re,
-                                                        const double *rhs_im, size_t ld_rhs, double *u_re, double *u_im, size_t ld_u)
+                                                        const int *__restrict__ rowmap, int n_rhs, int rhs_first, int rhs_members,
+                                                        const double *rhs_re, const double *rhs_im, size_t ld_rhs, double *u_re,
+                                                        double *u_im, size_t ld_u)
   {
     __shared__ double sPr[4][FB][FB + 1], sPi[4][FB][FB + 1], sLr[FB][FB + 1], sLi[FB][FB + 1];
     band += blockIdx.y * mstride, diag += blockIdx.y * mstride, dinv += blockIdx.y * mstride;
-    if (!shared)
-      {
-        rhs_re += (size_t)blockIdx.y * n_rhs;
-        if (rhs_im)
-          rhs_im += (size_t)blockIdx.y * n_rhs;
-      }
+    {
+      const size_t base = (size_t)(((unsigned)rhs_first + blockIdx.y) % (unsigned)rhs_members) * n_rhs;
+      rhs_re += base;
+      if (rhs_im)
+        rhs_im += base;
+    }
     u_re += (size_t)blockIdx.y * n_rhs, u_im += (size_t)blockIdx.y * n_rhs;
     const int    tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4;
     const int    c0 = blockIdx.x * FB;
@@ -885,14 +891,14 @@ int slod_lod_factor_check(const slod_handle *h, const char *who, const slod_lod_
 }
 
 void slod_lod_zfactor_solve_launch(const slod_lod_factor *f, hipStream_t st, int first_member, int n_members, const double *d_rhs_re,
-                                   const double *d_rhs_im, size_t ld_rhs, int n_rhs, bool shared_rhs, double *d_u_re, double *d_u_im,
-                                   size_t ld_u)
+                                   const double *d_rhs_im, size_t ld_rhs, int n_rhs, int rhs_first, int rhs_members, double *d_u_re,
+                                   double *d_u_im, size_t ld_u)
 {
   const size_t first = (size_t)first_member * f->member_doubles;
   const dim3   grid((unsigned)((n_rhs + FB - 1) / FB), (unsigned)n_members);
   hipLaunchKernelGGL(k_zfactor_solve, grid, dim3(256), 0, st, f->nb, f->bb, f->band + first, f->im_band, f->diag + first, f->im_diag,
-                     f->dinv + first, f->im_vec, f->member_doubles, f->rowmap, n_rhs, shared_rhs ? 1 : 0, d_rhs_re, d_rhs_im, ld_rhs,
-                     d_u_re, d_u_im, ld_u);
+                     f->dinv + first, f->im_vec, f->member_doubles, f->rowmap, n_rhs, rhs_first, rhs_members, d_rhs_re, d_rhs_im,
+                     ld_rhs, d_u_re, d_u_im, ld_u);
 }
 
 namespace
@@ -1029,8 +1035,9 @@ namespace
 
 // The complex factor: one allocation, per member  band (re, im), diagonal tiles (re, im), D (re, im), the two norms,
 // 1 / D (re, im), two vectors of row sums;  then the coefficients of all members, the row map and the status words.
-int slod_lod_zfactor_launch(slod_handle *h, hipStream_t st, const char *who, const double *d_a, const double *d_b,
-                            const uint32_t *d_cols, const double *alpha, const double *beta, int n_members, SlodZFactorBuild *z)
+int slod_lod_zfactor_launch(slod_handle *h, hipStream_t st, const char *who, const double *d_a, size_t ld_a, const double *d_b,
+                            size_t ld_b, int kmat, const uint32_t *d_cols, const double *alpha, const double *beta, size_t j0,
+                            int n_members, SlodZFactorBuild *z)
 {
   const SlodGrid   G = slod_grid_of(h);
   const int        s = G.spacedim, w = 2 * G.oversampling + 1, cap = slod_lod_row_capacity(h);
@@ -1062,7 +1069,10 @@ int slod_lod_zfactor_launch(slod_handle *h, hipStream_t st, const char *who, con
   std::vector<double> &coef = z->coef; // lives until finish() has waited
   coef.resize(4 * K);
   for (size_t k = 0; k < K; ++k)
-    coef[4 * k] = alpha[2 * k], coef[4 * k + 1] = alpha[2 * k + 1], coef[4 * k + 2] = beta[2 * k], coef[4 * k + 3] = beta[2 * k + 1];
+    {
+      const size_t c = (j0 + k) / (size_t)kmat; // the coefficient pair of flat member j0 + k
+      coef[4 * k] = alpha[2 * c], coef[4 * k + 1] = alpha[2 * c + 1], coef[4 * k + 2] = beta[2 * c], coef[4 * k + 3] = beta[2 * c + 1];
+    }
   e = hipMemsetAsync(f.band, 0, K * nd * sizeof(double), st);
   if (e == hipSuccess)
     e = hipMemsetAsync(f.status, 0xff, K * sizeof(int), st); // -1
@@ -1074,7 +1084,7 @@ int slod_lod_zfactor_launch(slod_handle *h, hipStream_t st, const char *who, con
       hipLaunchKernelGGL(k_factor_rowmap, dim3((unsigned)((npad + 255) / 256), (unsigned)K), dim3(256), 0, st, G, f.n, (int)npad, f.bb,
                          f.rowmap, f.band, nd);
       hipLaunchKernelGGL(k_zfactor_scatter, dim3((unsigned)((nval * K + 255) / 256)), dim3(256), 0, st, G, h->NP, cap, f.bb, n_members,
-                         d_a, d_b, f.coef, d_cols, f.band, nband, nd);
+                         d_a, ld_a, d_b, ld_b, kmat, j0, f.coef, d_cols, f.band, nband, nd);
       double    *norms = f.piv + 2 * npad, *work = f.dinv + 2 * npad, *work2 = work + npad;
       const dim3 rows_grid((unsigned)f.nb, (unsigned)K);
       hipLaunchKernelGGL(k_zldl_norms<0>, rows_grid, dim3(256), 0, st, f.nb, f.bb, f.band, nband, f.diag, ndiag, f.piv, npad, nullptr,
@@ -1102,8 +1112,8 @@ int slod_lod_zfactor_launch(slod_handle *h, hipStream_t st, const char *who, con
   return SLOD_OK;
 }
 
-int slod_lod_zfactor_finish(slod_handle *h, hipStream_t st, const char *who, const char *what, int first, SlodZFactorBuild *z,
-                            int32_t *bad_pivot)
+int slod_lod_zfactor_finish(slod_handle *h, hipStream_t st, const char *who, const char *what, size_t first, SlodZFactorBuild *z,
+                            int32_t *bad_pivot, const char *what_minor, int kmat)
 {
   slod_lod_factor &f = z->f;
   const size_t     npad = (size_t)f.nb * FB, nread = 2 * npad + 2, nd = f.member_doubles, K = (size_t)f.n_members;
@@ -1124,8 +1134,12 @@ int slod_lod_zfactor_finish(slod_handle *h, hipStream_t st, const char *who, con
       {
         char          msg[240];
         const double *d = z->piv.data() + k * nread + (size_t)z->bad[k];
-        std::snprintf(msg, sizeof msg, "%s: %s %zu: pivot %d of %d is zero or not finite (%g, %g)", who, what, (size_t)first + k,
-                      z->bad[k], f.n, d[0], d[npad]);
+        if (what_minor)
+          std::snprintf(msg, sizeof msg, "%s: %s %zu, %s %zu: pivot %d of %d is zero or not finite (%g, %g)", who, what,
+                        (first + k) / (size_t)kmat, what_minor, (first + k) % (size_t)kmat, z->bad[k], f.n, d[0], d[npad]);
+        else
+          std::snprintf(msg, sizeof msg, "%s: %s %zu: pivot %d of %d is zero or not finite (%g, %g)", who, what, first + k,
+                        z->bad[k], f.n, d[0], d[npad]);
         return slod_fail(h, SLOD_ERR_NUMERIC, msg);
       }
   f.member_min.resize(K), f.member_max.resize(K), f.inertia.resize(K);
@@ -1315,9 +1329,40 @@ int slod_lod_factor_create_zldl(slod_handle *h, const double *d_a, const double 
   if (const int rc = slod_enter(h, nullptr, &st))
     return rc;
   SlodZFactorBuild z;
-  if (const int rc = slod_lod_zfactor_launch(h, st, who, d_a, d_b, d_cols, alpha, beta, n_members, &z))
+  if (const int rc = slod_lod_zfactor_launch(h, st, who, d_a, 1, d_b, 1, 1, d_cols, alpha, beta, 0, n_members, &z))
     return rc;
   if (const int rc = slod_lod_zfactor_finish(h, st, who, "member", 0, &z, bad_pivot))
+    return rc;
+  *out = new slod_lod_factor(std::move(z.f));
+  return SLOD_OK;
+}
+
+int slod_lod_factor_create_zldl_ensemble(slod_handle *h, const double *d_a, size_t ld_a_m, const double *d_b, size_t ld_b_m,
+                                         int n_members, const uint32_t *d_cols, const double *alpha, const double *beta, int n_coef,
+                                         int32_t *bad_pivot, slod_lod_factor **out)
+{
+  const char *who = "slod_lod_factor_create_zldl_ensemble";
+  if (out)
+    *out = nullptr;
+  if (!h || !d_a || !d_b || !d_cols || !alpha || !beta || !out)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": NULL handle, array, alpha, beta or out");
+  if (n_members < 1 || n_members > MAX_MEMBERS)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": n_members < 1 or > 65535");
+  if (n_coef < 1 || n_coef > MAX_MEMBERS / n_members)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": n_coef < 1 or n_coef * n_members > 65535");
+  if (ld_a_m < (size_t)n_members || ld_b_m < (size_t)n_members)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": leading dimension of a matrix below n_members");
+  for (int k = 0; k < 2 * n_coef; ++k)
+    if (!std::isfinite(alpha[k]) || !std::isfinite(beta[k]))
+      return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": a coefficient is NaN or infinite");
+  hipStream_t st;
+  if (const int rc = slod_enter(h, nullptr, &st))
+    return rc;
+  SlodZFactorBuild z;
+  if (const int rc = slod_lod_zfactor_launch(h, st, who, d_a, ld_a_m, d_b, ld_b_m, n_members, d_cols, alpha, beta, 0,
+                                             n_coef * n_members, &z))
+    return rc;
+  if (const int rc = slod_lod_zfactor_finish(h, st, who, "coefficient", 0, &z, bad_pivot, "member", n_members))
     return rc;
   *out = new slod_lod_factor(std::move(z.f));
   return SLOD_OK;
@@ -1353,8 +1398,51 @@ int slod_lod_factor_solve_complex(slod_lod_factor *f, int first_member, int n_me
   hipStream_t st;
   if (const int rc = slod_enter(h, hip_stream, &st))
     return rc;
-  slod_lod_zfactor_solve_launch(f, st, first_member, n_members, d_rhs_re, d_rhs_im, ld_rhs, n_rhs, shared_rhs != 0, d_u_re, d_u_im,
-                                ld_u);
+  slod_lod_zfactor_solve_launch(f, st, first_member, n_members, d_rhs_re, d_rhs_im, ld_rhs, n_rhs, 0, shared_rhs ? 1 : n_members,
+                                d_u_re, d_u_im, ld_u);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, who);
+}
+
+int slod_lod_factor_solve_complex_ensemble(slod_lod_factor *f, int first_member, int n_members, const double *d_rhs_re,
+                                           const double *d_rhs_im, size_t ld_rhs, int n_rhs, int rhs_members, double *d_u_re,
+                                           double *d_u_im, size_t ld_u, void *hip_stream)
+{
+  const char *who = "slod_lod_factor_solve_complex_ensemble";
+  if (!f)
+    return slod_fail(nullptr, SLOD_ERR_ARGUMENT, std::string(who) + ": NULL factor");
+  slod_handle *h = f->h;
+  if (!d_rhs_re || !d_u_re || !d_u_im)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": NULL array");
+  if (n_rhs < 1 || n_members < 1)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": n_rhs < 1 or n_members < 1");
+  if (rhs_members < 1)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": rhs_members < 1");
+  if (f->kind != SLOD_FACTOR_ZLDL)
+    return slod_fail(h, SLOD_ERR_ARGUMENT,
+                     std::string(who) + ": a real factor (slod_lod_factor_create, _create_ldl) is solved by slod_lod_factor_solve");
+  if (first_member < 0 || first_member > f->n_members - n_members)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": members outside the factor");
+  if (ld_u / (size_t)n_rhs < (size_t)n_members)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": leading dimension of u below n_members * n_rhs");
+  // the rhs columns read: those of the members j % rhs_members, j = first_member .. first_member + n_members - 1
+  const int rhs_first = first_member % rhs_members;
+  const int rhs_used  = n_members >= rhs_members || rhs_first + n_members > rhs_members ? rhs_members : rhs_first + n_members;
+  if (ld_rhs / (size_t)n_rhs < (size_t)rhs_used)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": leading dimension of the rhs below the columns read");
+  // in place only where every member reads the columns it writes: j % rhs_members = j - first_member for all of them
+  if (n_members > rhs_members || rhs_first != 0)
+    for (const double *u : {d_u_re, d_u_im})
+      if (u == d_rhs_re || u == d_rhs_im)
+        return slod_fail(h, SLOD_ERR_ARGUMENT,
+                         std::string(who) + (n_members > rhs_members
+                                               ? ": rhs columns read by several members cannot be solved in place"
+                                               : ": in place needs first_member to be a multiple of rhs_members"));
+  hipStream_t st;
+  if (const int rc = slod_enter(h, hip_stream, &st))
+    return rc;
+  slod_lod_zfactor_solve_launch(f, st, first_member, n_members, d_rhs_re, d_rhs_im, ld_rhs, n_rhs, rhs_first, rhs_members, d_u_re,
+                                d_u_im, ld_u);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SLOD_OK : slod_hip_fail(h, e, who);
 }

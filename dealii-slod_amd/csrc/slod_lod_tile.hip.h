@@ -38,13 +38,14 @@ namespace
 // at values[e ld_m + col].  The chain is the same, on other operands; the lanes of a wave, which hold consecutive columns
 // of one row, read 64 consecutive words where the shared matrix gives them one.  There every (row, column) streams its
 // own values, so the loads of LOD_SLOTS slots are issued before the first fma needs one (they do not depend on acc): a
-// wave otherwise waits out a memory latency per slot.
+// wave otherwise waits out a memory latency per slot.  mcol: the column of the matrix, col: that of the vector; they
+// differ where several vector columns share a member (slod_lod_harmonic.hip).
 constexpr int LOD_SLOTS = 8; // slots whose loads are in flight together in the PER_COL product
 
 template <int S> // S = s, a constant here so that nothing stands between the loads
 __device__ __forceinline__ double slod_lod_row_product_per_col(int p, int d, int cap, int NP, const double *__restrict__ values,
                                                                size_t ld_m, const uint32_t *__restrict__ cols,
-                                                               const double *__restrict__ x, size_t ld, int col)
+                                                               const double *__restrict__ x, size_t ld, int col, int mcol)
 {
   const size_t slot0 = (size_t)p * cap;
   double       acc = 0.0;
@@ -63,7 +64,7 @@ __device__ __forceinline__ double slod_lod_row_product_per_col(int p, int d, int
 #pragma unroll
           for (int e = 0; e < S; ++e)
             {
-              a[u][e]  = values[(at + e) * ld_m + col];
+              a[u][e]  = values[(at + e) * ld_m + mcol];
               xv[u][e] = x[(qs + e) * ld + col];
             }
         }
@@ -88,8 +89,8 @@ __device__ __forceinline__ double slod_lod_row_product(int i, int s, int cap, in
   const size_t slot0 = (size_t)p * cap;
   double       acc = 0.0;
   if constexpr (PER_COL)
-    return s == 1 ? slod_lod_row_product_per_col<1>(p, d, cap, NP, values, ld_m, cols, x, ld, col)
-                  : slod_lod_row_product_per_col<2>(p, d, cap, NP, values, ld_m, cols, x, ld, col);
+    return s == 1 ? slod_lod_row_product_per_col<1>(p, d, cap, NP, values, ld_m, cols, x, ld, col, col)
+                  : slod_lod_row_product_per_col<2>(p, d, cap, NP, values, ld_m, cols, x, ld, col, col);
   for (int j = 0; j < cap; ++j)
     {
       // an unused slot (0xffffffff; anything >= NP) reads the row's own patch and adds nothing:

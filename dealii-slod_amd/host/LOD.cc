@@ -797,6 +797,69 @@ namespace slod
   }
 
   template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_harmonic_ensemble(const std::vector<double> &omegas, const double damp_mass, const double damp_stiff)
+  {
+    if (!d_ens_mass)
+      throw std::runtime_error("solve_harmonic_ensemble: assemble_mass_matrix_ensemble comes first");
+    if (omegas.empty())
+      throw std::runtime_error("solve_harmonic_ensemble: no frequency");
+    const int          K = (int)par.n_members;
+    const std::size_t  F = omegas.size(), ld_m = (std::size_t)K, ld = F * K;
+    const unsigned int n_patches = (unsigned int)patches.size();
+    const std::size_t  NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+    const std::size_t  fine_size = (NE + 1) * (NE + 1) * spacedim, n_coarse = (std::size_t)n_patches * spacedim;
+    const int          cap = slod_lod_row_capacity(handle);
+    check(cap, "slod_lod_row_capacity");
+    const std::size_t n_words = (std::size_t)n_patches * cap * spacedim * spacedim;
+    if (!d_ens_sym)
+      d_ens_sym = device_alloc<double>(n_words * K);
+    // the response interleaved [row][frequency][member], as the call writes it
+    double *d_ur = device_alloc<double>(2 * n_coarse * ld), *d_ui = d_ur + n_coarse * ld;
+    double *d_fine = device_alloc<double>(fine_size * K), *d_mean = device_alloc<double>(fine_size), *d_var = device_alloc<double>(fine_size);
+    check(slod_lod_matrix_symmetrize_ensemble(handle, d_ens_values, ld_m, d_ens_cols, K, d_ens_sym, ld_m, nullptr),
+          "slod_lod_matrix_symmetrize_ensemble");
+    ens_harmonic_growth.assign(ld, 0.0);
+    ens_harmonic_residuals.assign(ld, 0.0);
+    ens_harmonic_quantities.assign(4 * ld, 0.0);
+    // d_ens_rhs: the loads C_k^T f of solve_ensemble() (slod_lod_rhs_ensemble, f = 1), column = member
+    check(slod_lod_harmonic_response_ensemble(handle, d_ens_sym, ld_m, d_ens_mass, ld_m, d_ens_cols, K, damp_mass, damp_stiff,
+                                              omegas.data(), (int)F, d_ens_rhs, nullptr, ld_m, 1, d_ur, d_ui, ld,
+                                              ens_harmonic_residuals.data(), ens_harmonic_growth.data(), ens_harmonic_quantities.data()),
+          "slod_lod_harmonic_response_ensemble");
+    // u^H M u and u^H A u as solve_harmonic forms them (the two planes add), on every frequency's block of K columns
+    ens_harmonic_amplitude.assign(ld, 0.0);
+    ens_harmonic_power.assign(ld, 0.0);
+    std::vector<double> q[4] = {std::vector<double>(K), std::vector<double>(K), std::vector<double>(K), std::vector<double>(K)};
+    double              best = -1.0;
+    for (std::size_t k = 0; k < F; ++k)
+      {
+        const double *ur = d_ur + k * K, *ui = d_ui + k * K;
+        check(slod_lod_inner_ensemble(handle, d_ens_mass, ld_m, d_ens_cols, ur, ld, ur, ld, K, q[0].data(), nullptr), "slod_lod_inner_ensemble");
+        check(slod_lod_inner_ensemble(handle, d_ens_mass, ld_m, d_ens_cols, ui, ld, ui, ld, K, q[1].data(), nullptr), "slod_lod_inner_ensemble");
+        check(slod_lod_inner_ensemble(handle, d_ens_sym, ld_m, d_ens_cols, ur, ld, ur, ld, K, q[2].data(), nullptr), "slod_lod_inner_ensemble");
+        check(slod_lod_inner_ensemble(handle, d_ens_sym, ld_m, d_ens_cols, ui, ld, ui, ld, K, q[3].data(), nullptr), "slod_lod_inner_ensemble");
+        double mean = 0.0;
+        for (int m = 0; m < K; ++m)
+          {
+            const double uMu = q[0][m] + q[1][m], uAu = q[2][m] + q[3][m];
+            ens_harmonic_amplitude[k * K + m] = std::sqrt(uMu);
+            ens_harmonic_power[k * K + m]     = 0.5 * omegas[k] * (damp_mass * uMu + damp_stiff * uAu);
+            mean += ens_harmonic_amplitude[k * K + m];
+          }
+        if (mean / K > best)
+          best = mean / K, ens_harmonic_peak = (unsigned int)k;
+      }
+    // the two planes of the loudest frequency on the fine grid, and their moments over the members
+    for (int part = 0; part < 2; ++part)
+      {
+        const double *block = (part == 0 ? d_ur : d_ui) + (std::size_t)ens_harmonic_peak * K;
+        check(slod_lod_reconstruct_ensemble(handle, d_ens_basis, ens_stride, ens_member_stride, K, block, ld, d_fine, fine_size, nullptr),
+              "slod_lod_reconstruct_ensemble");
+        ensemble_moment_norms(d_fine, d_mean, d_var, ens_harmonic_norms[2 * part], ens_harmonic_norms[2 * part + 1]);
+      }
+  }
+
+  template <int dim, int spacedim>
   void LOD<dim, spacedim>::solve_eigenproblem_ensemble(const unsigned int n_eig, const double sigma)
   {
     eigenproblem_ensemble(n_eig, sigma, false, false);

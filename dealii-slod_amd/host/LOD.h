@@ -239,6 +239,25 @@ namespace slod
     // coefficient.  Then the final states on the fine grid and their moments as in solve_ensemble().
     // last_factor_info() is that of S, the range over all members.
     void solve_wave_ensemble(const unsigned int n_steps, const double dt, const double beta, const double gamma);
+    // solve_harmonic for all members at once, after assemble_mass_matrix_ensemble(): the symmetrised stiffness of every
+    // member (slod_lod_matrix_symmetrize_ensemble), the loads of solve_ensemble() (slod_lod_rhs_ensemble, f = 1) and one
+    // slod_lod_harmonic_response_ensemble call for all (frequency, member) pairs.  Entry [frequency * n_members + member] of
+    // growth, residual, amplitude and power is that of solve_harmonic of a problem with that member's coefficient: amplitude
+    // and power come from slod_lod_inner_ensemble on the frequency's block of the response, which is an ensemble coarse
+    // multi-vector (the call's own quantities are kept beside them).  For the frequency with the largest mean amplitude
+    // the real and the imaginary block go to the fine grid (slod_lod_reconstruct_ensemble) and their moments are taken
+    // as in solve_ensemble().
+    void solve_harmonic_ensemble(const std::vector<double> &omegas, const double damp_mass, const double damp_stiff);
+    const std::vector<double> &harmonic_ensemble_growth() const { return ens_harmonic_growth; }
+    const std::vector<double> &harmonic_ensemble_residuals() const { return ens_harmonic_residuals; }
+    const std::vector<double> &harmonic_ensemble_amplitude() const { return ens_harmonic_amplitude; }
+    const std::vector<double> &harmonic_ensemble_power() const { return ens_harmonic_power; }
+    const std::vector<double> &harmonic_ensemble_quantities() const { return ens_harmonic_quantities; } // [..][4]
+    unsigned int               harmonic_ensemble_peak() const { return ens_harmonic_peak; } // the frequency reconstructed
+    const slod_error_norms    &norms_harmonic_ensemble_real_mean() const { return ens_harmonic_norms[0]; }
+    const slod_error_norms    &norms_harmonic_ensemble_real_deviation() const { return ens_harmonic_norms[1]; }
+    const slod_error_norms    &norms_harmonic_ensemble_imag_mean() const { return ens_harmonic_norms[2]; }
+    const slod_error_norms    &norms_harmonic_ensemble_imag_deviation() const { return ens_harmonic_norms[3]; }
     // solve_eigenproblem(.., direct = true) for all members at once, after assemble_mass_matrix_ensemble(): the symmetrised
     // stiffness of every member, S_k = sym(A_k) - sigma M_k (sigma = 0: sym(A_k) itself), one factor object for all members
     // and slod_lod_eigs_ensemble_direct with the defaults of solve_eigenproblem.  Member k's eigenvalues, residuals and
@@ -374,6 +393,10 @@ namespace slod
     double             *d_ens_sym = nullptr;
     std::vector<double> ens_wave_kinetic, ens_wave_potential, ens_wave_work;
     slod_error_norms    ens_wave_mean_norms{}, ens_wave_dev_norms{};
+    // solve_harmonic_ensemble
+    std::vector<double> ens_harmonic_growth, ens_harmonic_residuals, ens_harmonic_amplitude, ens_harmonic_power, ens_harmonic_quantities;
+    unsigned int        ens_harmonic_peak = 0;
+    slod_error_norms    ens_harmonic_norms[4] = {};
     // solve_eigenproblem_ensemble
     std::vector<double> ens_eigenvalues, ens_eig_residuals;
     std::vector<int>    ens_eig_outer;

@@ -202,6 +202,12 @@ def load():
     lib.slod_lod_factor_solve_complex.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp, C.c_size_t, vp]
     lib.slod_lod_harmonic_response.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, dp, C.c_int, vp, vp, C.c_size_t, C.c_int,
                                                vp, vp, C.c_size_t, dp, dp]
+    lib.slod_lod_factor_create_zldl_ensemble.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, vp, dp, dp, C.c_int,
+                                                         C.POINTER(C.c_int32), C.POINTER(vp)]
+    lib.slod_lod_factor_solve_complex_ensemble.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_size_t, C.c_int, C.c_int, vp, vp,
+                                                           C.c_size_t, vp]
+    lib.slod_lod_harmonic_response_ensemble.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_int, C.c_double, C.c_double, dp,
+                                                        C.c_int, vp, vp, C.c_size_t, C.c_int, vp, vp, C.c_size_t, dp, dp, dp]
     lib.slod_update_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, C.c_int, C.c_size_t, C.c_int, vp]
     lib.slod_dirty_patches.argtypes = [vp, vp, u32p, C.c_size_t]
     lib.slod_plan_create_dirty.argtypes = [vp, C.c_uint32, vp, C.POINTER(vp)]
@@ -438,20 +444,32 @@ class EnsembleFactor(Factor):
 class ComplexFactor(EnsembleFactor):
     """slod_lod_factor of slod_lod_factor_create_zldl: the complex symmetric S_k = alpha_k A + beta_k B = L D L^T of every
     member k in one object.  alpha, beta: complex scalars or sequences of n_members.  .info / .member_info(k) give the
-    range of |D|, .inertia(k) the two norms (n_negative = n_positive = -1), .bad_pivot as EnsembleFactor."""
+    range of |D|, .inertia(k) the two norms (n_negative = n_positive = -1), .bad_pivot as EnsembleFactor.
+    matrix_members = K (slod_lod_factor_create_zldl_ensemble): d_a, d_b are ensemble matrices of K members, alpha and beta
+    have one entry per coefficient pair, and the factor member j = k K + m is pair k on the matrices of member m
+    (.n_members = len(alpha) * K, .n_coef = len(alpha))."""
 
-    def __init__(self, slod, d_a, d_b, d_cols, alpha, beta):
+    def __init__(self, slod, d_a, d_b, d_cols, alpha, beta, matrix_members=None, ld_a_m=None, ld_b_m=None):
         self.slod, self.lib = slod, slod.lib
         self.alpha = np.atleast_1d(np.asarray(alpha, dtype=np.complex128)).copy()
         self.beta = np.atleast_1d(np.asarray(beta, dtype=np.complex128)).copy()
         if self.alpha.shape != self.beta.shape or self.alpha.ndim != 1:
             raise ValueError("alpha and beta: one complex number per member each")
-        self.n_members = n_members = len(self.alpha)
+        self.n_coef = len(self.alpha)
+        self.matrix_members = matrix_members
+        self.n_members = n_members = self.n_coef * (1 if matrix_members is None else max(matrix_members, 0))
         self.f = C.c_void_p()
         self.bad_pivot = np.full(max(n_members, 1), -1, dtype=np.int32)
-        rc = self.lib.slod_lod_factor_create_zldl(slod.h, d_a, d_b, d_cols, _dp(self.alpha.view(np.float64)),
-                                                  _dp(self.beta.view(np.float64)), n_members,
-                                                  self.bad_pivot.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(self.f))
+        if matrix_members is None:
+            rc = self.lib.slod_lod_factor_create_zldl(slod.h, d_a, d_b, d_cols, _dp(self.alpha.view(np.float64)),
+                                                      _dp(self.beta.view(np.float64)), n_members,
+                                                      self.bad_pivot.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(self.f))
+        else:
+            K = matrix_members
+            rc = self.lib.slod_lod_factor_create_zldl_ensemble(
+                slod.h, d_a, K if ld_a_m is None else ld_a_m, d_b, K if ld_b_m is None else ld_b_m, K, d_cols,
+                _dp(self.alpha.view(np.float64)), _dp(self.beta.view(np.float64)), self.n_coef,
+                self.bad_pivot.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(self.f))
         if rc:
             err = SlodError(rc, self.lib.slod_last_error(slod.h).decode())
             err.bad_pivot = self.bad_pivot[:n_members].copy()
@@ -461,11 +479,20 @@ class ComplexFactor(EnsembleFactor):
         slod._factors.add(self)
 
     def solve_complex(self, d_rhs_re, d_rhs_im, d_u_re, d_u_im, n_rhs=1, first_member=0, n_members=None, shared_rhs=False,
-                      ld_rhs=None, ld_u=None, stream=None):
+                      ld_rhs=None, ld_u=None, stream=None, rhs_members=None):
         """Member first_member + k solves the columns k * n_rhs .. of (d_rhs_re, d_rhs_im) into (d_u_re, d_u_im);
         shared_rhs: every member reads the columns 0 .. n_rhs - 1.  d_rhs_im None: a real rhs.  ld defaults to
-        n_members * n_rhs (the shared rhs: n_rhs).  Asynchronous."""
+        n_members * n_rhs (the shared rhs: n_rhs).  Asynchronous.
+        rhs_members=R (slod_lod_factor_solve_complex_ensemble): factor member j reads the rhs columns (j % R) * n_rhs ..
+        and writes the columns (j - first_member) * n_rhs ..; ld_rhs defaults to R * n_rhs."""
         K = self.n_members - first_member if n_members is None else n_members
+        if rhs_members is not None:
+            if shared_rhs:
+                raise ValueError("shared_rhs is rhs_members=1")
+            self.slod._check(self.lib.slod_lod_factor_solve_complex_ensemble(
+                self.f, first_member, K, d_rhs_re, d_rhs_im, max(rhs_members, 1) * n_rhs if ld_rhs is None else ld_rhs, n_rhs,
+                rhs_members, d_u_re, d_u_im, K * n_rhs if ld_u is None else ld_u, stream))
+            return
         if ld_rhs is None:
             ld_rhs = n_rhs if shared_rhs else K * n_rhs
         self.slod._check(self.lib.slod_lod_factor_solve_complex(self.f, first_member, K, d_rhs_re, d_rhs_im, ld_rhs, n_rhs,
@@ -746,6 +773,27 @@ class Slod:
         """The complex symmetric LDL^T factors of S_k = alpha[k] A + beta[k] B (no pivoting), one member per pair of
         complex coefficients: a ComplexFactor with .info, .inertia(member), .solve_complex(...) and .close()."""
         return ComplexFactor(self, d_a, d_b, d_cols, alpha, beta)
+
+    def lod_factor_zldl_ensemble(self, d_a, d_b, d_cols, n_members, alpha, beta, ld_a_m=None, ld_b_m=None):
+        """lod_factor_zldl on ensemble matrices of n_members members: the factor member j = k * n_members + m is
+        alpha[k] A_m + beta[k] B_m.  A ComplexFactor; solve_complex(..., rhs_members=) maps the members to rhs columns."""
+        return ComplexFactor(self, d_a, d_b, d_cols, alpha, beta, matrix_members=n_members, ld_a_m=ld_a_m, ld_b_m=ld_b_m)
+
+    def lod_harmonic_response_ensemble(self, d_stiffness, d_mass, d_cols, n_members, omega, d_load_re, d_load_im, d_u_re, d_u_im,
+                                       n_rhs=1, damp_mass=0.0, damp_stiff=0.0, ld_a_m=None, ld_m_m=None, ld_load=None, ld_u=None):
+        """lod_harmonic_response for the n_members = K members of an ensemble matrix pair: (frequency k, member m, load
+        column c) is column (k K + m) * n_rhs + c of (d_u_re, d_u_im); member m's loads are the columns m * n_rhs + c of the
+        load.  Returns (rel_residual[F, K, n_rhs], growth[F, K], quantities[F, K, n_rhs, 4]) with
+        quantities = (u^H M u, u^H A u, Re u^H b, Im u^H b)."""
+        w = np.ascontiguousarray(np.atleast_1d(omega), dtype=np.float64)
+        F, K, n = len(w), max(n_members, 1), max(n_rhs, 1)
+        res, growth, q = np.zeros((F, K, n)), np.zeros((F, K)), np.zeros((F, K, n, 4))
+        self._check(self.lib.slod_lod_harmonic_response_ensemble(
+            self.h, d_stiffness, n_members if ld_a_m is None else ld_a_m, d_mass, n_members if ld_m_m is None else ld_m_m,
+            d_cols, n_members, damp_mass, damp_stiff, _dp(w), F, d_load_re, d_load_im,
+            n_members * n_rhs if ld_load is None else ld_load, n_rhs, d_u_re, d_u_im,
+            F * n_members * n_rhs if ld_u is None else ld_u, _dp(res), _dp(growth), _dp(q)))
+        return res, growth, q
 
     def lod_harmonic_response(self, d_stiffness, d_mass, d_cols, omega, d_load_re, d_load_im, d_u_re, d_u_im, n_rhs=1,
                               damp_mass=0.0, damp_stiff=0.0, ld_load=None, ld_u=None):

@@ -920,13 +920,79 @@ int slod_lod_factor_solve_complex(slod_lod_factor *f, int first_member, int n_me
  * negative, NaN or infinite (or so large that omega^2 overflows); ld_load < n_rhs; ld_u < n_freq n_rhs.
  * Runs on the handle's stream and has finished when it returns.
  * Not built: coefficient ensembles x frequencies, 2 x 2 pivots, damping that is not Rayleigh, adaptive frequency
- * refinement, this factor as a preconditioner. */
+ * refinement, this factor as a preconditioner.  (Of these, coefficient ensembles x frequencies exist by now as a call of
+ * their own: slod_lod_harmonic_response_ensemble, below.) */
 int slod_lod_harmonic_response(slod_handle *h, const double *d_stiffness, const double *d_mass, const uint32_t *d_cols,
                                double damp_mass, double damp_stiff, const double *omega /* HOST [n_freq] */, int n_freq,
                                const double *d_load_re, const double *d_load_im /* NULL = 0 */, size_t ld_load, int n_rhs,
                                double *d_u_re, double *d_u_im, size_t ld_u,
                                double *rel_residual /* HOST [n_freq * n_rhs], may be NULL */,
                                double *growth       /* HOST [n_freq], may be NULL */);
+
+/* ---- the frequency response of a coefficient ensemble: K members x F frequencies per call -----------
+ * The calls above for the K members of a coefficient ensemble on one pattern (the ensemble matrix layout: entry e of
+ * member m at values[e ld_m + m]).  The use is an uncertainty band around a transfer function: mean and spread of
+ * ||u(omega)|| over the realisations.  The factor members are numbered flat, frequency-major and member-minor:
+ *   factor member j = k K + m  is  S_j = alpha_k A_m + beta_k B_m,  coefficient pair (frequency) k on the matrices of member m.
+ * The banded factor pays one launch per block column whatever the number of members on it, so K x F members in one object
+ * cost the launches of one.
+ *
+ * LAYOUT of slod_lod_harmonic_response_ensemble: the response of (frequency k, member m, load column c) is column
+ * (k K + m) n_rhs + c of (d_u_re, d_u_im), ld_u >= F K n_rhs.  Member m's loads are the columns m n_rhs + c of d_load,
+ * ld_load >= K n_rhs; all frequencies share them.  With n_rhs = 1 the block of K columns at offset k K is therefore an
+ * ensemble coarse multi-vector, column = member: slod_lod_rhs_ensemble (the loads differ per member because C^T f does),
+ * slod_lod_reconstruct_ensemble, slod_lod_inner_ensemble and slod_ensemble_moments apply to a frequency's block as they
+ * are, by pointer offset with ld = F K.
+ * THE BITS: for every (k, m, c) the words of u, rel_residual and growth equal those of slod_lod_harmonic_response on
+ * member m's de-interleaved matrices and load at the single frequency omega_k (coefficients formed as there); they do not
+ * depend on K, F, a leading dimension, the member's position, the chunking or the run.  Padding entries >= K inside
+ * ld_a_m / ld_m_m and columns beyond the last inside ld_u are never read or written.
+ * The call works through the flat index j in chunks of at most 64 consecutive j (a chunk may start and end inside a
+ * frequency): one factor allocation per chunk, every chunk queued whole on the handle's stream and waited for once.
+ * n_freq n_members is unbounded there; slod_lod_factor_create_zldl_ensemble takes n_coef n_members <= 65535.
+ * quantities[col] = (u^H M u, u^H A u, Re u^H b, Im u^H b), col = (k K + m) n_rhs + c, A the symmetrised stiffness as
+ * passed: per row  u_re (M u)_re + u_im (M u)_im  (the same for A) and the two parts of conj(u_i) b_i  from the four
+ * products of the residual step, every product and sum rounded on its own, the rows summed in the fixed order of the
+ * residual, no atomics.  A zero load column gives four exact zeros.  Amplitude is sqrt(u^H M u), dissipated power
+ * omega (damp_mass u^H M u + damp_stiff u^H A u) / 2, and the balance
+ *   omega (damp_mass u^H M u + damp_stiff u^H A u) = Im u^H b
+ * tells whether a response is to be trusted.
+ * SLOD_ERR_NUMERIC reads
+ *   "slod_lod_harmonic_response_ensemble: frequency k, member m: pivot r of n is zero or not finite (re, im)"
+ * with the lowest flat j first; slod_lod_factor_create_zldl_ensemble names "coefficient k, member m", fills
+ * bad_pivot[k K + m] with the single call's index for that matrix (-1 elsewhere), leaves *out NULL and nothing allocated.
+ * SLOD_ERR_ARGUMENT, before any device work, with the call's name: what the single calls refuse; n_members < 1 or > 65535;
+ * n_coef < 1 or n_coef n_members > 65535; ld_a_m, ld_b_m or ld_m_m below n_members; ld_load < n_members n_rhs;
+ * ld_u / n_rhs < n_freq n_members; for the solve rhs_members < 1, members outside the factor, a real factor, a rhs
+ * leading dimension below the columns read, and in place (d_u == d_rhs) whenever two of the call's factor members read
+ * the same rhs columns or a member would read columns another one writes (first_member not a multiple of rhs_members).
+ * On the factor object slod_lod_factor_get_info_member(f, j, ..) and slod_lod_factor_inertia(f, j, ..) take the flat j;
+ * every real consumer refuses the object with the message above.
+ * Not built: members or frequencies spread over ranks, 2 x 2 pivots, damping that is not Rayleigh, adaptive frequency
+ * refinement, the complex factor as a preconditioner, output functionals other than u^H b, the deal.II adapter. */
+
+/* Factor member j = k * n_members + m is  S_j = alpha_k A_m + beta_k B_m;  A, B ensemble matrices (values member-minor,
+ * entry e of member m at d_a[e * ld_a_m + m]) on one d_cols; alpha, beta HOST [n_coef][2]. */
+int slod_lod_factor_create_zldl_ensemble(slod_handle *h, const double *d_a, size_t ld_a_m, const double *d_b, size_t ld_b_m,
+                                         int n_members, const uint32_t *d_cols, const double *alpha, const double *beta,
+                                         int n_coef, int32_t *bad_pivot /* HOST [n_coef * n_members], may be NULL */,
+                                         slod_lod_factor **out);
+
+/* slod_lod_factor_solve_complex in which factor member j reads the rhs columns (j % rhs_members) * n_rhs .. + n_rhs - 1
+ * and writes the columns (j - first_member) * n_rhs .. of u.  rhs_members = 1 is shared_rhs; rhs_members = the factor's
+ * member count is the distinct case. */
+int slod_lod_factor_solve_complex_ensemble(slod_lod_factor *f, int first_member, int n_members, const double *d_rhs_re,
+                                           const double *d_rhs_im, size_t ld_rhs, int n_rhs, int rhs_members,
+                                           double *d_u_re, double *d_u_im, size_t ld_u, void *hip_stream);
+
+int slod_lod_harmonic_response_ensemble(slod_handle *h, const double *d_stiffness, size_t ld_a_m, const double *d_mass,
+                                        size_t ld_m_m, const uint32_t *d_cols, int n_members, double damp_mass,
+                                        double damp_stiff, const double *omega /* HOST [n_freq] */, int n_freq,
+                                        const double *d_load_re, const double *d_load_im /* NULL = 0 */, size_t ld_load,
+                                        int n_rhs, double *d_u_re, double *d_u_im, size_t ld_u,
+                                        double *rel_residual /* HOST [n_freq*n_members*n_rhs], may be NULL */,
+                                        double *growth       /* HOST [n_freq*n_members], may be NULL */,
+                                        double *quantities   /* HOST [n_freq*n_members*n_rhs][4], may be NULL */);
 
 /* ---- refresh after a local coefficient change ----------------------------------------------
  * Every entry point above takes the coefficient as fixed for the life of a basis (the reference does too: one
