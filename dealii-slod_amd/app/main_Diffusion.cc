@@ -1,6 +1,6 @@
 // Counterpart of reference app/main_Diffusion.cc for the basis-construction path:
 //   main_Diffusion [n_global_refinements n_subdivisions oversampling stabilize [dump.bin]] [--compare] [--coarse] [--loads K]
-//                  [--heat STEPS DT] [--eigs K] [--shift SIGMA] [--wave STEPS DT] [--direct] [--ensemble K] [--perturb K]
+//                  [--heat STEPS DT] [--eigs K] [--shift SIGMA] [--wave STEPS DT] [--direct] [--irk gauss|radau] [--ensemble K] [--perturb K]
 //                  [--reuse-factor] [--precond-member J]
 //                  [--member K] [--ldl] [--harmonic K W0 W1 [--damping DM DS]] (with --ensemble: per member)
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
@@ -45,6 +45,11 @@
 // = .., power = ..", the numbers of the "harmonic J" line of a --member M --harmonic run; per frequency "harmonic J amplitude
 // over the ensemble of K: mean = .., standard deviation = .."; then for the frequency with the largest mean amplitude the L2
 // norms of the mean and of the standard deviation of the real and of the imaginary part on the fine grid.
+// --heat STEPS DT --irk gauss|radau, --wave STEPS DT --irk gauss|radau: the time loop by a two-stage implicit Runge-Kutta
+// scheme (Gauss-Legendre, order 4; Radau IIA, order 3, L-stable) with one complex solve per step on the complex LDL^T of its
+// step matrix (slod_lod_irk_coefficients, slod_lod_factor_create_zldl, slod_lod_irk_heat_steps_direct /
+// slod_lod_irk_wave_steps_direct; A_LOD symmetrised for both): the lines of --direct, the factor line with the range of |D|,
+// and behind it "factor: complex LDL^T of the SCHEME step, growth = ..".
 // --direct: the time loops of --heat and --wave run on a banded Cholesky factor of their matrix S instead of CG
 // (slod_lod_factor_create once, slod_lod_theta_steps_direct / slod_lod_newmark_steps_direct): one line "factor: n = ..,
 // half bandwidth = .., bytes = .., pivots in [.., ..]" per loop, then the same per-step lines without iterations and
@@ -136,6 +141,12 @@ static void print_factor(const slod_lod_factor_info &f)
               (unsigned long long)f.bytes, f.min_pivot, f.max_pivot);
 }
 
+static void print_irk_factor(const char *scheme, const slod_lod_factor_info &f, const slod_lod_factor_inertia_info &i)
+{
+  print_factor(f);
+  std::printf("factor: complex LDL^T of the %s step, growth = %.6e\n", scheme, i.norm_factor / i.norm_matrix);
+}
+
 static void print_ldl_factor(const slod_lod_factor_info &f, const slod_lod_factor_inertia_info &i)
 {
   std::printf("factor: n = %d, half bandwidth = %d, bytes = %llu, LDL^T, n_negative = %d (eigenvalues below sigma), growth = %.6e\n",
@@ -164,6 +175,8 @@ int main(int argc_all, char **argv_all)
   int                n_loads = 0, heat_steps = 0, n_eigs = 0, wave_steps = 0, n_members = 0, n_perturb = 0, member = 0, precond_member = -1;
   bool               reuse_factor = false;
   double             heat_dt = 0.0, wave_dt = 0.0, shift = 0.0;
+  int                irk = -1; // --irk gauss | radau: SLOD_IRK_GAUSS2, SLOD_IRK_RADAU2A
+  const char        *irk_name = "";
   std::vector<char *> args;
   for (int i = 0; i < argc_all; ++i)
     if (i > 0 && !std::strcmp(argv_all[i], "--compare"))
@@ -174,6 +187,11 @@ int main(int argc_all, char **argv_all)
       direct = true;
     else if (i > 0 && !std::strcmp(argv_all[i], "--ldl"))
       ldl = true;
+    else if (i > 0 && !std::strcmp(argv_all[i], "--irk") && i + 1 < argc_all)
+      {
+        irk_name = argv_all[++i];
+        irk      = !std::strcmp(irk_name, "gauss") ? SLOD_IRK_GAUSS2 : !std::strcmp(irk_name, "radau") ? SLOD_IRK_RADAU2A : -2;
+      }
     else if (i > 0 && !std::strcmp(argv_all[i], "--loads") && i + 1 < argc_all)
       n_loads = std::atoi(argv_all[++i]);
     else if (i > 0 && !std::strcmp(argv_all[i], "--heat") && i + 2 < argc_all)
@@ -217,6 +235,8 @@ int main(int argc_all, char **argv_all)
   char    **argv = args.data();
   try
     {
+      if (irk == -2)
+        throw std::runtime_error("--irk takes gauss or radau");
       LODParameters<2, 1> par;
       par.n_global_refinements  = argc > 1 ? std::atoi(argv[1]) : 3;
       par.n_subdivisions        = argc > 2 ? std::atoi(argv[2]) : 4;
@@ -299,12 +319,17 @@ int main(int argc_all, char **argv_all)
               problem.solve();
             }
           problem.assemble_mass_matrix();
-          problem.solve_heat((unsigned int)heat_steps, heat_dt, 1.0, direct);
+          if (irk >= 0)
+            problem.solve_heat_irk(irk, (unsigned int)heat_steps, heat_dt);
+          else
+            problem.solve_heat((unsigned int)heat_steps, heat_dt, 1.0, direct);
           problem.compare_heat_with_lod();
-          if (direct)
+          if (irk >= 0)
+            print_irk_factor(irk_name, problem.last_factor_info(), problem.last_factor_inertia());
+          else if (direct)
             print_factor(problem.last_factor_info());
           for (int k = 0; k < heat_steps; ++k)
-            if (direct)
+            if (direct || irk >= 0)
               std::printf("heat step %d\n", k + 1);
             else
               std::printf("heat step %d: iterations = %d, relative residual = %.6e\n", k + 1, problem.heat_iterations()[k],
@@ -358,11 +383,16 @@ int main(int argc_all, char **argv_all)
             }
           if (heat_steps <= 0 && n_eigs <= 0)
             problem.assemble_mass_matrix();
-          problem.solve_wave((unsigned int)wave_steps, wave_dt, 0.25, 0.5, direct);
-          if (direct)
+          if (irk >= 0)
+            problem.solve_wave_irk(irk, (unsigned int)wave_steps, wave_dt);
+          else
+            problem.solve_wave((unsigned int)wave_steps, wave_dt, 0.25, 0.5, direct);
+          if (irk >= 0)
+            print_irk_factor(irk_name, problem.last_factor_info(), problem.last_factor_inertia());
+          else if (direct)
             print_factor(problem.last_factor_info());
           for (int k = 0; k < wave_steps; ++k)
-            if (direct)
+            if (direct || irk >= 0)
               std::printf("wave step %d: kinetic = %.12e, potential = %.12e, work = %.12e\n", k + 1, problem.wave_kinetic()[k + 1],
                           problem.wave_potential()[k + 1], problem.wave_work()[k + 1]);
             else

@@ -1243,6 +1243,109 @@ namespace slod
           "slod_compute_error_norms");
   }
 
+  template <int dim, int spacedim>
+  slod_lod_factor *LOD<dim, spacedim>::factor_lod_irk(const int scheme, const int order, const double dt)
+  {
+    double alpha[2], beta[2];
+    if (slod_lod_irk_coefficients(scheme, order, dt, 0.0, 0.0, alpha, beta) != SLOD_OK)
+      throw std::runtime_error(std::string("slod_lod_irk_coefficients: ") + slod_last_error(nullptr));
+    slod_lod_factor *f = nullptr;
+    check(slod_lod_factor_create_zldl(handle, d_lod_sym, d_lod_mass, d_lod_cols, alpha, beta, 1, nullptr, &f),
+          "slod_lod_factor_create_zldl");
+    factors.push_back(f);
+    check(slod_lod_factor_get_info(f, &lod_factor_info), "slod_lod_factor_get_info");
+    check(slod_lod_factor_inertia(f, 0, &lod_factor_inertia), "slod_lod_factor_inertia");
+    return f;
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_heat_irk(const int scheme, const unsigned int n_steps, const double dt)
+  {
+    if (!d_lod_mass || !d_fem_rhs)
+      throw std::runtime_error("solve_heat_irk: assemble_mass_matrix and assemble_and_solve_fem_problem come first");
+    const unsigned int    n_patches = (unsigned int)patches.size();
+    const std::size_t     n_coarse = (std::size_t)n_patches * spacedim;
+    const int             cap = slod_lod_row_capacity(handle);
+    check(cap, "slod_lod_row_capacity");
+    std::vector<uint32_t> rows(n_patches);
+    for (unsigned int p = 0; p < n_patches; ++p)
+      rows[p] = p;
+    if (!d_lod_sym)
+      d_lod_sym = device_alloc<double>((std::size_t)n_patches * cap * spacedim * spacedim);
+    if (!d_heat_rhs)
+      d_heat_rhs = device_alloc<double>(n_coarse);
+    if (!d_heat_u)
+      d_heat_u = device_alloc<double>(n_coarse);
+    check(slod_lod_matrix_symmetrize(handle, d_lod_values, d_lod_cols, d_lod_sym, nullptr), "slod_lod_matrix_symmetrize");
+    check(slod_lod_rhs(handle, rows.data(), n_patches, d_basis, basis_stride, d_fem_rhs, d_heat_rhs, nullptr), "slod_lod_rhs");
+    if (hipMemset(d_heat_u, 0, n_coarse * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+      throw std::runtime_error("solve_heat_irk: clearing the initial state failed");
+    lod_heat_iterations.assign(n_steps, 0);
+    lod_heat_residuals.assign(n_steps, 0.0);
+    slod_lod_factor *f = factor_lod_irk(scheme, 1, dt);
+    check(slod_lod_irk_heat_steps_direct(handle, f, 0, scheme, d_lod_sym, d_lod_cols, dt, (int)n_steps, 1, d_heat_u, 1, d_heat_rhs, 1, 0),
+          "slod_lod_irk_heat_steps_direct");
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_wave_irk(const int scheme, const unsigned int n_steps, const double dt)
+  {
+    if (!d_lod_mass || !d_fem_rhs)
+      throw std::runtime_error("solve_wave_irk: assemble_mass_matrix and assemble_and_solve_fem_problem come first");
+    const unsigned int n_patches = (unsigned int)patches.size();
+    const std::size_t  n_coarse = (std::size_t)n_patches * spacedim;
+    const std::size_t  NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+    const std::size_t  fine_size = (NE + 1) * (NE + 1) * spacedim;
+    const int          cap = slod_lod_row_capacity(handle);
+    check(cap, "slod_lod_row_capacity");
+    std::vector<uint32_t> rows(n_patches);
+    for (unsigned int p = 0; p < n_patches; ++p)
+      rows[p] = p;
+    if (!d_lod_sym)
+      d_lod_sym = device_alloc<double>((std::size_t)n_patches * cap * spacedim * spacedim);
+    if (!d_wave_state)
+      d_wave_state = device_alloc<double>(4 * n_coarse);
+    if (!d_wave_fine)
+      d_wave_fine = device_alloc<double>(fine_size);
+    double *d_u = d_wave_state, *d_v = d_u + n_coarse, *d_b = d_v + 2 * n_coarse;
+    check(slod_lod_matrix_symmetrize(handle, d_lod_values, d_lod_cols, d_lod_sym, nullptr), "slod_lod_matrix_symmetrize");
+    check(slod_lod_rhs(handle, rows.data(), n_patches, d_basis, basis_stride, d_fem_rhs, d_b, nullptr), "slod_lod_rhs");
+    if (hipMemset(d_wave_state, 0, 3 * n_coarse * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+      throw std::runtime_error("solve_wave_irk: clearing the initial state failed");
+    std::vector<double> b(n_coarse), u(n_coarse);
+    if (hipMemcpy(b.data(), d_b, n_coarse * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      throw std::runtime_error("solve_wave_irk: download of the load failed");
+    slod_lod_factor *f = factor_lod_irk(scheme, 2, dt);
+    lod_wave_iterations.assign(n_steps, 0);
+    lod_wave_residuals.assign(n_steps, 0.0);
+    lod_wave_kinetic.assign(n_steps + 1, 0.0);
+    lod_wave_potential.assign(n_steps + 1, 0.0);
+    lod_wave_work.assign(n_steps + 1, 0.0);
+    for (unsigned int k = 0; k < n_steps; ++k)
+      {
+        double kinetic[2], potential[2];
+        check(slod_lod_irk_wave_steps_direct(handle, f, 0, scheme, d_lod_sym, d_lod_mass, d_lod_cols, dt, 0.0, 0.0, 1, 1, d_u, 1, d_v, 1,
+                                             d_b, 1, 0, kinetic, potential),
+              "slod_lod_irk_wave_steps_direct");
+        if (hipMemcpy(u.data(), d_u, n_coarse * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+          throw std::runtime_error("solve_wave_irk: download of the state failed");
+        if (k == 0)
+          {
+            lod_wave_kinetic[0]   = kinetic[0];
+            lod_wave_potential[0] = potential[0];
+          }
+        lod_wave_kinetic[k + 1]   = kinetic[1];
+        lod_wave_potential[k + 1] = potential[1];
+        double work = 0.0;
+        for (std::size_t i = 0; i < n_coarse; ++i)
+          work += u[i] * b[i];
+        lod_wave_work[k + 1] = work;
+      }
+    check(slod_lod_reconstruct(handle, d_basis, basis_stride, d_u, d_wave_fine, nullptr), "slod_lod_reconstruct");
+    check(slod_compute_error_norms(handle, 0, d_wave_fine, nullptr, nullptr, nullptr, &wave_norms, nullptr),
+          "slod_compute_error_norms");
+  }
+
   // LOD.cc:1103-1237 with f = 1.  The reference solves with SolverDirect; the CG of the fine problem runs on the
   // coarse grid to the tolerance of the fine solve.
   template <int dim, int spacedim>

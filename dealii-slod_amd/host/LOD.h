@@ -148,6 +148,8 @@ namespace slod
     // ldl: the banded LDL^T factor of a symmetric, possibly indefinite matrix instead (slod_lod_factor_create_ldl, no
     // pivoting); last_factor_inertia() then holds the signs of D, ||S||_inf and || |L||D||L^T| ||_inf of member 0.
     slod_lod_factor            *factor_lod_matrix(const double *d_values, const bool ldl = false);
+    // the complex LDL^T of alpha sym(A_LOD) + beta M_LOD (d_lod_sym must hold the symmetrised stiffness), owned like the others
+    slod_lod_factor            *factor_lod_irk(const int scheme, const int order, const double dt);
     const slod_lod_factor_info &last_factor_info() const { return lod_factor_info; }
     const slod_lod_factor_inertia_info &last_factor_inertia() const { return lod_factor_inertia; }
     const std::vector<int>    &heat_iterations() const { return lod_heat_iterations; }
@@ -188,6 +190,15 @@ namespace slod
     const std::vector<double> &wave_potential() const { return lod_wave_potential; }
     const std::vector<double> &wave_work() const { return lod_wave_work; }
     const slod_error_norms    &norms_wave() const { return wave_norms; }
+    // solve_heat / solve_wave by a two-stage implicit Runge-Kutta scheme (SLOD_IRK_GAUSS2: order 4, SLOD_IRK_RADAU2A: order 3,
+    // L-stable) with one complex solve per step: the pair of slod_lod_irk_coefficients, the complex LDL^T of
+    // S = alpha sym(A_LOD) + beta M_LOD (slod_lod_factor_create_zldl, owned by this object; last_factor_info() and
+    // last_factor_inertia() describe it: the range of |D|, the growth), then slod_lod_irk_heat_steps_direct in one call or
+    // slod_lod_irk_wave_steps_direct once per step (the calls compose bit for bit) for the work u^T b, as solve_wave.  The
+    // load is that of solve(), constant in time; the wave starts from rest, undamped, and carries no acceleration.  The
+    // results are read as those of solve_heat(.., direct) and solve_wave(.., direct).
+    void solve_heat_irk(const int scheme, const unsigned int n_steps, const double dt);
+    void solve_wave_irk(const int scheme, const unsigned int n_steps, const double dt);
     // The steady response to the harmonic load Re(b e^{i omega t}), b the load of solve(), with the Rayleigh damping
     // C = damp_mass M + damp_stiff sym(A): (1 + i omega damp_stiff) sym(A) u + (i omega damp_mass - omega^2) M u = b for every
     // omega of the sweep in one slod_lod_harmonic_response call; after assemble_mass_matrix() and

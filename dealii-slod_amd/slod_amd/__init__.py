@@ -208,6 +208,12 @@ def load():
                                                            C.c_size_t, vp]
     lib.slod_lod_harmonic_response_ensemble.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_int, C.c_double, C.c_double, dp,
                                                         C.c_int, vp, vp, C.c_size_t, C.c_int, vp, vp, C.c_size_t, dp, dp, dp]
+    lib.slod_lod_irk_coefficients.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, dp, dp]
+    lib.slod_lod_irk_heat_steps_direct.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, C.c_double, C.c_int, C.c_int, vp, C.c_size_t,
+                                                   vp, C.c_size_t, C.c_size_t]
+    lib.slod_lod_irk_wave_steps_direct.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_double, C.c_double, C.c_double,
+                                                   C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t,
+                                                   dp, dp]
     lib.slod_update_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, C.c_int, C.c_size_t, C.c_int, vp]
     lib.slod_dirty_patches.argtypes = [vp, vp, u32p, C.c_size_t]
     lib.slod_plan_create_dirty.argtypes = [vp, C.c_uint32, vp, C.POINTER(vp)]
@@ -505,6 +511,13 @@ LodFactor = Factor   # the name of the object in the documents of the LDL^T fact
 
 def _factor_ptr(f):
     return f.f if isinstance(f, Factor) else f
+
+
+IRK_GAUSS2, IRK_RADAU2A = 0, 1   # enum slod_irk_scheme
+
+
+def _irk_scheme(scheme):
+    return {"gauss": IRK_GAUSS2, "radau": IRK_RADAU2A}.get(scheme, scheme)
 
 
 class Slod:
@@ -834,6 +847,40 @@ class Slod:
             self.h, _factor_ptr(factor), d_stiffness, d_mass, d_cols, dt, beta, gamma, damp_mass, damp_stiff, n_steps, n_rhs,
             d_u, n_rhs if ld_u is None else ld_u, d_v, n_rhs if ld_v is None else ld_v, d_a, n_rhs if ld_a is None else ld_a,
             d_load, n_rhs if ld_load is None else ld_load, load_step_stride, _dp(kin) if energies else None,
+            _dp(pot) if energies else None))
+        return kin, pot
+
+    # ---- two-stage implicit Runge-Kutta on a member of a complex factor: one complex solve per step ----
+    def lod_irk_coefficients(self, scheme, order, dt, damp_mass=0.0, damp_stiff=0.0):
+        """(alpha, beta), complex, of the step matrix S = alpha A + beta M of scheme IRK_GAUSS2 / IRK_RADAU2A (or "gauss" /
+        "radau") for lod_factor_zldl(sym(A), M, cols, alpha, beta); order 1: heat, 2: wave."""
+        a, b = np.zeros(2), np.zeros(2)
+        rc = self.lib.slod_lod_irk_coefficients(_irk_scheme(scheme), order, dt, damp_mass, damp_stiff, _dp(a), _dp(b))
+        if rc:
+            raise SlodError(rc, self.lib.slod_last_error(None).decode())
+        return complex(a[0], a[1]), complex(b[0], b[1])
+
+    def lod_irk_heat_steps(self, factor, scheme, d_stiffness, d_cols, dt, n_steps, d_u, n_rhs=1, member=0, ld_u=None,
+                           d_load=None, ld_load=None, load_stage_stride=0):
+        """n_steps of the two-stage scheme for M u' + A u = b(t) on d_u in place, on member `member` of the complex
+        factor of S = M + dt lambda A (lod_irk_coefficients).  Stage i of step k reads the load at
+        d_load + (2 k + i) * load_stage_stride doubles."""
+        self._check(self.lib.slod_lod_irk_heat_steps_direct(
+            self.h, _factor_ptr(factor), member, _irk_scheme(scheme), d_stiffness, d_cols, dt, n_steps, n_rhs, d_u,
+            n_rhs if ld_u is None else ld_u, d_load, n_rhs if ld_load is None else ld_load, load_stage_stride))
+
+    def lod_irk_wave_steps(self, factor, scheme, d_stiffness, d_mass, d_cols, dt, n_steps, d_u, d_v, n_rhs=1, member=0,
+                           ld_u=None, ld_v=None, d_load=None, ld_load=None, load_stage_stride=0, damp_mass=0.0,
+                           damp_stiff=0.0, energies=True):
+        """n_steps of the two-stage scheme for M u'' + C u' + A u = b(t) on d_u, d_v in place, on member `member` of the
+        complex factor of lod_irk_coefficients(scheme, 2, dt, damp_mass, damp_stiff).  Returns (kinetic, potential) as
+        arrays [n_steps + 1, n_rhs], or (None, None) with energies=False."""
+        shape = (max(n_steps, 0) + 1, max(n_rhs, 1))
+        kin, pot = (np.zeros(shape), np.zeros(shape)) if energies else (None, None)
+        self._check(self.lib.slod_lod_irk_wave_steps_direct(
+            self.h, _factor_ptr(factor), member, _irk_scheme(scheme), d_stiffness, d_mass, d_cols, dt, damp_mass, damp_stiff,
+            n_steps, n_rhs, d_u, n_rhs if ld_u is None else ld_u, d_v, n_rhs if ld_v is None else ld_v, d_load,
+            n_rhs if ld_load is None else ld_load, load_stage_stride, _dp(kin) if energies else None,
             _dp(pot) if energies else None))
         return kin, pot
 

@@ -890,6 +890,7 @@ int slod_lod_eigs_shift_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, do
  * Every other call that takes a factor refuses a complex one (slod_lod_factor_solve(_ensemble), the theta and Newmark
  * _direct calls, the slod_lod_eigs*_direct calls, the _precond calls): SLOD_ERR_ARGUMENT,
  *   "<call>: a complex factor (slod_lod_factor_create_zldl) is solved by slod_lod_factor_solve_complex".
+ * (The implicit Runge-Kutta steppers slod_lod_irk_*_steps_direct, below, are the time loops on a complex factor.)
  *
  * S_k = alpha_k A + beta_k B, complex alpha_k, beta_k; A, B: values arrays of two full sets of block rows on one d_cols
  * (sym(A_LOD), M_LOD); ONLY THE LOWER TRIANGLE IN FACTOR ORDER IS READ.  alpha, beta: HOST [n_members][2] (re, im). */
@@ -993,6 +994,63 @@ int slod_lod_harmonic_response_ensemble(slod_handle *h, const double *d_stiffnes
                                         double *rel_residual /* HOST [n_freq*n_members*n_rhs], may be NULL */,
                                         double *growth       /* HOST [n_freq*n_members], may be NULL */,
                                         double *quantities   /* HOST [n_freq*n_members*n_rhs][4], may be NULL */);
+
+/* ---- fourth-order time stepping: two-stage implicit Runge-Kutta on the complex factor ----------------
+ * The direct steppers above are second order at best and pay one banded solve per step, whose cost is the serial walk of
+ * the block rows, not the arithmetic.  A two-stage implicit Runge-Kutta scheme has a 2 x 2 Butcher matrix
+ * A_rk = T diag(lambda, conj lambda) T^-1 with a complex conjugate pair of eigenvalues; for a linear system with real data
+ * the two transformed stage equations are conjugates of each other, so ONE complex solve per step, on a member of a
+ * factor of slod_lod_factor_create_zldl, gives
+ *   SLOD_IRK_GAUSS2   Gauss-Legendre, order 4, A-stable, conserves the quadratic energy of the undamped wave equation;
+ *                     lambda = 1/4 + i sqrt(3)/12, c = (1/2 - sqrt(3)/6, 1/2 + sqrt(3)/6)
+ *   SLOD_IRK_RADAU2A  Radau IIA, order 3, L-stable (stiff modes are damped out, the scheme for heat flow);
+ *                     lambda = 1/3 + i sqrt(2)/6, c = (1/3, 1).
+ * With z = dt lambda, tau the first row of T^-1, sigma = tau_1 + tau_2, mu = b^T T[:,0] (host constants in long double)
+ * and b_i the load at t_k + c_i dt:
+ *   heat  M u' + A u = b(t):  S = M + z A;  r = tau_1 (b_1 - A u) + tau_2 (b_2 - A u);  S w = r;  u += 2 dt Re(mu w)
+ *   wave  M u'' + C u' + A u = b(t), C = damp_mass M + damp_stiff A:  S = (1 + z damp_mass) M + (z damp_stiff + z^2) A;
+ *         r = tau_1 b_1 + tau_2 b_2 - sigma [A (u + (z + damp_stiff) v) + damp_mass M v];  S w_v = r;
+ *         w_u = sigma v + z w_v;  u += 2 dt Re(mu w_u);  v += 2 dt Re(mu w_v).   No acceleration vector is carried.
+ * Re S is symmetric positive definite (Re lambda > 0, Re z^2 > 0), so every leading block of S is non-singular and the
+ * factorisation exists without pivoting; its growth is measured, as for every complex factor (slod_lod_factor_inertia).
+ *
+ * slod_lod_irk_coefficients returns the pair for slod_lod_factor_create_zldl(h, sym(A_LOD), M_LOD, d_cols, alpha, beta, 1,
+ * ..):  heat (order 1) alpha = z, beta = 1;  wave (order 2) alpha = z damp_stiff + z^2, beta = 1 + z damp_mass, formed in
+ * long double and rounded once per part.  Host only, no handle; an error text is read by slod_last_error(NULL).
+ * SLOD_ERR_ARGUMENT: NULL alpha or beta; an unknown scheme or order; dt <= 0, NaN or infinite; a negative, NaN or infinite
+ * damping; a damping given with order = 1; a coefficient that overflows.
+ *
+ * THE STEPPERS run n_steps on d_u (and d_v) in place on member `member` of f_S, so one factor object may hold several dt.
+ * d_stiffness is the symmetrised stiffness the factor was built from.  LOADS are given at the stage times: stage i
+ * (0, 1) of step k is at d_load + (2 k + i) load_stage_stride; stride 0 is one constant load, d_load NULL the zero load.
+ * kinetic, potential: HOST [(n_steps + 1) n_rhs] with the meaning and the sums of slod_lod_newmark_steps (1/2 v^T M v,
+ * 1/2 u^T A u, row 0 the entry state); both NULL: not computed.  A step is three launches (right-hand side: the fma chains
+ * of slod_lod_apply_multi per row on one read of the row's column indices, then the complex combination with every product
+ * and sum rounded on its own; the sweeps of slod_lod_factor_solve_complex, out of place; the update) and two more with the
+ * energies.  The loop is queued whole on the handle's stream and waited for once: no allocation inside the loop, nothing
+ * read back per step; the mass product is skipped when damp_mass = 0.
+ * THE BITS of a column depend only on the factor member, the matrices, the parameters and that column's state and loads:
+ * not on n_rhs, a leading dimension, the column's position or the run; one call with n_steps = 2 equals two calls with
+ * n_steps = 1.  That the factor belongs to dt, the scheme and the dampings is not checked, as for the other _direct calls.
+ * SLOD_ERR_ARGUMENT, before any device work, with the call's name: a NULL handle, matrix, d_cols or state; an unknown
+ * scheme; dt <= 0, NaN or infinite; a negative, NaN or infinite damping; n_steps < 1 or n_rhs < 1; a leading dimension
+ * below n_rhs; exactly one of kinetic / potential; a NULL factor; the factor of another handle / row count; a real factor,
+ *   "<call>: takes a complex factor (slod_lod_factor_create_zldl)";
+ * a member outside the factor.  The real consumers go on refusing complex factors as above.
+ * Not built: three-stage schemes (Radau IIA of order 5 and Gauss of order 6 need one real and one complex member),
+ * ensemble forms, CG or PCG as the stage solver, step-size control, dense output, the deal.II adapter. */
+enum slod_irk_scheme { SLOD_IRK_GAUSS2 = 0, SLOD_IRK_RADAU2A = 1 };
+int slod_lod_irk_coefficients(int scheme, int order /* 1 heat, 2 wave */, double dt, double damp_mass, double damp_stiff,
+                              double alpha[2], double beta[2]);
+int slod_lod_irk_heat_steps_direct(slod_handle *h, slod_lod_factor *f_S, int member, int scheme, const double *d_stiffness,
+                                   const uint32_t *d_cols, double dt, int n_steps, int n_rhs, double *d_u, size_t ld_u,
+                                   const double *d_load /* NULL = 0 */, size_t ld_load, size_t load_stage_stride);
+int slod_lod_irk_wave_steps_direct(slod_handle *h, slod_lod_factor *f_S, int member, int scheme, const double *d_stiffness,
+                                   const double *d_mass, const uint32_t *d_cols, double dt, double damp_mass, double damp_stiff,
+                                   int n_steps, int n_rhs, double *d_u, size_t ld_u, double *d_v, size_t ld_v,
+                                   const double *d_load /* NULL = 0 */, size_t ld_load, size_t load_stage_stride,
+                                   double *kinetic   /* HOST [(n_steps+1)*n_rhs], may be NULL */,
+                                   double *potential /* HOST [(n_steps+1)*n_rhs], may be NULL */);
 
 /* ---- refresh after a local coefficient change ----------------------------------------------
  * Every entry point above takes the coefficient as fixed for the life of a basis (the reference does too: one
