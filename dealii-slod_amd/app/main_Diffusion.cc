@@ -70,6 +70,12 @@
 // members), one line "member K wave step J: kinetic = .., potential = .., work = .." per member and step, the numbers of
 // the "wave step J" line of a --member K --wave STEPS DT --direct run, then the L2 norms of the mean and of the standard
 // deviation of the final states.  Without --direct the two flags act independently.
+// --ensemble K --heat STEPS DT --irk gauss|radau, --ensemble K --wave STEPS DT --irk gauss|radau: after the lines above, the
+// same loops of every member by the two-stage scheme on one complex factor object with a member per realisation
+// (slod_lod_factor_create_zldl_ensemble, slod_lod_irk_heat_steps_ensemble_direct / slod_lod_irk_wave_steps_ensemble_direct):
+// the complex factor lines of member 0, "member K irk heat step J: L2 distance = .., energy distance = .." or "member K irk
+// wave step J: kinetic = .., potential = .., work = ..", the numbers of a --member K .. --irk run, then one line "SLOD irk
+// heat|wave ensemble of K at T = ..: L2 norm of the mean = .., of the standard deviation = ..".
 // --member K: a run without --ensemble on the coefficient that is member K of an ensemble run (K fields are drawn and
 // dropped before the problem draws its own).
 // --perturb K: a local coefficient change after everything else.  K cells of the coefficient's 2^r x 2^r grid, picked by a
@@ -435,7 +441,8 @@ int main(int argc_all, char **argv_all)
                 std::printf("member %d: PCG iterations = %d, Jacobi-CG iterations = %d\n", k, problem.ensemble_precond_iterations()[k],
                             problem.ensemble_precond_jacobi_iterations()[k]);
             }
-          if (((heat_steps > 0 || wave_steps > 0 || n_eigs > 0) && direct) || n_harmonic > 0)
+          const bool irk_ensemble = irk >= 0 && (heat_steps > 0 || wave_steps > 0);
+          if (((heat_steps > 0 || wave_steps > 0 || n_eigs > 0) && direct) || n_harmonic > 0 || irk_ensemble)
             problem.assemble_mass_matrix_ensemble();
           if (n_harmonic > 0)
             {
@@ -493,6 +500,36 @@ int main(int argc_all, char **argv_all)
                                 problem.wave_ensemble_work()[at]);
                   }
               std::printf("SLOD wave ensemble of %d at T = %g: L2 norm of the mean = %.12e, of the standard deviation = %.12e\n",
+                          n_members, wave_steps * wave_dt, problem.norms_wave_ensemble_mean().l2[0],
+                          problem.norms_wave_ensemble_deviation().l2[0]);
+            }
+          if (heat_steps > 0 && irk >= 0)
+            {
+              problem.solve_heat_irk_ensemble(irk, (unsigned int)heat_steps, heat_dt);
+              print_irk_factor(irk_name, problem.last_factor_info(), problem.last_factor_inertia());
+              for (int j = 0; j < heat_steps; ++j)
+                for (int k = 0; k < n_members; ++k)
+                  {
+                    const slod_error_norms &e = problem.error_heat_ensemble()[(std::size_t)j * n_members + k];
+                    std::printf("member %d irk heat step %d: L2 distance = %.12e, energy distance = %.12e\n", k, j + 1, e.l2[0], e.energy);
+                  }
+              std::printf("SLOD irk heat ensemble of %d at T = %g: L2 norm of the mean = %.12e, of the standard deviation = %.12e\n",
+                          n_members, heat_steps * heat_dt, problem.norms_heat_ensemble_mean().l2[0],
+                          problem.norms_heat_ensemble_deviation().l2[0]);
+            }
+          if (wave_steps > 0 && irk >= 0)
+            {
+              problem.solve_wave_irk_ensemble(irk, (unsigned int)wave_steps, wave_dt);
+              print_irk_factor(irk_name, problem.last_factor_info(), problem.last_factor_inertia());
+              for (int k = 0; k < n_members; ++k)
+                for (int j = 1; j <= wave_steps; ++j)
+                  {
+                    const std::size_t at = (std::size_t)j * n_members + k;
+                    std::printf("member %d irk wave step %d: kinetic = %.12e, potential = %.12e, work = %.12e\n", k, j,
+                                problem.wave_ensemble_kinetic()[at], problem.wave_ensemble_potential()[at],
+                                problem.wave_ensemble_work()[at]);
+                  }
+              std::printf("SLOD irk wave ensemble of %d at T = %g: L2 norm of the mean = %.12e, of the standard deviation = %.12e\n",
                           n_members, wave_steps * wave_dt, problem.norms_wave_ensemble_mean().l2[0],
                           problem.norms_wave_ensemble_deviation().l2[0]);
             }

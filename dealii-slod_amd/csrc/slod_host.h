@@ -296,10 +296,12 @@ void slod_lod_zfactor_solve_launch(const slod_lod_factor *f, hipStream_t st, int
 void slod_lod_factor_solve_launch(const slod_lod_factor *f, hipStream_t st, const double *d_rhs, size_t ld_rhs, int n_rhs, double *d_u,
                                   size_t ld_u, int first_member = 0, int n_members = 1);
 // out[0 .. n_rhs) = 1/2 v_c^T M v_c, out[n_rhs .. 2 n_rhs) = 1/2 u_c^T A u_c: the two launches of the energies of the Newmark
-// loop (slod_lod_wave.hip) for the other time loops; d_part_k, d_part_p: ngroup * n_rhs doubles each (slod_lod_tile.hip.h)
+// loop (slod_lod_wave.hip) for the other time loops; d_part_k, d_part_p: ngroup * n_rhs doubles each (slod_lod_tile.hip.h).
+// per_col: column c reads member c of the ensemble matrices (ld_a_m, ld_m_m), as the Newmark ensemble loop does.
 void slod_lod_energies_launch(const slod_handle *h, hipStream_t st, const double *d_stiffness, const double *d_mass,
                               const uint32_t *d_cols, int n_rhs, const double *d_u, size_t ld_u, const double *d_v, size_t ld_v,
-                              double *d_part_k, double *d_part_p, double *d_out);
+                              double *d_part_k, double *d_part_p, double *d_out, bool per_col = false, size_t ld_a_m = 1,
+                              size_t ld_m_m = 1);
 // SLOD_ERR_ARGUMENT, "<who>: NULL factor", "<who>: factor of another handle / row count" or "<who>: factor of another
 // member count" (the time loops on one matrix take a factor of one member) or "<who>: a complex factor
 // (slod_lod_factor_create_zldl) is solved by slod_lod_factor_solve_complex"; else SLOD_OK

@@ -20,6 +20,11 @@
 // host body (irk_steps), queued whole on the handle's stream and waited for once.  Everything besides the chains is
 // elementwise with fp contract off: the bits of a column depend on the factor member, the matrices, the parameters and
 // that column alone.
+//   slod_lod_irk_heat_steps_ensemble_direct, slod_lod_irk_wave_steps_ensemble_direct
+// are the same loops with a matrix, a factor member and a column per member of a coefficient ensemble: the right-hand
+// side kernels run with PER_COL set (the same chains on member m's words of the member-minor ensemble matrices, their
+// loads issued LOD_SLOTS slots ahead), the solve launches member first_member + m on column m, k_irk_advance serves as
+// it is, and the energies are k_lod_inner<true>.  Column m keeps the words of the single call on member m.
 #include "slod_lod_tile.hip.h"
 
 #include <cmath>
@@ -74,11 +79,89 @@ namespace
       }
   }
 
-  // r = tau_1 (b_1 - A u) + tau_2 (b_2 - A u) per (row, column), both planes; b1 NULL: zero load
+  // The same chains with a matrix per column on the one pattern (the ensemble layout of include/slod.h): entry e of
+  // column col's matrices at a[e ld_a + col] and m[e ld_m + col].  Every (row, column) streams its own matrix words, so,
+  // as in slod_lod_row_product_per_col, the loads of SLOTS slots are issued before the first fma needs one: every word of
+  // A once for the chains on x0 and x1, the words of M in the same batch when the mass chain runs.  A slot past the end
+  // of the row reads the last one and adds nothing, like an unused slot.
+  template <int NCHAIN, int S, int SLOTS> // S = s, a constant here so that nothing stands between the loads
+  __device__ __forceinline__ void irk_row_products_per_col(int p, int d, int cap, int NP, const double *__restrict__ a, size_t ld_a,
+                                                           const double *__restrict__ m, size_t ld_m,
+                                                           const uint32_t *__restrict__ cols, const double *__restrict__ x0,
+                                                           size_t ld0, const double *__restrict__ x1, size_t ld1, int col,
+                                                           double (&acc)[3])
+  {
+    const size_t slot0 = (size_t)p * cap;
+    acc[0] = acc[1] = acc[2] = 0.0;
+    for (int j0 = 0; j0 < cap; j0 += SLOTS)
+      {
+        bool   used[SLOTS];
+        double aw[SLOTS][S], mw[NCHAIN >= 3 ? SLOTS : 1][S], xu[SLOTS][S], xv[NCHAIN >= 2 ? SLOTS : 1][S];
+#pragma unroll
+        for (int u = 0; u < SLOTS; ++u)
+          {
+            const int      j = min(j0 + u, cap - 1);
+            const uint32_t q = cols[slot0 + j];
+            used[u]          = q < (uint32_t)NP && j0 + u < cap;
+            const size_t qs = (size_t)(used[u] ? q : (uint32_t)p) * S, at = (slot0 + j) * S * S + d * S;
+#pragma unroll
+            for (int e = 0; e < S; ++e)
+              {
+                aw[u][e] = a[(at + e) * ld_a + col];
+                xu[u][e] = x0[(qs + e) * ld0 + col];
+                if constexpr (NCHAIN >= 2)
+                  xv[u][e] = x1[(qs + e) * ld1 + col];
+                if constexpr (NCHAIN >= 3)
+                  mw[u][e] = m[(at + e) * ld_m + col];
+              }
+          }
+#pragma unroll
+        for (int u = 0; u < SLOTS; ++u)
+#pragma unroll
+          for (int e = 0; e < S; ++e)
+            {
+              const double t0 = fma(aw[u][e], xu[u][e], acc[0]);
+              acc[0]          = used[u] ? t0 : acc[0];
+              if constexpr (NCHAIN >= 2)
+                {
+                  const double t1 = fma(aw[u][e], xv[u][e], acc[1]);
+                  acc[1]          = used[u] ? t1 : acc[1];
+                  if constexpr (NCHAIN >= 3)
+                    {
+                      const double t2 = fma(mw[u][e], xv[u][e], acc[2]);
+                      acc[2]          = used[u] ? t2 : acc[2];
+                    }
+                }
+            }
+      }
+  }
+
+  // The chains of row i for column col: on the one matrix pair, or (PER_COL) on member col of the ensemble matrices
+  template <int NCHAIN, bool PER_COL>
+  __device__ __forceinline__ void irk_products(int i, int s, int cap, int NP, const double *__restrict__ a, size_t ld_a,
+                                               const double *__restrict__ m, size_t ld_m, const uint32_t *__restrict__ cols,
+                                               const double *__restrict__ x0, size_t ld0, const double *__restrict__ x1, size_t ld1,
+                                               int col, double (&acc)[3])
+  {
+    if constexpr (PER_COL)
+      {
+        const int p = i / s, d = i - p * s;
+        if (s == 1)
+          irk_row_products_per_col<NCHAIN, 1, LOD_SLOTS>(p, d, cap, NP, a, ld_a, m, ld_m, cols, x0, ld0, x1, ld1, col, acc);
+        else
+          irk_row_products_per_col<NCHAIN, 2, LOD_SLOTS>(p, d, cap, NP, a, ld_a, m, ld_m, cols, x0, ld0, x1, ld1, col, acc);
+      }
+    else
+      irk_row_products<NCHAIN>(i, s, cap, NP, a, m, cols, x0, ld0, x1, ld1, col, acc);
+  }
+
+  // r = tau_1 (b_1 - A u) + tau_2 (b_2 - A u) per (row, column), both planes; b1 NULL: zero load.  PER_COL: column c
+  // reads member c of the ensemble matrix stiffness (ld_a_m).
+  template <bool PER_COL>
   __global__ __launch_bounds__(256) void k_irk_heat_rhs(int nrow, int s, int cap, int NP, int n_rhs, IrkStep k,
-                                                       const double *__restrict__ stiffness, const uint32_t *__restrict__ cols,
-                                                       const double *b1, const double *b2, size_t ld_b, const double *u, size_t ld_u,
-                                                       double *r_re, double *r_im)
+                                                       const double *__restrict__ stiffness, size_t ld_a_m,
+                                                       const uint32_t *__restrict__ cols, const double *b1, const double *b2,
+                                                       size_t ld_b, const double *u, size_t ld_u, double *r_re, double *r_im)
   {
 #pragma clang fp contract(off)
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -86,7 +169,7 @@ namespace
       return;
     const int i = (int)(t / n_rhs), c = (int)(t - (size_t)i * n_rhs);
     double    acc[3];
-    irk_row_products<1>(i, s, cap, NP, stiffness, nullptr, cols, u, ld_u, nullptr, 0, c, acc);
+    irk_products<1, PER_COL>(i, s, cap, NP, stiffness, ld_a_m, nullptr, 0, cols, u, ld_u, nullptr, 0, c, acc);
     const double d1 = (b1 ? b1[(size_t)i * ld_b + c] : 0.0) - acc[0], d2 = (b1 ? b2[(size_t)i * ld_b + c] : 0.0) - acc[0];
     const double p1r = k.t1r * d1, p2r = k.t2r * d2, p1i = k.t1i * d1, p2i = k.t2i * d2;
     r_re[t] = p1r + p2r;
@@ -94,10 +177,12 @@ namespace
   }
 
   // r = tau_1 b_1 + tau_2 b_2 - sigma [A u + (z + damp_stiff) A v + damp_mass M v] per (row, column), both planes;
-  // b1 NULL: zero load.  HAS_MASS_DAMPING unset: no mass chain (damp_mass = 0).
-  template <bool HAS_MASS_DAMPING>
+  // b1 NULL: zero load.  HAS_MASS_DAMPING unset: no mass chain (damp_mass = 0).  PER_COL: column c reads member c of the
+  // ensemble matrices stiffness (ld_a_m) and mass (ld_m_m).
+  template <bool HAS_MASS_DAMPING, bool PER_COL>
   __global__ __launch_bounds__(256) void k_irk_wave_rhs(int nrow, int s, int cap, int NP, int n_rhs, IrkStep k,
-                                                       const double *__restrict__ stiffness, const double *__restrict__ mass,
+                                                       const double *__restrict__ stiffness, size_t ld_a_m,
+                                                       const double *__restrict__ mass, size_t ld_m_m,
                                                        const uint32_t *__restrict__ cols, const double *b1, const double *b2,
                                                        size_t ld_b, const double *u, size_t ld_u, const double *v, size_t ld_v,
                                                        double *r_re, double *r_im)
@@ -108,7 +193,7 @@ namespace
       return;
     const int i = (int)(t / n_rhs), c = (int)(t - (size_t)i * n_rhs);
     double    acc[3];
-    irk_row_products<HAS_MASS_DAMPING ? 3 : 2>(i, s, cap, NP, stiffness, mass, cols, u, ld_u, v, ld_v, c, acc);
+    irk_products<HAS_MASS_DAMPING ? 3 : 2, PER_COL>(i, s, cap, NP, stiffness, ld_a_m, mass, ld_m_m, cols, u, ld_u, v, ld_v, c, acc);
     // p = A u + (z + damp_stiff) A v + damp_mass M v
     const double av_r = k.zdr * acc[1];
     double       pr = acc[0] + av_r;
@@ -200,12 +285,15 @@ namespace
     return k;
   }
 
-  // n_steps of a two-stage scheme on n_rhs columns, heat (order 1: d_v, d_mass, the dampings and the energies are not
-  // used) or wave (order 2); the body of the two calls.  The whole loop is queued and the stream is waited for once.
-  int irk_steps(slod_handle *h, const std::string &who, int order, slod_lod_factor *f, int member, int scheme, const double *d_stiffness,
-                const double *d_mass, const uint32_t *d_cols, double dt, double damp_mass, double damp_stiff, int n_steps, int n_rhs,
-                double *d_u, size_t ld_u, double *d_v, size_t ld_v, const double *d_load, size_t ld_load, size_t load_stage_stride,
-                double *kinetic, double *potential)
+  // n_steps of a two-stage scheme on n columns, heat (order 1: d_v, d_mass, the dampings and the energies are not used)
+  // or wave (order 2); the body of the four calls.  Single: the n = n_rhs columns on the one matrix pair and on factor
+  // member first_member.  per_col: column m on member m of the ensemble matrices (ld_a_m, ld_m_m) and on factor member
+  // first_member + m, which reads column m of the right-hand side whatever first_member.  The whole loop is queued and
+  // the stream is waited for once: three launches a step, five with the energies, for any n.
+  int irk_steps(slod_handle *h, const std::string &who, int order, slod_lod_factor *f, int first_member, int scheme,
+                const double *d_stiffness, size_t ld_a_m, const double *d_mass, size_t ld_m_m, bool per_col, const uint32_t *d_cols,
+                double dt, double damp_mass, double damp_stiff, int n_steps, int n, double *d_u, size_t ld_u, double *d_v, size_t ld_v,
+                const double *d_load, size_t ld_load, size_t load_stage_stride, double *kinetic, double *potential)
   {
     const bool wave = order == 2;
     if (!h)
@@ -219,9 +307,10 @@ namespace
       return slod_fail(h, SLOD_ERR_ARGUMENT, who + ": dt <= 0, NaN or infinite");
     if (!(damp_mass >= 0.0) || !(damp_stiff >= 0.0) || std::isinf(damp_mass) || std::isinf(damp_stiff))
       return slod_fail(h, SLOD_ERR_ARGUMENT, who + ": negative, NaN or infinite damping coefficient");
-    if (n_steps < 1 || n_rhs < 1)
-      return slod_fail(h, SLOD_ERR_ARGUMENT, who + ": n_steps < 1 or n_rhs < 1");
-    if (const int rc = slod_check_ld(h, who.c_str(), "n_rhs", n_rhs, {ld_u, wave ? ld_v : ld_u, d_load ? ld_load : ld_u}))
+    if (n_steps < 1 || n < 1)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, who + (per_col ? ": n_steps < 1 or n_members < 1" : ": n_steps < 1 or n_rhs < 1"));
+    if (const int rc = slod_check_ld_of(h, who.c_str(), per_col, {ld_a_m, wave ? ld_m_m : ld_a_m}, n,
+                                        {ld_u, wave ? ld_v : ld_u, d_load ? ld_load : ld_u}))
       return rc;
     if ((kinetic == nullptr) != (potential == nullptr))
       return slod_fail(h, SLOD_ERR_ARGUMENT, who + ": kinetic and potential come together or not at all");
@@ -231,16 +320,17 @@ namespace
       return slod_fail(h, SLOD_ERR_ARGUMENT, who + ": factor of another handle / row count");
     if (f->kind != SLOD_FACTOR_ZLDL)
       return slod_fail(h, SLOD_ERR_ARGUMENT, who + ": takes a complex factor (slod_lod_factor_create_zldl)");
-    if (member < 0 || member >= f->n_members)
-      return slod_fail(h, SLOD_ERR_ARGUMENT, who + ": member outside the factor");
+    const int n_fm = per_col ? n : 1; // factor members of the call
+    if (first_member < 0 || first_member > f->n_members - n_fm)
+      return slod_fail(h, SLOD_ERR_ARGUMENT, who + (per_col ? ": members outside the factor" : ": member outside the factor"));
     hipStream_t st;
     if (const int rc = slod_enter(h, nullptr, &st))
       return rc;
-    const LodShape w = lod_shape(h, n_rhs);
+    const LodShape w = lod_shape(h, n);
     const IrkStep  k = irk_step(sch, dt, damp_mass, damp_stiff);
     const bool     energies = wave && kinetic != nullptr;
-    const size_t   nvec = (size_t)w.nrow * n_rhs, npart = energies ? (size_t)w.ngroup * n_rhs : 0;
-    const size_t   nenergy = energies ? 2 * (size_t)(n_steps + 1) * n_rhs : 0;
+    const size_t   nvec = (size_t)w.nrow * n, npart = energies ? (size_t)w.ngroup * n : 0;
+    const size_t   nenergy = energies ? 2 * (size_t)(n_steps + 1) * n : 0;
     // one allocation for the whole loop: the two planes of r and of w, and for the energies two arrays of partials and
     // [level][kinetic, potential][column]
     SlodDevBuf<double> work;
@@ -250,9 +340,12 @@ namespace
     double *r_re = work.get(), *r_im = r_re + nvec, *w_re = r_im + nvec, *w_im = w_re + nvec;
     double *part_k = w_im + nvec, *part_p = part_k + npart, *d_energy = part_p + npart;
     const dim3     nblk = lod_flat_grid(nvec);
+    const auto     heat_rhs = per_col ? k_irk_heat_rhs<true> : k_irk_heat_rhs<false>;
+    const auto     wave_rhs = damp_mass != 0.0 ? (per_col ? k_irk_wave_rhs<true, true> : k_irk_wave_rhs<true, false>)
+                                               : (per_col ? k_irk_wave_rhs<false, true> : k_irk_wave_rhs<false, false>);
     auto launch_energies = [&](int level) {
-      slod_lod_energies_launch(h, st, d_stiffness, d_mass, d_cols, n_rhs, d_u, ld_u, d_v, ld_v, part_k, part_p,
-                               d_energy + 2 * (size_t)level * n_rhs);
+      slod_lod_energies_launch(h, st, d_stiffness, d_mass, d_cols, n, d_u, ld_u, d_v, ld_v, part_k, part_p,
+                               d_energy + 2 * (size_t)level * n, per_col, ld_a_m, ld_m_m);
     };
     if (energies)
       launch_energies(0);
@@ -262,19 +355,20 @@ namespace
         const double *b1 = d_load ? d_load + (size_t)(2 * step) * load_stage_stride : nullptr;
         const double *b2 = d_load ? d_load + ((size_t)(2 * step) + 1) * load_stage_stride : nullptr;
         if (!wave)
-          hipLaunchKernelGGL(k_irk_heat_rhs, nblk, dim3(256), 0, st, w.nrow, w.s, w.cap, w.NP, n_rhs, k, d_stiffness, d_cols, b1, b2,
+          hipLaunchKernelGGL(heat_rhs, nblk, dim3(256), 0, st, w.nrow, w.s, w.cap, w.NP, n, k, d_stiffness, ld_a_m, d_cols, b1, b2,
                              ld_load, d_u, ld_u, r_re, r_im);
-        else if (damp_mass != 0.0)
-          hipLaunchKernelGGL(k_irk_wave_rhs<true>, nblk, dim3(256), 0, st, w.nrow, w.s, w.cap, w.NP, n_rhs, k, d_stiffness, d_mass,
-                             d_cols, b1, b2, ld_load, d_u, ld_u, d_v, ld_v, r_re, r_im);
         else
-          hipLaunchKernelGGL(k_irk_wave_rhs<false>, nblk, dim3(256), 0, st, w.nrow, w.s, w.cap, w.NP, n_rhs, k, d_stiffness, d_mass,
+          hipLaunchKernelGGL(wave_rhs, nblk, dim3(256), 0, st, w.nrow, w.s, w.cap, w.NP, n, k, d_stiffness, ld_a_m, d_mass, ld_m_m,
                              d_cols, b1, b2, ld_load, d_u, ld_u, d_v, ld_v, r_re, r_im);
-        slod_lod_zfactor_solve_launch(f, st, member, 1, r_re, r_im, (size_t)n_rhs, n_rhs, 0, 1, w_re, w_im, (size_t)n_rhs);
+        // single: the n columns on the one member; per_col: member first_member + m on column m of r, one column each
+        if (per_col)
+          slod_lod_zfactor_solve_launch(f, st, first_member, n, r_re, r_im, (size_t)n, 1, 0, n, w_re, w_im, (size_t)n);
+        else
+          slod_lod_zfactor_solve_launch(f, st, first_member, 1, r_re, r_im, (size_t)n, n, 0, 1, w_re, w_im, (size_t)n);
         if (!wave)
-          hipLaunchKernelGGL(k_irk_advance<1>, nblk, dim3(256), 0, st, w.nrow, n_rhs, k, w_re, w_im, d_u, ld_u, nullptr, 0);
+          hipLaunchKernelGGL(k_irk_advance<1>, nblk, dim3(256), 0, st, w.nrow, n, k, w_re, w_im, d_u, ld_u, nullptr, 0);
         else
-          hipLaunchKernelGGL(k_irk_advance<2>, nblk, dim3(256), 0, st, w.nrow, n_rhs, k, w_re, w_im, d_u, ld_u, d_v, ld_v);
+          hipLaunchKernelGGL(k_irk_advance<2>, nblk, dim3(256), 0, st, w.nrow, n, k, w_re, w_im, d_u, ld_u, d_v, ld_v);
         if (energies)
           launch_energies(step + 1);
         e = hipGetLastError();
@@ -290,10 +384,10 @@ namespace
       return slod_hip_fail(h, e, who.c_str());
     if (energies)
       for (size_t l = 0; l <= (size_t)n_steps; ++l)
-        for (size_t c = 0; c < (size_t)n_rhs; ++c)
+        for (size_t c = 0; c < (size_t)n; ++c)
           {
-            kinetic[l * n_rhs + c]   = host[2 * l * n_rhs + c];
-            potential[l * n_rhs + c] = host[(2 * l + 1) * n_rhs + c];
+            kinetic[l * n + c]   = host[2 * l * n + c];
+            potential[l * n + c] = host[(2 * l + 1) * n + c];
           }
     return SLOD_OK;
   }
@@ -332,8 +426,8 @@ int slod_lod_irk_heat_steps_direct(slod_handle *h, slod_lod_factor *f_S, int mem
                                    const uint32_t *d_cols, double dt, int n_steps, int n_rhs, double *d_u, size_t ld_u,
                                    const double *d_load, size_t ld_load, size_t load_stage_stride)
 {
-  return irk_steps(h, "slod_lod_irk_heat_steps_direct", 1, f_S, member, scheme, d_stiffness, nullptr, d_cols, dt, 0.0, 0.0, n_steps, n_rhs,
-                   d_u, ld_u, nullptr, 0, d_load, ld_load, load_stage_stride, nullptr, nullptr);
+  return irk_steps(h, "slod_lod_irk_heat_steps_direct", 1, f_S, member, scheme, d_stiffness, 1, nullptr, 1, false, d_cols, dt, 0.0, 0.0,
+                   n_steps, n_rhs, d_u, ld_u, nullptr, 0, d_load, ld_load, load_stage_stride, nullptr, nullptr);
 }
 
 int slod_lod_irk_wave_steps_direct(slod_handle *h, slod_lod_factor *f_S, int member, int scheme, const double *d_stiffness,
@@ -341,8 +435,30 @@ int slod_lod_irk_wave_steps_direct(slod_handle *h, slod_lod_factor *f_S, int mem
                                    int n_steps, int n_rhs, double *d_u, size_t ld_u, double *d_v, size_t ld_v, const double *d_load,
                                    size_t ld_load, size_t load_stage_stride, double *kinetic, double *potential)
 {
-  return irk_steps(h, "slod_lod_irk_wave_steps_direct", 2, f_S, member, scheme, d_stiffness, d_mass, d_cols, dt, damp_mass, damp_stiff,
-                   n_steps, n_rhs, d_u, ld_u, d_v, ld_v, d_load, ld_load, load_stage_stride, kinetic, potential);
+  return irk_steps(h, "slod_lod_irk_wave_steps_direct", 2, f_S, member, scheme, d_stiffness, 1, d_mass, 1, false, d_cols, dt, damp_mass,
+                   damp_stiff, n_steps, n_rhs, d_u, ld_u, d_v, ld_v, d_load, ld_load, load_stage_stride, kinetic, potential);
+}
+
+// slod_lod_irk_heat_steps_direct with a matrix, a factor member and a column per ensemble member
+int slod_lod_irk_heat_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, int first_member, int scheme,
+                                            const double *d_stiffness, size_t ld_a_m, const uint32_t *d_cols, double dt, int n_steps,
+                                            int n_members, double *d_u, size_t ld_u, const double *d_load, size_t ld_load,
+                                            size_t load_stage_stride)
+{
+  return irk_steps(h, "slod_lod_irk_heat_steps_ensemble_direct", 1, f_S, first_member, scheme, d_stiffness, ld_a_m, nullptr, ld_a_m, true,
+                   d_cols, dt, 0.0, 0.0, n_steps, n_members, d_u, ld_u, nullptr, 0, d_load, ld_load, load_stage_stride, nullptr, nullptr);
+}
+
+// slod_lod_irk_wave_steps_direct with a matrix pair, a factor member and a column per ensemble member
+int slod_lod_irk_wave_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, int first_member, int scheme,
+                                            const double *d_stiffness, size_t ld_a_m, const double *d_mass, size_t ld_m_m,
+                                            const uint32_t *d_cols, double dt, double damp_mass, double damp_stiff, int n_steps,
+                                            int n_members, double *d_u, size_t ld_u, double *d_v, size_t ld_v, const double *d_load,
+                                            size_t ld_load, size_t load_stage_stride, double *kinetic, double *potential)
+{
+  return irk_steps(h, "slod_lod_irk_wave_steps_ensemble_direct", 2, f_S, first_member, scheme, d_stiffness, ld_a_m, d_mass, ld_m_m, true,
+                   d_cols, dt, damp_mass, damp_stiff, n_steps, n_members, d_u, ld_u, d_v, ld_v, d_load, ld_load, load_stage_stride,
+                   kinetic, potential);
 }
 
 } // extern "C"

@@ -358,12 +358,13 @@ namespace
 } // namespace
 
 // k_lod_inner on the two forms of the energies, then k_lod_inner_sum, for the other time loops of the library
-// (slod_lod_irk.hip): the launches and the bits of the energies of nm_steps on one matrix pair
+// (slod_lod_irk.hip): the launches and the bits of the energies of nm_steps on one matrix pair, or (per_col) on the
+// ensemble matrices with a member per column
 void slod_lod_energies_launch(const slod_handle *h, hipStream_t st, const double *d_stiffness, const double *d_mass,
                               const uint32_t *d_cols, int n_rhs, const double *d_u, size_t ld_u, const double *d_v, size_t ld_v,
-                              double *d_part_k, double *d_part_p, double *d_out)
+                              double *d_part_k, double *d_part_p, double *d_out, bool per_col, size_t ld_a_m, size_t ld_m_m)
 {
-  const SlodLodOperator A{d_stiffness}, M{d_mass};
+  const SlodLodOperator A{d_stiffness, per_col ? ld_a_m : 1, per_col}, M{d_mass, per_col ? ld_m_m : 1, per_col};
   launch_inner(lod_shape(h, n_rhs), st, M, d_cols, n_rhs, 2, inner_job(M, d_v, ld_v, d_v, ld_v, d_part_k),
                inner_job(A, d_u, ld_u, d_u, ld_u, d_part_p), 0.5, d_out);
 }

@@ -652,6 +652,50 @@ namespace slod
   }
 
   template <int dim, int spacedim>
+  void LOD<dim, spacedim>::ensemble_elliptic_solutions(double *d_ell_fine)
+  {
+    const int          K = (int)par.n_members;
+    const unsigned int n_patches = (unsigned int)patches.size();
+    const std::size_t  NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+    const std::size_t  fine_size = (NE + 1) * (NE + 1) * spacedim, n_coarse = (std::size_t)n_patches * spacedim;
+    const int          cap = slod_lod_row_capacity(handle);
+    check(cap, "slod_lod_row_capacity");
+    const std::size_t n_words = (std::size_t)n_patches * cap * spacedim * spacedim;
+    double           *d_ell = device_alloc<double>(n_coarse * K);
+    double *d_one = device_alloc<double>(n_words + 2 * n_coarse); // one member's matrix, load and elliptic solution
+    // the elliptic solution of member k as solve() finds it: slod_lod_solve on the de-interleaved matrix and load
+    // (the copies go through the host: this is the driver's reference, not the loop)
+    std::vector<double> all_values(n_words * K), all_rhs(n_coarse * K), all_ell(n_coarse * K), one(n_words + n_coarse), u1(n_coarse);
+    double             *d_rhs1 = d_one + n_words, *d_u1 = d_rhs1 + n_coarse;
+    if (hipMemcpy(all_values.data(), d_ens_values, all_values.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(all_rhs.data(), d_ens_rhs, all_rhs.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      throw std::runtime_error("ensemble_elliptic_solutions: downloading the ensemble matrix failed");
+    for (int k = 0; k < K; ++k)
+      {
+        for (std::size_t i = 0; i < n_words; ++i)
+          one[i] = all_values[i * K + k];
+        for (std::size_t i = 0; i < n_coarse; ++i)
+          one[n_words + i] = all_rhs[i * K + k];
+        if (hipMemcpy(d_one, one.data(), one.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+          throw std::runtime_error("ensemble_elliptic_solutions: uploading a member failed");
+        check(slod_lod_solve(handle, d_one, d_ens_cols, d_rhs1, d_u1, lod_rel_tol, lod_max_iterations, nullptr), "slod_lod_solve");
+        if (hipMemcpy(u1.data(), d_u1, n_coarse * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+          throw std::runtime_error("ensemble_elliptic_solutions: downloading a solution failed");
+        for (std::size_t i = 0; i < n_coarse; ++i)
+          all_ell[i * K + k] = u1[i];
+      }
+    if (hipMemcpy(d_ell, all_ell.data(), all_ell.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+      throw std::runtime_error("ensemble_elliptic_solutions: uploading the elliptic solutions failed");
+    check(slod_lod_reconstruct_ensemble(handle, d_ens_basis, ens_stride, ens_member_stride, K, d_ell, (std::size_t)K, d_ell_fine,
+                                        fine_size, nullptr),
+          "slod_lod_reconstruct_ensemble");
+    ens_lod_norms.assign(K, slod_error_norms{});
+    for (int k = 0; k < K; ++k)
+      check(slod_compute_error_norms(handle, (uint32_t)k, d_ell_fine + k * fine_size, nullptr, nullptr, nullptr, &ens_lod_norms[k], nullptr),
+            "slod_compute_error_norms");
+  }
+
+  template <int dim, int spacedim>
   void LOD<dim, spacedim>::solve_heat_ensemble(const unsigned int n_steps, const double dt, const double theta)
   {
     if (!d_ens_mass)
@@ -665,40 +709,10 @@ namespace slod
     const std::size_t n_words = (std::size_t)n_patches * cap * spacedim * spacedim;
     if (!d_ens_shifted)
       d_ens_shifted = device_alloc<double>(n_words * K);
-    double *d_u = device_alloc<double>(n_coarse * K), *d_ell = device_alloc<double>(n_coarse * K);
+    double *d_u = device_alloc<double>(n_coarse * K);
     double *d_fine = device_alloc<double>(fine_size * K), *d_ell_fine = device_alloc<double>(fine_size * K);
     double *d_mean = device_alloc<double>(fine_size), *d_var = device_alloc<double>(fine_size);
-    double *d_one = device_alloc<double>(n_words + 2 * n_coarse); // one member's matrix, load and elliptic solution
-    // the elliptic solution of member k as solve() finds it: slod_lod_solve on the de-interleaved matrix and load
-    // (the copies go through the host: this is the driver's reference, not the loop)
-    std::vector<double> all_values(n_words * K), all_rhs(n_coarse * K), all_ell(n_coarse * K), one(n_words + n_coarse), u1(n_coarse);
-    double             *d_rhs1 = d_one + n_words, *d_u1 = d_rhs1 + n_coarse;
-    if (hipMemcpy(all_values.data(), d_ens_values, all_values.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(all_rhs.data(), d_ens_rhs, all_rhs.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-      throw std::runtime_error("solve_heat_ensemble: downloading the ensemble matrix failed");
-    for (int k = 0; k < K; ++k)
-      {
-        for (std::size_t i = 0; i < n_words; ++i)
-          one[i] = all_values[i * K + k];
-        for (std::size_t i = 0; i < n_coarse; ++i)
-          one[n_words + i] = all_rhs[i * K + k];
-        if (hipMemcpy(d_one, one.data(), one.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-          throw std::runtime_error("solve_heat_ensemble: uploading a member failed");
-        check(slod_lod_solve(handle, d_one, d_ens_cols, d_rhs1, d_u1, lod_rel_tol, lod_max_iterations, nullptr), "slod_lod_solve");
-        if (hipMemcpy(u1.data(), d_u1, n_coarse * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-          throw std::runtime_error("solve_heat_ensemble: downloading a solution failed");
-        for (std::size_t i = 0; i < n_coarse; ++i)
-          all_ell[i * K + k] = u1[i];
-      }
-    if (hipMemcpy(d_ell, all_ell.data(), all_ell.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-      throw std::runtime_error("solve_heat_ensemble: uploading the elliptic solutions failed");
-    check(slod_lod_reconstruct_ensemble(handle, d_ens_basis, ens_stride, ens_member_stride, K, d_ell, (std::size_t)K, d_ell_fine,
-                                        fine_size, nullptr),
-          "slod_lod_reconstruct_ensemble");
-    ens_lod_norms.assign(K, slod_error_norms{});
-    for (int k = 0; k < K; ++k)
-      check(slod_compute_error_norms(handle, (uint32_t)k, d_ell_fine + k * fine_size, nullptr, nullptr, nullptr, &ens_lod_norms[k], nullptr),
-            "slod_compute_error_norms");
+    ensemble_elliptic_solutions(d_ell_fine);
     // S_k = M_k + theta dt A_k, one factor object, the loop
     check(slod_lod_matrix_combine_ensemble(handle, 1.0, d_ens_mass, (std::size_t)K, theta * dt, d_ens_values, (std::size_t)K, K,
                                            d_ens_shifted, (std::size_t)K, nullptr),
@@ -1344,6 +1358,110 @@ namespace slod
     check(slod_lod_reconstruct(handle, d_basis, basis_stride, d_u, d_wave_fine, nullptr), "slod_lod_reconstruct");
     check(slod_compute_error_norms(handle, 0, d_wave_fine, nullptr, nullptr, nullptr, &wave_norms, nullptr),
           "slod_compute_error_norms");
+  }
+
+  template <int dim, int spacedim>
+  slod_lod_factor *LOD<dim, spacedim>::factor_lod_irk_ensemble(const int scheme, const int order, const double dt)
+  {
+    const int         K = (int)par.n_members;
+    const std::size_t ld = (std::size_t)K;
+    const int         cap = slod_lod_row_capacity(handle);
+    check(cap, "slod_lod_row_capacity");
+    if (!d_ens_sym)
+      d_ens_sym = device_alloc<double>((std::size_t)patches.size() * cap * spacedim * spacedim * K);
+    check(slod_lod_matrix_symmetrize_ensemble(handle, d_ens_values, ld, d_ens_cols, K, d_ens_sym, ld, nullptr),
+          "slod_lod_matrix_symmetrize_ensemble");
+    double alpha[2], beta[2];
+    if (slod_lod_irk_coefficients(scheme, order, dt, 0.0, 0.0, alpha, beta) != SLOD_OK)
+      throw std::runtime_error(std::string("slod_lod_irk_coefficients: ") + slod_last_error(nullptr));
+    slod_lod_factor *f = nullptr;
+    check(slod_lod_factor_create_zldl_ensemble(handle, d_ens_sym, ld, d_ens_mass, ld, K, d_ens_cols, alpha, beta, 1, nullptr, &f),
+          "slod_lod_factor_create_zldl_ensemble");
+    factors.push_back(f);
+    check(slod_lod_factor_get_info_member(f, 0, &lod_factor_info), "slod_lod_factor_get_info_member");
+    check(slod_lod_factor_inertia(f, 0, &lod_factor_inertia), "slod_lod_factor_inertia");
+    return f;
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_heat_irk_ensemble(const int scheme, const unsigned int n_steps, const double dt)
+  {
+    if (!d_ens_mass)
+      throw std::runtime_error("solve_heat_irk_ensemble: assemble_mass_matrix_ensemble comes first");
+    const int          K = (int)par.n_members;
+    const std::size_t  ld = (std::size_t)K;
+    const unsigned int n_patches = (unsigned int)patches.size();
+    const std::size_t  NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+    const std::size_t  fine_size = (NE + 1) * (NE + 1) * spacedim, n_coarse = (std::size_t)n_patches * spacedim;
+    double *d_u = device_alloc<double>(n_coarse * K);
+    double *d_fine = device_alloc<double>(fine_size * K), *d_ell_fine = device_alloc<double>(fine_size * K);
+    double *d_mean = device_alloc<double>(fine_size), *d_var = device_alloc<double>(fine_size);
+    ensemble_elliptic_solutions(d_ell_fine);
+    slod_lod_factor *f = factor_lod_irk_ensemble(scheme, 1, dt);
+    if (hipMemset(d_u, 0, n_coarse * K * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+      throw std::runtime_error("solve_heat_irk_ensemble: clearing the initial state failed");
+    ens_heat_error.assign((std::size_t)n_steps * K, slod_error_norms{});
+    for (unsigned int step = 0; step < n_steps; ++step)
+      {
+        check(slod_lod_irk_heat_steps_ensemble_direct(handle, f, 0, scheme, d_ens_sym, ld, d_ens_cols, dt, 1, K, d_u, ld, d_ens_rhs, ld, 0),
+              "slod_lod_irk_heat_steps_ensemble_direct");
+        check(slod_lod_reconstruct_ensemble(handle, d_ens_basis, ens_stride, ens_member_stride, K, d_u, ld, d_fine, fine_size, nullptr),
+              "slod_lod_reconstruct_ensemble");
+        for (int k = 0; k < K; ++k)
+          check(slod_compute_error_norms(handle, (uint32_t)k, d_ell_fine + k * fine_size, d_fine + k * fine_size, nullptr, nullptr,
+                                         &ens_heat_error[(std::size_t)step * K + k], nullptr),
+                "slod_compute_error_norms");
+      }
+    ensemble_moment_norms(d_fine, d_mean, d_var, ens_heat_mean_norms, ens_heat_dev_norms);
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::solve_wave_irk_ensemble(const int scheme, const unsigned int n_steps, const double dt)
+  {
+    if (!d_ens_mass)
+      throw std::runtime_error("solve_wave_irk_ensemble: assemble_mass_matrix_ensemble comes first");
+    const int          K = (int)par.n_members;
+    const std::size_t  ld = (std::size_t)K;
+    const unsigned int n_patches = (unsigned int)patches.size();
+    const std::size_t  NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+    const std::size_t  fine_size = (NE + 1) * (NE + 1) * spacedim, n_coarse = (std::size_t)n_patches * spacedim;
+    double *d_state = device_alloc<double>(2 * n_coarse * K), *d_u = d_state, *d_v = d_u + n_coarse * K;
+    double *d_fine = device_alloc<double>(fine_size * K), *d_mean = device_alloc<double>(fine_size), *d_var = device_alloc<double>(fine_size);
+    slod_lod_factor *f = factor_lod_irk_ensemble(scheme, 2, dt);
+    if (hipMemset(d_state, 0, 2 * n_coarse * K * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+      throw std::runtime_error("solve_wave_irk_ensemble: clearing the initial state failed");
+    std::vector<double> b(n_coarse * K), u(n_coarse * K);
+    if (hipMemcpy(b.data(), d_ens_rhs, b.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      throw std::runtime_error("solve_wave_irk_ensemble: download of the loads failed");
+    ens_wave_kinetic.assign((std::size_t)(n_steps + 1) * K, 0.0);
+    ens_wave_potential.assign((std::size_t)(n_steps + 1) * K, 0.0);
+    ens_wave_work.assign((std::size_t)(n_steps + 1) * K, 0.0);
+    std::vector<double> kinetic(2 * ld), potential(2 * ld);
+    for (unsigned int step = 0; step < n_steps; ++step)
+      {
+        check(slod_lod_irk_wave_steps_ensemble_direct(handle, f, 0, scheme, d_ens_sym, ld, d_ens_mass, ld, d_ens_cols, dt, 0.0, 0.0, 1, K,
+                                                      d_u, ld, d_v, ld, d_ens_rhs, ld, 0, kinetic.data(), potential.data()),
+              "slod_lod_irk_wave_steps_ensemble_direct");
+        if (hipMemcpy(u.data(), d_u, u.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+          throw std::runtime_error("solve_wave_irk_ensemble: download of the states failed");
+        for (int k = 0; k < K; ++k)
+          {
+            if (step == 0)
+              {
+                ens_wave_kinetic[k]   = kinetic[k];
+                ens_wave_potential[k] = potential[k];
+              }
+            ens_wave_kinetic[(std::size_t)(step + 1) * K + k]   = kinetic[ld + k];
+            ens_wave_potential[(std::size_t)(step + 1) * K + k] = potential[ld + k];
+            double work = 0.0;
+            for (std::size_t i = 0; i < n_coarse; ++i)
+              work += u[i * K + k] * b[i * K + k];
+            ens_wave_work[(std::size_t)(step + 1) * K + k] = work;
+          }
+      }
+    check(slod_lod_reconstruct_ensemble(handle, d_ens_basis, ens_stride, ens_member_stride, K, d_u, ld, d_fine, fine_size, nullptr),
+          "slod_lod_reconstruct_ensemble");
+    ensemble_moment_norms(d_fine, d_mean, d_var, ens_wave_mean_norms, ens_wave_dev_norms);
   }
 
   // LOD.cc:1103-1237 with f = 1.  The reference solves with SolverDirect; the CG of the fine problem runs on the

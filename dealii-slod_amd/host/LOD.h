@@ -250,6 +250,17 @@ namespace slod
     // coefficient.  Then the final states on the fine grid and their moments as in solve_ensemble().
     // last_factor_info() is that of S, the range over all members.
     void solve_wave_ensemble(const unsigned int n_steps, const double dt, const double beta, const double gamma);
+    // solve_heat_irk / solve_wave_irk for all members at once, after assemble_mass_matrix_ensemble(): the symmetrised
+    // stiffness of every member (slod_lod_matrix_symmetrize_ensemble), the pair of slod_lod_irk_coefficients, one complex
+    // factor object with a member per realisation (slod_lod_factor_create_zldl_ensemble with one coefficient pair;
+    // last_factor_info() and last_factor_inertia() are those of member 0), then n_steps calls of
+    // slod_lod_irk_heat_steps_ensemble_direct / slod_lod_irk_wave_steps_ensemble_direct with one step each (the calls
+    // compose bit for bit), from u = 0 (from rest, undamped) with the load of solve_ensemble().  The results are read as
+    // those of solve_heat_ensemble (error_heat_ensemble(), norms_heat_ensemble_*) and solve_wave_ensemble
+    // (wave_ensemble_*, norms_wave_ensemble_*): member k's numbers are those of solve_heat_irk / solve_wave_irk of a
+    // problem with member k's coefficient.
+    void solve_heat_irk_ensemble(const int scheme, const unsigned int n_steps, const double dt);
+    void solve_wave_irk_ensemble(const int scheme, const unsigned int n_steps, const double dt);
     // solve_harmonic for all members at once, after assemble_mass_matrix_ensemble(): the symmetrised stiffness of every
     // member (slod_lod_matrix_symmetrize_ensemble), the loads of solve_ensemble() (slod_lod_rhs_ensemble, f = 1) and one
     // slod_lod_harmonic_response_ensemble call for all (frequency, member) pairs.  Entry [frequency * n_members + member] of
@@ -418,6 +429,11 @@ namespace slod
     void eigenproblem_ensemble(const unsigned int n_eig, const double sigma, const bool near, const bool ldl);
     // mean and standard deviation of n_members fine fields: slod_ensemble_moments, the square root on the host, the norms
     void ensemble_moment_norms(const double *d_fine, double *d_mean, double *d_var, slod_error_norms &mean, slod_error_norms &dev);
+    // the members' elliptic solutions on the fine grid, [member][fine_size], and their norms (ens_lod_norms): the
+    // reference of the ensemble heat loops
+    void ensemble_elliptic_solutions(double *d_ell_fine);
+    // sym(A_k) of every member into d_ens_sym and the complex factor of the scheme's step matrices, a member per realisation
+    slod_lod_factor *factor_lod_irk_ensemble(const int scheme, const int order, const double dt);
 
     void check(const int status, const char *what) const;
     std::vector<Point<dim>> fine_quadrature_points() const;

@@ -214,6 +214,11 @@ def load():
     lib.slod_lod_irk_wave_steps_direct.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_double, C.c_double, C.c_double,
                                                    C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t,
                                                    dp, dp]
+    lib.slod_lod_irk_heat_steps_ensemble_direct.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_double, C.c_int,
+                                                            C.c_int, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t]
+    lib.slod_lod_irk_wave_steps_ensemble_direct.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp,
+                                                            C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.c_size_t,
+                                                            vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, dp, dp]
     lib.slod_update_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, C.c_int, C.c_size_t, C.c_int, vp]
     lib.slod_dirty_patches.argtypes = [vp, vp, u32p, C.c_size_t]
     lib.slod_plan_create_dirty.argtypes = [vp, C.c_uint32, vp, C.POINTER(vp)]
@@ -882,6 +887,32 @@ class Slod:
             n_steps, n_rhs, d_u, n_rhs if ld_u is None else ld_u, d_v, n_rhs if ld_v is None else ld_v, d_load,
             n_rhs if ld_load is None else ld_load, load_stage_stride, _dp(kin) if energies else None,
             _dp(pot) if energies else None))
+        return kin, pot
+
+    def lod_irk_heat_steps_ensemble(self, factor, scheme, d_stiffness, d_cols, dt, n_steps, n_members, d_u, first_member=0,
+                                    ld_a_m=None, ld_u=None, d_load=None, ld_load=None, load_stage_stride=0):
+        """lod_irk_heat_steps with a matrix, a factor member and a column per ensemble member: column m of d_u is advanced
+        on factor member first_member + m with member m of the ensemble matrix d_stiffness.  Stage i of step k, member m,
+        row r reads the load at d_load[(2 k + i) * load_stage_stride + r * ld_load + m]."""
+        K = n_members
+        self._check(self.lib.slod_lod_irk_heat_steps_ensemble_direct(
+            self.h, _factor_ptr(factor), first_member, _irk_scheme(scheme), d_stiffness, K if ld_a_m is None else ld_a_m,
+            d_cols, dt, n_steps, K, d_u, K if ld_u is None else ld_u, d_load, K if ld_load is None else ld_load,
+            load_stage_stride))
+
+    def lod_irk_wave_steps_ensemble(self, factor, scheme, d_stiffness, d_mass, d_cols, dt, n_steps, n_members, d_u, d_v,
+                                    first_member=0, ld_a_m=None, ld_m_m=None, ld_u=None, ld_v=None, d_load=None, ld_load=None,
+                                    load_stage_stride=0, damp_mass=0.0, damp_stiff=0.0, energies=True):
+        """lod_irk_wave_steps with a matrix pair, a factor member and a column per ensemble member.  Returns
+        (kinetic, potential) as arrays [n_steps + 1, n_members], or (None, None) with energies=False."""
+        K = n_members
+        shape = (max(n_steps, 0) + 1, max(K, 1))
+        kin, pot = (np.zeros(shape), np.zeros(shape)) if energies else (None, None)
+        self._check(self.lib.slod_lod_irk_wave_steps_ensemble_direct(
+            self.h, _factor_ptr(factor), first_member, _irk_scheme(scheme), d_stiffness, K if ld_a_m is None else ld_a_m,
+            d_mass, K if ld_m_m is None else ld_m_m, d_cols, dt, damp_mass, damp_stiff, n_steps, K, d_u,
+            K if ld_u is None else ld_u, d_v, K if ld_v is None else ld_v, d_load, K if ld_load is None else ld_load,
+            load_stage_stride, _dp(kin) if energies else None, _dp(pot) if energies else None))
         return kin, pot
 
     # ---- the LOD systems of a coefficient ensemble: member k = problem k of the handle = column k of the coarse

@@ -1038,7 +1038,8 @@ int slod_lod_harmonic_response_ensemble(slod_handle *h, const double *d_stiffnes
  *   "<call>: takes a complex factor (slod_lod_factor_create_zldl)";
  * a member outside the factor.  The real consumers go on refusing complex factors as above.
  * Not built: three-stage schemes (Radau IIA of order 5 and Gauss of order 6 need one real and one complex member),
- * ensemble forms, CG or PCG as the stage solver, step-size control, dense output, the deal.II adapter. */
+ * CG or PCG as the stage solver, step-size control, dense output, the deal.II adapter.  (The ensemble forms are
+ * slod_lod_irk_*_steps_ensemble_direct, below.) */
 enum slod_irk_scheme { SLOD_IRK_GAUSS2 = 0, SLOD_IRK_RADAU2A = 1 };
 int slod_lod_irk_coefficients(int scheme, int order /* 1 heat, 2 wave */, double dt, double damp_mass, double damp_stiff,
                               double alpha[2], double beta[2]);
@@ -1051,6 +1052,47 @@ int slod_lod_irk_wave_steps_direct(slod_handle *h, slod_lod_factor *f_S, int mem
                                    const double *d_load /* NULL = 0 */, size_t ld_load, size_t load_stage_stride,
                                    double *kinetic   /* HOST [(n_steps+1)*n_rhs], may be NULL */,
                                    double *potential /* HOST [(n_steps+1)*n_rhs], may be NULL */);
+
+/* ---- implicit Runge-Kutta time stepping for a coefficient ensemble: K members per call ----------------
+ * The two steppers above with a matrix, a factor member and a column per member of a coefficient ensemble on one pattern
+ * (the ensemble matrix layout: entry e of member m at values[e ld + m]).  The use is an uncertainty band on a transient
+ * at fourth order: the serial walk of the band, which is the cost of a step, is shared by the K members of one launch.
+ * LAYOUT, member = column as in slod_lod_newmark_steps_ensemble_direct: column m of d_u (and d_v) is member m's state; it
+ * is advanced on factor member first_member + m with member m of d_stiffness (ld_a_m) and d_mass (ld_m_m).  For a factor
+ * of slod_lod_factor_create_zldl_ensemble with n_coef pairs of slod_lod_irk_coefficients, first_member = k K picks dt_k,
+ * so several dt x K members sit in one object; first_member need not be a multiple of n_members (a member sub-range is
+ * first_member = k K + m0 with every pointer offset by m0 members), and factor member first_member + m always reads
+ * column m of the right-hand side.
+ * LOADS: stage i (0, 1) of step k, member m, row r at d_load[(2 k + i) load_stage_stride + r ld_load + m]; stride 0 is
+ * one constant load, d_load NULL the zero load.  kinetic, potential: HOST [(n_steps + 1) n_members], per member
+ * 1/2 v_m^T M_m v_m and 1/2 u_m^T A_m u_m with the sums of slod_lod_newmark_steps_ensemble_direct, row 0 the entry state.
+ * A step is three launches, five with the energies, for any number of members: the right-hand side (the chains of the
+ * single call on member m's words, the loads of 8 slots issued ahead of the first fma, every word of A read once for
+ * A u and A v and the words of M in the same batch), the complex sweeps with a member per blockIdx.y, the update.  One
+ * allocation per call, the loop queued whole on the handle's stream and waited for once, nothing read back per step.
+ * THE BITS: column m's u, v, kinetic and potential are, as 64-bit words, those of slod_lod_irk_{heat,wave}_steps_direct
+ * with n_rhs = 1 on member m's de-interleaved matrices and a one-member slod_lod_factor_create_zldl of the same
+ * (alpha, beta); they do not depend on K, a leading dimension, the member's position, first_member or the run; one call
+ * with n_steps = 2 equals two calls with n_steps = 1.  Padding entries >= n_members inside any ld are neither read nor
+ * written.
+ * SLOD_ERR_ARGUMENT, before any device work, with the call's name: everything the single calls refuse, with their
+ * messages (n_members in the place of n_rhs); n_members < 1; ld_a_m, ld_m_m, ld_u, ld_v or ld_load below n_members;
+ * first_member < 0 or first_member + n_members beyond the factor's members, "<call>: members outside the factor"; a real
+ * factor, "<call>: takes a complex factor (slod_lod_factor_create_zldl)".  The single calls go on taking `member` of a
+ * factor of several members; the real consumers go on refusing it.
+ * Not built: several columns per member, three-stage schemes, CG or PCG as the stage solver, members spread over ranks,
+ * the deal.II adapter. */
+int slod_lod_irk_heat_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, int first_member, int scheme,
+                                            const double *d_stiffness, size_t ld_a_m, const uint32_t *d_cols, double dt,
+                                            int n_steps, int n_members, double *d_u, size_t ld_u,
+                                            const double *d_load /* NULL = 0 */, size_t ld_load, size_t load_stage_stride);
+int slod_lod_irk_wave_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, int first_member, int scheme,
+                                            const double *d_stiffness, size_t ld_a_m, const double *d_mass, size_t ld_m_m,
+                                            const uint32_t *d_cols, double dt, double damp_mass, double damp_stiff,
+                                            int n_steps, int n_members, double *d_u, size_t ld_u, double *d_v, size_t ld_v,
+                                            const double *d_load /* NULL = 0 */, size_t ld_load, size_t load_stage_stride,
+                                            double *kinetic   /* HOST [(n_steps+1)*n_members], may be NULL */,
+                                            double *potential /* HOST [(n_steps+1)*n_members], may be NULL */);
 
 /* ---- refresh after a local coefficient change ----------------------------------------------
  * Every entry point above takes the coefficient as fixed for the life of a basis (the reference does too: one
