@@ -3,6 +3,7 @@
 //                  [--heat STEPS DT] [--eigs K] [--shift SIGMA] [--wave STEPS DT] [--direct] [--irk gauss|radau] [--ensemble K] [--perturb K]
 //                  [--reuse-factor] [--precond-member J]
 //                  [--member K] [--ldl] [--harmonic K W0 W1 [--damping DM DS]] (with --ensemble: per member)
+//                  [--receiver X Y [C]]... [--record-every M]
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
 // file name it dumps, per patch, phi and psi in patch-lexicographic order (parity tests).
 // --compare (anywhere on the command line): after run(), the rest of the reference run() -- global
@@ -50,6 +51,15 @@
 // step matrix (slod_lod_irk_coefficients, slod_lod_factor_create_zldl, slod_lod_irk_heat_steps_direct /
 // slod_lod_irk_wave_steps_direct; A_LOD symmetrised for both): the lines of --direct, the factor line with the range of |D|,
 // and behind it "factor: complex LDL^T of the SCHEME step, growth = ..".
+// --receiver X Y [C] (repeatable), --record-every M: with any flavour of --heat / --wave (CG, --direct, --irk, each with
+// --ensemble K or --member K) component C (default 0) of the solution at the point (X, Y) of the unit square is recorded
+// inside the time loop (LOD::create_receivers, LOD::record_next): after the loop one line per record, receiver and member,
+// "heat|wave receiver Q member K record J: t = .., u = ..[, v = ..]", record J the state after J * M steps, record 0 the
+// entry state.  With --ensemble K the ensemble loop records and the lines of member K are those of a --member K run.
+// The argument after "--receiver X Y" is taken as C whenever it is a plain non-negative integer, so the positional
+// arguments go before the first --receiver (or give C).  --receiver with fewer than two arguments, or without --heat or
+// --wave, is refused.  Of these loops only --heat without --ensemble runs the library's armed record
+// (slod_lod_time_record_arm); the others step one call at a time and observe the same states (LOD.h).
 // --direct: the time loops of --heat and --wave run on a banded Cholesky factor of their matrix S instead of CG
 // (slod_lod_factor_create once, slod_lod_theta_steps_direct / slod_lod_newmark_steps_direct): one line "factor: n = ..,
 // half bandwidth = .., bytes = .., pivots in [.., ..]" per loop, then the same per-step lines without iterations and
@@ -159,6 +169,27 @@ static void print_ldl_factor(const slod_lod_factor_info &f, const slod_lod_facto
               f.n, f.half_bandwidth, (unsigned long long)f.bytes, i.n_negative, i.norm_factor / i.norm_matrix);
 }
 
+// The trace of the receivers after a time loop: one line per record, receiver and member, "<what> receiver Q member K record
+// J: t = .., u = ..[, v = ..]"; a run without --ensemble prints its --member as K, so that the lines of --ensemble K are those
+// of K runs with --member.
+template <typename P>
+static void print_trace(const P &problem, const char *what, const double dt, const int first_member)
+{
+  const unsigned int nr = problem.trace_receivers(), nc = problem.trace_columns(), nq = problem.trace_quantities();
+  const std::vector<double> &t = problem.trace();
+  for (unsigned int j = 0; j < problem.trace_records(); ++j)
+    for (unsigned int q = 0; q < nr; ++q)
+      for (unsigned int c = 0; c < nc; ++c)
+        {
+          const double time = (double)(j * problem.trace_every()) * dt;
+          std::printf("%s receiver %u member %u record %u: t = %.12e, u = %.12e", what, q, (unsigned int)first_member + c, j, time,
+                      t[(((std::size_t)j * nq + 0) * nr + q) * nc + c]);
+          if (nq == 2)
+            std::printf(", v = %.12e", t[(((std::size_t)j * nq + 1) * nr + q) * nc + c]);
+          std::printf("\n");
+        }
+}
+
 // sample mean and unbiased standard deviation, summed in ascending order
 static void mean_and_deviation(const std::vector<double> &x, double &mean, double &dev)
 {
@@ -184,9 +215,27 @@ int main(int argc_all, char **argv_all)
   int                irk = -1; // --irk gauss | radau: SLOD_IRK_GAUSS2, SLOD_IRK_RADAU2A
   const char        *irk_name = "";
   std::vector<char *> args;
+  std::vector<Problem::ReceiverPoint> receivers; // --receiver X Y [C], repeatable
+  int                record_every = 1;           // --record-every M
   for (int i = 0; i < argc_all; ++i)
     if (i > 0 && !std::strcmp(argv_all[i], "--compare"))
       compare = true;
+    else if (i > 0 && !std::strcmp(argv_all[i], "--receiver"))
+      {
+        if (i + 2 >= argc_all)
+          {
+            std::fprintf(stderr, "--receiver takes X Y [C]\n");
+            return 1;
+          }
+        Problem::ReceiverPoint p{std::atof(argv_all[i + 1]), std::atof(argv_all[i + 2]), 0};
+        i += 2;
+        // the component, when the next argument is a plain non-negative integer
+        if (i + 1 < argc_all && argv_all[i + 1][0] != '\0' && std::strspn(argv_all[i + 1], "0123456789") == std::strlen(argv_all[i + 1]))
+          p.component = std::atoi(argv_all[++i]);
+        receivers.push_back(p);
+      }
+    else if (i > 0 && !std::strcmp(argv_all[i], "--record-every") && i + 1 < argc_all)
+      record_every = std::atoi(argv_all[++i]);
     else if (i > 0 && !std::strcmp(argv_all[i], "--coarse"))
       compare = coarse = true;
     else if (i > 0 && !std::strcmp(argv_all[i], "--direct"))
@@ -243,6 +292,10 @@ int main(int argc_all, char **argv_all)
     {
       if (irk == -2)
         throw std::runtime_error("--irk takes gauss or radau");
+      if (record_every < 1)
+        throw std::runtime_error("--record-every takes M >= 1");
+      if (!receivers.empty() && heat_steps <= 0 && wave_steps <= 0)
+        throw std::runtime_error("--receiver records inside a time loop: give --heat STEPS DT or --wave STEPS DT");
       LODParameters<2, 1> par;
       par.n_global_refinements  = argc > 1 ? std::atoi(argv[1]) : 3;
       par.n_subdivisions        = argc > 2 ? std::atoi(argv[2]) : 4;
@@ -325,10 +378,18 @@ int main(int argc_all, char **argv_all)
               problem.solve();
             }
           problem.assemble_mass_matrix();
+          const bool record = !receivers.empty() && n_members <= 0; // with --ensemble the ensemble loop records
+          if (record)
+            {
+              problem.create_receivers(receivers);
+              problem.record_next((unsigned int)record_every);
+            }
           if (irk >= 0)
             problem.solve_heat_irk(irk, (unsigned int)heat_steps, heat_dt);
           else
             problem.solve_heat((unsigned int)heat_steps, heat_dt, 1.0, direct);
+          if (record)
+            print_trace(problem, "heat", heat_dt, member);
           problem.compare_heat_with_lod();
           if (irk >= 0)
             print_irk_factor(irk_name, problem.last_factor_info(), problem.last_factor_inertia());
@@ -389,10 +450,18 @@ int main(int argc_all, char **argv_all)
             }
           if (heat_steps <= 0 && n_eigs <= 0)
             problem.assemble_mass_matrix();
+          const bool record = !receivers.empty() && n_members <= 0; // with --ensemble the ensemble loop records
+          if (record)
+            {
+              problem.create_receivers(receivers);
+              problem.record_next((unsigned int)record_every);
+            }
           if (irk >= 0)
             problem.solve_wave_irk(irk, (unsigned int)wave_steps, wave_dt);
           else
             problem.solve_wave((unsigned int)wave_steps, wave_dt, 0.25, 0.5, direct);
+          if (record)
+            print_trace(problem, "wave", wave_dt, member);
           if (irk >= 0)
             print_irk_factor(irk_name, problem.last_factor_info(), problem.last_factor_inertia());
           else if (direct)
@@ -475,7 +544,14 @@ int main(int argc_all, char **argv_all)
             }
           if (heat_steps > 0 && direct)
             {
+              if (!receivers.empty())
+                {
+                  problem.create_receivers(receivers, true);
+                  problem.record_next((unsigned int)record_every);
+                }
               problem.solve_heat_ensemble((unsigned int)heat_steps, heat_dt, 1.0);
+              if (!receivers.empty())
+                print_trace(problem, "heat", heat_dt, 0);
               print_factor(problem.last_factor_info());
               for (int j = 0; j < heat_steps; ++j)
                 for (int k = 0; k < n_members; ++k)
@@ -489,7 +565,14 @@ int main(int argc_all, char **argv_all)
             }
           if (wave_steps > 0 && direct)
             {
+              if (!receivers.empty())
+                {
+                  problem.create_receivers(receivers, true);
+                  problem.record_next((unsigned int)record_every);
+                }
               problem.solve_wave_ensemble((unsigned int)wave_steps, wave_dt, 0.25, 0.5);
+              if (!receivers.empty())
+                print_trace(problem, "wave", wave_dt, 0);
               print_factor(problem.last_factor_info());
               for (int k = 0; k < n_members; ++k)
                 for (int j = 1; j <= wave_steps; ++j)
@@ -505,7 +588,14 @@ int main(int argc_all, char **argv_all)
             }
           if (heat_steps > 0 && irk >= 0)
             {
+              if (!receivers.empty())
+                {
+                  problem.create_receivers(receivers, true);
+                  problem.record_next((unsigned int)record_every);
+                }
               problem.solve_heat_irk_ensemble(irk, (unsigned int)heat_steps, heat_dt);
+              if (!receivers.empty())
+                print_trace(problem, "heat", heat_dt, 0);
               print_irk_factor(irk_name, problem.last_factor_info(), problem.last_factor_inertia());
               for (int j = 0; j < heat_steps; ++j)
                 for (int k = 0; k < n_members; ++k)
@@ -519,7 +609,14 @@ int main(int argc_all, char **argv_all)
             }
           if (wave_steps > 0 && irk >= 0)
             {
+              if (!receivers.empty())
+                {
+                  problem.create_receivers(receivers, true);
+                  problem.record_next((unsigned int)record_every);
+                }
               problem.solve_wave_irk_ensemble(irk, (unsigned int)wave_steps, wave_dt);
+              if (!receivers.empty())
+                print_trace(problem, "wave", wave_dt, 0);
               print_irk_factor(irk_name, problem.last_factor_info(), problem.last_factor_inertia());
               for (int k = 0; k < n_members; ++k)
                 for (int j = 1; j <= wave_steps; ++j)

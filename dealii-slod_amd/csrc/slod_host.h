@@ -25,6 +25,8 @@ struct slod_handle
   hipStream_t         stream = nullptr;
   bool                device_ready = false; // stream and coefficient storage exist
   double             *d_err_ws = nullptr;   // slod_compute_error_norms partials (slod_error.hip), on first use
+  slod_lod_time_record record{};            // slod_lod_time_record_arm: what the next stepper call takes off the handle
+  bool                record_armed = false;
   mutable std::string error;
 };
 
@@ -306,6 +308,34 @@ void slod_lod_energies_launch(const slod_handle *h, hipStream_t st, const double
 // member count" (the time loops on one matrix take a factor of one member) or "<who>: a complex factor
 // (slod_lod_factor_create_zldl) is solved by slod_lod_factor_solve_complex"; else SLOD_OK
 int slod_lod_factor_check(const slod_handle *h, const char *who, const slod_lod_factor *f, int n_members = 1);
+// The rows of a set of receivers over the coarse unknowns (slod_lod_receivers.hip): CSR, values member-minor
+// (values[e n_members + m]); one allocation, the values first.
+struct slod_lod_receivers
+{
+  slod_handle     *h = nullptr;
+  int              n_recv = 0, n_members = 1;
+  size_t           nnz = 0, bytes = 0;
+  uint32_t        *row_begin = nullptr, *cols = nullptr; // DEVICE [n_recv + 1], [nnz]
+  double          *values = nullptr;                     // DEVICE [nnz][n_members]
+  SlodDevBuf<char> mem;
+};
+// The record of a time loop (slod_lod_time_record_arm).  A stepper body takes it off the handle as its first action
+// (take: one-shot, whatever the call returns then), checks it after its own checks and before any device work (check: the
+// refusals of include/slod.h in their order, nq = the quantities of a record), and queues one product on the loop's stream
+// for the entry state and after every every-th advance (launch: record j; u and v in one launch).  Not armed: check
+// returns SLOD_OK and the loop launches nothing more.
+struct SlodLodRecord
+{
+  bool                 armed = false;
+  int                  nq = 1;
+  slod_lod_time_record rec{};
+  // the record that the state after `steps_done` steps goes to, or -1
+  int slot(int steps_done) const { return armed && steps_done % rec.every == 0 ? steps_done / rec.every : -1; }
+};
+SlodLodRecord slod_lod_record_take(slod_handle *h);
+int  slod_lod_record_check(const slod_handle *h, const std::string &who, SlodLodRecord *r, bool has_v, int n_steps, int n, bool per_col);
+void slod_lod_record_launch(hipStream_t st, const SlodLodRecord &r, int j, int n, bool per_col, const double *d_u, size_t ld_u,
+                            const double *d_v, size_t ld_v);
 // ---- what the loops of the LOD space (slod_lod_time.hip, slod_lod_wave.hip) are written on, once per scheme
 // The operator of a column of a coarse multi-vector: one matrix for all columns, or (per_col) for column k member k of an
 // ensemble matrix with leading dimension ld_m (include/slod.h).

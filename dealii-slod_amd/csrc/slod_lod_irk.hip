@@ -289,13 +289,16 @@ namespace
   // or wave (order 2); the body of the four calls.  Single: the n = n_rhs columns on the one matrix pair and on factor
   // member first_member.  per_col: column m on member m of the ensemble matrices (ld_a_m, ld_m_m) and on factor member
   // first_member + m, which reads column m of the right-hand side whatever first_member.  The whole loop is queued and
-  // the stream is waited for once: three launches a step, five with the energies, for any n.
+  // the stream is waited for once: three launches a step, five with the energies, for any n.  A record armed on the
+  // handle (SlodLodRecord, slod_host.h) is taken first, checked after the call's own checks and adds one launch after the
+  // entry state and every every-th advance.
   int irk_steps(slod_handle *h, const std::string &who, int order, slod_lod_factor *f, int first_member, int scheme,
                 const double *d_stiffness, size_t ld_a_m, const double *d_mass, size_t ld_m_m, bool per_col, const uint32_t *d_cols,
                 double dt, double damp_mass, double damp_stiff, int n_steps, int n, double *d_u, size_t ld_u, double *d_v, size_t ld_v,
                 const double *d_load, size_t ld_load, size_t load_stage_stride, double *kinetic, double *potential)
   {
-    const bool wave = order == 2;
+    const bool    wave = order == 2;
+    SlodLodRecord rec = slod_lod_record_take(h);
     if (!h)
       return slod_fail(nullptr, SLOD_ERR_ARGUMENT, who + ": NULL handle");
     if (!d_stiffness || !d_cols || !d_u || (wave && (!d_mass || !d_v)))
@@ -323,6 +326,8 @@ namespace
     const int n_fm = per_col ? n : 1; // factor members of the call
     if (first_member < 0 || first_member > f->n_members - n_fm)
       return slod_fail(h, SLOD_ERR_ARGUMENT, who + (per_col ? ": members outside the factor" : ": member outside the factor"));
+    if (const int rc = slod_lod_record_check(h, who, &rec, wave, n_steps, n, per_col))
+      return rc;
     hipStream_t st;
     if (const int rc = slod_enter(h, nullptr, &st))
       return rc;
@@ -349,6 +354,8 @@ namespace
     };
     if (energies)
       launch_energies(0);
+    if (rec.armed)
+      slod_lod_record_launch(st, rec, 0, n, per_col, d_u, ld_u, d_v, ld_v);
     e = hipGetLastError();
     for (int step = 0; step < n_steps && e == hipSuccess; ++step)
       {
@@ -371,6 +378,8 @@ namespace
           hipLaunchKernelGGL(k_irk_advance<2>, nblk, dim3(256), 0, st, w.nrow, n, k, w_re, w_im, d_u, ld_u, d_v, ld_v);
         if (energies)
           launch_energies(step + 1);
+        if (const int j = rec.slot(step + 1); j >= 0)
+          slod_lod_record_launch(st, rec, j, n, per_col, d_u, ld_u, d_v, ld_v);
         e = hipGetLastError();
       }
     std::vector<double> host(nenergy);

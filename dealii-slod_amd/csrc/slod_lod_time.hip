@@ -130,13 +130,18 @@ namespace
   // n_steps of the theta scheme on n columns,  S delta = dt (theta b1 + (1 - theta) b0 - A u),  u += delta,  whatever
   // solves the step; the body of the three calls.  CG: S = M + theta dt A is built here and every solve synchronises; on a
   // factor (of that S) the whole loop is queued and the stream is waited for once.  Returns the largest iteration count
-  // of a step (0 on a factor) or a negative status.
+  // of a step (0 on a factor) or a negative status.  A record armed on the handle (SlodLodRecord, slod_host.h) is taken
+  // first, checked after the call's own checks and queued on st: u at the receivers after the entry state and every
+  // every-th advance.
   int theta_steps(slod_handle *h, const char *who, SlodLodStepSolve &&solve, const SlodLodOperator &A, const double *d_mass,
                   const uint32_t *d_cols, double dt, double theta, int n_steps, int n, double *d_u, size_t ld_u, const double *d_load,
                   size_t ld_load, size_t load_step_stride)
   {
+    SlodLodRecord rec = slod_lod_record_take(h);
     if (const int rc = theta_check(h, who, solve, A, A.values && (d_mass || !solve.cg()) && d_cols && d_u, dt, theta, n_steps, n,
                                    {ld_u, d_load ? ld_load : ld_u}))
+      return rc;
+    if (const int rc = slod_lod_record_check(h, who, &rec, false, n_steps, n, A.per_col))
       return rc;
     hipStream_t st;
     if (const int rc = slod_enter(h, nullptr, &st))
@@ -154,6 +159,8 @@ namespace
             solve.S = S;
             e       = hipGetLastError();
           }
+        if (rec.armed)
+          slod_lod_record_launch(st, rec, 0, n, A.per_col, d_u, ld_u, nullptr, 0);
         for (int k = 0; k < n_steps && e == hipSuccess; ++k)
           {
             const double *b0 = d_load ? d_load + (size_t)k * load_step_stride : nullptr;
@@ -166,6 +173,8 @@ namespace
             if (e != hipSuccess)
               break;
             hipLaunchKernelGGL(k_theta_advance, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n, delta, d_u, ld_u);
+            if (const int j = rec.slot(k + 1); j >= 0)
+              slod_lod_record_launch(st, rec, j, n, A.per_col, d_u, ld_u, nullptr, 0);
             e = hipGetLastError();
           }
         // on every path, a failed one too: the workspace is freed on return and a queued kernel may still touch it

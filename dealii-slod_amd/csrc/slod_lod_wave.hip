@@ -286,14 +286,19 @@ namespace
   // S a = g, corrector, and with kinetic / potential the two energies of every level; the body of the three steps calls.
   // CG: S = (1 + gamma dt damp_mass) M + (beta dt^2 + gamma dt damp_stiff) A is built here and every solve synchronises; on
   // a factor (of that S) the whole loop is queued and the stream is waited for once.  Returns the largest iteration count
-  // of a step (0 on a factor) or a negative status.
+  // of a step (0 on a factor) or a negative status.  A record armed on the handle (SlodLodRecord, slod_host.h) is taken
+  // first, checked after the call's own checks and queued on st: u and / or v at the receivers after the entry state and
+  // every every-th corrector.
   int nm_steps(slod_handle *h, const char *who, SlodLodStepSolve &&solve, const SlodLodOperator &A, const SlodLodOperator &M,
                const uint32_t *d_cols, double dt, double beta, double gamma, double damp_mass, double damp_stiff, int n_steps, int n,
                double *d_u, size_t ld_u, double *d_v, size_t ld_v, double *d_a, size_t ld_a, const double *d_load, size_t ld_load,
                size_t load_step_stride, double *kinetic, double *potential)
   {
+    SlodLodRecord rec = slod_lod_record_take(h);
     if (const int rc = nm_check(h, who, solve, true, A, M, d_cols && d_u && d_v && d_a, dt, beta, gamma, damp_mass, damp_stiff, n_steps,
                                 n, {ld_u, ld_v, ld_a, d_load ? ld_load : ld_u}, (kinetic == nullptr) == (potential == nullptr)))
+      return rc;
+    if (const int rc = slod_lod_record_check(h, who, &rec, true, n_steps, n, A.per_col))
       return rc;
     hipStream_t st;
     if (const int rc = slod_enter(h, nullptr, &st))
@@ -321,6 +326,8 @@ namespace
           }
         if (energies)
           launch_inner(w, st, M, d_cols, n, 2, jk, jp, 0.5, d_energy);
+        if (rec.armed)
+          slod_lod_record_launch(st, rec, 0, n, A.per_col, d_u, ld_u, d_v, ld_v);
         e = hipGetLastError();
         for (int k = 0; k < n_steps && e == hipSuccess; ++k)
           {
@@ -336,6 +343,8 @@ namespace
             hipLaunchKernelGGL(k_nm_correct, nblk, dim3(256), 0, st, w.nrow, n, bdt2, gdt, d_u, ld_u, d_v, ld_v, d_a, ld_a);
             if (energies)
               launch_inner(w, st, M, d_cols, n, 2, jk, jp, 0.5, d_energy + 2 * (size_t)(k + 1) * n);
+            if (const int j = rec.slot(k + 1); j >= 0)
+              slod_lod_record_launch(st, rec, j, n, A.per_col, d_u, ld_u, d_v, ld_v);
             e = hipGetLastError();
           }
         std::vector<double> host(nenergy);

@@ -26,6 +26,8 @@ namespace slod
   {
     for (slod_lod_factor *f : factors)
       slod_lod_factor_destroy(f);
+    slod_lod_receivers_destroy(receivers);
+    slod_lod_receivers_destroy(ens_receivers);
     for (void *p : device_arrays)
       (void)hipFree(p);
     slod_destroy(handle);
@@ -47,6 +49,120 @@ namespace slod
       throw std::runtime_error("hipMalloc of a global vector failed");
     device_arrays.push_back(p);
     return static_cast<T *>(p);
+  }
+
+  // ---- receivers and the record of the time loops
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::create_receivers(const std::vector<ReceiverPoint> &points, const bool ensemble)
+  {
+    if (ensemble ? !d_ens_basis : !d_basis)
+      throw std::runtime_error(ensemble ? "create_receivers: solve_ensemble comes first" :
+                                          "create_receivers: compute_basis_function_candidates comes first");
+    const unsigned int    NE = (1u << par.n_global_refinements) * par.n_subdivisions, NEp = NE + 1;
+    std::vector<uint32_t> begin(1, 0), node;
+    std::vector<int32_t>  comp;
+    std::vector<double>   weight;
+    for (const ReceiverPoint &p : points)
+      {
+        if (!(p.x >= 0.0 && p.x <= 1.0 && p.y >= 0.0 && p.y <= 1.0))
+          throw std::runtime_error("create_receivers: a point outside the unit square");
+        // the four bilinear terms of the element that holds the point; on the far boundary the missing node has weight 0
+        const double       fx = p.x * NE, fy = p.y * NE;
+        const unsigned int ex = std::min((unsigned int)fx, NE), ey = std::min((unsigned int)fy, NE);
+        const unsigned int x1 = std::min(ex + 1, NE), y1 = std::min(ey + 1, NE);
+        const double       tx = fx - ex, ty = fy - ey;
+        const uint32_t     nd[4] = {ex + ey * NEp, x1 + ey * NEp, ex + y1 * NEp, x1 + y1 * NEp};
+        const double       w[4] = {(1.0 - tx) * (1.0 - ty), tx * (1.0 - ty), (1.0 - tx) * ty, tx * ty};
+        for (int k = 0; k < 4; ++k)
+          {
+            node.push_back(nd[k]);
+            comp.push_back(p.component);
+            weight.push_back(w[k]);
+          }
+        begin.push_back((uint32_t)node.size());
+      }
+    slod_lod_receivers *&r = ensemble ? ens_receivers : receivers;
+    slod_lod_receivers_destroy(r);
+    r = nullptr;
+    if (ensemble)
+      check(slod_lod_receivers_create(handle, (int)points.size(), begin.data(), node.data(), comp.data(), weight.data(), d_ens_basis,
+                                      ens_stride, ens_member_stride, (int)par.n_members, &r),
+            "slod_lod_receivers_create");
+    else
+      check(slod_lod_receivers_create(handle, (int)points.size(), begin.data(), node.data(), comp.data(), weight.data(), d_basis,
+                                      basis_stride, 0, 1, &r),
+            "slod_lod_receivers_create");
+    n_receivers = (unsigned int)points.size();
+  }
+
+  template <int dim, int spacedim>
+  bool LOD<dim, spacedim>::record_open(const unsigned int n_steps, const unsigned int columns, const bool has_v, const bool ensemble)
+  {
+    trace_open = false;
+    if (record_every == 0)
+      return false;
+    trace_every_ = record_every;
+    record_every = 0; // one-shot, as the library's
+    if (ensemble ? !ens_receivers : !receivers)
+      throw std::runtime_error("record_next: create_receivers comes first");
+    trace_ensemble  = ensemble;
+    trace_nq        = has_v ? 2 : 1;
+    trace_cols      = columns;
+    trace_n_records = n_steps / trace_every_ + 1;
+    const std::size_t n = (std::size_t)trace_n_records * trace_nq * n_receivers * trace_cols;
+    if (n > d_trace_size) // kept for later records; a longer one takes a new array
+      {
+        d_trace      = device_alloc<double>(n);
+        d_trace_size = n;
+      }
+    if (hipMemset(d_trace, 0, n * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+      throw std::runtime_error("record_next: clearing the trace failed");
+    host_trace.assign(n, 0.0);
+    return trace_open = true;
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::record_arm(const unsigned int n_steps)
+  {
+    if (!trace_open)
+      return;
+    slod_lod_time_record rec{};
+    rec.recv          = trace_ensemble ? ens_receivers : receivers;
+    rec.what          = trace_nq == 2 ? (SLOD_RECORD_U | SLOD_RECORD_V) : SLOD_RECORD_U;
+    rec.every         = (int)trace_every_;
+    rec.d_trace       = d_trace;
+    rec.ld_trace      = trace_cols;
+    rec.record_stride = (std::size_t)trace_nq * n_receivers * trace_cols;
+    rec.capacity      = (int)(n_steps / trace_every_ + 1);
+    check(slod_lod_time_record_arm(handle, &rec), "slod_lod_time_record_arm");
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::record_state(const unsigned int steps_done, const double *d_u, const double *d_v)
+  {
+    if (!trace_open || steps_done % trace_every_ != 0)
+      return;
+    const std::size_t block = (std::size_t)n_receivers * trace_cols;
+    double           *at = d_trace + (std::size_t)(steps_done / trace_every_) * trace_nq * block;
+    const double     *x[2] = {d_u, d_v};
+    for (unsigned int w = 0; w < trace_nq; ++w)
+      if (trace_ensemble)
+        check(slod_lod_observe_ensemble(handle, ens_receivers, 0, (int)trace_cols, x[w], trace_cols, at + w * block, trace_cols, nullptr),
+              "slod_lod_observe_ensemble");
+      else
+        check(slod_lod_observe_multi(handle, receivers, x[w], trace_cols, (int)trace_cols, at + w * block, trace_cols, nullptr),
+              "slod_lod_observe_multi");
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::record_close()
+  {
+    if (!trace_open)
+      return;
+    trace_open = false;
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(host_trace.data(), d_trace, host_trace.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+      throw std::runtime_error("record_next: download of the trace failed");
   }
 
   // GridGenerator::hyper_cube + refine_global + evenly distributed partitioning (LOD.cc:110-119)
@@ -725,11 +841,14 @@ namespace slod
     if (hipMemset(d_u, 0, n_coarse * K * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
       throw std::runtime_error("solve_heat_ensemble: clearing the initial state failed");
     ens_heat_error.assign((std::size_t)n_steps * K, slod_error_norms{});
+    record_open(n_steps, (unsigned int)K, false, true);
+    record_state(0, d_u, nullptr);
     for (unsigned int step = 0; step < n_steps; ++step)
       {
         check(slod_lod_theta_steps_ensemble_direct(handle, f, d_ens_values, (std::size_t)K, d_ens_cols, dt, theta, 1, K, d_u,
                                                    (std::size_t)K, d_ens_rhs, (std::size_t)K, 0),
               "slod_lod_theta_steps_ensemble_direct");
+        record_state(step + 1, d_u, nullptr);
         check(slod_lod_reconstruct_ensemble(handle, d_ens_basis, ens_stride, ens_member_stride, K, d_u, (std::size_t)K, d_fine, fine_size,
                                             nullptr),
               "slod_lod_reconstruct_ensemble");
@@ -738,6 +857,7 @@ namespace slod
                                          &ens_heat_error[(std::size_t)step * K + k], nullptr),
                 "slod_compute_error_norms");
       }
+    record_close();
     ensemble_moment_norms(d_fine, d_mean, d_var, ens_heat_mean_norms, ens_heat_dev_norms);
   }
 
@@ -783,11 +903,14 @@ namespace slod
     ens_wave_potential.assign((std::size_t)(n_steps + 1) * K, 0.0);
     ens_wave_work.assign((std::size_t)(n_steps + 1) * K, 0.0);
     std::vector<double> kinetic(2 * ld), potential(2 * ld);
+    record_open(n_steps, (unsigned int)K, true, true);
+    record_state(0, d_u, d_v);
     for (unsigned int step = 0; step < n_steps; ++step)
       {
         check(slod_lod_newmark_steps_ensemble_direct(handle, f_S, d_ens_sym, ld, d_ens_mass, ld, d_ens_cols, dt, beta, gamma, 0.0, 0.0, 1,
                                                      K, d_u, ld, d_v, ld, d_a, ld, d_ens_rhs, ld, 0, kinetic.data(), potential.data()),
               "slod_lod_newmark_steps_ensemble_direct");
+        record_state(step + 1, d_u, d_v);
         if (hipMemcpy(u.data(), d_u, u.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
           throw std::runtime_error("solve_wave_ensemble: download of the states failed");
         for (int k = 0; k < K; ++k)
@@ -807,6 +930,7 @@ namespace slod
       }
     check(slod_lod_reconstruct_ensemble(handle, d_ens_basis, ens_stride, ens_member_stride, K, d_u, ld, d_fine, fine_size, nullptr),
           "slod_lod_reconstruct_ensemble");
+    record_close();
     ensemble_moment_norms(d_fine, d_mean, d_var, ens_wave_mean_norms, ens_wave_dev_norms);
   }
 
@@ -1017,13 +1141,19 @@ namespace slod
         if (hipDeviceSynchronize() != hipSuccess)
           throw std::runtime_error("solve_heat: forming S failed");
         slod_lod_factor *f = factor_lod_matrix(d_lod_shifted);
+        record_open(n_steps, 1, false, false);
+        record_arm(n_steps);
         check(slod_lod_theta_steps_direct(handle, f, d_lod_values, d_lod_cols, dt, theta, (int)n_steps, 1, d_heat_u, 1, d_heat_rhs, 1, 0),
               "slod_lod_theta_steps_direct");
+        record_close();
         return;
       }
+    record_open(n_steps, 1, false, false);
+    record_arm(n_steps);
     check(slod_lod_theta_steps(handle, d_lod_values, d_lod_mass, d_lod_cols, dt, theta, (int)n_steps, 1, d_heat_u, 1, d_heat_rhs, 1,
                                0, lod_rel_tol, lod_max_iterations, lod_heat_iterations.data(), lod_heat_residuals.data()),
           "slod_lod_theta_steps");
+    record_close();
   }
 
   template <int dim, int spacedim>
@@ -1224,6 +1354,8 @@ namespace slod
     lod_wave_kinetic.assign(n_steps + 1, 0.0);
     lod_wave_potential.assign(n_steps + 1, 0.0);
     lod_wave_work.assign(n_steps + 1, 0.0);
+    record_open(n_steps, 1, true, false);
+    record_state(0, d_u, d_v);
     for (unsigned int k = 0; k < n_steps; ++k)
       {
         double    kinetic[2], potential[2];
@@ -1238,6 +1370,7 @@ namespace slod
                                                    &lod_wave_iterations[k], &lod_wave_residuals[k], kinetic, potential);
             check(its < 0 ? its : 0, "slod_lod_newmark_steps");
           }
+        record_state(k + 1, d_u, d_v);
         if (hipMemcpy(u.data(), d_u, n_coarse * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
           throw std::runtime_error("solve_wave: download of the state failed");
         if (k == 0)
@@ -1252,6 +1385,7 @@ namespace slod
           work += u[i] * b[i];
         lod_wave_work[k + 1] = work;
       }
+    record_close();
     check(slod_lod_reconstruct(handle, d_basis, basis_stride, d_u, d_wave_fine, nullptr), "slod_lod_reconstruct");
     check(slod_compute_error_norms(handle, 0, d_wave_fine, nullptr, nullptr, nullptr, &wave_norms, nullptr),
           "slod_compute_error_norms");
@@ -1297,8 +1431,11 @@ namespace slod
     lod_heat_iterations.assign(n_steps, 0);
     lod_heat_residuals.assign(n_steps, 0.0);
     slod_lod_factor *f = factor_lod_irk(scheme, 1, dt);
+    record_open(n_steps, 1, false, false);
+    record_arm(n_steps);
     check(slod_lod_irk_heat_steps_direct(handle, f, 0, scheme, d_lod_sym, d_lod_cols, dt, (int)n_steps, 1, d_heat_u, 1, d_heat_rhs, 1, 0),
           "slod_lod_irk_heat_steps_direct");
+    record_close();
   }
 
   template <int dim, int spacedim>
@@ -1335,12 +1472,15 @@ namespace slod
     lod_wave_kinetic.assign(n_steps + 1, 0.0);
     lod_wave_potential.assign(n_steps + 1, 0.0);
     lod_wave_work.assign(n_steps + 1, 0.0);
+    record_open(n_steps, 1, true, false);
+    record_state(0, d_u, d_v);
     for (unsigned int k = 0; k < n_steps; ++k)
       {
         double kinetic[2], potential[2];
         check(slod_lod_irk_wave_steps_direct(handle, f, 0, scheme, d_lod_sym, d_lod_mass, d_lod_cols, dt, 0.0, 0.0, 1, 1, d_u, 1, d_v, 1,
                                              d_b, 1, 0, kinetic, potential),
               "slod_lod_irk_wave_steps_direct");
+        record_state(k + 1, d_u, d_v);
         if (hipMemcpy(u.data(), d_u, n_coarse * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
           throw std::runtime_error("solve_wave_irk: download of the state failed");
         if (k == 0)
@@ -1355,6 +1495,7 @@ namespace slod
           work += u[i] * b[i];
         lod_wave_work[k + 1] = work;
       }
+    record_close();
     check(slod_lod_reconstruct(handle, d_basis, basis_stride, d_u, d_wave_fine, nullptr), "slod_lod_reconstruct");
     check(slod_compute_error_norms(handle, 0, d_wave_fine, nullptr, nullptr, nullptr, &wave_norms, nullptr),
           "slod_compute_error_norms");
@@ -1401,10 +1542,13 @@ namespace slod
     if (hipMemset(d_u, 0, n_coarse * K * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
       throw std::runtime_error("solve_heat_irk_ensemble: clearing the initial state failed");
     ens_heat_error.assign((std::size_t)n_steps * K, slod_error_norms{});
+    record_open(n_steps, (unsigned int)K, false, true);
+    record_state(0, d_u, nullptr);
     for (unsigned int step = 0; step < n_steps; ++step)
       {
         check(slod_lod_irk_heat_steps_ensemble_direct(handle, f, 0, scheme, d_ens_sym, ld, d_ens_cols, dt, 1, K, d_u, ld, d_ens_rhs, ld, 0),
               "slod_lod_irk_heat_steps_ensemble_direct");
+        record_state(step + 1, d_u, nullptr);
         check(slod_lod_reconstruct_ensemble(handle, d_ens_basis, ens_stride, ens_member_stride, K, d_u, ld, d_fine, fine_size, nullptr),
               "slod_lod_reconstruct_ensemble");
         for (int k = 0; k < K; ++k)
@@ -1412,6 +1556,7 @@ namespace slod
                                          &ens_heat_error[(std::size_t)step * K + k], nullptr),
                 "slod_compute_error_norms");
       }
+    record_close();
     ensemble_moment_norms(d_fine, d_mean, d_var, ens_heat_mean_norms, ens_heat_dev_norms);
   }
 
@@ -1437,11 +1582,14 @@ namespace slod
     ens_wave_potential.assign((std::size_t)(n_steps + 1) * K, 0.0);
     ens_wave_work.assign((std::size_t)(n_steps + 1) * K, 0.0);
     std::vector<double> kinetic(2 * ld), potential(2 * ld);
+    record_open(n_steps, (unsigned int)K, true, true);
+    record_state(0, d_u, d_v);
     for (unsigned int step = 0; step < n_steps; ++step)
       {
         check(slod_lod_irk_wave_steps_ensemble_direct(handle, f, 0, scheme, d_ens_sym, ld, d_ens_mass, ld, d_ens_cols, dt, 0.0, 0.0, 1, K,
                                                       d_u, ld, d_v, ld, d_ens_rhs, ld, 0, kinetic.data(), potential.data()),
               "slod_lod_irk_wave_steps_ensemble_direct");
+        record_state(step + 1, d_u, d_v);
         if (hipMemcpy(u.data(), d_u, u.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
           throw std::runtime_error("solve_wave_irk_ensemble: download of the states failed");
         for (int k = 0; k < K; ++k)
@@ -1459,6 +1607,7 @@ namespace slod
             ens_wave_work[(std::size_t)(step + 1) * K + k] = work;
           }
       }
+    record_close();
     check(slod_lod_reconstruct_ensemble(handle, d_ens_basis, ens_stride, ens_member_stride, K, d_u, ld, d_fine, fine_size, nullptr),
           "slod_lod_reconstruct_ensemble");
     ensemble_moment_norms(d_fine, d_mean, d_var, ens_wave_mean_norms, ens_wave_dev_norms);

@@ -261,6 +261,28 @@ namespace slod
     // problem with member k's coefficient.
     void solve_heat_irk_ensemble(const int scheme, const unsigned int n_steps, const double dt);
     void solve_wave_irk_ensemble(const int scheme, const unsigned int n_steps, const double dt);
+    // Receivers: component `component` of the FE function at the points (x, y) of the unit square, four bilinear terms each
+    // (slod_lod_receivers_create on the basis slab after compute_basis_function_candidates(), or with ensemble = true on
+    // the members' slabs after solve_ensemble()).  record_next(every) makes the NEXT solve_heat* / solve_wave* call record
+    // them: record j holds the state after j * every steps, record 0 the entry state.  Only the loops that are one stepper
+    // call (solve_heat, CG and direct, and solve_heat_irk) arm the library's record, slod_lod_time_record_arm.  solve_wave,
+    // solve_wave_irk and the four ensemble loops call the stepper once per step (for the energies' work term or the
+    // distances); there nothing is armed and slod_lod_observe_multi / _ensemble is queued on the same states after the
+    // steps that belong to a record: the words are the same.  trace() is
+    // [record][quantity (u, then v for the wave)][receiver][column (member)], on the host.
+    struct ReceiverPoint
+    {
+      double x, y;
+      int    component;
+    };
+    void create_receivers(const std::vector<ReceiverPoint> &points, const bool ensemble = false);
+    void record_next(const unsigned int every = 1) { record_every = every; }
+    const std::vector<double> &trace() const { return host_trace; }
+    unsigned int trace_records() const { return trace_n_records; }
+    unsigned int trace_quantities() const { return trace_nq; }
+    unsigned int trace_columns() const { return trace_cols; }
+    unsigned int trace_receivers() const { return n_receivers; }
+    unsigned int trace_every() const { return trace_every_; }
     // solve_harmonic for all members at once, after assemble_mass_matrix_ensemble(): the symmetrised stiffness of every
     // member (slod_lod_matrix_symmetrize_ensemble), the loads of solve_ensemble() (slod_lod_rhs_ensemble, f = 1) and one
     // slod_lod_harmonic_response_ensemble call for all (frequency, member) pairs.  Entry [frequency * n_members + member] of
@@ -434,6 +456,19 @@ namespace slod
     void ensemble_elliptic_solutions(double *d_ell_fine);
     // sym(A_k) of every member into d_ens_sym and the complex factor of the scheme's step matrices, a member per realisation
     slod_lod_factor *factor_lod_irk_ensemble(const int scheme, const int order, const double dt);
+    // create_receivers / record_next.  record_open: when a record is pending, the trace of a loop of n_steps on `columns`
+    // columns (DEVICE, zeroed) and true; record_arm: before a stepper call that runs the whole loop; record_state: after
+    // `steps_done` one-step calls, the product on (d_u, d_v) if that state belongs to a record; record_close: the trace to the host.
+    slod_lod_receivers *receivers = nullptr, *ens_receivers = nullptr;
+    unsigned int        n_receivers = 0, record_every = 0, trace_every_ = 1, trace_n_records = 0, trace_nq = 0, trace_cols = 0;
+    bool                trace_open = false, trace_ensemble = false;
+    double             *d_trace = nullptr;
+    std::size_t         d_trace_size = 0;
+    std::vector<double> host_trace;
+    bool record_open(const unsigned int n_steps, const unsigned int columns, const bool has_v, const bool ensemble);
+    void record_arm(const unsigned int n_steps);
+    void record_state(const unsigned int steps_done, const double *d_u, const double *d_v);
+    void record_close();
 
     void check(const int status, const char *what) const;
     std::vector<Point<dim>> fine_quadrature_points() const;

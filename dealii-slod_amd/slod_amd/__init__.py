@@ -64,6 +64,19 @@ class InertiaInfo(C.Structure):
         return self.norm_factor / self.norm_matrix
 
 
+class ReceiversInfo(C.Structure):
+    """slod_lod_receivers_info: receivers, members, entries of the rows per member, device bytes."""
+    _fields_ = [("n_receivers", C.c_int32), ("n_members", C.c_int32), ("nnz", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class TimeRecord(C.Structure):
+    """slod_lod_time_record: what the next stepper call on the handle records (slod_lod_time_record_arm)."""
+    _fields_ = [("recv", C.c_void_p), ("what", C.c_int), ("every", C.c_int), ("d_trace", C.c_void_p),
+                ("ld_trace", C.c_size_t), ("record_stride", C.c_size_t), ("capacity", C.c_int)]
+
+
+RECORD_U, RECORD_V = 1, 2   # enum slod_record_what
+
 _lib = None
 
 
@@ -219,6 +232,17 @@ def load():
     lib.slod_lod_irk_wave_steps_ensemble_direct.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp,
                                                             C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.c_size_t,
                                                             vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, dp, dp]
+    lib.slod_lod_receiver_capacity.argtypes = [vp]
+    lib.slod_lod_receiver_pattern.argtypes = [vp, C.c_uint32, u32p, C.c_size_t]
+    lib.slod_lod_receivers_create.argtypes = [vp, C.c_int, u32p, u32p, C.POINTER(C.c_int32), dp, vp, C.c_size_t, C.c_size_t,
+                                              C.c_int, C.POINTER(vp)]
+    lib.slod_lod_receivers_get_info.argtypes = [vp, C.POINTER(ReceiversInfo)]
+    lib.slod_lod_receivers_rows.argtypes = [vp, C.c_int, u32p, u32p, dp]
+    lib.slod_lod_receivers_destroy.argtypes = [vp]
+    lib.slod_lod_receivers_destroy.restype = None
+    lib.slod_lod_observe_multi.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp]
+    lib.slod_lod_observe_ensemble.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp]
+    lib.slod_lod_time_record_arm.argtypes = [vp, C.POINTER(TimeRecord)]
     lib.slod_update_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, C.c_int, C.c_size_t, C.c_int, vp]
     lib.slod_dirty_patches.argtypes = [vp, vp, u32p, C.c_size_t]
     lib.slod_plan_create_dirty.argtypes = [vp, C.c_uint32, vp, C.POINTER(vp)]
@@ -509,6 +533,85 @@ class ComplexFactor(EnsembleFactor):
         self.slod._check(self.lib.slod_lod_factor_solve_complex(self.f, first_member, K, d_rhs_re, d_rhs_im, ld_rhs, n_rhs,
                                                                 1 if shared_rhs else 0, d_u_re, d_u_im,
                                                                 K * n_rhs if ld_u is None else ld_u, stream))
+
+
+def point_terms(NE, s, x, y, comp=0):
+    """The four bilinear terms [(node, comp, weight)] of component comp of the FE function at the point (x, y) of the unit
+    square on the fine grid of NE x NE elements: nodes (ex, ey), (ex+1, ey), (ex, ey+1), (ex+1, ey+1) of the element that
+    holds the point.  The weights sum to 1; for a point on a node they are (1, 0, 0, 0).  Host only."""
+    if not (0.0 <= x <= 1.0 and 0.0 <= y <= 1.0) or not 0 <= comp < s:
+        raise ValueError("point_terms: a point of the unit square and a component below s")
+    fx, fy = x * NE, y * NE
+    ex, ey = min(int(np.floor(fx)), NE), min(int(np.floor(fy)), NE)
+    tx, ty = fx - ex, fy - ey
+    x1, y1 = min(ex + 1, NE), min(ey + 1, NE)          # on the far boundary the weight of the missing node is 0
+    NEp = NE + 1
+    return [(ex + ey * NEp, comp, (1.0 - tx) * (1.0 - ty)), (x1 + ey * NEp, comp, tx * (1.0 - ty)),
+            (ex + y1 * NEp, comp, (1.0 - tx) * ty), (x1 + y1 * NEp, comp, tx * ty)]
+
+
+class Receivers:
+    """slod_lod_receivers: the rows O = W C of a set of receivers over the coarse unknowns, built from the basis slab.
+    receivers: a sequence of receivers, each a sequence of terms (node, comp, weight); or term_begin/term_node/term_comp/
+    term_weight arrays as the C call takes them (raw=True).  .info (n_receivers, n_members, nnz, bytes), .rows(member),
+    .observe(...), .observe_ensemble(...), .close()."""
+
+    def __init__(self, slod, receivers, d_basis, stride, n_members=1, member_stride=None, raw=False):
+        self.slod, self.lib = slod, slod.lib
+        self.r = C.c_void_p()
+        if raw:
+            begin, node, comp, weight = receivers
+            n_recv = len(begin) - 1
+        else:
+            n_recv = len(receivers)
+            begin = np.concatenate([[0], np.cumsum([len(t) for t in receivers])]) if n_recv else np.zeros(1)
+            flat = [t for r in receivers for t in r]
+            node, comp, weight = [t[0] for t in flat], [t[1] for t in flat], [t[2] for t in flat]
+        self.term_begin = np.ascontiguousarray(begin, dtype=np.uint32)
+        self.term_node = np.ascontiguousarray(node, dtype=np.uint32)
+        self.term_comp = np.ascontiguousarray(comp, dtype=np.int32)
+        self.term_weight = np.ascontiguousarray(weight, dtype=np.float64)
+        u32p = C.POINTER(C.c_uint32)
+        slod._check(self.lib.slod_lod_receivers_create(
+            slod.h, n_recv, self.term_begin.ctypes.data_as(u32p), self.term_node.ctypes.data_as(u32p),
+            self.term_comp.ctypes.data_as(C.POINTER(C.c_int32)), _dp(self.term_weight), d_basis, stride,
+            slod.num_patches * stride if member_stride is None else member_stride, n_members, C.byref(self.r)))
+        self.info = ReceiversInfo()
+        slod._check(self.lib.slod_lod_receivers_get_info(self.r, C.byref(self.info)))
+        self.n_recv, self.n_members = self.info.n_receivers, self.info.n_members
+        slod._factors.add(self)                        # the handle closes its objects before itself
+
+    def rows(self, member=0):
+        """(row_begin[n_recv + 1], cols[nnz], values[nnz]) of one member, host arrays.  Synchronises."""
+        rb = np.zeros(self.n_recv + 1, dtype=np.uint32)
+        cols = np.zeros(max(self.info.nnz, 1), dtype=np.uint32)
+        vals = np.zeros(max(self.info.nnz, 1))
+        u32p = C.POINTER(C.c_uint32)
+        self.slod._check(self.lib.slod_lod_receivers_rows(self.r, member, rb.ctypes.data_as(u32p), cols.ctypes.data_as(u32p),
+                                                          _dp(vals)))
+        return rb, cols[:self.info.nnz], vals[:self.info.nnz]
+
+    def observe(self, d_u, d_y, n_rhs=1, ld_u=None, ld_y=None, stream=None):
+        """y[q, c] = (O u_c)_q on a coarse multi-vector, d_y[q * ld_y + c]; an object of one member.  Asynchronous."""
+        self.slod._check(self.lib.slod_lod_observe_multi(self.slod.h, self.r, d_u, n_rhs if ld_u is None else ld_u, n_rhs, d_y,
+                                                         n_rhs if ld_y is None else ld_y, stream))
+
+    def observe_ensemble(self, d_u, d_y, n_members=None, first_member=0, ld_u=None, ld_y=None, stream=None):
+        """Column m with the values of member first_member + m (n_members defaults to the rest of the object)."""
+        K = self.n_members - first_member if n_members is None else n_members
+        self.slod._check(self.lib.slod_lod_observe_ensemble(self.slod.h, self.r, first_member, K, d_u, K if ld_u is None else ld_u,
+                                                            d_y, K if ld_y is None else ld_y, stream))
+
+    def close(self):
+        if self.r:
+            self.lib.slod_lod_receivers_destroy(self.r)
+            self.r = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 LodFactor = Factor   # the name of the object in the documents of the LDL^T factor: .inertia(member=0)
@@ -914,6 +1017,37 @@ class Slod:
             K if ld_u is None else ld_u, d_v, K if ld_v is None else ld_v, d_load, K if ld_load is None else ld_load,
             load_stage_stride, _dp(kin) if energies else None, _dp(pot) if energies else None))
         return kin, pot
+
+    # ---- receivers: (C u)(x) at a few points, as a product and as a trace of the time loops ----
+    def lod_receiver_capacity(self):
+        return self.lib.slod_lod_receiver_capacity(self.h)
+
+    def lod_receiver_pattern(self, node):
+        """The columns p * s + d of the row of a term at the fine node `node`, in row order (host only)."""
+        buf = (C.c_uint32 * self.lod_receiver_capacity())()
+        n = self.lib.slod_lod_receiver_pattern(self.h, node, buf, len(buf))
+        if n < 0:
+            self._check(n)
+        return list(buf)[:n]
+
+    def lod_receivers(self, receivers, d_basis, stride, n_members=1, member_stride=None, raw=False):
+        """The rows of a set of receivers (each a sequence of terms (node, comp, weight); point_terms gives the four of a
+        point) from the basis slab, or from the n_members slabs of an ensemble: a Receivers object."""
+        return Receivers(self, receivers, d_basis, stride, n_members, member_stride, raw)
+
+    def lod_time_record(self, recv, trace_ptr, capacity=0, what=RECORD_U, every=1, ld_trace=None, record_stride=None, columns=1):
+        """Arms the record of the NEXT stepper call on this handle (one-shot): record j, quantity w (u before v), receiver q,
+        column c at trace_ptr[j * record_stride + (w * n_recv + q) * ld_trace + c] doubles.  ld_trace defaults to `columns`
+        (n_rhs or n_members of the stepper), record_stride to n_quantities * n_recv * ld_trace.  recv=None disarms."""
+        if recv is None:
+            self._check(self.lib.slod_lod_time_record_arm(self.h, None))
+            return None
+        ld = columns if ld_trace is None else ld_trace
+        nq = 2 if what == (RECORD_U | RECORD_V) else 1
+        rec = TimeRecord(recv.r if isinstance(recv, Receivers) else recv, what, every, trace_ptr, ld,
+                         nq * recv.n_recv * ld if record_stride is None else record_stride, capacity)
+        self._check(self.lib.slod_lod_time_record_arm(self.h, C.byref(rec)))
+        return rec
 
     # ---- the LOD systems of a coefficient ensemble: member k = problem k of the handle = column k of the coarse
     # multi-vectors; matrix values member-minor, entry e of member k at [e * ld_m + k] (include/slod.h) ----

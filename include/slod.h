@@ -324,7 +324,8 @@ int slod_lod_matrix_combine(slod_handle *h, double alpha, const double *d_a, dou
  * matrices, the parameters, and column c of u^0 and of the loads; one call with n_steps = 2 equals two calls with
  * n_steps = 1.  Device workspace (one matrix, 6 vectors of n_rhs columns) allocated once per call.
  * SLOD_ERR_ARGUMENT: NULL handle, matrix, d_cols or d_u; dt <= 0; theta outside [0, 1]; n_steps < 1; n_rhs < 1;
- * ld_u < n_rhs; ld_load < n_rhs with a load; max_iterations < 0.  Runs on the handle's stream; synchronises. */
+ * ld_u < n_rhs; ld_load < n_rhs with a load; max_iterations < 0.  Runs on the handle's stream; synchronises.  A record
+ * armed by slod_lod_time_record_arm (below) is taken by this call: the trace of u at the receivers, on the device. */
 int slod_lod_theta_steps(slod_handle *h, const double *d_stiffness, const double *d_mass, const uint32_t *d_cols, double dt,
                          double theta, int n_steps, int n_rhs, double *d_u, size_t ld_u, const double *d_load, size_t ld_load,
                          size_t load_step_stride, double rel_tol, int max_iterations,
@@ -432,7 +433,8 @@ int slod_lod_newmark_accel(slod_handle *h, const double *d_stiffness, const doub
  * workspace (one matrix, 6 vectors of n_rhs columns, the energies) allocated once per call.
  * SLOD_ERR_ARGUMENT: NULL handle, matrix, d_cols, u, v or a; dt <= 0 or NaN; beta outside [0, 1/2] or gamma outside
  * [0, 1]; a negative or NaN damping coefficient; n_steps < 1; n_rhs < 1; a leading dimension below n_rhs (ld_load only
- * with a load); max_iterations < 0; exactly one of kinetic / potential given.  Runs on the handle's stream; synchronises. */
+ * with a load); max_iterations < 0; exactly one of kinetic / potential given.  Runs on the handle's stream; synchronises.
+ * A record armed by slod_lod_time_record_arm (below) is taken by this call: the traces of u and / or v at the receivers. */
 int slod_lod_newmark_steps(slod_handle *h, const double *d_stiffness, const double *d_mass, const uint32_t *d_cols, double dt,
                            double beta, double gamma, double damp_mass, double damp_stiff, int n_steps, int n_rhs,
                            double *d_u, size_t ld_u, double *d_v, size_t ld_v, double *d_a, size_t ld_a,
@@ -529,7 +531,8 @@ int slod_lod_factor_inertia(const slod_lod_factor *f, int member, slod_lod_facto
  * end.  A column's bits depend only on the factor, the matrices, the parameters and that column's state and loads, and
  * one call with n_steps = 2 equals two calls with n_steps = 1.  Return SLOD_OK or a negative slod_status.
  * SLOD_ERR_ARGUMENT: as the call without _direct, less rel_tol / max_iterations; a NULL factor; the factor of another
- * handle or row count.  Run on the handle's stream; synchronise. */
+ * handle or row count.  Run on the handle's stream; synchronise.  The two steppers take a record armed by
+ * slod_lod_time_record_arm (below), its launches inside the one queue-and-wait; slod_lod_newmark_accel_direct leaves it. */
 int slod_lod_theta_steps_direct(slod_handle *h, slod_lod_factor *f_S, const double *d_stiffness, const uint32_t *d_cols,
                                 double dt, double theta, int n_steps, int n_rhs, double *d_u, size_t ld_u,
                                 const double *d_load, size_t ld_load, size_t load_step_stride);
@@ -715,7 +718,8 @@ int slod_lod_solve_ensemble_precond(slod_handle *h, slod_lod_factor *f_P,
  * equals two calls with n_steps = 1.  Loads as in slod_lod_theta_steps (d_load NULL: none), column k = member k.
  * SLOD_ERR_ARGUMENT: NULL handle, matrix, d_cols or d_u; dt <= 0; theta outside [0, 1]; n_steps < 1; n_members < 1 or
  * > 65535; ld_m, ld_u or (with a load) ld_load below n_members; a NULL factor, the factor of another handle or row count,
- * a factor whose member count is not n_members. */
+ * a factor whose member count is not n_members.  A record armed by slod_lod_time_record_arm (below) is taken by this
+ * call; its receivers hold n_members members and trace column m is member m's. */
 int slod_lod_theta_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, const double *d_stiffness, size_t ld_m,
                                          const uint32_t *d_cols, double dt, double theta, int n_steps, int n_members,
                                          double *d_u, size_t ld_u, const double *d_load, size_t ld_load,
@@ -757,7 +761,8 @@ int slod_lod_newmark_accel_ensemble_direct(slod_handle *h, slod_lod_factor *f_M,
  * both NULL and damp_mass = 0 d_mass is not read.  The loop is queued on the handle's stream and waited for once, the
  * energies stay on the device and are copied once at the end; device workspace (2 vectors of n_members columns, the
  * partials and the energies) is allocated once per call.  n_steps = 2 equals two calls with n_steps = 1 carrying u, v, a
- * over. */
+ * over.  A record armed by slod_lod_time_record_arm (below) is taken by this call (u and / or v of n_members members);
+ * slod_lod_newmark_accel_ensemble_direct leaves it. */
 int slod_lod_newmark_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, const double *d_stiffness, size_t ld_a_m,
                                            const double *d_mass, size_t ld_m_m, const uint32_t *d_cols, double dt,
                                            double beta, double gamma, double damp_mass, double damp_stiff, int n_steps,
@@ -1039,7 +1044,7 @@ int slod_lod_harmonic_response_ensemble(slod_handle *h, const double *d_stiffnes
  * a member outside the factor.  The real consumers go on refusing complex factors as above.
  * Not built: three-stage schemes (Radau IIA of order 5 and Gauss of order 6 need one real and one complex member),
  * CG or PCG as the stage solver, step-size control, dense output, the deal.II adapter.  (The ensemble forms are
- * slod_lod_irk_*_steps_ensemble_direct, below.) */
+ * slod_lod_irk_*_steps_ensemble_direct, below.)  The four steppers take a record armed by slod_lod_time_record_arm (below). */
 enum slod_irk_scheme { SLOD_IRK_GAUSS2 = 0, SLOD_IRK_RADAU2A = 1 };
 int slod_lod_irk_coefficients(int scheme, int order /* 1 heat, 2 wave */, double dt, double damp_mass, double damp_stiff,
                               double alpha[2], double beta[2]);
@@ -1081,7 +1086,8 @@ int slod_lod_irk_wave_steps_direct(slod_handle *h, slod_lod_factor *f_S, int mem
  * factor, "<call>: takes a complex factor (slod_lod_factor_create_zldl)".  The single calls go on taking `member` of a
  * factor of several members; the real consumers go on refusing it.
  * Not built: several columns per member, three-stage schemes, CG or PCG as the stage solver, members spread over ranks,
- * the deal.II adapter. */
+ * the deal.II adapter.  The two steppers take a record armed by slod_lod_time_record_arm (below); its receivers hold
+ * n_members members, read from member 0 whatever first_member. */
 int slod_lod_irk_heat_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S, int first_member, int scheme,
                                             const double *d_stiffness, size_t ld_a_m, const uint32_t *d_cols, double dt,
                                             int n_steps, int n_members, double *d_u, size_t ld_u,
@@ -1093,6 +1099,93 @@ int slod_lod_irk_wave_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S
                                             const double *d_load /* NULL = 0 */, size_t ld_load, size_t load_stage_stride,
                                             double *kinetic   /* HOST [(n_steps+1)*n_members], may be NULL */,
                                             double *potential /* HOST [(n_steps+1)*n_members], may be NULL */);
+
+/* ---- receivers: the solution at a few points, as a product on the LOD space and as a trace of the time loops ----
+ * Who runs a time loop wants the solution at a few points as a function of time: a seismogram, a sensor, a band on either
+ * over an ensemble.  These calls evaluate (C u)(x) at chosen points without forming the fine field, and record it inside
+ * the loops without cutting them into single steps.
+ * A TERM is (global fine node < (NE+1)^2, component c < spacedim, weight w); a RECEIVER is a short list of terms, given
+ * in CSR form on the host: receiver q owns the terms term_begin[q] .. term_begin[q+1]-1, term_begin[0] = 0.  One term of
+ * weight 1 is a nodal value, four terms with bilinear weights the FE function at a point, two of opposite sign a
+ * difference, a handful a small average.
+ * ROWS.  The row of a term over the coarse unknowns is what slod_lod_reconstruct sums for that node and component, in its
+ * order: the patches by centre cell cy, then cx, over the cells whose closed patch holds the node, then d = 0 .. s-1,
+ * each giving the column p s + d and the value w phi_{p,d}(node, c), rounded once.  The rows of a receiver's terms are
+ * concatenated in term order; equal columns are not merged; a patch whose rim holds the node stays in the row.  Storage is
+ * CSR, row_begin[n_recv + 1], cols[nnz], values[nnz K] member-minor (entry e of member m at values[e K + m]) for the K
+ * members of an ensemble slab laid out as for slod_lod_matrix_ensemble (d_basis, stride, member_stride; K = 1: one slab).
+ * slod_lod_receiver_capacity: the bound (2 l + 2)^2 s on the entries of a term.  slod_lod_receiver_pattern: the columns
+ * of the row of a term at `node` (they do not depend on the component), in row order; returns their count.  Both host only.
+ * slod_lod_receivers_create reads the slab once (one gather kernel) and synchronises; the rows are not refreshed after
+ * slod_update_coefficient: create the object again.  SLOD_ERR_ARGUMENT, before any device work, with the call's name: a
+ * NULL handle, array or out; n_recv < 1; a receiver without terms; a term_begin that is not monotone; a node >= (NE+1)^2;
+ * a component >= spacedim; a weight that is not finite; n_members < 1 or > 65535; a stride below the words of a patch; nnz
+ * that does not fit 31 bits.  SLOD_ERR_DEVICE without a usable GPU.
+ * THE PRODUCT y = O u on coarse multi-vectors: y of receiver q, column c at d_y[q ld_y + c].  slod_lod_observe_multi takes
+ * an object of one member and applies its rows to every column; slod_lod_observe_ensemble reads for column m the values
+ * of member first_member + m.  One thread per (receiver, column), one chain acc = fma(value_e, u[cols_e ld_u + c], acc)
+ * from 0.0 over the row in order: a one-term receiver of weight 1 gives the 64-bit word slod_lod_reconstruct_multi /
+ * slod_lod_reconstruct_ensemble writes at that node and component, and the bits of a column do not depend on the number
+ * of columns, a leading dimension or the column's position.  Entries c >= n inside an ld are neither read nor written.
+ * Asynchronous, no allocation.  SLOD_ERR_ARGUMENT: a NULL handle, receivers or array; n < 1; ld_u or ld_y below the
+ * columns; the receivers of another handle; an object of several members given to slod_lod_observe_multi; members outside
+ * the object.
+ * THE RECORD.  slod_lod_time_record_arm leaves on the handle what the NEXT stepper call records:
+ *   record j (0 .. n_steps / every), quantity w (u before v, of those asked for), receiver q, column c at
+ *   d_trace[j record_stride + (w n_recv + q) ld_trace + c];
+ * record j holds the state after j every steps, record 0 the entry state; with every = 3 and n_steps = 7 the state after
+ * step 7 is not recorded.  The product is queued on the loop's stream after the entry state and after the advance of
+ * every every-th step, u and v in one launch, inside the one queue-and-wait of the loops on a factor: nothing is allocated
+ * and nothing is read back; when the stepper returns the trace is complete, on the device.  Words of d_trace outside these
+ * positions are not written.  A loop without a record runs the code and has the bits it had before.
+ * ONE-SHOT: the next call of slod_lod_theta_steps, _direct, _ensemble_direct, slod_lod_newmark_steps, _direct,
+ * _ensemble_direct, slod_lod_irk_heat_steps_direct, slod_lod_irk_wave_steps_direct or their _ensemble_direct forms on this
+ * handle takes the record off the handle as its first action and is the only call that sees it, whatever it returns.
+ * Every other call leaves it alone (the slod_lod_newmark_accel calls too); rec = NULL disarms, and so does
+ * slod_lod_receivers_destroy of the receivers it names.  The struct is copied; d_trace must live until the stepper has
+ * returned.
+ * A stepper with a record refuses with SLOD_ERR_ARGUMENT, before any device work, after its own checks and in this order,
+ * "<call>: record: ...": SLOD_RECORD_V in a theta or heat loop; a `what` outside 1 .. 3; every < 1; a NULL d_trace; an
+ * ld_trace below the columns of the call; a record_stride below n_quantities n_recv ld_trace; capacity < n_steps / every
+ * + 1; the receivers of another handle; a member count that is not 1 for a single-problem stepper or not n_members for an
+ * ensemble stepper (whose column m reads member m of the object).  slod_lod_time_record_arm itself refuses a NULL handle
+ * and a NULL recv inside a non-NULL record.
+ * Not built: time signals that scale a load inside the loop (sources); full-field snapshots every M steps; merging equal
+ * columns of a row; receivers refreshed after slod_update_coefficient; records from the eigen and harmonic calls; members
+ * spread over ranks; the deal.II adapter. */
+typedef struct slod_lod_receivers slod_lod_receivers;
+typedef struct
+{
+  int32_t  n_receivers, n_members;
+  uint64_t nnz;   /* entries of the rows, per member */
+  uint64_t bytes; /* device memory of the object */
+} slod_lod_receivers_info;
+int slod_lod_receiver_capacity(const slod_handle *h);
+int slod_lod_receiver_pattern(const slod_handle *h, uint32_t node, uint32_t *cols /* HOST */, size_t capacity);
+int slod_lod_receivers_create(slod_handle *h, int n_recv, const uint32_t *term_begin /* HOST [n_recv+1] */,
+                              const uint32_t *term_node /* HOST */, const int32_t *term_comp /* HOST */,
+                              const double *term_weight /* HOST */, const double *d_basis, size_t stride, size_t member_stride,
+                              int n_members, slod_lod_receivers **out);
+int slod_lod_receivers_get_info(const slod_lod_receivers *recv, slod_lod_receivers_info *info);
+/* row_begin [n_recv + 1], cols [nnz] and the values [nnz] of one member to HOST arrays; synchronises the handle's stream */
+int slod_lod_receivers_rows(const slod_lod_receivers *recv, int member, uint32_t *row_begin, uint32_t *cols, double *values);
+void slod_lod_receivers_destroy(slod_lod_receivers *recv);
+int slod_lod_observe_multi(slod_handle *h, const slod_lod_receivers *recv, const double *d_u, size_t ld_u, int n_rhs, double *d_y,
+                            size_t ld_y, void *hip_stream);
+int slod_lod_observe_ensemble(slod_handle *h, const slod_lod_receivers *recv, int first_member, int n_members, const double *d_u,
+                               size_t ld_u, double *d_y, size_t ld_y, void *hip_stream);
+enum slod_record_what { SLOD_RECORD_U = 1, SLOD_RECORD_V = 2 };
+typedef struct
+{
+  const slod_lod_receivers *recv;
+  int     what;          /* SLOD_RECORD_U = 1, SLOD_RECORD_V = 2, or both */
+  int     every;         /* >= 1: record j holds the state after j * every steps, j = 0 is the entry state */
+  double *d_trace;       /* DEVICE */
+  size_t  ld_trace;      /* >= columns of the stepper call */
+  size_t  record_stride; /* doubles between records, >= n_quantities * n_recv * ld_trace */
+  int     capacity;      /* records d_trace can hold */
+} slod_lod_time_record;
+int slod_lod_time_record_arm(slod_handle *h, const slod_lod_time_record *rec /* NULL disarms */);
 
 /* ---- refresh after a local coefficient change ----------------------------------------------
  * Every entry point above takes the coefficient as fixed for the life of a basis (the reference does too: one
