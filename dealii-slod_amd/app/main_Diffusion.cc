@@ -4,6 +4,7 @@
 //                  [--reuse-factor] [--precond-member J]
 //                  [--member K] [--ldl] [--harmonic K W0 W1 [--damping DM DS]] (with --ensemble: per member)
 //                  [--receiver X Y [C]]... [--record-every M]
+//                  [--source X Y [C]]... [--ricker F0 T0 [AMP]] [--quiet-load]
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
 // file name it dumps, per patch, phi and psi in patch-lexicographic order (parity tests).
 // --compare (anywhere on the command line): after run(), the rest of the reference run() -- global
@@ -60,6 +61,12 @@
 // arguments go before the first --receiver (or give C).  --receiver with fewer than two arguments, or without --heat or
 // --wave, is refused.  Of these loops only --heat without --ensemble runs the library's armed record
 // (slod_lod_time_record_arm); the others step one call at a time and observe the same states (LOD.h).
+// --source X Y [C] (repeatable) with --ricker F0 T0 [AMP]: a unit point force in component C at (X, Y), scaled in time by the
+// Ricker wavelet AMP (1 - 2 a) exp(-a), a = (pi F0 (t - T0))^2, drives every --heat / --wave loop (CG, --direct, --irk, each
+// with --ensemble K or --member K) through LOD::create_sources and LOD::drive_next: the source adds to the loop's load.  The
+// wavelet is sampled where the loop reads its load: at t_k = k DT, and with --irk at the stage times t_k + c_i DT.
+// --quiet-load drops the problem's own load (f = 1), so that the --receiver lines are the response of the sources alone.
+// --source without --ricker (or the reverse), or without --heat or --wave, is refused.
 // --direct: the time loops of --heat and --wave run on a banded Cholesky factor of their matrix S instead of CG
 // (slod_lod_factor_create once, slod_lod_theta_steps_direct / slod_lod_newmark_steps_direct): one line "factor: n = ..,
 // half bandwidth = .., bytes = .., pivots in [.., ..]" per loop, then the same per-step lines without iterations and
@@ -191,6 +198,13 @@ static void print_trace(const P &problem, const char *what, const double dt, con
 }
 
 // sample mean and unbiased standard deviation, summed in ascending order
+// AMP (1 - 2 a) exp(-a), a = (pi f0 (t - t0))^2
+static double ricker(const double t, const double f0, const double t0, const double amp)
+{
+  const double x = M_PI * f0 * (t - t0), a = x * x;
+  return amp * (1.0 - 2.0 * a) * std::exp(-a);
+}
+
 static void mean_and_deviation(const std::vector<double> &x, double &mean, double &dev)
 {
   mean = 0.0;
@@ -217,6 +231,9 @@ int main(int argc_all, char **argv_all)
   std::vector<char *> args;
   std::vector<Problem::ReceiverPoint> receivers; // --receiver X Y [C], repeatable
   int                record_every = 1;           // --record-every M
+  std::vector<Problem::ReceiverPoint> sources;   // --source X Y [C], repeatable
+  bool               have_ricker = false, quiet_load = false; // --ricker F0 T0 [AMP], --quiet-load
+  double             ricker_f0 = 0.0, ricker_t0 = 0.0, ricker_amp = 1.0;
   for (int i = 0; i < argc_all; ++i)
     if (i > 0 && !std::strcmp(argv_all[i], "--compare"))
       compare = true;
@@ -234,6 +251,38 @@ int main(int argc_all, char **argv_all)
           p.component = std::atoi(argv_all[++i]);
         receivers.push_back(p);
       }
+    else if (i > 0 && !std::strcmp(argv_all[i], "--source"))
+      {
+        if (i + 2 >= argc_all)
+          {
+            std::fprintf(stderr, "--source takes X Y [C]\n");
+            return 1;
+          }
+        Problem::ReceiverPoint p{std::atof(argv_all[i + 1]), std::atof(argv_all[i + 2]), 0};
+        i += 2;
+        if (i + 1 < argc_all && argv_all[i + 1][0] != '\0' && std::strspn(argv_all[i + 1], "0123456789") == std::strlen(argv_all[i + 1]))
+          p.component = std::atoi(argv_all[++i]);
+        sources.push_back(p);
+      }
+    else if (i > 0 && !std::strcmp(argv_all[i], "--ricker") && i + 2 < argc_all)
+      {
+        have_ricker = true;
+        ricker_f0   = std::atof(argv_all[++i]);
+        ricker_t0   = std::atof(argv_all[++i]);
+        // the amplitude, when the next argument is a number and no flag
+        if (i + 1 < argc_all && std::strncmp(argv_all[i + 1], "--", 2) != 0)
+          {
+            char        *end = nullptr;
+            const double amp = std::strtod(argv_all[i + 1], &end);
+            if (end != argv_all[i + 1] && *end == '\0')
+              {
+                ricker_amp = amp;
+                ++i;
+              }
+          }
+      }
+    else if (i > 0 && !std::strcmp(argv_all[i], "--quiet-load"))
+      quiet_load = true;
     else if (i > 0 && !std::strcmp(argv_all[i], "--record-every") && i + 1 < argc_all)
       record_every = std::atoi(argv_all[++i]);
     else if (i > 0 && !std::strcmp(argv_all[i], "--coarse"))
@@ -296,6 +345,10 @@ int main(int argc_all, char **argv_all)
         throw std::runtime_error("--record-every takes M >= 1");
       if (!receivers.empty() && heat_steps <= 0 && wave_steps <= 0)
         throw std::runtime_error("--receiver records inside a time loop: give --heat STEPS DT or --wave STEPS DT");
+      if (sources.empty() != !have_ricker)
+        throw std::runtime_error("--source X Y [C] and --ricker F0 T0 [AMP] come together");
+      if (!sources.empty() && heat_steps <= 0 && wave_steps <= 0)
+        throw std::runtime_error("--source drives a time loop: give --heat STEPS DT or --wave STEPS DT");
       LODParameters<2, 1> par;
       par.n_global_refinements  = argc > 1 ? std::atoi(argv[1]) : 3;
       par.n_subdivisions        = argc > 2 ? std::atoi(argv[2]) : 4;
@@ -308,6 +361,29 @@ int main(int argc_all, char **argv_all)
         problem_parameter<2>(1, 100, 3); // the draws of the members before this one
       Problem problem(par, 1, 100, 3);
       problem.run();
+      problem.quiet_load(quiet_load);
+      // the sources and their wavelet for the next loop of `steps` steps: sampled at t_k, with --irk at the stage times
+      auto drive = [&](const int steps, const double dt, const bool ensemble) {
+        if (sources.empty())
+          return;
+        problem.create_sources(sources, ensemble);
+        std::vector<double> times;
+        if (irk >= 0)
+          {
+            const double r3 = std::sqrt(3.0);
+            const double c[2] = {irk == SLOD_IRK_GAUSS2 ? 0.5 - r3 / 6.0 : 1.0 / 3.0, irk == SLOD_IRK_GAUSS2 ? 0.5 + r3 / 6.0 : 1.0};
+            for (int k = 0; k < steps; ++k)
+              for (int i = 0; i < 2; ++i)
+                times.push_back(((double)k + c[i]) * dt);
+          }
+        else
+          for (int k = 0; k <= steps; ++k)
+            times.push_back((double)k * dt);
+        std::vector<double> signal;
+        for (const double t : times)
+          signal.insert(signal.end(), sources.size(), ricker(t, ricker_f0, ricker_t0, ricker_amp));
+        problem.drive_next(signal, (unsigned int)times.size());
+      };
       double s1 = 0, s2 = 0;
       for (const auto &p : problem.get_patches())
         for (std::size_t i = 0; i < p.basis_function[0].size(); ++i)
@@ -384,6 +460,8 @@ int main(int argc_all, char **argv_all)
               problem.create_receivers(receivers);
               problem.record_next((unsigned int)record_every);
             }
+          if (n_members <= 0)
+            drive(heat_steps, heat_dt, false);
           if (irk >= 0)
             problem.solve_heat_irk(irk, (unsigned int)heat_steps, heat_dt);
           else
@@ -456,6 +534,8 @@ int main(int argc_all, char **argv_all)
               problem.create_receivers(receivers);
               problem.record_next((unsigned int)record_every);
             }
+          if (n_members <= 0)
+            drive(wave_steps, wave_dt, false);
           if (irk >= 0)
             problem.solve_wave_irk(irk, (unsigned int)wave_steps, wave_dt);
           else
@@ -549,6 +629,7 @@ int main(int argc_all, char **argv_all)
                   problem.create_receivers(receivers, true);
                   problem.record_next((unsigned int)record_every);
                 }
+              drive(heat_steps, heat_dt, true);
               problem.solve_heat_ensemble((unsigned int)heat_steps, heat_dt, 1.0);
               if (!receivers.empty())
                 print_trace(problem, "heat", heat_dt, 0);
@@ -570,6 +651,7 @@ int main(int argc_all, char **argv_all)
                   problem.create_receivers(receivers, true);
                   problem.record_next((unsigned int)record_every);
                 }
+              drive(wave_steps, wave_dt, true);
               problem.solve_wave_ensemble((unsigned int)wave_steps, wave_dt, 0.25, 0.5);
               if (!receivers.empty())
                 print_trace(problem, "wave", wave_dt, 0);
@@ -593,6 +675,7 @@ int main(int argc_all, char **argv_all)
                   problem.create_receivers(receivers, true);
                   problem.record_next((unsigned int)record_every);
                 }
+              drive(heat_steps, heat_dt, true);
               problem.solve_heat_irk_ensemble(irk, (unsigned int)heat_steps, heat_dt);
               if (!receivers.empty())
                 print_trace(problem, "heat", heat_dt, 0);
@@ -614,6 +697,7 @@ int main(int argc_all, char **argv_all)
                   problem.create_receivers(receivers, true);
                   problem.record_next((unsigned int)record_every);
                 }
+              drive(wave_steps, wave_dt, true);
               problem.solve_wave_irk_ensemble(irk, (unsigned int)wave_steps, wave_dt);
               if (!receivers.empty())
                 print_trace(problem, "wave", wave_dt, 0);

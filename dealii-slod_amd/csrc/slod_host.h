@@ -27,6 +27,8 @@ struct slod_handle
   double             *d_err_ws = nullptr;   // slod_compute_error_norms partials (slod_error.hip), on first use
   slod_lod_time_record record{};            // slod_lod_time_record_arm: what the next stepper call takes off the handle
   bool                record_armed = false;
+  slod_lod_time_source source{};            // slod_lod_time_source_arm: what drives the next stepper call, taken with the record
+  bool                source_armed = false;
   mutable std::string error;
 };
 
@@ -336,6 +338,34 @@ SlodLodRecord slod_lod_record_take(slod_handle *h);
 int  slod_lod_record_check(const slod_handle *h, const std::string &who, SlodLodRecord *r, bool has_v, int n_steps, int n, bool per_col);
 void slod_lod_record_launch(hipStream_t st, const SlodLodRecord &r, int j, int n, bool per_col, const double *d_u, size_t ld_u,
                             const double *d_v, size_t ld_v);
+// A set of sources (slod_lod_sources.hip): the rows of a receivers object transposed.  Coarse row r with slot[r] = t >= 0
+// owns the entries begin[t] .. begin[t + 1] - 1, entry i with the source src[i] and the values values[i n_members + m],
+// in the order of the receivers' entries; one allocation, the values first.
+struct slod_lod_sources
+{
+  slod_handle     *h = nullptr;
+  int              n_src = 0, n_members = 1, nrow = 0;
+  uint32_t         n_touched = 0;
+  size_t           nnz = 0, bytes = 0;
+  double          *values = nullptr;                 // DEVICE [nnz][n_members]
+  uint32_t        *begin = nullptr, *src = nullptr;  // DEVICE [n_touched + 1], [nnz]
+  int32_t         *slot = nullptr;                   // DEVICE [nrow]
+  SlodDevBuf<char> mem;
+};
+// The source of a time loop (slod_lod_time_source_arm), the mirror of the record: taken off the handle with it, checked
+// after it ("<who>: source: ...", need = the samples the loop reads, bound = their count in words), and one product
+// b = base + O^T g queued per step ahead of the right-hand side (launch: ny = 1 or 2 consecutive samples from `sample`, the
+// base of sample y at d_base + y base_stride or NULL, written to d_b + y b_stride with the leading dimension n).
+struct SlodLodSource
+{
+  bool                 armed = false;
+  slod_lod_time_source s{};
+};
+SlodLodSource slod_lod_source_take(slod_handle *h);
+int  slod_lod_source_check(const slod_handle *h, const std::string &who, const SlodLodSource &s, int need, const char *bound, int n,
+                           bool per_col);
+void slod_lod_source_launch(hipStream_t st, const SlodLodSource &s, int sample, int ny, int n, bool per_col, const double *d_base,
+                            size_t ld_base, size_t base_stride, double *d_b, size_t b_stride);
 // ---- what the loops of the LOD space (slod_lod_time.hip, slod_lod_wave.hip) are written on, once per scheme
 // The operator of a column of a coarse multi-vector: one matrix for all columns, or (per_col) for column k member k of an
 // ensemble matrix with leading dimension ld_m (include/slod.h).

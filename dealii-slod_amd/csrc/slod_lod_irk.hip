@@ -291,7 +291,8 @@ namespace
   // first_member + m, which reads column m of the right-hand side whatever first_member.  The whole loop is queued and
   // the stream is waited for once: three launches a step, five with the energies, for any n.  A record armed on the
   // handle (SlodLodRecord, slod_host.h) is taken first, checked after the call's own checks and adds one launch after the
-  // entry state and every every-th advance.
+  // entry state and every every-th advance.  A source armed on it (SlodLodSource) is taken with the record, checked after
+  // it, and adds one launch a step, whose two vectors the right-hand side reads in place of the stage loads.
   int irk_steps(slod_handle *h, const std::string &who, int order, slod_lod_factor *f, int first_member, int scheme,
                 const double *d_stiffness, size_t ld_a_m, const double *d_mass, size_t ld_m_m, bool per_col, const uint32_t *d_cols,
                 double dt, double damp_mass, double damp_stiff, int n_steps, int n, double *d_u, size_t ld_u, double *d_v, size_t ld_v,
@@ -299,6 +300,7 @@ namespace
   {
     const bool    wave = order == 2;
     SlodLodRecord rec = slod_lod_record_take(h);
+    SlodLodSource src = slod_lod_source_take(h);
     if (!h)
       return slod_fail(nullptr, SLOD_ERR_ARGUMENT, who + ": NULL handle");
     if (!d_stiffness || !d_cols || !d_u || (wave && (!d_mass || !d_v)))
@@ -328,6 +330,8 @@ namespace
       return slod_fail(h, SLOD_ERR_ARGUMENT, who + (per_col ? ": members outside the factor" : ": member outside the factor"));
     if (const int rc = slod_lod_record_check(h, who, &rec, wave, n_steps, n, per_col))
       return rc;
+    if (const int rc = slod_lod_source_check(h, who, src, 2 * n_steps, "2 n_steps", n, per_col))
+      return rc;
     hipStream_t st;
     if (const int rc = slod_enter(h, nullptr, &st))
       return rc;
@@ -337,13 +341,13 @@ namespace
     const size_t   nvec = (size_t)w.nrow * n, npart = energies ? (size_t)w.ngroup * n : 0;
     const size_t   nenergy = energies ? 2 * (size_t)(n_steps + 1) * n : 0;
     // one allocation for the whole loop: the two planes of r and of w, and for the energies two arrays of partials and
-    // [level][kinetic, potential][column]
+    // [level][kinetic, potential][column]; driven by a source, the two stage loads
     SlodDevBuf<double> work;
-    hipError_t         e = work.alloc(4 * nvec + 2 * npart + nenergy);
+    hipError_t         e = work.alloc(4 * nvec + 2 * npart + nenergy + (src.armed ? 2 * nvec : 0));
     if (e != hipSuccess)
       return slod_hip_fail(h, e, who.c_str());
     double *r_re = work.get(), *r_im = r_re + nvec, *w_re = r_im + nvec, *w_im = w_re + nvec;
-    double *part_k = w_im + nvec, *part_p = part_k + npart, *d_energy = part_p + npart;
+    double *part_k = w_im + nvec, *part_p = part_k + npart, *d_energy = part_p + npart, *lb = d_energy + nenergy;
     const dim3     nblk = lod_flat_grid(nvec);
     const auto     heat_rhs = per_col ? k_irk_heat_rhs<true> : k_irk_heat_rhs<false>;
     const auto     wave_rhs = damp_mass != 0.0 ? (per_col ? k_irk_wave_rhs<true, true> : k_irk_wave_rhs<true, false>)
@@ -361,12 +365,18 @@ namespace
       {
         const double *b1 = d_load ? d_load + (size_t)(2 * step) * load_stage_stride : nullptr;
         const double *b2 = d_load ? d_load + ((size_t)(2 * step) + 1) * load_stage_stride : nullptr;
+        size_t        ld_b = ld_load;
+        if (src.armed) // the two stage loads + O^T g of the samples 2 step and 2 step + 1, in one launch
+          {
+            slod_lod_source_launch(st, src, 2 * step, 2, n, per_col, b1, ld_load, load_stage_stride, lb, nvec);
+            b1 = lb, b2 = lb + nvec, ld_b = (size_t)n;
+          }
         if (!wave)
           hipLaunchKernelGGL(heat_rhs, nblk, dim3(256), 0, st, w.nrow, w.s, w.cap, w.NP, n, k, d_stiffness, ld_a_m, d_cols, b1, b2,
-                             ld_load, d_u, ld_u, r_re, r_im);
+                             ld_b, d_u, ld_u, r_re, r_im);
         else
           hipLaunchKernelGGL(wave_rhs, nblk, dim3(256), 0, st, w.nrow, w.s, w.cap, w.NP, n, k, d_stiffness, ld_a_m, d_mass, ld_m_m,
-                             d_cols, b1, b2, ld_load, d_u, ld_u, d_v, ld_v, r_re, r_im);
+                             d_cols, b1, b2, ld_b, d_u, ld_u, d_v, ld_v, r_re, r_im);
         // single: the n columns on the one member; per_col: member first_member + m on column m of r, one column each
         if (per_col)
           slod_lod_zfactor_solve_launch(f, st, first_member, n, r_re, r_im, (size_t)n, 1, 0, n, w_re, w_im, (size_t)n);

@@ -132,25 +132,31 @@ namespace
   // factor (of that S) the whole loop is queued and the stream is waited for once.  Returns the largest iteration count
   // of a step (0 on a factor) or a negative status.  A record armed on the handle (SlodLodRecord, slod_host.h) is taken
   // first, checked after the call's own checks and queued on st: u at the receivers after the entry state and every
-  // every-th advance.
+  // every-th advance.  A source armed on it (SlodLodSource) is taken with the record, checked after it, and adds one
+  // product a step, whose two vectors the right-hand side reads in place of the loads.
   int theta_steps(slod_handle *h, const char *who, SlodLodStepSolve &&solve, const SlodLodOperator &A, const double *d_mass,
                   const uint32_t *d_cols, double dt, double theta, int n_steps, int n, double *d_u, size_t ld_u, const double *d_load,
                   size_t ld_load, size_t load_step_stride)
   {
     SlodLodRecord rec = slod_lod_record_take(h);
+    SlodLodSource src = slod_lod_source_take(h);
     if (const int rc = theta_check(h, who, solve, A, A.values && (d_mass || !solve.cg()) && d_cols && d_u, dt, theta, n_steps, n,
                                    {ld_u, d_load ? ld_load : ld_u}))
       return rc;
     if (const int rc = slod_lod_record_check(h, who, &rec, false, n_steps, n, A.per_col))
+      return rc;
+    if (const int rc = slod_lod_source_check(h, who, src, n_steps + 1, "n_steps + 1", n, A.per_col))
       return rc;
     hipStream_t st;
     if (const int rc = slod_enter(h, nullptr, &st))
       return rc;
     const LodShape w = lod_shape(h, n);
     const size_t   nmat = solve.cg() ? (size_t)w.NP * w.cap * w.s * w.s : 0, nvec = (size_t)w.nrow * n;
-    // one allocation for the whole loop: S (CG), g, delta and the workspace of the solve
-    double    *S, *g, *delta;
-    hipError_t e = solve.alloc(n, [&](SlodCarver &c) { S = c.take(nmat), g = c.take(nvec), delta = c.take(nvec), solve.take(c, h); });
+    // one allocation for the whole loop: S (CG), g, delta, the workspace of the solve and, driven by a source, two loads
+    double    *S, *g, *delta, *lb;
+    hipError_t e = solve.alloc(n, [&](SlodCarver &c) {
+      S = c.take(nmat), g = c.take(nvec), delta = c.take(nvec), solve.take(c, h), lb = c.take(src.armed ? 2 * nvec : 0);
+    });
     if (e == hipSuccess)
       {
         if (solve.cg())
@@ -165,8 +171,14 @@ namespace
           {
             const double *b0 = d_load ? d_load + (size_t)k * load_step_stride : nullptr;
             const double *b1 = d_load ? d_load + (size_t)(k + 1) * load_step_stride : nullptr;
+            size_t        ld_b = ld_load;
+            if (src.armed) // b^k and b^(k+1) = the loads + O^T g of the samples k and k + 1, in one launch
+              {
+                slod_lod_source_launch(st, src, k, 2, n, A.per_col, b0, ld_load, load_step_stride, lb, nvec);
+                b0 = lb, b1 = lb + nvec, ld_b = (size_t)n;
+              }
             slod_lod_apply_launch(h, st, A, d_cols, d_u, ld_u, n, g, (size_t)n);
-            hipLaunchKernelGGL(k_theta_rhs, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n, dt, theta, b0, b1, ld_load, g);
+            hipLaunchKernelGGL(k_theta_rhs, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n, dt, theta, b0, b1, ld_b, g);
             e = hipGetLastError();
             if (e == hipSuccess)
               e = solve.solve(h, st, k, n, g, (size_t)n, delta, (size_t)n);

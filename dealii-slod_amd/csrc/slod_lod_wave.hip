@@ -288,17 +288,21 @@ namespace
   // a factor (of that S) the whole loop is queued and the stream is waited for once.  Returns the largest iteration count
   // of a step (0 on a factor) or a negative status.  A record armed on the handle (SlodLodRecord, slod_host.h) is taken
   // first, checked after the call's own checks and queued on st: u and / or v at the receivers after the entry state and
-  // every every-th corrector.
+  // every every-th corrector.  A source armed on it (SlodLodSource) is taken with the record, checked after it, and adds
+  // one product a step, whose vector the right-hand side reads in place of the load.
   int nm_steps(slod_handle *h, const char *who, SlodLodStepSolve &&solve, const SlodLodOperator &A, const SlodLodOperator &M,
                const uint32_t *d_cols, double dt, double beta, double gamma, double damp_mass, double damp_stiff, int n_steps, int n,
                double *d_u, size_t ld_u, double *d_v, size_t ld_v, double *d_a, size_t ld_a, const double *d_load, size_t ld_load,
                size_t load_step_stride, double *kinetic, double *potential)
   {
     SlodLodRecord rec = slod_lod_record_take(h);
+    SlodLodSource src = slod_lod_source_take(h);
     if (const int rc = nm_check(h, who, solve, true, A, M, d_cols && d_u && d_v && d_a, dt, beta, gamma, damp_mass, damp_stiff, n_steps,
                                 n, {ld_u, ld_v, ld_a, d_load ? ld_load : ld_u}, (kinetic == nullptr) == (potential == nullptr)))
       return rc;
     if (const int rc = slod_lod_record_check(h, who, &rec, true, n_steps, n, A.per_col))
+      return rc;
+    if (const int rc = slod_lod_source_check(h, who, src, n_steps + 1, "n_steps + 1", n, A.per_col))
       return rc;
     hipStream_t st;
     if (const int rc = slod_enter(h, nullptr, &st))
@@ -308,11 +312,11 @@ namespace
     const size_t   nmat = solve.cg() ? (size_t)w.NP * w.cap * w.s * w.s : 0, nvec = (size_t)w.nrow * n;
     const size_t   npart = energies ? (size_t)w.ngroup * n : 0, nenergy = energies ? 2 * (size_t)(n_steps + 1) * n : 0;
     // one allocation for the whole loop: S (CG), w = u~ + damp_stiff v~, g, the workspace of the solve, and for the
-    // energies two arrays of partials and [level][kinetic, potential][column]
-    double    *S, *arg, *g, *part_k, *part_p, *d_energy;
+    // energies two arrays of partials and [level][kinetic, potential][column]; driven by a source, one load
+    double    *S, *arg, *g, *part_k, *part_p, *d_energy, *lb;
     hipError_t e = solve.alloc(n, [&](SlodCarver &c) {
       S = c.take(nmat), arg = c.take(nvec), g = c.take(nvec), solve.take(c, h);
-      part_k = c.take(npart), part_p = c.take(npart), d_energy = c.take(nenergy);
+      part_k = c.take(npart), part_p = c.take(npart), d_energy = c.take(nenergy), lb = c.take(src.armed ? nvec : 0);
     });
     if (e == hipSuccess)
       {
@@ -332,9 +336,15 @@ namespace
         for (int k = 0; k < n_steps && e == hipSuccess; ++k)
           {
             const double *b1 = d_load ? d_load + (size_t)(k + 1) * load_step_stride : nullptr;
+            size_t        ld_b = ld_load;
+            if (src.armed) // b^(k+1) = the load + O^T g of sample k + 1
+              {
+                slod_lod_source_launch(st, src, k + 1, 1, n, A.per_col, b1, ld_load, 0, lb, 0);
+                b1 = lb, ld_b = (size_t)n;
+              }
             hipLaunchKernelGGL(k_nm_predict, nblk, dim3(256), 0, st, w.nrow, n, dt, dt * dt * (0.5 - beta), dt * (1.0 - gamma),
                                damp_stiff, d_u, ld_u, d_v, ld_v, d_a, ld_a, arg);
-            launch_rhs(w, st, A, M, d_cols, n, damp_mass, b1, ld_load, arg, d_v, ld_v, g);
+            launch_rhs(w, st, A, M, d_cols, n, damp_mass, b1, ld_b, arg, d_v, ld_v, g);
             e = hipGetLastError();
             if (e == hipSuccess)
               e = solve.solve(h, st, k, n, g, (size_t)n, d_a, ld_a);

@@ -28,6 +28,8 @@ namespace slod
       slod_lod_factor_destroy(f);
     slod_lod_receivers_destroy(receivers);
     slod_lod_receivers_destroy(ens_receivers);
+    slod_lod_sources_destroy(sources);
+    slod_lod_sources_destroy(ens_sources);
     for (void *p : device_arrays)
       (void)hipFree(p);
     slod_destroy(handle);
@@ -53,11 +55,11 @@ namespace slod
 
   // ---- receivers and the record of the time loops
   template <int dim, int spacedim>
-  void LOD<dim, spacedim>::create_receivers(const std::vector<ReceiverPoint> &points, const bool ensemble)
+  slod_lod_receivers *LOD<dim, spacedim>::make_receivers(const std::vector<ReceiverPoint> &points, const bool ensemble, const char *who)
   {
     if (ensemble ? !d_ens_basis : !d_basis)
-      throw std::runtime_error(ensemble ? "create_receivers: solve_ensemble comes first" :
-                                          "create_receivers: compute_basis_function_candidates comes first");
+      throw std::runtime_error(std::string(who) + (ensemble ? ": solve_ensemble comes first" :
+                                                              ": compute_basis_function_candidates comes first"));
     const unsigned int    NE = (1u << par.n_global_refinements) * par.n_subdivisions, NEp = NE + 1;
     std::vector<uint32_t> begin(1, 0), node;
     std::vector<int32_t>  comp;
@@ -65,7 +67,7 @@ namespace slod
     for (const ReceiverPoint &p : points)
       {
         if (!(p.x >= 0.0 && p.x <= 1.0 && p.y >= 0.0 && p.y <= 1.0))
-          throw std::runtime_error("create_receivers: a point outside the unit square");
+          throw std::runtime_error(std::string(who) + ": a point outside the unit square");
         // the four bilinear terms of the element that holds the point; on the far boundary the missing node has weight 0
         const double       fx = p.x * NE, fy = p.y * NE;
         const unsigned int ex = std::min((unsigned int)fx, NE), ey = std::min((unsigned int)fy, NE);
@@ -81,9 +83,7 @@ namespace slod
           }
         begin.push_back((uint32_t)node.size());
       }
-    slod_lod_receivers *&r = ensemble ? ens_receivers : receivers;
-    slod_lod_receivers_destroy(r);
-    r = nullptr;
+    slod_lod_receivers *r = nullptr;
     if (ensemble)
       check(slod_lod_receivers_create(handle, (int)points.size(), begin.data(), node.data(), comp.data(), weight.data(), d_ens_basis,
                                       ens_stride, ens_member_stride, (int)par.n_members, &r),
@@ -92,7 +92,89 @@ namespace slod
       check(slod_lod_receivers_create(handle, (int)points.size(), begin.data(), node.data(), comp.data(), weight.data(), d_basis,
                                       basis_stride, 0, 1, &r),
             "slod_lod_receivers_create");
+    return r;
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::create_receivers(const std::vector<ReceiverPoint> &points, const bool ensemble)
+  {
+    slod_lod_receivers *&r = ensemble ? ens_receivers : receivers;
+    slod_lod_receivers_destroy(r);
+    r           = nullptr;
+    r           = make_receivers(points, ensemble, "create_receivers");
     n_receivers = (unsigned int)points.size();
+  }
+
+  // ---- sources and the signal that drives the time loops
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::create_sources(const std::vector<ReceiverPoint> &points, const bool ensemble)
+  {
+    slod_lod_sources *&s = ensemble ? ens_sources : sources;
+    slod_lod_sources_destroy(s);
+    s                     = nullptr;
+    slod_lod_receivers *r = make_receivers(points, ensemble, "create_sources");
+    const int           rc = slod_lod_sources_create(handle, r, &s);
+    slod_lod_receivers_destroy(r); // the sources own their copy of the rows
+    check(rc, "slod_lod_sources_create");
+    n_sources = (unsigned int)points.size();
+  }
+
+  template <int dim, int spacedim>
+  bool LOD<dim, spacedim>::source_open(const unsigned int needed, const unsigned int columns, const bool ensemble)
+  {
+    drive_open = false;
+    if (drive_samples == 0)
+      return false;
+    const unsigned int samples = drive_samples;
+    drive_samples              = 0; // one-shot, as the library's
+    if (ensemble ? !ens_sources : !sources)
+      throw std::runtime_error("drive_next: create_sources comes first");
+    if (samples < needed || drive_signal.size() < (std::size_t)samples * n_sources)
+      throw std::runtime_error("drive_next: the signal is shorter than the samples of the loop");
+    drive_ensemble = ensemble;
+    drive_cols     = columns;
+    std::vector<double> wide((std::size_t)needed * n_sources * columns);
+    for (std::size_t i = 0; i < (std::size_t)needed * n_sources; ++i)
+      for (unsigned int c = 0; c < columns; ++c)
+        wide[i * columns + c] = drive_signal[i];
+    if (wide.size() > d_signal_size) // kept for later loops; a longer one takes a new array
+      {
+        d_signal      = device_alloc<double>(wide.size());
+        d_signal_size = wide.size();
+      }
+    if (hipMemcpy(d_signal, wide.data(), wide.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+      throw std::runtime_error("drive_next: upload of the signal failed");
+    drive_samples_open = needed;
+    return drive_open = true;
+  }
+
+  template <int dim, int spacedim>
+  void LOD<dim, spacedim>::source_arm(const unsigned int first)
+  {
+    if (!drive_open)
+      return;
+    slod_lod_time_source src{};
+    src.src           = drive_ensemble ? ens_sources : sources;
+    src.ld_signal     = drive_cols;
+    src.sample_stride = (std::size_t)n_sources * drive_cols;
+    src.d_signal      = d_signal + (std::size_t)first * src.sample_stride;
+    src.n_samples     = (int)(drive_samples_open - first);
+    check(slod_lod_time_source_arm(handle, &src), "slod_lod_time_source_arm");
+  }
+
+  template <int dim, int spacedim>
+  const double *LOD<dim, spacedim>::source_load(const double *d_load, double *d_out)
+  {
+    if (!drive_open)
+      return d_load;
+    if (drive_ensemble)
+      check(slod_lod_inject_ensemble(handle, ens_sources, 0, (int)drive_cols, d_signal, drive_cols, d_load, drive_cols, d_out, drive_cols,
+                                     nullptr),
+            "slod_lod_inject_ensemble");
+    else
+      check(slod_lod_inject_multi(handle, sources, d_signal, drive_cols, (int)drive_cols, d_load, drive_cols, d_out, drive_cols, nullptr),
+            "slod_lod_inject_multi");
+    return d_out;
   }
 
   template <int dim, int spacedim>
@@ -841,12 +923,14 @@ namespace slod
     if (hipMemset(d_u, 0, n_coarse * K * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
       throw std::runtime_error("solve_heat_ensemble: clearing the initial state failed");
     ens_heat_error.assign((std::size_t)n_steps * K, slod_error_norms{});
+    source_open(n_steps + 1, (unsigned int)K, true);
     record_open(n_steps, (unsigned int)K, false, true);
     record_state(0, d_u, nullptr);
     for (unsigned int step = 0; step < n_steps; ++step)
       {
+        source_arm(step);
         check(slod_lod_theta_steps_ensemble_direct(handle, f, d_ens_values, (std::size_t)K, d_ens_cols, dt, theta, 1, K, d_u,
-                                                   (std::size_t)K, d_ens_rhs, (std::size_t)K, 0),
+                                                   (std::size_t)K, own_load(d_ens_rhs), (std::size_t)K, 0),
               "slod_lod_theta_steps_ensemble_direct");
         record_state(step + 1, d_u, nullptr);
         check(slod_lod_reconstruct_ensemble(handle, d_ens_basis, ens_stride, ens_member_stride, K, d_u, (std::size_t)K, d_fine, fine_size,
@@ -858,6 +942,7 @@ namespace slod
                 "slod_compute_error_norms");
       }
     record_close();
+    drive_open = false;
     ensemble_moment_norms(d_fine, d_mean, d_var, ens_heat_mean_norms, ens_heat_dev_norms);
   }
 
@@ -887,12 +972,16 @@ namespace slod
     std::vector<double> b(n_coarse * K), u(n_coarse * K);
     if (hipMemcpy(b.data(), d_ens_rhs, b.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
       throw std::runtime_error("solve_wave_ensemble: download of the loads failed");
+    if (load_quiet)
+      b.assign(b.size(), 0.0);
+    source_open(n_steps + 1, (unsigned int)K, true);
+    const double *d_b0 = source_load(own_load(d_ens_rhs), drive_open ? device_alloc<double>(n_coarse * K) : nullptr);
     // the factors of M for the initial acceleration, then those of S = M + beta dt^2 A (no damping) for every step
     slod_lod_factor *f_M = nullptr, *f_S = nullptr;
     check(slod_lod_factor_create_ensemble(handle, d_ens_mass, ld, K, d_ens_cols, nullptr, &f_M), "slod_lod_factor_create_ensemble");
     factors.push_back(f_M);
     check(slod_lod_newmark_accel_ensemble_direct(handle, f_M, d_ens_sym, ld, d_ens_mass, ld, d_ens_cols, 0.0, 0.0, K, d_u, ld, d_v, ld,
-                                                 d_ens_rhs, ld, d_a, ld),
+                                                 d_b0, ld, d_a, ld),
           "slod_lod_newmark_accel_ensemble_direct");
     check(slod_lod_matrix_combine_ensemble(handle, 1.0, d_ens_mass, ld, beta * dt * dt, d_ens_sym, ld, K, d_ens_shifted, ld, nullptr),
           "slod_lod_matrix_combine_ensemble");
@@ -907,8 +996,10 @@ namespace slod
     record_state(0, d_u, d_v);
     for (unsigned int step = 0; step < n_steps; ++step)
       {
+        source_arm(step);
         check(slod_lod_newmark_steps_ensemble_direct(handle, f_S, d_ens_sym, ld, d_ens_mass, ld, d_ens_cols, dt, beta, gamma, 0.0, 0.0, 1,
-                                                     K, d_u, ld, d_v, ld, d_a, ld, d_ens_rhs, ld, 0, kinetic.data(), potential.data()),
+                                                     K, d_u, ld, d_v, ld, d_a, ld, own_load(d_ens_rhs), ld, 0, kinetic.data(),
+                                                     potential.data()),
               "slod_lod_newmark_steps_ensemble_direct");
         record_state(step + 1, d_u, d_v);
         if (hipMemcpy(u.data(), d_u, u.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
@@ -931,6 +1022,7 @@ namespace slod
     check(slod_lod_reconstruct_ensemble(handle, d_ens_basis, ens_stride, ens_member_stride, K, d_u, ld, d_fine, fine_size, nullptr),
           "slod_lod_reconstruct_ensemble");
     record_close();
+    drive_open = false;
     ensemble_moment_norms(d_fine, d_mean, d_var, ens_wave_mean_norms, ens_wave_dev_norms);
   }
 
@@ -1141,19 +1233,26 @@ namespace slod
         if (hipDeviceSynchronize() != hipSuccess)
           throw std::runtime_error("solve_heat: forming S failed");
         slod_lod_factor *f = factor_lod_matrix(d_lod_shifted);
+        source_open(n_steps + 1, 1, false);
         record_open(n_steps, 1, false, false);
         record_arm(n_steps);
-        check(slod_lod_theta_steps_direct(handle, f, d_lod_values, d_lod_cols, dt, theta, (int)n_steps, 1, d_heat_u, 1, d_heat_rhs, 1, 0),
+        source_arm(0);
+        check(slod_lod_theta_steps_direct(handle, f, d_lod_values, d_lod_cols, dt, theta, (int)n_steps, 1, d_heat_u, 1,
+                                          own_load(d_heat_rhs), 1, 0),
               "slod_lod_theta_steps_direct");
         record_close();
+        drive_open = false;
         return;
       }
+    source_open(n_steps + 1, 1, false);
     record_open(n_steps, 1, false, false);
     record_arm(n_steps);
-    check(slod_lod_theta_steps(handle, d_lod_values, d_lod_mass, d_lod_cols, dt, theta, (int)n_steps, 1, d_heat_u, 1, d_heat_rhs, 1,
+    source_arm(0);
+    check(slod_lod_theta_steps(handle, d_lod_values, d_lod_mass, d_lod_cols, dt, theta, (int)n_steps, 1, d_heat_u, 1, own_load(d_heat_rhs), 1,
                                0, lod_rel_tol, lod_max_iterations, lod_heat_iterations.data(), lod_heat_residuals.data()),
           "slod_lod_theta_steps");
     record_close();
+    drive_open = false;
   }
 
   template <int dim, int spacedim>
@@ -1328,12 +1427,18 @@ namespace slod
     std::vector<double> b(n_coarse), u(n_coarse);
     if (hipMemcpy(b.data(), d_b, n_coarse * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
       throw std::runtime_error("solve_wave: download of the load failed");
+    if (load_quiet)
+      b.assign(n_coarse, 0.0);
+    source_open(n_steps + 1, 1, false);
+    if (drive_open && !d_wave_load0)
+      d_wave_load0 = device_alloc<double>(n_coarse);
+    const double *d_b0 = source_load(own_load(d_b), d_wave_load0); // b^0 of the initial acceleration
     slod_lod_factor *f_S = nullptr;
     if (direct)
       {
         // the factor of M for the initial acceleration, then that of S = M + beta dt^2 A (no damping) for every step
         check(slod_lod_newmark_accel_direct(handle, factor_lod_matrix(d_lod_mass), d_lod_sym, d_lod_mass, d_lod_cols, 0.0, 0.0, 1, d_u,
-                                            1, d_v, 1, d_b, 1, d_a, 1),
+                                            1, d_v, 1, d_b0, 1, d_a, 1),
               "slod_lod_newmark_accel_direct");
         if (!d_lod_shifted)
           d_lod_shifted = device_alloc<double>((std::size_t)n_patches * cap * spacedim * spacedim);
@@ -1345,7 +1450,7 @@ namespace slod
       }
     else
       {
-        const int rc = slod_lod_newmark_accel(handle, d_lod_sym, d_lod_mass, d_lod_cols, 0.0, 0.0, 1, d_u, 1, d_v, 1, d_b, 1, d_a, 1,
+        const int rc = slod_lod_newmark_accel(handle, d_lod_sym, d_lod_mass, d_lod_cols, 0.0, 0.0, 1, d_u, 1, d_v, 1, d_b0, 1, d_a, 1,
                                               lod_rel_tol, lod_max_iterations, nullptr, nullptr);
         check(rc < 0 ? rc : 0, "slod_lod_newmark_accel");
       }
@@ -1359,14 +1464,15 @@ namespace slod
     for (unsigned int k = 0; k < n_steps; ++k)
       {
         double    kinetic[2], potential[2];
+        source_arm(k);
         if (direct)
           check(slod_lod_newmark_steps_direct(handle, f_S, d_lod_sym, d_lod_mass, d_lod_cols, dt, beta, gamma, 0.0, 0.0, 1, 1, d_u, 1,
-                                              d_v, 1, d_a, 1, d_b, 1, 0, kinetic, potential),
+                                              d_v, 1, d_a, 1, own_load(d_b), 1, 0, kinetic, potential),
                 "slod_lod_newmark_steps_direct");
         else
           {
             const int its = slod_lod_newmark_steps(handle, d_lod_sym, d_lod_mass, d_lod_cols, dt, beta, gamma, 0.0, 0.0, 1, 1, d_u, 1,
-                                                   d_v, 1, d_a, 1, d_b, 1, 0, lod_rel_tol, lod_max_iterations,
+                                                   d_v, 1, d_a, 1, own_load(d_b), 1, 0, lod_rel_tol, lod_max_iterations,
                                                    &lod_wave_iterations[k], &lod_wave_residuals[k], kinetic, potential);
             check(its < 0 ? its : 0, "slod_lod_newmark_steps");
           }
@@ -1386,6 +1492,7 @@ namespace slod
         lod_wave_work[k + 1] = work;
       }
     record_close();
+    drive_open = false;
     check(slod_lod_reconstruct(handle, d_basis, basis_stride, d_u, d_wave_fine, nullptr), "slod_lod_reconstruct");
     check(slod_compute_error_norms(handle, 0, d_wave_fine, nullptr, nullptr, nullptr, &wave_norms, nullptr),
           "slod_compute_error_norms");
@@ -1431,11 +1538,15 @@ namespace slod
     lod_heat_iterations.assign(n_steps, 0);
     lod_heat_residuals.assign(n_steps, 0.0);
     slod_lod_factor *f = factor_lod_irk(scheme, 1, dt);
+    source_open(2 * n_steps, 1, false);
     record_open(n_steps, 1, false, false);
     record_arm(n_steps);
-    check(slod_lod_irk_heat_steps_direct(handle, f, 0, scheme, d_lod_sym, d_lod_cols, dt, (int)n_steps, 1, d_heat_u, 1, d_heat_rhs, 1, 0),
+    source_arm(0);
+    check(slod_lod_irk_heat_steps_direct(handle, f, 0, scheme, d_lod_sym, d_lod_cols, dt, (int)n_steps, 1, d_heat_u, 1,
+                                         own_load(d_heat_rhs), 1, 0),
           "slod_lod_irk_heat_steps_direct");
     record_close();
+    drive_open = false;
   }
 
   template <int dim, int spacedim>
@@ -1466,6 +1577,9 @@ namespace slod
     std::vector<double> b(n_coarse), u(n_coarse);
     if (hipMemcpy(b.data(), d_b, n_coarse * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
       throw std::runtime_error("solve_wave_irk: download of the load failed");
+    if (load_quiet)
+      b.assign(n_coarse, 0.0);
+    source_open(2 * n_steps, 1, false);
     slod_lod_factor *f = factor_lod_irk(scheme, 2, dt);
     lod_wave_iterations.assign(n_steps, 0);
     lod_wave_residuals.assign(n_steps, 0.0);
@@ -1477,8 +1591,9 @@ namespace slod
     for (unsigned int k = 0; k < n_steps; ++k)
       {
         double kinetic[2], potential[2];
+        source_arm(2 * k);
         check(slod_lod_irk_wave_steps_direct(handle, f, 0, scheme, d_lod_sym, d_lod_mass, d_lod_cols, dt, 0.0, 0.0, 1, 1, d_u, 1, d_v, 1,
-                                             d_b, 1, 0, kinetic, potential),
+                                             own_load(d_b), 1, 0, kinetic, potential),
               "slod_lod_irk_wave_steps_direct");
         record_state(k + 1, d_u, d_v);
         if (hipMemcpy(u.data(), d_u, n_coarse * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
@@ -1496,6 +1611,7 @@ namespace slod
         lod_wave_work[k + 1] = work;
       }
     record_close();
+    drive_open = false;
     check(slod_lod_reconstruct(handle, d_basis, basis_stride, d_u, d_wave_fine, nullptr), "slod_lod_reconstruct");
     check(slod_compute_error_norms(handle, 0, d_wave_fine, nullptr, nullptr, nullptr, &wave_norms, nullptr),
           "slod_compute_error_norms");
@@ -1542,11 +1658,14 @@ namespace slod
     if (hipMemset(d_u, 0, n_coarse * K * sizeof(double)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
       throw std::runtime_error("solve_heat_irk_ensemble: clearing the initial state failed");
     ens_heat_error.assign((std::size_t)n_steps * K, slod_error_norms{});
+    source_open(2 * n_steps, (unsigned int)K, true);
     record_open(n_steps, (unsigned int)K, false, true);
     record_state(0, d_u, nullptr);
     for (unsigned int step = 0; step < n_steps; ++step)
       {
-        check(slod_lod_irk_heat_steps_ensemble_direct(handle, f, 0, scheme, d_ens_sym, ld, d_ens_cols, dt, 1, K, d_u, ld, d_ens_rhs, ld, 0),
+        source_arm(2 * step);
+        check(slod_lod_irk_heat_steps_ensemble_direct(handle, f, 0, scheme, d_ens_sym, ld, d_ens_cols, dt, 1, K, d_u, ld,
+                                                      own_load(d_ens_rhs), ld, 0),
               "slod_lod_irk_heat_steps_ensemble_direct");
         record_state(step + 1, d_u, nullptr);
         check(slod_lod_reconstruct_ensemble(handle, d_ens_basis, ens_stride, ens_member_stride, K, d_u, ld, d_fine, fine_size, nullptr),
@@ -1557,6 +1676,7 @@ namespace slod
                 "slod_compute_error_norms");
       }
     record_close();
+    drive_open = false;
     ensemble_moment_norms(d_fine, d_mean, d_var, ens_heat_mean_norms, ens_heat_dev_norms);
   }
 
@@ -1578,6 +1698,9 @@ namespace slod
     std::vector<double> b(n_coarse * K), u(n_coarse * K);
     if (hipMemcpy(b.data(), d_ens_rhs, b.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
       throw std::runtime_error("solve_wave_irk_ensemble: download of the loads failed");
+    if (load_quiet)
+      b.assign(b.size(), 0.0);
+    source_open(2 * n_steps, (unsigned int)K, true);
     ens_wave_kinetic.assign((std::size_t)(n_steps + 1) * K, 0.0);
     ens_wave_potential.assign((std::size_t)(n_steps + 1) * K, 0.0);
     ens_wave_work.assign((std::size_t)(n_steps + 1) * K, 0.0);
@@ -1586,8 +1709,9 @@ namespace slod
     record_state(0, d_u, d_v);
     for (unsigned int step = 0; step < n_steps; ++step)
       {
+        source_arm(2 * step);
         check(slod_lod_irk_wave_steps_ensemble_direct(handle, f, 0, scheme, d_ens_sym, ld, d_ens_mass, ld, d_ens_cols, dt, 0.0, 0.0, 1, K,
-                                                      d_u, ld, d_v, ld, d_ens_rhs, ld, 0, kinetic.data(), potential.data()),
+                                                      d_u, ld, d_v, ld, own_load(d_ens_rhs), ld, 0, kinetic.data(), potential.data()),
               "slod_lod_irk_wave_steps_ensemble_direct");
         record_state(step + 1, d_u, d_v);
         if (hipMemcpy(u.data(), d_u, u.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
@@ -1608,6 +1732,7 @@ namespace slod
           }
       }
     record_close();
+    drive_open = false;
     check(slod_lod_reconstruct_ensemble(handle, d_ens_basis, ens_stride, ens_member_stride, K, d_u, ld, d_fine, fine_size, nullptr),
           "slod_lod_reconstruct_ensemble");
     ensemble_moment_norms(d_fine, d_mean, d_var, ens_wave_mean_norms, ens_wave_dev_norms);

@@ -283,6 +283,22 @@ namespace slod
     unsigned int trace_columns() const { return trace_cols; }
     unsigned int trace_receivers() const { return n_receivers; }
     unsigned int trace_every() const { return trace_every_; }
+    // Sources: unit point forces in component `component` at the points (x, y), four bilinear terms each
+    // (slod_lod_sources_create on the receivers object of the same points, which is dropped afterwards; with ensemble =
+    // true on the members' slabs).  drive_next(signal, n_samples) makes the NEXT solve_heat* / solve_wave* call add
+    // O^T g(t) to its load: signal[j * n_sources + q] is sample j of source q, the same for every column; the theta and
+    // Newmark loops read the samples 0 .. n_steps (b^k = sample k), the IRK loops the samples 2 k + i of stage i of step k.
+    // solve_heat and solve_heat_irk arm the library's source once (slod_lod_time_source_arm); the six loops that call the
+    // stepper once per step arm it before every call with the signal advanced by that step's samples, and the wave loops
+    // form the load of the initial acceleration with slod_lod_inject_*.  quiet_load(): the loops drop the problem's own
+    // load, so that a driven run is the response of the sources alone.
+    void create_sources(const std::vector<ReceiverPoint> &points, const bool ensemble = false);
+    void drive_next(const std::vector<double> &signal, const unsigned int n_samples)
+    {
+      drive_signal  = signal;
+      drive_samples = n_samples;
+    }
+    void quiet_load(const bool quiet = true) { load_quiet = quiet; }
     // solve_harmonic for all members at once, after assemble_mass_matrix_ensemble(): the symmetrised stiffness of every
     // member (slod_lod_matrix_symmetrize_ensemble), the loads of solve_ensemble() (slod_lod_rhs_ensemble, f = 1) and one
     // slod_lod_harmonic_response_ensemble call for all (frequency, member) pairs.  Entry [frequency * n_members + member] of
@@ -469,6 +485,22 @@ namespace slod
     void record_arm(const unsigned int n_steps);
     void record_state(const unsigned int steps_done, const double *d_u, const double *d_v);
     void record_close();
+    // create_sources / drive_next / quiet_load.  make_receivers: the receivers object of a set of points.  source_open: when
+    // a signal is pending (one-shot), it goes to the device replicated over `columns` columns, checked against the
+    // `needed` samples of the loop, and true; source_arm: before a stepper call, from sample `first` on; source_load: the
+    // load d_load + O^T g(sample 0) of the initial acceleration in d_out (d_load when nothing is open); own_load: d_load or,
+    // quiet, NULL.
+    slod_lod_sources   *sources = nullptr, *ens_sources = nullptr;
+    unsigned int        n_sources = 0, drive_samples = 0, drive_samples_open = 0, drive_cols = 0;
+    bool                drive_open = false, drive_ensemble = false, load_quiet = false;
+    std::vector<double> drive_signal;
+    double             *d_signal = nullptr, *d_wave_load0 = nullptr;
+    std::size_t         d_signal_size = 0;
+    slod_lod_receivers *make_receivers(const std::vector<ReceiverPoint> &points, const bool ensemble, const char *who);
+    bool          source_open(const unsigned int needed, const unsigned int columns, const bool ensemble);
+    void          source_arm(const unsigned int first);
+    const double *source_load(const double *d_load, double *d_out);
+    const double *own_load(const double *d_load) const { return load_quiet ? nullptr : d_load; }
 
     void check(const int status, const char *what) const;
     std::vector<Point<dim>> fine_quadrature_points() const;

@@ -77,6 +77,19 @@ class TimeRecord(C.Structure):
 
 RECORD_U, RECORD_V = 1, 2   # enum slod_record_what
 
+
+class SourcesInfo(C.Structure):
+    """slod_lod_sources_info: sources, members, touched coarse rows, entries per member, device bytes."""
+    _fields_ = [("n_sources", C.c_int32), ("n_members", C.c_int32), ("n_rows_touched", C.c_uint32), ("nnz", C.c_uint64),
+                ("bytes", C.c_uint64)]
+
+
+class TimeSource(C.Structure):
+    """slod_lod_time_source: what drives the next stepper call on the handle (slod_lod_time_source_arm)."""
+    _fields_ = [("src", C.c_void_p), ("d_signal", C.c_void_p), ("ld_signal", C.c_size_t), ("sample_stride", C.c_size_t),
+                ("n_samples", C.c_int)]
+
+
 _lib = None
 
 
@@ -243,6 +256,13 @@ def load():
     lib.slod_lod_observe_multi.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp]
     lib.slod_lod_observe_ensemble.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp]
     lib.slod_lod_time_record_arm.argtypes = [vp, C.POINTER(TimeRecord)]
+    lib.slod_lod_sources_create.argtypes = [vp, vp, C.POINTER(vp)]
+    lib.slod_lod_sources_get_info.argtypes = [vp, C.POINTER(SourcesInfo)]
+    lib.slod_lod_sources_destroy.argtypes = [vp]
+    lib.slod_lod_sources_destroy.restype = None
+    lib.slod_lod_inject_multi.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp]
+    lib.slod_lod_inject_ensemble.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp]
+    lib.slod_lod_time_source_arm.argtypes = [vp, C.POINTER(TimeSource)]
     lib.slod_update_coefficient.argtypes = [vp, C.c_uint32, C.c_int, vp, C.c_int, C.c_size_t, C.c_int, vp]
     lib.slod_dirty_patches.argtypes = [vp, vp, u32p, C.c_size_t]
     lib.slod_plan_create_dirty.argtypes = [vp, C.c_uint32, vp, C.POINTER(vp)]
@@ -606,6 +626,52 @@ class Receivers:
         if self.r:
             self.lib.slod_lod_receivers_destroy(self.r)
             self.r = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ricker(t, f0, t0, amp=1.0):
+    """The Ricker wavelet amp (1 - 2 a) exp(-a), a = (pi f0 (t - t0))^2, at the times t: numpy float64, host only."""
+    a = (np.pi * np.float64(f0) * (np.asarray(t, dtype=np.float64) - np.float64(t0))) ** 2
+    return np.float64(amp) * (1.0 - 2.0 * a) * np.exp(-a)
+
+
+class Sources:
+    """slod_lod_sources: a receivers object applied transposed, b = base + O^T g; source q is receiver q of `recv`, which may
+    be closed afterwards.  .info (n_sources, n_members, n_rows_touched, nnz, bytes), .inject(...), .inject_ensemble(...),
+    .close()."""
+
+    def __init__(self, slod, recv):
+        self.slod, self.lib = slod, slod.lib
+        self.s = C.c_void_p()
+        slod._check(self.lib.slod_lod_sources_create(slod.h, recv.r if isinstance(recv, Receivers) else recv, C.byref(self.s)))
+        self.info = SourcesInfo()
+        slod._check(self.lib.slod_lod_sources_get_info(self.s, C.byref(self.info)))
+        self.n_src, self.n_members = self.info.n_sources, self.info.n_members
+        slod._factors.add(self)                        # the handle closes its objects before itself
+
+    def inject(self, d_g, d_b, n_rhs=1, d_base=None, ld_g=None, ld_base=None, ld_b=None, stream=None):
+        """b[r, c] = base[r, c] + (O^T g_c)_r, g of source q at d_g[q * ld_g + c]; d_base None: +0.0; d_b may be d_base.  An
+        object of one member.  Asynchronous."""
+        self.slod._check(self.lib.slod_lod_inject_multi(self.slod.h, self.s, d_g, n_rhs if ld_g is None else ld_g, n_rhs, d_base,
+                                                        n_rhs if ld_base is None else ld_base, d_b, n_rhs if ld_b is None else ld_b,
+                                                        stream))
+
+    def inject_ensemble(self, d_g, d_b, n_members=None, first_member=0, d_base=None, ld_g=None, ld_base=None, ld_b=None, stream=None):
+        """Column m with the values of member first_member + m (n_members defaults to the rest of the object)."""
+        K = self.n_members - first_member if n_members is None else n_members
+        self.slod._check(self.lib.slod_lod_inject_ensemble(self.slod.h, self.s, first_member, K, d_g, K if ld_g is None else ld_g,
+                                                           d_base, K if ld_base is None else ld_base, d_b,
+                                                           K if ld_b is None else ld_b, stream))
+
+    def close(self):
+        if self.s:
+            self.lib.slod_lod_sources_destroy(self.s)
+            self.s = None
 
     def __del__(self):
         try:
@@ -1048,6 +1114,25 @@ class Slod:
                          nq * recv.n_recv * ld if record_stride is None else record_stride, capacity)
         self._check(self.lib.slod_lod_time_record_arm(self.h, C.byref(rec)))
         return rec
+
+    # ---- sources: point forces with a time signal, as a product and as a load of the time loops ----
+    def lod_sources(self, recv):
+        """The sources of a Receivers object (source q is receiver q): a Sources object."""
+        return Sources(self, recv)
+
+    def lod_time_source(self, src, signal_ptr, n_samples=0, ld_signal=None, sample_stride=None, columns=1):
+        """Arms the source of the NEXT stepper call on this handle (one-shot): its load is d_load + O^T g, sample j, source q,
+        column c at signal_ptr[j * sample_stride + q * ld_signal + c] doubles; theta and Newmark loops read the samples
+        0 .. n_steps, IRK loops the samples 2 k + i of stage i of step k.  ld_signal defaults to `columns` (n_rhs or n_members
+        of the stepper), sample_stride to n_sources * ld_signal.  src=None disarms."""
+        if src is None:
+            self._check(self.lib.slod_lod_time_source_arm(self.h, None))
+            return
+        ld = columns if ld_signal is None else ld_signal
+        ts = TimeSource(src.s if isinstance(src, Sources) else src, signal_ptr, ld,
+                        src.n_src * ld if sample_stride is None else sample_stride, n_samples)
+        self._check(self.lib.slod_lod_time_source_arm(self.h, C.byref(ts)))
+        return ts
 
     # ---- the LOD systems of a coefficient ensemble: member k = problem k of the handle = column k of the coarse
     # multi-vectors; matrix values member-minor, entry e of member k at [e * ld_m + k] (include/slod.h) ----

@@ -1150,7 +1150,7 @@ int slod_lod_irk_wave_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S
  * + 1; the receivers of another handle; a member count that is not 1 for a single-problem stepper or not n_members for an
  * ensemble stepper (whose column m reads member m of the object).  slod_lod_time_record_arm itself refuses a NULL handle
  * and a NULL recv inside a non-NULL record.
- * Not built: time signals that scale a load inside the loop (sources); full-field snapshots every M steps; merging equal
+ * Not built: time signals that scale a load inside the loop (sources) came later, see the next block; full-field snapshots every M steps; merging equal
  * columns of a row; receivers refreshed after slod_update_coefficient; records from the eigen and harmonic calls; members
  * spread over ranks; the deal.II adapter. */
 typedef struct slod_lod_receivers slod_lod_receivers;
@@ -1186,6 +1186,73 @@ typedef struct
   int     capacity;      /* records d_trace can hold */
 } slod_lod_time_record;
 int slod_lod_time_record_arm(slod_handle *h, const slod_lod_time_record *rec /* NULL disarms */);
+
+/* ---- sources: point forces with a time signal, as a product on the LOD space and as a load of the time loops ----
+ * The other half of a seismogram.  A point force w e(node, c) has the coarse load C^T w e, which is the row of O = W C a
+ * receiver at that term has: a set of sources is a receivers object applied transposed,  b = b_base + O^T g,  and a time
+ * loop that knows the sources needs a wavelet per source and column in place of (n_steps + 1) n ld_load doubles of loads.
+ * THE OBJECT.  slod_lod_sources_create takes a receivers object of the same handle; source q is receiver q, with its
+ * terms, weights and members.  It reads the rows back, builds the transposed index on the host (the touched coarse rows,
+ * ascending; per touched row the entries e with cols[e] = r in ascending e, so by source, term and row order; the source
+ * q(e) of each entry; an int32 map coarse row -> slot, -1 if untouched, of num_patches s words) and copies the values
+ * into that order, member-minor, with one gather kernel: the words are those of the receivers object.  The object owns
+ * its copy; the receivers may be destroyed afterwards.  Synchronises.  Not refreshed after slod_update_coefficient: create
+ * again.  SLOD_ERR_ARGUMENT: a NULL handle, recv or out; the receivers of another handle.
+ * THE PRODUCT.  b of coarse row r, column c at d_b[r ld_b + c]; g of source q, column c at d_g[q ld_g + c]; d_base in the
+ * layout of d_b, NULL = +0.0.  slod_lod_inject_multi takes an object of one member; slod_lod_inject_ensemble reads for
+ * column m the values of member first_member + m.  One thread per (coarse row, column): an untouched row writes its base
+ * word (any word, a NaN too, bit for bit); a touched row runs one chain acc = fma(value_e, g[q(e) ld_g + c], acc) from the
+ * base word over its entries in the stored order.  A one-term source of weight 1 and signal 1 leaves in the touched rows
+ * the words slod_lod_rhs_multi gives for the fine field e(node, c).  The words of a column depend on the object, the
+ * member, that column of g and that column of the base alone.  d_b may be d_base.  Entries c >= n inside an ld are neither
+ * read nor written.  Asynchronous, no allocation, no atomics.  SLOD_ERR_ARGUMENT: a NULL handle, sources or d_g / d_b;
+ * n < 1; ld_g, ld_b or (with a base) ld_base below the columns; the sources of another handle; an object of several
+ * members given to slod_lod_inject_multi; members outside the object.
+ * THE ARMED SOURCE.  slod_lod_time_source_arm leaves on the handle what drives the NEXT stepper call: its load is d_load
+ * (as before: NULL = zero, stride 0 = constant) PLUS O^T g(t), with the sample of g taken as the loads are: the theta
+ * loops use sample k for b^k, k = 0 .. n_steps (n_samples >= n_steps + 1); Newmark uses sample k + 1 for step k (the same
+ * bound); IRK uses sample 2 k + i for stage i of step k (n_samples >= 2 n_steps).  The armed loop carves two load vectors
+ * of n x columns more (Newmark: one) out of its one workspace and queues one product per step on its stream ahead of the
+ * right-hand side, which reads them in place of d_load; its words are those of an un-armed call on loads materialised by
+ * slod_lod_inject_*.  Nothing else is allocated, nothing is read back, the loops on a factor stay one queue-and-wait.
+ * An ensemble stepper reads member m of the object for column m, whatever first_member of its factor.  A loop without a
+ * source runs the code and has the bits it had before.
+ * ONE-SHOT, as the record: the next call of one of the ten steppers named there takes source and record off the handle as
+ * its first action, whatever it returns; every other call leaves them (the slod_lod_newmark_accel calls too: their load at
+ * t_0 is the caller's, slod_lod_inject_* forms it); s = NULL disarms, and so does slod_lod_sources_destroy of the sources
+ * it names.  The struct is copied; d_signal must live until the stepper has returned.
+ * A stepper with a source refuses with SLOD_ERR_ARGUMENT, before any device work, after its own checks and the record's
+ * and in this order, "<call>: source: ...": a NULL d_signal; an ld_signal below the columns of the call; sample_stride /
+ * n_sources < ld_signal; n_samples below the bound above; the sources of another handle; a member count that is not 1 for
+ * a single-problem stepper or not n_members for an ensemble stepper.  slod_lod_time_source_arm itself refuses a NULL
+ * handle and a NULL src inside a non-NULL struct.
+ * Not built: sources in the slod_lod_newmark_accel, harmonic and eigen calls; a signal interpolated between samples;
+ * sources refreshed after slod_update_coefficient; moving sources; members spread over ranks; the deal.II adapter. */
+typedef struct slod_lod_sources slod_lod_sources;
+typedef struct
+{
+  int32_t  n_sources, n_members;
+  uint32_t n_rows_touched; /* coarse rows with an entry */
+  uint64_t nnz;            /* entries, per member */
+  uint64_t bytes;          /* device memory of the object */
+} slod_lod_sources_info;
+int slod_lod_sources_create(slod_handle *h, const slod_lod_receivers *recv, slod_lod_sources **out);
+int slod_lod_sources_get_info(const slod_lod_sources *src, slod_lod_sources_info *info);
+void slod_lod_sources_destroy(slod_lod_sources *src);
+int slod_lod_inject_multi(slod_handle *h, const slod_lod_sources *src, const double *d_g, size_t ld_g, int n_rhs,
+                          const double *d_base /* NULL = +0.0 */, size_t ld_base, double *d_b, size_t ld_b, void *hip_stream);
+int slod_lod_inject_ensemble(slod_handle *h, const slod_lod_sources *src, int first_member, int n_members, const double *d_g,
+                             size_t ld_g, const double *d_base /* NULL = +0.0 */, size_t ld_base, double *d_b, size_t ld_b,
+                             void *hip_stream);
+typedef struct
+{
+  const slod_lod_sources *src;
+  const double *d_signal; /* DEVICE: sample j, source q, column c at d_signal[j sample_stride + q ld_signal + c] */
+  size_t ld_signal;       /* >= columns of the stepper call */
+  size_t sample_stride;   /* >= n_sources * ld_signal */
+  int    n_samples;
+} slod_lod_time_source;
+int slod_lod_time_source_arm(slod_handle *h, const slod_lod_time_source *s /* NULL disarms */);
 
 /* ---- refresh after a local coefficient change ----------------------------------------------
  * Every entry point above takes the coefficient as fixed for the life of a basis (the reference does too: one
