@@ -3,6 +3,7 @@
 //                  [--heat STEPS DT] [--eigs K] [--shift SIGMA] [--wave STEPS DT] [--direct] [--irk gauss|radau] [--ensemble K] [--perturb K]
 //                  [--reuse-factor] [--precond-member J]
 //                  [--member K] [--ldl] [--harmonic K W0 W1 [--damping DM DS]] (with --ensemble: per member)
+//                  [--sponge WIDTH SIGMA_MAX]
 //                  [--receiver X Y [C]]... [--record-every M]
 //                  [--source X Y [C]]... [--ricker F0 T0 [AMP]] [--quiet-load]
 // prints the reference's patch summary (LOD.cc:237-242) and a digest of the basis; with a
@@ -47,6 +48,11 @@
 // = .., power = ..", the numbers of the "harmonic J" line of a --member M --harmonic run; per frequency "harmonic J amplitude
 // over the ensemble of K: mean = .., standard deviation = .."; then for the frequency with the largest mean amplitude the L2
 // norms of the mean and of the standard deviation of the real and of the imaginary part on the fine grid.
+// --sponge WIDTH SIGMA_MAX (with --wave STEPS DT [--direct] [--irk gauss|radau] and with --harmonic; not with --ensemble): a
+// sponge layer, the damping matrix D = C^T M_sigma C with sigma = SIGMA_MAX max(0, 1 - d / WIDTH)^2 per fine element (d the
+// distance of its centre from the rim), joins the model: M u'' + D u' + A u = C^T f, and S(omega) gains i omega D.  Prints
+// "sponge: width = .., sigma_max = .., zero coarse rows of D = .." ahead of the loop; the per-step and per-frequency lines
+// keep their format, and the harmonic power includes u^H D u.
 // --heat STEPS DT --irk gauss|radau, --wave STEPS DT --irk gauss|radau: the time loop by a two-stage implicit Runge-Kutta
 // scheme (Gauss-Legendre, order 4; Radau IIA, order 3, L-stable) with one complex solve per step on the complex LDL^T of its
 // step matrix (slod_lod_irk_coefficients, slod_lod_factor_create_zldl, slod_lod_irk_heat_steps_direct /
@@ -223,6 +229,7 @@ int main(int argc_all, char **argv_all)
   bool               compare = false, coarse = false, direct = false, ldl = false;
   int                n_harmonic = 0;
   double             harmonic_w0 = 0.0, harmonic_w1 = 0.0, damp_mass = 0.0, damp_stiff = 0.0;
+  double             sponge_width = 0.0, sponge_max = 0.0; // --sponge WIDTH SIGMA_MAX
   int                n_loads = 0, heat_steps = 0, n_eigs = 0, wave_steps = 0, n_members = 0, n_perturb = 0, member = 0, precond_member = -1;
   bool               reuse_factor = false;
   double             heat_dt = 0.0, wave_dt = 0.0, shift = 0.0;
@@ -323,6 +330,11 @@ int main(int argc_all, char **argv_all)
         damp_mass  = std::atof(argv_all[++i]);
         damp_stiff = std::atof(argv_all[++i]);
       }
+    else if (i > 0 && !std::strcmp(argv_all[i], "--sponge") && i + 2 < argc_all)
+      {
+        sponge_width = std::atof(argv_all[++i]);
+        sponge_max   = std::atof(argv_all[++i]);
+      }
     else if (i > 0 && !std::strcmp(argv_all[i], "--ensemble") && i + 1 < argc_all)
       n_members = std::atoi(argv_all[++i]);
     else if (i > 0 && !std::strcmp(argv_all[i], "--member") && i + 1 < argc_all)
@@ -349,6 +361,11 @@ int main(int argc_all, char **argv_all)
         throw std::runtime_error("--source X Y [C] and --ricker F0 T0 [AMP] come together");
       if (!sources.empty() && heat_steps <= 0 && wave_steps <= 0)
         throw std::runtime_error("--source drives a time loop: give --heat STEPS DT or --wave STEPS DT");
+      const bool sponge = sponge_width != 0.0 || sponge_max != 0.0;
+      if (sponge && (!(sponge_width > 0.0) || !(sponge_max >= 0.0)))
+        throw std::runtime_error("--sponge takes WIDTH > 0 and SIGMA_MAX >= 0");
+      if (sponge && ((wave_steps <= 0 && n_harmonic <= 0) || n_members > 0))
+        throw std::runtime_error("--sponge damps --wave STEPS DT [--direct] [--irk gauss|radau] or --harmonic K W0 W1, without --ensemble");
       LODParameters<2, 1> par;
       par.n_global_refinements  = argc > 1 ? std::atoi(argv[1]) : 3;
       par.n_subdivisions        = argc > 2 ? std::atoi(argv[2]) : 4;
@@ -383,6 +400,22 @@ int main(int argc_all, char **argv_all)
         for (const double t : times)
           signal.insert(signal.end(), sources.size(), ricker(t, ricker_f0, ricker_t0, ricker_amp));
         problem.drive_next(signal, (unsigned int)times.size());
+      };
+      // the sponge layer sigma = SIGMA_MAX max(0, 1 - d / WIDTH)^2 per fine element, d the distance of its centre from the rim
+      auto set_sponge = [&](Problem &pr) {
+        const std::size_t   NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+        std::vector<double> sigma(NE * NE);
+        for (std::size_t ey = 0; ey < NE; ++ey)
+          for (std::size_t ex = 0; ex < NE; ++ex)
+            {
+              const double x = ((double)ex + 0.5) / (double)NE, y = ((double)ey + 0.5) / (double)NE;
+              const double d = std::min(std::min(x, 1.0 - x), std::min(y, 1.0 - y));
+              const double r = std::max(0.0, 1.0 - d / sponge_width);
+              sigma[ey * NE + ex] = sponge_max * (r * r);
+            }
+        pr.assemble_damping_matrix(sigma);
+        std::printf("sponge: width = %g, sigma_max = %.12e, zero coarse rows of D = %u\n", sponge_width, sponge_max,
+                    pr.damping_zero_rows());
       };
       double s1 = 0, s2 = 0;
       for (const auto &p : problem.get_patches())
@@ -536,6 +569,8 @@ int main(int argc_all, char **argv_all)
             }
           if (n_members <= 0)
             drive(wave_steps, wave_dt, false);
+          if (sponge)
+            set_sponge(problem);
           if (irk >= 0)
             problem.solve_wave_irk(irk, (unsigned int)wave_steps, wave_dt);
           else
@@ -569,6 +604,8 @@ int main(int argc_all, char **argv_all)
           std::vector<double> omegas((std::size_t)n_harmonic);
           for (int k = 0; k < n_harmonic; ++k)
             omegas[k] = n_harmonic > 1 ? harmonic_w0 + k * ((harmonic_w1 - harmonic_w0) / (n_harmonic - 1)) : harmonic_w0;
+          if (sponge && wave_steps <= 0)
+            set_sponge(problem);
           problem.solve_harmonic(omegas, damp_mass, damp_stiff);
           for (int k = 0; k < n_harmonic; ++k)
             std::printf("harmonic %d: omega = %.12e, growth = %.6e, relative residual = %.6e, amplitude = %.12e, power = %.12e\n",

@@ -285,9 +285,12 @@ struct SlodZFactorBuild
 // d_a, d_b are ensemble matrices of kmat members (ld_a, ld_b; one matrix each: kmat = 1, ld = 1) and alpha, beta tables of
 // coefficient pairs: member k of the build is the flat member j = j0 + k, with the pair j / kmat on the matrices of member
 // j % kmat.  what_minor given: the error text names "<what> j / kmat, <what_minor> j % kmat", j = first + k.
+// d_c given: the third term gamma_j C of slod_lod_factor_create_zldl3, d_c and gamma laid out as d_a and alpha; the device
+// keeps gamma as [n_members][2] behind coef.
 int slod_lod_zfactor_launch(slod_handle *h, hipStream_t st, const char *who, const double *d_a, size_t ld_a, const double *d_b,
                             size_t ld_b, int kmat, const uint32_t *d_cols, const double *alpha, const double *beta, size_t j0,
-                            int n_members, SlodZFactorBuild *z);
+                            int n_members, SlodZFactorBuild *z, const double *d_c = nullptr, size_t ld_c = 1,
+                            const double *gamma = nullptr);
 int slod_lod_zfactor_finish(slod_handle *h, hipStream_t st, const char *who, const char *what, size_t first, SlodZFactorBuild *z,
                             int32_t *bad_pivot, const char *what_minor = nullptr, int kmat = 1);
 // The launch of slod_lod_factor_solve_complex(_ensemble): member first_member + k reads the rhs columns

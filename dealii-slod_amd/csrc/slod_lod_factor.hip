@@ -539,9 +539,13 @@ namespace
   // product and every sum rounded on its own.  coef: [n_members][4].  a, b: ensemble matrices of kmat members (entry t of
   // member m at a[t ld_a + m]); factor member k is the flat member j = j0 + k of a (coefficient, matrix) table and reads
   // matrix member j % kmat.  One matrix each for all members is the launch kmat = 1, ld_a = ld_b = 1.
+  // THREE: a third term gamma_k c (slod_lod_factor_create_zldl3), coef_c: [n_members][2]; the word is
+  // ((alpha_re a + beta_re b) + gamma_re c, (alpha_im a + beta_im b) + gamma_im c), rounded the same way.
+  template <bool THREE>
   __global__ __launch_bounds__(256) void k_zfactor_scatter(const SlodGrid G, int NP, int cap, int bb, int n_members,
                                                           const double *__restrict__ a, size_t ld_a, const double *__restrict__ b,
-                                                          size_t ld_b, int kmat, size_t j0, const double *__restrict__ coef,
+                                                          size_t ld_b, const double *__restrict__ c3, size_t ld_c, int kmat, size_t j0,
+                                                          const double *__restrict__ coef, const double *__restrict__ coef_c,
                                                           const uint32_t *__restrict__ cols, double *band, size_t im_band,
                                                           size_t mstride)
   {
@@ -564,8 +568,19 @@ namespace
     const double  av = a[t * ld_a + m], bv = b[t * ld_b + m];
     const double  re_a = ck[0] * av, re_b = ck[2] * bv, im_a = ck[1] * av, im_b = ck[3] * bv;
     double       *out = band + k * mstride + ((size_t)I * (bb + 1) + kb) * FT + (size_t)(c % FB) * FB + r % FB;
-    out[0]       = re_a + re_b;
-    out[im_band] = im_a + im_b;
+    if constexpr (THREE)
+      {
+        const double cv = c3[t * ld_c + m];
+        const double re_c = coef_c[2 * k] * cv, im_c = coef_c[2 * k + 1] * cv;
+        const double re = re_a + re_b, im = im_a + im_b;
+        out[0]       = re + re_c;
+        out[im_band] = im + im_c;
+      }
+    else
+      {
+        out[0]       = re_a + re_b;
+        out[im_band] = im_a + im_b;
+      }
   }
 
   // Block column K of the complex  S = L D L^T:  the launch shape, the operands and the storage of k_ldl_column, every
@@ -1035,9 +1050,10 @@ namespace
 
 // The complex factor: one allocation, per member  band (re, im), diagonal tiles (re, im), D (re, im), the two norms,
 // 1 / D (re, im), two vectors of row sums;  then the coefficients of all members, the row map and the status words.
+// d_c given: the third term gamma_k C of slod_lod_factor_create_zldl3, its coefficients behind those of the two.
 int slod_lod_zfactor_launch(slod_handle *h, hipStream_t st, const char *who, const double *d_a, size_t ld_a, const double *d_b,
                             size_t ld_b, int kmat, const uint32_t *d_cols, const double *alpha, const double *beta, size_t j0,
-                            int n_members, SlodZFactorBuild *z)
+                            int n_members, SlodZFactorBuild *z, const double *d_c, size_t ld_c, const double *gamma)
 {
   const SlodGrid   G = slod_grid_of(h);
   const int        s = G.spacedim, w = 2 * G.oversampling + 1, cap = slod_lod_row_capacity(h);
@@ -1053,7 +1069,8 @@ int slod_lod_zfactor_launch(slod_handle *h, hipStream_t st, const char *who, con
   const size_t nd = 2 * nband + 2 * ndiag + nread + 4 * npad, K = (size_t)n_members;
   f.im_band = nband, f.im_diag = ndiag, f.im_vec = npad;
   f.member_doubles = nd;
-  f.bytes          = (K * nd + 4 * K) * sizeof(double) + (npad + K) * sizeof(int);
+  const size_t ncoef = d_c ? 6 : 4; // per member: alpha, beta and, with a third term, gamma
+  f.bytes          = (K * nd + ncoef * K) * sizeof(double) + (npad + K) * sizeof(int);
   hipError_t e     = f.mem.alloc(f.bytes); // freed with z on every error return
   if (e != hipSuccess)
     return slod_hip_fail(h, e, who);
@@ -1062,29 +1079,32 @@ int slod_lod_zfactor_launch(slod_handle *h, hipStream_t st, const char *who, con
   f.piv    = f.diag + 2 * ndiag;
   f.dinv   = f.piv + nread;
   f.coef   = f.band + K * nd;
-  f.rowmap = (int *)(f.coef + 4 * K);
+  f.rowmap = (int *)(f.coef + ncoef * K);
   f.status = f.rowmap + npad;
   z->piv.assign(K * nread, 0.0);
   z->bad.assign(K, -1);
   std::vector<double> &coef = z->coef; // lives until finish() has waited
-  coef.resize(4 * K);
+  coef.resize(ncoef * K);
   for (size_t k = 0; k < K; ++k)
     {
       const size_t c = (j0 + k) / (size_t)kmat; // the coefficient pair of flat member j0 + k
       coef[4 * k] = alpha[2 * c], coef[4 * k + 1] = alpha[2 * c + 1], coef[4 * k + 2] = beta[2 * c], coef[4 * k + 3] = beta[2 * c + 1];
+      if (d_c)
+        coef[4 * K + 2 * k] = gamma[2 * c], coef[4 * K + 2 * k + 1] = gamma[2 * c + 1];
     }
   e = hipMemsetAsync(f.band, 0, K * nd * sizeof(double), st);
   if (e == hipSuccess)
     e = hipMemsetAsync(f.status, 0xff, K * sizeof(int), st); // -1
   if (e == hipSuccess)
-    e = hipMemcpyAsync(f.coef, coef.data(), 4 * K * sizeof(double), hipMemcpyHostToDevice, st);
+    e = hipMemcpyAsync(f.coef, coef.data(), ncoef * K * sizeof(double), hipMemcpyHostToDevice, st);
   if (e == hipSuccess)
     {
       const size_t nval = (size_t)h->NP * cap * s * s;
       hipLaunchKernelGGL(k_factor_rowmap, dim3((unsigned)((npad + 255) / 256), (unsigned)K), dim3(256), 0, st, G, f.n, (int)npad, f.bb,
                          f.rowmap, f.band, nd);
-      hipLaunchKernelGGL(k_zfactor_scatter, dim3((unsigned)((nval * K + 255) / 256)), dim3(256), 0, st, G, h->NP, cap, f.bb, n_members,
-                         d_a, ld_a, d_b, ld_b, kmat, j0, f.coef, d_cols, f.band, nband, nd);
+      hipLaunchKernelGGL(d_c ? k_zfactor_scatter<true> : k_zfactor_scatter<false>, dim3((unsigned)((nval * K + 255) / 256)), dim3(256), 0,
+                         st, G, h->NP, cap, f.bb, n_members, d_a, ld_a, d_b, ld_b, d_c, ld_c, kmat, j0, f.coef, f.coef + 4 * K, d_cols,
+                         f.band, nband, nd);
       double    *norms = f.piv + 2 * npad, *work = f.dinv + 2 * npad, *work2 = work + npad;
       const dim3 rows_grid((unsigned)f.nb, (unsigned)K);
       hipLaunchKernelGGL(k_zldl_norms<0>, rows_grid, dim3(256), 0, st, f.nb, f.bb, f.band, nband, f.diag, ndiag, f.piv, npad, nullptr,
@@ -1330,6 +1350,33 @@ int slod_lod_factor_create_zldl(slod_handle *h, const double *d_a, const double 
     return rc;
   SlodZFactorBuild z;
   if (const int rc = slod_lod_zfactor_launch(h, st, who, d_a, 1, d_b, 1, 1, d_cols, alpha, beta, 0, n_members, &z))
+    return rc;
+  if (const int rc = slod_lod_zfactor_finish(h, st, who, "member", 0, &z, bad_pivot))
+    return rc;
+  *out = new slod_lod_factor(std::move(z.f));
+  return SLOD_OK;
+}
+
+// slod_lod_factor_create_zldl with a third term:  S_k = alpha_k A + beta_k B + gamma_k C
+int slod_lod_factor_create_zldl3(slod_handle *h, const double *d_a, const double *d_b, const double *d_c, const uint32_t *d_cols,
+                                 const double *alpha, const double *beta, const double *gamma, int n_members, int32_t *bad_pivot,
+                                 slod_lod_factor **out)
+{
+  const char *who = "slod_lod_factor_create_zldl3";
+  if (out)
+    *out = nullptr;
+  if (!h || !d_a || !d_b || !d_c || !d_cols || !alpha || !beta || !gamma || !out)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": NULL handle, array, alpha, beta, gamma or out");
+  if (n_members < 1 || n_members > MAX_MEMBERS)
+    return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": n_members < 1 or > 65535");
+  for (int k = 0; k < 2 * n_members; ++k)
+    if (!std::isfinite(alpha[k]) || !std::isfinite(beta[k]) || !std::isfinite(gamma[k]))
+      return slod_fail(h, SLOD_ERR_ARGUMENT, std::string(who) + ": a coefficient is NaN or infinite");
+  hipStream_t st;
+  if (const int rc = slod_enter(h, nullptr, &st))
+    return rc;
+  SlodZFactorBuild z;
+  if (const int rc = slod_lod_zfactor_launch(h, st, who, d_a, 1, d_b, 1, 1, d_cols, alpha, beta, 0, n_members, &z, d_c, 1, gamma))
     return rc;
   if (const int rc = slod_lod_zfactor_finish(h, st, who, "member", 0, &z, bad_pivot))
     return rc;

@@ -20,6 +20,10 @@
 // host body (irk_steps), queued whole on the handle's stream and waited for once.  Everything besides the chains is
 // elementwise with fp contract off: the bits of a column depend on the factor member, the matrices, the parameters and
 // that column alone.
+//   slod_lod_irk_damping_coefficient, slod_lod_irk_wave_steps_damped_direct
+// add a third matrix to the damping, C = damp_mass M + damp_stiff A + D (a sponge layer): S gains z D (the gamma of
+// slod_lod_factor_create_zldl3), the bracket of r gains D v, a fourth chain on the loads of v (DAMP).  Without D the loop
+// runs the instantiations and has the words it had before.
 //   slod_lod_irk_heat_steps_ensemble_direct, slod_lod_irk_wave_steps_ensemble_direct
 // are the same loops with a matrix, a factor member and a column per member of a coefficient ensemble: the right-hand
 // side kernels run with PER_COL set (the same chains on member m's words of the member-minor ensemble matrices, their
@@ -45,16 +49,17 @@ namespace
   };
 
   // The row's chains in one walk over its slots: acc[0] = (A x0)_i and, as far as asked for, acc[1] = (A x1)_i and
-  // acc[2] = (M x1)_i, every one the fma chain of slod_lod_row_product on its own operands.
-  template <int NCHAIN>
+  // acc[2] = (M x1)_i, every one the fma chain of slod_lod_row_product on its own operands.  DAMP (NCHAIN >= 2): the
+  // fourth chain acc[3] = (D x1)_i of the third matrix dm, on the same loads of x1.
+  template <int NCHAIN, bool DAMP>
   __device__ __forceinline__ void irk_row_products(int i, int s, int cap, int NP, const double *__restrict__ a,
-                                                   const double *__restrict__ m, const uint32_t *__restrict__ cols,
-                                                   const double *__restrict__ x0, size_t ld0, const double *__restrict__ x1,
-                                                   size_t ld1, int col, double (&acc)[3])
+                                                   const double *__restrict__ m, const double *__restrict__ dm,
+                                                   const uint32_t *__restrict__ cols, const double *__restrict__ x0, size_t ld0,
+                                                   const double *__restrict__ x1, size_t ld1, int col, double (&acc)[4])
   {
     const int    p = i / s, d = i - p * s;
     const size_t slot0 = (size_t)p * cap;
-    acc[0] = acc[1] = acc[2] = 0.0;
+    acc[0] = acc[1] = acc[2] = acc[3] = 0.0;
     for (int j = 0; j < cap; ++j)
       {
         const uint32_t q = cols[slot0 + j];
@@ -74,6 +79,11 @@ namespace
                     const double t2 = fma(m[at + e], xv, acc[2]);
                     acc[2]          = used ? t2 : acc[2];
                   }
+                if constexpr (DAMP)
+                  {
+                    const double t3 = fma(dm[at + e], xv, acc[3]);
+                    acc[3]          = used ? t3 : acc[3];
+                  }
               }
           }
       }
@@ -83,20 +93,22 @@ namespace
   // column col's matrices at a[e ld_a + col] and m[e ld_m + col].  Every (row, column) streams its own matrix words, so,
   // as in slod_lod_row_product_per_col, the loads of SLOTS slots are issued before the first fma needs one: every word of
   // A once for the chains on x0 and x1, the words of M in the same batch when the mass chain runs.  A slot past the end
-  // of the row reads the last one and adds nothing, like an unused slot.
-  template <int NCHAIN, int S, int SLOTS> // S = s, a constant here so that nothing stands between the loads
+  // of the row reads the last one and adds nothing, like an unused slot.  DAMP: the words of the third matrix dm (ld_d) in
+  // the same batch, for the chain acc[3].
+  template <int NCHAIN, bool DAMP, int S, int SLOTS> // S = s, a constant here so that nothing stands between the loads
   __device__ __forceinline__ void irk_row_products_per_col(int p, int d, int cap, int NP, const double *__restrict__ a, size_t ld_a,
-                                                           const double *__restrict__ m, size_t ld_m,
-                                                           const uint32_t *__restrict__ cols, const double *__restrict__ x0,
-                                                           size_t ld0, const double *__restrict__ x1, size_t ld1, int col,
-                                                           double (&acc)[3])
+                                                           const double *__restrict__ m, size_t ld_m, const double *__restrict__ dm,
+                                                           size_t ld_d, const uint32_t *__restrict__ cols,
+                                                           const double *__restrict__ x0, size_t ld0, const double *__restrict__ x1,
+                                                           size_t ld1, int col, double (&acc)[4])
   {
     const size_t slot0 = (size_t)p * cap;
-    acc[0] = acc[1] = acc[2] = 0.0;
+    acc[0] = acc[1] = acc[2] = acc[3] = 0.0;
     for (int j0 = 0; j0 < cap; j0 += SLOTS)
       {
         bool   used[SLOTS];
         double aw[SLOTS][S], mw[NCHAIN >= 3 ? SLOTS : 1][S], xu[SLOTS][S], xv[NCHAIN >= 2 ? SLOTS : 1][S];
+        double dw[DAMP ? SLOTS : 1][S];
 #pragma unroll
         for (int u = 0; u < SLOTS; ++u)
           {
@@ -113,6 +125,8 @@ namespace
                   xv[u][e] = x1[(qs + e) * ld1 + col];
                 if constexpr (NCHAIN >= 3)
                   mw[u][e] = m[(at + e) * ld_m + col];
+                if constexpr (DAMP)
+                  dw[u][e] = dm[(at + e) * ld_d + col];
               }
           }
 #pragma unroll
@@ -131,28 +145,36 @@ namespace
                       const double t2 = fma(mw[u][e], xv[u][e], acc[2]);
                       acc[2]          = used[u] ? t2 : acc[2];
                     }
+                  if constexpr (DAMP)
+                    {
+                      const double t3 = fma(dw[u][e], xv[u][e], acc[3]);
+                      acc[3]          = used[u] ? t3 : acc[3];
+                    }
                 }
             }
       }
   }
 
   // The chains of row i for column col: on the one matrix pair, or (PER_COL) on member col of the ensemble matrices
-  template <int NCHAIN, bool PER_COL>
+  template <int NCHAIN, bool PER_COL, bool DAMP = false>
   __device__ __forceinline__ void irk_products(int i, int s, int cap, int NP, const double *__restrict__ a, size_t ld_a,
-                                               const double *__restrict__ m, size_t ld_m, const uint32_t *__restrict__ cols,
-                                               const double *__restrict__ x0, size_t ld0, const double *__restrict__ x1, size_t ld1,
-                                               int col, double (&acc)[3])
+                                               const double *__restrict__ m, size_t ld_m, const double *__restrict__ dm, size_t ld_d,
+                                               const uint32_t *__restrict__ cols, const double *__restrict__ x0, size_t ld0,
+                                               const double *__restrict__ x1, size_t ld1, int col, double (&acc)[4])
   {
+    static_assert(!DAMP || NCHAIN >= 2, "the damping chain runs on the loads of x1");
     if constexpr (PER_COL)
       {
         const int p = i / s, d = i - p * s;
         if (s == 1)
-          irk_row_products_per_col<NCHAIN, 1, LOD_SLOTS>(p, d, cap, NP, a, ld_a, m, ld_m, cols, x0, ld0, x1, ld1, col, acc);
+          irk_row_products_per_col<NCHAIN, DAMP, 1, LOD_SLOTS>(p, d, cap, NP, a, ld_a, m, ld_m, dm, ld_d, cols, x0, ld0, x1, ld1, col,
+                                                               acc);
         else
-          irk_row_products_per_col<NCHAIN, 2, LOD_SLOTS>(p, d, cap, NP, a, ld_a, m, ld_m, cols, x0, ld0, x1, ld1, col, acc);
+          irk_row_products_per_col<NCHAIN, DAMP, 2, LOD_SLOTS>(p, d, cap, NP, a, ld_a, m, ld_m, dm, ld_d, cols, x0, ld0, x1, ld1, col,
+                                                               acc);
       }
     else
-      irk_row_products<NCHAIN>(i, s, cap, NP, a, m, cols, x0, ld0, x1, ld1, col, acc);
+      irk_row_products<NCHAIN, DAMP>(i, s, cap, NP, a, m, dm, cols, x0, ld0, x1, ld1, col, acc);
   }
 
   // r = tau_1 (b_1 - A u) + tau_2 (b_2 - A u) per (row, column), both planes; b1 NULL: zero load.  PER_COL: column c
@@ -168,8 +190,8 @@ namespace
     if (t >= (size_t)nrow * n_rhs)
       return;
     const int i = (int)(t / n_rhs), c = (int)(t - (size_t)i * n_rhs);
-    double    acc[3];
-    irk_products<1, PER_COL>(i, s, cap, NP, stiffness, ld_a_m, nullptr, 0, cols, u, ld_u, nullptr, 0, c, acc);
+    double    acc[4];
+    irk_products<1, PER_COL>(i, s, cap, NP, stiffness, ld_a_m, nullptr, 0, nullptr, 0, cols, u, ld_u, nullptr, 0, c, acc);
     const double d1 = (b1 ? b1[(size_t)i * ld_b + c] : 0.0) - acc[0], d2 = (b1 ? b2[(size_t)i * ld_b + c] : 0.0) - acc[0];
     const double p1r = k.t1r * d1, p2r = k.t2r * d2, p1i = k.t1i * d1, p2i = k.t2i * d2;
     r_re[t] = p1r + p2r;
@@ -178,11 +200,13 @@ namespace
 
   // r = tau_1 b_1 + tau_2 b_2 - sigma [A u + (z + damp_stiff) A v + damp_mass M v] per (row, column), both planes;
   // b1 NULL: zero load.  HAS_MASS_DAMPING unset: no mass chain (damp_mass = 0).  PER_COL: column c reads member c of the
-  // ensemble matrices stiffness (ld_a_m) and mass (ld_m_m).
-  template <bool HAS_MASS_DAMPING, bool PER_COL>
+  // ensemble matrices stiffness (ld_a_m) and mass (ld_m_m).  HAS_DAMPING: the bracket gains D v of the third matrix
+  // damping (ld_d_m), added after the mass term.
+  template <bool HAS_MASS_DAMPING, bool PER_COL, bool HAS_DAMPING = false>
   __global__ __launch_bounds__(256) void k_irk_wave_rhs(int nrow, int s, int cap, int NP, int n_rhs, IrkStep k,
                                                        const double *__restrict__ stiffness, size_t ld_a_m,
                                                        const double *__restrict__ mass, size_t ld_m_m,
+                                                       const double *__restrict__ damping, size_t ld_d_m,
                                                        const uint32_t *__restrict__ cols, const double *b1, const double *b2,
                                                        size_t ld_b, const double *u, size_t ld_u, const double *v, size_t ld_v,
                                                        double *r_re, double *r_im)
@@ -192,9 +216,10 @@ namespace
     if (t >= (size_t)nrow * n_rhs)
       return;
     const int i = (int)(t / n_rhs), c = (int)(t - (size_t)i * n_rhs);
-    double    acc[3];
-    irk_products<HAS_MASS_DAMPING ? 3 : 2, PER_COL>(i, s, cap, NP, stiffness, ld_a_m, mass, ld_m_m, cols, u, ld_u, v, ld_v, c, acc);
-    // p = A u + (z + damp_stiff) A v + damp_mass M v
+    double    acc[4];
+    irk_products<HAS_MASS_DAMPING ? 3 : 2, PER_COL, HAS_DAMPING>(i, s, cap, NP, stiffness, ld_a_m, mass, ld_m_m, damping, ld_d_m, cols,
+                                                                 u, ld_u, v, ld_v, c, acc);
+    // p = A u + (z + damp_stiff) A v + damp_mass M v [+ D v]
     const double av_r = k.zdr * acc[1];
     double       pr = acc[0] + av_r;
     const double pi = k.zi * acc[1];
@@ -203,6 +228,8 @@ namespace
         const double dm = k.damp_mass * acc[2];
         pr              = pr + dm;
       }
+    if constexpr (HAS_DAMPING)
+      pr = pr + acc[3];
     // sigma p, complex product written out
     const double a = k.sr * pr, b = k.si * pi, e = k.sr * pi, f = k.si * pr;
     const double qr = a - b, qi = e + f;
@@ -216,6 +243,17 @@ namespace
     r_re[t] = lr - qr;
     r_im[t] = li - qi;
   }
+
+  // The damping chain with a matrix per column has no entry point yet; instantiated here so that it keeps compiling and an
+  // ensemble form of the damped call is a launch.
+  template __global__ void k_irk_wave_rhs<true, true, true>(int, int, int, int, int, IrkStep, const double *, size_t, const double *,
+                                                            size_t, const double *, size_t, const uint32_t *, const double *,
+                                                            const double *, size_t, const double *, size_t, const double *, size_t,
+                                                            double *, double *);
+  template __global__ void k_irk_wave_rhs<false, true, true>(int, int, int, int, int, IrkStep, const double *, size_t, const double *,
+                                                             size_t, const double *, size_t, const uint32_t *, const double *,
+                                                             const double *, size_t, const double *, size_t, const double *, size_t,
+                                                             double *, double *);
 
   // ORDER 1:  u += 2 dt Re(mu w).  ORDER 2:  w_u = sigma v + z w,  u += 2 dt Re(mu w_u),  v += 2 dt Re(mu w).
   template <int ORDER>
@@ -293,8 +331,10 @@ namespace
   // handle (SlodLodRecord, slod_host.h) is taken first, checked after the call's own checks and adds one launch after the
   // entry state and every every-th advance.  A source armed on it (SlodLodSource) is taken with the record, checked after
   // it, and adds one launch a step, whose two vectors the right-hand side reads in place of the stage loads.
+  // d_damping (wave; NULL: none): the third matrix D of the _damped call, on a factor of S + z D.
   int irk_steps(slod_handle *h, const std::string &who, int order, slod_lod_factor *f, int first_member, int scheme,
-                const double *d_stiffness, size_t ld_a_m, const double *d_mass, size_t ld_m_m, bool per_col, const uint32_t *d_cols,
+                const double *d_stiffness, size_t ld_a_m, const double *d_mass, size_t ld_m_m, const double *d_damping, size_t ld_d_m,
+                bool per_col, const uint32_t *d_cols,
                 double dt, double damp_mass, double damp_stiff, int n_steps, int n, double *d_u, size_t ld_u, double *d_v, size_t ld_v,
                 const double *d_load, size_t ld_load, size_t load_stage_stride, double *kinetic, double *potential)
   {
@@ -350,8 +390,9 @@ namespace
     double *part_k = w_im + nvec, *part_p = part_k + npart, *d_energy = part_p + npart, *lb = d_energy + nenergy;
     const dim3     nblk = lod_flat_grid(nvec);
     const auto     heat_rhs = per_col ? k_irk_heat_rhs<true> : k_irk_heat_rhs<false>;
-    const auto     wave_rhs = damp_mass != 0.0 ? (per_col ? k_irk_wave_rhs<true, true> : k_irk_wave_rhs<true, false>)
-                                               : (per_col ? k_irk_wave_rhs<false, true> : k_irk_wave_rhs<false, false>);
+    const auto     wave_rhs = d_damping && !per_col ? (damp_mass != 0.0 ? k_irk_wave_rhs<true, false, true> : k_irk_wave_rhs<false, false, true>)
+                              : damp_mass != 0.0    ? (per_col ? k_irk_wave_rhs<true, true> : k_irk_wave_rhs<true, false>)
+                                                    : (per_col ? k_irk_wave_rhs<false, true> : k_irk_wave_rhs<false, false>);
     auto launch_energies = [&](int level) {
       slod_lod_energies_launch(h, st, d_stiffness, d_mass, d_cols, n, d_u, ld_u, d_v, ld_v, part_k, part_p,
                                d_energy + 2 * (size_t)level * n, per_col, ld_a_m, ld_m_m);
@@ -376,7 +417,7 @@ namespace
                              ld_b, d_u, ld_u, r_re, r_im);
         else
           hipLaunchKernelGGL(wave_rhs, nblk, dim3(256), 0, st, w.nrow, w.s, w.cap, w.NP, n, k, d_stiffness, ld_a_m, d_mass, ld_m_m,
-                             d_cols, b1, b2, ld_b, d_u, ld_u, d_v, ld_v, r_re, r_im);
+                             d_damping, ld_d_m, d_cols, b1, b2, ld_b, d_u, ld_u, d_v, ld_v, r_re, r_im);
         // single: the n columns on the one member; per_col: member first_member + m on column m of r, one column each
         if (per_col)
           slod_lod_zfactor_solve_launch(f, st, first_member, n, r_re, r_im, (size_t)n, 1, 0, n, w_re, w_im, (size_t)n);
@@ -445,7 +486,7 @@ int slod_lod_irk_heat_steps_direct(slod_handle *h, slod_lod_factor *f_S, int mem
                                    const uint32_t *d_cols, double dt, int n_steps, int n_rhs, double *d_u, size_t ld_u,
                                    const double *d_load, size_t ld_load, size_t load_stage_stride)
 {
-  return irk_steps(h, "slod_lod_irk_heat_steps_direct", 1, f_S, member, scheme, d_stiffness, 1, nullptr, 1, false, d_cols, dt, 0.0, 0.0,
+  return irk_steps(h, "slod_lod_irk_heat_steps_direct", 1, f_S, member, scheme, d_stiffness, 1, nullptr, 1, nullptr, 1, false, d_cols, dt, 0.0, 0.0,
                    n_steps, n_rhs, d_u, ld_u, nullptr, 0, d_load, ld_load, load_stage_stride, nullptr, nullptr);
 }
 
@@ -454,8 +495,37 @@ int slod_lod_irk_wave_steps_direct(slod_handle *h, slod_lod_factor *f_S, int mem
                                    int n_steps, int n_rhs, double *d_u, size_t ld_u, double *d_v, size_t ld_v, const double *d_load,
                                    size_t ld_load, size_t load_stage_stride, double *kinetic, double *potential)
 {
-  return irk_steps(h, "slod_lod_irk_wave_steps_direct", 2, f_S, member, scheme, d_stiffness, 1, d_mass, 1, false, d_cols, dt, damp_mass,
+  return irk_steps(h, "slod_lod_irk_wave_steps_direct", 2, f_S, member, scheme, d_stiffness, 1, d_mass, 1, nullptr, 1, false, d_cols, dt, damp_mass,
                    damp_stiff, n_steps, n_rhs, d_u, ld_u, d_v, ld_v, d_load, ld_load, load_stage_stride, kinetic, potential);
+}
+
+// gamma = z = dt lambda of the scheme, the coefficient of D in the step matrix of the damped wave
+int slod_lod_irk_damping_coefficient(int scheme, double dt, double gamma[2])
+{
+  const std::string who = "slod_lod_irk_damping_coefficient";
+  IrkScheme         s;
+  if (!gamma)
+    return slod_fail(nullptr, SLOD_ERR_ARGUMENT, who + ": NULL gamma");
+  if (!irk_scheme(scheme, &s))
+    return slod_fail(nullptr, SLOD_ERR_ARGUMENT, who + ": unknown scheme");
+  if (!(dt > 0.0) || std::isinf(dt))
+    return slod_fail(nullptr, SLOD_ERR_ARGUMENT, who + ": dt <= 0, NaN or infinite");
+  const cld z = (long double)dt * s.lambda;
+  gamma[0] = (double)z.real(), gamma[1] = (double)z.imag();
+  return SLOD_OK;
+}
+
+// slod_lod_irk_wave_steps_direct with the third damping matrix D, on a member of the factor of S + z D
+// (slod_lod_factor_create_zldl3); d_damping NULL: D = 0, the launches and the words of slod_lod_irk_wave_steps_direct
+int slod_lod_irk_wave_steps_damped_direct(slod_handle *h, slod_lod_factor *f_S, int member, int scheme, const double *d_stiffness,
+                                          const double *d_mass, const double *d_damping, const uint32_t *d_cols, double dt,
+                                          double damp_mass, double damp_stiff, int n_steps, int n_rhs, double *d_u, size_t ld_u,
+                                          double *d_v, size_t ld_v, const double *d_load, size_t ld_load, size_t load_stage_stride,
+                                          double *kinetic, double *potential)
+{
+  return irk_steps(h, "slod_lod_irk_wave_steps_damped_direct", 2, f_S, member, scheme, d_stiffness, 1, d_mass, 1, d_damping, 1, false,
+                   d_cols, dt, damp_mass, damp_stiff, n_steps, n_rhs, d_u, ld_u, d_v, ld_v, d_load, ld_load, load_stage_stride, kinetic,
+                   potential);
 }
 
 // slod_lod_irk_heat_steps_direct with a matrix, a factor member and a column per ensemble member
@@ -464,7 +534,7 @@ int slod_lod_irk_heat_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S
                                             int n_members, double *d_u, size_t ld_u, const double *d_load, size_t ld_load,
                                             size_t load_stage_stride)
 {
-  return irk_steps(h, "slod_lod_irk_heat_steps_ensemble_direct", 1, f_S, first_member, scheme, d_stiffness, ld_a_m, nullptr, ld_a_m, true,
+  return irk_steps(h, "slod_lod_irk_heat_steps_ensemble_direct", 1, f_S, first_member, scheme, d_stiffness, ld_a_m, nullptr, ld_a_m, nullptr, 1, true,
                    d_cols, dt, 0.0, 0.0, n_steps, n_members, d_u, ld_u, nullptr, 0, d_load, ld_load, load_stage_stride, nullptr, nullptr);
 }
 
@@ -475,7 +545,7 @@ int slod_lod_irk_wave_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S
                                             int n_members, double *d_u, size_t ld_u, double *d_v, size_t ld_v, const double *d_load,
                                             size_t ld_load, size_t load_stage_stride, double *kinetic, double *potential)
 {
-  return irk_steps(h, "slod_lod_irk_wave_steps_ensemble_direct", 2, f_S, first_member, scheme, d_stiffness, ld_a_m, d_mass, ld_m_m, true,
+  return irk_steps(h, "slod_lod_irk_wave_steps_ensemble_direct", 2, f_S, first_member, scheme, d_stiffness, ld_a_m, d_mass, ld_m_m, nullptr, 1, true,
                    d_cols, dt, damp_mass, damp_stiff, n_steps, n_members, d_u, ld_u, d_v, ld_v, d_load, ld_load, load_stage_stride,
                    kinetic, potential);
 }

@@ -13,6 +13,9 @@
 // of slod_lod_solve_multi (SlodLodWork::solve, slod_lod_multi.hip) on a workspace the loop owns, every one from zero; on
 // a factor the whole loop is queued and waited for once.  Row products, tiling and sums are those of slod_lod_tile.hip.h.
 // Everything else is elementwise with fp contract off, so the bits of a column depend on that column alone.
+// The _damped calls add a third matrix to the damping, C = damp_mass M + damp_stiff A + D (a sponge layer: D = C^T M_sigma C
+// of slod_lod_mass_matrix with d_rho = sigma): the bodies take it as an optional third operator, k_nm_rhs<.., true> forms
+// M v and D v in one walk over the row, and a call without D runs the launches and has the words it had before.
 #include "slod_lod_tile.hip.h"
 
 #include <algorithm>
@@ -106,11 +109,43 @@ namespace
     w[t]            = up + dv;
   }
 
+  // (M x)_i and (D x)_i of row i in one walk over its slots: the column indices and x are read once, every chain is the
+  // fma chain of slod_lod_row_product on its own operands.  HAS_M unset: the D chain alone (accm stays 0).
+  template <bool HAS_M>
+  __device__ __forceinline__ void nm_damping_products(int i, int s, int cap, int NP, const double *__restrict__ m,
+                                                      const double *__restrict__ dmat, const uint32_t *__restrict__ cols,
+                                                      const double *__restrict__ x, size_t ld, int col, double &accm, double &accd)
+  {
+    const int    p = i / s, d = i - p * s;
+    const size_t slot0 = (size_t)p * cap;
+    accm = accd = 0.0;
+    for (int j = 0; j < cap; ++j)
+      {
+        const uint32_t q = cols[slot0 + j];
+        const bool     used = q < (uint32_t)NP;
+        const size_t   qs = (size_t)(used ? q : (uint32_t)p) * s, at = (slot0 + j) * s * s + d * s;
+        for (int e = 0; e < s; ++e)
+          {
+            const double xv = x[(qs + e) * ld + col];
+            const double td = fma(dmat[at + e], xv, accd);
+            accd            = used ? td : accd;
+            if constexpr (HAS_M)
+              {
+                const double tm = fma(m[at + e], xv, accm);
+                accm            = used ? tm : accm;
+              }
+          }
+      }
+  }
+
   // g = (b - A w) - damp_mass (M v) per (row, column); load NULL: b = 0; mass NULL: no mass term (damp_mass = 0).
   // PER_COL: column c reads member c of the ensemble matrices stiffness (ld_a_m) and mass (ld_m_m).
-  template <bool PER_COL>
+  // DAMPED: g = ((b - A w) - damp_mass (M v)) - (D v) with the third matrix damping (ld_d_m); M v and D v come from one
+  // walk over the row (with a member per column: from a product each).
+  template <bool PER_COL, bool DAMPED = false>
   __global__ __launch_bounds__(256) void k_nm_rhs(int nrow, int s, int cap, int NP, int n_rhs, const double *__restrict__ stiffness,
                                                  size_t ld_a_m, const double *__restrict__ mass, size_t ld_m_m,
+                                                 const double *__restrict__ damping, size_t ld_d_m,
                                                  const uint32_t *__restrict__ cols, double damp_mass, const double *load,
                                                  size_t ld_load, const double *w, const double *v, size_t ld_v, double *g)
   {
@@ -121,7 +156,27 @@ namespace
     const int    i = (int)(t / n_rhs), c = (int)(t - (size_t)i * n_rhs);
     const double Aw = slod_lod_row_product<PER_COL>(i, s, cap, NP, stiffness, cols, w, (size_t)n_rhs, c, ld_a_m);
     double       r = (load ? load[(size_t)i * ld_load + c] : 0.0) - Aw;
-    if (mass)
+    if constexpr (DAMPED)
+      {
+        double Mv = 0.0, Dv;
+        if constexpr (PER_COL)
+          {
+            if (mass)
+              Mv = slod_lod_row_product<true>(i, s, cap, NP, mass, cols, v, ld_v, c, ld_m_m);
+            Dv = slod_lod_row_product<true>(i, s, cap, NP, damping, cols, v, ld_v, c, ld_d_m);
+          }
+        else if (mass)
+          nm_damping_products<true>(i, s, cap, NP, mass, damping, cols, v, ld_v, c, Mv, Dv);
+        else
+          nm_damping_products<false>(i, s, cap, NP, nullptr, damping, cols, v, ld_v, c, Mv, Dv);
+        if (mass)
+          {
+            const double dm = damp_mass * Mv;
+            r               = r - dm;
+          }
+        r = r - Dv;
+      }
+    else if (mass)
       {
         const double Mv = slod_lod_row_product<PER_COL>(i, s, cap, NP, mass, cols, v, ld_v, c, ld_m_m);
         const double dm = damp_mass * Mv;
@@ -162,14 +217,16 @@ namespace
                        j0.partial, j1.partial, scale, out);
   }
 
-  // g = (b - A arg) - damp_mass (M v) on n_rhs columns; the mass product is skipped when damp_mass = 0
-  void launch_rhs(const LodShape &w, hipStream_t st, const SlodLodOperator &A, const SlodLodOperator &M, const uint32_t *cols,
-                  int n_rhs, double damp_mass, const double *load, size_t ld_load, const double *arg, const double *v, size_t ld_v,
-                  double *g)
+  // g = (b - A arg) - damp_mass (M v) on n_rhs columns; the mass product is skipped when damp_mass = 0.  D.values given:
+  // the damped instantiation, g = ((b - A arg) - damp_mass (M v)) - (D v); the ensemble loops pass none.
+  void launch_rhs(const LodShape &w, hipStream_t st, const SlodLodOperator &A, const SlodLodOperator &M, const SlodLodOperator &D,
+                  const uint32_t *cols, int n_rhs, double damp_mass, const double *load, size_t ld_load, const double *arg,
+                  const double *v, size_t ld_v, double *g)
   {
-    hipLaunchKernelGGL(A.per_col ? k_nm_rhs<true> : k_nm_rhs<false>, lod_flat_grid((size_t)w.nrow * n_rhs), dim3(256), 0, st, w.nrow,
-                       w.s, w.cap, w.NP, n_rhs, A.values, A.ld_m, damp_mass != 0.0 ? M.values : nullptr, M.ld_m, cols, damp_mass,
-                       load, ld_load, arg, v, ld_v, g);
+    const auto kernel = D.values ? k_nm_rhs<false, true> : A.per_col ? k_nm_rhs<true> : k_nm_rhs<false>;
+    hipLaunchKernelGGL(kernel, lod_flat_grid((size_t)w.nrow * n_rhs), dim3(256), 0, st, w.nrow, w.s, w.cap, w.NP, n_rhs, A.values,
+                       A.ld_m, damp_mass != 0.0 ? M.values : nullptr, M.ld_m, D.values, D.ld_m, cols, damp_mass, load, ld_load, arg, v,
+                       ld_v, g);
   }
 
   // out[c] = x_c^T (A y_c) on n columns with the operator of every column: the body of slod_lod_inner_multi and, with a
@@ -240,11 +297,11 @@ namespace
     return cg ? SLOD_OK : slod_lod_factor_check(h, who.c_str(), solve.f, ens ? n : 1);
   }
 
-  // M a = b^0 - A (u + damp_stiff v) - damp_mass M v on n columns, whatever solves with M (the CG on M itself, or its
-  // factor): the body of the three accel calls.  iterations, rel_residual: of the CG, per column.  Returns the largest
+  // M a = b^0 - A (u + damp_stiff v) - damp_mass M v [- D v] on n columns, whatever solves with M (the CG on M itself, or
+  // its factor): the body of the accel calls.  D: the third matrix of the _damped calls, values NULL: none.  iterations, rel_residual: of the CG, per column.  Returns the largest
   // iteration count (0 on a factor) or a negative status.
   int nm_accel(slod_handle *h, const char *who, SlodLodStepSolve &&solve, const SlodLodOperator &A, const SlodLodOperator &M,
-               const uint32_t *d_cols, double damp_mass, double damp_stiff, int n, const double *d_u, size_t ld_u, const double *d_v,
+               const SlodLodOperator &D, const uint32_t *d_cols, double damp_mass, double damp_stiff, int n, const double *d_u, size_t ld_u, const double *d_v,
                size_t ld_v, const double *d_load, size_t ld_load, double *d_a, size_t ld_a, int *iterations = nullptr,
                double *rel_residual = nullptr)
   {
@@ -262,7 +319,7 @@ namespace
     if (e == hipSuccess)
       {
         hipLaunchKernelGGL(k_nm_shift, lod_flat_grid(nvec), dim3(256), 0, st, w.nrow, n, damp_stiff, d_u, ld_u, d_v, ld_v, arg);
-        launch_rhs(w, st, A, M, d_cols, n, damp_mass, d_load, ld_load, arg, d_v, ld_v, g);
+        launch_rhs(w, st, A, M, D, d_cols, n, damp_mass, d_load, ld_load, arg, d_v, ld_v, g);
         e = hipGetLastError();
         if (e == hipSuccess)
           e = solve.solve(h, st, 0, n, g, (size_t)n, d_a, ld_a);
@@ -285,13 +342,14 @@ namespace
   // n_steps of Newmark-beta in acceleration form on n columns, whatever solves the step: predictor, right-hand side,
   // S a = g, corrector, and with kinetic / potential the two energies of every level; the body of the three steps calls.
   // CG: S = (1 + gamma dt damp_mass) M + (beta dt^2 + gamma dt damp_stiff) A is built here and every solve synchronises; on
-  // a factor (of that S) the whole loop is queued and the stream is waited for once.  Returns the largest iteration count
+  // a factor (of that S) the whole loop is queued and the stream is waited for once.  D (values NULL: none): the third
+  // matrix of the _damped calls; the CG form then adds (gamma dt) D to S in a second combine, in place.  Returns the largest iteration count
   // of a step (0 on a factor) or a negative status.  A record armed on the handle (SlodLodRecord, slod_host.h) is taken
   // first, checked after the call's own checks and queued on st: u and / or v at the receivers after the entry state and
   // every every-th corrector.  A source armed on it (SlodLodSource) is taken with the record, checked after it, and adds
   // one product a step, whose vector the right-hand side reads in place of the load.
   int nm_steps(slod_handle *h, const char *who, SlodLodStepSolve &&solve, const SlodLodOperator &A, const SlodLodOperator &M,
-               const uint32_t *d_cols, double dt, double beta, double gamma, double damp_mass, double damp_stiff, int n_steps, int n,
+               const SlodLodOperator &D, const uint32_t *d_cols, double dt, double beta, double gamma, double damp_mass, double damp_stiff, int n_steps, int n,
                double *d_u, size_t ld_u, double *d_v, size_t ld_v, double *d_a, size_t ld_a, const double *d_load, size_t ld_load,
                size_t load_step_stride, double *kinetic, double *potential)
   {
@@ -326,6 +384,8 @@ namespace
         if (solve.cg())
           {
             slod_lod_combine_launch(st, nmat, 1.0 + gdt * damp_mass, M.values, bdt2 + gdt * damp_stiff, A.values, S);
+            if (D.values)
+              slod_lod_combine_launch(st, nmat, 1.0, S, gdt, D.values, S);
             solve.S = S;
           }
         if (energies)
@@ -344,7 +404,7 @@ namespace
               }
             hipLaunchKernelGGL(k_nm_predict, nblk, dim3(256), 0, st, w.nrow, n, dt, dt * dt * (0.5 - beta), dt * (1.0 - gamma),
                                damp_stiff, d_u, ld_u, d_v, ld_v, d_a, ld_a, arg);
-            launch_rhs(w, st, A, M, d_cols, n, damp_mass, b1, ld_b, arg, d_v, ld_v, g);
+            launch_rhs(w, st, A, M, D, d_cols, n, damp_mass, b1, ld_b, arg, d_v, ld_v, g);
             e = hipGetLastError();
             if (e == hipSuccess)
               e = solve.solve(h, st, k, n, g, (size_t)n, d_a, ld_a);
@@ -409,7 +469,7 @@ int slod_lod_newmark_accel(slod_handle *h, const double *d_stiffness, const doub
                            const double *d_load, size_t ld_load, double *d_a, size_t ld_a, double rel_tol, int max_iterations,
                            int *iterations, double *rel_residual)
 {
-  return nm_accel(h, "slod_lod_newmark_accel", {SLOD_SOLVE_CG, nullptr, d_cols, d_mass, rel_tol, max_iterations}, {d_stiffness}, {d_mass},
+  return nm_accel(h, "slod_lod_newmark_accel", {SLOD_SOLVE_CG, nullptr, d_cols, d_mass, rel_tol, max_iterations}, {d_stiffness}, {d_mass}, {nullptr},
                   d_cols, damp_mass, damp_stiff, n_rhs, d_u, ld_u, d_v, ld_v, d_load, ld_load, d_a, ld_a, iterations, rel_residual);
 }
 
@@ -418,7 +478,7 @@ int slod_lod_newmark_accel_direct(slod_handle *h, slod_lod_factor *f_M, const do
                                   const uint32_t *d_cols, double damp_mass, double damp_stiff, int n_rhs, const double *d_u, size_t ld_u,
                                   const double *d_v, size_t ld_v, const double *d_load, size_t ld_load, double *d_a, size_t ld_a)
 {
-  return nm_accel(h, "slod_lod_newmark_accel_direct", {SLOD_SOLVE_FACTOR, f_M}, {d_stiffness}, {d_mass}, d_cols, damp_mass, damp_stiff,
+  return nm_accel(h, "slod_lod_newmark_accel_direct", {SLOD_SOLVE_FACTOR, f_M}, {d_stiffness}, {d_mass}, {nullptr}, d_cols, damp_mass, damp_stiff,
                   n_rhs, d_u, ld_u, d_v, ld_v, d_load, ld_load, d_a, ld_a);
 }
 
@@ -429,7 +489,7 @@ int slod_lod_newmark_accel_ensemble_direct(slod_handle *h, slod_lod_factor *f_M,
                                            size_t ld_v, const double *d_load, size_t ld_load, double *d_a, size_t ld_a)
 {
   return nm_accel(h, "slod_lod_newmark_accel_ensemble_direct", {SLOD_SOLVE_FACTOR_PER_COL, f_M}, {d_stiffness, ld_a_m, true},
-                  {d_mass, ld_m_m, true}, d_cols, damp_mass, damp_stiff, n_members, d_u, ld_u, d_v, ld_v, d_load, ld_load, d_a, ld_a);
+                  {d_mass, ld_m_m, true}, {nullptr}, d_cols, damp_mass, damp_stiff, n_members, d_u, ld_u, d_v, ld_v, d_load, ld_load, d_a, ld_a);
 }
 
 int slod_lod_newmark_steps(slod_handle *h, const double *d_stiffness, const double *d_mass, const uint32_t *d_cols, double dt,
@@ -439,7 +499,7 @@ int slod_lod_newmark_steps(slod_handle *h, const double *d_stiffness, const doub
                            double *kinetic, double *potential)
 {
   return nm_steps(h, "slod_lod_newmark_steps", {SLOD_SOLVE_CG, nullptr, d_cols, nullptr, rel_tol, max_iterations, iterations, rel_residual},
-                  {d_stiffness}, {d_mass}, d_cols, dt, beta, gamma, damp_mass, damp_stiff, n_steps, n_rhs, d_u, ld_u, d_v, ld_v, d_a, ld_a,
+                  {d_stiffness}, {d_mass}, {nullptr}, d_cols, dt, beta, gamma, damp_mass, damp_stiff, n_steps, n_rhs, d_u, ld_u, d_v, ld_v, d_a, ld_a,
                   d_load, ld_load, load_step_stride, kinetic, potential);
 }
 
@@ -449,7 +509,7 @@ int slod_lod_newmark_steps_direct(slod_handle *h, slod_lod_factor *f_S, const do
                                   int n_steps, int n_rhs, double *d_u, size_t ld_u, double *d_v, size_t ld_v, double *d_a, size_t ld_a,
                                   const double *d_load, size_t ld_load, size_t load_step_stride, double *kinetic, double *potential)
 {
-  return nm_steps(h, "slod_lod_newmark_steps_direct", {SLOD_SOLVE_FACTOR, f_S}, {d_stiffness}, {d_mass}, d_cols, dt, beta, gamma,
+  return nm_steps(h, "slod_lod_newmark_steps_direct", {SLOD_SOLVE_FACTOR, f_S}, {d_stiffness}, {d_mass}, {nullptr}, d_cols, dt, beta, gamma,
                   damp_mass, damp_stiff, n_steps, n_rhs, d_u, ld_u, d_v, ld_v, d_a, ld_a, d_load, ld_load, load_step_stride, kinetic,
                   potential);
 }
@@ -462,8 +522,52 @@ int slod_lod_newmark_steps_ensemble_direct(slod_handle *h, slod_lod_factor *f_S,
                                            size_t ld_load, size_t load_step_stride, double *kinetic, double *potential)
 {
   return nm_steps(h, "slod_lod_newmark_steps_ensemble_direct", {SLOD_SOLVE_FACTOR_PER_COL, f_S}, {d_stiffness, ld_a_m, true},
-                  {d_mass, ld_m_m, true}, d_cols, dt, beta, gamma, damp_mass, damp_stiff, n_steps, n_members, d_u, ld_u, d_v, ld_v, d_a,
+                  {d_mass, ld_m_m, true}, {nullptr}, d_cols, dt, beta, gamma, damp_mass, damp_stiff, n_steps, n_members, d_u, ld_u, d_v, ld_v, d_a,
                   ld_a, d_load, ld_load, load_step_stride, kinetic, potential);
+}
+
+// The four calls with a third damping matrix, C = damp_mass M + damp_stiff A + D; d_damping NULL: D = 0, the launches and
+// the words of the namesake
+int slod_lod_newmark_accel_damped(slod_handle *h, const double *d_stiffness, const double *d_mass, const double *d_damping,
+                                  const uint32_t *d_cols, double damp_mass, double damp_stiff, int n_rhs, const double *d_u, size_t ld_u,
+                                  const double *d_v, size_t ld_v, const double *d_load, size_t ld_load, double *d_a, size_t ld_a,
+                                  double rel_tol, int max_iterations, int *iterations, double *rel_residual)
+{
+  return nm_accel(h, "slod_lod_newmark_accel_damped", {SLOD_SOLVE_CG, nullptr, d_cols, d_mass, rel_tol, max_iterations}, {d_stiffness},
+                  {d_mass}, {d_damping}, d_cols, damp_mass, damp_stiff, n_rhs, d_u, ld_u, d_v, ld_v, d_load, ld_load, d_a, ld_a,
+                  iterations, rel_residual);
+}
+
+int slod_lod_newmark_accel_damped_direct(slod_handle *h, slod_lod_factor *f_M, const double *d_stiffness, const double *d_mass,
+                                         const double *d_damping, const uint32_t *d_cols, double damp_mass, double damp_stiff,
+                                         int n_rhs, const double *d_u, size_t ld_u, const double *d_v, size_t ld_v,
+                                         const double *d_load, size_t ld_load, double *d_a, size_t ld_a)
+{
+  return nm_accel(h, "slod_lod_newmark_accel_damped_direct", {SLOD_SOLVE_FACTOR, f_M}, {d_stiffness}, {d_mass}, {d_damping}, d_cols,
+                  damp_mass, damp_stiff, n_rhs, d_u, ld_u, d_v, ld_v, d_load, ld_load, d_a, ld_a);
+}
+
+int slod_lod_newmark_steps_damped(slod_handle *h, const double *d_stiffness, const double *d_mass, const double *d_damping,
+                                  const uint32_t *d_cols, double dt, double beta, double gamma, double damp_mass, double damp_stiff,
+                                  int n_steps, int n_rhs, double *d_u, size_t ld_u, double *d_v, size_t ld_v, double *d_a, size_t ld_a,
+                                  const double *d_load, size_t ld_load, size_t load_step_stride, double rel_tol, int max_iterations,
+                                  int *iterations, double *rel_residual, double *kinetic, double *potential)
+{
+  return nm_steps(h, "slod_lod_newmark_steps_damped",
+                  {SLOD_SOLVE_CG, nullptr, d_cols, nullptr, rel_tol, max_iterations, iterations, rel_residual}, {d_stiffness}, {d_mass},
+                  {d_damping}, d_cols, dt, beta, gamma, damp_mass, damp_stiff, n_steps, n_rhs, d_u, ld_u, d_v, ld_v, d_a, ld_a, d_load,
+                  ld_load, load_step_stride, kinetic, potential);
+}
+
+int slod_lod_newmark_steps_damped_direct(slod_handle *h, slod_lod_factor *f_S, const double *d_stiffness, const double *d_mass,
+                                         const double *d_damping, const uint32_t *d_cols, double dt, double beta, double gamma,
+                                         double damp_mass, double damp_stiff, int n_steps, int n_rhs, double *d_u, size_t ld_u,
+                                         double *d_v, size_t ld_v, double *d_a, size_t ld_a, const double *d_load, size_t ld_load,
+                                         size_t load_step_stride, double *kinetic, double *potential)
+{
+  return nm_steps(h, "slod_lod_newmark_steps_damped_direct", {SLOD_SOLVE_FACTOR, f_S}, {d_stiffness}, {d_mass}, {d_damping}, d_cols, dt,
+                  beta, gamma, damp_mass, damp_stiff, n_steps, n_rhs, d_u, ld_u, d_v, ld_v, d_a, ld_a, d_load, ld_load, load_step_stride,
+                  kinetic, potential);
 }
 
 } // extern "C"

@@ -1187,6 +1187,54 @@ namespace slod
   }
 
   template <int dim, int spacedim>
+  void LOD<dim, spacedim>::assemble_damping_matrix(const std::vector<double> &sigma)
+  {
+    if (!d_lod_values)
+      throw std::runtime_error("assemble_damping_matrix: assemble_global_matrix comes first");
+    const unsigned int n_patches = (unsigned int)patches.size();
+    const std::size_t  NE = (std::size_t)(1u << par.n_global_refinements) * par.n_subdivisions;
+    if (sigma.size() != NE * NE)
+      throw std::runtime_error("assemble_damping_matrix: sigma has one value per fine element");
+    const int cap = slod_lod_row_capacity(handle);
+    check(cap, "slod_lod_row_capacity");
+    const std::size_t n_slots = (std::size_t)n_patches * cap, n_values = n_slots * spacedim * spacedim;
+    if (!d_lod_damping)
+      d_lod_damping = device_alloc<double>(n_values);
+    double *d_sigma = device_alloc<double>(sigma.size());
+    if (hipMemcpy(d_sigma, sigma.data(), sigma.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+      throw std::runtime_error("assemble_damping_matrix: upload of sigma failed");
+    uint32_t *d_m_cols = nullptr;
+    if (hipMalloc((void **)&d_m_cols, n_slots * sizeof(uint32_t)) != hipSuccess)
+      throw std::runtime_error("assemble_damping_matrix: hipMalloc of the columns failed");
+    std::vector<uint32_t> rows(n_patches);
+    for (unsigned int p = 0; p < n_patches; ++p)
+      rows[p] = p;
+    const int             rc = slod_lod_mass_matrix(handle, rows.data(), n_patches, d_basis, basis_stride, d_sigma, d_lod_damping,
+                                                    d_m_cols, nullptr);
+    std::vector<uint32_t> m_cols(n_slots), a_cols(n_slots);
+    std::vector<double>   values(n_values);
+    const bool            copied = rc == SLOD_OK &&
+                        hipMemcpy(m_cols.data(), d_m_cols, n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess &&
+                        hipMemcpy(a_cols.data(), d_lod_cols, n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess &&
+                        hipMemcpy(values.data(), d_lod_damping, n_values * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(d_m_cols);
+    check(rc, "slod_lod_mass_matrix");
+    if (!copied || m_cols != a_cols)
+      throw std::runtime_error("assemble_damping_matrix: the pattern of D_LOD differs from that of A_LOD");
+    lod_damping_zero_rows = 0;
+    for (unsigned int p = 0; p < n_patches; ++p)
+      for (int d = 0; d < spacedim; ++d)
+        {
+          bool zero = true;
+          for (int j = 0; j < cap; ++j)
+            if (a_cols[(std::size_t)p * cap + j] < n_patches)
+              for (int e = 0; e < spacedim; ++e)
+                zero = zero && values[((std::size_t)p * cap + j) * spacedim * spacedim + d * spacedim + e] == 0.0;
+          lod_damping_zero_rows += zero;
+        }
+  }
+
+  template <int dim, int spacedim>
   slod_lod_factor *LOD<dim, spacedim>::factor_lod_matrix(const double *d_values, const bool ldl)
   {
     slod_lod_factor *f = nullptr;
@@ -1378,6 +1426,23 @@ namespace slod
     check(slod_lod_rhs(handle, rows.data(), n_patches, d_basis, basis_stride, d_fem_rhs, d_b, nullptr), "slod_lod_rhs");
     lod_harmonic_growth.assign(K, 0.0);
     lod_harmonic_residuals.assign(K, 0.0);
+    lod_harmonic_amplitude.assign(K, 0.0);
+    lod_harmonic_power.assign(K, 0.0);
+    if (d_lod_damping) // the sponge: S gains i omega D, and the call returns u^H M u, u^H A u and u^H D u
+      {
+        std::vector<double> quantities(5 * K);
+        check(slod_lod_harmonic_response_damped(handle, d_lod_sym, d_lod_mass, d_lod_damping, d_lod_cols, damp_mass, damp_stiff,
+                                                omegas.data(), (int)K, d_b, nullptr, 1, 1, d_ur, d_ui, K, lod_harmonic_residuals.data(),
+                                                lod_harmonic_growth.data(), quantities.data()),
+              "slod_lod_harmonic_response_damped");
+        for (std::size_t k = 0; k < K; ++k)
+          {
+            const double *q = quantities.data() + 5 * k;
+            lod_harmonic_amplitude[k] = std::sqrt(q[0]);
+            lod_harmonic_power[k]     = 0.5 * omegas[k] * (damp_mass * q[0] + damp_stiff * q[1] + q[2]);
+          }
+        return;
+      }
     check(slod_lod_harmonic_response(handle, d_lod_sym, d_lod_mass, d_lod_cols, damp_mass, damp_stiff, omegas.data(), (int)K, d_b,
                                      nullptr, 1, 1, d_ur, d_ui, K, lod_harmonic_residuals.data(), lod_harmonic_growth.data()),
           "slod_lod_harmonic_response");
@@ -1387,8 +1452,6 @@ namespace slod
     check(slod_lod_inner_multi(handle, d_lod_mass, d_lod_cols, d_ui, K, d_ui, K, (int)K, q[1].data(), nullptr), "slod_lod_inner_multi");
     check(slod_lod_inner_multi(handle, d_lod_sym, d_lod_cols, d_ur, K, d_ur, K, (int)K, q[2].data(), nullptr), "slod_lod_inner_multi");
     check(slod_lod_inner_multi(handle, d_lod_sym, d_lod_cols, d_ui, K, d_ui, K, (int)K, q[3].data(), nullptr), "slod_lod_inner_multi");
-    lod_harmonic_amplitude.assign(K, 0.0);
-    lod_harmonic_power.assign(K, 0.0);
     for (std::size_t k = 0; k < K; ++k)
       {
         const double uMu = q[0][k] + q[1][k], uAu = q[2][k] + q[3][k];
@@ -1437,22 +1500,26 @@ namespace slod
     if (direct)
       {
         // the factor of M for the initial acceleration, then that of S = M + beta dt^2 A (no damping) for every step
-        check(slod_lod_newmark_accel_direct(handle, factor_lod_matrix(d_lod_mass), d_lod_sym, d_lod_mass, d_lod_cols, 0.0, 0.0, 1, d_u,
-                                            1, d_v, 1, d_b0, 1, d_a, 1),
-              "slod_lod_newmark_accel_direct");
+        // (with a sponge D the _damped calls; without one they are the calls they extend)
+        check(slod_lod_newmark_accel_damped_direct(handle, factor_lod_matrix(d_lod_mass), d_lod_sym, d_lod_mass, d_lod_damping,
+                                                   d_lod_cols, 0.0, 0.0, 1, d_u, 1, d_v, 1, d_b0, 1, d_a, 1),
+              "slod_lod_newmark_accel_damped_direct");
         if (!d_lod_shifted)
           d_lod_shifted = device_alloc<double>((std::size_t)n_patches * cap * spacedim * spacedim);
         check(slod_lod_matrix_combine(handle, 1.0, d_lod_mass, beta * dt * dt, d_lod_sym, d_lod_shifted, nullptr),
               "slod_lod_matrix_combine");
+        if (d_lod_damping) // S + gamma dt D, the second rounding of the CG call
+          check(slod_lod_matrix_combine(handle, 1.0, d_lod_shifted, gamma * dt, d_lod_damping, d_lod_shifted, nullptr),
+                "slod_lod_matrix_combine");
         if (hipDeviceSynchronize() != hipSuccess)
           throw std::runtime_error("solve_wave: forming S failed");
         f_S = factor_lod_matrix(d_lod_shifted);
       }
     else
       {
-        const int rc = slod_lod_newmark_accel(handle, d_lod_sym, d_lod_mass, d_lod_cols, 0.0, 0.0, 1, d_u, 1, d_v, 1, d_b0, 1, d_a, 1,
-                                              lod_rel_tol, lod_max_iterations, nullptr, nullptr);
-        check(rc < 0 ? rc : 0, "slod_lod_newmark_accel");
+        const int rc = slod_lod_newmark_accel_damped(handle, d_lod_sym, d_lod_mass, d_lod_damping, d_lod_cols, 0.0, 0.0, 1, d_u, 1, d_v,
+                                                     1, d_b0, 1, d_a, 1, lod_rel_tol, lod_max_iterations, nullptr, nullptr);
+        check(rc < 0 ? rc : 0, "slod_lod_newmark_accel_damped");
       }
     lod_wave_iterations.assign(n_steps, 0);
     lod_wave_residuals.assign(n_steps, 0.0);
@@ -1466,15 +1533,16 @@ namespace slod
         double    kinetic[2], potential[2];
         source_arm(k);
         if (direct)
-          check(slod_lod_newmark_steps_direct(handle, f_S, d_lod_sym, d_lod_mass, d_lod_cols, dt, beta, gamma, 0.0, 0.0, 1, 1, d_u, 1,
-                                              d_v, 1, d_a, 1, own_load(d_b), 1, 0, kinetic, potential),
-                "slod_lod_newmark_steps_direct");
+          check(slod_lod_newmark_steps_damped_direct(handle, f_S, d_lod_sym, d_lod_mass, d_lod_damping, d_lod_cols, dt, beta, gamma, 0.0,
+                                                     0.0, 1, 1, d_u, 1, d_v, 1, d_a, 1, own_load(d_b), 1, 0, kinetic, potential),
+                "slod_lod_newmark_steps_damped_direct");
         else
           {
-            const int its = slod_lod_newmark_steps(handle, d_lod_sym, d_lod_mass, d_lod_cols, dt, beta, gamma, 0.0, 0.0, 1, 1, d_u, 1,
-                                                   d_v, 1, d_a, 1, own_load(d_b), 1, 0, lod_rel_tol, lod_max_iterations,
-                                                   &lod_wave_iterations[k], &lod_wave_residuals[k], kinetic, potential);
-            check(its < 0 ? its : 0, "slod_lod_newmark_steps");
+            const int its = slod_lod_newmark_steps_damped(handle, d_lod_sym, d_lod_mass, d_lod_damping, d_lod_cols, dt, beta, gamma, 0.0,
+                                                          0.0, 1, 1, d_u, 1, d_v, 1, d_a, 1, own_load(d_b), 1, 0, lod_rel_tol,
+                                                          lod_max_iterations, &lod_wave_iterations[k], &lod_wave_residuals[k], kinetic,
+                                                          potential);
+            check(its < 0 ? its : 0, "slod_lod_newmark_steps_damped");
           }
         record_state(k + 1, d_u, d_v);
         if (hipMemcpy(u.data(), d_u, n_coarse * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
@@ -1505,8 +1573,17 @@ namespace slod
     if (slod_lod_irk_coefficients(scheme, order, dt, 0.0, 0.0, alpha, beta) != SLOD_OK)
       throw std::runtime_error(std::string("slod_lod_irk_coefficients: ") + slod_last_error(nullptr));
     slod_lod_factor *f = nullptr;
-    check(slod_lod_factor_create_zldl(handle, d_lod_sym, d_lod_mass, d_lod_cols, alpha, beta, 1, nullptr, &f),
-          "slod_lod_factor_create_zldl");
+    if (d_lod_damping && order == 2) // the sponge: S + z D
+      {
+        double z[2];
+        if (slod_lod_irk_damping_coefficient(scheme, dt, z) != SLOD_OK)
+          throw std::runtime_error(std::string("slod_lod_irk_damping_coefficient: ") + slod_last_error(nullptr));
+        check(slod_lod_factor_create_zldl3(handle, d_lod_sym, d_lod_mass, d_lod_damping, d_lod_cols, alpha, beta, z, 1, nullptr, &f),
+              "slod_lod_factor_create_zldl3");
+      }
+    else
+      check(slod_lod_factor_create_zldl(handle, d_lod_sym, d_lod_mass, d_lod_cols, alpha, beta, 1, nullptr, &f),
+            "slod_lod_factor_create_zldl");
     factors.push_back(f);
     check(slod_lod_factor_get_info(f, &lod_factor_info), "slod_lod_factor_get_info");
     check(slod_lod_factor_inertia(f, 0, &lod_factor_inertia), "slod_lod_factor_inertia");
@@ -1592,9 +1669,9 @@ namespace slod
       {
         double kinetic[2], potential[2];
         source_arm(2 * k);
-        check(slod_lod_irk_wave_steps_direct(handle, f, 0, scheme, d_lod_sym, d_lod_mass, d_lod_cols, dt, 0.0, 0.0, 1, 1, d_u, 1, d_v, 1,
-                                             own_load(d_b), 1, 0, kinetic, potential),
-              "slod_lod_irk_wave_steps_direct");
+        check(slod_lod_irk_wave_steps_damped_direct(handle, f, 0, scheme, d_lod_sym, d_lod_mass, d_lod_damping, d_lod_cols, dt, 0.0, 0.0,
+                                                    1, 1, d_u, 1, d_v, 1, own_load(d_b), 1, 0, kinetic, potential),
+              "slod_lod_irk_wave_steps_damped_direct");
         record_state(k + 1, d_u, d_v);
         if (hipMemcpy(u.data(), d_u, n_coarse * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
           throw std::runtime_error("solve_wave_irk: download of the state failed");

@@ -137,6 +137,12 @@ namespace slod
     // M_LOD = C^T M C (consistent Q1 mass, density 1) in the pattern of A_LOD, after assemble_global_matrix() (the
     // reference has no counterpart: it has no time-dependent problem)
     void assemble_mass_matrix();
+    // A sponge layer: D_LOD = C^T M_sigma C (slod_lod_mass_matrix with the density sigma per fine element, [NE * NE], ex
+    // fastest, sigma >= 0) in the pattern of A_LOD, after assemble_global_matrix().  Once it is set, solve_wave,
+    // solve_wave_irk and solve_harmonic add D u' to the model (the slod_lod_*_damped calls and slod_lod_factor_create_zldl3)
+    // and solve_harmonic's power includes u^H D u.  damping_zero_rows(): the coarse rows of D that are zero.
+    void         assemble_damping_matrix(const std::vector<double> &sigma);
+    unsigned int damping_zero_rows() const { return lod_damping_zero_rows; }
     // n_steps of the theta scheme for M u' + A u = C^T f_h from u = 0 with the load of solve(), constant in time,
     // through slod_lod_theta_steps; after assemble_mass_matrix() and assemble_and_solve_fem_problem()
     // direct: the steps run on the banded Cholesky factor of S = M + theta dt A_LOD (lower triangle; factor_lod_matrix,
@@ -405,6 +411,8 @@ namespace slod
     double             *d_fem_coarse_solution = nullptr, *d_fem_coarse_interpolated = nullptr;
     slod_error_norms    lod_fem_error{}, fem_norms{}, femH_fem_error{};
     // assemble_mass_matrix, solve_heat
+    double             *d_lod_damping = nullptr; // assemble_damping_matrix
+    unsigned int        lod_damping_zero_rows = 0;
     double             *d_lod_mass = nullptr, *d_heat_rhs = nullptr, *d_heat_u = nullptr, *d_heat_fine = nullptr;
     std::vector<int>    lod_heat_iterations;
     std::vector<double> lod_heat_residuals;

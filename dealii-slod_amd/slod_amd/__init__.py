@@ -245,6 +245,24 @@ def load():
     lib.slod_lod_irk_wave_steps_ensemble_direct.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp,
                                                             C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.c_size_t,
                                                             vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, dp, dp]
+    lib.slod_lod_newmark_accel_damped.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, C.c_size_t, vp,
+                                                  C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_double, C.c_int,
+                                                  C.POINTER(C.c_int), dp]
+    lib.slod_lod_newmark_steps_damped.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                  C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp,
+                                                  C.c_size_t, C.c_size_t, C.c_double, C.c_int, C.POINTER(C.c_int), dp, dp, dp]
+    lib.slod_lod_newmark_accel_damped_direct.argtypes = [vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, C.c_size_t,
+                                                         vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t]
+    lib.slod_lod_newmark_steps_damped_direct.argtypes = [vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                         C.c_double, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp,
+                                                         C.c_size_t, vp, C.c_size_t, C.c_size_t, dp, dp]
+    lib.slod_lod_factor_create_zldl3.argtypes = [vp, vp, vp, vp, vp, dp, dp, dp, C.c_int, C.POINTER(C.c_int32), C.POINTER(vp)]
+    lib.slod_lod_irk_damping_coefficient.argtypes = [C.c_int, C.c_double, dp]
+    lib.slod_lod_irk_wave_steps_damped_direct.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_double, C.c_double,
+                                                          C.c_double, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp,
+                                                          C.c_size_t, C.c_size_t, dp, dp]
+    lib.slod_lod_harmonic_response_damped.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.c_double, dp, C.c_int, vp, vp, C.c_size_t,
+                                                      C.c_int, vp, vp, C.c_size_t, dp, dp, dp]
     lib.slod_lod_receiver_capacity.argtypes = [vp]
     lib.slod_lod_receiver_pattern.argtypes = [vp, C.c_uint32, u32p, C.c_size_t]
     lib.slod_lod_receivers_create.argtypes = [vp, C.c_int, u32p, u32p, C.POINTER(C.c_int32), dp, vp, C.c_size_t, C.c_size_t,
@@ -502,9 +520,11 @@ class ComplexFactor(EnsembleFactor):
     range of |D|, .inertia(k) the two norms (n_negative = n_positive = -1), .bad_pivot as EnsembleFactor.
     matrix_members = K (slod_lod_factor_create_zldl_ensemble): d_a, d_b are ensemble matrices of K members, alpha and beta
     have one entry per coefficient pair, and the factor member j = k K + m is pair k on the matrices of member m
-    (.n_members = len(alpha) * K, .n_coef = len(alpha))."""
+    (.n_members = len(alpha) * K, .n_coef = len(alpha)).
+    d_c, gamma (slod_lod_factor_create_zldl3, single matrices only): S_k = alpha_k A + beta_k B + gamma_k C."""
 
-    def __init__(self, slod, d_a, d_b, d_cols, alpha, beta, matrix_members=None, ld_a_m=None, ld_b_m=None):
+    def __init__(self, slod, d_a, d_b, d_cols, alpha, beta, matrix_members=None, ld_a_m=None, ld_b_m=None, d_c=None,
+                 gamma=None):
         self.slod, self.lib = slod, slod.lib
         self.alpha = np.atleast_1d(np.asarray(alpha, dtype=np.complex128)).copy()
         self.beta = np.atleast_1d(np.asarray(beta, dtype=np.complex128)).copy()
@@ -515,7 +535,17 @@ class ComplexFactor(EnsembleFactor):
         self.n_members = n_members = self.n_coef * (1 if matrix_members is None else max(matrix_members, 0))
         self.f = C.c_void_p()
         self.bad_pivot = np.full(max(n_members, 1), -1, dtype=np.int32)
-        if matrix_members is None:
+        if gamma is not None:
+            if matrix_members is not None:
+                raise ValueError("a third term takes single matrices")
+            self.gamma = np.atleast_1d(np.asarray(gamma, dtype=np.complex128)).copy()
+            if self.gamma.shape != self.alpha.shape:
+                raise ValueError("gamma: one complex number per member")
+            rc = self.lib.slod_lod_factor_create_zldl3(slod.h, d_a, d_b, d_c, d_cols, _dp(self.alpha.view(np.float64)),
+                                                       _dp(self.beta.view(np.float64)), _dp(self.gamma.view(np.float64)),
+                                                       n_members, self.bad_pivot.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                       C.byref(self.f))
+        elif matrix_members is None:
             rc = self.lib.slod_lod_factor_create_zldl(slod.h, d_a, d_b, d_cols, _dp(self.alpha.view(np.float64)),
                                                       _dp(self.beta.view(np.float64)), n_members,
                                                       self.bad_pivot.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(self.f))
@@ -553,6 +583,17 @@ class ComplexFactor(EnsembleFactor):
         self.slod._check(self.lib.slod_lod_factor_solve_complex(self.f, first_member, K, d_rhs_re, d_rhs_im, ld_rhs, n_rhs,
                                                                 1 if shared_rhs else 0, d_u_re, d_u_im,
                                                                 K * n_rhs if ld_u is None else ld_u, stream))
+
+
+def sponge_profile(NE, width, sigma_max):
+    """The damping coefficient of a sponge layer per fine element, [NE * NE] with ex fastest (the d_rho of lod_mass_matrix):
+    sigma = sigma_max * max(0, 1 - d / width)^2, d the distance of the element's centre from the rim of the unit square."""
+    if not (NE >= 1 and width > 0.0 and sigma_max >= 0.0):
+        raise ValueError("sponge_profile: NE >= 1, width > 0, sigma_max >= 0")
+    x = (np.arange(NE) + 0.5) / NE
+    d1 = np.minimum(x, 1.0 - x)
+    d = np.minimum(d1[:, None], d1[None, :])                      # [ey][ex]
+    return np.ascontiguousarray((sigma_max * np.maximum(0.0, 1.0 - d / width) ** 2).reshape(-1), dtype=np.float64)
 
 
 def point_terms(NE, s, x, y, comp=0):
@@ -911,35 +952,42 @@ class Slod:
         return out[:n_rhs]
 
     def lod_newmark_accel(self, d_stiffness, d_mass, d_cols, d_u, d_v, d_a, n_rhs=1, ld_u=None, ld_v=None, ld_a=None,
-                          d_load=None, ld_load=None, damp_mass=0.0, damp_stiff=0.0, rel_tol=1e-12, max_iterations=2000):
+                          d_load=None, ld_load=None, damp_mass=0.0, damp_stiff=0.0, rel_tol=1e-12, max_iterations=2000,
+                          d_damping=None):
         """d_a = the solution of M a = b^0 - A (u + damp_stiff v) - damp_mass M v per column.  Returns
-        (iterations, rel_residual), one entry per column; max(iterations) is the C call's return value."""
+        (iterations, rel_residual), one entry per column; max(iterations) is the C call's return value.
+        d_damping: the third damping matrix D (slod_lod_newmark_accel_damped), - D v joins the right-hand side."""
         its = np.zeros(max(n_rhs, 1), dtype=np.intc)
         res = np.zeros(max(n_rhs, 1))
-        rc = self.lib.slod_lod_newmark_accel(self.h, d_stiffness, d_mass, d_cols, damp_mass, damp_stiff, n_rhs, d_u,
-                                             n_rhs if ld_u is None else ld_u, d_v, n_rhs if ld_v is None else ld_v, d_load,
-                                             n_rhs if ld_load is None else ld_load, d_a, n_rhs if ld_a is None else ld_a,
-                                             rel_tol, max_iterations, its.ctypes.data_as(C.POINTER(C.c_int)), _dp(res))
+        fn, mats = (self.lib.slod_lod_newmark_accel, (d_stiffness, d_mass)) if d_damping is None else \
+            (self.lib.slod_lod_newmark_accel_damped, (d_stiffness, d_mass, d_damping))
+        rc = fn(self.h, *mats, d_cols, damp_mass, damp_stiff, n_rhs, d_u,
+                n_rhs if ld_u is None else ld_u, d_v, n_rhs if ld_v is None else ld_v, d_load,
+                n_rhs if ld_load is None else ld_load, d_a, n_rhs if ld_a is None else ld_a,
+                rel_tol, max_iterations, its.ctypes.data_as(C.POINTER(C.c_int)), _dp(res))
         if rc < 0:
             self._check(rc)
         return its[:n_rhs], res[:n_rhs]
 
     def lod_newmark_steps(self, d_stiffness, d_mass, d_cols, dt, n_steps, d_u, d_v, d_a, beta=0.25, gamma=0.5, n_rhs=1,
                           ld_u=None, ld_v=None, ld_a=None, d_load=None, ld_load=None, load_step_stride=0, damp_mass=0.0,
-                          damp_stiff=0.0, rel_tol=1e-12, max_iterations=2000, energies=True):
+                          damp_stiff=0.0, rel_tol=1e-12, max_iterations=2000, energies=True, d_damping=None):
         """n_steps of Newmark-beta on d_u, d_v, d_a in place.  Returns (iterations, rel_residual, kinetic, potential):
         the first two with one entry per step, the energies as arrays [n_steps + 1, n_rhs] (row 0: the entry state), or
-        None for both with energies=False; max(iterations) is the C call's return value."""
+        None for both with energies=False; max(iterations) is the C call's return value.
+        d_damping: the third damping matrix D (slod_lod_newmark_steps_damped)."""
         its = np.zeros(max(n_steps, 1), dtype=np.intc)
         res = np.zeros(max(n_steps, 1))
         shape = (max(n_steps, 0) + 1, max(n_rhs, 1))
         kin, pot = (np.zeros(shape), np.zeros(shape)) if energies else (None, None)
-        rc = self.lib.slod_lod_newmark_steps(self.h, d_stiffness, d_mass, d_cols, dt, beta, gamma, damp_mass, damp_stiff,
-                                             n_steps, n_rhs, d_u, n_rhs if ld_u is None else ld_u, d_v,
-                                             n_rhs if ld_v is None else ld_v, d_a, n_rhs if ld_a is None else ld_a, d_load,
-                                             n_rhs if ld_load is None else ld_load, load_step_stride, rel_tol, max_iterations,
-                                             its.ctypes.data_as(C.POINTER(C.c_int)), _dp(res),
-                                             _dp(kin) if energies else None, _dp(pot) if energies else None)
+        fn, mats = (self.lib.slod_lod_newmark_steps, (d_stiffness, d_mass)) if d_damping is None else \
+            (self.lib.slod_lod_newmark_steps_damped, (d_stiffness, d_mass, d_damping))
+        rc = fn(self.h, *mats, d_cols, dt, beta, gamma, damp_mass, damp_stiff,
+                n_steps, n_rhs, d_u, n_rhs if ld_u is None else ld_u, d_v,
+                n_rhs if ld_v is None else ld_v, d_a, n_rhs if ld_a is None else ld_a, d_load,
+                n_rhs if ld_load is None else ld_load, load_step_stride, rel_tol, max_iterations,
+                its.ctypes.data_as(C.POINTER(C.c_int)), _dp(res),
+                _dp(kin) if energies else None, _dp(pot) if energies else None)
         if rc < 0:
             self._check(rc)
         return its[:n_steps], res[:n_steps], kin, pot
@@ -960,6 +1008,10 @@ class Slod:
         """The complex symmetric LDL^T factors of S_k = alpha[k] A + beta[k] B (no pivoting), one member per pair of
         complex coefficients: a ComplexFactor with .info, .inertia(member), .solve_complex(...) and .close()."""
         return ComplexFactor(self, d_a, d_b, d_cols, alpha, beta)
+
+    def lod_factor_zldl3(self, d_a, d_b, d_c, d_cols, alpha, beta, gamma):
+        """lod_factor_zldl with a third term: S_k = alpha[k] A + beta[k] B + gamma[k] C (slod_lod_factor_create_zldl3)."""
+        return ComplexFactor(self, d_a, d_b, d_cols, alpha, beta, d_c=d_c, gamma=gamma)
 
     def lod_factor_zldl_ensemble(self, d_a, d_b, d_cols, n_members, alpha, beta, ld_a_m=None, ld_b_m=None):
         """lod_factor_zldl on ensemble matrices of n_members members: the factor member j = k * n_members + m is
@@ -983,12 +1035,21 @@ class Slod:
         return res, growth, q
 
     def lod_harmonic_response(self, d_stiffness, d_mass, d_cols, omega, d_load_re, d_load_im, d_u_re, d_u_im, n_rhs=1,
-                              damp_mass=0.0, damp_stiff=0.0, ld_load=None, ld_u=None):
+                              damp_mass=0.0, damp_stiff=0.0, ld_load=None, ld_u=None, d_damping=None):
         """S(omega_k) u = load for every frequency of omega, S = (1 + i omega damp_stiff) A + (i omega damp_mass - omega^2) M;
         frequency k writes the columns k * n_rhs .. of (d_u_re, d_u_im).  d_load_im None: a real load.  Returns
-        (rel_residual[n_freq, n_rhs], growth[n_freq])."""
+        (rel_residual[n_freq, n_rhs], growth[n_freq]).
+        d_damping: the third damping matrix D (slod_lod_harmonic_response_damped), S gains i omega D; the call then also
+        returns quantities[n_freq, n_rhs, 5] = (u^H M u, u^H A u, u^H D u, Re u^H b, Im u^H b)."""
         w = np.ascontiguousarray(np.atleast_1d(omega), dtype=np.float64)
         res, growth = np.zeros((len(w), max(n_rhs, 1))), np.zeros(len(w))
+        if d_damping is not None:
+            q = np.zeros((len(w), max(n_rhs, 1), 5))
+            self._check(self.lib.slod_lod_harmonic_response_damped(
+                self.h, d_stiffness, d_mass, d_damping, d_cols, damp_mass, damp_stiff, _dp(w), len(w), d_load_re, d_load_im,
+                n_rhs if ld_load is None else ld_load, n_rhs, d_u_re, d_u_im, len(w) * n_rhs if ld_u is None else ld_u,
+                _dp(res), _dp(growth), _dp(q)))
+            return res, growth, q
         self._check(self.lib.slod_lod_harmonic_response(
             self.h, d_stiffness, d_mass, d_cols, damp_mass, damp_stiff, _dp(w), len(w), d_load_re, d_load_im,
             n_rhs if ld_load is None else ld_load, n_rhs, d_u_re, d_u_im, len(w) * n_rhs if ld_u is None else ld_u,
@@ -1003,22 +1064,27 @@ class Slod:
                                                          n_rhs if ld_load is None else ld_load, load_step_stride))
 
     def lod_newmark_accel_direct(self, factor, d_stiffness, d_mass, d_cols, d_u, d_v, d_a, n_rhs=1, ld_u=None, ld_v=None,
-                                 ld_a=None, d_load=None, ld_load=None, damp_mass=0.0, damp_stiff=0.0):
-        """lod_newmark_accel on the factor of M."""
-        self._check(self.lib.slod_lod_newmark_accel_direct(
-            self.h, _factor_ptr(factor), d_stiffness, d_mass, d_cols, damp_mass, damp_stiff, n_rhs, d_u,
+                                 ld_a=None, d_load=None, ld_load=None, damp_mass=0.0, damp_stiff=0.0, d_damping=None):
+        """lod_newmark_accel on the factor of M; d_damping: slod_lod_newmark_accel_damped_direct."""
+        fn, mats = (self.lib.slod_lod_newmark_accel_direct, (d_stiffness, d_mass)) if d_damping is None else \
+            (self.lib.slod_lod_newmark_accel_damped_direct, (d_stiffness, d_mass, d_damping))
+        self._check(fn(
+            self.h, _factor_ptr(factor), *mats, d_cols, damp_mass, damp_stiff, n_rhs, d_u,
             n_rhs if ld_u is None else ld_u, d_v, n_rhs if ld_v is None else ld_v, d_load,
             n_rhs if ld_load is None else ld_load, d_a, n_rhs if ld_a is None else ld_a))
 
     def lod_newmark_steps_direct(self, factor, d_stiffness, d_mass, d_cols, dt, n_steps, d_u, d_v, d_a, beta=0.25, gamma=0.5,
                                  n_rhs=1, ld_u=None, ld_v=None, ld_a=None, d_load=None, ld_load=None, load_step_stride=0,
-                                 damp_mass=0.0, damp_stiff=0.0, energies=True):
+                                 damp_mass=0.0, damp_stiff=0.0, energies=True, d_damping=None):
         """lod_newmark_steps on the factor of S = (1 + gamma dt damp_mass) M + (beta dt^2 + gamma dt damp_stiff) A.
-        Returns (kinetic, potential) as arrays [n_steps + 1, n_rhs], or (None, None) with energies=False."""
+        Returns (kinetic, potential) as arrays [n_steps + 1, n_rhs], or (None, None) with energies=False.
+        d_damping: the third damping matrix D (slod_lod_newmark_steps_damped_direct) on the factor of S + gamma dt D."""
         shape = (max(n_steps, 0) + 1, max(n_rhs, 1))
         kin, pot = (np.zeros(shape), np.zeros(shape)) if energies else (None, None)
-        self._check(self.lib.slod_lod_newmark_steps_direct(
-            self.h, _factor_ptr(factor), d_stiffness, d_mass, d_cols, dt, beta, gamma, damp_mass, damp_stiff, n_steps, n_rhs,
+        fn, mats = (self.lib.slod_lod_newmark_steps_direct, (d_stiffness, d_mass)) if d_damping is None else \
+            (self.lib.slod_lod_newmark_steps_damped_direct, (d_stiffness, d_mass, d_damping))
+        self._check(fn(
+            self.h, _factor_ptr(factor), *mats, d_cols, dt, beta, gamma, damp_mass, damp_stiff, n_steps, n_rhs,
             d_u, n_rhs if ld_u is None else ld_u, d_v, n_rhs if ld_v is None else ld_v, d_a, n_rhs if ld_a is None else ld_a,
             d_load, n_rhs if ld_load is None else ld_load, load_step_stride, _dp(kin) if energies else None,
             _dp(pot) if energies else None))
@@ -1034,6 +1100,15 @@ class Slod:
             raise SlodError(rc, self.lib.slod_last_error(None).decode())
         return complex(a[0], a[1]), complex(b[0], b[1])
 
+    def lod_irk_damping_coefficient(self, scheme, dt):
+        """gamma = dt lambda, complex: the coefficient of D in the step matrix of the damped wave, for lod_factor_zldl3 with
+        the pair of lod_irk_coefficients(scheme, 2, ..)."""
+        g = np.zeros(2)
+        rc = self.lib.slod_lod_irk_damping_coefficient(_irk_scheme(scheme), dt, _dp(g))
+        if rc:
+            raise SlodError(rc, self.lib.slod_last_error(None).decode())
+        return complex(g[0], g[1])
+
     def lod_irk_heat_steps(self, factor, scheme, d_stiffness, d_cols, dt, n_steps, d_u, n_rhs=1, member=0, ld_u=None,
                            d_load=None, ld_load=None, load_stage_stride=0):
         """n_steps of the two-stage scheme for M u' + A u = b(t) on d_u in place, on member `member` of the complex
@@ -1045,14 +1120,18 @@ class Slod:
 
     def lod_irk_wave_steps(self, factor, scheme, d_stiffness, d_mass, d_cols, dt, n_steps, d_u, d_v, n_rhs=1, member=0,
                            ld_u=None, ld_v=None, d_load=None, ld_load=None, load_stage_stride=0, damp_mass=0.0,
-                           damp_stiff=0.0, energies=True):
+                           damp_stiff=0.0, energies=True, d_damping=None):
         """n_steps of the two-stage scheme for M u'' + C u' + A u = b(t) on d_u, d_v in place, on member `member` of the
         complex factor of lod_irk_coefficients(scheme, 2, dt, damp_mass, damp_stiff).  Returns (kinetic, potential) as
-        arrays [n_steps + 1, n_rhs], or (None, None) with energies=False."""
+        arrays [n_steps + 1, n_rhs], or (None, None) with energies=False.
+        d_damping: the third damping matrix D (slod_lod_irk_wave_steps_damped_direct), on a member of lod_factor_zldl3 with
+        gamma = lod_irk_damping_coefficient(scheme, dt)."""
         shape = (max(n_steps, 0) + 1, max(n_rhs, 1))
         kin, pot = (np.zeros(shape), np.zeros(shape)) if energies else (None, None)
-        self._check(self.lib.slod_lod_irk_wave_steps_direct(
-            self.h, _factor_ptr(factor), member, _irk_scheme(scheme), d_stiffness, d_mass, d_cols, dt, damp_mass, damp_stiff,
+        fn, mats = (self.lib.slod_lod_irk_wave_steps_direct, (d_stiffness, d_mass)) if d_damping is None else \
+            (self.lib.slod_lod_irk_wave_steps_damped_direct, (d_stiffness, d_mass, d_damping))
+        self._check(fn(
+            self.h, _factor_ptr(factor), member, _irk_scheme(scheme), *mats, d_cols, dt, damp_mass, damp_stiff,
             n_steps, n_rhs, d_u, n_rhs if ld_u is None else ld_u, d_v, n_rhs if ld_v is None else ld_v, d_load,
             n_rhs if ld_load is None else ld_load, load_stage_stride, _dp(kin) if energies else None,
             _dp(pot) if energies else None))

@@ -1254,6 +1254,92 @@ typedef struct
 } slod_lod_time_source;
 int slod_lod_time_source_arm(slod_handle *h, const slod_lod_time_source *s /* NULL disarms */);
 
+/* ---- sponge layers: a third damping matrix in the wave steppers and the frequency response ----
+ * The calls above damp with Rayleigh's C = damp_mass M + damp_stiff A, the same everywhere, in a box with a homogeneous
+ * Dirichlet rim: a wavelet returns from the rim.  A sponge is a coefficient sigma(x) >= 0 that is zero in the region of
+ * interest and grows towards the rim.  These calls take the model
+ *   M u'' + (damp_mass M + damp_stiff A + D) u' + A u = b(t)
+ * with D a full set of block rows on the d_cols of A and M, typically slod_lod_mass_matrix(.., d_rho = sigma, ..), that is
+ * D_LOD = C^T M_sigma C, bit-symmetric like M_LOD.  Any symmetric positive semi-definite matrix in that layout is allowed;
+ * it may have zero rows (be rank deficient).  Semi-definiteness is the caller's business, as the positivity of a shift is
+ * elsewhere: nothing checks it, and a D with a negative direction feeds energy.
+ * In every call d_damping == NULL means D = 0: the call then runs the launches and returns the 64-bit words of the call
+ * it extends, whose arguments it takes with d_damping after d_mass.  Each refuses what the extended call refuses, with
+ * its own name in the text, SLOD_ERR_ARGUMENT before any device work.  A record and a source armed on the handle serve
+ * the damped steppers as they serve their namesakes.
+ * NEWMARK.  slod_lod_newmark_accel_damped, slod_lod_newmark_steps_damped (CG) and their _direct forms.
+ *   acceleration   M a = b^0 - A (u + damp_stiff v) - damp_mass M v - D v
+ *   step matrix    S = (1 + gamma dt damp_mass) M + (beta dt^2 + gamma dt damp_stiff) A + (gamma dt) D
+ *   step rhs       g = ((b - A w) - damp_mass (M v~)) - (D v~), each product and difference rounded on its own; M v~ and D v~
+ *                  are two fma chains in the slot order of slod_lod_apply_multi on one read of the row's column indices
+ *                  and of v~; with damp_mass = 0 the D chain runs alone.
+ * The CG forms build S in the call's workspace as two slod_lod_matrix_combine roundings: (c_M M + c_A A), then that + c_D D
+ * (1.0 times the first sum is exact, so S = fl(fl(fl(c_M M) + fl(c_A A)) + fl(c_D D))).  The _direct forms take the
+ * caller's factor of that S, Cholesky or LDL^T, and the factor of M for the acceleration.  Predictor, corrector, energies
+ * (1/2 v^T M v, 1/2 u^T A u), n_steps = 2 == 2 x 1, column independence stay as they are.  For beta = 1/4, gamma = 1/2 and no
+ * load the energy obeys  E_{k+1} - E_k = -dt vbar^T C vbar,  vbar = (v_k + v_{k+1}) / 2.
+ * COMPLEX FACTOR.  slod_lod_factor_create_zldl3 factors S_k = alpha_k A + beta_k B + gamma_k C, gamma HOST [n_members][2]
+ * like alpha and beta.  Band word: re = ((alpha_re a) + (beta_re b)) + (gamma_re c), the imaginary plane alike, every product
+ * and sum rounded on its own.  Everything else is slod_lod_factor_create_zldl: its error texts with the new name, the
+ * independence of a member's words from n_members and its position, slod_lod_factor_solve_complex, get_info and inertia,
+ * and every real consumer refuses the object.  SLOD_ERR_ARGUMENT: a NULL handle, array (d_c too), alpha, beta, gamma or
+ * out; n_members < 1 or > 65535; a coefficient (of gamma too) that is NaN or infinite.
+ * IRK.  slod_lod_irk_damping_coefficient (host only) returns gamma = z = dt lambda of the scheme, formed in long double and
+ * rounded once per part; it refuses a NULL gamma, an unknown scheme and dt <= 0, NaN or infinite, as
+ * slod_lod_irk_coefficients does.  slod_lod_irk_wave_steps_damped_direct runs on a member of
+ *   S = (1 + z damp_mass) M + (z damp_stiff + z^2) A + z D,
+ * slod_lod_factor_create_zldl3 with the pair of slod_lod_irk_coefficients(scheme, 2, ..) and gamma = z.  Re S stays
+ * symmetric positive definite because Re z > 0, so the factor exists without pivoting.
+ *   r = tau_1 b_1 + tau_2 b_2 - sigma [A (u + (z + damp_stiff) v) + damp_mass M v + D v],   the update is unchanged;
+ * D v is a fourth fma chain next to A u, A v and M v on the same loads of v.
+ * FREQUENCY RESPONSE.  slod_lod_harmonic_response_damped, with a trailing quantities (HOST [n_freq * n_rhs][5], may be NULL):
+ *   S(omega) = (1 + i omega damp_stiff) A + (i omega damp_mass - omega^2) M + i omega D,   gamma_k = (0, omega_k).
+ * It works in chunks of 64 frequencies, waited for once each.  The true residual is formed from the three matrices: six
+ * row products in one launch.  quantities[(k n_rhs + c)] = (u^H M u, u^H A u, u^H D u, Re u^H b, Im u^H b) with the roundings
+ * and the fixed summation order of the ensemble call's quantities (u^H D u is +0.0 without D); a zero load column gives
+ * five zeros.  They balance:  omega (damp_mass u^H M u + damp_stiff u^H A u + u^H D u) = Im u^H b,  the imaginary part of
+ * u^H S u = u^H b; the real part is u^H A u - omega^2 u^H M u = Re u^H b.
+ * With damp_mass = damp_stiff = 0 and a D that is only semi-definite the imaginary part of S is not definite: the
+ * existence of the factor is then the caller's risk and the growth is reported, as for omega = 0 in
+ * slod_lod_harmonic_response.
+ * Not built: ensemble forms of the four damped calls and of slod_lod_factor_create_zldl3; theta-scheme or heat calls
+ * (damping is second order only); the eigen calls (a quadratic eigenproblem); perfectly matched layers (they change A);
+ * a refresh of D after slod_update_coefficient (rebuild it with slod_lod_mass_matrix); the deal.II adapter. */
+int slod_lod_newmark_accel_damped(slod_handle *h, const double *d_stiffness, const double *d_mass,
+                                  const double *d_damping /* NULL: D = 0 */, const uint32_t *d_cols, double damp_mass,
+                                  double damp_stiff, int n_rhs, const double *d_u, size_t ld_u, const double *d_v, size_t ld_v,
+                                  const double *d_load, size_t ld_load, double *d_a, size_t ld_a, double rel_tol, int max_iterations,
+                                  int *iterations, double *rel_residual);
+int slod_lod_newmark_steps_damped(slod_handle *h, const double *d_stiffness, const double *d_mass,
+                                  const double *d_damping /* NULL: D = 0 */, const uint32_t *d_cols, double dt, double beta,
+                                  double gamma, double damp_mass, double damp_stiff, int n_steps, int n_rhs, double *d_u, size_t ld_u,
+                                  double *d_v, size_t ld_v, double *d_a, size_t ld_a, const double *d_load, size_t ld_load,
+                                  size_t load_step_stride, double rel_tol, int max_iterations, int *iterations, double *rel_residual,
+                                  double *kinetic, double *potential);
+int slod_lod_newmark_accel_damped_direct(slod_handle *h, slod_lod_factor *f_M, const double *d_stiffness, const double *d_mass,
+                                         const double *d_damping /* NULL: D = 0 */, const uint32_t *d_cols, double damp_mass,
+                                         double damp_stiff, int n_rhs, const double *d_u, size_t ld_u, const double *d_v, size_t ld_v,
+                                         const double *d_load, size_t ld_load, double *d_a, size_t ld_a);
+int slod_lod_newmark_steps_damped_direct(slod_handle *h, slod_lod_factor *f_S, const double *d_stiffness, const double *d_mass,
+                                         const double *d_damping /* NULL: D = 0 */, const uint32_t *d_cols, double dt, double beta,
+                                         double gamma, double damp_mass, double damp_stiff, int n_steps, int n_rhs, double *d_u,
+                                         size_t ld_u, double *d_v, size_t ld_v, double *d_a, size_t ld_a, const double *d_load,
+                                         size_t ld_load, size_t load_step_stride, double *kinetic, double *potential);
+int slod_lod_factor_create_zldl3(slod_handle *h, const double *d_a, const double *d_b, const double *d_c, const uint32_t *d_cols,
+                                 const double *alpha /* HOST [n_members][2] */, const double *beta, const double *gamma,
+                                 int n_members, int32_t *bad_pivot /* HOST [n_members], may be NULL */, slod_lod_factor **out);
+int slod_lod_irk_damping_coefficient(int scheme, double dt, double gamma[2]);
+int slod_lod_irk_wave_steps_damped_direct(slod_handle *h, slod_lod_factor *f_S, int member, int scheme, const double *d_stiffness,
+                                          const double *d_mass, const double *d_damping /* NULL: D = 0 */, const uint32_t *d_cols,
+                                          double dt, double damp_mass, double damp_stiff, int n_steps, int n_rhs, double *d_u,
+                                          size_t ld_u, double *d_v, size_t ld_v, const double *d_load, size_t ld_load,
+                                          size_t load_stage_stride, double *kinetic, double *potential);
+int slod_lod_harmonic_response_damped(slod_handle *h, const double *d_stiffness, const double *d_mass,
+                                      const double *d_damping /* NULL: D = 0 */, const uint32_t *d_cols, double damp_mass,
+                                      double damp_stiff, const double *omega /* HOST [n_freq] */, int n_freq, const double *d_load_re,
+                                      const double *d_load_im, size_t ld_load, int n_rhs, double *d_u_re, double *d_u_im, size_t ld_u,
+                                      double *rel_residual, double *growth, double *quantities /* HOST [n_freq*n_rhs][5], may be NULL */);
+
 /* ---- refresh after a local coefficient change ----------------------------------------------
  * Every entry point above takes the coefficient as fixed for the life of a basis (the reference does too: one
  * compute_basis_function_candidates per run, LOD.cc:1425-1433).  When it changes in a small part of the domain -- a
