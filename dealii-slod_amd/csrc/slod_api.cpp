@@ -723,6 +723,9 @@ int slod_plan_create(slod_handle *h, const uint32_t *gids, size_t n, const uint6
   // estimated cost (canonical solve flops, rim patches are cheaper) and dealt in a snake over rows of
   // n_cu give every CU the same mix.
   p->n_chunks = (n + p->chunk - 1) / p->chunk;
+  // wave priorities by row of that order (k_solve_tw): only where one launch holds the whole plan and it is
+  // resident at once -- a plan in several chunks counts as larger than any resident set
+  slod_choose_stagger(s, tuning, p->n_chunks == 1 ? n : (size_t)-1, n_cu, &p->choice);
   p->ev.assign(4 * p->n_chunks, nullptr);
   for (auto &ev : p->ev)
     ok = ok && hipEventCreate(&ev) == hipSuccess;

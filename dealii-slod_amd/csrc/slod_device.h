@@ -26,6 +26,11 @@ struct SlodPatchDesc
 
 __host__ __device__ inline size_t slod_mt_stride(int nc_max) { return (size_t)nc_max * nc_max + 1; }
 
+// Priority class of a workgroup of k_solve_tw (SlodKernelArgs::stagger): the blocks b, b + row, b + 2 row, ... of a
+// launch that is resident all at once share a CU, and the balanced launch order deals the patches by falling cost
+// over rows of `row` blocks -- the row of a block is its rank among its CU's four and its rank by cost.
+__host__ __device__ inline int slod_stagger_class(unsigned block, int row) { return (int)((block / (unsigned)(row > 0 ? row : 1)) & 3u); }
+
 enum : int32_t
 {
   SLOD_F_LOD        = 1 << 4,
@@ -83,6 +88,9 @@ struct SlodKernelArgs
                     // is there, 0.0: the patch fell back); stride slod_mt_stride, not the stamps of ms
   int32_t m_tw;     // 1: k_solve_tw builds M in its sweeps where the patch allows it
   int32_t bwd_ksplit; // 1: k_solve_tw splits the backward sweep's GEMM by K half between the chain's two waves
+  int32_t stagger;  // k_solve_tw: wave priorities by class of the workgroup (0: Gauss-Jordan waves 3 up to the meeting line,
+                    // everything else 0; 1..4: see the knob list of slod_dispatch.cpp)
+  int32_t stagger_row; // blocks per row of the balanced launch order: the class is slod_stagger_class(blockIdx.x, stagger_row)
   int32_t svd_regs; // 1: the SVD fallback of the selection stage keeps a Jacobi pair's rows and the pivoted QR's column
                     // order in registers (patches of at most 32 columns; 0: the loops that go through LDS)
   int32_t nb_buf;   // rows of the selection stage's boundary-trace buffer
@@ -104,6 +112,8 @@ enum SlodSolverKind : int32_t
   SLOD_K_ND   = 5  // slod_solve_nd.hip
 };
 
+#define SLOD_STAGGER_MODES 5   // 0 .. 4
+#define SLOD_STAGGER_DEFAULT 4 // the mode with the lowest median step time at C2
 // tuning knobs (environment, read once per plan) and the resulting kernel choice: slod_dispatch.cpp
 struct SlodTuning
 {
@@ -113,6 +123,8 @@ struct SlodTuning
   int balance = 1;       // launch order balanced over the CUs (SLOD_BALANCE=0: the caller's order)
   int bwd_ksplit = 1;    // k_solve_tw backward sweep: K split over the chain's two waves (SLOD_BWD_KSPLIT=0: column split)
   int svd_regs = 1;      // selection stage, SVD fallback: Jacobi pairs and the pivot order in registers (SLOD_SVD_REGS=0: LDS loops)
+  int stagger = SLOD_STAGGER_DEFAULT; // k_solve_tw: wave priorities by workgroup class (SLOD_STAGGER=0..4; 0: none)
+  int stagger_row = 0;   // blocks per class row (SLOD_STAGGER_ROW; 0: the device's CU count, the row of the balanced order)
   int debug = 0;
 };
 struct SlodSolveChoice
@@ -120,12 +132,15 @@ struct SlodSolveChoice
   int    kind = 0;
   size_t lds  = 0;
   int    fuse_select = 0, fuse_assemble = 0, m_tw = 0, bwd_ksplit = 0, svd_regs = 0, twisted = 0, debug = 0;
+  int    stagger = 0, stagger_row = 1; // set by slod_choose_stagger once the plan's launch size is known
   int    v_line_pad = 0; // rows = columns of a V line as the kernel sees it
   size_t v_line_elems = 0; // doubles per stored V line (k_solve_tw: the 8 x 8 lane tiles, both triangles)
   int    nv = 0;            // k_solve_nd: cell size
   size_t v_patch_elems = 0; // k_solve_nd: doubles of scratch per patch (replaces L_max * v_line_elems)
 };
 SlodTuning slod_read_tuning();
+// the stagger mode of a plan whose launches hold at most `per_launch` patches on a device of n_cu CUs
+void       slod_choose_stagger(int S, const SlodTuning &t, size_t per_launch, int n_cu, SlodSolveChoice *c);
 bool       slod_choose_solver(int S, int n_sub, int m_max, int L_max, int nc_max, int nb_buf, int nf_max, size_t n_patches,
                               const SlodTuning &t, SlodSolveChoice *out);
 

@@ -19,6 +19,18 @@
 //   SLOD_SVD_REGS=0|1         SVD fallback of the selection stage (scalar patches of at most 32 columns after the QR): a Jacobi
 //                             pair's rows and the pivoted QR's column order live in registers (default) or, 0, the
 //                             loops that read them from LDS (what every other patch shape runs; same bits)
+//   SLOD_STAGGER=0..4         tw, plans that are resident all at once (scalar problems): wave priorities (s_setprio) by the
+//                             class k = (block / row) & 3 of the workgroup, the row of the balanced launch order, so that
+//                             the workgroups that share a CU leave the issue-bound forward sweep one after the other.
+//                             GJ = Gauss-Jordan waves, H = helpers, "after" = once the meeting line is factorised, before its row
+//                             tiles (where the parent set priority 0).
+//                               0  GJ 3, H 0, after 0, whatever the class
+//                               1  classes 0, 1: GJ 3, H 2, after 2; classes 2, 3: GJ 1, H 0, after 0
+//                               2  every wave 3 - k for the whole kernel
+//                               3  GJ 3 - k, H max(2 - k, 0), after 0
+//                               4  mode 1 with the classes swapped: classes 2, 3 (the rim patches, whose selection stage takes
+//                                  the SVD fallback most often and ends last) GJ 3, H 2, after 2; classes 0, 1: GJ 1, H 0, after 0
+//   SLOD_STAGGER_ROW=n        blocks per class row (default: the device's CU count, the row of the balanced order)
 //   SLOD_TWISTED=0|1 (coop only) SLOD_DEBUG=1 print the choice
 //   SLOD_BALANCE=0            launch the patches in the caller's order (default: balanced over the CUs)
 SlodTuning slod_read_tuning()
@@ -37,6 +49,10 @@ SlodTuning slod_read_tuning()
     t.bwd_ksplit = atoi(e) ? 1 : 0;
   if (const char *e = getenv("SLOD_SVD_REGS"))
     t.svd_regs = atoi(e) ? 1 : 0;
+  if (const char *e = getenv("SLOD_STAGGER"))
+    t.stagger = std::min(std::max(atoi(e), 0), SLOD_STAGGER_MODES - 1);
+  if (const char *e = getenv("SLOD_STAGGER_ROW"))
+    t.stagger_row = std::max(atoi(e), 0);
   if (const char *e = getenv("SLOD_TWISTED"))
     t.twisted = atoi(e) ? 1 : 0;
   if (const char *e = getenv("SLOD_BALANCE"))
@@ -155,9 +171,27 @@ bool slod_choose_solver(int S, int n_sub, int m_max, int L_max, int nc_max, int 
   return true;
 }
 
+// Wave priorities by workgroup class (k_solve_tw) need the classes to be co-residents: a plan whose launches
+// hold more patches than one resident set (occupancy x CUs; several workspace chunks likewise) starts its
+// workgroups one after the other and is de-phased by itself, and its rows do not share CUs.  Vector plans
+// stay at 0.  The row is kept whatever the mode: the launch log prints both.
+void slod_choose_stagger(int S, const SlodTuning &t, size_t per_launch, int n_cu, SlodSolveChoice *c)
+{
+  // workgroups per CU: by LDS, and by registers what the launch bounds of k_solve_tw<T,S> ask for (lane_tile_min_waves:
+  // 128 VGPRs and four waves per SIMD up to T = 5, two up to T = 7, one beyond; a workgroup puts one wave on each SIMD)
+  const int    wt        = c->v_line_pad / 8;
+  const size_t by_regs   = wt <= 5 ? 4 : (wt <= 7 ? 2 : 1);
+  const size_t occupancy = std::min<size_t>(by_regs, (160 * 1024) / std::max<size_t>(c->lds, 1));
+  c->stagger_row = t.stagger_row > 0 ? t.stagger_row : std::max(n_cu, 1);
+  // (the four classes are the four co-residents of a CU: a kernel that fits fewer workgroups per CU runs mode 0)
+  c->stagger = (c->kind == SLOD_K_TW && S == 1 && occupancy == 4 && per_launch <= occupancy * (size_t)std::max(n_cu, 1)) ? t.stagger : 0;
+}
+
 hipError_t slod_launch_solve(int S, const SlodSolveChoice &c, SlodKernelArgs &a, int n_patches, hipStream_t st)
 {
   a.m_tw          = c.m_tw;
+  a.stagger       = c.stagger;
+  a.stagger_row   = c.stagger_row;
   a.bwd_ksplit    = c.bwd_ksplit;
   a.svd_regs      = c.svd_regs;
   a.fuse_select   = c.fuse_select;

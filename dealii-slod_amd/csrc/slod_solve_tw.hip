@@ -32,6 +32,44 @@ namespace
     int                 lane = tid & 63;
     const int           chain = wave & 1;
     const bool          is_gj = wave < 2;
+    // Wave priority by class of the workgroup (A.stagger, the modes are listed in slod_dispatch.cpp): set once before
+    // the forward loops and once after the meeting line's factorisation, before its row tiles (mid_phase).  s_setprio
+    // takes an immediate and ignores EXEC: mode, class and role are wave-uniform, so the switch is a scalar branch.
+    auto set_prio = [&](bool after) __attribute__((always_inline)) {
+      const int k = slod_stagger_class(blockIdx.x, A.stagger_row);
+      int       pr;
+      switch (A.stagger)
+        {
+          case 1:
+            pr = k < 2 ? (after || !is_gj ? 2 : 3) : (after || !is_gj ? 0 : 1);
+            break;
+          case 2:
+            pr = 3 - k;
+            break;
+          case 3:
+            pr = after ? 0 : is_gj ? 3 - k : max(2 - k, 0);
+            break;
+          case 4:
+            pr = k >= 2 ? (after || !is_gj ? 2 : 3) : (after || !is_gj ? 0 : 1);
+            break;
+          default:
+            pr = (is_gj && !after) ? 3 : 0;
+        }
+      switch (__builtin_amdgcn_readfirstlane(pr))
+        {
+          case 3:
+            __builtin_amdgcn_s_setprio(3);
+            break;
+          case 2:
+            __builtin_amdgcn_s_setprio(2);
+            break;
+          case 1:
+            __builtin_amdgcn_s_setprio(1);
+            break;
+          default:
+            __builtin_amdgcn_s_setprio(0);
+        }
+    };
     const int           m = d.m, L = d.L, nc = d.n_c, n = A.n_sub;
     const int           mm = A.m_max, ncs = (A.nc_max + 1) & ~1, ncg = A.nc_max;
     const bool          tr  = (d.flags & SLOD_F_TRANSPOSED) != 0;
@@ -325,7 +363,7 @@ namespace
     // ------------------------------ forward elimination ---------------------------
     if (is_gj)
       {
-        __builtin_amdgcn_s_setprio(3);
+        set_prio(false);
         int    gy = lane >> 3, gx = lane & 7;
         double a[T][T];
         // neighbour lane in the same lane-grid row through DPP (row_shr:1 / row_shl:1, no LDS trip):
@@ -625,13 +663,14 @@ namespace
           }
         if (bad != 0 && lane == 0 && !SLOD_DG(A, -1))
           atomicOr(A.status, 1);
-        __builtin_amdgcn_s_setprio(0);
+        set_prio(true);
         __syncthreads(); // M2: V_mid is in the workspace
         mid_phase();
       }
     else
       {
         // ===== helper wave of the chain: one wave, so its own phases need no barrier =====
+        set_prio(false);
         // R = (with_F ? F_line : 0) - Bprev^T Z(prev line), Z from the workspace
         // Each lane owns column r = lane&31 (+32 ...) and one half of the rows; it walks down its
         // rows with a sliding window of Z(prev)[p][r], p = i-W..i+W: one coalesced workspace load
@@ -1006,6 +1045,7 @@ namespace
                 mfull[idx] = v;
               }
           }
+        set_prio(true);
         __syncthreads(); // M2: V_mid is in the workspace (and mfull holds the chain terms)
         mid_phase();
       }
@@ -1486,8 +1526,9 @@ static hipError_t launch_tw_TS(const SlodKernelArgs &a, int n_patches, size_t ld
     {
       int nb = 0;
       (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, lds);
-      fprintf(stderr, "[slod] k_solve_tw<%d,%d>: %d patches, lds %zu B, occupancy %d blocks/CU, backward K split %d, M in the sweeps %d\n",
-              T, S, n_patches, lds, nb, a.bwd_ksplit, a.m_tw);
+      fprintf(stderr, "[slod] k_solve_tw<%d,%d>: %d patches, lds %zu B, occupancy %d blocks/CU, stagger %d row %d, backward K split %d, "
+                      "M in the sweeps %d\n",
+              T, S, n_patches, lds, nb, a.stagger, a.stagger_row, a.bwd_ksplit, a.m_tw);
     }
   hipLaunchKernelGGL((k_solve_tw<T, S>), dim3(n_patches), dim3(256), lds, st, a);
   return hipGetLastError();
